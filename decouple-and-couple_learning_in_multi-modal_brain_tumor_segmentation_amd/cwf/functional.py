@@ -7,6 +7,7 @@ gradient (recomputed) and undone analytically in the data gradient (full Instanc
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Optional
 
@@ -195,6 +196,7 @@ class _ConvFn(torch.autograd.Function):
             # InstanceNorm-backward apply pass (which matters for the last layers of backward: nothing is left to hide behind)
             ctx.x16 = K.to_bf16_side(x, in_scale, in_shift, slope)
         ctx.up16 = getattr(x, "_cwf_want16", False)     # x's producer is such a layer: hand its gradient on with a bf16 image ("only": nothing else)
+        ctx.single = _SINGLE_CONSUMER                    # (backward runs after the declaring forward has returned: it reads this, not the global)
         # the LAST layers of backward: nothing is left to hide their weight gradient behind, so it must not wait for this layer's own data
         # gradient + apply pass (which would deliver xa16): it is issued first and converts x itself on the side stream
         ctx.wgrad_first = bool(getattr(x, "_cwf_wgrad_first", False))
@@ -300,7 +302,7 @@ class _ConvFn(torch.autograd.Function):
                     # the apply pass has x, its statistics and dx in registers: it also writes this layer's weight-gradient operand
                     # bf16(act(IN(x))) and the bf16 image of dx for the layer that produced x -- and ONLY that image where the layer
                     # that produced x reads nothing else (ctx.up16 == "only", a single-consumer graph)
-                    only16 = want_dx and ctx.up16 == "only" and _SINGLE_CONSUMER and to_sink
+                    only16 = want_dx and ctx.up16 == "only" and ctx.single and to_sink
                     dx, dx16, xa16 = K.in_bwd_apply16(dxa, x, in_scale, in_shift, ctx.slope, sums, dx_add=dcarry,
                                                       want_dx16=want_dx, want_xa16=want_xa, need_f32=not only16)
                     if dx16 is not None:
@@ -396,18 +398,26 @@ def fused_conv3(x, convs, spec):
     return y, (sc, sh)
 
 
-# A model may declare that every tensor it hands to conv() / norm_act_add() has ONE gradient consumer (ClsWiseFormer does, in its
-# forward).  Only then may a backward pass leave the fp32 gradient of such a tensor unwritten and hand on its bf16 image alone
-# (autograd would otherwise add the unwritten buffer to another consumer's gradient).
+# A model may declare that every tensor it hands to conv() / norm_act_add() has ONE gradient consumer (ClsWiseFormer does, for the
+# duration of its forward: single_consumer_graph).  Only then may a backward pass leave the fp32 gradient of such a tensor unwritten
+# and hand on its bf16 image alone (autograd would otherwise add the unwritten buffer to another consumer's gradient).  conv() marks
+# an output "only" while the declaration holds, and each Function records it at forward time for its backward.
 _SINGLE_CONSUMER = False
 import os as _os
 _DY16_ON_MAIN = _os.environ.get("CWF_DY16_ON_MAIN", "0") != "0"     # (measured 0.3 % slower than leaving the conversion to the side stream)
 _FIRST_X16_FWD = _os.environ.get("CWF_FIRST_X16_FWD", "1") != "0"     # the layer behind the stem: its xa16 is made in the forward pass (side stream)
 
 
-def set_single_consumer_graph(flag: bool):
+@contextlib.contextmanager
+def single_consumer_graph():
+    """Declare, for the forward pass run inside, that every tensor handed to conv() / norm_act_add() has ONE gradient consumer.
+    The previous state is restored on exit: graphs built outside never take the bf16-only gradient hand-off."""
     global _SINGLE_CONSUMER
-    _SINGLE_CONSUMER = bool(flag)
+    prev, _SINGLE_CONSUMER = _SINGLE_CONSUMER, True
+    try:
+        yield
+    finally:
+        _SINGLE_CONSUMER = prev
 
 
 def _dy_f32(K, dy):
@@ -467,7 +477,7 @@ def conv(x, w, b, spec, in_norm=None, slope=1.0, residual=None, out_scale=None, 
         # them ("only") if its data gradient reads bf16 images too
         okd = getattr(backend(), "bf16_dgrad_ok", None)
         # (with a residual the fp32 gradient is needed as well: it is the residual's gradient)
-        y._cwf_want16 = "only" if (residual is None and okd is not None and
+        y._cwf_want16 = "only" if (_SINGLE_CONSUMER and residual is None and okd is not None and
                                    okd(spec.op, spec.cin, spec.cout, y.shape[1] * y.shape[2] * y.shape[3])) else True
     st = (s1, s2) if want_stats else None
     return (y, st, xc) if carry else (y, st)
@@ -574,6 +584,7 @@ class _NormActAddFn(torch.autograd.Function):
         ctx.has_res = residual is not None
         ctx.link = link
         ctx.up16 = getattr(x, "_cwf_want16", False)
+        ctx.single = _SINGLE_CONSUMER
         ctx.save_for_backward(x, scale, shift)
         if want16:
             y, y16 = backend().norm_act_add(x, scale, shift, slope, residual, want16=True)
@@ -589,7 +600,7 @@ class _NormActAddFn(torch.autograd.Function):
         if link is not None and link.sums is not None and not link.shared:
             sums, link.sums = link.sums, None        # from the consuming conv's data-gradient epilogue (this backward pass)
             if ctx.up16 and "dx" in getattr(K, "APPLY_EMITS", ()):
-                only16 = ctx.up16 == "only" and _SINGLE_CONSUMER and active_sink() is not None
+                only16 = ctx.up16 == "only" and ctx.single and active_sink() is not None
                 dx, dx16, _ = K.in_bwd_apply16(dy, x, scale, shift, ctx.slope, sums, want_dx16=True, need_f32=not only16)
                 dx._cwf16 = dx16
                 if only16:

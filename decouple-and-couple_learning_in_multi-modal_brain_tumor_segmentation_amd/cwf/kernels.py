@@ -67,6 +67,11 @@ _WGRAD_PRECISION = None      # None = follow _PRECISION; "bf16" = single-bf16 pr
 _DGRAD_PRECISION = None      # the same for the data-gradient convolutions
 
 
+# Debug switch (read at every call): in_bwd_apply16(..., need_f32=False) fills the fp32 carrier it leaves unwritten with NaN, so a
+# consumer that reads it after all -- a graph whose single-consumer declaration is false -- shows up as a non-finite gradient.
+POISON_UNWRITTEN_CARRIERS = False
+
+
 def set_precision(mode: str, wgrad: str = None, dgrad: str = None):
     """`wgrad` / `dgrad` optionally select the operand form of the weight-gradient / data-gradient kernels alone ("bf16": one
     bf16 product, fp32 accumulate -- the usual mixed-precision choice for gradients), leaving the forward in `mode`."""
@@ -352,6 +357,8 @@ class HipBackend:
         x, x_ldc = cl(x)
         n, d, h, w, c = x.shape
         dx = torch.empty((n, d, h, w, c), dtype=_f32, device=x.device)
+        if not need_f32 and POISON_UNWRITTEN_CARRIERS:
+            dx.fill_(float("nan"))
         dx16 = torch.empty((n, d, h, w, c), dtype=torch.bfloat16, device=x.device) if want_dx16 else None
         xa16 = torch.empty((n, d, h, w, c), dtype=torch.bfloat16, device=x.device) if want_xa16 else None
         assert need_f32 or dx16 is not None
@@ -494,7 +501,10 @@ class HipBackend:
     def wgrad_to(self, key, op, x, in_scale, in_shift, slope, dy, cout, inv_map, dw_dst, db_dst, prec=None, x16=None, dy16=None, dy_scale=None,
                  allow_async=False):
         """x16 / dy16: bf16 operand images (see bf16_operands_ok).  Given one of them for an eligible layer, the other is made by a
-        conversion pass in front of the launch (on the stream the launch runs on); x / dy are then not read."""
+        conversion pass in front of the launch (on the stream the launch runs on); x / dy are then not read.
+        dy_scale: [N, cout] fp32, dy is taken as dy * dy_scale[n, c] (see dy_scale_ok); refused where no kernel of this call applies it."""
+        if dy_scale is not None:
+            self._check_dy_scale(op, x, dy, cout, prec, dy_scale)
         if self.wgrad_async and allow_async and self.wgrad_defer:
             self._wg_held.append((key, op, x, in_scale, in_shift, slope, dy, cout, inv_map, dw_dst, db_dst, prec, x16, dy16, dy_scale))
             return
@@ -514,6 +524,18 @@ class HipBackend:
             # step -- it should carry a handful of layers, not a whole phase.  (The Trainer switches this off in hipGraph mode:
             # the descriptor tables are keyed by their rows and must already exist when the capture runs.)
             self.wgrad_flush(x.device)
+
+    def _check_dy_scale(self, op, x, dy, cout, prec, dy_scale):
+        # only the fp32-tensor kernel of dy_scale_ok's layers scales dy while staging it: the bf16-image kernels and the fp32 mode would
+        # drop the scale (or run in another precision), so such a call is an error, never a different computation
+        n, do, ho, wo = dy.shape[0], dy.shape[1], dy.shape[2], dy.shape[3]
+        mode = prec or _WGRAD_PRECISION or _PRECISION
+        if mode == "fp32" or not self.dy_scale_ok(op, x.shape[-1], cout, do * ho * wo):
+            raise _lib.CwfError("wgrad_to(dy_scale=) is not implemented for this layer / mode (op %d, %d -> %d channels, %d voxels, %s)"
+                                % (op, x.shape[-1], cout, do * ho * wo, mode))
+        if (tuple(dy_scale.shape) != (n, cout) or dy_scale.dtype != _f32 or not dy_scale.is_contiguous() or dy_scale.device != dy.device
+                or dy_scale.data_ptr() % 16):
+            raise _lib.CwfError("dy_scale must be a contiguous, 16-byte aligned float32 [%d, %d] tensor on %s" % (n, cout, dy.device))
 
     def _wgrad_to_impl(self, key, op, x, in_scale, in_shift, slope, dy, cout, inv_map, dw_dst, db_dst, prec, x16=None, dy16=None, dy_scale=None):
         x, x_ldc = cl(x)

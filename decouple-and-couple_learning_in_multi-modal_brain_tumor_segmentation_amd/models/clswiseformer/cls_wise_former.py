@@ -209,12 +209,13 @@ class ClsWiseFormer(nn.Module):
         self.aux = {}
         self._cut_state = {}
         # every conv output / block tail of this model has ONE gradient consumer: a backward pass may hand on a bf16 gradient image alone
-        CF.set_single_consumer_graph(True)
-        backend().begin_step(x.device)
-        self._packer.refresh()
-        xc = x.to(torch.float32).permute(0, 2, 3, 4, 1).contiguous()  # NDHWC
-        x1, x2, x3, xb, sup, edge, mid_sup, mid_edge = self.encode(xc, missing_modal)
-        prob = self.decoder(x1, x2, x3, None, xb, aux=self.aux if self.collect_aux else None)
+        # (declared for this forward pass only; other graphs in the process keep their fp32 gradients)
+        with CF.single_consumer_graph():
+            backend().begin_step(x.device)
+            self._packer.refresh()
+            xc = x.to(torch.float32).permute(0, 2, 3, 4, 1).contiguous()  # NDHWC
+            x1, x2, x3, xb, sup, edge, mid_sup, mid_edge = self.encode(xc, missing_modal)
+            prob = self.decoder(x1, x2, x3, None, xb, aux=self.aux if self.collect_aux else None)
         return prob, sup, edge, mid_sup, mid_edge
 
 

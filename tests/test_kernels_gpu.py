@@ -355,6 +355,97 @@ def test_bf16_operand_images_and_dma_weight_gradient(hip, size, n):
     close(db_b, gb_ref, rtol=PREC_TOL["bf16"], what="dma bgrad vs oracle")
 
 
+def _dy_scale(n, seed):
+    """[n, 16] per-(sample, channel) scale: dropped channels (0), the stem's keep scale 1.25 and general values; channel 7 is 0 in every
+    sample, and the samples differ (a wrong sample index must show)."""
+    base = torch.tensor([1.25, 0.0, -0.7, 3.0, 1.25, 0.5, 0.0, 1.25, -2.0, 1.25, 0.0, 0.25, 1.25, 1.5, 1.25, -0.3])
+    s = torch.stack([base.roll(3 * i + seed) for i in range(n)])
+    s[:, 7] = 0.0
+    assert n == 1 or not torch.equal(s[0], s[1])
+    return s.contiguous()
+
+
+@pytest.mark.parametrize("cin,prologue,mode", [(4, False, "bf16"), (4, False, "bf16x3"), (16, True, "bf16x3")])
+@pytest.mark.parametrize("size,n", [((32, 32, 32), 2), ((34, 38, 50), 2), ((64, 64, 64), 1)])
+def test_weight_gradient_folds_a_per_sample_channel_scale(hip, cin, prologue, mode, size, n):
+    """wgrad_to(..., dy_scale=s) (cwf_wgrad_mfma_bf16_dys: the stem's dropout3d folded into its weight gradient under a gradient sink)
+    == wgrad_to on channel_scale(dy, s) == the oracle on dy * s.  (32, 32, 32) x 2 is exactly the 32768-voxel threshold, (34, 38, 50)
+    has ragged 4 x 4 x 16 tiles in every dimension.  Single-bf16 products: bit equal to the unfolded call (same kernel, grid and operand
+    values).  Split-bf16 (bf16x3): the compiler contracts the fold's multiply into the lo-part subtraction, lo = bf16(fma(dy, s, -hi))
+    instead of bf16(round(dy * s) - hi) -- the lo operands may differ in their last bits, so summation-order tolerance there."""
+    from cwf import functional as CF, kernels
+    d, h, w_ = size
+    x = rnd(n, d, h, w_, cin, seed=31)
+    g = rnd(n, d, h, w_, 16, seed=32)
+    sc = rnd(n, cin, seed=33).abs() + 0.5 if prologue else None
+    sh = rnd(n, cin, seed=34) if prologue else None
+    slope = 0.01 if prologue else 1.0
+    s = _dy_scale(n, seed=cin)
+    xd, gd, sd = x.to(DEV), g.to(DEV), s.to(DEV)
+    scd, shd = (sc.to(DEV), sh.to(DEV)) if prologue else (None, None)
+    spec = CF.ConvSpec(pk.CONV3_S1, cin, 16).to(torch.device(DEV))
+    wn = 16 * cin * 27
+    # (1) channel_scale is one multiply per element
+    gs_ref = gd * sd[:, None, None, None, :]
+    gs = hip.channel_scale(gd, sd)
+    assert torch.equal(gs, gs_ref)
+    kernels.set_precision("bf16x3", wgrad=mode, dgrad="bf16")
+    try:
+        assert hip.dy_scale_ok(pk.CONV3_S1, cin, 16, d * h * w_)
+        if cin == 16:                                   # the bf16-image kernel would drop the scale: the gate says no there
+            kernels.set_precision("bf16x3", wgrad="bf16", dgrad="bf16")
+            assert not hip.dy_scale_ok(pk.CONV3_S1, cin, 16, d * h * w_)
+            kernels.set_precision("bf16x3", wgrad=mode, dgrad="bf16")
+        dw_f = torch.zeros(wn, device=DEV); db_f = torch.zeros(16, device=DEV)
+        dw_u = torch.zeros(wn, device=DEV); db_u = torch.zeros(16, device=DEV)
+        hip.wgrad_to("dys_f", pk.CONV3_S1, xd, scd, shd, slope, gd, 16, spec.inv_map, dw_f, db_f, dy_scale=sd)
+        hip.wgrad_flush(torch.device(DEV))
+        hip.wgrad_to("dys_u", pk.CONV3_S1, xd, scd, shd, slope, gs, 16, spec.inv_map, dw_u, db_u)
+        hip.wgrad_flush(torch.device(DEV))
+    finally:
+        kernels.set_precision("fp32")
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(dw_f).all()) and float(dw_f.abs().max()) > 0
+    # (2) folded == unfolded
+    if mode == "bf16":
+        assert torch.equal(dw_f, dw_u) and torch.equal(db_f, db_u)
+    else:
+        close(dw_f, dw_u.cpu(), rtol=2e-5, what="folded vs unfolded wgrad")
+        close(db_f, db_u.cpu(), rtol=2e-5, what="folded vs unfolded bgrad")
+    # (3) both against the oracle on the torch-scaled gradient
+    gw_ref, gb_ref = E.wgrad(pk.CONV3_S1, x, sc, sh, slope, g * s[:, None, None, None, :], 16, None, True, wn, w_ref_shape=(16, cin, 3, 3, 3))
+    for dw, db, what in ((dw_f, db_f, "folded"), (dw_u, db_u, "unfolded")):
+        close(dw, gw_ref, rtol=PREC_TOL[mode], what=what + " wgrad vs oracle")
+        close(db, gb_ref, rtol=PREC_TOL[mode], what=what + " bgrad vs oracle")
+    # (4) a channel dropped in every sample has exactly zero weight / bias gradient
+    assert float(dw_f.view(16, -1)[7].abs().max()) == 0.0 and float(db_f[7]) == 0.0
+
+
+@pytest.mark.parametrize("case", ["below_threshold", "fp32", "bf16_images"])
+def test_weight_gradient_refuses_a_scale_it_cannot_fold(hip, case):
+    """Where dy_scale_ok says no -- fewer than 32768 output voxels, the fp32 mode, a 16 -> 16 layer whose weight gradient reads bf16
+    operand images -- wgrad_to(..., dy_scale=) raises instead of dropping the scale or running another precision's kernel."""
+    from cwf import _lib, functional as CF, kernels
+    cin, size, prec = {"below_threshold": (4, (31, 32, 33), ("bf16x3", "bf16")), "fp32": (4, (32, 32, 32), ("fp32", None)),
+                       "bf16_images": (16, (32, 32, 32), ("bf16x3", "bf16"))}[case]
+    n = 2
+    d, h, w_ = size
+    xd, gd = rnd(n, d, h, w_, cin, seed=41).to(DEV), rnd(n, d, h, w_, 16, seed=42).to(DEV)
+    sd = _dy_scale(n, seed=0).to(DEV)
+    spec = CF.ConvSpec(pk.CONV3_S1, cin, 16).to(torch.device(DEV))
+    dw, db = torch.zeros(16 * cin * 27, device=DEV), torch.zeros(16, device=DEV)
+    kernels.set_precision(prec[0], wgrad=prec[1], dgrad=prec[1])
+    try:
+        assert not hip.dy_scale_ok(pk.CONV3_S1, cin, 16, d * h * w_)
+        pending = len(hip._wg_pending)
+        with pytest.raises(_lib.CwfError):
+            hip.wgrad_to("dys_refused", pk.CONV3_S1, xd, None, None, 1.0, gd, 16, spec.inv_map, dw, db, dy_scale=sd)
+        assert len(hip._wg_pending) == pending          # nothing was queued for the reduce
+    finally:
+        kernels.set_precision("fp32")
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
 @pytest.mark.parametrize("cin,cout,size,n", [
     (32, 32, (16, 16, 32), 2),       # 64 tiles, two samples: 32 workgroups x one round

@@ -1,6 +1,7 @@
 """GPU: the whole HIP model + losses + backward against the golden fixtures generated from the imported reference
 (tests/golden/model_{64,128}.npz) and against the CPU oracle run on this box.  Target (BASELINE.json): logits /
 probabilities within 1e-3 relative of the fp32 CPU reference on identical inputs."""
+import functools
 import os
 
 import numpy as np
@@ -634,3 +635,170 @@ def test_grouped_head_maps_materialise_like_eval_and_ungrouped(hip, monkeypatch)
     (o2[3]["01"][:, 1].mean() + o2[4]["04"].sum() * 1e-6).backward()        # indexing / tensor methods materialise
     gl = m2.mid_supervise_label.down_label_1.weight.grad            # (outputs[3] = the mid-level label heads)
     assert gl is not None and bool(torch.isfinite(gl).all()) and float(gl.abs().sum()) > 0
+
+
+# The stem's dropout3d, teacher-forced: a pre-scaled [2, 16] keep mask (p = 0.2), different per sample; channel 3 is dropped in both.
+_STEM_MASK = torch.full((2, 16), 1.25)
+_STEM_MASK[0, [3, 6, 11]] = 0.0
+_STEM_MASK[1, [3, 9, 14]] = 0.0
+_STEM_DROPPED = 3
+
+
+@functools.lru_cache(maxsize=None)
+def _stem_dropout_oracle():
+    """The restated model on the CPU with the stem mask and its own top-k selections forced: float64 gradients (the truth), the float32
+    run's distance from them per parameter (its noise floor, as oracle/make_golden.py records it) and the float64 stem weight gradient
+    with the samples' masks swapped and with no mask (what a mask mix-up would compute).  Computed once per module."""
+    state = syn.det_state_dict(rm.param_shapes())
+    x, target, edge = syn.synthetic_batch([0, 1], (64, 64, 64))
+    with torch.no_grad():
+        _, aux = rm.forward(state, x, stem_keep=_STEM_MASK, return_aux=True)
+    forced = {k: v for k, v in aux.items() if v.dtype == torch.int64}
+
+    def grads(dt, keep):
+        p = {k: v.to(dt).clone().requires_grad_(not k.endswith(".pe")) for k, v in state.items()}
+        o = rm.forward(p, x.to(dt), stem_keep=None if keep is None else keep.to(dt), forced_index=forced)
+        loss, _ = rm.total_loss(o, target, edge)
+        loss.backward()
+        return {k: v.grad.double() for k, v in p.items() if v.grad is not None}
+
+    g64 = grads(torch.float64, _STEM_MASK)
+    g32 = grads(torch.float32, _STEM_MASK)
+    noise = {n: float((g32[n] - g64[n]).norm() / (g64[n].norm() + 1e-30)) for n in g64}
+    sw = "Unet_list.InitConv.conv.weight"
+    alt = {"swapped": grads(torch.float64, _STEM_MASK.flip(0))[sw], "no mask": grads(torch.float64, None)[sw]}
+    return dict(x=x, target=target, edge=edge, forced=forced, g64=g64, noise=noise, alt=alt)
+
+
+def _stem_dropout_model(forced):
+    """training mode, the stem's dropout ON (every other dropout rate zeroed: those sites are tested at function level)"""
+    m = _no_dropout_model(forced)
+    m.Unet_list.InitConv.dropout = 0.2
+    return m
+
+
+def _flat_by_name(m, tr):
+    pname = {id(p): n for n, p in m.named_parameters()}
+    got, off = {}, 0
+    for p in tr.opt.sink.params:
+        got[pname[id(p)]] = tr.opt.flat_grad[off:off + p.numel()].view_as(p)
+        off += p.numel()
+    assert off == tr.opt.flat_grad.numel()
+    return got
+
+
+@pytest.mark.parametrize("wgrad", ["bf16", "bf16x3"])
+def test_trainer_step_with_stem_dropout_vs_oracle(hip, monkeypatch, wgrad):
+    """bench.py trains with the stem's always-on dropout3d; under the gradient sink its backward folds the keep mask into the stem's weight
+    gradient (cwf_wgrad_mfma_bf16_dys: wgrad_to(..., dy_scale=)) instead of a channel_scale pass over dy.  With the mask and the top-k
+    selections teacher-forced, batch 2 at 64^3 in the bench precision (single- and split-bf16 weight-gradient products):
+    (1) the Trainer's flat gradient against the float64 oracle, twice (the second step on cached tables), with the golden test's bounds;
+    (2) the fold ran: one wgrad_to call per step carries dy_scale, for the stem;  (3) plain autograd (no sink) takes channel_scale and
+    gives the same gradients to reduction-order noise;  (4) the stem rows of the channel dropped in both samples are exactly 0;
+    (5) the bounds tell masks apart: the oracle's stem gradient with the masks swapped / with no mask fails them;  (6) plan mode (what
+    bench.py times) gives the eager flat gradient;  (7) with unwritten fp32 gradient carriers poisoned (NaN) the step is unchanged:
+    the model's single-consumer declaration holds."""
+    from cwf import functional as CF, kernels
+    from cwf.trainer import Trainer, total_loss
+    orc = _stem_dropout_oracle()
+    g64, noise = orc["g64"], orc["noise"]
+    mask = _STEM_MASK.to(DEV)
+    draws = []
+
+    def forced_mask(shape, p, device, p2=0.0):
+        assert tuple(shape) == (2, 16) and p == 0.2 and p2 == 0.0, (shape, p, p2)
+        draws.append(shape)
+        return mask                                     # (the same tensor every time: a plan replays its address)
+    monkeypatch.setattr(CF, "dropout_mask", forced_mask)
+    calls = []
+    wgrad_to = hip.wgrad_to
+
+    def spy(*a, **kw):
+        calls.append((a[0], kw.get("dy_scale")))
+        return wgrad_to(*a, **kw)
+    monkeypatch.setattr(hip, "wgrad_to", spy)
+    forced = {k: v.to(DEV) for k, v in orc["forced"].items()}
+    x, target, edge = orc["x"].to(DEV), orc["target"].to(DEV), orc["edge"].to(DEV)
+    gold = np.load(os.path.join(GOLDEN, "model_64.npz"))
+    full = [k[6:] for k in gold.files if k.startswith("grad::")] + ["Unet_list.InitConv.conv.bias"]
+    sw, sb = "Unet_list.InitConv.conv.weight", "Unet_list.InitConv.conv.bias"
+    kernels.set_precision("bf16x3", wgrad=wgrad, dgrad="bf16")
+    try:
+        m = _stem_dropout_model(forced)
+        stem = m.Unet_list.InitConv.conv.spec
+        tr = Trainer(m)
+        assert tr.wgrad_async
+        flats = []
+        for rep in range(2):
+            calls.clear()
+            tr._fwd_bwd(x, target, edge)
+            torch.cuda.synchronize()
+            assert all(p.grad is None for p in m.parameters())
+            folded = [c for c in calls if c[1] is not None]
+            assert len(folded) == 1 and folded[0][0] is stem and torch.equal(folded[0][1], mask), (rep, len(folded))
+            got = _flat_by_name(m, tr)
+            bad = []
+            for n, ref in g64.items():
+                assert bool(torch.isfinite(got[n]).all()), n
+                rn = float(ref.norm())
+                if rn > 1e-7:
+                    v = float(got[n].double().norm())
+                    if abs(v - rn) > max(10 * noise[n], 1e-2) * rn:
+                        bad.append((n, v, rn))
+            assert not bad, (rep, bad[:10])
+            for n in full:
+                d = float((got[n].double().cpu() - g64[n]).norm() / g64[n].norm())
+                assert d < max(10 * noise[n], 2e-2), (rep, n, d)
+            # exact zeros: the channel dropped in both samples
+            assert float(got[sw][_STEM_DROPPED].abs().max()) == 0.0 and float(got[sb][_STEM_DROPPED]) == 0.0
+            flats.append(tr.opt.flat_grad.clone())
+        assert len(draws) == 2
+        eager_noise = float((flats[0] - flats[1]).norm() / flats[0].norm())
+        # the bounds the HIP stem gradient passes reject the oracle's gradient under a mixed-up mask
+        bound = max(10 * noise[sw], 2e-2)
+        assert float((got[sw].double().cpu() - g64[sw]).norm() / g64[sw].norm()) < bound
+        for what, alt in orc["alt"].items():
+            assert float((alt - g64[sw]).norm() / g64[sw].norm()) > bound, what
+
+        # plain autograd: per-parameter .grad, the mask applied by channel_scale (no fold)
+        plain = []
+        for _ in range(2):
+            calls.clear()
+            mp = _stem_dropout_model(forced)
+            loss, _ = total_loss(mp(x, None), target, edge)
+            loss.backward()
+            assert all(c[1] is None for c in calls)
+            plain.append({n: p.grad.clone() for n, p in mp.named_parameters()})
+        pnoise = max(float((plain[0][n] - plain[1][n]).norm() / (plain[0][n].norm() + 1e-30)) for n in plain[0]
+                     if float(plain[0][n].norm()) > 1e-7)
+        got = _flat_by_name(m, tr)
+        for n, ref in plain[0].items():
+            if float(ref.norm()) > 1e-7 and float(g64[n].norm()) > 1e-7:
+                d = float((got[n] - ref).norm() / ref.norm())
+                assert d < max(5e-5, 10 * pnoise), (n, d, pnoise)
+
+        # unwritten fp32 gradient carriers filled with NaN: nothing reads them
+        monkeypatch.setattr(kernels, "POISON_UNWRITTEN_CARRIERS", True)
+        tr._fwd_bwd(x, target, edge)
+        torch.cuda.synchronize()
+        monkeypatch.setattr(kernels, "POISON_UNWRITTEN_CARRIERS", False)
+        g = tr.opt.flat_grad
+        assert bool(torch.isfinite(g).all())
+        diff = float((g - flats[0]).norm() / flats[0].norm())
+        assert diff < max(5e-5, 10 * eager_noise), (diff, eager_noise)
+
+        # plan mode: one eager warm-up, then the captured launch list
+        trg = Trainer(_stem_dropout_model(forced), use_graph="plan")
+        trg._fwd_bwd(x, target, edge)
+        torch.cuda.synchronize()
+        trg._capture(x, target, edge)
+        assert trg._plan is not None and "error" not in trg.plan_info, trg.plan_info
+        for i in range(2):
+            _replay(trg)
+            torch.cuda.synchronize()
+            g = trg.opt.flat_grad
+            assert bool(torch.isfinite(g).all())
+            diff = float((g - flats[0]).norm() / flats[0].norm())
+            assert diff < max(5e-5, 10 * eager_noise), (i, diff, eager_noise)
+    finally:
+        kernels.set_precision("fp32")

@@ -352,8 +352,9 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgsB a) {
       }
     }
     __syncthreads();
-    if (tid < WN * NT * 16 * 2) {
-      const int which = tid & 1, rr = (tid >> 1) & 15, jj = (tid >> 5) % NT, ww = (tid >> 5) / NT;
+    // WN * NT * 32 (channel, sum) pairs: 512 for {4, 4, 1} -- more than the 256 threads, hence the loop
+    for (int t = tid; t < WN * NT * 16 * 2; t += 256) {
+      const int which = t & 1, rr = (t >> 1) & 15, jj = (t >> 5) % NT, ww = (t >> 5) / NT;
       double s = 0.0;
 #pragma unroll
       for (int w = 0; w < WM; ++w) s += (double)red[(((w * WN + ww) * NT + jj) * 16 + rr) * 2 + which];
@@ -1757,6 +1758,29 @@ extern "C" int cwf_conv_mfma_bf16_in16(int op, const void* x16, const void* zero
                         nb_x, nb_ldc, nb_scale, nb_shift, nb_slope, N, D, H, W, 16, D, H, W, 16, stream, x16, zero16);
 }
 
+// The extent choose_cfg tiles (per output-parity class) and the class count of a launch: the output extent, or for the eight-class
+// launches (ConvTranspose forward, stride-2 data gradient) the extent of one class.
+static int cfg_extent(int op, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int cd[3]) {
+  cd[0] = Do; cd[1] = Ho; cd[2] = Wo;
+  if (op == CWF_CONVT2) { cd[0] = Di; cd[1] = Hi; cd[2] = Wi; return 8; }
+  if (op == CWF_CONV3_S2_DGRAD) { cd[0] = (Do + 1) / 2; cd[1] = (Ho + 1) / 2; cd[2] = (Wo + 1) / 2; return 8; }
+  return 1;
+}
+
+// Read-only query (tests): the tile configuration {MT, NT, WM} that conv_bf16_impl's choose_cfg picks for a launch of `op` from input
+// extent Di x Hi x Wi to output extent Do x Ho x Wo (no CWF_FORCE_CFG).  Whether the launch reaches the tap-table kernel at all (pointwise,
+// weight-stationary, conv16 routes) is not decided here.  Launches nothing.
+extern "C" int cwf_debug_conv_bf16_cfg(int op, int N, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cout, int* mt_nt_wm) {
+  if (!mt_nt_wm || N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || op < CWF_CONV3_S1 ||
+      op > CWF_CONVT2_DGRAD)
+    return CWF_E_BADARG;
+  int cd[3];
+  const int ncls = cfg_extent(op, Di, Hi, Wi, Do, Ho, Wo, cd);
+  const TileCfg c = choose_cfg(op, cd, ncls, N, cdiv(Cout, 16));
+  mt_nt_wm[0] = c.MT; mt_nt_wm[1] = c.NT; mt_nt_wm[2] = c.WM;
+  return 0;
+}
+
 static int conv_bf16_impl(int op, int x3, const float* x, int x_ldc, const void* wpk16, const float* bias,
                           float* y, int y_ldc, const float* in_scale, const float* in_shift, float in_slope,
                           const float* residual, int r_ldc, const float* out_scale, double* stats,
@@ -1769,9 +1793,8 @@ static int conv_bf16_impl(int op, int x3, const float* x, int x_ldc, const void*
   if (((uintptr_t)x & 15) || ((uintptr_t)wpk16 & 15)) return CWF_E_ALIGN;
   if (in_scale && !in_shift) return CWF_E_BADARG;
   ConvArgsB a;
-  int cd[3] = {Do, Ho, Wo}; int ncls = 1;
-  if (op == CWF_CONVT2) { cd[0] = Di; cd[1] = Hi; cd[2] = Wi; ncls = 8; }
-  if (op == CWF_CONV3_S2_DGRAD) { cd[0] = (Do + 1) / 2; cd[1] = (Ho + 1) / 2; cd[2] = (Wo + 1) / 2; ncls = 8; }
+  int cd[3];
+  const int ncls = cfg_extent(op, Di, Hi, Wi, Do, Ho, Wo, cd);
   TileCfg c = choose_cfg(op, cd, ncls, N, cdiv(Cout, 16));
   {                                                    // tuning aid: CWF_FORCE_CFG="MT,NT,WM" overrides the tile choice
     static const char* force = getenv("CWF_FORCE_CFG");
@@ -1842,8 +1865,8 @@ extern "C" int cwf_conv_mfma_bf16_grouped(int op, int x3, const float* x, int x_
   if ((Cin & 3) || (x_ldc & 3) || (x_goff & 3) || x_ldc < (groups - 1) * x_goff + Cin || y_ldc < (groups - 1) * y_goff + Cout) return CWF_E_ALIGN;
   if ((uintptr_t)x & 15) return CWF_E_ALIGN;
   ConvArgsB a;
-  int cd[3] = {Do, Ho, Wo};
-  TileCfg c = choose_cfg(op, cd, 1, N * groups, cdiv(Cout, 16));
+  int cd[3];
+  TileCfg c = choose_cfg(op, cd, cfg_extent(op, Di, Hi, Wi, Do, Ho, Wo, cd), N * groups, cdiv(Cout, 16));
   int rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, c.MT * c.WM);
   if (rc) return rc;
   a.x = x; a.wpk = nullptr; a.bias = nullptr; a.y = y; a.in_scale = nullptr; a.in_shift = nullptr; a.in_slope = 1.f;

@@ -143,8 +143,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
       }
     }
     __syncthreads();
-    if (tid < WN * NT * 16 * 2) {
-      const int which = tid & 1, rr = (tid >> 1) & 15, jj = (tid >> 5) % NT, ww = (tid >> 5) / NT;
+    // WN * NT * 32 (channel, sum) pairs: 512 for {4, 4, 1} -- more than the 256 threads, hence the loop
+    for (int t = tid; t < WN * NT * 16 * 2; t += 256) {
+      const int which = t & 1, rr = (t >> 1) & 15, jj = (t >> 5) % NT, ww = (t >> 5) / NT;
       double s = 0.0;
 #pragma unroll
       for (int w = 0; w < WM; ++w) s += (double)red[(((w * WN + ww) * NT + jj) * 16 + rr) * 2 + which];

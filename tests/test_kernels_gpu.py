@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import bf16_operand_ref as R
 from cwf import packing as pk
 from oracle.kernel_emul import EmulBackend
 
@@ -43,6 +44,22 @@ def _packed(spec, w, prec="fp32"):
 
 
 PREC_TOL = {"fp32": 2e-5, "bf16x3": 2e-4, "bf16": 3e-2}
+
+
+def exact(got, ref, prec, what, gamma=R.GAMMA_CONV):
+    """beside the fp32-oracle check of a bf16-mode result: the operand-exact bound |got - ref| <= gamma * A of tests/bf16_operand_ref.py"""
+    if prec != "fp32":
+        R.check(got, ref, gamma, what)
+
+
+def exact_wgrad(gw, gb, op, x, dy, prec, in_scale, in_shift, slope, size, what):
+    """the weight / bias gradient of hip.wgrad / wgrad_to against the operand-exact reference (operand form of the kernel that ran)"""
+    if prec == "fp32":
+        return
+    dw, db, aw, ab = R.wgrad_ref(op, x, dy, R.wgrad_operand_mode(op, x.shape[-1], dy.shape[-1], size, prec), in_scale, in_shift, slope)
+    R.assert_operand_exact(gw.reshape(dw.shape), dw, aw, R.GAMMA_WGRAD, what + " dW")
+    if gb is not None:
+        R.assert_operand_exact(gb, db, ab, R.GAMMA_WGRAD, what + " db")
 
 
 CONV_CASES = [
@@ -96,10 +113,16 @@ def test_conv_family_fwd_dgrad_wgrad(hip, op, cin, cout, size, n, prec):
     assert y.shape == y_ref.shape                       # (padding channels of a 2-channel head are allocated but not initialised)
     close(y[..., :cout], y_ref[..., :cout], rtol=tol, what="fwd")
     close(st, st_ref, rtol=max(1e-5, tol), what="stats")
+    if prec != "fp32":
+        ex = R.conv_ref(op, x, w, prec, bias=b, in_scale=in_scale, in_shift=in_shift, slope=0.01, residual=res, out_scale=out_scale)
+        exact(y[..., :cout], ex, prec, "fwd")
+        R.assert_stats(st, ex, R.GAMMA_CONV, "stats")
     # ---- plain forward (no prologue / epilogue extras)
     y2_ref = E.conv(op, x, None, None, cout, w_ref=w, out_channels_alloc=spec.cout_alloc)
     y2 = hip.conv(op, x.to(DEV), wf, None, cout, out_channels_alloc=spec.cout_alloc, prec=prec)
     close(y2[..., :cout], y2_ref[..., :cout], rtol=tol, what="fwd plain")
+    if prec != "fp32":
+        exact(y2[..., :cout], R.conv_ref(op, x, w, prec), prec, "fwd plain")
 
     # ---- data gradient
     dy = torch.zeros(n, do, ho, wo, spec.cout_alloc)
@@ -107,6 +130,8 @@ def test_conv_family_fwd_dgrad_wgrad(hip, op, cin, cout, size, n, prec):
     dx_ref = E.conv(pk.dgrad_op(op), dy, None, None, cin, out=torch.empty(n, d, h, w_, cin), w_ref=w, fwd_op=op)
     dx = hip.conv(pk.dgrad_op(op), dy.to(DEV), wd, None, cin, out=torch.empty((n, d, h, w_, cin), device=DEV), prec=prec)
     close(dx, dx_ref, rtol=tol, what="dgrad")
+    if prec != "fp32":
+        exact(dx, R.conv_ref(op, dy, w, prec, dgrad=True, out_size=size), prec, "dgrad")
 
     # ---- weight / bias gradient with the recomputed prologue
     dyv = dy[..., :cout]
@@ -115,6 +140,7 @@ def test_conv_family_fwd_dgrad_wgrad(hip, op, cin, cout, size, n, prec):
     close(gw, gw_ref, rtol=max(5e-5, tol), what="wgrad")
     if gb is not None:
         close(gb, gb_ref, rtol=max(5e-5, tol), what="bgrad")
+    exact_wgrad(gw, gb, op, x, dyv, prec, in_scale, in_shift, 0.0, size, "wgrad")
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
@@ -213,6 +239,8 @@ def test_dma_weight_gradient_32_channel_groups(hip, cin, cout, size, n):
     gw_ref, gb_ref = E.wgrad(pk.CONV3_S1, x, sc, sh, 0.01, g, cout, None, True, wn, w_ref_shape=(cout, cin, 3, 3, 3))
     close(dw_b, gw_ref, rtol=PREC_TOL["bf16"], what="dma wgrad vs oracle")
     close(db_b, gb_ref, rtol=PREC_TOL["bf16"], what="dma bgrad vs oracle")
+    for dw, db, what in ((dw_a, db_a, "fp32-tensor"), (dw_b, db_b, "dma")):
+        exact_wgrad(dw, db, pk.CONV3_S1, x, g, "bf16", sc, sh, 0.01, size, what)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
@@ -238,6 +266,10 @@ def test_stem_kernel_packs_eight_taps_times_four_channels(hip, size, n, prec):
     close(st_a, st_ref, rtol=max(1e-5, tol), what="stem stats vs oracle")
     close(y_a, y_b.cpu(), rtol=2e-5 if prec == "bf16x3" else 2e-5, what="stem vs conv16s")
     close(st_a, st_b.cpu(), rtol=2e-5, what="stem stats vs conv16s")
+    ex = R.conv_ref(pk.CONV3_S1, x, w, prec, bias=b, out_scale=osc)
+    for y_, st_, what in ((y_a, st_a, "stem"), (y_b, st_b, "conv16s")):
+        exact(y_, ex, prec, what)
+        R.assert_stats(st_, ex, R.GAMMA_CONV, what)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
@@ -263,6 +295,12 @@ def test_first_downsampling_kernel(hip, size, n, prec):
         y_ref = E.conv(pk.CONV3_S2, x, None, b, 32, None, None, 1.0, None, None, st_ref, w_ref=w)
         close(y_a, y_ref, rtol=tol, what="s2 vs oracle")
         close(st_a, st_ref, rtol=max(1e-5, tol), what="s2 stats vs oracle")
+        ex = R.conv_ref(pk.CONV3_S2, x, w, prec, bias=b)
+        R.assert_stats(st_a, ex, R.GAMMA_CONV, "s2 stats")
+    else:                                   # 128^3: the reference at every voxel of the last tiles, the faces and a random sample
+        ex = R.conv_ref(pk.CONV3_S2, x, w, prec, bias=b, vox=R.edge_voxels(n, pk.out_dims(pk.CONV3_S2, d, h, w_), tile=(2, 2, 16), n_random=8192))
+    exact(y_a, ex, prec, "s2 kernel")
+    exact(y_b, ex, prec, "s2 tap-table kernel")
 
 
 @pytest.mark.parametrize("cin,cout,size,n", [(32, 16, (32, 32, 32), 2), (64, 32, (16, 16, 16), 1), (128, 64, (8, 8, 8), 2), (16, 4, (8, 8, 16), 1)])
@@ -353,6 +391,8 @@ def test_bf16_operand_images_and_dma_weight_gradient(hip, size, n):
     gw_ref, gb_ref = E.wgrad(pk.CONV3_S1, x, sc, sh, 0.01, g, c, None, True, wn, w_ref_shape=(c, c, 3, 3, 3))
     close(dw_b, gw_ref, rtol=PREC_TOL["bf16"], what="dma wgrad vs oracle")
     close(db_b, gb_ref, rtol=PREC_TOL["bf16"], what="dma bgrad vs oracle")
+    for dw, db, what in ((dw_a, db_a, "fp32-tensor"), (dw_b, db_b, "dma")):
+        exact_wgrad(dw, db, pk.CONV3_S1, x, g, "bf16", sc, sh, 0.01, size, what)
 
 
 def _dy_scale(n, seed):
@@ -491,11 +531,15 @@ def _weight_stationary_case(hip, cin, cout, size, n, prec, tol, CF):
     y = hip.conv(op, x.to(DEV), spec.wpk16_f, b.to(DEV), cout, in_scale.to(DEV), in_shift.to(DEV), 0.01, res.to(DEV), None, st, prec=prec)
     close(y, y_ref, rtol=tol, what="fwd")
     close(st, st_ref, rtol=max(1e-5, tol), what="stats")
+    ex = R.conv_ref(op, x, w, prec, bias=b, in_scale=in_scale, in_shift=in_shift, slope=0.01, residual=res)
+    exact(y, ex, prec, "fwd")
+    R.assert_stats(st, ex, R.GAMMA_CONV, "stats")
     # ReLU prologue, no residual, into a channel slice of a wider buffer, strided input
     wide = torch.full((n, d, h, w_, cout + 8), 7.0, device=DEV)
     xw = torch.zeros((n, d, h, w_, cin + 4), device=DEV); xw[..., :cin] = x.to(DEV)
     hip.conv(op, xw[..., :cin], spec.wpk16_f, b.to(DEV), cout, in_scale.to(DEV), in_shift.to(DEV), 0.0, out=wide[..., 8:], prec=prec)
     close(wide[..., 8:], E.conv(op, x, None, b, cout, in_scale, in_shift, 0.0, w_ref=w), rtol=tol, what="fwd into slice")
+    exact(wide[..., 8:], R.conv_ref(op, x, w, prec, bias=b, in_scale=in_scale, in_shift=in_shift, slope=0.0), prec, "fwd into slice")
     assert bool((wide[..., :8] == 7.0).all())
     # data gradient with a residual (the carried skip gradient) and the norm-backward sums, against the two-pass form
     dy = rnd(n, d, h, w_, cout, seed=38)
@@ -507,6 +551,9 @@ def _weight_stationary_case(hip, cin, cout, size, n, prec, tol, CF):
                  prec=prec, stats=sums, nb=(xd, sc, sh, 0.01))
     close(g, dx_ref, rtol=tol, what="dgrad + residual")
     close(hip.in_bwd_apply(g, xd, sc, sh, 0.01, sums), hip.in_bwd(g, xd, sc, sh, 0.01).cpu(), rtol=2e-5, what="norm-backward sums")
+    ex = R.conv_ref(op, dy, w, prec, residual=carry, dgrad=True, out_size=size)
+    exact(g, ex, prec, "dgrad + residual")
+    R.assert_nb_sums(sums, ex, (x, in_scale, in_shift, 0.01), R.GAMMA_CONV, "norm-backward sums")
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
@@ -541,12 +588,16 @@ def test_pointwise_stream_kernel(hip, op, cin, cout, size, n, prec):
     y = hip.conv(op, x.to(DEV), spec.wpk16_f, b.to(DEV), cout, None, None, 1.0, None if res is None else res.to(DEV), None, st, prec=prec)
     close(y, y_ref, rtol=tol, what="fwd")
     close(st, st_ref, rtol=max(1e-5, tol), what="stats")
+    ex = R.conv_ref(op, x, w, prec, bias=b, residual=res)
+    exact(y, ex, prec, "fwd")
+    R.assert_stats(st, ex, R.GAMMA_CONV, "stats")
     # into a channel slice of a wider buffer (the concatenation buffer of DeUp_Cat), strided input
     wide = torch.full((n, do, ho, wo, cout + 8), 7.0, device=DEV)
     xw = torch.zeros((n, d, h, w_, cin + 4), device=DEV); xw[..., :cin] = x.to(DEV)
     hip.conv(op, xw[..., :cin], spec.wpk16_f, b.to(DEV), cout, out=wide[..., 8:], prec=prec)
     y_plain = E.conv(op, x, None, b, cout, w_ref=w)
     close(wide[..., 8:], y_plain, rtol=tol, what="fwd into slice")
+    exact(wide[..., 8:], R.conv_ref(op, x, w, prec, bias=b), prec, "fwd into slice")
     assert bool((wide[..., :8] == 7.0).all())
     if op != pk.CONV1:
         return
@@ -562,6 +613,9 @@ def test_pointwise_stream_kernel(hip, op, cin, cout, size, n, prec):
                   prec=prec, stats=sums, nb=(xd, sc, sh, 0.01))
     close(dx, dx_ref, rtol=tol, what="dgrad + residual")
     close(hip.in_bwd_apply(dx, xd, sc, sh, 0.01, sums), hip.in_bwd(dx, xd, sc, sh, 0.01).cpu(), rtol=2e-5, what="norm-backward sums")
+    ex = R.conv_ref(pk.CONV1, dy, w, prec, residual=carry, dgrad=True, out_size=size)
+    exact(dx, ex, prec, "dgrad + residual")
+    R.assert_nb_sums(sums, ex, (x, in_scale, in_shift, 0.01), R.GAMMA_CONV, "norm-backward sums")
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
@@ -663,6 +717,9 @@ def test_channel_grouped_conv(hip, cin, cout, size, n, G, prec):
     for q in range(G):
         ref = E.conv(pk.CONV3_S1, x_all[..., q * cin:(q + 1) * cin], None, bs[q], cout, w_ref=ws[q])
         close(y_all[..., q * ca:q * ca + cout], ref[..., :cout], rtol=tol, what="fwd group %d" % q)
+        if prec != "fp32":
+            exact(y_all[..., q * ca:q * ca + cout], R.conv_ref(pk.CONV3_S1, x_all[..., q * cin:(q + 1) * cin], ws[q], prec, bias=bs[q]), prec,
+                  "fwd group %d" % q)
         if ca != cout:
             assert bool((y_all[..., q * ca + cout:(q + 1) * ca] == 5.0).all())
     dy_all = torch.zeros(n, d, h, w_, G * ca)
@@ -673,6 +730,9 @@ def test_channel_grouped_conv(hip, cin, cout, size, n, G, prec):
     for q in range(G):
         ref = E.conv(pk.CONV3_S1, dy_all[..., q * ca:(q + 1) * ca], None, None, cin, out=torch.empty(n, d, h, w_, cin), w_ref=ws[q], fwd_op=pk.CONV3_S1)
         close(dx_all[..., q * cin:(q + 1) * cin], ref, rtol=tol, what="dgrad group %d" % q)
+        if prec != "fp32":
+            exact(dx_all[..., q * cin:(q + 1) * cin], R.conv_ref(pk.CONV3_S1, dy_all[..., q * ca:(q + 1) * ca], ws[q], prec, dgrad=True, out_size=size),
+                  prec, "dgrad group %d" % q)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])

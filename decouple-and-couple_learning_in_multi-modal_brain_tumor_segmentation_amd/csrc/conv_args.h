@@ -11,7 +11,9 @@ struct ConvArgsB {
   const float* x; const uint4* wpk; const float* bias; float* y;
   const float* in_scale; const float* in_shift; float in_slope;
   const float* residual; int r_ldc; const float* out_scale; double* stats;
-  unsigned long long* diag; int diag_mode;
+  // 16 unused bytes: without them every later field moves and hipcc schedules conv16s_kernel / convws_kernel differently; they keep
+  // the compiled kernels byte-for-byte as measured
+  unsigned long long unused_[2];
   // "norm-backward" statistics (data-gradient launches whose output g feeds the backward of y = act(IN(x))): with nb_x set,
   // stats receives per (n, channel)  S1 = sum g*act'(h), S2 = sum g*act'(h)*h,  h = nb_x*nb_scale + nb_shift  -- what
   // cwf_in_bwd_stats would compute in a separate pass over g and x (norm.hip) -- instead of (sum y, sum y^2).

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgsB a) {
   for (int j = 0; j < NT; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
   // fast path (workgroup/wave-uniform test): interior tile of a plain (single-class, unit output stride) geometry with all NT
   // channel tiles valid -- every store is SGPR row base + tile-invariant 32-bit lane offset, no per-element bounds or
-  // 64-bit address arithmetic (cf. conv16_kernel's epilogue)
+  // 64-bit address arithmetic (as in conv16s' epilogue)
   // (output-parity classes -- stride-2 data gradient, ConvTranspose -- take it too: voxel stride os = 2 and the class offset
   // only change the row base and the per-lane voxel step; the scalar path below cost the EnDown data gradient 2x)
   const bool fast = od0 + g.TD <= Dc && oh0 + g.TH <= Hc && ow0 + 16 <= Wc && (nt0 + NT) * 16 <= g.Cout &&
@@ -372,12 +372,23 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgsB a) {
 // instructions per MFMA (staging index arithmetic, bf16 splitting, epilogue addressing) and waiting on their own loads.
 //   * producer / consumer waves: a workgroup is 8 waves, one per CU.  Waves 0-3 ("MFMA waves", one per SIMD) hold the whole
 //     weight set in registers (14 tap pairs x (hi|lo) x 16 B per lane) and do nothing but LDS reads, MFMAs and the epilogue;
-//     waves 4-7 ("loader waves", their SIMD partners) fetch the next halo tile from HBM, apply InstanceNorm + activation,
-//     split to bf16 hi/lo and write the OTHER LDS buffer.  The matrix pipe and the VALU/memory pipes of a SIMD run side by
-//     side; one barrier per tile hands the buffers over.
-//   * persistent workgroups walk the 4x4x16 output tiles; a tile's global loads are issued a full tile ahead.
-//   * tile geometry is compile-time (6x6x18 halo): LDS offsets are immediates; the loader keeps one precomputed
-//     voxel-relative offset per staging slot and adds it to a scalar tile base (no div/mod or 64-bit math per voxel).
+//     waves 4-7 ("loader waves", their SIMD partners) fetch the next halo rows from HBM, apply InstanceNorm + activation,
+//     split to bf16 hi/lo and write them to LDS.  The matrix pipe and the VALU/memory pipes of a SIMD run side by side; one
+//     barrier per tile hands the rows over.  Only the hi weight images live in registers (56 VGPRs); the lo images sit in LDS,
+//     lane-linear and conflict-free, fetched with the A fragments (hi + lo both in registers spills).
+//   * tile geometry is compile-time (6x6x18 halo): LDS offsets are immediates (the ds_read offset field), and the MFMA loop
+//     carries no address arithmetic -- the kernel is bound by each SIMD's vector-issue port, shared by its MFMA wave and its
+//     loader wave, so instructions, not bytes, are what is being saved; the loader keeps one precomputed voxel-relative
+//     offset per staging slot and adds it to a scalar tile base (no div/mod or 64-bit math per voxel).
+//   * deferred epilogue: an interior tile without residual or output scale is written out not after its own MFMA phase but
+//     during the next tile's (one store and two statistics FMAs after each of the first 16 MFMA groups), where those ~50
+//     vector instructions cost issue slots only; done serially they cost ~2k cycles per tile.
+//   * InstanceNorm statistics of the output stay in registers over a workgroup's tiles and are flushed with one f64 atomic
+//     pair per wave and channel when the sample index changes and at the end.
+//   * XCD-aware work order: workgroups are dealt round-robin over the 8 XCDs (each with its own L2), so each XCD takes a
+//     contiguous range of the work and neighbouring tiles share their halo in one L2.  Measured on a full-halo form of this
+//     kernel (2 x 16 x 128^3 bf16x3, L2-miss reads; ideal 268 MB): tile = b + it*256 320 MB 0.350 ms, per-workgroup
+//     contiguous chunks 593 MB 0.333 ms, XCD strips 406 MB 0.310 ms (fastest).
 // ---------------------------------------------------------------------------------------------------
 // Tap order of the <= 16-channel 3x3x3 stride-1 layers (cwf/packing.py: _taps3_order16): position -> natural tap index
 // kd*9 + kh*3 + kw.  Pairs (2s, 2s+1): s = 0..8 (kw0, kw1) of row (kd, kh) = (s/3, s%3); s = 9..11 (kd0, kd1) of (kh = s-9,
@@ -392,430 +403,9 @@ __host__ __device__ constexpr int c16_tap(int pos) {
 #define C16_ID 6
 #define C16_IH 6
 #define C16_IW 18
-#define C16_NVOX (C16_ID * C16_IH * C16_IW)          // 648
-#define C16_SLOTS ((C16_NVOX + 63) / 64)             // 11 staging slots per loader thread (4 threads per voxel)
-
-// In-kernel phase stamps (diagnostic build only, DIAG = true: cwf_debug_conv16_diag): s_memtime per phase and wave role.
-#define CWF_STAMP(v) unsigned long long v = 0; if (DIAG) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
-
-template <bool X3, bool DIAG>
-__global__ __launch_bounds__(512) void conv16_kernel(const ConvArgsB a, int total_tiles) {
-  extern __shared__ float4 lds4[];
-  const ConvGeom& g = a.g;
-  constexpr int IMG = C16_NVOX * 16;                   // bf16 elements per image
-  constexpr int BUF = IMG * (X3 ? 2 : 1);              // per buffer: hi image (+ lo image)
-  unsigned short* lds = reinterpret_cast<unsigned short*>(lds4);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the role branch below is provably wave-uniform
-  const int tiles_sp = g.tiles_d * g.tiles_h * g.tiles_w;
-  // Tile -> workgroup map (speed only, never correctness).  Workgroups are dealt round-robin over the 8 XCDs, each with its own
-  // L2: XCD x = b & 7 hosts the `per` workgroups s = b >> 3.  Each XCD owns a contiguous range of "strips" of `per`
-  // consecutive tiles (at 128^3: 4 full rows of tiles along H x 8 along W) and its workgroups take one strip per iteration:
-  // neighbours in W and H run on the same XCD in the same or the previous iteration, so their shared halo hits in that XCD's
-  // L2; only the D halo (8 iterations = 10 MB away) falls through to the Infinity Cache.
-  // Measured (2 x 16 x 128^3 bf16x3, PMC FETCH_SIZE x 2 = L2-miss reads; ideal 268 MB):
-  //   tile = b + it*256                      320 MB   0.350 ms
-  //   per-workgroup contiguous chunks        593 MB   0.333 ms
-  //   XCD strips (this map)                  406 MB   0.310 ms   <- fastest
-  //   XCD segment of a whole-plane front     308 MB   0.335 ms   (4 MB address jumps per iteration; used by wgrad16)
-  const int G = (int)gridDim.x, per = G >> 3;                // grid is a multiple of 8, see launcher
-  const int nstrips = (total_tiles + per - 1) / per;
-  const int S = (nstrips + 7) >> 3;                          // strips per XCD
-  const int xcd = blockIdx.x & 7;
-  const int first = xcd * S * per + (blockIdx.x >> 3);       // tile(it) = first + it * per
-  int niter = 0;
-  {
-    const int my_strips = min(S, nstrips - xcd * S);         // may be <= 0 for the last XCDs of a small problem
-    if (my_strips > 0) niter = (first + (my_strips - 1) * per < total_tiles) ? my_strips : my_strips - 1;
-  }
-  if (niter == 0) return;                                    // uniform for the whole workgroup
-
-  if (wave < 4) {
-    // =============================================================== MFMA waves
-    const int r = lane & 15, kq = lane >> 4;
-    const bool second = (kq >> 1) != 0;
-    // hi weight images in registers (56 VGPRs); lo images in LDS, lane-linear [14][64] x 16 B (conflict-free), fetched with the
-    // A fragments one tap pair ahead.  (hi + lo both in registers spills next to the double-buffered A fragments.)
-    uint4 bh[14];
-    const uint4* wl = reinterpret_cast<const uint4*>(lds + 2 * BUF) + lane;
-    {
-      const uint4* wp = a.wpk + lane * 2;
-#pragma unroll
-      for (int s = 0; s < 14; ++s) bh[s] = wp[s * 128];
-      if (X3) {
-        uint4* wls = reinterpret_cast<uint4*>(lds + 2 * BUF);
-        for (int i = tid; i < 14 * 64; i += 256) wls[i] = a.wpk[(i >> 6) * 128 + (i & 63) * 2 + 1];
-      }
-    }
-    // ---- A-fragment addressing.  LDS byte address = buffer parity + per-lane base[m] + tap offset.  The two taps of
-    // one K = 32 step are split over lane halves (lanes 32-63 take the second), whose offset differs from the first's by one of
-    // three constants (next kw / next kh row / next kd plane: see c16_tap) or 0 (last, unpaired tap).  Four classes x four M-tiles of per-lane bases
-    // stay in registers, so the tap offset is the ds_read immediate and the MFMA loop carries no address arithmetic: the
-    // kernel is bound by each SIMD's vector-issue port, shared by its MFMA wave and its loader wave (an MFMA holds it for 8
-    // of its 16 cycles, every other vector instruction for >= 4) -- instructions, not bytes, are what is being saved here.
-    constexpr int D_KW = 32, D_ROW = C16_IW * 32, D_PLANE = C16_IH * C16_IW * 32;
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-    typedef const u32x4_t __attribute__((address_space(3)))* lds_u4p;    // 32-bit LDS pointer formed from an integer address
-    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds4;
-    unsigned ab[4][4];                                   // [class: 0 = +kw, 1 = +row (kh), 2 = +plane (kd), 3 = same tap][m]
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const unsigned base = lds_base + (((wave * C16_IH + m) * C16_IW + r) * 16 + (kq & 1) * 8) * 2;
-      ab[0][m] = base + (second ? D_KW : 0); ab[1][m] = base + (second ? D_ROW : 0);
-      ab[2][m] = base + (second ? D_PLANE : 0); ab[3][m] = base;
-    }
-    const float bv = (a.bias && r < g.Cout) ? a.bias[r] : 0.f;
-    const f32x4 bias4 = {bv, bv, bv, bv};                // accumulators start from the bias (lane = output channel r)
-    // epilogue addressing: uniform 64-bit row base (SGPRs) + tile-invariant 32-bit lane offsets -> no address VALU per store
-    unsigned yofs[4], rofs[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { yofs[i] = (unsigned)((kq * 4 + i) * g.y_ldc + r) * 4u; rofs[i] = (unsigned)((kq * 4 + i) * a.r_ldc + r) * 4u; }   // bytes
-    // InstanceNorm statistics of the output: kept in registers over this workgroup's tiles, flushed with one f64 atomic
-    // pair per wave and channel when the sample index changes and at the end.
-    float s1 = 0.f, s2 = 0.f;
-    int stat_n = first / tiles_sp;
-    float osc = 1.f; int osc_n = -1;                     // per-(n, channel) output scale (stem dropout3d), reloaded when n changes
-    auto flush_stats = [&](int n_) {
-      float u1 = s1, u2 = s2;
-      u1 += __shfl_xor(u1, 16, 64); u1 += __shfl_xor(u1, 32, 64);
-      u2 += __shfl_xor(u2, 16, 64); u2 += __shfl_xor(u2, 32, 64);
-      if (kq == 0 && r < g.Cout) {
-        atomic_add_f64(a.stats + ((int64_t)n_ * g.Cout + r) * 2 + 0, (double)u1);
-        atomic_add_f64(a.stats + ((int64_t)n_ * g.Cout + r) * 2 + 1, (double)u2);
-      }
-      s1 = 0.f; s2 = 0.f;
-    };
-    // every load issued so far (weights, bias) is complete before the loop: the only VMEM traffic of the loop are the
-    // epilogue's stores, which are never waited for (an s_waitcnt vmcnt(0) at the loop head would expose their latency)
-    __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0), expcnt/lgkmcnt untouched
-
-    if (DIAG && (a.diag_mode & 32)) __builtin_amdgcn_s_setprio(1);
-    // Deferred epilogue: the common case (interior tile, no residual, no output scale) is not written out after its MFMA
-    // phase but DURING the next tile's (one element -- a store and two statistics FMAs -- after each of the first 16 MFMA
-    // triples), where those ~50 vector instructions cost issue slots only; done serially they cost ~2k cycles per tile,
-    // because the loader wave of the SIMD is converting at the same time.
-    f32x4 prev[4];                                       // accumulators of the deferred tile
-    float* prev_yb = nullptr;                            // its output base (uniform)
-    int pend = 0;                                        // 0 = nothing deferred, 1 = deferred with statistics, 2 = without
-    auto drain = [&](auto HT) {                          // non-interleaved form (after the last tile)
-      constexpr bool HAS_STATS = decltype(HT)::value;
-      unsigned yo[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { yo[i] = yofs[i]; asm volatile("" : "+v"(yo[i])); }
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        char* ybm = reinterpret_cast<char*>(prev_yb + (int64_t)m * g.Wo * g.y_ldc);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float v = prev[m][i];
-          if (!(DIAG && (a.diag_mode & 1))) *reinterpret_cast<float*>(ybm + yo[i]) = v;
-          if (HAS_STATS) { s1 += v; s2 = fmaf(v, v, s2); }
-        }
-      }
-    };
-    unsigned long long d_bar = 0, d_mfma = 0, d_epi = 0;
-    for (int it = 0; it < niter; ++it) {
-      const int tile = first + it * per;
-      CWF_STAMP(t0);
-      // Raw barrier: __syncthreads() would add s_waitcnt vmcnt(0) and make this wave wait for its own output stores.
-      asm volatile("s_barrier" ::: "memory");            // buffer it&1 is complete
-      CWF_STAMP(t1);
-      f32x4 acc[4];
-      // A fragments are double-buffered in registers: the 8 LDS reads of tap pair s+1 are issued BEFORE the 12 MFMAs of
-      // pair s (one MFMA wave per SIMD: nothing else hides the LDS latency).  sched_barrier pins that order.
-      u32x4_t fa[2][4], fl[2][4]; uint4 fb[2];
-      auto load_step = [&](int s_, int b_) {
-        if (X3) fb[b_] = wl[s_ * 64];
-        const int ta = c16_tap(2 * s_);                      // natural index of the step's first tap (second: +kw / +kd / +kh)
-        const int oa = (((ta / 9) * C16_IH + (ta / 3) % 3) * C16_IW + ta % 3) * 32;
-        const int cls = s_ < 9 ? 0 : s_ < 12 ? 2 : s_ == 12 ? 1 : 3;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          fa[b_][m] = *(lds_u4p)(uintptr_t)(ab[cls][m] + (unsigned)oa);
-          if (X3) fl[b_][m] = *(lds_u4p)(uintptr_t)(ab[cls][m] + (unsigned)(oa + IMG * 2));
-        }
-      };
-      auto phase = [&](auto PEND_) {
-        constexpr int PEND = decltype(PEND_)::value;
-        unsigned yo[4];
-        if (PEND) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { yo[i] = yofs[i]; asm volatile("" : "+v"(yo[i])); }     // see the epilogue: keeps the saddr form
-        }
-        load_step(0, 0);
-#pragma unroll
-        for (int s = 0; s < 14; ++s) {
-          if (s + 1 < 14) load_step(s + 1, (s + 1) & 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[s & 1][m]), __builtin_bit_cast(bf16x8, bh[s]), s == 0 ? bias4 : acc[m], 0, 0, 0);
-            if (X3) {
-              acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[s & 1][m]), __builtin_bit_cast(bf16x8, fb[s & 1]), acc[m], 0, 0, 0);
-              acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fl[s & 1][m]), __builtin_bit_cast(bf16x8, bh[s]), acc[m], 0, 0, 0);
-            }
-            if (PEND != 0 && s < 4) {                    // deferred element: output row s of the previous tile, register m
-              char* ybm = reinterpret_cast<char*>(prev_yb + (int64_t)s * g.Wo * g.y_ldc);
-              const float v = prev[s][m];
-              if (!(DIAG && (a.diag_mode & 1))) *reinterpret_cast<float*>(ybm + yo[m]) = v;
-              if (PEND == 1) { s1 += v; s2 = fmaf(v, v, s2); }
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      };
-      if (pend == 0) phase(std::integral_constant<int, 0>{});
-      else if (pend == 1) phase(std::integral_constant<int, 1>{});
-      else phase(std::integral_constant<int, 2>{});
-      pend = 0;
-      // the other buffer is read next: toggle the parity of the 16 base addresses
-      {
-        const unsigned dlt = (it & 1) ? (unsigned)(-(BUF * 2)) : (unsigned)(BUF * 2);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int m = 0; m < 4; ++m) ab[c][m] += dlt;
-      }
-      CWF_STAMP(t2);
-      // ---- epilogue.  (A variant that transposes the accumulators through LDS and stores one contiguous 1 KiB dwordx4 per
-      // M-tile was measured SLOWER.)
-      const int n = tile / tiles_sp; int rem = tile - n * tiles_sp;
-      const int tile_w = rem % g.tiles_w; rem /= g.tiles_w;
-      const int tile_h = rem % g.tiles_h; const int tile_d = rem / g.tiles_h;
-      const int od = tile_d * C16_TD + wave, oh0 = tile_h * C16_TH, ow0 = tile_w * 16;
-      if (a.stats && n != stat_n) { flush_stats(stat_n); stat_n = n; }     // wave-uniform
-      if (od < g.Do && !(DIAG && (a.diag_mode & 8))) {                      // wave-uniform
-        const int64_t vox0 = (((int64_t)n * g.Do + od) * g.Ho + oh0) * g.Wo + ow0;
-        float* yb = a.y + vox0 * g.y_ldc;
-        const float* rb = a.residual ? a.residual + vox0 * a.r_ldc : nullptr;
-        const bool hs = a.out_scale != nullptr;
-        if (hs && n != osc_n) {                                               // rare; its wait must not sit in the tile loop
-          osc = r < g.Cout ? a.out_scale[(int64_t)n * g.Cout + r] : 1.f;
-          asm volatile("" :: "v"(osc));                                      // consume here -> the s_waitcnt lands here
-          osc_n = n;
-        }
-        const bool full = (oh0 + C16_TH <= g.Ho) && (ow0 + 16 <= g.Wo) && g.Cout == 16 && !(hs && rb);     // wave-uniform
-        if (full && !rb && !hs) {
-          // common case: deferred into the next tile's MFMA phase
-#pragma unroll
-          for (int m = 0; m < 4; ++m) prev[m] = acc[m];
-          prev_yb = yb; pend = a.stats ? 1 : 2;
-        } else if (full) {
-          // branch-free fast path (interior tiles, 16 output channels), specialised on the wave-uniform options so that
-          // an element costs its store + 2 statistics FMAs: 16 stores at SGPR-base + 32-bit lane-offset addresses.
-          // Without a residual the loop issues no loads, so nothing ever waits for the stores (vmcnt is in-order).
-          if (hs) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m) acc[m] *= osc;
-          }
-          auto epi = [&](auto HR, auto HT) {
-            constexpr bool HAS_RES = decltype(HR)::value, HAS_STATS = decltype(HT)::value;
-            // The 32-bit lane offsets are made opaque HERE so that their zero-extension stays in this basic block: only then
-            // does instruction selection see "SGPR base + zext(VGPR)" and emit the saddr form (no 64-bit address VALU).
-            unsigned yo[4], ro[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { yo[i] = yofs[i]; asm volatile("" : "+v"(yo[i])); if (HAS_RES) { ro[i] = rofs[i]; asm volatile("" : "+v"(ro[i])); } }
-            float rv[4][4];
-            if (HAS_RES) {
-#pragma unroll
-              for (int m = 0; m < 4; ++m) {
-                const char* rbm = reinterpret_cast<const char*>(rb + (int64_t)m * g.Wo * a.r_ldc);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) rv[m][i] = *reinterpret_cast<const float*>(rbm + ro[i]);
-              }
-            }
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-              char* ybm = reinterpret_cast<char*>(yb + (int64_t)m * g.Wo * g.y_ldc);
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                float v = acc[m][i];
-                if (HAS_RES) v += rv[m][i];
-                if (!(DIAG && (a.diag_mode & 1))) *reinterpret_cast<float*>(ybm + yo[i]) = v;
-                if (HAS_STATS) { s1 += v; s2 = fmaf(v, v, s2); }
-              }
-            }
-          };
-          using T_ = std::true_type; using F_ = std::false_type;
-          const bool ht = a.stats != nullptr;
-          if (rb) { if (ht) epi(T_{}, T_{}); else epi(T_{}, F_{}); }
-          else    { if (ht) epi(F_{}, T_{}); else epi(F_{}, F_{}); }
-        } else {
-#pragma unroll
-          for (int m = 0; m < 4; ++m) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const bool ok = r < g.Cout && oh0 + m < g.Ho && ow0 + kq * 4 + i < g.Wo;
-              if (!ok) continue;
-              const int eo = m * g.Wo;
-              float v = acc[m][i];
-              if (rb) v += rb[eo * a.r_ldc + (rofs[i] >> 2)];
-              v *= osc;
-              yb[eo * g.y_ldc + (yofs[i] >> 2)] = v;
-              s1 += v; s2 += v * v;
-            }
-          }
-        }
-      }
-      CWF_STAMP(t3);
-      if (DIAG) { d_bar += t1 - t0; d_mfma += t2 - t1; d_epi += t3 - t2; if (a.diag_mode & 8) { s1 += acc[0][0] + acc[1][1] + acc[2][2] + acc[3][3]; } }
-    }
-    if (pend == 1) drain(std::true_type{}); else if (pend == 2) drain(std::false_type{});
-    if (a.stats) flush_stats(stat_n);
-    if (DIAG && a.diag && lane == 0) {
-      unsigned long long* o = a.diag + ((int64_t)blockIdx.x * 8 + wave) * 4;
-      o[0] = d_bar; o[1] = d_mfma; o[2] = d_epi; o[3] = 0;
-    }
-  } else {
-    // =============================================================== loader waves
-    const int lt = tid - 256;                            // 0..255
-    const int q = lt & 3;
-    const int c = q * 4;
-    const bool cval = c < g.Cin;
-    const bool has_norm = a.in_scale != nullptr;
-    const float slope = a.in_slope;
-    const int HW = g.Hi * g.Wi;
-    int rel[C16_SLOTS];
-#pragma unroll
-    for (int i = 0; i < C16_SLOTS; ++i) {
-      const int v = (lt >> 2) + 64 * i;
-      const int iw = v % C16_IW, t2 = v / C16_IW;
-      const int ih = t2 % C16_IH, idd = t2 / C16_IH;
-      rel[i] = (idd * HW + ih * g.Wi + iw) * g.x_ldc + c;
-    }
-    const bool last_slot_ok = (lt >> 2) + 64 * (C16_SLOTS - 1) < C16_NVOX;
-    // Two tiles of loads are kept in flight in two register sets (2 x 11 float4): the ~4 us latency of this halo access
-    // pattern exceeds one tile time (measured: with a one-tile distance the tile time equilibrates at the latency).
-    // Everything below is STRAIGHT-LINE per tile (out-of-range slots load a dummy address and are zeroed by a select): any
-    // per-slot branch makes the compiler fall back from counted s_waitcnt vmcnt(N) to vmcnt(0), which serialises the pipeline.
-    float4 pre[2][C16_SLOTS];
-    unsigned pre_inb[2] = {0u, 0u};
-    if (!(DIAG && (a.diag_mode & 16))) __builtin_amdgcn_s_setprio(1);   // loaders are the critical path: win VALU/VMEM issue arbitration
-    struct TileOrg { const float* base; bool interior; int id0, ih0, iw0, n; };
-    auto origin = [&](int tile) {
-      TileOrg o;
-      o.n = tile / tiles_sp; int rem = tile - o.n * tiles_sp;
-      const int tile_w = rem % g.tiles_w; rem /= g.tiles_w;
-      const int tile_h = rem % g.tiles_h; const int tile_d = rem / g.tiles_h;
-      o.id0 = tile_d * C16_TD - 1; o.ih0 = tile_h * C16_TH - 1; o.iw0 = tile_w * 16 - 1;
-      o.base = a.x + ((((int64_t)o.n * g.Di + o.id0) * g.Hi + o.ih0) * g.Wi + o.iw0) * g.x_ldc;
-      o.interior = o.id0 >= 0 && o.id0 + C16_ID <= g.Di && o.ih0 >= 0 && o.ih0 + C16_IH <= g.Hi && o.iw0 >= 0 && o.iw0 + C16_IW <= g.Wi;
-      return o;
-    };
-    const bool lane_ok = cval && !(DIAG && (a.diag_mode & 2));
-    // issue the 11 loads of tile `o` into register set S; returns the in-bounds mask.  No branches inside.
-    auto issue = [&](const TileOrg& o, auto S) -> unsigned {
-      constexpr int SET = decltype(S)::value;
-      unsigned inb = 0;
-      if (o.interior) {                                  // wave-uniform; both arms are straight-line
-#pragma unroll
-        for (int i = 0; i < C16_SLOTS; ++i) {
-          if (DIAG && (a.diag_mode & 4) && i >= 7) continue;
-          const bool ok = lane_ok && (i < C16_SLOTS - 1 || last_slot_ok);
-          const float* p = ok ? o.base + rel[i] : a.x;
-          pre[SET][i] = *reinterpret_cast<const float4*>(p);
-          inb |= ok ? (1u << i) : 0u;
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < C16_SLOTS; ++i) {
-          const int v = (lt >> 2) + 64 * i;
-          const int iw = v % C16_IW, t2 = v / C16_IW;
-          const int ih = t2 % C16_IH, idd = t2 / C16_IH;
-          const int gd = o.id0 + idd, gh = o.ih0 + ih, gw = o.iw0 + iw;
-          const bool ok = lane_ok && (i < C16_SLOTS - 1 || last_slot_ok) &&
-                          (unsigned)gd < (unsigned)g.Di && (unsigned)gh < (unsigned)g.Hi && (unsigned)gw < (unsigned)g.Wi;
-          const float* p = ok ? o.base + rel[i] : a.x;
-          pre[SET][i] = *reinterpret_cast<const float4*>(p);
-          inb |= ok ? (1u << i) : 0u;
-        }
-      }
-      return inb;
-    };
-    // convert register set S (tile tc) into LDS buffer `buf`.  Specialised on two wave-uniform facts so that the common case
-    // (interior tile, all 16 channels) carries no per-value selects: PLAIN = no norm/activation prologue (data gradients),
-    // ALLIN = every slot of every lane of this wave was in bounds.  ~22 vector instructions per float4 instead of 34.
-    const unsigned full_mask = last_slot_ok ? ((1u << C16_SLOTS) - 1u) : ((1u << (C16_SLOTS - 1)) - 1u);
-    const bool plain = !has_norm && slope == 1.f;
-    auto convert = [&](int tc, int buf, auto S) {
-      constexpr int SET = decltype(S)::value;
-      float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (has_norm && cval) {
-        const int n = tc / tiles_sp;
-        sc = *reinterpret_cast<const float4*>(a.in_scale + (int64_t)n * g.Cin + c);
-        sh = *reinterpret_cast<const float4*>(a.in_shift + (int64_t)n * g.Cin + c);
-      }
-      const float sl = slope;
-      const unsigned inb = pre_inb[SET];
-      unsigned short* dh = lds + buf * BUF + (lt >> 2) * 16 + q * 4;
-      unsigned short* dl = dh + IMG;
-      auto body = [&](auto PL, auto AI) {
-        constexpr bool PLAIN = decltype(PL)::value, ALLIN = decltype(AI)::value;
-#pragma unroll
-        for (int i = 0; i < C16_SLOTS; ++i) {
-          if (i == C16_SLOTS - 1 && !last_slot_ok) continue;         // (whole-quad predicate, not per slot: cheap)
-          if (DIAG && (a.diag_mode & 4) && i >= 7) continue;
-          const float4 val = pre[SET][i];
-          float v0 = val.x, v1 = val.y, v2 = val.z, v3 = val.w;
-          if (!PLAIN) {
-            v0 = act01(fmaf(v0, sc.x, sh.x), sl); v1 = act01(fmaf(v1, sc.y, sh.y), sl);
-            v2 = act01(fmaf(v2, sc.z, sh.z), sl); v3 = act01(fmaf(v3, sc.w, sh.w), sl);
-          }
-          uint2 h, l;
-          if (X3) { split_bf16(v0, v1, h.x, l.x); split_bf16(v2, v3, h.y, l.y); }
-          else { h.x = pack_bf16(v0, v1); h.y = pack_bf16(v2, v3); }
-          if (!ALLIN) {
-            // zero padding is applied AFTER the activation: out-of-range voxels are exactly 0 in both images
-            const bool was = (inb >> i) & 1u;
-            h.x = was ? h.x : 0u; h.y = was ? h.y : 0u;
-            if (X3) { l.x = was ? l.x : 0u; l.y = was ? l.y : 0u; }
-          }
-          *reinterpret_cast<uint2*>(dh + i * 64 * 16) = h;
-          if (X3) *reinterpret_cast<uint2*>(dl + i * 64 * 16) = l;
-        }
-      };
-      using T_ = std::true_type; using F_ = std::false_type;
-      const bool allin = __ballot(inb != full_mask) == 0ull;          // wave-uniform
-      if (plain) { if (allin) body(T_{}, T_{}); else body(T_{}, F_{}); }
-      else       { if (allin) body(F_{}, T_{}); else body(F_{}, F_{}); }
-    };
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, 1>;
-    unsigned long long d_bar = 0, d_commit = 0;
-    // prologue: tile 0 -> set 0 -> LDS buffer 0; then tiles 1 (set 1) and 2 (set 0) in flight
-    pre_inb[0] = issue(origin(first), S0{});
-    convert(first, 0, S0{});
-    if (niter > 1) pre_inb[1] = issue(origin(first + per), S1{});
-    if (niter > 2) pre_inb[0] = issue(origin(first + 2 * per), S0{});
-    // iteration it: tile it+1 sits in set (it+1)&1 -> LDS buffer (it+1)&1; that set is then refilled with tile it+3
-    for (int it = 0; it < niter; ++it) {
-      CWF_STAMP(t0);
-      // LDS writes done -> barrier.  Raw form: __syncthreads() would also wait (vmcnt(0)) for the prefetches in flight.
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // buffer it&1 handed over; buffer (it+1)&1 is free
-      CWF_STAMP(t1);
-      if (it + 1 < niter) {
-        if ((it + 1) & 1) {
-          convert(first + (it + 1) * per, 1, S1{});
-          if (it + 3 < niter) pre_inb[1] = issue(origin(first + (it + 3) * per), S1{});
-        } else {
-          convert(first + (it + 1) * per, 0, S0{});
-          if (it + 3 < niter) pre_inb[0] = issue(origin(first + (it + 3) * per), S0{});
-        }
-      }
-      if (DIAG) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      CWF_STAMP(t2);
-      if (DIAG) { d_bar += t1 - t0; d_commit += t2 - t1; }
-    }
-    if (DIAG && a.diag && lane == 0) {
-      unsigned long long* o = a.diag + ((int64_t)blockIdx.x * 8 + wave) * 4;
-      o[0] = d_bar; o[1] = 0; o[2] = d_commit; o[3] = 0;
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------
-// conv16s: conv16 with a SLIDING WINDOW along H.  A workgroup walks a column of 4x4x16 tiles (fixed n, tile_d, tile_w,
+// conv16s: the conv16 scheme above with a SLIDING WINDOW along H.  A workgroup walks a column of 4x4x16 tiles (fixed n, tile_d, tile_w,
 // increasing tile_h); the halo rows two neighbouring tiles share stay in LDS, so a tile stages 4 new rows per plane
 // (7 staging slots per loader thread) instead of 6 (11 slots): the loader waves -- the longer of the kernel's two per-tile
 // chains -- do 36 % less work (loads, converts, LDS writes).  LDS holds, per plane, a RING of 12 rows:
@@ -827,19 +417,17 @@ __global__ __launch_bounds__(512) void conv16_kernel(const ConvArgsB a, int tota
 // by a loader-only "pre-tile" (element e = 0) that stages rows -2..1 exactly like any other 4-row block (the MFMA waves only
 // pass its barrier), so the ring simply keeps turning across segments and the loader has no special case at all
 // (cost: one extra 4-row block per segment, ~3 % at 128^3).  Elements u = 0, 1, 2, ... of a workgroup: new rows -> group u % 3.
-// Everything else (weights in registers, deferred epilogue, statistics in registers, XCD-aware work order) is conv16_kernel's.
 // ---------------------------------------------------------------------------------------------------
 #define C16_RH 12
 #define C16S_SLOTS 7                                     // ceil(6 planes * 4 rows * 18 / 64)
 #define C16S_HSLOTS 4                                    // ceil(6 planes * 2 rows * 18 / 64)
 
 struct C16sWork { int nseg, seg_len, hsplit, ncols; };
-static int g_conv16_diag_mode = 0;                   // diagnostics (cwf_debug_conv16_mode): 1 no stores, 2 no loads, 8 no epilogue
 
 // IN16 = true (single-bf16 data-gradient launches whose input gradient exists as a bf16 image, [N][D][H][W][16]): the loader waves
 // convert nothing -- they issue LDS-DMA pieces (global_load_lds_dwordx4, 1 KiB of LDS each; zero padding = a 16-byte zero page) and the
 // ring has FOUR row groups per plane (16 rows) so that two elements stay in flight while a tile reads one and a half groups.
-template <bool X3, bool DIAG, bool IN16 = false>
+template <bool X3, bool IN16 = false>
 __global__ __launch_bounds__(512) void conv16s_kernel(const ConvArgsB a, const C16sWork wk) {
   static_assert(!(IN16 && X3), "the bf16 input image is a single-bf16 operand");
   constexpr int RH = IN16 ? 16 : C16_RH;               // ring rows per plane
@@ -915,7 +503,7 @@ __global__ __launch_bounds__(512) void conv16s_kernel(const ConvArgsB a, const C
     };
     __builtin_amdgcn_s_waitcnt(0x0F70);                  // prologue loads done: the loop's stores are never waited for
 
-    f32x4 prev[4]; float* prev_yb = nullptr; int pend = 0;               // deferred epilogue (see conv16_kernel)
+    f32x4 prev[4]; float* prev_yb = nullptr; int pend = 0;               // deferred epilogue (see conv16 above)
     auto drain = [&](auto HT) __attribute__((always_inline)) {
       constexpr bool HAS_STATS = decltype(HT)::value;
       unsigned yo[4];
@@ -1001,7 +589,7 @@ __global__ __launch_bounds__(512) void conv16s_kernel(const ConvArgsB a, const C
       const int n = sg.n;
       const int od = sg.tile_d * C16_TD + wave, oh0 = (sg.th0 + t) * C16_TH, ow0 = sg.tile_w * 16;
       if (a.stats && n != stat_n) { flush_stats(stat_n); stat_n = n; }
-      if (od < g.Do && !(DIAG && (a.diag_mode & 8))) {     // diag_mode 8: no epilogue (DIAG build only)
+      if (od < g.Do) {
         const int64_t vox0 = (((int64_t)n * g.Do + od) * g.Ho + oh0) * g.Wo + ow0;
         float* yb = a.y + vox0 * g.y_ldc;
         const float* rb = a.residual ? a.residual + vox0 * a.r_ldc : nullptr;
@@ -1168,7 +756,7 @@ __global__ __launch_bounds__(512) void conv16s_kernel(const ConvArgsB a, const C
     // =============================================================== loader waves
     const int lt = tid - 256;
     const int q = lt & 3, c = q * 4;
-    const bool cval = c < g.Cin && !(DIAG && (a.diag_mode & 2));   // diag_mode 2: no loads (DIAG build only)
+    const bool cval = c < g.Cin;
     const bool has_norm = a.in_scale != nullptr;
     const float slope = a.in_slope;
     const bool plain = !has_norm && slope == 1.f;
@@ -1278,7 +866,7 @@ __global__ __launch_bounds__(512) void conv16s_kernel(const ConvArgsB a, const C
       else convert(S, std::integral_constant<int, 2>{});
     };
     // Flattened element sequence of this workgroup; element number `it` uses register set it & 1 and two elements of loads are
-    // in flight (three sets in flight measured SLOWER: 0.265 vs 0.247 ms).  Same straight-line shape as conv16_kernel's loader
+    // in flight (three sets in flight measured SLOWER: 0.265 vs 0.247 ms).  Straight-line per element
     // (each parity arm converts one set, then refills that same set) so that the compiler keeps counted s_waitcnt vmcnt(N).
     int niter = 0;
     for (int k = 0; k < nk; ++k) niter += seg_of(k).len + 1;
@@ -1316,37 +904,10 @@ static int launch_conv16s(const ConvArgsB& a, hipStream_t st) {
   const size_t lds = IN16 ? (size_t)C16_ID * 16 * C16_IW * 32                                    // hi ring of 16 rows
                           : (size_t)2 * C16_ID * C16_RH * C16_IW * 32 + (X3 ? 14 * 64 * 16 : 0);   // hi + lo rings (+ lo weights)
   int grid = 256; while (grid > 8 && grid > wk.nseg) grid -= 8;
-  ConvArgsB aa = a; aa.diag = nullptr; aa.diag_mode = g_conv16_diag_mode;
-  // the product kernel has no diagnostic branches; cwf_debug_conv16_mode (tools/) selects the ablation instantiation
-  auto go = [&](auto D) {
-    constexpr bool DG = decltype(D)::value;
-    CWF_MAX_LDS_ONCE((&conv16s_kernel<X3, DG, IN16>));
-    hipLaunchKernelGGL((conv16s_kernel<X3, DG, IN16>), dim3(grid), dim3(512), lds, st, aa, wk);
-  };
-  if (g_conv16_diag_mode && !IN16) go(std::true_type{}); else go(std::false_type{});
+  CWF_MAX_LDS_ONCE((&conv16s_kernel<X3, IN16>));
+  hipLaunchKernelGGL((conv16s_kernel<X3, IN16>), dim3(grid), dim3(512), lds, st, a, wk);
   CWF_LAUNCH_CHECK();
   return 0;
-}
-
-static unsigned long long* g_conv16_diag = nullptr;
-extern "C" void cwf_debug_conv16_diag(unsigned long long* buf) { g_conv16_diag = buf; }
-extern "C" void cwf_debug_conv16_mode(int m) { g_conv16_diag_mode = m; }   // diagnostic builds: 1 = no stores, 2 = no loads   // [256][8][4] u64, or NULL = off
-
-template <bool X3, bool DIAG>
-static int launch_conv16_impl(ConvArgsB a, hipStream_t st) {
-  const ConvGeom& g = a.g;
-  const int total = g.N * g.tiles_d * g.tiles_h * g.tiles_w;
-  const size_t lds = (size_t)2 * C16_NVOX * 16 * sizeof(unsigned short) * (X3 ? 2 : 1) + (X3 ? 14 * 64 * 16 : 0);
-  CWF_MAX_LDS_ONCE((&conv16_kernel<X3, DIAG>));
-  a.diag = DIAG ? g_conv16_diag : nullptr; a.diag_mode = g_conv16_diag_mode;
-  int grid = 256; while (grid > 8 && grid > total) grid -= 8;   // one 8-wave workgroup per CU; multiple of 8 (XCD map)
-  hipLaunchKernelGGL((conv16_kernel<X3, DIAG>), dim3(grid), dim3(512), lds, st, a, total);
-  CWF_LAUNCH_CHECK();
-  return 0;
-}
-template <bool X3>
-static int launch_conv16(const ConvArgsB& a, hipStream_t st) {
-  return g_conv16_diag ? launch_conv16_impl<X3, true>(a, st) : launch_conv16_impl<X3, false>(a, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1567,8 +1128,6 @@ static int launch_pw(const ConvArgsB& a, hipStream_t st) {
 static bool pw_eligible(int op, const ConvArgsB& a, int* ks, int* nt) {
   const ConvGeom& g = a.g;
   if (op != CWF_CONV1 && op != CWF_CONVT2) return false;
-  static const bool off = getenv("CWF_NO_POINTWISE") != nullptr;          // A/B switch (diagnostics)
-  if (off) return false;
   const int64_t Vin = (int64_t)g.Di * g.Hi * g.Wi;
   if ((Vin & 15) || Vin * (g.x_ldc > g.y_ldc * 8 ? g.x_ldc : g.y_ldc * 8) >= (1ll << 31)) return false;
   if ((g.Cout & 3) || (g.y_ldc & 3) || ((uintptr_t)a.y & 15)) return false;
@@ -1768,7 +1327,7 @@ static int cfg_extent(int op, int Di, int Hi, int Wi, int Do, int Ho, int Wo, in
 }
 
 // Read-only query (tests): the tile configuration {MT, NT, WM} that conv_bf16_impl's choose_cfg picks for a launch of `op` from input
-// extent Di x Hi x Wi to output extent Do x Ho x Wo (no CWF_FORCE_CFG).  Whether the launch reaches the tap-table kernel at all (pointwise,
+// extent Di x Hi x Wi to output extent Do x Ho x Wo.  Whether the launch reaches the tap-table kernel at all (pointwise,
 // weight-stationary, conv16 routes) is not decided here.  Launches nothing.
 extern "C" int cwf_debug_conv_bf16_cfg(int op, int N, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cout, int* mt_nt_wm) {
   if (!mt_nt_wm || N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || op < CWF_CONV3_S1 ||
@@ -1795,18 +1354,12 @@ static int conv_bf16_impl(int op, int x3, const float* x, int x_ldc, const void*
   ConvArgsB a;
   int cd[3];
   const int ncls = cfg_extent(op, Di, Hi, Wi, Do, Ho, Wo, cd);
-  TileCfg c = choose_cfg(op, cd, ncls, N, cdiv(Cout, 16));
-  {                                                    // tuning aid: CWF_FORCE_CFG="MT,NT,WM" overrides the tile choice
-    static const char* force = getenv("CWF_FORCE_CFG");
-    int fm, fn, fw;
-    if (force && sscanf(force, "%d,%d,%d", &fm, &fn, &fw) == 3) { c.MT = fm; c.NT = fn; c.WM = fw; }
-  }
+  const TileCfg c = choose_cfg(op, cd, ncls, N, cdiv(Cout, 16));
   int rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, c.MT * c.WM);
   if (rc) return rc;
   a.x = x; a.wpk = reinterpret_cast<const uint4*>(wpk16); a.bias = bias; a.y = y; a.in_scale = in_scale; a.in_shift = in_shift;
   a.in_slope = in_slope; a.residual = residual; a.r_ldc = r_ldc; a.out_scale = out_scale; a.stats = stats;
   a.nb_x = nb_x; a.nb_ldc = nb_ldc; a.nb_scale = nb_scale; a.nb_shift = nb_shift; a.nb_slope = nb_slope;
-  a.diag = nullptr; a.diag_mode = 0;
   a.groups = 0; a.x_goff = 0; a.y_goff = 0;
   a.x16 = reinterpret_cast<const uint4*>(x16); a.zero16 = reinterpret_cast<const uint4*>(zero16);
   a.y16 = reinterpret_cast<unsigned short*>(y16);
@@ -1841,10 +1394,7 @@ static int conv_bf16_impl(int op, int x3, const float* x, int x_ldc, const void*
     // full-resolution 16-channel convs: the persistent register-resident-weight kernel (tile 4x4x16)
     rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, 16);
     if (rc) return rc;
-    // sliding-window kernel by default; CWF_CONV16_NOSLIDE=1 selects the double-buffered full-halo kernel (A/B, diagnostics)
-    static const bool noslide = getenv("CWF_CONV16_NOSLIDE") != nullptr;
-    if ((!noslide && !g_conv16_diag) || nb_x) return x3 ? launch_conv16s<true>(a, st) : launch_conv16s<false>(a, st);   // (conv16 has no nb epilogue)
-    return x3 ? launch_conv16<true>(a, st) : launch_conv16<false>(a, st);
+    return x3 ? launch_conv16s<true>(a, st) : launch_conv16s<false>(a, st);
   }
 #define CWF_CFG(mt, nt, wm) if (c.MT == mt && c.NT == nt && c.WM == wm) return x3 ? launch_cfg<mt, nt, wm, true>(a, st) : launch_cfg<mt, nt, wm, false>(a, st);
   CWF_CFG(4, 4, 1) CWF_CFG(2, 4, 2) CWF_CFG(2, 4, 4) CWF_CFG(4, 2, 4) CWF_CFG(4, 1, 4)
@@ -1872,7 +1422,6 @@ extern "C" int cwf_conv_mfma_bf16_grouped(int op, int x3, const float* x, int x_
   a.x = x; a.wpk = nullptr; a.bias = nullptr; a.y = y; a.in_scale = nullptr; a.in_shift = nullptr; a.in_slope = 1.f;
   a.residual = nullptr; a.r_ldc = 0; a.out_scale = nullptr; a.stats = nullptr;
   a.nb_x = nullptr; a.nb_ldc = 0; a.nb_scale = nullptr; a.nb_shift = nullptr; a.nb_slope = 1.f;
-  a.diag = nullptr; a.diag_mode = 0;
   a.groups = groups; a.x_goff = x_goff; a.y_goff = y_goff;
   a.x16 = nullptr; a.zero16 = nullptr; a.y16 = nullptr;
   for (int q = 0; q < 3; ++q) {

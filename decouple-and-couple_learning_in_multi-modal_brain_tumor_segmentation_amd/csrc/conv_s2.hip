@@ -226,8 +226,7 @@ extern "C" int cwf_conv_s2c16_bf16(int x3, const float* x, int x_ldc, const floa
   a.N = N; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Do = (Di + 1) / 2; a.Ho = (Hi + 1) / 2; a.Wo = (Wi + 1) / 2;
   a.tiles_d = cdiv(a.Do, 2); a.tiles_h = cdiv(a.Ho, 2); a.tiles_w = cdiv(a.Wo, 16);
   a.total_tiles = N * a.tiles_d * a.tiles_h * a.tiles_w;
-  static const int g0 = getenv("CWF_S2_GRID") ? atoi(getenv("CWF_S2_GRID")) : 256;
-  int grid = g0; if (grid > a.total_tiles) grid = a.total_tiles;
+  int grid = 256; if (grid > a.total_tiles) grid = a.total_tiles;
   a.tiles_per_wg = cdiv(a.total_tiles, grid);
   grid = cdiv(a.total_tiles, a.tiles_per_wg);
   const size_t lds = (size_t)2 * (x3 ? 2 : 1) * S2_IMG * 2 + (x3 ? 14 * 2 * 64 * 16 : 0) + 4 * 64 * sizeof(float);      // two image buffers

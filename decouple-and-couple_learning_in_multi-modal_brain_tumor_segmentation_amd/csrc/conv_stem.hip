@@ -199,8 +199,8 @@ extern "C" int cwf_conv_stem_bf16(int x3, const float* x, int x_ldc, const float
   a.N = N; a.D = D; a.H = H; a.W = W;
   a.tiles_d = cdiv(D, 4); a.tiles_h = cdiv(H, 4); a.tiles_w = cdiv(W, 16);
   a.total_tiles = N * a.tiles_d * a.tiles_h * a.tiles_w;
-  static const int g0 = getenv("CWF_STEM_GRID") ? atoi(getenv("CWF_STEM_GRID")) : 1024;      // (512 / 1024 / 2048 / 4096 workgroups: 108 / 110 / 121 / 131 us)
-  int grid = g0; if (grid > a.total_tiles) grid = a.total_tiles;
+  int grid = 1024;                                  // (512 / 1024 / 2048 / 4096 workgroups: 108 / 110 / 121 / 131 us)
+  if (grid > a.total_tiles) grid = a.total_tiles;
   a.tiles_per_wg = cdiv(a.total_tiles, grid);
   grid = cdiv(a.total_tiles, a.tiles_per_wg);
   if (x3) hipLaunchKernelGGL(stem_conv_kernel<true>, dim3(grid), dim3(256), 0, cwf_stream(stream), a);

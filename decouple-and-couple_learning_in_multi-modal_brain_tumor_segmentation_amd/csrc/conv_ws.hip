@@ -29,12 +29,11 @@
 #define WS_SLOTS 11                          // staging slots per thread of a group: 648 voxels x 4 channel quads / 256 threads
 #define WS_NT 2                              // output-channel tiles (of 16) per workgroup
 
-// diag: ablation bits of the DIAG build (CWF_WS_DIAG): 1 no loads, 2 no MFMA phase, 4 no epilogue, 8 no convert
-struct WsWork { int ngroups, slots, tiles, xcd_perm, diag; };
+struct WsWork { int ngroups, slots, tiles, xcd_perm; };
 
 __host__ __device__ constexpr int ws_tap_bytes(int t) { return (((t / 9) * WS_IH + (t / 3) % 3) * WS_IW + t % 3) * 32; }
 
-template <bool X3, bool DIAG>
+template <bool X3>
 __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const WsWork wk) {
   constexpr int NT = WS_NT;
   constexpr int T = 1;                                     // tiles per group and round (two per group do not fit the register file beside the prefetch)
@@ -288,62 +287,60 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
     const char* bl = Bl + b_lane;
     const char* ah0 = Ah + a_lane;
     const char* al0 = Al + a_lane;
-    if (!(DIAG && (wk.diag & 2))) {
-      // Fragment reads are pipelined by hand; the scheduling barrier per step keeps hipcc from hoisting further steps' reads on top
-      // (three steps of split-bf16 fragments in flight spilled registers).  The hi fragments of step s + 1 are requested before the
-      // MFMAs of step s (two named sets); the lo fragments of step s are requested at the head of step s and first used by its
-      // ninth MFMA (one set): per accumulator the order stays hi.hi, hi.lo, lo.hi.
-      uint4 fa[2][4], fb[2][NT], fl[4], fbl[NT];
-      auto rd_hi = [&](auto S, auto P) {
-        constexpr int s = decltype(S)::value, p = decltype(P)::value;
-        constexpr int c0 = ws_tap_bytes(2 * s), c1 = ws_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);   // padded tap: zero weights, valid address
-        const int to = second ? c1 : c0;
+    // Fragment reads are pipelined by hand; the scheduling barrier per step keeps hipcc from hoisting further steps' reads on top
+    // (three steps of split-bf16 fragments in flight spilled registers).  The hi fragments of step s + 1 are requested before the
+    // MFMAs of step s (two named sets); the lo fragments of step s are requested at the head of step s and first used by its
+    // ninth MFMA (one set): per accumulator the order stays hi.hi, hi.lo, lo.hi.
+    uint4 fa[2][4], fb[2][NT], fl[4], fbl[NT];
+    auto rd_hi = [&](auto S, auto P) {
+      constexpr int s = decltype(S)::value, p = decltype(P)::value;
+      constexpr int c0 = ws_tap_bytes(2 * s), c1 = ws_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);   // padded tap: zero weights, valid address
+      const int to = second ? c1 : c0;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) fa[p][m] = *reinterpret_cast<const uint4*>(ah0 + to + m * (WS_IW * 32));
+      for (int m = 0; m < 4; ++m) fa[p][m] = *reinterpret_cast<const uint4*>(ah0 + to + m * (WS_IW * 32));
 #pragma unroll
-        for (int j = 0; j < NT; ++j) fb[p][j] = *reinterpret_cast<const uint4*>(bh + (s * NT + j) * 1024);
-      };
-      auto rd_lo = [&](auto S) {
-        constexpr int s = decltype(S)::value;
-        constexpr int c0 = ws_tap_bytes(2 * s), c1 = ws_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);
-        const int to = second ? c1 : c0;
+      for (int j = 0; j < NT; ++j) fb[p][j] = *reinterpret_cast<const uint4*>(bh + (s * NT + j) * 1024);
+    };
+    auto rd_lo = [&](auto S) {
+      constexpr int s = decltype(S)::value;
+      constexpr int c0 = ws_tap_bytes(2 * s), c1 = ws_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);
+      const int to = second ? c1 : c0;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) fl[m] = *reinterpret_cast<const uint4*>(al0 + to + m * (WS_IW * 32));
+      for (int m = 0; m < 4; ++m) fl[m] = *reinterpret_cast<const uint4*>(al0 + to + m * (WS_IW * 32));
 #pragma unroll
-        for (int j = 0; j < NT; ++j) fbl[j] = *reinterpret_cast<const uint4*>(bl + (s * NT + j) * 1024);
-      };
-      auto mm = [&](auto P) {
-        constexpr int p = decltype(P)::value;
+      for (int j = 0; j < NT; ++j) fbl[j] = *reinterpret_cast<const uint4*>(bl + (s * NT + j) * 1024);
+    };
+    auto mm = [&](auto P) {
+      constexpr int p = decltype(P)::value;
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+          acc[k][m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[p][m]), __builtin_bit_cast(bf16x8, fb[p][j]), acc[k][m][j], 0, 0, 0);
+      if (X3) {
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
           for (int j = 0; j < NT; ++j)
-            acc[k][m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[p][m]), __builtin_bit_cast(bf16x8, fb[p][j]), acc[k][m][j], 0, 0, 0);
-        if (X3) {
+            acc[k][m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[p][m]), __builtin_bit_cast(bf16x8, fbl[j]), acc[k][m][j], 0, 0, 0);
 #pragma unroll
-          for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < 4; ++m)
 #pragma unroll
-            for (int j = 0; j < NT; ++j)
-              acc[k][m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[p][m]), __builtin_bit_cast(bf16x8, fbl[j]), acc[k][m][j], 0, 0, 0);
-#pragma unroll
-          for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-              acc[k][m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fl[m]), __builtin_bit_cast(bf16x8, fb[p][j]), acc[k][m][j], 0, 0, 0);
-        }
-      };
-      using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
+          for (int j = 0; j < NT; ++j)
+            acc[k][m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fl[m]), __builtin_bit_cast(bf16x8, fb[p][j]), acc[k][m][j], 0, 0, 0);
+      }
+    };
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
 #define WS_IC(v) std::integral_constant<int, (v)>{}
 #define WS_STEP2(S0)                                                                                           \
-      if (X3) rd_lo(WS_IC(S0)); rd_hi(WS_IC((S0) + 1), I1{}); mm(I0{}); __builtin_amdgcn_sched_barrier(0);       \
-      if (X3) rd_lo(WS_IC((S0) + 1)); if ((S0) + 2 < 14) rd_hi(WS_IC((S0) + 2 < 14 ? (S0) + 2 : 13), I0{});      \
-      mm(I1{}); __builtin_amdgcn_sched_barrier(0);
-      rd_hi(I0{}, I0{});
-      WS_STEP2(0) WS_STEP2(2) WS_STEP2(4) WS_STEP2(6) WS_STEP2(8) WS_STEP2(10) WS_STEP2(12)
+    if (X3) rd_lo(WS_IC(S0)); rd_hi(WS_IC((S0) + 1), I1{}); mm(I0{}); __builtin_amdgcn_sched_barrier(0);       \
+    if (X3) rd_lo(WS_IC((S0) + 1)); if ((S0) + 2 < 14) rd_hi(WS_IC((S0) + 2 < 14 ? (S0) + 2 : 13), I0{});      \
+    mm(I1{}); __builtin_amdgcn_sched_barrier(0);
+    rd_hi(I0{}, I0{});
+    WS_STEP2(0) WS_STEP2(2) WS_STEP2(4) WS_STEP2(6) WS_STEP2(8) WS_STEP2(10) WS_STEP2(12)
 #undef WS_STEP2
 #undef WS_IC
-    }
-    if (chunk == nch - 1 && !(DIAG && (wk.diag & 4))) { epilogue(tile, KK); return true; }
+    if (chunk == nch - 1) { epilogue(tile, KK); return true; }
     return false;
   };
   // convert step of item (block, k): the halo prefetched for it -> the group's A image; then the loads of the group's next item
@@ -359,10 +356,9 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
   // The two groups run separate loops with equal barrier counts (3 per block + 1): group 0's weight registers then have no live
   // range through group 1's MFMA code.
   using K0 = std::integral_constant<int, 0>;
-  const bool no_loads = DIAG && (wk.diag & 1), no_conv = DIAG && (wk.diag & 8);
   auto do_issue = [&](int blk) {                           // the halo + prologue parameters of this group's item of block blk
     const int round = blk / nch, tile = item_tile(round, 0);
-    if (tile >= 0 && !no_loads) issue_loads(tile, blk - round * nch);
+    if (tile >= 0) issue_loads(tile, blk - round * nch);
   };
   auto do_convert = [&](int blk, int younger) {           // younger < 0: the loads have been waited for already
     const int round = blk / nch, tile = item_tile(round, 0);
@@ -371,7 +367,7 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
     // (a use of the two parameter vectors on EVERY path: left pending in hipcc's model on the path that never reads them -- no
     // prologue -- it would protect their registers later with a full s_waitcnt vmcnt(0))
     asm volatile("" : "+v"(pf_sc), "+v"(pf_sh));
-    if (!no_conv) convert_write(tile, blk - round * nch, pf_sc, pf_sh);
+    convert_write(tile, blk - round * nch, pf_sc, pf_sh);
   };
   if (n_blocks > 0) {
     // the first item of either group: requested AND waited for before the code of the two groups parts (hipcc hoists the common
@@ -448,40 +444,32 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
 }
 
 namespace {
-template <bool X3, bool DIAG>
-int launch_ws_impl(const ConvArgsB& a, const WsWork& wk, int grid, hipStream_t st) {
+template <bool X3>
+int launch_ws(const ConvArgsB& a, const WsWork& wk, int grid, hipStream_t st) {
   const size_t lds = (size_t)14 * WS_NT * 1024 * (X3 ? 2 : 1) + (size_t)2 * WS_NVOX * 32 * (X3 ? 2 : 1) + 8 * WS_NT * 16 * 2 * sizeof(float) + 64;
   if (lds > 160 * 1024) return CWF_E_TOOLARGE;
-  CWF_MAX_LDS_ONCE((&convws_kernel<X3, DIAG>));
-  hipLaunchKernelGGL((convws_kernel<X3, DIAG>), dim3(grid), dim3(512), lds, st, a, wk);
+  CWF_MAX_LDS_ONCE((&convws_kernel<X3>));
+  hipLaunchKernelGGL((convws_kernel<X3>), dim3(grid), dim3(512), lds, st, a, wk);
   CWF_LAUNCH_CHECK();
   return 0;
 }
-template <bool X3>
-int launch_ws(const ConvArgsB& a, WsWork wk, int grid, hipStream_t st) {
-  static const char* diag = getenv("CWF_WS_DIAG");          // ablation build for profiling; the product kernel has no such branches
-  if (diag) { wk.diag = atoi(diag); return launch_ws_impl<X3, true>(a, wk, grid, st); }
-  wk.diag = 0;
-  return launch_ws_impl<X3, false>(a, wk, grid, st);
-}
 }  // namespace
 
-static int g_ws_min_units = getenv("CWF_WS_MIN_UNITS") ? atoi(getenv("CWF_WS_MIN_UNITS")) : 256;
+static int g_ws_min_units = 256;
 // tests / tools: lower the size threshold so that small shapes reach this kernel too (returns the previous value)
 extern "C" int cwf_debug_ws_min_units(int v) { const int old = g_ws_min_units; g_ws_min_units = v; return old; }
 // The split-bf16 (forward) instantiation is correct and tested but NOT faster than the tap-table kernel (32 ch @ 64^3: 105 us against
 // 101; 64 ch @ 32^3: 51 against 50): the product sends only single-bf16 launches (the data gradients: 62 against 74 us, 31 against
-// 34) here.  CWF_WS_X3=1 / cwf_debug_ws_x3(1) sends the split form here too (tests, experiments).
-static int g_ws_x3 = getenv("CWF_WS_X3") ? atoi(getenv("CWF_WS_X3")) : 0;
+// 34) here.  cwf_debug_ws_x3(1) sends the split form here too (tests, experiments).
+static int g_ws_x3 = 0;
 extern "C" int cwf_debug_ws_x3(int v) { const int old = g_ws_x3; g_ws_x3 = v; return old; }
 
 // Returns 1 and launches if the layer is one this kernel takes (3x3x3 stride 1, Cin a multiple of 16 and >= 32, Cout a multiple of 32,
 // extents multiples of the 4x4x16 tile, no per-channel output scale, enough tiles to occupy the chip); 0 = not eligible (the caller
 // falls through to the tap-table kernel).  The launch status is returned through *rc.
 int cwf_try_conv_ws(int op, int x3, ConvArgsB& a, hipStream_t st, int* rc) {
-  static const bool off = getenv("CWF_NO_CONV_WS") != nullptr;
   const ConvGeom& g = a.g;
-  if (off || op != CWF_CONV3_S1 || a.groups || a.out_scale || (x3 && !g_ws_x3)) return 0;
+  if (op != CWF_CONV3_S1 || a.groups || a.out_scale || (x3 && !g_ws_x3)) return 0;
   if (g.Cin < 32 || (g.Cin & 15) || (g.Cout & 31)) return 0;
   if ((g.Do & 3) || (g.Ho & 3) || (g.Wo & 15)) return 0;
   if (g.x_ldc < g.Cin || (g.x_ldc & 3)) return 0;

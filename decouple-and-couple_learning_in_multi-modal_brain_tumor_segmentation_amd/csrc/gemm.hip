@@ -325,9 +325,8 @@ extern "C" int cwf_gemm_ex(const struct cwf_gemm_args* args, void* stream) {
   for (int z = 0; z < a.ZB && z < 4; ++z)
     if ((a.B_tab[0] && !a.B_tab[z]) || (a.bias_tab[0] && !a.bias_tab[z]) || (a.C_tab[0] && !a.C_tab[z]) || (a.rowsum_tab[0] && !a.rowsum_tab[z])) return CWF_E_BADARG;
   const int64_t wg64 = (int64_t)cdiv(a.N, 64) * cdiv(a.M, 64) * a.ZB * a.ZH;
-  static const bool no_vec = getenv("CWF_GEMM_SCALAR") != nullptr;      // A/B switch: the scalar-load kernel for everything
   bool ak = false, bn = false;
-  if (!no_vec && a.K >= 64 && gemm_vec_ok(a, &ak, &bn)) {
+  if (a.K >= 64 && gemm_vec_ok(a, &ak, &bn)) {
     const bool big = wg64 >= 256;
     dim3 grid(cdiv(a.N, big ? 64 : 32), cdiv(a.M, big ? 64 : 32), a.ZB * a.ZH);
 #define CWF_GV(AKv, BNv) do { if (big) hipLaunchKernelGGL((gemm_mfma_v_kernel<64, 64, 32, AKv, BNv>), grid, dim3(256), 0, cwf_stream(stream), a); \

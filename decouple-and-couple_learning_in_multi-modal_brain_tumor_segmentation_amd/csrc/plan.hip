@@ -4,9 +4,9 @@
 // token selection, device-resident dropout counters.  cwf.trainer captures it ONCE with stream capture (which records every launch
 // of the step -- this library's kernels and the handful of torch fills/copies -- with its arguments and its cross-stream
 // dependencies) and hands the resulting hipGraph_t to cwf_plan_create.  The plan orders the graph's nodes topologically (ties in
-// the order the host issued them), assigns them to a small set of streams along the chains the capture had (the main stream's
-// data-gradient chain, the weight-gradient side stream), and cwf_plan_run re-issues them: one hipModuleLaunchKernel per kernel
-// node, hipEventRecord / hipStreamWaitEvent for the cross-stream edges.  On ROCm 7.2 hipGraphLaunch costs the host ~44 us per
+// the order the host issued them), puts the weight-gradient nodes on a low-priority side stream and everything else on the caller's
+// stream, and cwf_plan_run re-issues them: one hipModuleLaunchKernel per kernel node, hipEventRecord / hipStreamWaitEvent for the
+// cross-stream edges.  On ROCm 7.2 hipGraphLaunch costs the host ~44 us per
 // node of this graph (20.6 ms per step, more than Python's eager enqueue); the plan costs a plain launch per node.
 //
 // Marker nodes (cwf_plan_marker, captured on the communication stream behind the streams it waits for) cut the list into
@@ -27,7 +27,7 @@ namespace {
 __global__ void plan_marker_kernel(int id) { (void)id; }
 
 enum NodeKind { NK_KERNEL = 0, NK_MEMSET = 1, NK_EMPTY = 3, NK_MARKER = 4 };
-const int MAX_STREAMS = 4;
+const int MAX_STREAMS = 2;      // the caller's stream and the weight-gradient stream
 
 struct PlanNode {
     int kind = NK_EMPTY;
@@ -43,11 +43,10 @@ struct PlanNode {
 
 struct Plan {
     std::vector<PlanNode> nodes;          // in issue order
-    std::vector<hipStream_t> owned;       // streams 1.. (stream 0 is the caller's)
+    std::vector<hipStream_t> owned;       // stream 1, if any (stream 0 is the caller's)
     std::vector<hipEvent_t> join_ev;      // one per owned stream
     hipEvent_t start_ev = nullptr;
     int n_streams = 1, n_kernels = 0, n_markers = 0, n_events = 0;
-    int last_on[MAX_STREAMS] = {-1, -1, -1, -1};
 };
 
 char g_detail[256] = "";       // why the last cwf_plan_create refused a graph (cwf_plan_last_error)
@@ -172,23 +171,10 @@ extern "C" int cwf_plan_create(void* graph_, void** out) {
             return CWF_E_TOOLARGE;       // not a step this library captured
         }
     }
-    // ---- chains.  depth[v] = longest path from v to a sink.  A node hands its stream to ONE successor: a successor that has no other
-    // predecessor if there is one (under stream capture the next node of the SAME stream depends on its predecessor alone, whereas a
-    // node of another stream that waited for an event here also depends on that stream's tail), else -- and among several such -- the
-    // one with the largest depth (the main stream's data-gradient chain is by far the longest).  Depth alone is not enough: late in
-    // backward the serialised weight-gradient chain is DEEPER than what is left of the main stream, and handing stream 0 to it split
-    // the main chain over extra streams (4 streams, 33 ms per step instead of 19).  Every other successor continues another
-    // predecessor's stream, takes a side stream whose chain has ended, or opens one.  Any assignment is CORRECT (same-stream edges
-    // are FIFO order, cross-stream edges get an event); the choice only decides what may overlap.
-    std::vector<int> depth(n, 1);
-    for (int i = (int)n - 1; i >= 0; --i) {
-        int u = order[i];
-        for (int v : succ[u]) depth[u] = std::max(depth[u], depth[v] + 1);
-    }
     // The weight-gradient chain is recognised by its kernels (weight-gradient kernels, their operand conversions and slab reduces):
-    // those nodes ALWAYS go to stream 1, the low-priority stream, wherever the capture had them, and take no part in the chain
-    // logic of the other nodes -- a structural guess that put them on a high-priority stream, or the main chain on the low-priority
-    // one, cost 30-40 % of the step (any assignment is correct; the events below carry every cross-stream edge).
+    // those nodes ALWAYS go to stream 1, the low-priority stream, wherever the capture had them -- a structural guess that put them
+    // on a high-priority stream, or the main chain on the low-priority one, cost 30-40 % of the step (any assignment is correct; the
+    // events below carry every cross-stream edge).
     std::vector<char> side(n, 0);
     bool any_side = false;
     for (size_t i = 0; i < n; ++i) {
@@ -210,58 +196,15 @@ extern "C" int cwf_plan_create(void* graph_, void** out) {
         any_side = any_side || all_side;
     }
     // Everything that is not part of the weight-gradient chain stays on the caller's stream, in the order the host issued it (a valid
-    // topological order: ties above are broken by creation index).  The chain logic below (CWF_PLAN_CHAINS=1) can spread independent
-    // branches over further streams, but on this runtime a third stream made every step 60 % SLOWER (three plan streams: 31 ms per
-    // step against 18), and a chain that breaks at a weight-gradient node would open one.
-    static const bool chains = getenv("CWF_PLAN_CHAINS") != nullptr;
-    std::vector<int> heir(n, -1);
-    for (size_t u = 0; u < n; ++u) {
-        int best = -1;
-        for (int v : succ[u]) {
-            if (P->nodes[pos[v]].kind == NK_MARKER || side[v]) continue;
-            if (best < 0) { best = v; continue; }
-            const bool sv = pred[v].size() == 1, sb = pred[best].size() == 1;
-            if (sv != sb) { if (sv) best = v; continue; }
-            if (depth[v] > depth[best] || (depth[v] == depth[best] && pos[v] < pos[best])) best = v;
-        }
-        heir[u] = best;
-    }
-    int tail[MAX_STREAMS] = {-1, -1, -1, -1};                 // creation index of the last node on each stream
+    // topological order: ties above are broken by creation index).  Spreading independent branches over a third stream made every
+    // step 60 % SLOWER on this runtime (31 ms per step against 18).
     int waited[MAX_STREAMS + 1][MAX_STREAMS];                 // [waiting stream (MAX_STREAMS = marker stream)][source] -> last position waited for
     for (auto& row : waited) for (int& w : row) w = -1;
-    std::vector<int> stream_of(n, -2);
-    int n_streams = any_side ? 2 : 1;                      // stream 1 is reserved for the weight-gradient chain
-    bool any = false;
+    const int n_streams = any_side ? 2 : 1;
     for (size_t i = 0; i < n; ++i) {
-        int v = order[i];
+        const int v = order[i];
         PlanNode& N = P->nodes[i];
-        if (N.kind == NK_MARKER) {
-            N.stream = -1;
-        } else if (side[v]) {
-            N.stream = 1;
-            tail[1] = v;
-        } else if (!chains) {
-            N.stream = 0;
-            tail[0] = v;
-            any = true;
-        } else {
-            int s = -1;
-            for (int p : pred[v]) {
-                int sp = stream_of[p];
-                if (sp >= 0 && sp != 1 && tail[sp] == p && heir[p] == v && (s < 0 || sp < s)) s = sp;
-            }
-            if (s < 0 && !any) s = 0;
-            for (int c = 2; s < 0 && c < n_streams; ++c) {
-                int t = tail[c];
-                if (t < 0 || heir[t] < 0 || pos[heir[t]] < (int)i) s = c;         // that chain has ended
-            }
-            if (s < 0 && n_streams < MAX_STREAMS) { if (n_streams < 2) n_streams = 2; s = n_streams++; }
-            if (s < 0) s = 0;
-            N.stream = s;
-            tail[s] = v;
-            any = true;
-        }
-        stream_of[v] = N.stream;
+        N.stream = N.kind == NK_MARKER ? -1 : side[v] ? 1 : 0;
         std::vector<int> w;
         for (int p : pred[v]) {
             const PlanNode& Q = P->nodes[pos[p]];
@@ -285,18 +228,14 @@ extern "C" int cwf_plan_create(void* graph_, void** out) {
         }
     }
     P->n_streams = n_streams;
-    for (int c = 0; c < MAX_STREAMS; ++c) P->last_on[c] = tail[c] < 0 ? -1 : pos[tail[c]];
     int least = 0, greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
     for (int c = 1; c < n_streams; ++c) {
         hipStream_t st;
         hipEvent_t ev;
         // stream 1 = the weight-gradient chain: the runtime's LOW priority (its own hardware-queue pool and the right scheduling hint
-        // beside the data-gradient chain, see cwf.kernels.HipBackend.wgrad_stream); further streams: high
-        static const char* sp = getenv("CWF_PLAN_SIDE_PRIO");          // A/B: "normal" / "high" for the weight-gradient stream (default low)
-        int side_prio = least;
-        if (sp && !strcmp(sp, "normal")) side_prio = (least + greatest) / 2; else if (sp && !strcmp(sp, "high")) side_prio = greatest;
-        e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, c == 1 ? side_prio : greatest);
+        // beside the data-gradient chain, see cwf.kernels.HipBackend.wgrad_stream)
+        e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least);
         if (e != hipSuccess) { destroy(P); return (int)e; }
         P->owned.push_back(st);
         e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
@@ -320,11 +259,11 @@ extern "C" const char* cwf_plan_last_error(void) { return g_detail; }
 extern "C" int cwf_plan_info(void* plan, int* info8) {
     if (!plan || !info8) return CWF_E_BADARG;
     Plan* P = (Plan*)plan;
-    int per[MAX_STREAMS] = {0, 0, 0, 0};
+    int per[MAX_STREAMS] = {0, 0};
     for (auto& N : P->nodes)
         if (N.stream >= 0 && N.stream < MAX_STREAMS) per[N.stream]++;
     info8[0] = (int)P->nodes.size(); info8[1] = P->n_kernels; info8[2] = P->n_markers; info8[3] = P->n_streams;
-    info8[4] = P->n_events; info8[5] = per[0]; info8[6] = per[1]; info8[7] = per[2] + per[3];
+    info8[4] = P->n_events; info8[5] = per[0]; info8[6] = per[1]; info8[7] = 0;   // (no further streams)
     return 0;
 }
 
@@ -337,7 +276,7 @@ extern "C" int cwf_plan_run(void* plan, void* main_stream, void* comm_stream, in
     Plan* P = (Plan*)plan;
     const int n = (int)P->nodes.size();
     if (start < 0 || start > n) return CWF_E_BADARG;
-    hipStream_t st[MAX_STREAMS] = {(hipStream_t)main_stream, nullptr, nullptr, nullptr};
+    hipStream_t st[MAX_STREAMS] = {(hipStream_t)main_stream, nullptr};
     for (int c = 1; c < P->n_streams; ++c) st[c] = P->owned[c - 1];
     hipError_t e;
     if (start == 0 && P->n_streams > 1) {

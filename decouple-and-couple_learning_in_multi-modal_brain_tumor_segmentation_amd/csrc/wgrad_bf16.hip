@@ -22,9 +22,8 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 // the step faster).  Round 2, launches from Python: 192 (99.3 -> 100.1 volumes/s).  Round 3, launch plan (the main stream never
 // waits for the host any more): 128 -- 64 / 96 / 128 / 160 / 192 / 256 give 91.3 / 99.9 / 104.8 / 103.7 / 103.1 / 102.6 volumes/s.
 // End of round 3 (LDS-DMA weight gradients; only their chain off the main stream): 128 / 160 / 192 / 256 give 110.0 / 110.4 / 110.0 / 108.9: 160.
-// CWF_SIDE_WGS overrides (multiple of 8).
 extern "C" int cwf_wgrad_nsplit(int op, int N, int Do, int Ho, int Wo, int Cin, int Cout);
-static int side_wgs() { static const int v = getenv("CWF_SIDE_WGS") ? atoi(getenv("CWF_SIDE_WGS")) : 160; return v; }
+constexpr int SIDE_WGS = 160;
 
 struct WgArgsB {
   ConvGeom g;
@@ -896,7 +895,7 @@ extern "C" int cwf_wgrad16_bf16(const void* xa16, const void* dy16, const void* 
   a.tiles_d = cdiv(D, 4); a.tiles_h = cdiv(H, 4); a.tiles_w = cdiv(W, 16);
   a.total_tiles = N * a.tiles_d * a.tiles_h * a.tiles_w;
   a.slab_floats = 28 * 256;                               // = cwf_wgrad_slab_floats(CWF_CONV3_S1, 16, 16)
-  int grid = side_wgs(); while (grid > 8 && grid > a.total_tiles) grid -= 8;      // multiple of 8 (XCD-aware tile map)
+  int grid = SIDE_WGS; while (grid > 8 && grid > a.total_tiles) grid -= 8;      // multiple of 8 (XCD-aware tile map)
   if (grid > cwf_wgrad_nsplit(CWF_CONV3_S1, N, D, H, W, 16, 16)) return CWF_E_BADARG;    // (the caller's slab buffer is sized by it)
   const size_t lds = (size_t)W16D_NBUF * W16D_BUFB;
   CWF_MAX_LDS_ONCE((&wgrad16d_kernel));
@@ -1328,7 +1327,7 @@ extern "C" int cwf_wgrad_s1_bf16(const void* xa16, const void* dy16, const void*
   const int nblk = nchunks * a.ngroups;
   a.slab_floats = (int64_t)nblk * 28 * 2 * 256;
   if (a.slab_floats != cwf_wgrad_slab_floats(CWF_CONV3_S1, Cin, Cout)) return CWF_E_BADARG;
-  int want = side_wgs() / nblk; if (want < 1) want = 1; if (want > a.total_tiles) want = a.total_tiles;
+  int want = SIDE_WGS / nblk; if (want < 1) want = 1; if (want > a.total_tiles) want = a.total_tiles;
   a.tiles_per_split = cdiv(a.total_tiles, want);
   const int splits = cdiv(a.total_tiles, a.tiles_per_split);
   if (splits > cwf_wgrad_nsplit(CWF_CONV3_S1, N, D, H, W, Cin, Cout)) return CWF_E_BADARG;     // (the caller's slab buffer is sized by it)
@@ -1489,7 +1488,7 @@ static int launch_pw_wgrad(const WgArgsB& a, int CG, int max_slabs, int* nsplit_
   PwWgWork wk;
   wk.Vin = g.Di * g.Hi * g.Wi;
   wk.gps = wk.Vin >> 2;
-  int wps = side_wgs() / g.N; if (wps < 1) wps = 1;        // ~one 8/16-wave workgroup per CU in all, each inside one sample
+  int wps = SIDE_WGS / g.N; if (wps < 1) wps = 1;        // ~one 8/16-wave workgroup per CU in all, each inside one sample
   if (wps * g.N > max_slabs) wps = max_slabs / g.N;
   if (wps < 1) return -1;
   constexpr int PWG_WAVES = PwgCfg<NCH, NTL, NCLS>::WAVES;
@@ -1583,7 +1582,7 @@ static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const floa
   if (!groups && op == CWF_CONV3_S1 && Cin <= 16 && Cout == 16 && (dy_ldc & 3) == 0 && (((uintptr_t)dy) & 15) == 0 && (int64_t)Do * Ho * Wo >= 32768) {
     // full-resolution 16-channel layers: persistent producer/consumer kernel, one slab per workgroup (<= 256 <= generic nsplit)
     // (the stem layer -- 4 input channels -- is the LAST kernel of backward: nothing runs beside it, it takes every CU)
-    int grid = Cin <= 4 ? 256 : side_wgs(); while (grid > 8 && grid > total) grid -= 8;      // multiple of 8 (XCD-aware tile map)
+    int grid = Cin <= 4 ? 256 : SIDE_WGS; while (grid > 8 && grid > total) grid -= 8;      // multiple of 8 (XCD-aware tile map)
     const size_t lds16 = (size_t)2 * (36 * W16_XW * 16 + 16 * W16_DW * 16) * sizeof(unsigned short) * (x3 ? 2 : 1);
     hipStream_t st16 = cwf_stream(stream);
     if (x3) {
@@ -1600,44 +1599,38 @@ static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const floa
   if (!groups && (op == CWF_CONV1 || op == CWF_CONVT2) && ((int64_t)Di * Hi * Wi & 3) == 0 && (op == CWF_CONV1 || (Wi & 3) == 0) &&
       (int64_t)Di * Hi * Wi * (x_ldc > 8 * dy_ldc ? x_ldc : 8 * dy_ldc) < (1ll << 31)) {
     // pointwise layers: stream kernel (fp32 MFMA straight from global memory, every operand read once), both precision modes
-    static const bool off = getenv("CWF_NO_PW_WGRAD") != nullptr;        // A/B switch (diagnostics)
     const int nch = nchunks, ntl = a.g.ntiles;
     const int max_slabs = wg_splits * 4;                  // what the workspace was sized for
     hipStream_t stp = cwf_stream(stream);
     int r = -2;
-    if (!off) {
-      if (op == CWF_CONV1) {
-        if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 1>(a, CG, max_slabs, nsplit_used, stp);
-        else if (nch == 2 && ntl == 1) r = launch_pw_wgrad<2, 1, 1>(a, CG, max_slabs, nsplit_used, stp);
-        else if (nch == 4 && ntl == 2) r = launch_pw_wgrad<4, 2, 1>(a, CG, max_slabs, nsplit_used, stp);
-        else if (nch == 8 && ntl == 4) r = launch_pw_wgrad<8, 4, 1>(a, CG, max_slabs, nsplit_used, stp);
-      } else {
-        if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 8>(a, CG, max_slabs, nsplit_used, stp);
-        else if (nch == 2 && ntl == 2) r = launch_pw_wgrad<2, 2, 8>(a, CG, max_slabs, nsplit_used, stp);
-      }
+    if (op == CWF_CONV1) {
+      if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 1>(a, CG, max_slabs, nsplit_used, stp);
+      else if (nch == 2 && ntl == 1) r = launch_pw_wgrad<2, 1, 1>(a, CG, max_slabs, nsplit_used, stp);
+      else if (nch == 4 && ntl == 2) r = launch_pw_wgrad<4, 2, 1>(a, CG, max_slabs, nsplit_used, stp);
+      else if (nch == 8 && ntl == 4) r = launch_pw_wgrad<8, 4, 1>(a, CG, max_slabs, nsplit_used, stp);
+    } else {
+      if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 8>(a, CG, max_slabs, nsplit_used, stp);
+      else if (nch == 2 && ntl == 2) r = launch_pw_wgrad<2, 2, 8>(a, CG, max_slabs, nsplit_used, stp);
     }
     if (r >= 0) return r;
   }
   if (!x3 && op == CWF_CONV3_S1 && CG <= 2 && a.g.TD == 4 && a.g.TH == 4 && a.g.ID == 6 && a.g.IH == 6 && a.g.IW == 18 && (Cout & 3) == 0 &&
       (dy_ldc & 3) == 0 && dy_al) {
-    static const bool off = getenv("CWF_NO_WGRAD_S1") != nullptr;       // A/B switch (diagnostics)
-    if (!off) {
-      // producer / consumer kernel: ~256 eight-wave workgroups in all (one per CU), each a contiguous tile range of one (chunk, group)
-      int want1 = side_wgs() / nblk; if (want1 < 1) want1 = 1; if (want1 > total) want1 = total;
-      const int tps1 = cdiv(total, want1), splits1 = cdiv(total, tps1);
-      if (splits1 <= wg_splits) {                          // (the workspace was sized for wg_splits slabs)
-        a.tiles_per_split = tps1;
-        if (nsplit_used) *nsplit_used = splits1;
-        const size_t lds1 = (size_t)2 * (36 * 20 * 16 + 16 * (CG == 1 ? 20 : 16) * CG * 16 + (16 / 2 + 1) * (CG == 2 ? 16 : 0)) * sizeof(unsigned short);
-        dim3 grid1(splits1, nchunks * ngroups, groups ? groups : 1);
-        hipStream_t st1 = cwf_stream(stream);
-        CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<1>));
-        CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<2>));
-        if (CG == 1) hipLaunchKernelGGL((wgrad_s1_kernel<1>), grid1, dim3(256 + 64 * WS1_LW), lds1, st1, a);
-        else hipLaunchKernelGGL((wgrad_s1_kernel<2>), grid1, dim3(256 + 64 * WS1_LW), lds1, st1, a);
-        CWF_LAUNCH_CHECK();
-        return 0;
-      }
+    // producer / consumer kernel: ~256 eight-wave workgroups in all (one per CU), each a contiguous tile range of one (chunk, group)
+    int want1 = SIDE_WGS / nblk; if (want1 < 1) want1 = 1; if (want1 > total) want1 = total;
+    const int tps1 = cdiv(total, want1), splits1 = cdiv(total, tps1);
+    if (splits1 <= wg_splits) {                          // (the workspace was sized for wg_splits slabs)
+      a.tiles_per_split = tps1;
+      if (nsplit_used) *nsplit_used = splits1;
+      const size_t lds1 = (size_t)2 * (36 * 20 * 16 + 16 * (CG == 1 ? 20 : 16) * CG * 16 + (16 / 2 + 1) * (CG == 2 ? 16 : 0)) * sizeof(unsigned short);
+      dim3 grid1(splits1, nchunks * ngroups, groups ? groups : 1);
+      hipStream_t st1 = cwf_stream(stream);
+      CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<1>));
+      CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<2>));
+      if (CG == 1) hipLaunchKernelGGL((wgrad_s1_kernel<1>), grid1, dim3(256 + 64 * WS1_LW), lds1, st1, a);
+      else hipLaunchKernelGGL((wgrad_s1_kernel<2>), grid1, dim3(256 + 64 * WS1_LW), lds1, st1, a);
+      CWF_LAUNCH_CHECK();
+      return 0;
     }
   }
   const size_t ximg = (size_t)a.g.ID * a.g.IH * wg_x_pitch(a.g.IW, a.g.is) * 16;

@@ -190,10 +190,12 @@ class _ConvFn(torch.autograd.Function):
         ctx.use16 = bool(ok16 is not None and ok16(spec.op, spec.cin, spec.cout, y.shape[1] * y.shape[2] * y.shape[3]))
         ctx.x16 = getattr(x, "_cwf16x", None) if (ctx.use16 and in_scale is None) else None     # bf16(x) from x's producer (a block tail)
         if ctx.use16 and ctx.x16 is None and ctx.needs_input_grad[1] and getattr(K, "wgrad_async", False) and \
-                (getattr(K, "xa16_in_forward", False) or (getattr(x, "_cwf_wgrad_first", False) and _FIRST_X16_FWD)):   # (wgrad_async: a Trainer step)
+                getattr(x, "_cwf_wgrad_first", False):   # (wgrad_async: a Trainer step)
             # the weight-gradient operand bf16(act(IN(x))) depends on forward data only: made NOW, on the weight-gradient side stream,
             # which idles during the forward pass -- the backward pass then neither converts it nor waits for this layer's own
-            # InstanceNorm-backward apply pass (which matters for the last layers of backward: nothing is left to hide behind)
+            # InstanceNorm-backward apply pass (which matters for the last layers of backward: nothing is left to hide behind).  Only
+            # for that layer: made in the forward pass for every eligible layer, the conversions slowed the forward's own kernels
+            # (105.9 against 108.5 volumes/s with the apply pass writing it).
             ctx.x16 = K.to_bf16_side(x, in_scale, in_shift, slope)
         ctx.up16 = getattr(x, "_cwf_want16", False)     # x's producer is such a layer: hand its gradient on with a bf16 image ("only": nothing else)
         ctx.single = _SINGLE_CONSUMER                    # (backward runs after the declaring forward has returned: it reads this, not the global)
@@ -250,14 +252,9 @@ class _ConvFn(torch.autograd.Function):
         sb = sink.view(ctx.bias_ref) if (sw is not None and ctx.bias_ref is not None) else None
         to_sink = sw is not None and (ctx.bias_ref is None or sb is not None)
         use16 = ctx.use16 and to_sink and out_scale is None
+        # (no producer wrote a bf16 image of a gradient that comes out of a stride-2 data gradient: the weight gradient converts it on
+        # the side stream -- one conversion here on the main stream, for both gradients, measured 0.3 % slower)
         dy16 = getattr(dy, "_cwf16", None) if out_scale is None else None
-        if (_DY16_ON_MAIN and dy16 is None and use16 and ctx.needs_input_grad[0] and not getattr(dy, "_cwf_f32_missing", False) and
-                getattr(K, "bf16_dgrad_ok", lambda *a: False)(spec.op, spec.cin, spec.cout, dy.shape[1] * dy.shape[2] * dy.shape[3])
-                and dy.shape[-1] == spec.cout):
-            # no producer wrote the bf16 image of this gradient (it comes out of a stride-2 data gradient): one conversion pass HERE,
-            # on the main stream, serves both the data gradient (LDS-DMA form) and the weight gradient -- left to the weight gradient it
-            # runs on the side stream beside the HBM-bound end of backward (480 us instead of 65) and delays the optimizer
-            dy16 = K.to_bf16(dy)
         dg16 = dy16 if (dy16 is not None and getattr(K, "bf16_dgrad_ok", lambda *a: False)(
             spec.op, spec.cin, spec.cout, dy.shape[1] * dy.shape[2] * dy.shape[3])) else None     # the data gradient reads the bf16 image
         if getattr(dy, "_cwf_f32_missing", False) and not (use16 and dy16 is not None and (dg16 is not None or not ctx.needs_input_grad[0])
@@ -403,9 +400,6 @@ def fused_conv3(x, convs, spec):
 # and hand on its bf16 image alone (autograd would otherwise add the unwritten buffer to another consumer's gradient).  conv() marks
 # an output "only" while the declaration holds, and each Function records it at forward time for its backward.
 _SINGLE_CONSUMER = False
-import os as _os
-_DY16_ON_MAIN = _os.environ.get("CWF_DY16_ON_MAIN", "0") != "0"     # (measured 0.3 % slower than leaving the conversion to the side stream)
-_FIRST_X16_FWD = _os.environ.get("CWF_FIRST_X16_FWD", "1") != "0"     # the layer behind the stem: its xa16 is made in the forward pass (side stream)
 
 
 @contextlib.contextmanager
@@ -458,8 +452,7 @@ def conv(x, w, b, spec, in_norm=None, slope=1.0, residual=None, out_scale=None, 
     # block's first conv): the same launch writes bf16(y)
     y16 = None
     ok16_ = getattr(backend(), "bf16_operands_ok", None)
-    if emit16 and ok16_ is not None and torch.is_grad_enabled() and "xa" in getattr(backend(), "APPLY_EMITS", ()) and out is None and out_scale is None \
-            and not _os.environ.get("CWF_NO_PW_Y16"):
+    if emit16 and ok16_ is not None and torch.is_grad_enabled() and "xa" in getattr(backend(), "APPLY_EMITS", ()) and out is None and out_scale is None:
         n_, d_, h_, w_ = x.shape[0], *pk.out_dims(spec.op, x.shape[1], x.shape[2], x.shape[3])
         if ok16_(pk.CONV3_S1, spec.cout, spec.cout, d_ * h_ * w_) and (spec.cout_alloc or spec.cout) == spec.cout:
             y16 = torch.empty((n_, d_, h_, w_, spec.cout), dtype=torch.bfloat16, device=x.device)

@@ -130,14 +130,12 @@ class HipBackend:
         self._wg_pending = []                  # descriptor rows awaiting the batched reduce (wgrad_flush)
         self._wg_held = []                     # launches held back while wgrad_defer is set (wgrad_release)
         self._wg_keep = []                     # operands of released launches, referenced until join_wgrad_stream
-        import os
-        self.flush_every_default = int(os.environ.get("CWF_FLUSH_EVERY", "10"))
+        self.flush_every_default = 10
         self.flush_every = self.flush_every_default
         self.wgrad_defer = False
         self._wg_tables = {}
         self.wgrad_async = False
         self._rng_lock = threading.Lock()      # the autograd engine may call in from its own thread
-        self._no_stem = bool(os.environ.get("CWF_NO_STEM_KERNEL"))      # A/B: the stem on conv16s (K slots 3/4 empty)
 
     # ------------------------------------------------------------------ helpers
     @staticmethod
@@ -262,14 +260,14 @@ class HipBackend:
             return y
         if (op == pk.CONV3_S1 and cin == 4 and cout == 16 and mode != "fp32" and fwd_op is None and in_scale is None and residual is None
                 and nb is None and torch.is_tensor(w_ref) and tuple(w_ref.shape) == (16, 4, 3, 3, 3) and w_ref.is_contiguous()
-                and w_ref.dtype == _f32 and do * ho * wo >= 32768 and not self._no_stem):
+                and w_ref.dtype == _f32 and do * ho * wo >= 32768):
             # the stem: K = 8 taps x 4 channels (conv_stem.hip), straight from the raw weight
             self._call("cwf_conv_stem_bf16", 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, w_ref.data_ptr(), _p(bias), y.data_ptr(), y_ldc,
                        _p(out_scale), _p(stats), n, di, hi, wi, self._stream())
             return y
         if (op == pk.CONV3_S2 and cin == 16 and cout == 32 and mode != "fp32" and fwd_op is None and in_scale is None and residual is None
                 and out_scale is None and nb is None and torch.is_tensor(w_ref) and tuple(w_ref.shape) == (32, 16, 3, 3, 3) and w_ref.is_contiguous()
-                and w_ref.dtype == _f32 and do * ho * wo >= 32768 and not self._no_stem
+                and w_ref.dtype == _f32 and do * ho * wo >= 32768
                 and (do, ho, wo) == ((di + 1) // 2, (hi + 1) // 2, (wi + 1) // 2)):
             # the first down-sampling layer: persistent prefetching kernel with parity-split halo rows (conv_s2.hip)
             self._call("cwf_conv_s2c16_bf16", 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, w_ref.data_ptr(), _p(bias), y.data_ptr(), y_ldc,
@@ -315,29 +313,22 @@ class HipBackend:
     # exist (cwf_wgrad16_bf16: LDS-DMA staging, half the bytes, no conversion): xa16 = bf16(act(IN(x))) is a side output of the
     # layer's own InstanceNorm-backward apply pass, dy16 of the pass that produced the incoming gradient.  Same operand values as
     # the fp32-tensor kernel computes per tile (single-bf16 products), so results do not change.
-    # which bf16 images the main-stream InstanceNorm-backward apply pass (and the block tail) write as side outputs
-    # (CWF_APPLY_EMITS="xa,dx", "" = none): each costs the main stream 2 B per element; without it a conversion pass in front of the
-    # weight gradient costs the side stream 6 B per element.  Measured (plan mode, one box, volumes/s): none 102.7, dx 104.2, xa,dx 106.2.
-    import os as _os
-    APPLY_EMITS = tuple(t for t in _os.environ.get("CWF_APPLY_EMITS", "dx" if _os.environ.get("CWF_XA16_FWD", "0") != "0" else "xa,dx").split(",") if t)
+    # which bf16 images the main-stream InstanceNorm-backward apply pass (and the block tail) write as side outputs: each costs the
+    # main stream 2 B per element; without it a conversion pass in front of the weight gradient costs the side stream 6 B per
+    # element.  Measured (plan mode, one box, volumes/s): none 102.7, dx 104.2, xa,dx 106.2.
+    APPLY_EMITS = ("xa", "dx")
 
     def bf16_operands_ok(self, op, cin, cout, nvox):
-        import os
-        if os.environ.get("CWF_NO_BF16_OPERANDS"):
-            return False
         if op != pk.CONV3_S1 or (_WGRAD_PRECISION or _PRECISION) != "bf16":
             return 0
         if cin == 16 and cout == 16 and nvox >= 32768:
             return 16                                      # wgrad16d_kernel
-        if cin >= 32 and cin % 16 == 0 and cout % 32 == 0 and not os.environ.get("CWF_NO_BF16_S1D"):
+        if cin >= 32 and cin % 16 == 0 and cout % 32 == 0:
             return 32                                      # wgrad_s1d_kernel (32-channel output groups)
         return 0
 
     def bf16_dgrad_ok(self, op, cin, cout, nvox):
         """the data gradient of such a layer can read its incoming gradient as a bf16 image (conv(..., x16=))"""
-        import os
-        if os.environ.get("CWF_NO_BF16_OPERANDS") or os.environ.get("CWF_NO_BF16_DGRAD"):
-            return False
         return op == pk.CONV3_S1 and cin == 16 and cout == 16 and nvox >= 32768 and (_DGRAD_PRECISION or _PRECISION) == "bf16"
 
     def zero16(self, device):
@@ -377,12 +368,6 @@ class HipBackend:
         assert y.dtype == torch.bfloat16 and y.is_contiguous() and tuple(y.shape) == (n, d, h, w, c)
         self._call("cwf_to_bf16", x.data_ptr(), x_ldc, _p(scale), _p(shift), float(slope), y.data_ptr(), n, d * h * w, c, self._stream())
         return y
-
-    # CWF_XA16_FWD=1: bf16(act(IN(x))) of the eligible layers during the FORWARD pass, on the weight-gradient side stream (idle then);
-    # default: the apply pass / a conversion in front of the weight gradient makes it during backward
-    import os as _os2
-    # (measured: 105.9 volumes/s against 108.5 with the apply pass writing it -- the conversions slow the forward's own kernels; off)
-    xa16_in_forward = _os2.environ.get("CWF_XA16_FWD", "0") != "0"
 
     def to_bf16_side(self, x, scale, shift, slope):
         if not self.wgrad_async:
@@ -430,9 +415,7 @@ class HipBackend:
             # gradients then run strictly between the main stream's kernels (measured: zero overlap, 87.7 -> 78.5 volumes/s
             # with nothing but a one-rank process group alive).  Each priority has its own queue pool.  "low" is also the
             # right scheduling hint: the data-gradient chain on the main stream is the critical path.
-            import os
-            pr = os.environ.get("CWF_WGRAD_PRIORITY", "low")
-            st = _priority_stream(device, pr)
+            st = _priority_stream(device, "low")
             self._wg_stream[device] = st
         return st
 

@@ -89,13 +89,10 @@ class Trainer:
         # The decoder's (full-resolution) weight gradients are queued and released when backward leaves the decoder: they then run
         # beside the backward of the supervision heads / couplers -- 10-20 us kernels behind ~35 us of Python each, where the main
         # stream idles 1.7 ms per step -- instead of competing with the decoder's own HBM-bound data gradients (95.6 -> 96.7
-        # volumes/s; neutral while the step was still bound elsewhere).  CWF_DEFER_WGRAD=0 launches them immediately.
-        # Level 2 also holds the heads / couplers / decouplers phase's ~40 small weight-gradient launches until backward is in the
-        # encoder.  Round 3, launch plan (the host is never the bound): level 2 was best (103.1 -> 104.8 volumes/s with 128 side
-        # workgroups) while the eight residual layers' weight gradients still ran on the main stream; with them on the side stream
-        # (functional.CarryLink) the SIDE stream ends the step, and it must start earlier: level 1 (0 / 1 / 2: 104.0 / 106.2 / 100.5).
-        self.defer_level = int(os.environ.get("CWF_DEFER_WGRAD", "1"))
-        self.defer_decoder_wgrad = self.defer_level >= 1
+        # volumes/s; neutral while the step was still bound elsewhere).  Holding the heads / couplers / decouplers phase's ~40 small
+        # weight-gradient launches too, until backward is in the encoder, was best while the eight residual layers' weight gradients
+        # still ran on the main stream (103.1 -> 104.8 volumes/s); with them on the side stream (functional.CarryLink) the SIDE
+        # stream ends the step and must start earlier (launch plan, nothing / decoder / both held: 104.0 / 106.2 / 100.5).
 
     # ------------------------------------------------------------------------------------------------
     def _phase_done(self, k):
@@ -106,11 +103,9 @@ class Trainer:
             return
         K = kernels_backend()
         if getattr(K, "wgrad_defer", False):
-            # the weight gradients queued during the phase that just ended start now.  Decoder (k = 0): beside the GPU-light heads /
-            # couplers backward.  Heads / couplers / decouplers (k = 1, level 2): their ~40 small side-stream launches leave the
-            # host-bound stretch and are enqueued where the host has slack (the encoder's backward).  The last phase is never held.
+            # the decoder's weight gradients, queued during phase 0, start now: beside the GPU-light heads / couplers backward
             K.wgrad_release()
-            K.wgrad_defer = self.wgrad_async and self.defer_level >= 2 and k == 0
+            K.wgrad_defer = False
         K.wgrad_flush()
         if self.overlap_comm:
             self._allreduce_chunk(k)
@@ -146,12 +141,10 @@ class Trainer:
         loss, parts = total_loss(outputs, target, edge)
         self.opt.zero_grad(set_to_none=True)
         if hasattr(K, "flush_every_default"):
-            # graph modes: one reduce per phase, in warm-up too (CWF_PLAN_FLUSH=N: instalments of N layers in plan mode as in eager mode --
-            # the descriptor tables are keyed by their rows, so the warm-up steps must already produce the capture's instalments)
-            pf = int(os.environ.get("CWF_PLAN_FLUSH", "0"))
-            K.flush_every = (pf if (pf > 0 and self.graph_mode == "plan") else (1 << 30)) if self.use_graph else K.flush_every_default
+            # graph modes: one reduce per phase, in warm-up too
+            K.flush_every = (1 << 30) if self.use_graph else K.flush_every_default
         if hasattr(K, "wgrad_release"):
-            K.wgrad_defer = self.wgrad_async and self.defer_decoder_wgrad and hasattr(self.model, "phase_callback")
+            K.wgrad_defer = self.wgrad_async and hasattr(self.model, "phase_callback")
         self._in_backward = True
         try:
             with sink:

@@ -19,8 +19,6 @@ Deliberate relaxations of reference limitations:
   * the always-on stem dropout (F4) is kept by default; set ``model.Unet_list.InitConv.dropout = 0.0`` to disable.
 Returned tensors are logical NC(DHW) views of channels-last (NDHWC) memory.
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -37,6 +35,8 @@ REGIONS = ("01", "02", "04")
 
 
 class ClsWiseFormer(nn.Module):
+    grouped_heads = True       # the supervision heads as channel-grouped launches (False: one conv launch per region)
+
     def __init__(self, img_dim, patch_dim, num_channels, num_classes, embedding_dim, num_heads, num_layers, hidden_dim,
                  dropout_rate=0.0, attn_dropout_rate=0.0, conv_patch_representation=True,
                  positional_encoding_type="learned", gpu=0):
@@ -135,7 +135,7 @@ class ClsWiseFormer(nn.Module):
 
     def _heads3(self, heads, feats_all):
         """the three sub-regions' supervision heads on the channel groups of one tensor (zero-copy slices)"""
-        if os.environ.get("CWF_GROUPED_HEADS", "1") == "1":
+        if self.grouped_heads:
             return heads.heads3(feats_all)               # both conv stages as one channel-grouped launch each way
         parts = CP.split_channels3(feats_all)
         return {r: heads.head(k, p) for r, k, p in zip(REGIONS, (1, 2, 4), parts)}

@@ -211,7 +211,6 @@ def test_dma_weight_gradient_32_channel_groups(hip, cin, cout, size, n):
     """cwf_wgrad_s1_bf16 (wgrad_s1d_kernel: bf16 images by LDS-DMA, 16-channel chunks x 32-channel groups) against the fp32-tensor
     kernel (same single-bf16 operands: summation order only) and the oracle; ragged tiles included."""
     from cwf import functional as CF, kernels
-    import os
     d, h, w_ = size
     x = rnd(n, d, h, w_, cin, seed=41); g = rnd(n, d, h, w_, cout, seed=42)
     sc = rnd(n, cin, seed=43).abs() + 0.5; sh = rnd(n, cin, seed=44)
@@ -223,12 +222,9 @@ def test_dma_weight_gradient_32_channel_groups(hip, cin, cout, size, n):
         assert hip.bf16_operands_ok(pk.CONV3_S1, cin, cout, d * h * w_) == 32
         dw_a = torch.zeros(wn, device=DEV); db_a = torch.zeros(cout, device=DEV)
         dw_b = torch.zeros(wn, device=DEV); db_b = torch.zeros(cout, device=DEV)
-        os.environ["CWF_NO_BF16_OPERANDS"] = "1"
-        try:
-            hip.wgrad_to(("s1a", cin, cout), pk.CONV3_S1, xd, scd, shd, 0.01, gd, cout, spec.inv_map, dw_a, db_a)
-            hip.wgrad_flush(torch.device(DEV))
-        finally:
-            del os.environ["CWF_NO_BF16_OPERANDS"]
+        # explicit prec: the fp32-tensor kernel (no bf16 images), same precision mode
+        hip.wgrad_to(("s1a", cin, cout), pk.CONV3_S1, xd, scd, shd, 0.01, gd, cout, spec.inv_map, dw_a, db_a, prec="bf16")
+        hip.wgrad_flush(torch.device(DEV))
         hip.wgrad_to(("s1b", cin, cout), pk.CONV3_S1, xd, scd, shd, 0.01, gd, cout, spec.inv_map, dw_b, db_b)
         hip.wgrad_flush(torch.device(DEV))
     finally:
@@ -367,13 +363,8 @@ def test_bf16_operand_images_and_dma_weight_gradient(hip, size, n):
         dw_a = torch.zeros(wn, device=DEV); db_a = torch.zeros(c, device=DEV)
         dw_b = torch.zeros(wn, device=DEV); db_b = torch.zeros(c, device=DEV)
         dw_c = torch.zeros(wn, device=DEV); db_c = torch.zeros(c, device=DEV)
-        import os
-        os.environ["CWF_NO_BF16_OPERANDS"] = "1"                                                                   # the fp32-tensor kernel
-        try:
-            hip.wgrad_to("t16a", pk.CONV3_S1, xd, scd, shd, 0.01, gd, c, spec.inv_map, dw_a, db_a)
-            hip.wgrad_flush(torch.device(DEV))
-        finally:
-            del os.environ["CWF_NO_BF16_OPERANDS"]
+        hip.wgrad_to("t16a", pk.CONV3_S1, xd, scd, shd, 0.01, gd, c, spec.inv_map, dw_a, db_a, prec="bf16")      # the fp32-tensor kernel
+        hip.wgrad_flush(torch.device(DEV))
         xa16 = hip.to_bf16(xd, scd, shd, 0.01)
         hip.wgrad_to("t16b", pk.CONV3_S1, xd, scd, shd, 0.01, gd, c, spec.inv_map, dw_b, db_b, x16=xa16, dy16=hip.to_bf16(gd))
         hip.wgrad_flush(torch.device(DEV))

@@ -599,11 +599,11 @@ def test_rccl_phase_allreduce_path_one_rank(hip, monkeypatch):
     assert float((w2 - w0c).norm() / w0c.norm()) < 1e-5
 
 
-def test_grouped_head_maps_materialise_like_eval_and_ungrouped(hip, monkeypatch):
+def test_grouped_heads_attribute_maps_materialise_like_eval_and_ungrouped(hip):
     """The three sub-regions' heads run as channel-grouped launches; their training-mode outputs are LazyProb maps that share one
     grouped logit buffer.  (1) Touching such a map materialises the real tensor (strided logits through upsample_softmax) and a loss
     written against it back-propagates; (2) the fused loss over the grouped maps and its gradients equal the ungrouped path
-    (CWF_GROUPED_HEADS=0: one conv launch per region, per-map head-loss gradients)."""
+    (grouped_heads = False: one conv launch per region, per-map head-loss gradients)."""
     from cwf import functional as CF
     xc, target, edge = syn.synthetic_batch([0], (64, 64, 64))
     with torch.no_grad():
@@ -612,8 +612,8 @@ def test_grouped_head_maps_materialise_like_eval_and_ungrouped(hip, monkeypatch)
     x, target, edge = xc.to(DEV), target.to(DEV), edge.to(DEV)
 
     def run(grouped):
-        monkeypatch.setenv("CWF_GROUPED_HEADS", "1" if grouped else "0")
         m = _no_dropout_model(forced)
+        m.grouped_heads = grouped
         outs = m(x, None)
         assert all(isinstance(v, CF.LazyProb) and (v.parent is not None) == grouped for v in outs[1].values())
         loss = sum(_losses(outs, target, edge))

@@ -49,38 +49,3 @@ for _ in range(iters): run()
 e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / iters
 print("%s %s: %.4f ms  %.1f TFLOP/s alg  %.1f GB/s alg" % (what, prec, ms, 2.0 * 27 * c * c * n * s ** 3 / ms / 1e9, 2.0 * n * s ** 3 * c * 4 / ms / 1e6))
-if os.environ.get("CWF_SMODE"):
-    import ctypes
-    K.lib.cwf_debug_conv16_mode.argtypes = [ctypes.c_int]; K.lib.cwf_debug_conv16_mode.restype = None
-    for mode in (0, 2, 8, 10):
-        K.lib.cwf_debug_conv16_mode(mode)
-        run(); torch.cuda.synchronize()
-        e0.record()
-        for _ in range(5): run()
-        e1.record(); torch.cuda.synchronize()
-        print("sliding kernel, mode %d (2 = no loads, 8 = no epilogue): %.4f ms" % (mode, e0.elapsed_time(e1) / 5))
-    K.lib.cwf_debug_conv16_mode(0)
-if os.environ.get("CWF_DIAG"):
-    import ctypes
-    diag = torch.zeros((256, 8, 4), dtype=torch.int64, device=dev)
-    K.lib.cwf_debug_conv16_diag.argtypes = [ctypes.c_void_p]; K.lib.cwf_debug_conv16_diag.restype = None
-    K.lib.cwf_debug_conv16_diag(diag.data_ptr())
-    K.lib.cwf_debug_conv16_mode.argtypes = [ctypes.c_int]; K.lib.cwf_debug_conv16_mode.restype = None
-    for mode in (0, 1, 2, 4, 6, 8):
-        K.lib.cwf_debug_conv16_mode(mode)
-        run(); torch.cuda.synchronize()
-        e0.record()
-        for _ in range(5): run()
-        e1.record(); torch.cuda.synchronize()
-        print("diag build, mode %d: %.4f ms" % (mode, e0.elapsed_time(e1) / 5))
-    tiles = 2 * 8192 / 256
-    for mode in (0, 1, 2, 4, 6, 8):
-        K.lib.cwf_debug_conv16_mode(mode)
-        diag.zero_(); torch.cuda.synchronize()
-        run(); torch.cuda.synchronize()
-        d = diag.cpu().double()
-        m = d[:, :4].mean((0, 1)) / tiles
-        l = d[:, 4:].mean((0, 1)) / tiles
-        print("mode %2d per tile ticks  MFMA waves: barrier %.0f  mfma %.0f  epilogue %.0f | loader waves: barrier %.0f  commit %.0f" % (mode, m[0], m[1], m[2], l[0], l[2]))
-    K.lib.cwf_debug_conv16_mode(0)
-    K.lib.cwf_debug_conv16_diag(None)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import bf16_operand_ref as R
+import head_loss_ref as HL
 from cwf import packing as pk
 from oracle.kernel_emul import EmulBackend
 
@@ -773,6 +774,12 @@ def test_head_loss_backward_into_channel_groups(hip):
     for q in range(3):
         assert torch.equal(d_all[..., 4 * q:4 * q + 4], ref[q]) and outs[q].data_ptr() == d_all[..., 4 * q:4 * q + 4].data_ptr()
         assert bool((d_all[..., 4 * q + 2:4 * q + 4] == 0).all())
+        # elementwise against the float64 reference (tests/head_loss_ref.py)
+        mats = HL.axis_matrices((d, h, w_), scale)
+        t = HL.target(label.cpu(), 2, masks[q])
+        sl, c = slices[q].cpu(), c0[q].cpu().double()
+        bound, _ = HL.logit_grad_bound(sl, 2, mats, t, c, 0.7, scale)
+        HL.worst(d_all[..., 4 * q:4 * q + 2], HL.logit_grad(sl, 2, mats, t, c, 0.7), bound, "grouped dlogit %d, elementwise" % q)
 
 
 def test_gather_batched_matches_index_maps(hip):
@@ -921,7 +928,20 @@ def test_upsample_softmax_heads(hip, scale, lo):
     p4 = hip.channel_softmax(l4.to(DEV), 4)
     close(p4, E.channel_softmax(l4, 4), rtol=1e-6, atol=1e-7)
     d4 = rnd(n, 6, 6, 6, 4, seed=4)
-    close(hip.channel_softmax_bwd(d4.to(DEV), p4), E.channel_softmax_bwd(d4, p4.cpu()), rtol=1e-5)
+    dl4 = hip.channel_softmax_bwd(d4.to(DEV), p4)
+    close(dl4, E.channel_softmax_bwd(d4, p4.cpu()), rtol=1e-5)
+    # elementwise against the float64 reference (tests/head_loss_ref.py)
+    mats = HL.axis_matrices(lo, scale)
+    pr, q = HL.probs(logit.double(), 2, mats)
+    HL.worst(p, pr, HL.GAMMA_P * q * pr, "upsample fwd, elementwise")
+    pk, gk = p.cpu().double(), dprob.double()
+    HL.worst(dl[..., :2], HL.interp_adjoint(HL.softmax_adjoint(pk, gk), mats),
+             HL.gamma_softmax_bwd(2, scale) * HL.interp_adjoint(HL.softmax_adjoint_mag(pk, gk.abs()), mats), "upsample bwd, elementwise")
+    pr4, q4 = HL.probs(l4.double(), 4, None)
+    HL.worst(p4, pr4, HL.GAMMA_P * q4 * pr4, "channel softmax, elementwise")
+    p4k, d4k = p4.cpu().double(), d4.double()
+    HL.worst(dl4, HL.softmax_adjoint(p4k, d4k), HL.gamma_softmax_bwd(4, 1) * HL.softmax_adjoint_mag(p4k, d4k.abs()),
+             "channel softmax bwd, elementwise")
 
 
 @pytest.mark.parametrize("scale,lo,codes", [(8, (4, 6, 4), (0, 1, 2, 3)), (4, (8, 8, 12), (0, 1, 2, 4, 5, 6, 7, 8)), (8, (16, 16, 16), (0, 1, 2, 3))])
@@ -952,6 +972,12 @@ def test_head_loss_fused_vs_unfused_chain(hip, scale, lo, codes):
     for a, b in zip(dls, dls_e):
         close(a, b, rtol=5e-5, what="fused dlogit")
         assert float(a[..., 2:].abs().max()) == 0.0                      # pad channels written as zeros
+    mats = HL.axis_matrices(lo, scale)
+    for m, (a, lg) in enumerate(zip(dls, logits)):                       # elementwise against the float64 reference
+        t = HL.target(label, 2, pm[m])
+        c = coef[m].cpu().double()
+        bound, _ = HL.logit_grad_bound(lg, 2, mats, t, c, 0.7, scale)
+        HL.worst(a[..., :2], HL.logit_grad(lg, 2, mats, t, c, 0.7), bound, "fused dlogit %d, elementwise" % m)
     # (b) unfused HIP chain, through autograd, on the same logits
     leaves = [t.clone().requires_grad_(True) for t in ld]
     unf = sum(tools.dice_ce(CF.upsample_softmax(t, 2, scale).permute(0, 4, 1, 2, 3), label.to(DEV), 2, m) for t, m in zip(leaves, pm))
@@ -996,6 +1022,18 @@ def test_losses_against_reference_fixture(hip):
     assert abs(float(le) - float(g["edge_separate_loss"])) < 5e-6
     for r in outs:
         close(outs[r].grad, torch.from_numpy(g["edge_grad_" + r]), rtol=1e-5, what="edge grad")
+    # elementwise: each dLoss/dp against the float64 sums -> finalize -> dprob of tests/head_loss_ref.py, the kernels' sum error
+    # carried into the coefficients
+    def exact(grad, p_ncdhw, t):
+        p = p_ncdhw.detach().cpu().double().permute(0, 2, 3, 4, 1)
+        n, V = p.shape[0], p[0, ..., 0].numel()
+        S, A = HL.sums(p, t)
+        _, c, _ = HL.finalize(S, V)
+        ref, bound = HL.dprob_bound(p, t, c, 1.0, HL.coef_error(S, A, HL.gamma_sums(HL.unfused_terms_per_thread(n, V), False), c))
+        HL.worst(grad.permute(0, 2, 3, 4, 1), ref, bound, "fixture dprob, elementwise")
+    exact(p4.grad, p4, HL.target(target.cpu(), 4))
+    for r in outs:
+        exact(outs[r].grad, outs[r], HL.target(edge.cpu(), 2, tools.EDGE_MASKS[r]))
 
 
 def test_loss_edge_cases(hip):

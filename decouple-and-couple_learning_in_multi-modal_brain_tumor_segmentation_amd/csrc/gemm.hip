@@ -313,9 +313,19 @@ static bool gemm_vec_ok(const GemmArgs& a, bool* ak, bool* bn) {
   return true;
 }
 
-extern "C" int cwf_gemm_ex(const struct cwf_gemm_args* args, void* stream) {
-  if (!args) return CWF_E_BADARG;
-  const GemmArgs& a = *args;
+// The kernel cwf_gemm_ex launches for a set of arguments: the 16-byte-load kernel when K >= 64 and gemm_vec_ok (its <AK, BN> form
+// from the operands' unit-stride dimensions), the scalar one otherwise; 64 x 64 tiles when that grid has >= 256 workgroups,
+// 32 x 32 below.
+struct GemmVariant { bool vec; int tm; bool ak, bn; };
+static GemmVariant gemm_variant(const GemmArgs& a) {
+  const int64_t wg64 = (int64_t)cdiv(a.N, 64) * cdiv(a.M, 64) * a.ZB * a.ZH;
+  GemmVariant v = {false, wg64 >= 256 ? 64 : 32, false, false};
+  if (a.K >= 64 && gemm_vec_ok(a, &v.ak, &v.bn)) v.vec = true;
+  else v.ak = v.bn = false;
+  return v;
+}
+
+static int gemm_check(const GemmArgs& a) {
   if (!a.A || (!a.B && !a.B_tab[0]) || (!a.C && !a.C_tab[0]) || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.ZB <= 0 || a.ZH <= 0) return CWF_E_BADARG;
   if ((a.B_tab[0] || a.bias_tab[0] || a.C_tab[0] || a.rowsum_tab[0]) && (a.ZH != 1 || a.ZB > 4)) return CWF_E_BADARG;
   if ((int64_t)a.ZB * a.ZH > 65535) return CWF_E_TOOLARGE;
@@ -324,19 +334,26 @@ extern "C" int cwf_gemm_ex(const struct cwf_gemm_args* args, void* stream) {
   if (a.rowsum && (int64_t)a.ZB * a.ZH != 1) return CWF_E_BADARG;
   for (int z = 0; z < a.ZB && z < 4; ++z)
     if ((a.B_tab[0] && !a.B_tab[z]) || (a.bias_tab[0] && !a.bias_tab[z]) || (a.C_tab[0] && !a.C_tab[z]) || (a.rowsum_tab[0] && !a.rowsum_tab[z])) return CWF_E_BADARG;
-  const int64_t wg64 = (int64_t)cdiv(a.N, 64) * cdiv(a.M, 64) * a.ZB * a.ZH;
-  bool ak = false, bn = false;
-  if (a.K >= 64 && gemm_vec_ok(a, &ak, &bn)) {
-    const bool big = wg64 >= 256;
+  return 0;
+}
+
+extern "C" int cwf_gemm_ex(const struct cwf_gemm_args* args, void* stream) {
+  if (!args) return CWF_E_BADARG;
+  const GemmArgs& a = *args;
+  const int rc = gemm_check(a);
+  if (rc) return rc;
+  const GemmVariant v = gemm_variant(a);
+  const bool big = v.tm == 64;
+  if (v.vec) {
     dim3 grid(cdiv(a.N, big ? 64 : 32), cdiv(a.M, big ? 64 : 32), a.ZB * a.ZH);
 #define CWF_GV(AKv, BNv) do { if (big) hipLaunchKernelGGL((gemm_mfma_v_kernel<64, 64, 32, AKv, BNv>), grid, dim3(256), 0, cwf_stream(stream), a); \
                               else hipLaunchKernelGGL((gemm_mfma_v_kernel<32, 32, 64, AKv, BNv>), grid, dim3(256), 0, cwf_stream(stream), a); } while (0)
-    if (ak && bn) CWF_GV(true, true); else if (ak) CWF_GV(true, false); else if (bn) CWF_GV(false, true); else CWF_GV(false, false);
+    if (v.ak && v.bn) CWF_GV(true, true); else if (v.ak) CWF_GV(true, false); else if (v.bn) CWF_GV(false, true); else CWF_GV(false, false);
 #undef CWF_GV
     CWF_LAUNCH_CHECK();
     return 0;
   }
-  if (wg64 >= 256) {
+  if (big) {
     dim3 grid(cdiv(a.N, 64), cdiv(a.M, 64), a.ZB * a.ZH);
     hipLaunchKernelGGL((gemm_mfma_kernel<64, 64, 32>), grid, dim3(256), 0, cwf_stream(stream), a);
   } else {
@@ -344,6 +361,17 @@ extern "C" int cwf_gemm_ex(const struct cwf_gemm_args* args, void* stream) {
     hipLaunchKernelGGL((gemm_mfma_kernel<32, 32, 32>), grid, dim3(256), 0, cwf_stream(stream), a);
   }
   CWF_LAUNCH_CHECK();
+  return 0;
+}
+
+// Read-only query (tests): out = {vector kernel?, tile rows TM, AK, BN} of the kernel cwf_gemm_ex would launch for *args, or its
+// refusal code for arguments it refuses.  Launches nothing.
+extern "C" int cwf_debug_gemm_variant(const struct cwf_gemm_args* args, int* out) {
+  if (!args || !out) return CWF_E_BADARG;
+  const int rc = gemm_check(*args);
+  if (rc) return rc;
+  const GemmVariant v = gemm_variant(*args);
+  out[0] = v.vec; out[1] = v.tm; out[2] = v.ak; out[3] = v.bn;
   return 0;
 }
 

@@ -293,17 +293,23 @@ __global__ __launch_bounds__(256) void token_scores2_kernel(const float* __restr
 
 struct TopkJob { const float* score; int32_t* index; int32_t* inv; };
 
+// sort key of a score: an integer with the order -inf < ... < -0.0 == +0.0 < ... < +inf < NaN (NaN above +inf, as torch.topk
+// orders it; mapping NaN to +inf would tie the two and let an +inf score of lower index go first)
+__device__ __forceinline__ int topk_key(float s) {
+  if (s != s) return 0x7fffffff;
+  const int b = __float_as_int(s + 0.0f);                 // -0.0 + 0.0 = +0.0
+  return b >= 0 ? b : b ^ 0x7fffffff;
+}
+
 // the bitonic top-k of topk_kernel for up to two score vectors per launch (grid (B, njobs)), also writing the inverse map
 __global__ __launch_bounds__(1024) void topk_inv_kernel(const TopkJob j0, const TopkJob j1, int T, int k, int P) {
   extern __shared__ float4 lds4[];
-  float* key = reinterpret_cast<float*>(lds4);
+  int* key = reinterpret_cast<int*>(lds4);
   int* val = reinterpret_cast<int*>(key + P);
   const TopkJob job = blockIdx.y ? j1 : j0;
   const int b = blockIdx.x;
   for (int i = threadIdx.x; i < P; i += blockDim.x) {
-    float s = i < T ? job.score[(int64_t)b * T + i] : -INFINITY;
-    if (s != s) s = INFINITY;                             // NaN orders as the largest value (torch.topk)
-    key[i] = s;
+    key[i] = topk_key(i < T ? job.score[(int64_t)b * T + i] : -INFINITY);
     val[i] = i < T ? i : 0x7fffffff;
   }
   __syncthreads();
@@ -313,7 +319,7 @@ __global__ __launch_bounds__(1024) void topk_inv_kernel(const TopkJob j0, const 
         const int lo = 2 * i - (i & (stride - 1));
         const int hi = lo + stride;
         const bool desc = ((lo & size) == 0);
-        const float ka = key[lo], kb = key[hi]; const int va = val[lo], vb = val[hi];
+        const int ka = key[lo], kb = key[hi]; const int va = val[lo], vb = val[hi];
         const bool a_first = (ka > kb) || (ka == kb && va < vb);
         if (desc ? !a_first : a_first) { key[lo] = kb; key[hi] = ka; val[lo] = vb; val[hi] = va; }
       }

@@ -14,6 +14,7 @@ L = C.c_int64
 F = C.c_float
 U = C.c_uint32
 U64 = C.c_uint64
+D = C.c_double
 
 # name -> argtypes, exactly as declared in include/cwf_hip.h
 SIGNATURES = {
@@ -107,6 +108,9 @@ SIGNATURES = {
     "cwf_stitch_windows": [P, P, I, P],
     "cwf_argmax_dice": [P, L, L, L, P, P, P, I, L, P],
     "cwf_argmax_metrics": [P, L, L, L, P, P, P, I, L, P],
+    "cwf_region_bits": [P, P, L, P],
+    "cwf_hausdorff_workspace": [I, I, I, I, I],
+    "cwf_hausdorff": [P, P, I, I, I, I, I, D, D, D, I, I, P, P, P, P, L, P],
     "cwf_rng_advance": [P, P],
     "cwf_dropout_mask_rng": [P, L, F, F, P, U64, P],
     "cwf_plan_create": [P, P],
@@ -139,7 +143,7 @@ class GatherJob(C.Structure):
     """struct cwf_gather_job (include/cwf_hip.h)"""
     _fields_ = [("feats", P), ("index", P), ("head", P), ("out", P), ("head_bstride", L), ("out_bstride", L), ("T", I),
                 ("drop_off", C.c_uint64), ("head_g", P * 4), ("group_B", I)]
-RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats"}
+RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace"}
 
 _lib = None
 

@@ -1271,6 +1271,48 @@ class HipBackend:
                 return seg, dice, iou
         return seg, dice
 
+    def region_bits(self, labels):
+        """int64 label map (any shape) -> uint8 region bits of tools.softmax_output_dice: bit 0 WT, bit 1 TC, bit 2 ET (cwf_region_bits)"""
+        labels = labels.contiguous()
+        assert labels.dtype == torch.int64 and labels.is_cuda
+        bits = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+        if labels.numel():
+            self._call("cwf_region_bits", labels.data_ptr(), bits.data_ptr(), labels.numel(), self._stream())
+        return bits
+
+    def hausdorff(self, a_bits, b_bits, R, spacing=None, connectivity=1, all_border=False):
+        """medpy's hd / hd95 of the masks a, b ([B, D0, D1, D2] uint8 region bits or bool, bit r = region r < R <= 8) on the device:
+        -> (hd [B, R] float64, hd95 [B, R] float64, counts [B, R, 4] int64 = |A|, |B|, |dA|, |dB|); NaN distances where a mask is
+        empty.  spacing: None, a scalar or three per-axis values; all_border: every mask voxel is a border voxel (medpy on [1, ...]
+        arrays).  No host synchronisation: the workspace comes from torch's allocator on the current stream."""
+        if a_bits.dtype == torch.bool:
+            a_bits = a_bits.view(torch.uint8)
+        if b_bits.dtype == torch.bool:
+            b_bits = b_bits.view(torch.uint8)
+        if a_bits.dim() != 4 or tuple(a_bits.shape) != tuple(b_bits.shape) or a_bits.dtype != torch.uint8 or b_bits.dtype != torch.uint8:
+            raise ValueError("hausdorff: a_bits and b_bits must be uint8 / bool tensors of one [B, D0, D1, D2] shape")
+        if spacing is None:
+            sp = (1.0, 1.0, 1.0)
+        elif isinstance(spacing, (int, float)):
+            sp = (float(spacing),) * 3
+        else:
+            sp = tuple(float(s) for s in spacing)
+            if len(sp) != 3:
+                raise ValueError("hausdorff: spacing needs one value per axis, got %r" % (spacing,))
+        a_bits, b_bits = a_bits.contiguous(), b_bits.contiguous()
+        nb, d0, d1, d2 = (int(s) for s in a_bits.shape)
+        dev = a_bits.device
+        nbytes = self.lib.cwf_hausdorff_workspace(nb, int(R), d0, d1, d2)
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_hausdorff_workspace failed with status %d (B=%d R=%d %dx%dx%d)" % (nbytes, nb, R, d0, d1, d2))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        hd = torch.empty((nb, int(R)), dtype=torch.float64, device=dev)
+        hd95 = torch.empty((nb, int(R)), dtype=torch.float64, device=dev)
+        counts = torch.empty((nb, int(R), 4), dtype=torch.int64, device=dev)
+        self._call("cwf_hausdorff", a_bits.data_ptr(), b_bits.data_ptr(), nb, int(R), d0, d1, d2, sp[0], sp[1], sp[2], int(connectivity),
+                   int(bool(all_border)), hd.data_ptr(), hd95.data_ptr(), counts.data_ptr(), ws.data_ptr(), int(nbytes), self._stream())
+        return hd, hd95, counts
+
     # ------------------------------------------------------------------ K11 / misc
     def adam(self, table, ntensors, max_n, lr, beta1, beta2, eps, wd, step, amsgrad, hyper_dev=None, grad_scale=1.0):
         self._call("cwf_adam_amsgrad_scaled", table.data_ptr(), ntensors, max_n, lr, beta1, beta2, eps, wd, step, int(amsgrad),

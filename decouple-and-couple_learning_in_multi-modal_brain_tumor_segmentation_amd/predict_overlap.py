@@ -8,7 +8,7 @@ for parity.  The reference runs the eight windows as eight sequential B=1 forwar
 one batch, so they go through the kernels as ONE batch-8 forward.
 
 ``validate_softmax`` (predict_overlap.py:103-171) minus file I/O (nibabel / imageio are not hot-path): argmax over
-classes and the WT / TC / ET Dice of ``utils.tools.softmax_output_dice``.
+classes and the WT / TC / ET Dice of ``utils.tools.softmax_output_dice``; optionally the per-region surface HD95 (``with_hd95``).
 
 ``flip_tta`` (N4; predict_simple.py:333-349, predict_cls.py:184-203): the reference's 8-flip test-time augmentation -- the
 mean over all subsets of the three spatial axes of ``softmax(model(flip(x))[0]).flip`` (the reference re-applies softmax to
@@ -68,10 +68,14 @@ def flip_tta(x, missing_modal, forward, resoftmax=True, batch=8):
 
 
 @torch.no_grad()
-def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False):
+def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False, with_hd95=False):
     """One subject: stitched probabilities -> label map (argmax; class 3 stands for BraTS label 4) -> [WT, TC, ET] Dice.
     ``deterministic`` zeroes the stem dropout that the reference leaves on in eval mode.  ``with_miou`` adds the per-class
-    IoU list of tools.softmax_mIOU_score (what predict_simple.py reports next to Dice) as a fourth result."""
+    IoU list of tools.softmax_mIOU_score (what predict_simple.py reports next to Dice) as a fourth result.  ``with_hd95`` appends the
+    BraTS surface HD95: a [B, 3] float64 tensor of per-sample WT / TC / ET HD95 between ``seg`` and the target, on 3-D surfaces (unit
+    spacing, connectivity 1), 0 where either region is empty or full (the rule of utils.hausdorff.hausdorff_distance_95), computed on
+    the device (cwf_hausdorff); None without a target.  Result order: (seg, prob, dice[, miou][, hd95]).  predict_simple.py's own numbers
+    come from utils.hausdorff on [1, ...] arrays, where every mask voxel counts as a border voxel."""
     model.eval()
     saved = model.Unet_list.InitConv.dropout
     if deterministic:
@@ -83,6 +87,13 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
             prob = tailor_and_concat(x, None, model)
     finally:
         model.Unet_list.InitConv.dropout = saved
+    res = _validate(prob, target, with_miou)
+    if with_hd95:
+        res = res + ((None if target is None else hd95_regions(res[0], target[..., :155].long())),)
+    return res
+
+
+def _validate(prob, target, with_miou):
     if prob.is_cuda and prob.dtype == torch.float32 and prob.dim() == 5 and prob.shape[1] == 4:
         from cwf.kernels import backend                     # argmax + WT/TC/ET counts in one launch (cwf_argmax_dice)
         tgt = None if target is None else target[..., :155].long()
@@ -97,3 +108,15 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
     if with_miou:
         return seg, prob, dice, (tools.softmax_mIOU_score(seg, target[..., :155]) if target is not None else None)
     return seg, prob, dice
+
+
+def hd95_regions(seg, target):
+    """[B, 3] float64 WT / TC / ET surface HD95 of two [B, D0, D1, D2] int64 label maps on the device, 0 where either region is empty
+    or full (utils.hausdorff's rule).  No host synchronisation."""
+    from cwf.kernels import backend
+    be = backend()
+    target = target.to(seg.device)
+    _, hd95, counts = be.hausdorff(be.region_bits(seg), be.region_bits(target), 3)
+    nvox = seg[0].numel()
+    degenerate = (counts[..., 0] == 0) | (counts[..., 1] == 0) | (counts[..., 0] == nvox) | (counts[..., 1] == nvox)
+    return hd95.masked_fill(degenerate, 0.0)

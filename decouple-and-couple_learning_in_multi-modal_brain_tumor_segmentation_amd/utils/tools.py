@@ -1,6 +1,7 @@
 """Drop-in for the hot-path part of the reference ``utils.tools``: the per-sub-region Dice / weighted-CE losses
-(tools.py:8-34,112-231) on the fused HIP loss kernels, the collective helper (:37-41) and the integer Dice / IoU metrics
-(:44-61,89-109).  ``medpy`` (Hausdorff, tools.py:5) is not required.
+(tools.py:8-34,112-231) on the fused HIP loss kernels, the collective helper (:37-41), the integer Dice / IoU metrics
+(:44-61,89-109) and ``softmax_hd_dice`` (:64-86), whose medpy Hausdorff distances (tools.py:5) run on the device kernels of
+``utils.hausdorff``: ``medpy`` is not required.
 
 Label decoding happens inside the kernel: a 4-class map uses the label as class; a binary map uses
 ``(posmask >> label) & 1`` -- sub-region k -> {target == k}; edge sets E1={1,5,6,7}, E2={2,5,6,8}, E4={4,5,7,8}
@@ -67,6 +68,13 @@ def mIOU(o, t, eps=1e-8):
 def softmax_mIOU_score(output, target):
     """tools.softmax_mIOU_score (tools.py:56-61): IoU of classes 1, 2, 3 of integer label maps (numpy or torch)."""
     return [mIOU(o=(output == 1), t=(target == 1)), mIOU(o=(output == 2), t=(target == 2)), mIOU(o=(output == 3), t=(target == 3))]
+
+
+def softmax_hd_dice(output, target):
+    """tools.softmax_hd_dice (tools.py:64-86): ([WT, TC, ET] Dice, [WT, TC, ET] medpy hd) of integer label maps (numpy or torch, any
+    device).  A region that is empty in either map raises medpy's RuntimeError; rank rules as utils.hausdorff."""
+    from utils import hausdorff
+    return softmax_output_dice(output, target), hausdorff.softmax_hd(output, target)
 
 
 def softmax_output_dice(output, target):

@@ -437,7 +437,8 @@ int cwf_dice_ce_bwd(const float* prob, const int64_t* label, uint32_t posmask, c
                     float* dprob, int N, int64_t V, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * N1  sliding-window inference glue   predict_overlap.py:31-58 (tailor_and_concat), :134-141 + utils/tools.py:44-47,89-109
+ * N1  sliding-window inference glue   predict_overlap.py:31-58 (tailor_and_concat), :134-141 + utils/tools.py:44-47,64-109
+ *     and utils/hausdorff.py (Hausdorff distance / HD95)
  * ---------------------------------------------------------------------------------------------- */
 /* y [B][4][240][240][155] (NCDHW) <- the eight 128^3 window outputs windows[(w*B + b)][128][128][128][4] (channels-last, the model's
  * own output memory), w in the reference's window order; hard overwrite by the later window incl. the reference's last-axis offset
@@ -451,6 +452,24 @@ int cwf_argmax_dice(const float* prob, int64_t sb, int64_t sc, int64_t sv, const
  * WT, TC, ET, class 1, class 2, class 3, each (|o & t|, |o|, |t|); IoU = |o & t| / (|o| + |t| - |o & t|).  target is required.      */
 int cwf_argmax_metrics(const float* prob, int64_t sb, int64_t sc, int64_t sv, const int64_t* target, int64_t* seg, uint64_t* counts,
                        int B, int64_t V, void* stream);
+/* Hausdorff metrics (medpy.metric.binary hd / hd95 as called by the reference's utils/hausdorff.py and tools.softmax_hd_dice).
+ * Masks are bytes of region bits: bit r set = the voxel belongs to region r (R <= 8 regions per call).
+ * bits[i] <- region bits of int64 labels[i] for tools.softmax_output_dice's regions: bit 0 WT (> 0), bit 1 TC (1 or 3), bit 2 ET (3). */
+int cwf_region_bits(const int64_t* labels, uint8_t* bits, int64_t n, void* stream);
+/* Bytes of device workspace cwf_hausdorff needs for B samples x R regions of D0 x D1 x D2 voxels (256-B aligned; about 32 bytes
+ * per voxel plus 2 bytes per voxel and sample), or a negative CWF_E_* (CWF_E_TOOLARGE: D2 > 4096 or 2^31 voxels or more). */
+int64_t cwf_hausdorff_workspace(int B, int R, int D0, int D1, int D2);
+/* For every sample b and region r of the masks a, b [B][D0][D1][D2] (region bits): the borders dA, dB (mask & ~erosion under the
+ * connectivity 1/2/3 footprint of 6/18/26 neighbours, out-of-volume unset; all_border != 0: border = mask, medpy's result for
+ * [1, D0, D1, D2] arrays), the exact float64 Euclidean distances (spacing s0, s1, s2 along axes 0, 1, 2) from each voxel of dA to the
+ * nearest of dB and from dB to dA, and
+ *   hd[b][r]    max of both directions (medpy hd)
+ *   hd95[b][r]  numpy's linear 95th percentile of the union of both directions (medpy hd95); NaN in both when a mask is empty
+ *   counts[b][r][4] = |A|, |B|, |dA|, |dB|  (zeroed here).
+ * ws: cwf_hausdorff_workspace(...) bytes, 256-B aligned.  Only the [B][R] results are written outside the workspace.            */
+int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int D1, int D2, double s0, double s1, double s2,
+                  int connectivity, int all_border, double* hd, double* hd95, int64_t* counts, void* ws, int64_t ws_bytes,
+                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K11 fused Adam (amsgrad, L2 weight decay in the gradient)  torch.optim.Adam as used at train_no_amp.py:136,239

@@ -1,0 +1,309 @@
+// N3 -- training-batch preparation on the device (utils/data.py prepare_batch / DeviceBraTS).  One launch per (up to) eight samples
+// turns source volumes into (x, target, edge):
+//   source coordinate  s_i = o_i + (flip_i ? C_i-1-p_i : p_i); s_i >= S_i is outside the volume (image 0, label 0)
+//                      = utils.data.crop_pad followed by torch.flip of the crop
+//   x                  copied bit for bit, or fadd_rn(fmul_rn(v, scale_c), shift_c) with intensity on (padded voxels: 0 * scale + shift)
+//   target             the label with 4 -> 3, as int64
+//   edge               utils.synthetic.edge_codes of the cropped, flipped target (max_pool3d footprint: out-of-crop neighbours ignored)
+//
+// Edge codes, separably: every voxel carries six bits, any_k (bits 0-2) and all_k (bits 3-5) of (label == k), k = 1, 2, 3.  Three 1-D
+// passes over the 3-box take OR of the any bits and AND of the all bits, out-of-crop voxels being the identity of both (0x38); then
+// band_k = any_k & ~all_k = dilate(R_k) & ~erode(R_k) and the code is membership-coded as edge_codes does.  The bits of four
+// consecutive voxels sit in one 32-bit word (one byte each), so every pass step is one OR and one AND per four voxels.
+//
+// Tile: 4 x 16 x 64 output voxels per 256-thread workgroup; each thread owns four quads (4 voxels along the contiguous axis, one
+// quad per axis-0 slice).  LDS holds the label-bit halo [6][18][68 B], the axis-2 pass [6][18][16 words] and the axis-1 pass
+// [6][16][16 words] (20.4 KiB).  The image is read with dword loads -- crop origins are arbitrary, so source rows have no 16-B
+// alignment, and a flipped contiguous axis is read in descending order by the same loads -- and written with one 16-B store per
+// quad and channel; target and edge with two 16-B stores per quad (two int64 voxels each).  Crops whose rows are not a multiple of
+// four voxels, or outputs without 16-B alignment, take the same kernel with per-voxel stores.
+//
+// cwf_normalize_nonzero: per-channel z-score over the voxels whose four-channel sum ((x0 + x1) + x2) + x3 (float32) is > 0, float64
+// two-pass statistics (partials per workgroup, reduced in a fixed order by one thread: the result does not depend on scheduling).
+// This file is compiled with -ffp-contract=off.
+#include "common.h"
+
+#define PREP_T0 4
+#define PREP_T1 16
+#define PREP_T2 64
+#define PREP_Q2 (PREP_T2 / 4)              // quads per tile row
+#define PREP_H0 (PREP_T0 + 2)
+#define PREP_H1 (PREP_T1 + 2)
+#define PREP_H2 (PREP_T2 + 2)
+#define PREP_ROW 68                         // halo row bytes (66 used, padded to whole words)
+#define PREP_MAXS 8                         // samples per launch
+
+struct PrepSample {
+  const float* image;
+  const uint8_t* label;
+  int S0, S1, S2, o0, o1, o2, flip, intensity;
+  float scale[4], shift[4];
+};
+
+struct PrepArgs {
+  PrepSample s[PREP_MAXS];
+  float* x;
+  int64_t* target;
+  int64_t* edge;
+  int64_t x_bs, t_bs, e_bs;                 // sample strides (elements)
+  int C0, C1, C2, vec;
+};
+
+__device__ __forceinline__ uint32_t prep_or_and(uint32_t a, uint32_t b, uint32_t c) {
+  return ((a | b | c) & 0x07070707u) | ((a & b & c) & 0x38383838u);
+}
+
+// label bits of a source label: {1, 2, 3|4} -> any and all bit of that region; anything else (0) -> none
+__device__ __forceinline__ uint32_t prep_bits(uint32_t l) {
+  return l == 1 ? 0x09u : l == 2 ? 0x12u : (l == 3 || l == 4) ? 0x24u : 0u;
+}
+
+__device__ __forceinline__ int64_t prep_label(uint32_t bits) {
+  return (bits & 1u) ? 1 : (bits & 2u) ? 2 : (bits & 4u) ? 3 : 0;
+}
+
+__device__ __forceinline__ int64_t prep_code(uint32_t band) {
+  // band = b1 | b2 << 1 | b4 << 2  ->  edge_codes: 1, 2, 4 alone; 6 = 1&2, 7 = 1&4, 8 = 2&4, 5 = all three
+  return (int64_t)((0x58746210u >> (4u * band)) & 0xFu);
+}
+
+__global__ __launch_bounds__(256) void prep_batch_kernel(const PrepArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t H[PREP_H0][PREP_H1][PREP_ROW];
+  __shared__ uint32_t P1[PREP_H0][PREP_H1][PREP_Q2];
+  __shared__ uint32_t P2[PREP_H0][PREP_T1][PREP_Q2];
+  const PrepSample& S = a.s[blockIdx.y];
+  const int C0 = a.C0, C1 = a.C1, C2 = a.C2;
+  const int n2 = (C2 + PREP_T2 - 1) / PREP_T2, n1 = (C1 + PREP_T1 - 1) / PREP_T1;
+  const int t = blockIdx.x;
+  const int b2 = (t % n2) * PREP_T2, b1 = ((t / n2) % n1) * PREP_T1, b0 = (t / (n2 * n1)) * PREP_T0;
+  const int f0 = S.flip & 1, f1 = (S.flip >> 1) & 1, f2 = (S.flip >> 2) & 1;
+  const int64_t plane = (int64_t)S.S1 * S.S2, V = (int64_t)S.S0 * plane;
+  const int tid = threadIdx.x;
+
+  // 1. label bits of the halo tile
+  for (int i = tid; i < PREP_H0 * PREP_H1 * PREP_H2; i += 256) {
+    const int h2 = i % PREP_H2, h1 = (i / PREP_H2) % PREP_H1, h0 = i / (PREP_H2 * PREP_H1);
+    const int p0 = b0 + h0 - 1, p1 = b1 + h1 - 1, p2 = b2 + h2 - 1;
+    uint32_t v = 0x38u;                                       // out of the crop: identity of OR and AND
+    if (p0 >= 0 && p0 < C0 && p1 >= 0 && p1 < C1 && p2 >= 0 && p2 < C2) {
+      const int s0 = S.o0 + (f0 ? C0 - 1 - p0 : p0), s1 = S.o1 + (f1 ? C1 - 1 - p1 : p1), s2 = S.o2 + (f2 ? C2 - 1 - p2 : p2);
+      v = (s0 < S.S0 && s1 < S.S1 && s2 < S.S2) ? prep_bits(S.label[s0 * plane + (int64_t)s1 * S.S2 + s2]) : 0u;
+    }
+    H[h0][h1][h2] = (uint8_t)v;
+  }
+
+  // 2. image: independent of the label tile, issued before the first barrier's wait
+  const bool inten = S.intensity != 0;
+  const int64_t V_out = (int64_t)C0 * C1 * C2;
+  float* xs = a.x + (int64_t)blockIdx.y * a.x_bs;
+#pragma unroll 1
+  for (int k = 0; k < PREP_T0; ++k) {
+    const int q = tid + 256 * k;
+    const int w = q % PREP_Q2, j = (q / PREP_Q2) % PREP_T1, i = q / (PREP_Q2 * PREP_T1);
+    const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
+    if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
+    const int s0 = S.o0 + (f0 ? C0 - 1 - p0 : p0), s1 = S.o1 + (f1 ? C1 - 1 - p1 : p1);
+    const bool row_in = s0 < S.S0 && s1 < S.S1;
+    const int64_t src_row = s0 * plane + (int64_t)s1 * S.S2;
+    const int64_t dst = ((int64_t)p0 * C1 + p1) * C2 + p2;
+    int s2[4];
+    bool in[4], out_ok[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      out_ok[e] = p2 + e < C2;
+      s2[e] = S.o2 + (f2 ? C2 - 1 - (p2 + e) : p2 + e);
+      in[e] = row_in && out_ok[e] && s2[e] < S.S2;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float* src = S.image + c * V + src_row;
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[e] = in[e] ? src[s2[e]] : 0.f;
+        if (inten) v[e] = __fadd_rn(__fmul_rn(v[e], S.scale[c]), S.shift[c]);
+      }
+      float* d = xs + c * V_out + dst;
+      if (a.vec) {
+        f32x4 o = {v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<f32x4*>(d) = o;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (out_ok[e]) d[e] = v[e];
+      }
+    }
+  }
+  __syncthreads();
+
+  // 3. axis-2 pass: [6][18][16 quads]
+  for (int i = tid; i < PREP_H0 * PREP_H1 * PREP_Q2; i += 256) {
+    const int w = i % PREP_Q2, h1 = (i / PREP_Q2) % PREP_H1, h0 = i / (PREP_Q2 * PREP_H1);
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(&H[h0][h1][0]);
+    const uint32_t w0 = row[w], w1 = row[w + 1];
+    P1[h0][h1][w] = prep_or_and(w0, (w0 >> 8) | (w1 << 24), (w0 >> 16) | (w1 << 16));
+  }
+  __syncthreads();
+  // 4. axis-1 pass: [6][16][16]
+  for (int i = tid; i < PREP_H0 * PREP_T1 * PREP_Q2; i += 256) {
+    const int w = i % PREP_Q2, j = (i / PREP_Q2) % PREP_T1, h0 = i / (PREP_Q2 * PREP_T1);
+    P2[h0][j][w] = prep_or_and(P1[h0][j][w], P1[h0][j + 1][w], P1[h0][j + 2][w]);
+  }
+  __syncthreads();
+
+  // 5. axis-0 pass in registers, target and edge codes
+  int64_t* ts = a.target + (int64_t)blockIdx.y * a.t_bs;
+  int64_t* es = a.edge + (int64_t)blockIdx.y * a.e_bs;
+#pragma unroll 1
+  for (int k = 0; k < PREP_T0; ++k) {
+    const int q = tid + 256 * k;
+    const int w = q % PREP_Q2, j = (q / PREP_Q2) % PREP_T1, i = q / (PREP_Q2 * PREP_T1);
+    const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
+    if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
+    const uint32_t r = prep_or_and(P2[i][j][w], P2[i + 1][j][w], P2[i + 2][j][w]);
+    const uint32_t band = (r & 0x07070707u) & ~((r >> 3) & 0x07070707u);
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(&H[i + 1][j + 1][0]);
+    const uint32_t centre = (row[w] >> 8) | (row[w + 1] << 24);
+    int64_t tl[4], ec[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      tl[e] = prep_label((centre >> (8 * e)) & 0xFFu);
+      ec[e] = prep_code((band >> (8 * e)) & 0xFFu);
+    }
+    const int64_t dst = ((int64_t)p0 * C1 + p1) * C2 + p2;
+    if (a.vec) {
+      typedef long long i64x2 __attribute__((ext_vector_type(2)));
+      i64x2* tp = reinterpret_cast<i64x2*>(ts + dst);
+      i64x2* ep = reinterpret_cast<i64x2*>(es + dst);
+      tp[0] = i64x2{tl[0], tl[1]};
+      tp[1] = i64x2{tl[2], tl[3]};
+      ep[0] = i64x2{ec[0], ec[1]};
+      ep[1] = i64x2{ec[2], ec[3]};
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (p2 + e < C2) {
+          ts[dst + e] = tl[e];
+          es[dst + e] = ec[e];
+        }
+    }
+  }
+}
+
+extern "C" int cwf_prepare_batch(const struct cwf_prep_sample* h_samples, int B, int C0, int C1, int C2, float* x, int64_t x_bstride,
+                                 int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream) {
+  if (!h_samples || B <= 0 || C0 <= 0 || C1 <= 0 || C2 <= 0 || !x || !target || !edge) return CWF_E_BADARG;
+  const int64_t V = (int64_t)C0 * C1 * C2;
+  if (V >= (int64_t(1) << 31)) return CWF_E_TOOLARGE;
+  if (((uintptr_t)x & 3) || ((uintptr_t)target & 7) || ((uintptr_t)edge & 7)) return CWF_E_BADARG;
+  if (x_bstride < 4 * V || t_bstride < V || e_bstride < V) return CWF_E_BADARG;
+  const int C[3] = {C0, C1, C2};
+  for (int b = 0; b < B; ++b) {
+    const cwf_prep_sample& s = h_samples[b];
+    if (!s.image || !s.label || ((uintptr_t)s.image & 3) || s.flip < 0 || s.flip > 7) return CWF_E_BADARG;
+    const int Sx[3] = {s.S0, s.S1, s.S2}, o[3] = {s.o0, s.o1, s.o2};
+    for (int d = 0; d < 3; ++d)
+      if (Sx[d] <= 0 || o[d] < 0 || o[d] > std::max(Sx[d] - C[d], 0)) return CWF_E_BADARG;
+  }
+  PrepArgs a;
+  a.x = x; a.target = target; a.edge = edge;
+  a.x_bs = x_bstride; a.t_bs = t_bstride; a.e_bs = e_bstride;
+  a.C0 = C0; a.C1 = C1; a.C2 = C2;
+  a.vec = (C2 % 4 == 0) && !((uintptr_t)x & 15) && !((uintptr_t)target & 15) && !((uintptr_t)edge & 15) && x_bstride % 4 == 0 &&
+          t_bstride % 2 == 0 && e_bstride % 2 == 0;
+  const int64_t tiles = (int64_t)cdiv(C0, PREP_T0) * cdiv(C1, PREP_T1) * cdiv(C2, PREP_T2);
+  hipStream_t st = cwf_stream(stream);
+  for (int b0 = 0; b0 < B; b0 += PREP_MAXS) {
+    const int nb = std::min(PREP_MAXS, B - b0);
+    for (int i = 0; i < PREP_MAXS; ++i) {
+      PrepSample& d = a.s[i];
+      if (i >= nb) { d = PrepSample{}; continue; }
+      const cwf_prep_sample& s = h_samples[b0 + i];
+      d.image = s.image; d.label = s.label;
+      d.S0 = s.S0; d.S1 = s.S1; d.S2 = s.S2; d.o0 = s.o0; d.o1 = s.o1; d.o2 = s.o2;
+      d.flip = s.flip; d.intensity = s.intensity;
+      for (int c = 0; c < 4; ++c) { d.scale[c] = s.scale[c]; d.shift[c] = s.shift[c]; }
+    }
+    PrepArgs ab = a;
+    ab.x = x + (int64_t)b0 * x_bstride;
+    ab.target = target + (int64_t)b0 * t_bstride;
+    ab.edge = edge + (int64_t)b0 * e_bstride;
+    hipLaunchKernelGGL(prep_batch_kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, st, ab);
+    CWF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ brain-mask z-score
+#define NORM_BLOCKS 512
+
+__device__ __forceinline__ bool norm_mask(const float* __restrict__ x, int64_t v, int64_t V) {
+  return __fadd_rn(__fadd_rn(__fadd_rn(x[v], x[V + v]), x[2 * V + v]), x[3 * V + v]) > 0.f;
+}
+
+// pass 0: partial (count, sum_c); pass 1: partial (count, sum_c (x - mean_c)^2).  ws[blk * 5 + {0: count, 1..4: channel}]
+__global__ __launch_bounds__(256) void norm_partial_kernel(const float* __restrict__ x, int64_t V, double* __restrict__ ws, int pass) {
+  __shared__ double red[4][5];
+  const double* mean = ws + NORM_BLOCKS * 5;
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (int64_t)gridDim.x * 256) {
+    if (!norm_mask(x, v, V)) continue;
+    acc[0] += 1.0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const double d = (double)x[c * V + v];
+      if (pass == 0) {
+        acc[1 + c] += d;
+      } else {
+        const double e = d - mean[c];
+        acc[1 + c] += e * e;
+      }
+    }
+  }
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const double s = wave_sum_d(acc[k]);
+    if (lane == 0) red[wv][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) ws[blockIdx.x * 5 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// one thread: reduce the partials in block order; pass 0 -> mean[4] (ws[NB*5 + 0..3]), pass 1 -> std[4] (ws[NB*5 + 4..7])
+__global__ void norm_finalize_kernel(double* __restrict__ ws, int pass) {
+  if (threadIdx.x != 0) return;
+  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int b = 0; b < NORM_BLOCKS; ++b)
+    for (int k = 0; k < 5; ++k) s[k] += ws[b * 5 + k];
+  double* out = ws + NORM_BLOCKS * 5 + (pass == 0 ? 0 : 4);
+  for (int c = 0; c < 4; ++c) out[c] = s[0] > 0.0 ? (pass == 0 ? s[1 + c] / s[0] : sqrt(s[1 + c] / s[0])) : 0.0;
+}
+
+__global__ __launch_bounds__(256) void norm_apply_kernel(float* __restrict__ x, int64_t V, const double* __restrict__ ws) {
+  const double* mean = ws + NORM_BLOCKS * 5;
+  const double* sd = mean + 4;
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (int64_t)gridDim.x * 256) {
+    if (!norm_mask(x, v, V)) continue;
+    float r[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[c] = sd[c] > 0.0 ? (float)(((double)x[c * V + v] - mean[c]) / sd[c]) : x[c * V + v];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[c * V + v] = r[c];
+  }
+}
+
+extern "C" int cwf_normalize_nonzero(float* image, int64_t V, double* ws, void* stream) {
+  if (!image || !ws || V <= 0 || ((uintptr_t)image & 3) || ((uintptr_t)ws & 7)) return CWF_E_BADARG;
+  hipStream_t st = cwf_stream(stream);
+  for (int pass = 0; pass < 2; ++pass) {
+    hipLaunchKernelGGL(norm_partial_kernel, dim3(NORM_BLOCKS), dim3(256), 0, st, (const float*)image, V, ws, pass);
+    CWF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, ws, pass);
+    CWF_LAUNCH_CHECK();
+  }
+  const int nb = (int)std::min<int64_t>(cdiv64(V, 256), 4096);
+  hipLaunchKernelGGL(norm_apply_kernel, dim3(nb), dim3(256), 0, st, image, V, (const double*)ws);
+  CWF_LAUNCH_CHECK();
+  return 0;
+}

@@ -111,6 +111,8 @@ SIGNATURES = {
     "cwf_region_bits": [P, P, L, P],
     "cwf_hausdorff_workspace": [I, I, I, I, I],
     "cwf_hausdorff": [P, P, I, I, I, I, I, D, D, D, I, I, P, P, P, P, L, P],
+    "cwf_prepare_batch": [P, I, I, I, I, P, L, P, L, P, L, P],
+    "cwf_normalize_nonzero": [P, L, P, P],
     "cwf_rng_advance": [P, P],
     "cwf_dropout_mask_rng": [P, L, F, F, P, U64, P],
     "cwf_plan_create": [P, P],
@@ -143,6 +145,15 @@ class GatherJob(C.Structure):
     """struct cwf_gather_job (include/cwf_hip.h)"""
     _fields_ = [("feats", P), ("index", P), ("head", P), ("out", P), ("head_bstride", L), ("out_bstride", L), ("T", I),
                 ("drop_off", C.c_uint64), ("head_g", P * 4), ("group_B", I)]
+
+
+class PrepSample(C.Structure):
+    """struct cwf_prep_sample (include/cwf_hip.h)"""
+    _fields_ = [("image", P), ("label", P), ("S0", I), ("S1", I), ("S2", I), ("o0", I), ("o1", I), ("o2", I), ("flip", I),
+                ("intensity", I), ("scale", F * 4), ("shift", F * 4)]
+
+
+NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
 RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace"}
 
 _lib = None

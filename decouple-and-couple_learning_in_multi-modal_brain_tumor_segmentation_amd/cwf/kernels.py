@@ -1313,6 +1313,65 @@ class HipBackend:
                    int(bool(all_border)), hd.data_ptr(), hd95.data_ptr(), counts.data_ptr(), ws.data_ptr(), int(nbytes), self._stream())
         return hd, hd95, counts
 
+    # ------------------------------------------------------------------ N3 training-batch preparation
+    def prepare_batch(self, images, labels, params, crop, out=None):
+        """Training batch (x [B,4,C0,C1,C2] fp32, target [B,C0,C1,C2] int64, edge [B,C0,C1,C2] int64) from per-sample source volumes
+        (images[b] fp32 [4,S0,S1,S2], labels[b] uint8 [S0,S1,S2], contiguous, one device) in launches of eight samples (cwf_prepare_batch).
+        params[b]: .origin (3 ints), .flip (3 bools), .scale / .shift (4 floats each, or None: intensity off).  out: (x, target, edge)
+        to write into; each needs contiguous inner dimensions, its sample stride may be larger than one sample."""
+        crop = tuple(int(c) for c in crop)
+        if len(crop) != 3:
+            raise ValueError("prepare_batch: crop needs three extents, got %r" % (crop,))
+        nb = len(images)
+        if len(labels) != nb or len(params) != nb:
+            raise ValueError("prepare_batch: %d images, %d labels and %d parameter sets" % (nb, len(labels), len(params)))
+        if nb == 0:
+            raise ValueError("prepare_batch: empty batch")
+        dev = images[0].device
+        if dev.type != "cuda":
+            raise ValueError("prepare_batch: the images must be on a GPU")
+        samples = (_lib.PrepSample * nb)()
+        for b, (img, lab, p) in enumerate(zip(images, labels, params)):
+            if img.dtype != _f32 or img.dim() != 4 or img.shape[0] != 4 or not img.is_contiguous() or img.device != dev:
+                raise ValueError("prepare_batch: images[%d] must be a contiguous float32 [4, S0, S1, S2] tensor on %s" % (b, dev))
+            if lab.dtype != torch.uint8 or tuple(lab.shape) != tuple(img.shape[1:]) or not lab.is_contiguous() or lab.device != dev:
+                raise ValueError("prepare_batch: labels[%d] must be a contiguous uint8 %s tensor on %s" % (b, tuple(img.shape[1:]), dev))
+            s = samples[b]
+            s.image, s.label = img.data_ptr(), lab.data_ptr()
+            s.S0, s.S1, s.S2 = (int(v) for v in img.shape[1:])
+            s.o0, s.o1, s.o2 = (int(v) for v in p.origin)
+            s.flip = sum(1 << i for i, f in enumerate(p.flip) if f)
+            s.intensity = int(p.scale is not None)
+            if p.scale is not None:
+                s.scale[:] = [float(v) for v in p.scale]
+                s.shift[:] = [float(v) for v in p.shift]
+        if out is None:
+            # (a crop the library refuses -- an extent <= 0 or 2^31 voxels and more -- gets placeholders: the refusal comes from it)
+            ok = all(c > 0 for c in crop) and crop[0] * crop[1] * crop[2] < (1 << 31)
+            shape = crop if ok else (1, 1, 1)
+            x = torch.empty((nb, 4) + shape, dtype=_f32, device=dev)
+            target = torch.empty((nb,) + shape, dtype=torch.int64, device=dev)
+            edge = torch.empty((nb,) + shape, dtype=torch.int64, device=dev)
+        else:
+            x, target, edge = out
+            for name, t, shape, dt in (("x", x, (nb, 4) + crop, _f32), ("target", target, (nb,) + crop, torch.int64),
+                                       ("edge", edge, (nb,) + crop, torch.int64)):
+                inner = torch.empty(shape[1:], device="meta").stride()
+                if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or tuple(t.stride()[1:]) != inner:
+                    raise ValueError("prepare_batch: out %s must be a %s %s tensor on %s with contiguous samples" % (name, dt, shape, dev))
+        self._call("cwf_prepare_batch", ctypes.addressof(samples), nb, crop[0], crop[1], crop[2], x.data_ptr(), x.stride(0),
+                   target.data_ptr(), target.stride(0), edge.data_ptr(), edge.stride(0), self._stream())
+        return x, target, edge
+
+    def normalize_nonzero(self, image):
+        """In place: per-channel z-score of one subject image (contiguous fp32 [4, H, W, D] on a GPU) over the voxels whose
+        four-channel sum is > 0, float64 two-pass statistics (cwf_normalize_nonzero).  Returns image."""
+        if image.dtype != _f32 or image.dim() != 4 or image.shape[0] != 4 or not image.is_contiguous() or not image.is_cuda:
+            raise ValueError("normalize_nonzero: image must be a contiguous float32 [4, H, W, D] tensor on a GPU")
+        ws = torch.empty(_lib.NORM_WS_DOUBLES, dtype=torch.float64, device=image.device)
+        self._call("cwf_normalize_nonzero", image.data_ptr(), image[0].numel(), ws.data_ptr(), self._stream())
+        return image
+
     # ------------------------------------------------------------------ K11 / misc
     def adam(self, table, ntensors, max_n, lr, beta1, beta2, eps, wd, step, amsgrad, hyper_dev=None, grad_scale=1.0):
         self._call("cwf_adam_amsgrad_scaled", table.data_ptr(), ntensors, max_n, lr, beta1, beta2, eps, wd, step, int(amsgrad),

@@ -232,6 +232,12 @@ class Trainer:
         except Exception:
             pass
 
+    @property
+    def static_inputs(self):
+        """(x, target, edge) of the captured step, or None before capture: a batch written into these buffers is consumed by the next
+        step without a copy."""
+        return self._static if self._graph is not None else None
+
     def step(self, x, target, edge, epoch=0):
         """One optimisation step on a rank-local batch.  Returns (loss, [five parts]) as device tensors (no host sync)."""
         self.opt.param_groups[0]["lr"] = float(poly_lr(self.init_lr, epoch, self.end_epoch))   # plain float: checkpoints stay weights_only-loadable

@@ -88,6 +88,14 @@ def build_parser():
     p.add_argument("--log_every", default=10, type=int)
     p.add_argument("--max_iters", default=0, type=int, help="stop after this many iterations (smoke runs); 0 = no limit")
     p.add_argument("--backend", default=None, type=str, help="torch.distributed backend (default: nccl = RCCL on GPU, gloo on CPU)")
+    p.add_argument("--device_data", default="off", choices=("off", "cache", "staged"),
+                   help="prepare batches on the device (utils.data.DeviceBraTS): cache = every subject held in device memory, staged = "
+                        "crops read by DataLoader workers and finished on the device; off = the DataLoader path")
+    p.add_argument("--aug_flip", default=False, type=_bool, help="(--device_data) flip each crop axis with probability 1/2")
+    p.add_argument("--aug_intensity", default=0.0, type=float,
+                   help="(--device_data) f > 0: per-channel x * U(1-f, 1+f) + U(-f, f)")
+    p.add_argument("--normalize", default=False, type=_bool,
+                   help="(--device_data) z-score each subject's channels over its brain mask (four-channel sum > 0) at load")
     return p
 
 
@@ -111,8 +119,28 @@ def make_dataset(args):
     return data.NpzBraTS(root, lst if os.path.isfile(lst) else None, crop, args.seed, train=(args.mode == "train"))
 
 
+def make_device_dataset(args, device):
+    """utils.data.DeviceBraTS for --device_data: --synthetic N generates N subjects of (input_H, input_W, output_D) voxels."""
+    from utils import data
+    from utils import synthetic as syn
+    crop = (args.crop_H, args.crop_W, args.crop_D)
+    if args.synthetic > 0:
+        full = (args.input_H, args.input_W, args.output_D)
+        source = [syn.synthetic_volume(i, full, args.seed) for i in range(args.synthetic)]
+        source = [(x, t.to(torch.uint8)) for x, t in source]
+        lst = None
+    else:
+        source = os.path.join(args.root, args.train_dir)
+        lst = os.path.join(source, args.train_file)
+        lst = lst if os.path.isfile(lst) else None
+    return data.DeviceBraTS(source, device, crop, args.seed, flip=args.aug_flip, intensity=args.aug_intensity,
+                            normalize=args.normalize, cache=(args.device_data == "cache"), list_file=lst)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.device_data != "off" and args.mode != "train":
+        raise SystemExit("--device_data %s prepares training batches: only --mode train is supported on that path" % args.device_data)
     from cwf import kernels
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint
@@ -159,15 +187,24 @@ def main(argv=None):
     ckpt_dir = os.path.join(args.project_root, "checkpoint", args.experiment + args.date)
     if is_printer:
         os.makedirs(ckpt_dir, exist_ok=True)
-    ds = make_dataset(args)
+    device_data = args.device_data != "off"
+    ds = make_device_dataset(args, device) if device_data else make_dataset(args)
     t_start, iters, pending = time.time(), 0, None
     done = False
     for epoch in range(args.start_epoch, args.end_epoch):
         if hasattr(ds, "set_epoch"):
             ds.set_epoch(epoch)
         mine = shard_indices(len(ds), rank, world, epoch=epoch, shuffle=True, seed=args.seed)      # DistributedSampler semantics
-        loader = torch.utils.data.DataLoader(torch.utils.data.Subset(ds, mine), batch_size=args.batch_size, shuffle=False,
-                                             drop_last=(args.step_mode != "eager" and use_cuda), num_workers=args.num_workers if use_cuda else 0, pin_memory=use_cuda)
+        drop_last = args.step_mode != "eager" and use_cuda
+        if device_data:
+            groups = [mine[k:k + args.batch_size] for k in range(0, len(mine), args.batch_size)]
+            if drop_last and groups and len(groups[-1]) < args.batch_size:
+                groups.pop()
+            # plan / hipgraph mode: once the step is captured, batches are written straight into its static inputs
+            loader = ds.batches(groups, num_workers=args.num_workers if use_cuda else 0, out=lambda: trainer.static_inputs)
+        else:
+            loader = torch.utils.data.DataLoader(torch.utils.data.Subset(ds, mine), batch_size=args.batch_size, shuffle=False,
+                                                 drop_last=drop_last, num_workers=args.num_workers if use_cuda else 0, pin_memory=use_cuda)
         for i, (x, target, edge, _missing) in enumerate(loader):
             x, target, edge = (t.to(device, non_blocking=True) for t in (x, target, edge))
             loss, parts = trainer.step(x, target, edge, epoch)

@@ -8,7 +8,10 @@ Two map-style datasets produce exactly that tuple from 240 x 240 x 155 volumes w
   * ``NpzBraTS``       -- one ``.npz`` per subject with ``image [4,H,W,D]`` (or ``[H,W,D,4]``) float and ``label [H,W,D]`` integer
                           (BraTS labels 0,1,2,4 -- 4 is mapped to 3 as the reference's loaders do).  nibabel is not available in
                           this image, so NIfTI conversion is left to the user (one ``np.savez`` per subject).
-Edge codes are derived from the label with utils.synthetic.edge_codes (boundary of each sub-region, coded per E1/E2/E4)."""
+Edge codes are derived from the label with utils.synthetic.edge_codes (boundary of each sub-region, coded per E1/E2/E4).
+
+``DeviceBraTS`` / ``prepare_batch`` produce the same tuple on the GPU (csrc/prep.hip: crop, optional flips and intensity scale / shift,
+label remap and edge codes in one launch per eight samples), bit-equal to the CPU statement in this module."""
 import glob
 import os
 
@@ -93,3 +96,290 @@ class NpzBraTS(Dataset):
             o = random_crop_origin(tuple(lab.shape), self.crop, rng)
             img, lab = crop_pad(img, o, self.crop), crop_pad(lab, o, self.crop)
         return img, lab, syn.edge_codes(lab), torch.zeros(4, dtype=torch.bool)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Training batches prepared on the device.  The flip and intensity augmentations are this project's definitions (the TransBTS-family
+# loaders the reference descends from flip each axis and shift intensities per channel; the reference's own `data/` package is absent),
+# so they are opt-in and off by default.
+class AugParams:
+    """Per-sample batch parameters: crop origin (3 ints), flips of the three crop axes, and the per-channel intensity scale / shift
+    (float32 [4] each; None = intensity off)."""
+    __slots__ = ("origin", "flip", "scale", "shift")
+
+    def __init__(self, origin, flip=(False, False, False), scale=None, shift=None):
+        self.origin = tuple(int(o) for o in origin)
+        self.flip = tuple(bool(f) for f in flip)
+        if (scale is None) != (shift is None):
+            raise ValueError("AugParams: scale and shift go together")
+        self.scale = None if scale is None else tuple(float(v) for v in np.asarray(scale, dtype=np.float32))
+        self.shift = None if shift is None else tuple(float(v) for v in np.asarray(shift, dtype=np.float32))
+        if len(self.origin) != 3 or len(self.flip) != 3 or (self.scale is not None and (len(self.scale) != 4 or len(self.shift) != 4)):
+            raise ValueError("AugParams: origin and flip take 3 values, scale and shift 4")
+
+    def at_origin(self, origin):
+        return AugParams(origin, self.flip, self.scale, self.shift)
+
+    def __eq__(self, other):
+        return isinstance(other, AugParams) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __repr__(self):
+        return "AugParams(origin=%r, flip=%r, scale=%r, shift=%r)" % (self.origin, self.flip, self.scale, self.shift)
+
+
+def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0):
+    """Parameters of sample `index` in `epoch`: a pure function of the arguments, drawn from default_rng([seed, epoch, index]).  The
+    origin is drawn first, by random_crop_origin's calls, so with augmentation off it is the origin NpzBraTS / SyntheticBraTS pick.
+    flip: three uniforms, each < 0.5 flipping that axis; intensity f > 0: scale ~ U(1-f, 1+f)[4], then shift ~ U(-f, f)[4] (float32)."""
+    rng = np.random.default_rng([int(seed), int(epoch), int(index)])
+    origin = random_crop_origin(tuple(full), tuple(crop), rng)
+    fl = tuple(bool(u < 0.5) for u in rng.random(3)) if flip else (False, False, False)
+    scale = shift = None
+    f = float(intensity)
+    if f > 0.0:
+        scale = rng.uniform(1.0 - f, 1.0 + f, 4).astype(np.float32)
+        shift = rng.uniform(-f, f, 4).astype(np.float32)
+    return AugParams(origin, fl, scale, shift)
+
+
+def _prepare_one_cpu(img, lab, p, crop):
+    x = crop_pad(img, p.origin, crop)
+    t = crop_pad(lab.to(torch.int64), p.origin, crop)
+    dims = [d for d in range(3) if p.flip[d]]
+    if dims:
+        x = torch.flip(x, [d + 1 for d in dims])
+        t = torch.flip(t, dims)
+    if p.scale is not None:
+        x = x * torch.tensor(p.scale, dtype=torch.float32).reshape(4, 1, 1, 1)
+        x = x + torch.tensor(p.shift, dtype=torch.float32).reshape(4, 1, 1, 1)
+    t[t == 4] = 3
+    return x, t, syn.edge_codes(t)
+
+
+def prepare_batch(images, labels, params, crop, out=None):
+    """(x [B,4,*crop] float32, target [B,*crop] int64, edge [B,*crop] int64) from source volumes images[b] float32 [4,S0,S1,S2] and
+    labels[b] uint8 [S0,S1,S2] (values 0..4): crop_pad at params[b].origin -> torch.flip of the flipped crop axes -> x * scale then
+    + shift in float32 -> label 4 -> 3 -> utils.synthetic.edge_codes.  On GPU tensors this is one HIP launch per eight samples
+    (HipBackend.prepare_batch, bit-equal to the CPU statement); on CPU tensors it is the CPU statement itself.  out: (x, target, edge)
+    to write into (sample stride free, samples contiguous)."""
+    crop = tuple(int(c) for c in crop)
+    if len(images) and images[0].is_cuda:
+        from cwf import kernels
+        return kernels.backend().prepare_batch(images, labels, params, crop, out=out)
+    xs, ts, es = zip(*(_prepare_one_cpu(i, l, p, crop) for i, l, p in zip(images, labels, params)))
+    x, t, e = torch.stack(xs), torch.stack(ts), torch.stack(es)
+    if out is None:
+        return x, t, e
+    for dst, src in zip(out, (x, t, e)):
+        dst.copy_(src)
+    return tuple(out)
+
+
+def normalize_nonzero(image):
+    """In place: z-score each channel of image [4,H,W,D] float32 over the voxels whose four-channel sum ((x0 + x1) + x2) + x3 is > 0,
+    float64 two-pass mean and population std; masked voxels become float32((x - mean) / std), the rest and channels with std 0 stay.
+    GPU tensors: HipBackend.normalize_nonzero; CPU tensors: numpy float64."""
+    if image.is_cuda:
+        from cwf import kernels
+        return kernels.backend().normalize_nonzero(image)
+    a = image.numpy()
+    s = ((a[0] + a[1]) + a[2]) + a[3]
+    m = s > 0
+    if m.any():
+        for c in range(4):
+            v = a[c][m].astype(np.float64)
+            mean = v.sum() / v.size
+            std = np.sqrt(((v - mean) ** 2).sum() / v.size)
+            if std > 0:
+                a[c][m] = ((v - mean) / std).astype(np.float32)
+    return image
+
+
+def _npz_paths(root, list_file=None):
+    if list_file is not None:
+        with open(list_file) as f:
+            names = [ln.strip() for ln in f if ln.strip()]
+        paths = [os.path.join(root, n if n.endswith(".npz") else n + ".npz") for n in names]
+    else:
+        paths = sorted(glob.glob(os.path.join(root, "*.npz")))
+    if not paths:
+        raise FileNotFoundError("no .npz subjects under %s" % root)
+    return paths
+
+
+def _npz_shapes(path):
+    """(image shape, label shape) read from the .npy headers inside an .npz, without loading the arrays."""
+    import zipfile
+    out = {}
+    with zipfile.ZipFile(path) as zf:
+        for key in ("image", "label"):
+            with zf.open(key + ".npy") as f:
+                version = np.lib.format.read_magic(f)
+                read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+                out[key] = read(f)[0]
+    return out["image"], out["label"]
+
+
+def _subject_arrays(img, lab, name):
+    """image -> float32 [4,H,W,D] (accepting [H,W,D,4]), label -> uint8 [H,W,D] with values in {0,1,2,3,4} (CPU tensors)."""
+    img = torch.as_tensor(np.ascontiguousarray(img.numpy() if isinstance(img, torch.Tensor) else img, dtype=np.float32))
+    if img.shape[-1] == 4 and img.shape[0] != 4:
+        img = img.permute(3, 0, 1, 2)
+    img = img.contiguous()
+    lab = np.asarray(lab.numpy() if isinstance(lab, torch.Tensor) else lab)
+    if lab.size and (lab.min() < 0 or lab.max() > 4 or np.any(lab != np.round(lab))):
+        bad = sorted(set(np.unique(lab).tolist()) - {0, 1, 2, 3, 4})
+        raise ValueError("%s: label values must lie in {0, 1, 2, 3, 4} (BraTS labels), found %s" % (name, bad[:8]))
+    lab = torch.from_numpy(np.ascontiguousarray(lab.astype(np.uint8)))
+    if img.dim() != 4 or img.shape[0] != 4 or tuple(img.shape[1:]) != tuple(lab.shape):
+        raise ValueError("%s: image %s and label %s do not form one [4,H,W,D] / [H,W,D] subject" % (name, tuple(img.shape), tuple(lab.shape)))
+    return img, lab
+
+
+class NpzCropSource(Dataset):
+    """Map-style dataset of the staged device path (DeviceBraTS(cache=False)), run in DataLoader workers: item i is the crop of subject
+    i at draw_params' origin, before any flip or intensity -- (image float32 [4,*crop], label uint8 [*crop], index) -- from one
+    np.load + crop_pad (no edge codes).  `subjects`: .npz paths, or in-memory (image, label) pairs."""
+
+    def __init__(self, subjects, crop, seed=1000, normalize=False):
+        self.subjects, self.crop, self.seed, self.normalize, self.epoch = list(subjects), tuple(crop), int(seed), bool(normalize), 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.subjects)
+
+    def load(self, i):
+        s = self.subjects[i]
+        if isinstance(s, str):
+            with np.load(s, allow_pickle=False) as z:
+                img, lab = _subject_arrays(z["image"], z["label"], s)
+        else:
+            img, lab = s
+            if not (isinstance(img, torch.Tensor) and img.dtype == torch.float32 and img.dim() == 4 and img.shape[0] == 4
+                    and lab.dtype == torch.uint8):
+                img, lab = _subject_arrays(img, lab, "subject %d" % i)
+            elif self.normalize:
+                img = img.clone()
+        if self.normalize:
+            normalize_nonzero(img)
+        return img, lab
+
+    def __getitem__(self, i):
+        img, lab = self.load(i)
+        o = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop).origin
+        return crop_pad(img, o, self.crop), crop_pad(lab, o, self.crop), i
+
+
+def _collate_crops(items):
+    imgs, labs, idx = zip(*items)
+    return torch.stack(imgs), torch.stack(labs), list(idx)
+
+
+class DeviceBraTS:
+    """Training batches (x, target, edge, missing_modal [B,4] bool) prepared on `device` by prepare_batch: one HIP launch per eight
+    samples for crop + flips + intensity + label remap + edge codes, written straight into caller-owned buffers with out=.
+
+    source: a directory of .npz subjects (NpzBraTS's layout; `list_file` as NpzBraTS's) or a list of (image, label) pairs -- e.g.
+    utils.synthetic.synthetic_volume outputs.  Sample i of epoch e uses draw_params(seed, e, i, its extents, crop, flip, intensity);
+    with augmentation off a batch equals torch.stack of NpzBraTS / SyntheticBraTS items.
+      cache=True   every subject is loaded once onto the device (fp32 image, uint8 label, optionally z-scored by normalize_nonzero)
+      cache=False  "staged": NpzCropSource crops in DataLoader workers (batches()), the crops are uploaded from pinned memory and
+                   prepared at origin 0 -- 36 MB per 128^3 sample over the host link instead of a whole subject."""
+
+    def __init__(self, source, device, crop=(128, 128, 128), seed=1000, flip=False, intensity=0.0, normalize=False, cache=True,
+                 list_file=None):
+        self.device = torch.device(device)
+        self.crop, self.seed, self.epoch = tuple(int(c) for c in crop), int(seed), 0
+        self.flip, self.intensity, self.normalize, self.cache = bool(flip), float(intensity), bool(normalize), bool(cache)
+        subjects = _npz_paths(source, list_file) if isinstance(source, str) else list(source)
+        if not subjects:
+            raise ValueError("DeviceBraTS: no subjects")
+        self.source = NpzCropSource(subjects, self.crop, self.seed, self.normalize)
+        self.images = self.labels = None
+        if self.cache:
+            self._load_all(subjects)
+
+    def _load_all(self, subjects):
+        if self.device.type == "cuda":
+            need = 0
+            for s in subjects:
+                if isinstance(s, str):
+                    ishape, lshape = _npz_shapes(s)
+                else:
+                    ishape, lshape = tuple(s[0].shape), tuple(s[1].shape)
+                need += 4 * int(np.prod(ishape)) + int(np.prod(lshape))
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if need > 0.9 * free:
+                raise MemoryError("DeviceBraTS(cache=True) needs %.1f GB of device memory for %d subjects, %.1f GB are free: use "
+                                  "cache=False (the 'staged' mode) instead" % (need / 1e9, len(subjects), free / 1e9))
+        self.images, self.labels = [], []
+        for i in range(len(subjects)):
+            img, lab = self.source.load(i) if self.device.type == "cpu" else self._load_raw(i)
+            self.images.append(img)
+            self.labels.append(lab)
+
+    def _load_raw(self, i):
+        """subject i on the device; normalised there (the device kernel) when asked"""
+        src = self.source
+        norm, src.normalize = src.normalize, False
+        try:
+            img, lab = src.load(i)
+        finally:
+            src.normalize = norm
+        img, lab = img.to(self.device).contiguous(), lab.to(self.device).contiguous()
+        if self.normalize:
+            normalize_nonzero(img)
+        return img, lab
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+        self.source.set_epoch(epoch)
+
+    def __len__(self):
+        return len(self.source)
+
+    def extents(self, i):
+        if self.labels is not None:
+            return tuple(self.labels[i].shape)
+        s = self.source.subjects[i]
+        return tuple(_npz_shapes(s)[1]) if isinstance(s, str) else tuple(s[1].shape)
+
+    def params(self, i):
+        return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity)
+
+    def _missing(self, n):
+        return torch.zeros((n, 4), dtype=torch.bool, device=self.device)
+
+    def batch(self, indices, out=None):
+        """(x, target, edge, missing) for the subjects `indices` in the current epoch."""
+        indices = [int(i) for i in indices]
+        if self.cache:
+            x, t, e = prepare_batch([self.images[i] for i in indices], [self.labels[i] for i in indices],
+                                    [self.params(i) for i in indices], self.crop, out=out)
+            return x, t, e, self._missing(len(indices))
+        return self.prepare_staged(_collate_crops([self.source[i] for i in indices]), out=out)
+
+    def prepare_staged(self, crops, out=None):
+        """(image crops [B,4,*crop] float32, label crops [B,*crop] uint8, indices) from NpzCropSource -> the prepared batch"""
+        imgs, labs, idx = crops
+        if self.device.type == "cuda":
+            imgs, labs = imgs.to(self.device, non_blocking=True), labs.to(self.device, non_blocking=True)
+        zero = (0, 0, 0)
+        x, t, e = prepare_batch(list(imgs), list(labs), [self.params(i).at_origin(zero) for i in idx], self.crop, out=out)
+        return x, t, e, self._missing(len(idx))
+
+    def batches(self, index_batches, num_workers=0, out=None):
+        """Yield batch(b) for each index list b; out may be a callable evaluated per batch (e.g. a Trainer's captured inputs, which
+        exist only after the first steps).  A batch is prepared only when asked for, behind the work already on the stream."""
+        index_batches = [list(b) for b in index_batches]
+        get_out = out if callable(out) else (lambda: out)
+        if self.cache:
+            for b in index_batches:
+                yield self.batch(b, out=get_out())
+            return
+        loader = torch.utils.data.DataLoader(self.source, batch_sampler=index_batches, num_workers=int(num_workers),
+                                             collate_fn=_collate_crops, pin_memory=self.device.type == "cuda")
+        for crops in loader:
+            yield self.prepare_staged(crops, out=get_out())

@@ -104,6 +104,12 @@ def synthetic_sample(index: int, size: Sequence[int] = (128, 128, 128), seed: in
     """One BraTS-shaped sample: (x float32 [4,D,H,W], target int64 [D,H,W], edge int64 [D,H,W]).
     x is unit-variance noise plus a class-dependent offset; the target is three nested
     ellipsoids (background >> tumour, as in BraTS, which the CE class weights depend on)."""
+    x, target = synthetic_volume(index, size, seed)
+    return x, target, edge_codes(target)
+
+
+def synthetic_volume(index: int, size: Sequence[int] = (128, 128, 128), seed: int = 1000):
+    """(x, target) of synthetic_sample without the edge codes (utils.data.DeviceBraTS derives those per crop)."""
     d, h, w = size
     name = "sample%d_%d" % (seed, index)
     u = uniform01(name + "_c", 8)
@@ -118,7 +124,7 @@ def synthetic_sample(index: int, size: Sequence[int] = (128, 128, 128), seed: in
     n = 4 * d * h * w
     x = torch.from_numpy(((uniform01(name + "_x", n) * 2.0 - 1.0) * math.sqrt(3.0)).astype(np.float32)).reshape(4, d, h, w)
     x = x + 0.5 * target.float()[None] * torch.tensor([1.0, -1.0, 0.5, 0.25]).reshape(4, 1, 1, 1)
-    return x, target, edge_codes(target)
+    return x, target
 
 
 def synthetic_batch(indices: Sequence[int], size=(128, 128, 128), seed: int = 1000):

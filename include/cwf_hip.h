@@ -472,6 +472,31 @@ int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int 
                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * N3  training-batch preparation (utils/data.py prepare_batch / DeviceBraTS: crop, flips, intensity, label remap, edge codes)
+ * ---------------------------------------------------------------------------------------------- */
+/* One source subject: image fp32 [4][S0][S1][S2] and label uint8 [S0][S1][S2] (values 0..4), both contiguous device memory; crop
+ * origin o* in [0, max(S* - C*, 0)]; flip bit i reverses output axis i; intensity != 0 applies x * scale[c] + shift[c]. */
+struct cwf_prep_sample {
+  const float* image; const uint8_t* label;
+  int S0, S1, S2, o0, o1, o2, flip, intensity;
+  float scale[4], shift[4];
+};
+/* For each of the B samples (h_samples is HOST memory, passed to the kernels by value: nothing is copied host-to-device, so the call
+ * can be captured), with p the output voxel of the shared crop C0 x C1 x C2 and s_i = o_i + (flip_i ? C_i-1-p_i : p_i):
+ *   x      [b*x_bstride + c*C0*C1*C2 + p]  image[c][s] (0 where some s_i >= S_i), or fadd_rn(fmul_rn(that, scale[c]), shift[c])
+ *   target [b*t_bstride + p]               label[s] with 4 -> 3 (0 outside the volume), int64
+ *   edge   [b*e_bstride + p]               utils.synthetic.edge_codes of the cropped, flipped target, int64
+ * Eight samples per launch.  CWF_E_BADARG: B or a crop extent <= 0, an origin out of range, a flip mask > 7, a null or
+ * misaligned pointer (image / x 4 B, target / edge 8 B), a stride smaller than one sample; CWF_E_TOOLARGE: 2^31 output voxels or more. */
+int cwf_prepare_batch(const struct cwf_prep_sample* h_samples, int B, int C0, int C1, int C2, float* x, int64_t x_bstride,
+                      int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream);
+/* In place on one subject image fp32 [4][V]: over the voxels whose ((x0 + x1) + x2) + x3 > 0 (float32), each channel becomes
+ * float32((x - mean_c) / std_c) with the float64 mean and population std of that channel over those voxels (two passes); other voxels,
+ * and channels with std 0, are untouched.  ws: CWF_NORM_WS_DOUBLES doubles of device scratch. */
+#define CWF_NORM_WS_DOUBLES 2568
+int cwf_normalize_nonzero(float* image, int64_t V, double* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K11 fused Adam (amsgrad, L2 weight decay in the gradient)  torch.optim.Adam as used at train_no_amp.py:136,239
  *   table: device array of cwf_adam_desc; one launch updates every parameter.
  * ---------------------------------------------------------------------------------------------- */

@@ -18,7 +18,7 @@ struct ConvArgsB {
   // stats receives per (n, channel)  S1 = sum g*act'(h), S2 = sum g*act'(h)*h,  h = nb_x*nb_scale + nb_shift  -- what
   // cwf_in_bwd_stats would compute in a separate pass over g and x (norm.hip) -- instead of (sum y, sum y^2).
   const float* nb_x; int nb_ldc; const float* nb_scale; const float* nb_shift; float nb_slope;
-  // channel-grouped launches (cwf_conv_mfma_bf16_grouped: the three sub-regions' supervision-head convs as one launch): group q reads
+  // channel-grouped launches (cwf_conv with groups: the three sub-regions' supervision-head convs as one launch): group q reads
   // input channels [q*x_goff, q*x_goff + Cin) and writes output channels [q*y_goff, q*y_goff + Cout) of the same voxel rows, with its
   // own packed weights and bias; blockIdx.z = (group * N + n) * ncls + class.  groups == 0: an ordinary launch.
   int groups, x_goff, y_goff;
@@ -26,7 +26,7 @@ struct ConvArgsB {
   // conv16s, IN16 instantiation: the input as a bf16 image (16-byte granules, two per voxel) and the 16-byte zero page of its loaders
   const uint4* x16; const uint4* zero16;
   // pointwise stream kernel (1x1x1 forward): the output also as a bf16 image [N][V][Cout] (the operand image of a consuming layer's weight
-  // gradient, see cwf_conv_mfma_bf16_y16): one extra 8-byte store per lane
+  // gradient, see cwf_conv_args.y16): one extra 8-byte store per lane
   unsigned short* y16;
 };
 
@@ -49,3 +49,9 @@ __device__ __forceinline__ float act01(float v, float slope) { return fmaxf(v, v
 
 // conv_ws.hip: launches the weight-stationary kernel when the layer is one it takes (returns 1, status in *rc); 0 = not eligible.
 int cwf_try_conv_ws(int op, int x3, ConvArgsB& a, hipStream_t st, int* rc);
+
+// Host launchers behind the routers cwf_conv (conv_bf16.hip) and cwf_wgrad (wgrad_bf16.hip), which have checked the route.
+int conv_fp32_launch(const cwf_conv_args& d, hipStream_t st);        // conv_mfma.hip: the fp32 tap-table kernel
+int conv_stem_launch(const cwf_conv_args& d, hipStream_t st);        // conv_stem.hip: 4 -> 16 channels from the raw weight w_raw
+int conv_s2c16_launch(const cwf_conv_args& d, hipStream_t st);       // conv_s2.hip: stride 2, 16 -> 32 channels from w_raw
+int wgrad_fp32_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st);   // wgrad_mfma.hip: the fp32 slab kernel

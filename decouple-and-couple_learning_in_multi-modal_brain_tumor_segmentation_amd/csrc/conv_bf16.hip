@@ -1262,61 +1262,6 @@ int launch_cfg(const ConvArgsB& a, hipStream_t st) {
 }
 }  // namespace
 
-extern "C" int cwf_conv_mfma_bf16_nb(int op, int x3, const float* x, int x_ldc, const void* wpk16, const float* bias,
-                                     float* y, int y_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                                     const float* residual, int r_ldc, const float* out_scale, double* stats,
-                                     const float* nb_x, int nb_ldc, const float* nb_scale, const float* nb_shift, float nb_slope,
-                                     int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream);
-
-extern "C" int cwf_conv_mfma_bf16(int op, int x3, const float* x, int x_ldc, const void* wpk16, const float* bias,
-                                  float* y, int y_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                                  const float* residual, int r_ldc, const float* out_scale, double* stats,
-                                  int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream) {
-  return cwf_conv_mfma_bf16_nb(op, x3, x, x_ldc, wpk16, bias, y, y_ldc, in_scale, in_shift, in_slope, residual, r_ldc, out_scale, stats,
-                               nullptr, 0, nullptr, nullptr, 1.f, N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, stream);
-}
-
-static int conv_bf16_impl(int op, int x3, const float* x, int x_ldc, const void* wpk16, const float* bias,
-                          float* y, int y_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                          const float* residual, int r_ldc, const float* out_scale, double* stats,
-                          const float* nb_x, int nb_ldc, const float* nb_scale, const float* nb_shift, float nb_slope,
-                          int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream,
-                          const void* x16, const void* zero16, void* y16 = nullptr);
-
-extern "C" int cwf_conv_mfma_bf16_nb(int op, int x3, const float* x, int x_ldc, const void* wpk16, const float* bias,
-                                     float* y, int y_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                                     const float* residual, int r_ldc, const float* out_scale, double* stats,
-                                     const float* nb_x, int nb_ldc, const float* nb_scale, const float* nb_shift, float nb_slope,
-                                     int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream) {
-  return conv_bf16_impl(op, x3, x, x_ldc, wpk16, bias, y, y_ldc, in_scale, in_shift, in_slope, residual, r_ldc, out_scale, stats,
-                        nb_x, nb_ldc, nb_scale, nb_shift, nb_slope, N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, stream, nullptr, nullptr);
-}
-
-// cwf_conv_mfma_bf16 for a 1x1x1 conv that also writes its output as a bf16 image y16 [N][Do*Ho*Wo][Cout] (DeUp_Cat.conv3, cls_wise_former.py:
-// 716-729: its output is the un-normalised input of the next block's first conv, whose weight gradient reads that image).  CWF_E_BADARG
-// if the layer is not one the pointwise stream kernel takes (the caller then converts with cwf_to_bf16).
-extern "C" int cwf_conv_mfma_bf16_y16(int op, int x3, const float* x, int x_ldc, const void* wpk16, const float* bias,
-                                      float* y, int y_ldc, void* y16, const float* in_scale, const float* in_shift, float in_slope,
-                                      const float* residual, int r_ldc, double* stats,
-                                      int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream) {
-  if (!y16) return CWF_E_BADARG;
-  return conv_bf16_impl(op, x3, x, x_ldc, wpk16, bias, y, y_ldc, in_scale, in_shift, in_slope, residual, r_ldc, nullptr, stats,
-                        nullptr, 0, nullptr, nullptr, 1.f, N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, stream, nullptr, nullptr, y16);
-}
-
-// The same conv with its INPUT given as a bf16 image x16 [N][Di][Hi][Wi][16] (single-bf16 operand launches of the 3x3x3 stride-1
-// 16 -> 16 full-resolution layers without prologue, i.e. their data gradients: x16 = the bf16 image of dy that the producer of dy wrote,
-// cwf_in_bwd_apply_ex).  x (fp32) is not read and may be NULL.  zero16: 16 zero bytes (padding source of the LDS-DMA loaders).
-extern "C" int cwf_conv_mfma_bf16_in16(int op, const void* x16, const void* zero16, const void* wpk16, const float* bias,
-                                       float* y, int y_ldc, const float* residual, int r_ldc, double* stats,
-                                       const float* nb_x, int nb_ldc, const float* nb_scale, const float* nb_shift, float nb_slope,
-                                       int N, int D, int H, int W, void* stream) {
-  if (!x16 || !zero16 || ((uintptr_t)x16 & 15) || ((uintptr_t)zero16 & 15)) return CWF_E_BADARG;
-  if (op != CWF_CONV3_S1 || (int64_t)D * H * W < 32768 || (int64_t)N * D * H * W >= (1ll << 30)) return CWF_E_BADARG;
-  return conv_bf16_impl(op, 0, reinterpret_cast<const float*>(x16), 16, wpk16, bias, y, y_ldc, nullptr, nullptr, 1.f, residual, r_ldc, nullptr, stats,
-                        nb_x, nb_ldc, nb_scale, nb_shift, nb_slope, N, D, H, W, 16, D, H, W, 16, stream, x16, zero16);
-}
-
 // The extent choose_cfg tiles (per output-parity class) and the class count of a launch: the output extent, or for the eight-class
 // launches (ConvTranspose forward, stride-2 data gradient) the extent of one class.
 static int cfg_extent(int op, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int cd[3]) {
@@ -1340,59 +1285,60 @@ extern "C" int cwf_debug_conv_bf16_cfg(int op, int N, int Di, int Hi, int Wi, in
   return 0;
 }
 
-static int conv_bf16_impl(int op, int x3, const float* x, int x_ldc, const void* wpk16, const float* bias,
-                          float* y, int y_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                          const float* residual, int r_ldc, const float* out_scale, double* stats,
-                          const float* nb_x, int nb_ldc, const float* nb_scale, const float* nb_shift, float nb_slope,
-                          int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream,
-                          const void* x16, const void* zero16, void* y16) {
-  if (!x || !wpk16 || !y || N <= 0 || Cin <= 0 || Cout <= 0) return CWF_E_BADARG;
-  if (nb_x && (!stats || !nb_scale || !nb_shift || nb_ldc < Cout)) return CWF_E_BADARG;
+// layers with Cin, Cout <= 16 are packed in conv16's tap order (c16_tap)
+static void c16_tap_order(ConvGeom& g) {
+  int nat[27];
+  for (int t = 0; t < 27; ++t) nat[t] = g.tapofs[t];
+  for (int t = 0; t < 27; ++t) g.tapofs[t] = nat[c16_tap(t)];
+}
+
+// The split-bf16 launches that share ConvArgsB, in order of preference: conv16s on a bf16 input image (x16), the pointwise streams,
+// the weight-stationary kernel, conv16s, the tap-table kernel.
+static int conv_bf16_impl(const cwf_conv_args& d, hipStream_t st) {
+  const int op = d.op, x3 = d.precision == CWF_BF16X3, N = d.N, Cin = d.Cin, Cout = d.Cout, y_ldc = d.y_ldc;
+  // a bf16 input image stands in for x: conv16s reads it through its LDS-DMA loaders (16-byte granules, two per voxel)
+  const float* x = d.x16 ? reinterpret_cast<const float*>(d.x16) : d.x;
+  const int x_ldc = d.x16 ? 16 : d.x_ldc;
+  if (!x || !d.wpk || !d.y || N <= 0 || Cin <= 0 || Cout <= 0) return CWF_E_BADARG;
+  if (d.nb_x && (!d.stats || !d.nb_scale || !d.nb_shift || d.nb_ldc < Cout)) return CWF_E_BADARG;
   if ((Cin & 3) || (x_ldc & 3) || x_ldc < Cin || y_ldc < Cout) return CWF_E_ALIGN;
-  if (((uintptr_t)x & 15) || ((uintptr_t)wpk16 & 15)) return CWF_E_ALIGN;
-  if (in_scale && !in_shift) return CWF_E_BADARG;
+  if (((uintptr_t)x & 15) || ((uintptr_t)d.wpk & 15)) return CWF_E_ALIGN;
+  if (d.in_scale && !d.in_shift) return CWF_E_BADARG;
   ConvArgsB a;
   int cd[3];
-  const int ncls = cfg_extent(op, Di, Hi, Wi, Do, Ho, Wo, cd);
+  const int ncls = cfg_extent(op, d.Di, d.Hi, d.Wi, d.Do, d.Ho, d.Wo, cd);
   const TileCfg c = choose_cfg(op, cd, ncls, N, cdiv(Cout, 16));
-  int rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, c.MT * c.WM);
+  int rc = cwf_build_geom(a.g, op, N, d.Di, d.Hi, d.Wi, Cin, x_ldc, d.Do, d.Ho, d.Wo, Cout, y_ldc, c.MT * c.WM);
   if (rc) return rc;
-  a.x = x; a.wpk = reinterpret_cast<const uint4*>(wpk16); a.bias = bias; a.y = y; a.in_scale = in_scale; a.in_shift = in_shift;
-  a.in_slope = in_slope; a.residual = residual; a.r_ldc = r_ldc; a.out_scale = out_scale; a.stats = stats;
-  a.nb_x = nb_x; a.nb_ldc = nb_ldc; a.nb_scale = nb_scale; a.nb_shift = nb_shift; a.nb_slope = nb_slope;
+  a.x = x; a.wpk = reinterpret_cast<const uint4*>(d.wpk); a.bias = d.bias; a.y = d.y; a.in_scale = d.in_scale; a.in_shift = d.in_shift;
+  a.in_slope = d.x16 ? 1.f : d.in_slope; a.residual = d.residual; a.r_ldc = d.r_ldc; a.out_scale = d.out_scale; a.stats = d.stats;
+  a.nb_x = d.nb_x; a.nb_ldc = d.nb_ldc; a.nb_scale = d.nb_scale; a.nb_shift = d.nb_shift; a.nb_slope = d.nb_x ? d.nb_slope : 1.f;
   a.groups = 0; a.x_goff = 0; a.y_goff = 0;
-  a.x16 = reinterpret_cast<const uint4*>(x16); a.zero16 = reinterpret_cast<const uint4*>(zero16);
-  a.y16 = reinterpret_cast<unsigned short*>(y16);
+  a.x16 = reinterpret_cast<const uint4*>(d.x16); a.zero16 = reinterpret_cast<const uint4*>(d.zero16);
+  a.y16 = reinterpret_cast<unsigned short*>(d.y16);
   for (int q = 0; q < 3; ++q) { a.wpk_g[q] = nullptr; a.bias_g[q] = nullptr; }
-  hipStream_t st = cwf_stream(stream);
-  if (x16) {                                           // (cwf_conv_mfma_bf16_in16 has checked the layer)
-    int nat[27];
-    for (int t = 0; t < 27; ++t) nat[t] = a.g.tapofs[t];
-    for (int t = 0; t < 27; ++t) a.g.tapofs[t] = nat[c16_tap(t)];
-    rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, 16);
+  if (d.x16) {                                         // (cwf_conv has checked the layer)
+    c16_tap_order(a.g);
+    rc = cwf_build_geom(a.g, op, N, d.Di, d.Hi, d.Wi, Cin, x_ldc, d.Do, d.Ho, d.Wo, Cout, y_ldc, 16);
     if (rc) return rc;
     return launch_conv16s<false, true>(a, st);
   }
   {
     int ks, nt;
     if (pw_eligible(op, a, &ks, &nt)) {                   // 1x1x1 / ConvTranspose streams: no LDS staging (pw_conv_kernel)
-      if (y16 && (op != CWF_CONV1 || (Cout & 3) || ((uintptr_t)y16 & 7))) return CWF_E_BADARG;
+      if (d.y16 && (op != CWF_CONV1 || (Cout & 3) || ((uintptr_t)d.y16 & 7))) return CWF_E_BADARG;
       return x3 ? dispatch_pw<true>(op, a, st, ks, nt) : dispatch_pw<false>(op, a, st, ks, nt);
     }
-    if (y16) return CWF_E_BADARG;                        // the bf16 side output is the pointwise stream kernel's
+    if (d.y16) return CWF_E_BADARG;                      // the bf16 side output is the pointwise stream kernel's
   }
   {
     int rcw = 0;                                           // 32 / 64 / 128-channel 3x3x3 layers: weight-stationary kernel (conv_ws.hip)
     if (cwf_try_conv_ws(op, x3, a, st, &rcw)) return rcw;
   }
-  if (op == CWF_CONV3_S1 && Cin <= 16 && Cout <= 16) {      // these layers are packed in conv16's tap order (c16_tap)
-    int nat[27];
-    for (int t = 0; t < 27; ++t) nat[t] = a.g.tapofs[t];
-    for (int t = 0; t < 27; ++t) a.g.tapofs[t] = nat[c16_tap(t)];
-  }
-  if (op == CWF_CONV3_S1 && Cin <= 16 && Cout <= 16 && (int64_t)Do * Ho * Wo >= 32768) {
+  if (op == CWF_CONV3_S1 && Cin <= 16 && Cout <= 16) c16_tap_order(a.g);
+  if (op == CWF_CONV3_S1 && Cin <= 16 && Cout <= 16 && (int64_t)d.Do * d.Ho * d.Wo >= 32768) {
     // full-resolution 16-channel convs: the persistent register-resident-weight kernel (tile 4x4x16)
-    rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, 16);
+    rc = cwf_build_geom(a.g, op, N, d.Di, d.Hi, d.Wi, Cin, x_ldc, d.Do, d.Ho, d.Wo, Cout, y_ldc, 16);
     if (rc) return rc;
     return x3 ? launch_conv16s<true>(a, st) : launch_conv16s<false>(a, st);
   }
@@ -1403,41 +1349,86 @@ static int conv_bf16_impl(int op, int x3, const float* x, int x_ldc, const void*
   return CWF_E_BADARG;
 }
 
-// Channel-grouped 3x3x3 stride-1 conv (forward, or data gradient through transposed packed weights): `groups` (2 or 3) independent
-// convs Cin -> Cout on channel groups of one input tensor, written into channel groups of one output tensor, ONE launch (the
-// supervision heads of the three sub-regions: SuperviseLabel.py:58-81, EdgeSuperviseLabel.py:56-76 -- 24 tiny layers per step whose
-// launches, not their arithmetic, are the cost).  Bias only: no normalising prologue, residual, out_scale or statistics.
-extern "C" int cwf_conv_mfma_bf16_grouped(int op, int x3, const float* x, int x_ldc, int x_goff, const void* const* wpk16, const float* const* bias,
-                                          float* y, int y_ldc, int y_goff, int groups,
-                                          int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream) {
-  if (!x || !wpk16 || !y || N <= 0 || Cin <= 0 || Cout <= 0 || groups < 2 || groups > 3) return CWF_E_BADARG;
-  if (op != CWF_CONV3_S1) return CWF_E_BADARG;
+// Channel-grouped 3x3x3 stride-1 conv, ONE tap-table launch for `groups` (2 or 3) convs (the supervision heads of the three
+// sub-regions: 24 tiny layers per step whose launches, not their arithmetic, are the cost).
+static int conv_grouped_impl(const cwf_conv_args& d, hipStream_t st) {
+  const int op = d.op, x3 = d.precision == CWF_BF16X3, groups = d.groups, N = d.N, Cin = d.Cin, Cout = d.Cout;
+  const int x_ldc = d.x_ldc, y_ldc = d.y_ldc, x_goff = d.x_goff, y_goff = d.y_goff;
+  if (!d.x || !d.y || N <= 0 || Cin <= 0 || Cout <= 0) return CWF_E_BADARG;
   if ((Cin & 3) || (x_ldc & 3) || (x_goff & 3) || x_ldc < (groups - 1) * x_goff + Cin || y_ldc < (groups - 1) * y_goff + Cout) return CWF_E_ALIGN;
-  if ((uintptr_t)x & 15) return CWF_E_ALIGN;
+  if ((uintptr_t)d.x & 15) return CWF_E_ALIGN;
   ConvArgsB a;
   int cd[3];
-  TileCfg c = choose_cfg(op, cd, cfg_extent(op, Di, Hi, Wi, Do, Ho, Wo, cd), N * groups, cdiv(Cout, 16));
-  int rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, c.MT * c.WM);
+  TileCfg c = choose_cfg(op, cd, cfg_extent(op, d.Di, d.Hi, d.Wi, d.Do, d.Ho, d.Wo, cd), N * groups, cdiv(Cout, 16));
+  int rc = cwf_build_geom(a.g, op, N, d.Di, d.Hi, d.Wi, Cin, x_ldc, d.Do, d.Ho, d.Wo, Cout, y_ldc, c.MT * c.WM);
   if (rc) return rc;
-  a.x = x; a.wpk = nullptr; a.bias = nullptr; a.y = y; a.in_scale = nullptr; a.in_shift = nullptr; a.in_slope = 1.f;
+  a.x = d.x; a.wpk = nullptr; a.bias = nullptr; a.y = d.y; a.in_scale = nullptr; a.in_shift = nullptr; a.in_slope = 1.f;
   a.residual = nullptr; a.r_ldc = 0; a.out_scale = nullptr; a.stats = nullptr;
   a.nb_x = nullptr; a.nb_ldc = 0; a.nb_scale = nullptr; a.nb_shift = nullptr; a.nb_slope = 1.f;
   a.groups = groups; a.x_goff = x_goff; a.y_goff = y_goff;
   a.x16 = nullptr; a.zero16 = nullptr; a.y16 = nullptr;
   for (int q = 0; q < 3; ++q) {
-    a.wpk_g[q] = q < groups ? reinterpret_cast<const uint4*>(wpk16[q]) : nullptr;
-    a.bias_g[q] = (q < groups && bias) ? bias[q] : nullptr;
-    if (q < groups && (!wpk16[q] || ((uintptr_t)wpk16[q] & 15))) return CWF_E_ALIGN;
+    a.wpk_g[q] = q < groups ? reinterpret_cast<const uint4*>(d.wpk_g[q]) : nullptr;
+    a.bias_g[q] = q < groups ? d.bias_g[q] : nullptr;
+    if (q < groups && (!d.wpk_g[q] || ((uintptr_t)d.wpk_g[q] & 15))) return CWF_E_ALIGN;
   }
-  if (Cin <= 16 && Cout <= 16) {                           // these layers are packed in conv16's tap order (c16_tap)
-    int nat[27];
-    for (int t = 0; t < 27; ++t) nat[t] = a.g.tapofs[t];
-    for (int t = 0; t < 27; ++t) a.g.tapofs[t] = nat[c16_tap(t)];
-  }
-  hipStream_t st = cwf_stream(stream);
+  if (Cin <= 16 && Cout <= 16) c16_tap_order(a.g);
 #define CWF_CFG(mt, nt, wm) if (c.MT == mt && c.NT == nt && c.WM == wm) return x3 ? launch_cfg<mt, nt, wm, true>(a, st) : launch_cfg<mt, nt, wm, false>(a, st);
   CWF_CFG(4, 4, 1) CWF_CFG(2, 4, 2) CWF_CFG(2, 4, 4) CWF_CFG(4, 2, 4) CWF_CFG(4, 1, 4)
   CWF_CFG(1, 4, 4) CWF_CFG(1, 2, 4) CWF_CFG(1, 2, 2) CWF_CFG(1, 1, 4)
 #undef CWF_CFG
   return CWF_E_BADARG;
+}
+
+// The one place that chooses a forward / data-gradient kernel (include/cwf_hip.h, struct cwf_conv_args).
+extern "C" int cwf_conv(const struct cwf_conv_args* args, void* stream) {
+  if (!args) return CWF_E_BADARG;
+  const cwf_conv_args& d = *args;
+  if (d.precision != CWF_FP32 && d.precision != CWF_BF16X3 && d.precision != CWF_BF16) return CWF_E_BADARG;
+  const bool fp32 = d.precision == CWF_FP32;
+  hipStream_t st = cwf_stream(stream);
+  if (d.groups) {
+    if (d.groups < 2 || d.groups > 3 || d.op != CWF_CONV3_S1 || d.in_scale || d.residual || d.out_scale || d.stats || d.nb_x || d.x16 ||
+        d.y16 || d.w_raw)
+      return CWF_E_BADARG;
+    if (!fp32) return conv_grouped_impl(d, st);
+    for (int q = 0; q < d.groups; ++q) {                   // exact fp32: one launch per group
+      cwf_conv_args g = d;
+      g.groups = 0; g.x = d.x + q * d.x_goff; g.y = d.y + q * d.y_goff; g.wpk = d.wpk_g[q]; g.bias = d.bias_g[q];
+      const int rc = conv_fp32_launch(g, st);
+      if (rc) return rc;
+    }
+    return 0;
+  }
+  if (d.x16) {
+    if (d.precision != CWF_BF16 || d.in_scale || d.out_scale || d.y16 || !d.zero16 || ((uintptr_t)d.x16 & 15) || ((uintptr_t)d.zero16 & 15))
+      return CWF_E_BADARG;
+    if (d.op != CWF_CONV3_S1 || d.Cin != 16 || d.Cout != 16 || d.Do != d.Di || d.Ho != d.Hi || d.Wo != d.Wi ||
+        (int64_t)d.Di * d.Hi * d.Wi < 32768 || (int64_t)d.N * d.Di * d.Hi * d.Wi >= (1ll << 30))
+      return CWF_E_BADARG;
+    return conv_bf16_impl(d, st);
+  }
+  if (d.y16) {
+    if (d.nb_x || d.out_scale) return CWF_E_BADARG;
+    if (!fp32 && d.op == CWF_CONV1) {                      // the pointwise stream kernel writes the image in the same launch
+      const int rc = conv_bf16_impl(d, st);
+      if (rc != CWF_E_BADARG) return rc;
+    }
+    cwf_conv_args f = d;                                   // any other layer: the same launch, then a conversion pass
+    f.y16 = nullptr;
+    const int rc = cwf_conv(&f, stream);
+    if (rc) return rc;
+    return cwf_to_bf16(d.y, d.y_ldc, nullptr, nullptr, 1.f, d.y16, d.N, (int64_t)d.Do * d.Ho * d.Wo, d.Cout, stream);
+  }
+  const int64_t vo = (int64_t)d.Do * d.Ho * d.Wo;
+  if (d.w_raw && !fp32 && !d.in_scale && !d.residual && !d.nb_x) {
+    // the stem: K = 8 taps x 4 channels (conv_stem.hip), straight from the raw weight
+    if (d.op == CWF_CONV3_S1 && d.Cin == 4 && d.Cout == 16 && vo >= 32768) return conv_stem_launch(d, st);
+    // the first down-sampling layer: persistent prefetching kernel with parity-split halo rows (conv_s2.hip)
+    if (d.op == CWF_CONV3_S2 && d.Cin == 16 && d.Cout == 32 && !d.out_scale && vo >= 32768 &&
+        d.Do == (d.Di + 1) / 2 && d.Ho == (d.Hi + 1) / 2 && d.Wo == (d.Wi + 1) / 2)
+      return conv_s2c16_launch(d, st);
+  }
+  if (fp32) return d.nb_x ? CWF_E_BADARG : conv_fp32_launch(d, st);
+  return conv_bf16_impl(d, st);
 }

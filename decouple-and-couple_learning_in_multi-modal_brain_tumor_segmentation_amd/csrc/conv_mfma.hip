@@ -16,7 +16,7 @@
 //
 // Reference ops replaced: nn.Conv3d / nn.ConvTranspose3d + InstanceNorm3d + ReLU/LeakyReLU chains at
 // Unet_skipconnection.py:22-78, cls_wise_former.py:157-204,257-273,284-324,614-754, SuperviseLabel.py:10-51.
-#include "common.h"
+#include "conv_args.h"
 
 struct ConvArgs {
   ConvGeom g;
@@ -283,11 +283,11 @@ int launch_cfg(const ConvArgs& a, hipStream_t st) {
 }
 }  // namespace
 
-extern "C" int cwf_conv_mfma(int op, const float* x, int x_ldc, const float* wpk, const float* bias,
-                             float* y, int y_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                             const float* residual, int r_ldc, const float* out_scale, double* stats,
-                             int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream) {
-  if (!x || !wpk || !y || N <= 0 || Cin <= 0 || Cout <= 0) return CWF_E_BADARG;
+int conv_fp32_launch(const cwf_conv_args& d, hipStream_t st) {
+  const int op = d.op, N = d.N, Di = d.Di, Hi = d.Hi, Wi = d.Wi, Cin = d.Cin, Do = d.Do, Ho = d.Ho, Wo = d.Wo, Cout = d.Cout;
+  const float* x = d.x; const int x_ldc = d.x_ldc, y_ldc = d.y_ldc;
+  const float* wpk = static_cast<const float*>(d.wpk);
+  if (!x || !wpk || !d.y || N <= 0 || Cin <= 0 || Cout <= 0) return CWF_E_BADARG;
   if ((Cin & 3) || (x_ldc & 3) || x_ldc < Cin || y_ldc < Cout) return CWF_E_ALIGN;
   if (((uintptr_t)x & 15) || ((uintptr_t)wpk & 15)) return CWF_E_ALIGN;
   ConvArgs a;
@@ -298,10 +298,9 @@ extern "C" int cwf_conv_mfma(int op, const float* x, int x_ldc, const float* wpk
   const TileCfg c = choose_cfg(op, cd, ncls, N, cdiv(Cout, 16));
   int rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, c.MT * c.WM);
   if (rc) return rc;
-  a.x = x; a.wpk = wpk; a.bias = bias; a.y = y; a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope;
-  a.residual = residual; a.r_ldc = r_ldc; a.out_scale = out_scale; a.stats = stats;
-  if (in_scale && !in_shift) return CWF_E_BADARG;
-  hipStream_t st = cwf_stream(stream);
+  a.x = x; a.wpk = wpk; a.bias = d.bias; a.y = d.y; a.in_scale = d.in_scale; a.in_shift = d.in_shift; a.in_slope = d.in_slope;
+  a.residual = d.residual; a.r_ldc = d.r_ldc; a.out_scale = d.out_scale; a.stats = d.stats;
+  if (d.in_scale && !d.in_shift) return CWF_E_BADARG;
 #define CWF_CFG(mt, nt, wm) if (c.MT == mt && c.NT == nt && c.WM == wm) return launch_cfg<mt, nt, wm>(a, st);
   CWF_CFG(4, 4, 1) CWF_CFG(2, 4, 2) CWF_CFG(2, 4, 4) CWF_CFG(4, 2, 4) CWF_CFG(4, 1, 4)
   CWF_CFG(1, 4, 4) CWF_CFG(1, 2, 4) CWF_CFG(1, 2, 2) CWF_CFG(1, 1, 4)

@@ -10,7 +10,7 @@
 //     [32][16][3][3][3] at kernel start), the lo fragments lane-linear in LDS;
 //   * wave w owns M-tile (td, th) = (w >> 1, w & 1) and both 16-channel output tiles; bias starts the accumulators; the InstanceNorm
 //     statistics of the output leave as one atomic instruction per workgroup and sample.
-#include "common.h"
+#include "conv_args.h"
 #include <cstdlib>
 
 typedef __bf16 bf16x8_d __attribute__((ext_vector_type(8)));
@@ -217,12 +217,14 @@ __global__ __launch_bounds__(512) void conv_s2c16_kernel(const S2Args a) {
 
 // y = conv3x3x3 stride 2 (x; w) + bias (+ statistics of y) for 16 -> 32 channels.  x [N][Di][Hi][Wi][16] fp32 (ldc x_ldc), w the raw
 // nn.Conv3d weight [32][16][3][3][3], y [N][Do][Ho][Wo][32] (ldc y_ldc), Do = (Di + 1) / 2 ...; stats [N][32][2] nullable.
-extern "C" int cwf_conv_s2c16_bf16(int x3, const float* x, int x_ldc, const float* w, const float* bias, float* y, int y_ldc, double* stats,
-                                   int N, int Di, int Hi, int Wi, void* stream) {
+int conv_s2c16_launch(const cwf_conv_args& d, hipStream_t st) {
+  const bool x3 = d.precision == CWF_BF16X3;
+  const float* x = d.x; const float* w = d.w_raw; float* y = d.y;
+  const int x_ldc = d.x_ldc, y_ldc = d.y_ldc, N = d.N, Di = d.Di, Hi = d.Hi, Wi = d.Wi;
   if (!x || !w || !y || N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0) return CWF_E_BADARG;
   if ((x_ldc & 3) || x_ldc < 16 || y_ldc < 32 || ((uintptr_t)x & 15)) return CWF_E_ALIGN;
   S2Args a;
-  a.x = x; a.x_ldc = x_ldc; a.w = w; a.bias = bias; a.y = y; a.y_ldc = y_ldc; a.stats = stats;
+  a.x = x; a.x_ldc = x_ldc; a.w = w; a.bias = d.bias; a.y = y; a.y_ldc = y_ldc; a.stats = d.stats;
   a.N = N; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Do = (Di + 1) / 2; a.Ho = (Hi + 1) / 2; a.Wo = (Wi + 1) / 2;
   a.tiles_d = cdiv(a.Do, 2); a.tiles_h = cdiv(a.Ho, 2); a.tiles_w = cdiv(a.Wo, 16);
   a.total_tiles = N * a.tiles_d * a.tiles_h * a.tiles_w;
@@ -230,8 +232,8 @@ extern "C" int cwf_conv_s2c16_bf16(int x3, const float* x, int x_ldc, const floa
   a.tiles_per_wg = cdiv(a.total_tiles, grid);
   grid = cdiv(a.total_tiles, a.tiles_per_wg);
   const size_t lds = (size_t)2 * (x3 ? 2 : 1) * S2_IMG * 2 + (x3 ? 14 * 2 * 64 * 16 : 0) + 4 * 64 * sizeof(float);      // two image buffers
-  if (x3) { CWF_MAX_LDS_ONCE((&conv_s2c16_kernel<true>)); hipLaunchKernelGGL(conv_s2c16_kernel<true>, dim3(grid), dim3(512), lds, cwf_stream(stream), a); }
-  else { CWF_MAX_LDS_ONCE((&conv_s2c16_kernel<false>)); hipLaunchKernelGGL(conv_s2c16_kernel<false>, dim3(grid), dim3(512), lds, cwf_stream(stream), a); }
+  if (x3) { CWF_MAX_LDS_ONCE((&conv_s2c16_kernel<true>)); hipLaunchKernelGGL(conv_s2c16_kernel<true>, dim3(grid), dim3(512), lds, st, a); }
+  else { CWF_MAX_LDS_ONCE((&conv_s2c16_kernel<false>)); hipLaunchKernelGGL(conv_s2c16_kernel<false>, dim3(grid), dim3(512), lds, st, a); }
   CWF_LAUNCH_CHECK();
   return 0;
 }

@@ -11,7 +11,7 @@
 //     registers; bias starts the accumulator; dropout3d's per-(sample, channel) scale and the InstanceNorm statistics of the output
 //     are the epilogue, as in conv16s; a workgroup owns a contiguous run of tiles and its statistics leave as one atomic instruction
 //     per sample.
-#include "common.h"
+#include "conv_args.h"
 #include <cstdlib>
 
 typedef __bf16 bf16x8_s __attribute__((ext_vector_type(8)));
@@ -190,12 +190,14 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemArgs a) {
 
 // y = (conv3x3x3(x; w) + bias) * out_scale (+ statistics of y): the stem layer.  x [N][D][H][W][4 (ldc x_ldc)] fp32, w the raw
 // nn.Conv3d weight [16][4][3][3][3], y [N][D][H][W][16 (ldc y_ldc)]; out_scale [N][16] and stats [N][16][2] nullable.
-extern "C" int cwf_conv_stem_bf16(int x3, const float* x, int x_ldc, const float* w, const float* bias, float* y, int y_ldc,
-                                  const float* out_scale, double* stats, int N, int D, int H, int W, void* stream) {
+int conv_stem_launch(const cwf_conv_args& d, hipStream_t st) {
+  const bool x3 = d.precision == CWF_BF16X3;
+  const float* x = d.x; const float* w = d.w_raw; float* y = d.y;
+  const int x_ldc = d.x_ldc, y_ldc = d.y_ldc, N = d.N, D = d.Di, H = d.Hi, W = d.Wi;
   if (!x || !w || !y || N <= 0 || D <= 0 || H <= 0 || W <= 0) return CWF_E_BADARG;
   if ((x_ldc & 3) || x_ldc < 4 || y_ldc < 16 || ((uintptr_t)x & 15)) return CWF_E_ALIGN;
   StemArgs a;
-  a.x = x; a.x_ldc = x_ldc; a.w = w; a.bias = bias; a.y = y; a.y_ldc = y_ldc; a.out_scale = out_scale; a.stats = stats;
+  a.x = x; a.x_ldc = x_ldc; a.w = w; a.bias = d.bias; a.y = y; a.y_ldc = y_ldc; a.out_scale = d.out_scale; a.stats = d.stats;
   a.N = N; a.D = D; a.H = H; a.W = W;
   a.tiles_d = cdiv(D, 4); a.tiles_h = cdiv(H, 4); a.tiles_w = cdiv(W, 16);
   a.total_tiles = N * a.tiles_d * a.tiles_h * a.tiles_w;
@@ -203,8 +205,8 @@ extern "C" int cwf_conv_stem_bf16(int x3, const float* x, int x_ldc, const float
   if (grid > a.total_tiles) grid = a.total_tiles;
   a.tiles_per_wg = cdiv(a.total_tiles, grid);
   grid = cdiv(a.total_tiles, a.tiles_per_wg);
-  if (x3) hipLaunchKernelGGL(stem_conv_kernel<true>, dim3(grid), dim3(256), 0, cwf_stream(stream), a);
-  else hipLaunchKernelGGL(stem_conv_kernel<false>, dim3(grid), dim3(256), 0, cwf_stream(stream), a);
+  if (x3) hipLaunchKernelGGL(stem_conv_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(stem_conv_kernel<false>, dim3(grid), dim3(256), 0, st, a);
   CWF_LAUNCH_CHECK();
   return 0;
 }

@@ -97,7 +97,7 @@ __global__ void norm_act_add_kernel(const float* __restrict__ x, int x_ldc, cons
 
 // dx = scale*(g - S1/V - xhat*S2/V) (+ dx_add), g = dy*act'(xhat).
 // Optional bf16 side outputs (the operands of the 16-channel weight-gradient / data-gradient kernels that take bf16 tensors,
-// cwf_wgrad16_bf16): DX16 -- dx rounded to bf16 (the gradient the producing layer's kernels consume; they round it to bf16
+// cwf_wgrad / cwf_conv with xa16, dy16 / x16): DX16 -- dx rounded to bf16 (the gradient the producing layer's kernels consume; they round it to bf16
 // themselves otherwise); XA16 -- bf16(act(xhat)), the activated input of THIS layer, i.e. the x operand of its weight gradient
 // (the weight-gradient kernels recompute it from x otherwise).  F32 = false skips the fp32 dx (no reader left).
 template <bool F32, bool DX16, bool XA16>

@@ -181,5 +181,5 @@ extern "C" int cwf_copy_strided(const float* x, int x_ldc, float* y, int y_ldc, 
   return 0;
 }
 
-extern "C" int cwf_version(void) { return 2; }
+extern "C" int cwf_version(void) { return 3; }
 extern "C" const char* cwf_arch(void) { return "gfx950"; }

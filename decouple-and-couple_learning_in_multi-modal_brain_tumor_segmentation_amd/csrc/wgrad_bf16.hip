@@ -8,7 +8,7 @@
 // (EXEC is all ones at every such read: all branches around them are wave-uniform.)
 // X3 = true: x = xh + xl, dy = dh + dl -> xh.dh + xh.dl + xl.dh (fp32 accumulate);  X3 = false: xh.dh only.
 // Work split, persistent tile walk, partial-slab layout and the reduce step are those of wgrad_mfma.hip.
-#include "common.h"
+#include "conv_args.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -32,7 +32,7 @@ struct WgArgsB {
   int ngroups, tiles_per_split, total_tiles;
   int64_t slab_floats;
   int cls_slab_base[8];
-  // grouped launches (cwf_wgrad_mfma_bf16_grouped: the three sub-regions' head layers): blockIdx.z = group, each with its own
+  // grouped launches (cwf_wgrad with groups: the three sub-regions' head layers): blockIdx.z = group, each with its own
   // x / dy / slab buffer; single-class (3x3x3 stride-1) operators only.  groups == 0: an ordinary launch (blockIdx.z = class)
   int groups;
   const float* x_g[3]; const float* dy_g[3]; float* partial_g[3];
@@ -884,8 +884,9 @@ __global__ __launch_bounds__(256 + 64 * W16D_LW) void wgrad16d_kernel(const W16d
   }
 }
 
-extern "C" int cwf_wgrad16_bf16(const void* xa16, const void* dy16, const void* zero16, float* partial,
-                                int N, int D, int H, int W, int* nsplit_used, void* stream) {
+static int wgrad16_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
+  const void* xa16 = d.xa16; const void* dy16 = d.dy16; const void* zero16 = d.zero16; float* partial = d.partial;
+  const int N = d.N, D = d.Di, H = d.Hi, W = d.Wi;
   if (!xa16 || !dy16 || !zero16 || !partial || N <= 0 || D <= 0 || H <= 0 || W <= 0) return CWF_E_BADARG;
   if (((uintptr_t)xa16 & 15) || ((uintptr_t)dy16 & 15) || ((uintptr_t)zero16 & 15) || ((uintptr_t)partial & 15)) return CWF_E_ALIGN;
   if ((int64_t)N * D * H * W >= (1ll << 30)) return CWF_E_TOOLARGE;
@@ -899,7 +900,7 @@ extern "C" int cwf_wgrad16_bf16(const void* xa16, const void* dy16, const void* 
   if (grid > cwf_wgrad_nsplit(CWF_CONV3_S1, N, D, H, W, 16, 16)) return CWF_E_BADARG;    // (the caller's slab buffer is sized by it)
   const size_t lds = (size_t)W16D_NBUF * W16D_BUFB;
   CWF_MAX_LDS_ONCE((&wgrad16d_kernel));
-  hipLaunchKernelGGL(wgrad16d_kernel, dim3(grid), dim3(256 + 64 * W16D_LW), lds, cwf_stream(stream), a);
+  hipLaunchKernelGGL(wgrad16d_kernel, dim3(grid), dim3(256 + 64 * W16D_LW), lds, st, a);
   CWF_LAUNCH_CHECK();
   if (nsplit_used) *nsplit_used = grid;
   return 0;
@@ -1310,9 +1311,9 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1d_kernel(const Ws1d
   }
 }
 
-extern "C" int64_t cwf_wgrad_slab_floats(int op, int Cin, int Cout);
-extern "C" int cwf_wgrad_s1_bf16(const void* xa16, const void* dy16, const void* zero16, float* partial,
-                                 int N, int D, int H, int W, int Cin, int Cout, int* nsplit_used, void* stream) {
+static int wgrad_s1d_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
+  const void* xa16 = d.xa16; const void* dy16 = d.dy16; const void* zero16 = d.zero16; float* partial = d.partial;
+  const int N = d.N, D = d.Di, H = d.Hi, W = d.Wi, Cin = d.Cin, Cout = d.Cout;
   if (!xa16 || !dy16 || !zero16 || !partial || N <= 0 || D <= 0 || H <= 0 || W <= 0) return CWF_E_BADARG;
   if (((uintptr_t)xa16 & 15) || ((uintptr_t)dy16 & 15) || ((uintptr_t)zero16 & 15) || ((uintptr_t)partial & 15)) return CWF_E_ALIGN;
   if (Cin < 16 || (Cin & 15) || Cout < 32 || (Cout & 31)) return CWF_E_BADARG;
@@ -1333,7 +1334,7 @@ extern "C" int cwf_wgrad_s1_bf16(const void* xa16, const void* dy16, const void*
   if (splits > cwf_wgrad_nsplit(CWF_CONV3_S1, N, D, H, W, Cin, Cout)) return CWF_E_BADARG;     // (the caller's slab buffer is sized by it)
   const size_t lds = (size_t)WS1D_NBUF * WS1D_BUFB;
   CWF_MAX_LDS_ONCE((&wgrad_s1d_kernel));
-  hipLaunchKernelGGL(wgrad_s1d_kernel, dim3(splits, nblk), dim3(256 + 64 * WS1_LW), lds, cwf_stream(stream), a);
+  hipLaunchKernelGGL(wgrad_s1d_kernel, dim3(splits, nblk), dim3(256 + 64 * WS1_LW), lds, st, a);
   CWF_LAUNCH_CHECK();
   if (nsplit_used) *nsplit_used = splits;
   return 0;
@@ -1502,54 +1503,20 @@ static int launch_pw_wgrad(const WgArgsB& a, int CG, int max_slabs, int* nsplit_
   return 0;
 }
 
-// plan: identical decisions to wgrad_mfma.hip (the Python side sizes the workspace through cwf_wgrad_nsplit / _slab_floats)
-extern "C" int cwf_wgrad_nsplit(int op, int N, int Do, int Ho, int Wo, int Cin, int Cout);
-extern "C" int64_t cwf_wgrad_slab_floats(int op, int Cin, int Cout);
-
-static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                           const float* dy, int dy_ldc, float* partial,
-                           int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int* nsplit_used, void* stream,
-                           int groups, const float* const* xg, const float* const* dyg, float* const* pg, const float* dy_scale = nullptr);
-
-// cwf_wgrad_mfma_bf16 with dy taken as dy * dy_scale[n][co] (full-resolution 16-output-channel 3x3x3 stride-1 layers only: the stem)
-extern "C" int cwf_wgrad_mfma_bf16_dys(int op, int x3, const float* x, int x_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                                       const float* dy, int dy_ldc, const float* dy_scale, float* partial,
-                                       int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int* nsplit_used, void* stream) {
-  if (!dy_scale) return CWF_E_BADARG;
-  return wgrad_bf16_impl(op, x3, x, x_ldc, in_scale, in_shift, in_slope, dy, dy_ldc, partial, N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, nsplit_used, stream,
-                         0, nullptr, nullptr, nullptr, dy_scale);
-}
-
-extern "C" int cwf_wgrad_mfma_bf16(int op, int x3, const float* x, int x_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                                   const float* dy, int dy_ldc, float* partial,
-                                   int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int* nsplit_used, void* stream) {
-  return wgrad_bf16_impl(op, x3, x, x_ldc, in_scale, in_shift, in_slope, dy, dy_ldc, partial, N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, nsplit_used, stream,
-                         0, nullptr, nullptr, nullptr);
-}
-
-// `groups` (2 or 3) same-shape 3x3x3 stride-1 layers in ONE launch (blockIdx.z = group): group q has its own activation view x[q]
-// (row pitch x_ldc), gradient view dy[q] (row pitch dy_ldc) and slab buffer partial[q] (each sized like a single layer's); no
-// normalising prologue.  h_x / h_dy / h_partial: HOST arrays of device pointers.  The three sub-regions' supervision-head layers.
-extern "C" int cwf_wgrad_mfma_bf16_grouped(int op, int x3, const float* const* h_x, int x_ldc, const float* const* h_dy, int dy_ldc,
-                                           float* const* h_partial, int groups,
-                                           int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int* nsplit_used, void* stream) {
-  if (!h_x || !h_dy || !h_partial || groups < 2 || groups > 3 || op != CWF_CONV3_S1) return CWF_E_BADARG;
-  for (int q = 0; q < groups; ++q)
-    if (!h_x[q] || !h_dy[q] || !h_partial[q] || ((uintptr_t)h_x[q] & 15) || ((uintptr_t)h_partial[q] & 15)) return CWF_E_ALIGN;
-  return wgrad_bf16_impl(op, x3, h_x[0], x_ldc, nullptr, nullptr, 1.f, h_dy[0], dy_ldc, h_partial[0], N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, nsplit_used,
-                         stream, groups, h_x, h_dy, h_partial);
-}
-
-static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                           const float* dy, int dy_ldc, float* partial,
-                           int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int* nsplit_used, void* stream,
-                           int groups, const float* const* xg, const float* const* dyg, float* const* pg, const float* dy_scale) {
+// The generic split-bf16 slab kernels (tiled, persistent 16-channel, pointwise stream, producer / consumer).  The plan makes the same
+// decisions as wgrad_mfma.hip's: the caller sized the slab buffer through cwf_wgrad_nsplit / cwf_wgrad_slab_floats.
+static int wgrad_bf16_impl(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
+  const int op = d.op, x3 = d.precision == CWF_BF16X3, groups = d.groups, N = d.N, Cin = d.Cin, Cout = d.Cout;
+  const int Di = d.Di, Hi = d.Hi, Wi = d.Wi, Do = d.Do, Ho = d.Ho, Wo = d.Wo, x_ldc = d.x_ldc, dy_ldc = d.dy_ldc;
+  // a grouped launch passes group 0's views through the plain fields
+  const float* x = groups ? d.x_g[0] : d.x; const float* dy = groups ? d.dy_g[0] : d.dy; float* partial = groups ? d.partial_g[0] : d.partial;
+  const float* in_scale = d.in_scale; const float* dy_scale = d.dy_scale;
   if (!x || !dy || !partial || N <= 0) return CWF_E_BADARG;
   // dy_scale is implemented by wgrad16_kernel alone
   if (dy_scale && !(!groups && op == CWF_CONV3_S1 && Cin <= 16 && Cout == 16 && (dy_ldc & 3) == 0 && (((uintptr_t)dy) & 15) == 0 && (int64_t)Do * Ho * Wo >= 32768))
     return CWF_E_BADARG;
   if ((Cin & 3) || (x_ldc & 3) || ((uintptr_t)x & 15) || ((uintptr_t)partial & 15)) return CWF_E_ALIGN;
-  if (in_scale && !in_shift) return CWF_E_BADARG;
+  if (in_scale && !d.in_shift) return CWF_E_BADARG;
   if (!(op == CWF_CONV3_S1 || op == CWF_CONV3_S2 || op == CWF_CONV1 || op == CWF_CONVT2)) return CWF_E_BADARG;
   const bool tapsplit = (op == CWF_CONV3_S1 || op == CWF_CONV3_S2);
   const int MTOT = (op == CWF_CONV3_S2) ? 4 : 16;
@@ -1569,13 +1536,14 @@ static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const floa
   // must agree with wgrad_mfma.hip's plan (the workspace was sized from it)
   if ((tapsplit ? wg_splits : wg_splits * 4) != cwf_wgrad_nsplit(op, N, Do, Ho, Wo, Cin, Cout) || blocks * 256 != cwf_wgrad_slab_floats(op, Cin, Cout))
     return CWF_E_BADARG;
-  a.x = x; a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope; a.dy = dy; a.dy_ldc = dy_ldc; a.partial = partial;
+  a.x = x; a.in_scale = in_scale; a.in_shift = d.in_shift; a.in_slope = d.in_slope; a.dy = dy; a.dy_ldc = dy_ldc; a.partial = partial;
   a.ngroups = ngroups; a.tiles_per_split = tps; a.total_tiles = total; a.slab_floats = blocks * 256;
   a.groups = groups; a.dy_scale = dy_scale;
   bool dy_al = (((uintptr_t)dy) & 15) == 0;
   for (int q = 0; q < 3; ++q) {
-    a.x_g[q] = (groups && q < groups) ? xg[q] : nullptr; a.dy_g[q] = (groups && q < groups) ? dyg[q] : nullptr; a.partial_g[q] = (groups && q < groups) ? pg[q] : nullptr;
-    if (groups && q < groups && (((uintptr_t)dyg[q]) & 15)) dy_al = false;
+    a.x_g[q] = (groups && q < groups) ? d.x_g[q] : nullptr; a.dy_g[q] = (groups && q < groups) ? d.dy_g[q] : nullptr;
+    a.partial_g[q] = (groups && q < groups) ? d.partial_g[q] : nullptr;
+    if (groups && q < groups && (((uintptr_t)d.dy_g[q]) & 15)) dy_al = false;
   }
   const int gz = groups ? groups : ncls;                 // grid z: group (grouped launches are single-class) or parity class
   if (nsplit_used) *nsplit_used = tapsplit ? wg_splits : wg_splits * 4;
@@ -1584,13 +1552,12 @@ static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const floa
     // (the stem layer -- 4 input channels -- is the LAST kernel of backward: nothing runs beside it, it takes every CU)
     int grid = Cin <= 4 ? 256 : SIDE_WGS; while (grid > 8 && grid > total) grid -= 8;      // multiple of 8 (XCD-aware tile map)
     const size_t lds16 = (size_t)2 * (36 * W16_XW * 16 + 16 * W16_DW * 16) * sizeof(unsigned short) * (x3 ? 2 : 1);
-    hipStream_t st16 = cwf_stream(stream);
     if (x3) {
       CWF_MAX_LDS_ONCE((&wgrad16_kernel<true>));
-      hipLaunchKernelGGL((wgrad16_kernel<true>), dim3(grid), dim3(256 + 64 * W16_LW), lds16, st16, a, total);
+      hipLaunchKernelGGL((wgrad16_kernel<true>), dim3(grid), dim3(256 + 64 * W16_LW), lds16, st, a, total);
     } else {
       CWF_MAX_LDS_ONCE((&wgrad16_kernel<false>));
-      hipLaunchKernelGGL((wgrad16_kernel<false>), dim3(grid), dim3(256 + 64 * W16_LW), lds16, st16, a, total);
+      hipLaunchKernelGGL((wgrad16_kernel<false>), dim3(grid), dim3(256 + 64 * W16_LW), lds16, st, a, total);
     }
     CWF_LAUNCH_CHECK();
     if (nsplit_used) *nsplit_used = grid;
@@ -1601,16 +1568,15 @@ static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const floa
     // pointwise layers: stream kernel (fp32 MFMA straight from global memory, every operand read once), both precision modes
     const int nch = nchunks, ntl = a.g.ntiles;
     const int max_slabs = wg_splits * 4;                  // what the workspace was sized for
-    hipStream_t stp = cwf_stream(stream);
     int r = -2;
     if (op == CWF_CONV1) {
-      if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 1>(a, CG, max_slabs, nsplit_used, stp);
-      else if (nch == 2 && ntl == 1) r = launch_pw_wgrad<2, 1, 1>(a, CG, max_slabs, nsplit_used, stp);
-      else if (nch == 4 && ntl == 2) r = launch_pw_wgrad<4, 2, 1>(a, CG, max_slabs, nsplit_used, stp);
-      else if (nch == 8 && ntl == 4) r = launch_pw_wgrad<8, 4, 1>(a, CG, max_slabs, nsplit_used, stp);
+      if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 1>(a, CG, max_slabs, nsplit_used, st);
+      else if (nch == 2 && ntl == 1) r = launch_pw_wgrad<2, 1, 1>(a, CG, max_slabs, nsplit_used, st);
+      else if (nch == 4 && ntl == 2) r = launch_pw_wgrad<4, 2, 1>(a, CG, max_slabs, nsplit_used, st);
+      else if (nch == 8 && ntl == 4) r = launch_pw_wgrad<8, 4, 1>(a, CG, max_slabs, nsplit_used, st);
     } else {
-      if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 8>(a, CG, max_slabs, nsplit_used, stp);
-      else if (nch == 2 && ntl == 2) r = launch_pw_wgrad<2, 2, 8>(a, CG, max_slabs, nsplit_used, stp);
+      if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 8>(a, CG, max_slabs, nsplit_used, st);
+      else if (nch == 2 && ntl == 2) r = launch_pw_wgrad<2, 2, 8>(a, CG, max_slabs, nsplit_used, st);
     }
     if (r >= 0) return r;
   }
@@ -1624,11 +1590,10 @@ static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const floa
       if (nsplit_used) *nsplit_used = splits1;
       const size_t lds1 = (size_t)2 * (36 * 20 * 16 + 16 * (CG == 1 ? 20 : 16) * CG * 16 + (16 / 2 + 1) * (CG == 2 ? 16 : 0)) * sizeof(unsigned short);
       dim3 grid1(splits1, nchunks * ngroups, groups ? groups : 1);
-      hipStream_t st1 = cwf_stream(stream);
       CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<1>));
       CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<2>));
-      if (CG == 1) hipLaunchKernelGGL((wgrad_s1_kernel<1>), grid1, dim3(256 + 64 * WS1_LW), lds1, st1, a);
-      else hipLaunchKernelGGL((wgrad_s1_kernel<2>), grid1, dim3(256 + 64 * WS1_LW), lds1, st1, a);
+      if (CG == 1) hipLaunchKernelGGL((wgrad_s1_kernel<1>), grid1, dim3(256 + 64 * WS1_LW), lds1, st, a);
+      else hipLaunchKernelGGL((wgrad_s1_kernel<2>), grid1, dim3(256 + 64 * WS1_LW), lds1, st, a);
       CWF_LAUNCH_CHECK();
       return 0;
     }
@@ -1638,7 +1603,6 @@ static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const floa
   const size_t lds = (ximg + dimg) * sizeof(unsigned short) * (x3 ? 2 : 1);
   if (lds > 160 * 1024) return CWF_E_TOOLARGE;
   dim3 grid(wg_splits, nchunks * ngroups, gz);
-  hipStream_t st = cwf_stream(stream);
 #define CWF_WG(tpw, ntw, ts, xx) do { CWF_MAX_LDS_ONCE((&wgrad_bf16_kernel<tpw, ntw, ts, xx>)); \
     hipLaunchKernelGGL((wgrad_bf16_kernel<tpw, ntw, ts, xx>), grid, dim3(256), lds, st, a); } while (0)
 #define CWF_WGX(tpw, ntw, ts) do { if (x3) CWF_WG(tpw, ntw, ts, true); else CWF_WG(tpw, ntw, ts, false); } while (0)
@@ -1648,4 +1612,25 @@ static int wgrad_bf16_impl(int op, int x3, const float* x, int x_ldc, const floa
 #undef CWF_WG
   CWF_LAUNCH_CHECK();
   return 0;
+}
+
+// The one place that chooses a weight-gradient slab kernel (include/cwf_hip.h, struct cwf_wgrad_args).
+extern "C" int cwf_wgrad(const struct cwf_wgrad_args* args, int* nsplit_used, void* stream) {
+  if (!args) return CWF_E_BADARG;
+  const cwf_wgrad_args& d = *args;
+  if (d.precision != CWF_FP32 && d.precision != CWF_BF16X3 && d.precision != CWF_BF16) return CWF_E_BADARG;
+  hipStream_t st = cwf_stream(stream);
+  if (d.xa16 || d.dy16) {                                  // bf16 operand images (x, dy and x's prologue are not read)
+    if (!d.xa16 || !d.dy16 || d.precision != CWF_BF16 || d.op != CWF_CONV3_S1 || d.groups || d.dy_scale) return CWF_E_BADARG;
+    if (d.Cin == 16 && d.Cout == 16 && (int64_t)d.Do * d.Ho * d.Wo >= 32768) return wgrad16_launch(d, nsplit_used, st);
+    return wgrad_s1d_launch(d, nsplit_used, st);
+  }
+  if (d.groups) {
+    if (d.groups < 2 || d.groups > 3 || d.op != CWF_CONV3_S1 || d.precision == CWF_FP32 || d.in_scale || d.dy_scale) return CWF_E_BADARG;
+    for (int q = 0; q < d.groups; ++q)
+      if (!d.x_g[q] || !d.dy_g[q] || !d.partial_g[q] || ((uintptr_t)d.x_g[q] & 15) || ((uintptr_t)d.partial_g[q] & 15)) return CWF_E_ALIGN;
+    return wgrad_bf16_impl(d, nsplit_used, st);
+  }
+  if (d.precision == CWF_FP32) return d.dy_scale ? CWF_E_BADARG : wgrad_fp32_launch(d, nsplit_used, st);
+  return wgrad_bf16_impl(d, nsplit_used, st);
 }

@@ -15,7 +15,7 @@
 //
 // Replaces the weight/bias halves of aten::convolution_backward for every conv of the model
 // (38 % of the reference's CPU step).
-#include "common.h"
+#include "conv_args.h"
 
 struct WgArgs {
   ConvGeom g;
@@ -254,17 +254,17 @@ extern "C" int64_t cwf_wgrad_partial_floats(int op, int N, int Do, int Ho, int W
   WgPlan p; int rc = make_plan_shape(p, op, N, Do, Ho, Wo, Cin, Cout); return rc ? rc : p.slab * p.nsplit;
 }
 
-extern "C" int cwf_wgrad_mfma(int op, const float* x, int x_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                              const float* dy, int dy_ldc, float* partial,
-                              int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream) {
+int wgrad_fp32_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
+  const int op = d.op, N = d.N, Cin = d.Cin, x_ldc = d.x_ldc, dy_ldc = d.dy_ldc;
+  const float* x = d.x; const float* dy = d.dy; float* partial = d.partial;
   if (!x || !dy || !partial || N <= 0) return CWF_E_BADARG;
   if ((Cin & 3) || (x_ldc & 3) || ((uintptr_t)x & 15) || ((uintptr_t)partial & 15)) return CWF_E_ALIGN;
-  if (in_scale && !in_shift) return CWF_E_BADARG;
+  if (d.in_scale && !d.in_shift) return CWF_E_BADARG;
   WgPlan p;
-  int rc = make_plan(p, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, dy_ldc);
+  int rc = make_plan(p, op, N, d.Di, d.Hi, d.Wi, Cin, x_ldc, d.Do, d.Ho, d.Wo, d.Cout, dy_ldc);
   if (rc) return rc;
   WgArgs a;
-  a.g = p.g; a.x = x; a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope;
+  a.g = p.g; a.x = x; a.in_scale = d.in_scale; a.in_shift = d.in_shift; a.in_slope = d.in_slope;
   a.dy = dy; a.dy_ldc = dy_ldc; a.partial = partial; a.ngroups = p.ngroups;
   a.tiles_per_split = p.tps; a.total_tiles = p.total; a.slab_floats = p.slab;
   int base = 0;
@@ -272,13 +272,13 @@ extern "C" int cwf_wgrad_mfma(int op, const float* x, int x_ldc, const float* in
   const size_t lds = ((size_t)p.g.ID * p.g.IH * p.g.IW * 16 + (size_t)p.g.TD * p.g.TH * 16 * p.CG * 16) * sizeof(float);
   if (lds > 160 * 1024) return CWF_E_TOOLARGE;
   dim3 grid(p.wg_splits, p.nchunks * p.ngroups, p.ncls);
-  hipStream_t st = cwf_stream(stream);
 #define CWF_WG(tpw, ntw, ts) do { CWF_MAX_LDS_ONCE((&wgrad_mfma_kernel<tpw, ntw, ts>)); \
     hipLaunchKernelGGL((wgrad_mfma_kernel<tpw, ntw, ts>), grid, dim3(256), lds, st, a); } while (0)
   if (p.tapsplit) { if (p.CG == 1) CWF_WG(7, 1, true); else CWF_WG(7, 2, true); }
   else { if (p.CG == 1) CWF_WG(2, 1, false); else if (p.CG == 2) CWF_WG(2, 2, false); else CWF_WG(2, 4, false); }
 #undef CWF_WG
   CWF_LAUNCH_CHECK();
+  if (nsplit_used) *nsplit_used = p.nsplit;
   return 0;
 }
 

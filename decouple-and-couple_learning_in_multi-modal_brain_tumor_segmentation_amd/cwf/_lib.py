@@ -19,18 +19,12 @@ D = C.c_double
 # name -> argtypes, exactly as declared in include/cwf_hip.h
 SIGNATURES = {
     "cwf_version": [],
-    "cwf_conv_mfma": [I, P, I, P, P, P, I, P, P, F, P, I, P, P, I, I, I, I, I, I, I, I, I, P],
-    "cwf_conv_mfma_bf16": [I, I, P, I, P, P, P, I, P, P, F, P, I, P, P, I, I, I, I, I, I, I, I, I, P],
-    "cwf_conv_mfma_bf16_nb": [I, I, P, I, P, P, P, I, P, P, F, P, I, P, P, P, I, P, P, F, I, I, I, I, I, I, I, I, I, P],
-    "cwf_conv_s2c16_bf16": [I, P, I, P, P, P, I, P, I, I, I, I, P],
-    "cwf_conv_mfma_bf16_y16": [I, I, P, I, P, P, P, I, P, P, P, F, P, I, P, I, I, I, I, I, I, I, I, I, P],
-    "cwf_conv_stem_bf16": [I, P, I, P, P, P, I, P, P, I, I, I, I, P],
-    "cwf_wgrad_mfma_bf16": [I, I, P, I, P, P, F, P, I, P, I, I, I, I, I, I, I, I, I, P, P],
+    "cwf_conv": [P, P],
+    "cwf_wgrad": [P, P, P],
     "cwf_gather_split_bf16": [P, I, L, P],
     "cwf_wgrad_nsplit": [I, I, I, I, I, I, I],
     "cwf_wgrad_partial_floats": [I, I, I, I, I, I, I],
     "cwf_wgrad_slab_floats": [I, I, I],
-    "cwf_wgrad_mfma": [I, P, I, P, P, F, P, I, P, I, I, I, I, I, I, I, I, I, P],
     "cwf_wgrad_reduce": [P, I, L, P, P, P, P],
     "cwf_gather_batched": [P, I, L, P],
     "cwf_in_finalize": [P, P, P, I, L, F, P],
@@ -41,10 +35,6 @@ SIGNATURES = {
     "cwf_in_bwd_apply_ex": [P, I, P, I, P, P, F, P, P, I, P, I, P, P, I, L, I, P],
     "cwf_norm_act_add_ex": [P, I, P, P, F, P, I, P, I, P, I, L, I, P],
     "cwf_to_bf16": [P, I, P, P, F, P, I, L, I, P],
-    "cwf_wgrad16_bf16": [P, P, P, P, I, I, I, I, P, P],
-    "cwf_wgrad_mfma_bf16_dys": [I, I, P, I, P, P, F, P, I, P, P, I, I, I, I, I, I, I, I, I, P, P],
-    "cwf_wgrad_s1_bf16": [P, P, P, P, I, I, I, I, I, I, P, P],
-    "cwf_conv_mfma_bf16_in16": [I, P, P, P, P, P, I, P, I, P, P, I, P, P, F, I, I, I, I, P],
     "cwf_gemm": [P, L, L, L, L, P, L, L, L, L, P, L, L, L, P, P, L, L, L, I, I, I, I, I, F, I, I, P],
     "cwf_layernorm_fwd": [P, P, P, P, P, P, I, I, F, P],
     "cwf_layernorm_bwd": [P, P, P, P, P, P, P, P, I, I, I, P],
@@ -96,8 +86,6 @@ SIGNATURES = {
     "cwf_head_loss_sums": [P, I, I, P, P, P, I, I, I, I, I, P],
     "cwf_head_loss_bwd": [P, I, I, P, P, P, P, P, I, P, I, I, I, I, I, P],
     "cwf_head_loss_bwd_ex": [P, I, I, P, P, P, P, P, I, I, P, I, I, I, I, I, P],
-    "cwf_wgrad_mfma_bf16_grouped": [I, I, P, I, P, I, P, I, I, I, I, I, I, I, I, I, I, P, P],
-    "cwf_conv_mfma_bf16_grouped": [I, I, P, I, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P],
     "cwf_ln_pair_fwd_g": [P, P, I, P, I, P, P, P, I, I, F, P],
     "cwf_ln_pair_bwd_g": [P, P, P, P, P, I, P, I, P, P, P, I, I, I, P],
     "cwf_token_scores2_g": [P, P, P, I, I, P, P, I, I, I, P],
@@ -134,6 +122,34 @@ class GemmArgs(C.Structure):
                 ("a_drop_off", C.c_uint64), ("a_drop_n", C.c_uint64), ("a_drop_p", F), ("a_drop_p2", F),
                 ("c_drop_off", C.c_uint64), ("c_drop_n", C.c_uint64), ("c_drop_p", F), ("c_drop_p2", F),
                 ("B_tab", P * 4), ("bias_tab", P * 4), ("C_tab", P * 4), ("rowsum_tab", P * 4)]
+
+
+class ConvArgs(C.Structure):
+    """struct cwf_conv_args (include/cwf_hip.h)"""
+    _fields_ = [("op", I), ("precision", I),
+                ("x", P), ("x_ldc", I), ("wpk", P), ("bias", P), ("y", P), ("y_ldc", I),
+                ("in_scale", P), ("in_shift", P), ("in_slope", F),
+                ("residual", P), ("r_ldc", I), ("out_scale", P), ("stats", P),
+                ("nb_x", P), ("nb_ldc", I), ("nb_scale", P), ("nb_shift", P), ("nb_slope", F),
+                ("x16", P), ("zero16", P), ("y16", P),
+                ("w_raw", P),
+                ("groups", I), ("x_goff", I), ("y_goff", I), ("wpk_g", P * 3), ("bias_g", P * 3),
+                ("N", I), ("Di", I), ("Hi", I), ("Wi", I), ("Cin", I), ("Do", I), ("Ho", I), ("Wo", I), ("Cout", I)]
+
+
+class WgradArgs(C.Structure):
+    """struct cwf_wgrad_args (include/cwf_hip.h)"""
+    _fields_ = [("op", I), ("precision", I),
+                ("x", P), ("x_ldc", I), ("in_scale", P), ("in_shift", P), ("in_slope", F),
+                ("dy", P), ("dy_ldc", I),
+                ("dy_scale", P), ("xa16", P), ("dy16", P), ("zero16", P),
+                ("partial", P),
+                ("groups", I), ("x_g", P * 3), ("dy_g", P * 3), ("partial_g", P * 3),
+                ("N", I), ("Di", I), ("Hi", I), ("Wi", I), ("Cin", I), ("Do", I), ("Ho", I), ("Wo", I), ("Cout", I)]
+
+
+# struct cwf_conv_args / cwf_wgrad_args .precision
+PRECISION = {"fp32": 0, "bf16x3": 1, "bf16": 2}
 
 
 class LnGroupParams(C.Structure):

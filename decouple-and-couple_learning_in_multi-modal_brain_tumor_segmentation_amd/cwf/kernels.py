@@ -213,8 +213,8 @@ class HipBackend:
              stats=None, out=None, w_ref=None, out_channels_alloc=None, fwd_op=None, prec=None, nb=None, bias_ref=None, x16=None, y16=None):
         """Returns the output buffer.  With out_channels_alloc > cout the buffer has zero-filled padding channels
         (2-channel heads live in 4-channel tensors so that every later kernel sees 16-byte voxel rows).
-        w_ref / bias_ref (the original parameters; tuples for a fused layer) and fwd_op are not read here: the kernels take the
-        packed operands."""
+        The library chooses the kernel (cwf_conv).  w_ref / bias_ref are the original parameters (tuples for a fused layer); a forward
+        launch (fwd_op None) hands a single contiguous w_ref over as the raw weight, which the stem and first down-sampling kernels read."""
         x, x_ldc = cl(x)
         n, di, hi, wi, cin = x.shape
         if op == pk.CONV3_S2_DGRAD or op == pk.CONVT2_DGRAD:
@@ -228,67 +228,30 @@ class HipBackend:
             out = torch.empty((n, do, ho, wo, ca), dtype=_f32, device=x.device)
         y = out
         _, do, ho, wo, _ = y.shape
-        y_ldc = y.stride(3)
-        r_ldc = 0
-        if residual is not None:
-            residual, r_ldc = cl(residual)
         mode = prec or ((_DGRAD_PRECISION or _PRECISION) if (fwd_op is not None) else _PRECISION)
-        if x16 is not None:
-            # the input as a bf16 image (bf16_dgrad_ok): conv16s with LDS-DMA loaders; x itself is not read
-            assert mode == "bf16" and in_scale is None and out_scale is None and x16.dtype == torch.bfloat16 and x16.is_contiguous()
-            assert tuple(x16.shape) == (n, di, hi, wi, 16) and cin == 16 and cout == 16
-            nbp = (0, 0, 0, 0, 1.0)
-            if nb is not None:
-                nb_x, nb_scale, nb_shift, nb_slope = nb
-                nb_x, nb_ldc = cl(nb_x)
-                nbp = (nb_x.data_ptr(), nb_ldc, nb_scale.data_ptr(), nb_shift.data_ptr(), float(nb_slope))
-            self._call("cwf_conv_mfma_bf16_in16", op, x16.data_ptr(), self.zero16(x.device).data_ptr(), wpk.data_ptr(), _p(bias),
-                       y.data_ptr(), y_ldc, _p(residual), r_ldc, _p(stats), *nbp, n, di, hi, wi, self._stream())
-            return y
-        if y16 is not None:
-            # 1x1x1 forward that also leaves its output as a bf16 image (y16 [N,D,H,W,cout] bfloat16): the pointwise stream kernel's side
-            # output; any other layer converts afterwards
-            assert x16 is None and nb is None and out_scale is None and y16.dtype == torch.bfloat16 and y16.is_contiguous()
-            rc = 1
-            if mode != "fp32" and op == pk.CONV1:
-                rc = self.lib.cwf_conv_mfma_bf16_y16(op, 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, wpk.data_ptr(), _p(bias), y.data_ptr(), y_ldc,
-                                                     y16.data_ptr(), _p(in_scale), _p(in_shift), float(slope), _p(residual), r_ldc, _p(stats),
-                                                     n, di, hi, wi, cin, do, ho, wo, cout, self._stream())
-            if rc != 0:
-                self.conv(op, x, wpk, bias, cout, in_scale, in_shift, slope, residual, None, stats, out=y, w_ref=w_ref, prec=prec, bias_ref=bias_ref)
-                self.to_bf16(y if y.shape[-1] == cout else y[..., :cout], out=y16)      # (no copy node: a captured step stays plan-able)
-            return y
-        if (op == pk.CONV3_S1 and cin == 4 and cout == 16 and mode != "fp32" and fwd_op is None and in_scale is None and residual is None
-                and nb is None and torch.is_tensor(w_ref) and tuple(w_ref.shape) == (16, 4, 3, 3, 3) and w_ref.is_contiguous()
-                and w_ref.dtype == _f32 and do * ho * wo >= 32768):
-            # the stem: K = 8 taps x 4 channels (conv_stem.hip), straight from the raw weight
-            self._call("cwf_conv_stem_bf16", 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, w_ref.data_ptr(), _p(bias), y.data_ptr(), y_ldc,
-                       _p(out_scale), _p(stats), n, di, hi, wi, self._stream())
-            return y
-        if (op == pk.CONV3_S2 and cin == 16 and cout == 32 and mode != "fp32" and fwd_op is None and in_scale is None and residual is None
-                and out_scale is None and nb is None and torch.is_tensor(w_ref) and tuple(w_ref.shape) == (32, 16, 3, 3, 3) and w_ref.is_contiguous()
-                and w_ref.dtype == _f32 and do * ho * wo >= 32768
-                and (do, ho, wo) == ((di + 1) // 2, (hi + 1) // 2, (wi + 1) // 2)):
-            # the first down-sampling layer: persistent prefetching kernel with parity-split halo rows (conv_s2.hip)
-            self._call("cwf_conv_s2c16_bf16", 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, w_ref.data_ptr(), _p(bias), y.data_ptr(), y_ldc,
-                       _p(stats), n, di, hi, wi, self._stream())
-            return y
-        if mode == "fp32":
-            self._call("cwf_conv_mfma", op, x.data_ptr(), x_ldc, wpk.data_ptr(), _p(bias), y.data_ptr(), y_ldc,
-                       _p(in_scale), _p(in_shift), float(slope), _p(residual), r_ldc, _p(out_scale), _p(stats),
-                       n, di, hi, wi, cin, do, ho, wo, cout, self._stream())
-        elif nb is not None:
+        a = _lib.ConvArgs(op=op, precision=_lib.PRECISION[mode], x=x.data_ptr(), x_ldc=x_ldc, wpk=wpk.data_ptr(), bias=_p(bias),
+                          y=y.data_ptr(), y_ldc=y.stride(3), in_scale=_p(in_scale), in_shift=_p(in_shift), in_slope=float(slope),
+                          out_scale=_p(out_scale), stats=_p(stats), nb_slope=1.0,
+                          N=n, Di=di, Hi=hi, Wi=wi, Cin=cin, Do=do, Ho=ho, Wo=wo, Cout=cout)
+        if residual is not None:
+            residual, a.r_ldc = cl(residual)
+            a.residual = residual.data_ptr()
+        if nb is not None:
             # data gradient whose output feeds the backward of act(IN(nb_x)): stats := (S1, S2) of that backward (see in_bwd_fused)
-            nb_x, nb_scale, nb_shift, nb_slope = nb
-            nb_x, nb_ldc = cl(nb_x)
-            self._call("cwf_conv_mfma_bf16_nb", op, 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, wpk.data_ptr(), _p(bias),
-                       y.data_ptr(), y_ldc, _p(in_scale), _p(in_shift), float(slope), _p(residual), r_ldc, _p(out_scale),
-                       _p(stats), nb_x.data_ptr(), nb_ldc, nb_scale.data_ptr(), nb_shift.data_ptr(), float(nb_slope),
-                       n, di, hi, wi, cin, do, ho, wo, cout, self._stream())
-        else:
-            self._call("cwf_conv_mfma_bf16", op, 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, wpk.data_ptr(), _p(bias),
-                       y.data_ptr(), y_ldc, _p(in_scale), _p(in_shift), float(slope), _p(residual), r_ldc, _p(out_scale),
-                       _p(stats), n, di, hi, wi, cin, do, ho, wo, cout, self._stream())
+            nb_x, nb_scale, nb_shift, a.nb_slope = nb
+            nb_x, a.nb_ldc = cl(nb_x)
+            a.nb_x, a.nb_scale, a.nb_shift = nb_x.data_ptr(), nb_scale.data_ptr(), nb_shift.data_ptr()
+        if x16 is not None:
+            # the input as a bf16 image (bf16_dgrad_ok): x itself is not read
+            assert x16.dtype == torch.bfloat16 and x16.is_contiguous() and tuple(x16.shape) == (n, di, hi, wi, 16)
+            a.x16, a.zero16 = x16.data_ptr(), self.zero16(x.device).data_ptr()
+        if y16 is not None:
+            # the output also as a bf16 image (y16 [N,D,H,W,cout] bfloat16)
+            assert y16.dtype == torch.bfloat16 and y16.is_contiguous()
+            a.y16 = y16.data_ptr()
+        if fwd_op is None and torch.is_tensor(w_ref) and w_ref.is_contiguous() and w_ref.dtype == _f32:
+            a.w_raw = w_ref.data_ptr()             # (the stem and the first down-sampling layer read the raw weight)
+        self._call("cwf_conv", ctypes.addressof(a), self._stream())
         return y
 
     def supports_fused_norm_bwd(self, prec=None):
@@ -310,7 +273,7 @@ class HipBackend:
 
     # ------------------------------------------------------------------ bf16 operand images (16-channel full-resolution layers)
     # The weight gradient of the full-resolution 16-channel 3x3x3 layers takes its operands as bf16 tensors [N,D,H,W,16] when both
-    # exist (cwf_wgrad16_bf16: LDS-DMA staging, half the bytes, no conversion): xa16 = bf16(act(IN(x))) is a side output of the
+    # exist (wgrad16d_kernel: LDS-DMA staging, half the bytes, no conversion): xa16 = bf16(act(IN(x))) is a side output of the
     # layer's own InstanceNorm-backward apply pass, dy16 of the pass that produced the incoming gradient.  Same operand values as
     # the fp32-tensor kernel computes per tile (single-bf16 products), so results do not change.
     # which bf16 images the main-stream InstanceNorm-backward apply pass (and the block tail) write as side outputs: each costs the
@@ -383,7 +346,7 @@ class HipBackend:
         return y
 
     def conv_grouped(self, x_all, cin, wpks, biases, cout, y_all, x_goff, y_goff, w_refs=None, fwd_op=None, prec=None):
-        """G = len(wpks) channel-grouped 3x3x3 stride-1 convs in ONE launch (cwf_conv_mfma_bf16_grouped): group q reads channels
+        """G = len(wpks) channel-grouped 3x3x3 stride-1 convs in ONE launch (cwf_conv with groups): group q reads channels
         [q*x_goff, q*x_goff + cin) of x_all and writes channels [q*y_goff, q*y_goff + cout) of y_all (same voxel rows).  Data
         gradients: pass the transposed packed weights (spec.packed(True)) and fwd_op.  Exact-fp32 mode: one launch per group."""
         x_all, x_ldc = cl(x_all)
@@ -391,15 +354,13 @@ class HipBackend:
         n, d, h, w, _ = x_all.shape
         G = len(wpks)
         mode = prec or ((_DGRAD_PRECISION or _PRECISION) if (fwd_op is not None) else _PRECISION)
-        if mode == "fp32":
-            for q in range(G):
-                self.conv(pk.CONV3_S1, x_all[..., q * x_goff:q * x_goff + cin], wpks[q], None if biases is None else biases[q], cout,
-                          out=y[..., q * y_goff:q * y_goff + cout], fwd_op=fwd_op, prec=mode)
-            return y_all
-        wp = (ctypes.c_void_p * G)(*[t.data_ptr() for t in wpks])
-        bp = (ctypes.c_void_p * G)(*[(0 if (biases is None or b is None) else b.data_ptr()) for b in (biases or [None] * G)])
-        self._call("cwf_conv_mfma_bf16_grouped", pk.CONV3_S1, 1 if mode == "bf16x3" else 0, x_all.data_ptr(), x_ldc, x_goff,
-                   ctypes.addressof(wp), ctypes.addressof(bp), y.data_ptr(), y_ldc, y_goff, G, n, d, h, w, cin, d, h, w, cout, self._stream())
+        a = _lib.ConvArgs(op=pk.CONV3_S1, precision=_lib.PRECISION[mode], x=x_all.data_ptr(), x_ldc=x_ldc, y=y.data_ptr(), y_ldc=y_ldc,
+                          in_slope=1.0, nb_slope=1.0, groups=G, x_goff=x_goff, y_goff=y_goff,
+                          N=n, Di=d, Hi=h, Wi=w, Cin=cin, Do=d, Ho=h, Wo=w, Cout=cout)
+        for q in range(G):
+            a.wpk_g[q] = wpks[q].data_ptr()
+            a.bias_g[q] = 0 if biases is None else _p(biases[q])
+        self._call("cwf_conv", ctypes.addressof(a), self._stream())
         return y_all
 
 
@@ -537,7 +498,7 @@ class HipBackend:
         if part is None or part.numel() < nsplit * slab:
             part = torch.empty(int(nsplit * slab), dtype=_f32, device=x.device)
             self._wg_part[pk_] = part
-        mode = prec or _WGRAD_PRECISION or _PRECISION
+        a = self._wgrad_args(op, x, x_ldc, in_scale, in_shift, slope, dy, dy_ldc, cout, part, prec)
         if use16:
             if x16 is None:
                 x16 = self.to_bf16(x, in_scale, in_shift, slope)
@@ -545,35 +506,24 @@ class HipBackend:
                 dy16 = self.to_bf16(dy)
             assert x16.dtype == torch.bfloat16 and dy16.dtype == torch.bfloat16 and x16.is_contiguous() and dy16.is_contiguous()
             assert tuple(x16.shape) == (n, di, hi, wi, cin) and tuple(dy16.shape) == (n, do, ho, wo, cout)
-            used = ctypes.c_int(0)
-            if use16 == 16:
-                self._call("cwf_wgrad16_bf16", x16.data_ptr(), dy16.data_ptr(), self.zero16(x.device).data_ptr(), part.data_ptr(),
-                           n, di, hi, wi, ctypes.addressof(used), self._stream())
-            else:
-                self._call("cwf_wgrad_s1_bf16", x16.data_ptr(), dy16.data_ptr(), self.zero16(x.device).data_ptr(), part.data_ptr(),
-                           n, di, hi, wi, cin, cout, ctypes.addressof(used), self._stream())
-            nsplit = used.value
-        elif dy_scale is not None:
-            used = ctypes.c_int(0)
-            self._call("cwf_wgrad_mfma_bf16_dys", op, 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, _p(in_scale), _p(in_shift),
-                       float(slope), dy.data_ptr(), dy_ldc, dy_scale.data_ptr(), part.data_ptr(), n, di, hi, wi, cin, do, ho, wo, cout,
-                       ctypes.addressof(used), self._stream())
-            nsplit = used.value
-        elif mode == "fp32":
-            self._call("cwf_wgrad_mfma", op, x.data_ptr(), x_ldc, _p(in_scale), _p(in_shift), float(slope),
-                       dy.data_ptr(), dy_ldc, part.data_ptr(), n, di, hi, wi, cin, do, ho, wo, cout, self._stream())
-        else:
-            used = ctypes.c_int(0)
-            self._call("cwf_wgrad_mfma_bf16", op, 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, _p(in_scale), _p(in_shift),
-                       float(slope), dy.data_ptr(), dy_ldc, part.data_ptr(), n, di, hi, wi, cin, do, ho, wo, cout,
-                       ctypes.addressof(used), self._stream())
-            nsplit = used.value
-        self._wg_pending.append((part.data_ptr(), inv_map.data_ptr(), dw_dst.data_ptr(), _p(db_dst), int(slab), int(nsplit)))
+            a.xa16, a.dy16, a.zero16 = x16.data_ptr(), dy16.data_ptr(), self.zero16(x.device).data_ptr()
+        a.dy_scale = _p(dy_scale)
+        used = ctypes.c_int(0)
+        self._call("cwf_wgrad", ctypes.addressof(a), ctypes.addressof(used), self._stream())
+        self._wg_pending.append((part.data_ptr(), inv_map.data_ptr(), dw_dst.data_ptr(), _p(db_dst), int(slab), int(used.value)))
 
+    @staticmethod
+    def _wgrad_args(op, x, x_ldc, in_scale, in_shift, slope, dy, dy_ldc, cout, part, prec):
+        """struct cwf_wgrad_args of one layer (x / dy channels-last views, part its slab buffer)"""
+        n, di, hi, wi, cin = x.shape
+        _, do, ho, wo, _ = dy.shape
+        return _lib.WgradArgs(op=op, precision=_lib.PRECISION[prec or _WGRAD_PRECISION or _PRECISION], x=x.data_ptr(), x_ldc=x_ldc,
+                              in_scale=_p(in_scale), in_shift=_p(in_shift), in_slope=float(slope), dy=dy.data_ptr(), dy_ldc=dy_ldc,
+                              partial=part.data_ptr(), N=n, Di=di, Hi=hi, Wi=wi, Cin=cin, Do=do, Ho=ho, Wo=wo, Cout=cout)
 
     def wgrad_to_grouped(self, keys, op, xs, dys, cout, inv_maps, dw_dsts, db_dsts, prec=None, allow_async=False):
         """wgrad_to for G same-shape 3x3x3 stride-1 layers without prologue (channel-group views xs[q] / dys[q] of shared buffers):
-        ONE slab launch (cwf_wgrad_mfma_bf16_grouped); each layer keeps its own slab buffer and row in the batched reduce."""
+        ONE slab launch (cwf_wgrad with groups); each layer keeps its own slab buffer and row in the batched reduce."""
         mode = prec or _WGRAD_PRECISION or _PRECISION
         if mode == "fp32" or (self.wgrad_async and allow_async and self.wgrad_defer):
             for q in range(len(keys)):
@@ -610,12 +560,12 @@ class HipBackend:
                 part = torch.empty(int(nsplit * slab), dtype=_f32, device=x0.device)
                 self._wg_part[pk_] = part
             parts.append(part)
-        xp = (ctypes.c_void_p * G)(*[t.data_ptr() for t in xs])
-        dp = (ctypes.c_void_p * G)(*[t.data_ptr() for t in dys])
-        pp = (ctypes.c_void_p * G)(*[t.data_ptr() for t in parts])
+        a = _lib.WgradArgs(op=op, precision=_lib.PRECISION[mode], x_ldc=x_ldc, in_slope=1.0, dy_ldc=dy_ldc, groups=G,
+                           N=n, Di=di, Hi=hi, Wi=wi, Cin=cin, Do=do, Ho=ho, Wo=wo, Cout=cout)
+        for q in range(G):
+            a.x_g[q], a.dy_g[q], a.partial_g[q] = xs[q].data_ptr(), dys[q].data_ptr(), parts[q].data_ptr()
         used = ctypes.c_int(0)
-        self._call("cwf_wgrad_mfma_bf16_grouped", op, 1 if mode == "bf16x3" else 0, ctypes.addressof(xp), x_ldc, ctypes.addressof(dp), dy_ldc,
-                   ctypes.addressof(pp), G, n, di, hi, wi, cin, do, ho, wo, cout, ctypes.addressof(used), self._stream())
+        self._call("cwf_wgrad", ctypes.addressof(a), ctypes.addressof(used), self._stream())
         for q in range(G):
             self._wg_pending.append((parts[q].data_ptr(), inv_maps[q].data_ptr(), dw_dsts[q].data_ptr(), _p(db_dsts[q]), int(slab), int(used.value)))
 
@@ -663,16 +613,10 @@ class HipBackend:
         if nsplit <= 0 or slab <= 0 or slab != inv_map.numel():
             raise _lib.CwfError("cwf_wgrad plan failed (%d, %d, %d)" % (nsplit, slab, inv_map.numel()))
         part = self.workspace("wgrad", nsplit * slab, x.device)
-        mode = prec or _WGRAD_PRECISION or _PRECISION
-        if mode == "fp32":
-            self._call("cwf_wgrad_mfma", op, x.data_ptr(), x_ldc, _p(in_scale), _p(in_shift), float(slope),
-                       dy.data_ptr(), dy_ldc, part.data_ptr(), n, di, hi, wi, cin, do, ho, wo, cout, self._stream())
-        else:
-            used = ctypes.c_int(0)
-            self._call("cwf_wgrad_mfma_bf16", op, 1 if mode == "bf16x3" else 0, x.data_ptr(), x_ldc, _p(in_scale), _p(in_shift),
-                       float(slope), dy.data_ptr(), dy_ldc, part.data_ptr(), n, di, hi, wi, cin, do, ho, wo, cout,
-                       ctypes.addressof(used), self._stream())
-            nsplit = used.value
+        a = self._wgrad_args(op, x, x_ldc, in_scale, in_shift, slope, dy, dy_ldc, cout, part, prec)
+        used = ctypes.c_int(0)
+        self._call("cwf_wgrad", ctypes.addressof(a), ctypes.addressof(used), self._stream())
+        nsplit = used.value
         dw = torch.empty(w_numel, dtype=_f32, device=x.device)
         db = torch.empty(cout, dtype=_f32, device=x.device) if has_bias_map else None
         self._call("cwf_wgrad_reduce", part.data_ptr(), nsplit, slab, inv_map.data_ptr(), dw.data_ptr(), _p(db), self._stream())

@@ -2,9 +2,9 @@
 nn.ConvTranspose3d.weight [Cin,Cout,2,2,2]; cls_wise_former.py:157-273,623-642) and the layouts the MFMA
 kernels consume / produce (csrc/conv_mfma.hip, csrc/wgrad_mfma.hip).
 
-Packed weights (input of cwf_conv_mfma):   [class][ci_chunk16][tap][co_tile16][lane64][4]
+Packed weights (input of fp32 cwf_conv):    [class][ci_chunk16][tap][co_tile16][lane64][4]
     element (lane, j): ci = chunk*16 + (lane>>4)*4 + j,  co = tile*16 + (lane & 15)
-Gradient slab (output of cwf_wgrad_mfma):  [class][ci_chunk16][co_group][tap slot 0..ntaps][tile in group][lane64][4]
+Gradient slab (output of fp32 cwf_wgrad):  [class][ci_chunk16][co_group][tap slot 0..ntaps][tile in group][lane64][4]
     element (lane, i): ci = chunk*16 + (lane>>4)*4 + i,  co = (group*CG + tile)*16 + (lane & 15); slot ntaps = bias row.
 
 The maps are int32 arrays: packed[i] = W.flat[map[i]] (or 0 where map < 0), dW.flat[e] = sum_splits slab[map[e]].

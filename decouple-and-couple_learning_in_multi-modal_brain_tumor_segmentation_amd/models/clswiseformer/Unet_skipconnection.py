@@ -2,7 +2,7 @@
 
 Same module tree / parameter names as the reference (InitConv.conv, EnBlock*.conv1/conv2, EnDown*.conv,
 EnDown_4.conv).  InstanceNorm + ReLU never run as separate passes: a conv's epilogue emits the statistics of its
-output and the consumer applies normalise + ReLU while staging its input tile (cwf_conv_mfma prologue).
+output and the consumer applies normalise + ReLU while staging its input tile (cwf_conv prologue).
 All activations are [N, D, H, W, C]."""
 import torch
 import torch.nn as nn

@@ -50,34 +50,79 @@ const char* cwf_arch(void);       /* "gfx950" */
  *   in_scale/in_shift, bias, residual, out_scale may be NULL.
  * stats (nullable): double [N][Cout][2], accumulates sum(y), sum(y*y) per (n, co)  -- the InstanceNorm
  *   statistics of the output, fused into the epilogue.  Must be zeroed by the caller.
- * wpk: weights packed by cwf_gather_batched with an index map built by the host (layout documented in
- *   cwf/packing.py: [class][ci_chunk16][tap][co_tile16][lane64][4]).
  * Input dims (Di,Hi,Wi,Cin), output dims (Do,Ho,Wo,Cout) are the tensor extents of x and y.
+ *
+ * precision selects the MFMA operand form (activations and weights stay fp32 in HBM in every form):
+ *   CWF_FP32    v_mfma_f32_16x16x4_f32, exact f32; wpk packed by cwf_gather_batched ([class][ci_chunk16][tap][co_tile16][lane64][4])
+ *   CWF_BF16X3  split bf16 on v_mfma_f32_16x16x32_bf16: v = hi + lo per operand, hi.hi + hi.lo + lo.hi (~2^-16 per product)
+ *   CWF_BF16    hi.hi only (2^-9 per product)
+ *   The bf16 forms take wpk packed by cwf_gather_split_bf16 ([class][ci_chunk16][tap pair][co_tile16][lane64][hi 8 | lo 8]).
+ *   Layouts and index maps: cwf/packing.py.
  * ---------------------------------------------------------------------------------------------- */
 enum { CWF_CONV3_S1 = 0, CWF_CONV3_S2 = 1, CWF_CONV1 = 2, CWF_CONVT2 = 3, CWF_CONV3_S2_DGRAD = 4, CWF_CONVT2_DGRAD = 5 };
+enum { CWF_FP32 = 0, CWF_BF16X3 = 1, CWF_BF16 = 2 };
 
-int cwf_conv_mfma(int op,
-                  const float* x, int x_ldc, const float* wpk, const float* bias,
-                  float* y, int y_ldc,
-                  const float* in_scale, const float* in_shift, float in_slope,
-                  const float* residual, int r_ldc, const float* out_scale, double* stats,
-                  int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
-                  void* stream);
+/* One forward or data-gradient launch.  Zero-initialise the struct; every optional field is NULL / 0 when unused.  The library
+ * chooses the kernel from the descriptor; a field that no kernel for the layer can honour makes the call return CWF_E_BADARG.
+ *   nb_*     data gradients whose output g feeds the backward of act(IN(nb_x)) (Unet_skipconnection.py:31-77,
+ *            cls_wise_former.py:157-204): stats receives per (n, channel) S1 = sum g*act'(h), S2 = sum g*act'(h)*h with
+ *            h = nb_x*nb_scale + nb_shift (what cwf_in_bwd_stats computes in a pass of its own) instead of (sum y, sum y^2).
+ *            bf16 forms only; stats required.
+ *   x16      the input as a bf16 image [N][D][H][W][16] (x is then not read), zero16 = 16 zero bytes: the single-bf16 data gradient
+ *            of a 3x3x3 stride-1 16 -> 16 layer of >= 32768 voxels reading the image of dy that cwf_in_bwd_apply_ex wrote
+ *            (EnBlock1 / EnBlock1_1 / DeBlock2 / DeBlock2_1).  No prologue, no out_scale.
+ *   y16      also write the output as a bf16 image [N][Do*Ho*Wo][Cout] (DeUp_Cat.conv3, cls_wise_former.py:716-729: the input of the
+ *            next block's first conv, whose weight gradient reads that image): in the same launch where the pointwise stream
+ *            kernel takes the layer, otherwise by a cwf_to_bf16 pass after it.  No nb_x, no out_scale.
+ *   w_raw    the raw nn.Conv3d weight of a forward launch: lets the stem (4 -> 16 channels, InitConv, Unet_skipconnection.py:22-33)
+ *            and the first down-sampling layer (stride 2, 16 -> 32, EnDown1, :60-68) run kernels that read it directly.
+ *   groups   2 or 3 channel-grouped 3x3x3 stride-1 convs in one launch (the three sub-regions' supervision-head convs,
+ *            SuperviseLabel.py:58-81, EdgeSuperviseLabel.py:56-76): group q reads input channels [q*x_goff, q*x_goff + Cin) and
+ *            writes output channels [q*y_goff, q*y_goff + Cout) of the same voxel rows with weights wpk_g[q] and bias bias_g[q]
+ *            (wpk / bias unused).  Bias only: no prologue, residual, out_scale, statistics or images.  0 = an ordinary launch. */
+struct cwf_conv_args {
+  int op, precision;
+  const float* x; int x_ldc; const void* wpk; const float* bias; float* y; int y_ldc;
+  const float* in_scale; const float* in_shift; float in_slope;
+  const float* residual; int r_ldc; const float* out_scale; double* stats;
+  const float* nb_x; int nb_ldc; const float* nb_scale; const float* nb_shift; float nb_slope;
+  const void* x16; const void* zero16; void* y16;
+  const float* w_raw;
+  int groups, x_goff, y_goff; const void* wpk_g[3]; const float* bias_g[3];
+  int N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout;
+};
+int cwf_conv(const struct cwf_conv_args* args /* host */, void* stream);
 
 /* Weight gradient (+ bias gradient) of the same family (op in {CONV3_S1, CONV3_S2, CONV1, CONVT2}):
  *   dW[tap][ci][co] = sum_{n,vox} act(x*in_scale+in_shift)[n, vox*is+tap, ci] * dy[n, vox, co]
- * in two launches: cwf_wgrad_mfma writes `nsplit` partial slabs (MFMA accumulator layout) into `partial`
- * (cwf_wgrad_partial_floats() floats); cwf_wgrad_reduce sums the slabs in slab order and scatters through a host-built
- * INVERSE map (int32 [slab_floats]: >= 0 index into dW ([Cout][Cin][k][k][k] as nn.Conv3d.weight), <= -2 bias index
- * -2-v into db ([Cout], may be NULL), -1 padding).  The split count is chosen by the library: cwf_wgrad_nsplit().      */
+ * in two launches: cwf_wgrad writes partial slabs (MFMA accumulator layout) into `partial` (cwf_wgrad_partial_floats() floats)
+ * and reports how many in *nsplit_used (<= cwf_wgrad_nsplit()); cwf_wgrad_reduce sums the slabs in slab order and scatters
+ * through a host-built INVERSE map (int32 [slab_floats]: >= 0 index into dW ([Cout][Cin][k][k][k] as nn.Conv3d.weight), <= -2
+ * bias index -2-v into db ([Cout], may be NULL), -1 padding).  The slab layout depends on (op, Cin, Cout) only.
+ * Descriptor (zero-initialise; x / dy with their row pitches; precision as for cwf_conv):
+ *   xa16 / dy16  both operands as bf16 images (xa16 = bf16(act(IN(x))) [N][D][H][W][Cin], dy16 [N][D][H][W][Cout]; x / dy are then
+ *                not read), zero16 = 16 zero bytes: single-bf16 3x3x3 stride-1 layers, 16 -> 16 of >= 32768 voxels
+ *                (EnBlock1 / EnBlock1_1 / DeBlock2 / DeBlock2_1) or Cin a multiple of 16 (>= 32) and Cout a multiple of 32
+ *                (EnBlock2/3/4, DeBlock3/4, Enblock8, decouplers; Unet_skipconnection.py:36-57, cls_wise_former.py:691-754).
+ *   dy_scale     dy is taken as dy * dy_scale[n][co]: the backward of the always-on dropout3d behind InitConv
+ *                (Unet_skipconnection.py:29-33) folded into the stem's weight gradient; bf16 forms, 3x3x3 stride-1 layers with
+ *                Cin <= 16, Cout = 16 and >= 32768 voxels.
+ *   groups       2 or 3 same-shape 3x3x3 stride-1 layers in one launch: group q has its own activation view x_g[q], gradient view
+ *                dy_g[q] (row pitches x_ldc / dy_ldc) and slab buffer partial_g[q] (each sized like a single layer's); no
+ *                prologue; bf16 forms.  Reduce each group like a single layer.  0 = an ordinary launch.                  */
 int cwf_wgrad_nsplit(int op, int N, int Do, int Ho, int Wo, int Cin, int Cout);
 int64_t cwf_wgrad_partial_floats(int op, int N, int Do, int Ho, int Wo, int Cin, int Cout);
 int64_t cwf_wgrad_slab_floats(int op, int Cin, int Cout);
-int cwf_wgrad_mfma(int op,
-                   const float* x, int x_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                   const float* dy, int dy_ldc, float* partial,
-                   int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
-                   void* stream);
+struct cwf_wgrad_args {
+  int op, precision;
+  const float* x; int x_ldc; const float* in_scale; const float* in_shift; float in_slope;
+  const float* dy; int dy_ldc;
+  const float* dy_scale; const void* xa16; const void* dy16; const void* zero16;
+  float* partial;
+  int groups; const float* x_g[3]; const float* dy_g[3]; float* partial_g[3];
+  int N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout;
+};
+int cwf_wgrad(const struct cwf_wgrad_args* args /* host */, int* nsplit_used /* host out, nullable */, void* stream);
 int cwf_wgrad_reduce(const float* partial, int nsplit, int64_t slab_floats,
                      const int32_t* inv_map, float* dW, float* db, void* stream);
 /* every layer of a backward phase in one launch: table = DEVICE array of descriptors (same slab / inverse-map conventions as
@@ -87,62 +132,8 @@ int cwf_wgrad_reduce_batched(const struct cwf_wgrad_reduce_desc* table, int nlay
 
 struct cwf_gather_desc { const float* src; float* dst; const int32_t* map; int64_t n; };
 
-/* The stem: y = (conv3x3x3(x; w) + bias) * out_scale for 4 -> 16 channels (InitConv + its always-on dropout3d, Unet_skipconnection.py:22-33)
- * with K = 8 taps x 4 channels per MFMA step; x [N][D][H][W][4] fp32 (ldc x_ldc), w the RAW nn.Conv3d weight [16][4][3][3][3], y ldc y_ldc;
- * out_scale [N][16] and stats [N][16][2] (sum, sum of squares of y) nullable.  x3: split-bf16 (3 MFMAs) / single bf16. */
-int cwf_conv_stem_bf16(int x3, const float* x, int x_ldc, const float* w, const float* bias, float* y, int y_ldc,
-                       const float* out_scale, double* stats, int N, int D, int H, int W, void* stream);
-
-/* The first down-sampling layer: y = conv3x3x3 stride 2 (x; w) + bias for 16 -> 32 channels (EnDown1, Unet_skipconnection.py:60-68); x
- * [N][Di][Hi][Wi][16] fp32 (ldc x_ldc), w the RAW nn.Conv3d weight [32][16][3][3][3], y [N][(Di+1)/2][(Hi+1)/2][(Wi+1)/2][32] (ldc y_ldc);
- * stats [N][32][2] nullable. */
-int cwf_conv_s2c16_bf16(int x3, const float* x, int x_ldc, const float* w, const float* bias, float* y, int y_ldc, double* stats,
-                        int N, int Di, int Hi, int Wi, void* stream);
-
-/* Split-bf16 forms of K1 (same geometry, epilogues and argument meaning; activations and weights stay fp32 in HBM):
- * MFMA operands are bf16 on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.
- *   x3 != 0 ("bf16x3"): v = hi + lo per operand, products hi.hi + hi.lo + lo.hi  (~2^-16 relative per product, 3 MFMAs)
- *   x3 == 0 ("bf16")  : hi.hi only                                                 (2^-9 relative per product, 1 MFMA)
- * wpk16: weights packed by cwf_gather_split_bf16 ([class][ci_chunk16][tap pair][co_tile16][lane64][hi 8 | lo 8] bf16);
- * its index map has one int32 per bf16 element of the hi image (8 per lane), see cwf/packing.py.                       */
-int cwf_conv_mfma_bf16(int op, int x3,
-                       const float* x, int x_ldc, const void* wpk16, const float* bias,
-                       float* y, int y_ldc,
-                       const float* in_scale, const float* in_shift, float in_slope,
-                       const float* residual, int r_ldc, const float* out_scale, double* stats,
-                       int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
-                       void* stream);
-/* Same, with "norm-backward" statistics for data-gradient launches whose output g is the gradient of act(IN(x)) (the fused
- * prologue of the forward conv, Unet_skipconnection.py:31-77 / cls_wise_former.py:157-204): with nb_x set, stats receives per
- * (n, channel)  S1 = sum g*act'(h), S2 = sum g*act'(h)*h  with h = nb_x*nb_scale + nb_shift -- exactly what cwf_in_bwd_stats
- * computes in a separate pass over g and x -- so that only cwf_in_bwd_apply remains of the InstanceNorm backward. */
-int cwf_conv_mfma_bf16_nb(int op, int x3,
-                          const float* x, int x_ldc, const void* wpk16, const float* bias,
-                          float* y, int y_ldc,
-                          const float* in_scale, const float* in_shift, float in_slope,
-                          const float* residual, int r_ldc, const float* out_scale, double* stats,
-                          const float* nb_x, int nb_ldc, const float* nb_scale, const float* nb_shift, float nb_slope,
-                          int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
-                          void* stream);
-/* `groups` (2 or 3) same-shape 3x3x3 stride-1 layers' weight-gradient slabs in ONE launch: group q has its own activation view
- * h_x[q] (row pitch x_ldc), gradient view h_dy[q] (row pitch dy_ldc) and slab buffer h_partial[q] (each sized like a single layer's,
- * cwf_wgrad_partial_floats); no prologue.  h_*: HOST arrays of device pointers.  Reduce each group like a single layer. */
-int cwf_wgrad_mfma_bf16_grouped(int op, int x3, const float* const* h_x, int x_ldc, const float* const* h_dy, int dy_ldc,
-                                float* const* h_partial, int groups,
-                                int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int* nsplit_used, void* stream);
-/* Channel-grouped 3x3x3 stride-1 conv (op = CWF_CONV3_S1; forward, or the data gradient through the transposed packed weights):
- * `groups` (2 or 3) independent convs Cin -> Cout, group q reading input channels [q*x_goff, q*x_goff + Cin) and writing output
- * channels [q*y_goff, q*y_goff + Cout) of the same voxel rows, each with its own packed weights / bias (h_wpk16, h_bias: HOST arrays
- * of `groups` device pointers; h_bias or its entries may be NULL) -- one launch for the three sub-regions' supervision-head convs
- * (SuperviseLabel.py:58-81, EdgeSuperviseLabel.py:56-76).  Bias only: no prologue, residual, out_scale or statistics. */
-int cwf_conv_mfma_bf16_grouped(int op, int x3, const float* x, int x_ldc, int x_goff, const void* const* h_wpk16, const float* const* h_bias,
-                               float* y, int y_ldc, int y_goff, int groups,
-                               int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream);
-int cwf_wgrad_mfma_bf16(int op, int x3,
-                        const float* x, int x_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                        const float* dy, int dy_ldc, float* partial,
-                        int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
-                        int* nsplit_used /* host out, nullable: slabs actually written (<= cwf_wgrad_nsplit()) */, void* stream);
+/* the bf16 packing: cwf_gather_batched's table, each value written as its bf16 hi and lo parts (the index map has one int32 per
+ * bf16 element of the hi image, 8 per lane) */
 int cwf_gather_split_bf16(const struct cwf_gather_desc* table, int nlayers, int64_t max_n, void* stream);
 
 /* dst[i] = map[i] >= 0 ? src[map[i]] : 0 for a table of `nlayers` descriptors resident in device memory
@@ -181,40 +172,6 @@ int cwf_norm_act_add_ex(const float* x, int x_ldc, const float* scale, const flo
 /* y16 [N*V][C] bf16 = bf16(act(x*scale+shift))  (scale == NULL: bf16(x)) */
 int cwf_to_bf16(const float* x, int x_ldc, const float* scale, const float* shift, float slope, void* y16,
                 int N, int64_t V, int C, void* stream);
-/* cwf_conv_mfma_bf16 for a 1x1x1 conv (CWF_CONV1, Cout a multiple of 4) that ALSO writes its output as a bf16 image y16 [N][Do*Ho*Wo][Cout]
- * (DeUp_Cat.conv3, cls_wise_former.py:716-729: the un-normalised input of the next block's first conv, whose weight gradient reads that
- * image).  CWF_E_BADARG if the layer is not one the pointwise stream kernel takes. */
-int cwf_conv_mfma_bf16_y16(int op, int x3, const float* x, int x_ldc, const void* wpk16, const float* bias,
-                           float* y, int y_ldc, void* y16, const float* in_scale, const float* in_shift, float in_slope,
-                           const float* residual, int r_ldc, double* stats,
-                           int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, void* stream);
-/* cwf_conv_mfma_bf16_nb (single-bf16 operand products) for a 3x3x3 stride-1 16 -> 16 layer of >= 32768 voxels whose INPUT exists as a
- * bf16 image x16 [N][D][H][W][16] -- the data gradient of EnBlock1 / EnBlock1_1 / DeBlock2 / DeBlock2_1 reading the bf16 image of dy that
- * cwf_in_bwd_apply_ex wrote (the data half of aten::convolution_backward, Unet_skipconnection.py:36-57).  zero16: 16 zero bytes. */
-int cwf_conv_mfma_bf16_in16(int op, const void* x16, const void* zero16, const void* wpk16, const float* bias,
-                            float* y, int y_ldc, const float* residual, int r_ldc, double* stats,
-                            const float* nb_x, int nb_ldc, const float* nb_scale, const float* nb_shift, float nb_slope,
-                            int N, int D, int H, int W, void* stream);
-/* Weight / bias gradient slabs of a 3x3x3 stride-1 16 -> 16 conv (padding 1) from bf16 operand images (single-bf16 products, fp32
- * accumulate): xa16 = bf16(act(IN(x))) [N][D][H][W][16], dy16 [N][D][H][W][16], zero16 = 16 zero bytes (the padding source of the
- * LDS-DMA loaders).  Slab layout and reduction: cwf_wgrad_mfma_bf16(CWF_CONV3_S1, 16, 16) / cwf_wgrad_reduce.
- * Replaces the weight half of aten::convolution_backward for EnBlock1 / EnBlock1_1 / DeBlock2 / DeBlock2_1 (Unet_skipconnection.py:36-57,
- * cls_wise_former.py:732-754). */
-int cwf_wgrad16_bf16(const void* xa16, const void* dy16, const void* zero16, float* partial,
-                     int N, int D, int H, int W, int* nsplit_used, void* stream);
-
-/* cwf_wgrad_mfma_bf16 with dy taken as dy * dy_scale[n][co] -- the backward of the always-on dropout3d behind InitConv
- * (Unet_skipconnection.py:29-33) folded into the stem's weight gradient; CWF_CONV3_S1 layers with Cin <= 16, Cout = 16 and
- * >= 32768 voxels only (CWF_E_BADARG otherwise). */
-int cwf_wgrad_mfma_bf16_dys(int op, int x3, const float* x, int x_ldc, const float* in_scale, const float* in_shift, float in_slope,
-                            const float* dy, int dy_ldc, const float* dy_scale, float* partial,
-                            int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int* nsplit_used, void* stream);
-/* The same for the 3x3x3 stride-1 layers with Cin a multiple of 16 (>= 32) and Cout a multiple of 32 (EnBlock2/3/4, DeBlock3/4, Enblock8,
- * decouplers; Unet_skipconnection.py:36-57, cls_wise_former.py:691-754): xa16 [N][D][H][W][Cin], dy16 [N][D][H][W][Cout] bf16.
- * Slab layout and reduction: cwf_wgrad_mfma_bf16(CWF_CONV3_S1, Cin, Cout) / cwf_wgrad_reduce. */
-int cwf_wgrad_s1_bf16(const void* xa16, const void* dy16, const void* zero16, float* partial,
-                      int N, int D, int H, int W, int Cin, int Cout, int* nsplit_used, void* stream);
-
 /* ------------------------------------------------------------------------------------------------
  * K6/K7  token path: LayerNorm, Linear (strided batched MFMA GEMM), softmax rows, GELU
  *        ResidualNorm.py:4-47, SelfAttention.py:74-102

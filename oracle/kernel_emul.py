@@ -105,7 +105,7 @@ class EmulBackend:
     # ------------------------------------------------------------------ K1
     def conv(self, op, x, wpk, bias, cout, in_scale=None, in_shift=None, slope=1.0, residual=None, out_scale=None,
              stats=None, out=None, w_ref=None, out_channels_alloc=None, fwd_op=None, prec=None, bias_ref=None):
-        """cwf_conv_mfma: F.conv3d / F.conv_transpose3d on act(IN(x)) (+bias, +residual, *out_scale) or, for the
+        """cwf_conv: F.conv3d / F.conv_transpose3d on act(IN(x)) (+bias, +residual, *out_scale) or, for the
         data-gradient forms (fwd_op given), the adjoint of the forward conv w.r.t. its (activated) input."""
         assert w_ref is not None
         if isinstance(w_ref, (tuple, list)):               # a fused layer (FusedConvSpec): the sources' parameters, concatenated
@@ -138,7 +138,7 @@ class EmulBackend:
 
 
     def conv_grouped(self, x_all, cin, wpks, biases, cout, y_all, x_goff, y_goff, w_refs=None, fwd_op=None, prec=None):
-        """cwf_conv_mfma_bf16_grouped: G channel-grouped 3x3x3 stride-1 convs (or their data gradients) -- one conv per group"""
+        """cwf_conv with groups: G channel-grouped 3x3x3 stride-1 convs (or their data gradients) -- one conv per group"""
         assert w_refs is not None
         for q, w in enumerate(w_refs):
             xs = x_all[..., q * x_goff:q * x_goff + cin]
@@ -151,7 +151,7 @@ class EmulBackend:
                 y_all[..., q * y_goff:q * y_goff + cout] = out
         return y_all
     def wgrad(self, op, x, in_scale, in_shift, slope, dy, cout, inv_map, has_bias_map, w_numel, w_ref_shape=None, prec=None, allow_async=False):
-        """cwf_wgrad_mfma + cwf_wgrad_reduce: weight / bias halves of aten::convolution_backward on act(IN(x))."""
+        """cwf_wgrad + cwf_wgrad_reduce: weight / bias halves of aten::convolution_backward on act(IN(x))."""
         xa = _prologue(x, in_scale, in_shift, slope).detach()
         w = torch.zeros(w_ref_shape, dtype=torch.float32, requires_grad=True)
         b = torch.zeros(cout, dtype=torch.float32, requires_grad=True)

@@ -20,12 +20,12 @@ What each kernel path rounds, read from its source (csrc/):
       epilogue       = (acc + bias + residual) * out_scale (the fast epilogue never has residual and out_scale together);
                        statistics S1 = sum y, S2 = sum y^2 of the stored fp32 y; norm-backward sums (nb=) S1 = sum g,
                        S2 = sum g * h with g = y * act'(h), h = fmaf(nb_x, nb_scale, nb_shift).
-  conv16s with x16= (cwf_conv_mfma_bf16_in16): the input is the bf16 image hi(dy) -- the same operand as the single-bf16 launch.
-  cwf_conv_stem_bf16, cwf_conv_s2c16_bf16: raw fp32 weights split in the kernel by the same rule; no prologue.
-  cwf_wgrad_mfma_bf16 (tiled, both modes), cwf_wgrad16_bf16 / cwf_wgrad_s1_bf16 (bf16 images: hi only), the grouped launch:
+  conv16s with x16= (cwf_conv with x16): the input is the bf16 image hi(dy) -- the same operand as the single-bf16 launch.
+  stem and stride-2 kernels (cwf_conv with w_raw): raw fp32 weights split in the kernel by the same rule; no prologue.
+  cwf_wgrad (tiled, both modes), wgrad16d / wgrad_s1d (bf16 images: hi only), the grouped launch:
       x operand as above (recomputed prologue), dy operand hi(dy) (+ lo(dy) in split mode);
       bias slot = ones . dy with the bf16 operand: sum hi(dy) (single), sum hi(dy) + lo(dy) (split).
-  cwf_wgrad_mfma_bf16_dys (dy_scale): dy operand hi(fp32(dy * s)); in split mode the compiler contracts the multiply into the
+  cwf_wgrad with dy_scale: dy operand hi(fp32(dy * s)); in split mode the compiler contracts the multiply into the
       lo-part subtraction, lo = bf16(fma(dy, s, -hi)) -- emulated here as bf16(fp32(dy * s - hi)) from an exact float64
       product (one fp32 rounding, as the fma).  The bias slot carries the same operands.
   pw_wgrad_kernel (1x1x1 / ConvTranspose weight gradients): fp32 MFMA on fp32 operands -- exact products in both bf16 modes;
@@ -218,7 +218,7 @@ def conv_ref(op, x, w, mode, bias=None, in_scale=None, in_shift=None, slope=1.0,
 
 
 def wgrad_operand_mode(op, cin, cout, size, mode):
-    """the operand form of the weight-gradient kernel cwf_wgrad_mfma_bf16 runs for op (cin -> cout) on a forward input of extent
+    """the operand form of the weight-gradient kernel cwf_wgrad runs for op (cin -> cout) on a forward input of extent
     size (D, H, W) -- wgrad_bf16_impl, csrc/wgrad_bf16.hip: pw_wgrad_kernel (exact fp32 products in both bf16 modes) for 1x1x1 layers
     with D*H*W % 4 == 0 and (16-channel chunks, 16-channel tiles) in {(1, 1), (2, 1), (4, 2), (8, 4)}, and for ConvTranspose layers
     with D*H*W % 4 == 0, W % 4 == 0 and (chunks, tiles) in {(1, 1), (2, 2)}; the bf16 tiled / persistent kernels otherwise"""

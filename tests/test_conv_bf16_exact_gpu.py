@@ -197,7 +197,7 @@ def test_pointwise_bf16_side_output_is_the_rounded_output(hip):
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("cin,cout,size,n,G", [(128, 32, (8, 8, 16), 2, 3), (8, 2, (8, 12, 16), 2, 3), (16, 16, (6, 8, 20), 2, 2)])
 def test_grouped_conv_is_operand_exact(hip, cin, cout, size, n, G, mode, probe):
-    """cwf_conv_mfma_bf16_grouped forward and data gradient; padding channels and other groups' channels stay as written"""
+    """cwf_conv with groups: forward and data gradient; padding channels and other groups' channels stay as written"""
     ca = (cout + 3) // 4 * 4
     x_all = _field((n, *size, G * cin), probe, seed=21)
     ws = [_weights(pk.CONV3_S1, cin, cout, probe, seed=22 + q) for q in range(G)]
@@ -341,7 +341,7 @@ def test_every_tile_configuration_is_operand_exact(hip, cfg, cin, cout, size, n,
 
 
 # ====================================================================================================== weight gradient
-# path: (op, cin, cout, size, n, route): "tiled" = hip.wgrad (cwf_wgrad_mfma_bf16, pw_wgrad_kernel for 1x1x1 / transposed),
+# path: (op, cin, cout, size, n, route): "tiled" = hip.wgrad (cwf_wgrad, pw_wgrad_kernel for 1x1x1 / transposed),
 # "images" = wgrad_to in the bench's precision setting (bf16 operand images: wgrad16 / wgrad_s1), "dys" = the dy_scale fold
 WGRAD = {
     "tiled_s1": (pk.CONV3_S1, 48, 16, (9, 10, 20), 2, "tiled"),

@@ -209,7 +209,7 @@ def test_conv16s_reads_a_bf16_input_image(hip, size, n):
 
 @pytest.mark.parametrize("cin,cout,size,n", [(32, 32, (16, 16, 32), 2), (64, 64, (8, 12, 16), 1), (128, 256, (6, 6, 10), 2), (96, 96, (8, 8, 16), 1)])
 def test_dma_weight_gradient_32_channel_groups(hip, cin, cout, size, n):
-    """cwf_wgrad_s1_bf16 (wgrad_s1d_kernel: bf16 images by LDS-DMA, 16-channel chunks x 32-channel groups) against the fp32-tensor
+    """cwf_wgrad on bf16 images (wgrad_s1d_kernel: bf16 images by LDS-DMA, 16-channel chunks x 32-channel groups) against the fp32-tensor
     kernel (same single-bf16 operands: summation order only) and the oracle; ragged tiles included."""
     from cwf import functional as CF, kernels
     d, h, w_ = size
@@ -243,7 +243,7 @@ def test_dma_weight_gradient_32_channel_groups(hip, cin, cout, size, n):
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
 @pytest.mark.parametrize("size,n", [((32, 32, 32), 2), ((34, 38, 50), 1), ((64, 64, 64), 2)])
 def test_stem_kernel_packs_eight_taps_times_four_channels(hip, size, n, prec):
-    """cwf_conv_stem_bf16 (K = 8 taps x 4 channels, raw weights) against the oracle and against the 16-channel-slot kernel it replaces
+    """the stem kernel (cwf_conv with w_raw; K = 8 taps x 4 channels, raw weights) against the oracle and against the 16-channel-slot kernel it replaces
     (same operand values, another summation order), with bias, dropout3d scale and output statistics; ragged tiles included."""
     from cwf import functional as CF
     d, h, w_ = size
@@ -272,7 +272,7 @@ def test_stem_kernel_packs_eight_taps_times_four_channels(hip, size, n, prec):
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
 @pytest.mark.parametrize("size,n", [((64, 64, 64), 2), ((34, 38, 70), 1), ((128, 128, 128), 1)])
 def test_first_downsampling_kernel(hip, size, n, prec):
-    """cwf_conv_s2c16_bf16 (3x3x3 stride 2, 16 -> 32, parity-split halo rows, raw weights) against the oracle and against the tap-table
+    """the first down-sampling kernel (cwf_conv with w_raw; 3x3x3 stride 2, 16 -> 32, parity-split halo rows, raw weights) against the oracle and against the tap-table
     kernel it replaces, with bias and output statistics; odd extents / ragged tiles included."""
     from cwf import functional as CF
     d, h, w_ = size
@@ -322,7 +322,7 @@ def _bf16_rne(t):
 
 @pytest.mark.parametrize("size,n", [((64, 64, 64), 2), ((34, 38, 50), 1), ((32, 32, 32), 1)])
 def test_bf16_operand_images_and_dma_weight_gradient(hip, size, n):
-    """Round 3: the full-resolution 16-channel weight gradient on bf16 operand images (cwf_wgrad16_bf16, LDS-DMA staging).
+    """Round 3: the full-resolution 16-channel weight gradient on bf16 operand images (wgrad16d_kernel, LDS-DMA staging).
     (a) cwf_in_bwd_apply_ex: dx bit-equal to cwf_in_bwd_apply, dx16 = bf16(dx), xa16 = bf16(act(IN(x))) -- with and without the
         fp32 output; cwf_norm_act_add_ex / cwf_to_bf16 likewise.
     (b) the DMA kernel's dW / db equal the fp32-tensor kernel's (same single-bf16 operand values: tolerance = summation order only),
@@ -400,7 +400,7 @@ def _dy_scale(n, seed):
 @pytest.mark.parametrize("cin,prologue,mode", [(4, False, "bf16"), (4, False, "bf16x3"), (16, True, "bf16x3")])
 @pytest.mark.parametrize("size,n", [((32, 32, 32), 2), ((34, 38, 50), 2), ((64, 64, 64), 1)])
 def test_weight_gradient_folds_a_per_sample_channel_scale(hip, cin, prologue, mode, size, n):
-    """wgrad_to(..., dy_scale=s) (cwf_wgrad_mfma_bf16_dys: the stem's dropout3d folded into its weight gradient under a gradient sink)
+    """wgrad_to(..., dy_scale=s) (cwf_wgrad with dy_scale: the stem's dropout3d folded into its weight gradient under a gradient sink)
     == wgrad_to on channel_scale(dy, s) == the oracle on dy * s.  (32, 32, 32) x 2 is exactly the 32768-voxel threshold, (34, 38, 50)
     has ragged 4 x 4 x 16 tiles in every dimension.  Single-bf16 products: bit equal to the unfolded call (same kernel, grid and operand
     values).  Split-bf16 (bf16x3): the compiler contracts the fold's multiply into the lo-part subtraction, lo = bf16(fma(dy, s, -hi))
@@ -692,7 +692,7 @@ def test_pointwise_weight_gradient_stream(hip, op, cin, cout, size, n, prec):
     (16, 16, (6, 8, 20), 1, 2),                  # two groups, ragged tiles
 ])
 def test_channel_grouped_conv(hip, cin, cout, size, n, G, prec):
-    """cwf_conv_mfma_bf16_grouped (forward and data gradient) against one oracle conv per group; other channels of the output
+    """cwf_conv with groups (forward and data gradient) against one oracle conv per group; other channels of the output
     buffer stay untouched."""
     tol = PREC_TOL[prec]
     from cwf import functional as CF
@@ -730,7 +730,7 @@ def test_channel_grouped_conv(hip, cin, cout, size, n, G, prec):
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
 @pytest.mark.parametrize("cin,cout,size,n", [(128, 32, (8, 8, 16), 2), (32, 2, (8, 8, 16), 2), (32, 8, (8, 12, 16), 1), (8, 2, (8, 12, 16), 2)])
 def test_channel_grouped_weight_gradient(hip, cin, cout, size, n, prec):
-    """cwf_wgrad_mfma_bf16_grouped: three layers' slabs from one launch (producer/consumer kernel for 128 -> 32 and 32 -> 8, the
+    """cwf_wgrad with groups: three layers' slabs from one launch (producer/consumer kernel for 128 -> 32 and 32 -> 8, the
     generic tiled kernel for the 2-channel layers), reduced by the batched reduce, equal the per-layer weight / bias gradients."""
     from cwf import functional as CF
     G = 3

@@ -690,7 +690,7 @@ def _flat_by_name(m, tr):
 @pytest.mark.parametrize("wgrad", ["bf16", "bf16x3"])
 def test_trainer_step_with_stem_dropout_vs_oracle(hip, monkeypatch, wgrad):
     """bench.py trains with the stem's always-on dropout3d; under the gradient sink its backward folds the keep mask into the stem's weight
-    gradient (cwf_wgrad_mfma_bf16_dys: wgrad_to(..., dy_scale=)) instead of a channel_scale pass over dy.  With the mask and the top-k
+    gradient (cwf_wgrad with dy_scale: wgrad_to(..., dy_scale=)) instead of a channel_scale pass over dy.  With the mask and the top-k
     selections teacher-forced, batch 2 at 64^3 in the bench precision (single- and split-bf16 weight-gradient products):
     (1) the Trainer's flat gradient against the float64 oracle, twice (the second step on cached tables), with the golden test's bounds;
     (2) the fold ran: one wgrad_to call per step carries dy_scale, for the stem;  (3) plain autograd (no sink) takes channel_scale and

@@ -47,6 +47,16 @@ __device__ __forceinline__ void split_bf16(float a, float b, unsigned& hi, unsig
 __device__ __forceinline__ float act01(float v, float slope) { return fmaxf(v, v * slope); }
 
 
+// The extent choose_cfg tiles (per output-parity class) and the class count of a launch: the output extent, or for the eight-class
+// launches (ConvTranspose forward, stride-2 data gradient) the extent of one class.  Shared by the fp32 (conv_mfma.hip) and the
+// split-bf16 (conv_bf16.hip) tap-table launches and their configuration queries.
+static inline int cfg_extent(int op, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int cd[3]) {
+  cd[0] = Do; cd[1] = Ho; cd[2] = Wo;
+  if (op == CWF_CONVT2) { cd[0] = Di; cd[1] = Hi; cd[2] = Wi; return 8; }
+  if (op == CWF_CONV3_S2_DGRAD) { cd[0] = (Do + 1) / 2; cd[1] = (Ho + 1) / 2; cd[2] = (Wo + 1) / 2; return 8; }
+  return 1;
+}
+
 // conv_ws.hip: launches the weight-stationary kernel when the layer is one it takes (returns 1, status in *rc); 0 = not eligible.
 int cwf_try_conv_ws(int op, int x3, ConvArgsB& a, hipStream_t st, int* rc);
 

@@ -1262,15 +1262,6 @@ int launch_cfg(const ConvArgsB& a, hipStream_t st) {
 }
 }  // namespace
 
-// The extent choose_cfg tiles (per output-parity class) and the class count of a launch: the output extent, or for the eight-class
-// launches (ConvTranspose forward, stride-2 data gradient) the extent of one class.
-static int cfg_extent(int op, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int cd[3]) {
-  cd[0] = Do; cd[1] = Ho; cd[2] = Wo;
-  if (op == CWF_CONVT2) { cd[0] = Di; cd[1] = Hi; cd[2] = Wi; return 8; }
-  if (op == CWF_CONV3_S2_DGRAD) { cd[0] = (Do + 1) / 2; cd[1] = (Ho + 1) / 2; cd[2] = (Wo + 1) / 2; return 8; }
-  return 1;
-}
-
 // Read-only query (tests): the tile configuration {MT, NT, WM} that conv_bf16_impl's choose_cfg picks for a launch of `op` from input
 // extent Di x Hi x Wi to output extent Do x Ho x Wo.  Whether the launch reaches the tap-table kernel at all (pointwise,
 // weight-stationary, conv16 routes) is not decided here.  Launches nothing.

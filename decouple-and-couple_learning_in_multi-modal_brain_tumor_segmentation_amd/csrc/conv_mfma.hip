@@ -283,6 +283,19 @@ int launch_cfg(const ConvArgs& a, hipStream_t st) {
 }
 }  // namespace
 
+// Read-only query (tests): the tile configuration {MT, NT, WM} that conv_fp32_launch picks for a launch of `op` from input extent
+// Di x Hi x Wi to output extent Do x Ho x Wo.  Launches nothing.
+extern "C" int cwf_debug_conv_fp32_cfg(int op, int N, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cout, int* mt_nt_wm) {
+  if (!mt_nt_wm || N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || op < CWF_CONV3_S1 ||
+      op > CWF_CONVT2_DGRAD)
+    return CWF_E_BADARG;
+  int cd[3];
+  const int ncls = cfg_extent(op, Di, Hi, Wi, Do, Ho, Wo, cd);
+  const TileCfg c = choose_cfg(op, cd, ncls, N, cdiv(Cout, 16));
+  mt_nt_wm[0] = c.MT; mt_nt_wm[1] = c.NT; mt_nt_wm[2] = c.WM;
+  return 0;
+}
+
 int conv_fp32_launch(const cwf_conv_args& d, hipStream_t st) {
   const int op = d.op, N = d.N, Di = d.Di, Hi = d.Hi, Wi = d.Wi, Cin = d.Cin, Do = d.Do, Ho = d.Ho, Wo = d.Wo, Cout = d.Cout;
   const float* x = d.x; const int x_ldc = d.x_ldc, y_ldc = d.y_ldc;
@@ -291,10 +304,8 @@ int conv_fp32_launch(const cwf_conv_args& d, hipStream_t st) {
   if ((Cin & 3) || (x_ldc & 3) || x_ldc < Cin || y_ldc < Cout) return CWF_E_ALIGN;
   if (((uintptr_t)x & 15) || ((uintptr_t)wpk & 15)) return CWF_E_ALIGN;
   ConvArgs a;
-  // class grid extents for the heuristic
-  int cd[3] = {Do, Ho, Wo}; int ncls = 1;
-  if (op == CWF_CONVT2) { cd[0] = Di; cd[1] = Hi; cd[2] = Wi; ncls = 8; }
-  if (op == CWF_CONV3_S2_DGRAD) { cd[0] = (Do + 1) / 2; cd[1] = (Ho + 1) / 2; cd[2] = (Wo + 1) / 2; ncls = 8; }
+  int cd[3];
+  const int ncls = cfg_extent(op, Di, Hi, Wi, Do, Ho, Wo, cd);
   const TileCfg c = choose_cfg(op, cd, ncls, N, cdiv(Cout, 16));
   int rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, y_ldc, c.MT * c.WM);
   if (rc) return rc;

@@ -254,6 +254,18 @@ extern "C" int64_t cwf_wgrad_partial_floats(int op, int N, int Do, int Ho, int W
   WgPlan p; int rc = make_plan_shape(p, op, N, Do, Ho, Wo, Cin, Cout); return rc ? rc : p.slab * p.nsplit;
 }
 
+// Read-only query (tests): the plan wgrad_fp32_launch makes for a launch on the real geometry (input extent Di x Hi x Wi, output
+// extent Do x Ho x Wo): out = {tapsplit (1: the 27-tap kernel, 0: the 1-tap kernel), CG (16-channel output tiles per workgroup),
+// nsplit (slabs written), tiles per split, slab floats, spatial tiles in all}.  Launches nothing.
+extern "C" int cwf_debug_wgrad_fp32_plan(int op, int N, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int64_t* out) {
+  if (!out || N <= 0 || Cin <= 0 || Cout <= 0) return CWF_E_BADARG;
+  WgPlan p;
+  const int rc = make_plan(p, op, N, Di, Hi, Wi, Cin, (Cin + 3) & ~3, Do, Ho, Wo, Cout, (Cout + 3) & ~3);
+  if (rc) return rc;
+  out[0] = p.tapsplit; out[1] = p.CG; out[2] = p.nsplit; out[3] = p.tps; out[4] = p.slab; out[5] = p.total;
+  return 0;
+}
+
 int wgrad_fp32_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
   const int op = d.op, N = d.N, Cin = d.Cin, x_ldc = d.x_ldc, dy_ldc = d.dy_ldc;
   const float* x = d.x; const float* dy = d.dy; float* partial = d.partial;

@@ -30,10 +30,14 @@ What each kernel path rounds, read from its source (csrc/):
       product (one fp32 rounding, as the fma).  The bias slot carries the same operands.
   pw_wgrad_kernel (1x1x1 / ConvTranspose weight gradients): fp32 MFMA on fp32 operands -- exact products in both bf16 modes;
       bias = sum dy.
+The fp32 family (csrc/conv_mfma.hip conv_mfma_kernel, csrc/wgrad_mfma.hip wgrad_mfma_kernel + the slab reduces) multiplies the
+fp32 operands themselves ("fp32" mode: exact products in float64) and is held to gamma_fp32(chain) below, not to GAMMA_CONV.
 Not reproduced bit for bit: the prologue's fma is emulated in float64 and rounded once to fp32 (a double rounding can differ
 from fmaf in the last fp32 bit in rare ties; the bf16 rounding after it hides that except at bf16 ties) -- covered by gamma.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -44,6 +48,47 @@ FWD_OF_DGRAD = {CONV3_S2_DGRAD: CONV3_S2, CONVT2_DGRAD: CONVT2}
 GAMMA_CONV = 2.0 ** -18         # forward / data gradient: |got - ref| <= gamma * A
 GAMMA_WGRAD = 2.0 ** -16        # weight gradients (K up to millions, split-K slabs + reduce)
 REL_SUMS = 1e-6                 # statistics / norm-backward sums, relative to the float64 sums of |terms|
+
+# ------------------------------------------------------------------ the fp32 family's bound
+# Rounding model.  v_mfma_f32_16x16x4_f32 adds 4 products per step to an fp32 accumulator.  Whether it rounds once per step or once
+# per product is not documented here, so the weaker model is assumed: every product is added with a rounding of its own (and the
+# product itself may round once).  A result s = sum p_i then carries err = sum_j delta_j s_j, |delta_j| <= u = 2^-24, where the s_j
+# are partial sums of the same terms, |s_j| <= A.  "chain" = the number of roundings on the longest path from a product to the
+# stored result.  The worst case, chain * u * A (2^-11.2 A at 256 channels x 27 taps), would let a missing channel chunk through;
+# round-to-nearest errors are mean-zero and, in the standard probabilistic model (Higham & Mary 2019), independent, so err is a sum
+# of `chain` independent terms bounded by u A each and Hoeffding's inequality gives
+#     P(|err| > lambda sqrt(chain) u A) <= 2 exp(-lambda^2 / 2)        lambda = 8:  2.5e-14 per result
+# i.e. gamma_fp32(chain) = 8 sqrt(chain) 2^-24.  (2^-18 = GAMMA_CONV is lambda ~ 0.77 at chain 6912: at or past its limit -- a CPU
+# simulation of that chain with all-positive operands reaches 1.25 x 2^-18.)
+# The chains, read from the kernels:
+#   forward / data gradient (conv_mfma_kernel): one register accumulator per (output voxel, channel), never split across waves; the
+#       channel-chunk loop (ceil(C/16) chunks of 16 input channels) x the tap loop (ntaps of the output's class: 27, 8 (ConvTranspose
+#       data gradient), 1..8 (stride-2 data-gradient parity classes), 1) x 4 MFMAs x 4 products -- 16 ceil(C/16) ntaps products --
+#       then the epilogue's + bias, + residual, * out_scale (3), plus the product's own rounding (1): conv_chain_fp32.  C is the
+#       launch's input channel count (the forward's Cout for a data gradient).  256 channels x 27 taps: chain 6916, gamma 2^-14.6.
+#   weight gradient (wgrad_mfma_kernel): one accumulator per (tap, ci, co) and slab over the voxels of `tiles per split` spatial
+#       tiles of TD x TH x 16 voxels (the 27-tap kernel: every voxel of a tile through one wave; the 1-tap kernel: a quarter of the
+#       M-tiles per wave, each wave its own slab -- shorter), then the reduce of the nsplit slabs: in slab order
+#       (wgrad_reduce_kernel) or four lanes of stride 4 combined as (l0 + l1) + (l2 + l3) (wgrad_reduce_batched_kernel), at most
+#       nsplit + 1 roundings; plus the product's own: wgrad_chain_fp32.
+#   statistics: per-thread fp32 sums of at most 16 stored values, shuffles, f64 across waves: REL_SUMS, as for the bf16 kernels.
+U32 = 2.0 ** -24
+LAMBDA_FP32 = 8.0
+
+
+def gamma_fp32(chain):
+    """elementwise bound |got - ref| <= gamma * A of an fp32-family result whose longest rounding chain is `chain` (see above)"""
+    return LAMBDA_FP32 * math.sqrt(chain) * U32
+
+
+def conv_chain_fp32(c, ntaps):
+    """the chain of conv_mfma_kernel with c input channels (of the launch) and ntaps taps per output"""
+    return 16 * (-(-c // 16)) * ntaps + 4
+
+
+def wgrad_chain_fp32(tiles_per_split, tile_voxels, nsplit):
+    """the chain of wgrad_mfma_kernel + either reduce: tiles_per_split tiles of tile_voxels voxels per slab, nsplit slabs"""
+    return tiles_per_split * tile_voxels + nsplit + 2
 
 
 # ------------------------------------------------------------------ operand rounding

@@ -47,20 +47,30 @@ def _packed(spec, w, prec="fp32"):
 PREC_TOL = {"fp32": 2e-5, "bf16x3": 2e-4, "bf16": 3e-2}
 
 
-def exact(got, ref, prec, what, gamma=R.GAMMA_CONV):
-    """beside the fp32-oracle check of a bf16-mode result: the operand-exact bound |got - ref| <= gamma * A of tests/bf16_operand_ref.py"""
-    if prec != "fp32":
-        R.check(got, ref, gamma, what)
+NTAPS = {pk.CONV3_S1: 27, pk.CONV3_S2: 27, pk.CONV1: 1, pk.CONVT2: 1, pk.CONV3_S2_DGRAD: 8, pk.CONVT2_DGRAD: 8}
 
 
-def exact_wgrad(gw, gb, op, x, dy, prec, in_scale, in_shift, slope, size, what):
-    """the weight / bias gradient of hip.wgrad / wgrad_to against the operand-exact reference (operand form of the kernel that ran)"""
+def exact(got, ref, prec, what, gamma=R.GAMMA_CONV, chain=None):
+    """beside the fp32-oracle check: the operand-exact bound |got - ref| <= gamma * A of tests/bf16_operand_ref.py; an fp32-mode result
+    (conv_mfma_kernel) is held to gamma_fp32 of its chain = conv_chain_fp32(launch input channels, taps)"""
     if prec == "fp32":
-        return
+        gamma = R.gamma_fp32(R.conv_chain_fp32(*chain))
+    R.check(got, ref, gamma, what)
+
+
+def exact_wgrad(gw, gb, op, x, dy, prec, in_scale, in_shift, slope, size, what, hip=None):
+    """the weight / bias gradient of hip.wgrad / wgrad_to against the operand-exact reference (operand form of the kernel that ran; in
+    fp32 wgrad_mfma_kernel, held to gamma_fp32 of the chain of its plan)"""
     dw, db, aw, ab = R.wgrad_ref(op, x, dy, R.wgrad_operand_mode(op, x.shape[-1], dy.shape[-1], size, prec), in_scale, in_shift, slope)
-    R.assert_operand_exact(gw.reshape(dw.shape), dw, aw, R.GAMMA_WGRAD, what + " dW")
+    gamma = R.GAMMA_WGRAD
+    if prec == "fp32":
+        import ctypes
+        p = (ctypes.c_int64 * 6)()
+        assert hip.lib.cwf_debug_wgrad_fp32_plan(op, x.shape[0], *size, x.shape[-1], *dy.shape[1:4], dy.shape[-1], p) == 0
+        gamma = R.gamma_fp32(R.wgrad_chain_fp32(p[3], 64 if op == pk.CONV3_S2 else 256, p[2]))
+    R.assert_operand_exact(gw.reshape(dw.shape), dw, aw, gamma, what + " dW")
     if gb is not None:
-        R.assert_operand_exact(gb, db, ab, R.GAMMA_WGRAD, what + " db")
+        R.assert_operand_exact(gb, db, ab, gamma, what + " db")
 
 
 CONV_CASES = [
@@ -114,16 +124,15 @@ def test_conv_family_fwd_dgrad_wgrad(hip, op, cin, cout, size, n, prec):
     assert y.shape == y_ref.shape                       # (padding channels of a 2-channel head are allocated but not initialised)
     close(y[..., :cout], y_ref[..., :cout], rtol=tol, what="fwd")
     close(st, st_ref, rtol=max(1e-5, tol), what="stats")
-    if prec != "fp32":
-        ex = R.conv_ref(op, x, w, prec, bias=b, in_scale=in_scale, in_shift=in_shift, slope=0.01, residual=res, out_scale=out_scale)
-        exact(y[..., :cout], ex, prec, "fwd")
-        R.assert_stats(st, ex, R.GAMMA_CONV, "stats")
+    fch = (cin, NTAPS[op])
+    ex = R.conv_ref(op, x, w, prec, bias=b, in_scale=in_scale, in_shift=in_shift, slope=0.01, residual=res, out_scale=out_scale)
+    exact(y[..., :cout], ex, prec, "fwd", chain=fch)
+    R.assert_stats(st, ex, R.gamma_fp32(R.conv_chain_fp32(*fch)) if prec == "fp32" else R.GAMMA_CONV, "stats")
     # ---- plain forward (no prologue / epilogue extras)
     y2_ref = E.conv(op, x, None, None, cout, w_ref=w, out_channels_alloc=spec.cout_alloc)
     y2 = hip.conv(op, x.to(DEV), wf, None, cout, out_channels_alloc=spec.cout_alloc, prec=prec)
     close(y2[..., :cout], y2_ref[..., :cout], rtol=tol, what="fwd plain")
-    if prec != "fp32":
-        exact(y2[..., :cout], R.conv_ref(op, x, w, prec), prec, "fwd plain")
+    exact(y2[..., :cout], R.conv_ref(op, x, w, prec), prec, "fwd plain", chain=fch)
 
     # ---- data gradient
     dy = torch.zeros(n, do, ho, wo, spec.cout_alloc)
@@ -131,8 +140,7 @@ def test_conv_family_fwd_dgrad_wgrad(hip, op, cin, cout, size, n, prec):
     dx_ref = E.conv(pk.dgrad_op(op), dy, None, None, cin, out=torch.empty(n, d, h, w_, cin), w_ref=w, fwd_op=op)
     dx = hip.conv(pk.dgrad_op(op), dy.to(DEV), wd, None, cin, out=torch.empty((n, d, h, w_, cin), device=DEV), prec=prec)
     close(dx, dx_ref, rtol=tol, what="dgrad")
-    if prec != "fp32":
-        exact(dx, R.conv_ref(op, dy, w, prec, dgrad=True, out_size=size), prec, "dgrad")
+    exact(dx, R.conv_ref(op, dy, w, prec, dgrad=True, out_size=size), prec, "dgrad", chain=(spec.cout_alloc, NTAPS[pk.dgrad_op(op)]))
 
     # ---- weight / bias gradient with the recomputed prologue
     dyv = dy[..., :cout]
@@ -141,7 +149,7 @@ def test_conv_family_fwd_dgrad_wgrad(hip, op, cin, cout, size, n, prec):
     close(gw, gw_ref, rtol=max(5e-5, tol), what="wgrad")
     if gb is not None:
         close(gb, gb_ref, rtol=max(5e-5, tol), what="bgrad")
-    exact_wgrad(gw, gb, op, x, dyv, prec, in_scale, in_shift, 0.0, size, "wgrad")
+    exact_wgrad(gw, gb, op, x, dyv, prec, in_scale, in_shift, 0.0, size, "wgrad", hip=hip)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])

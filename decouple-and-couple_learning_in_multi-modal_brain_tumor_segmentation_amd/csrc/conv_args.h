@@ -1,5 +1,5 @@
 // Declarations shared by the split-bf16 conv kernels (conv_bf16.hip: tap-table kernel, conv16 / conv16s, pointwise streams;
-// conv_ws.hip: weight-stationary kernel for the 32/64/128-channel 3x3x3 layers).
+// conv_ws.hip: weight-stationary kernel for the 32/64/128-channel 3x3x3 layers; conv_wsp.hip: its wave-specialised split-bf16 forward).
 #pragma once
 #include "common.h"
 
@@ -59,6 +59,11 @@ static inline int cfg_extent(int op, int Di, int Hi, int Wi, int Do, int Ho, int
 
 // conv_ws.hip: launches the weight-stationary kernel when the layer is one it takes (returns 1, status in *rc); 0 = not eligible.
 int cwf_try_conv_ws(int op, int x3, ConvArgsB& a, hipStream_t st, int* rc);
+// conv_ws.hip: 1 while cwf_debug_ws_x3 sends split-bf16 launches to the weight-stationary kernel
+int cwf_ws_takes_x3();
+// conv_wsp.hip: the wave-specialised split-bf16 forward of the 32-256-channel 3x3x3 layers (same contract as cwf_try_conv_ws; cfg_mt /
+// cfg_wm: the tap-table configuration the launch would otherwise take, whose statistics partials it reproduces)
+int cwf_try_conv_wsp(int op, int x3, int cfg_mt, int cfg_wm, ConvArgsB& a, hipStream_t st, int* rc);
 
 // Host launchers behind the routers cwf_conv (conv_bf16.hip) and cwf_wgrad (wgrad_bf16.hip), which have checked the route.
 int conv_fp32_launch(const cwf_conv_args& d, hipStream_t st);        // conv_mfma.hip: the fp32 tap-table kernel

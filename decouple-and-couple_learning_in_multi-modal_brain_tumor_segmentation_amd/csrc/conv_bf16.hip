@@ -1284,7 +1284,7 @@ static void c16_tap_order(ConvGeom& g) {
 }
 
 // The split-bf16 launches that share ConvArgsB, in order of preference: conv16s on a bf16 input image (x16), the pointwise streams,
-// the weight-stationary kernel, conv16s, the tap-table kernel.
+// the weight-stationary kernels (conv_wsp, conv_ws), conv16s, the tap-table kernel.
 static int conv_bf16_impl(const cwf_conv_args& d, hipStream_t st) {
   const int op = d.op, x3 = d.precision == CWF_BF16X3, N = d.N, Cin = d.Cin, Cout = d.Cout, y_ldc = d.y_ldc;
   // a bf16 input image stands in for x: conv16s reads it through its LDS-DMA loaders (16-byte granules, two per voxel)
@@ -1323,8 +1323,9 @@ static int conv_bf16_impl(const cwf_conv_args& d, hipStream_t st) {
     if (d.y16) return CWF_E_BADARG;                      // the bf16 side output is the pointwise stream kernel's
   }
   {
-    int rcw = 0;                                           // 32 / 64 / 128-channel 3x3x3 layers: weight-stationary kernel (conv_ws.hip)
-    if (cwf_try_conv_ws(op, x3, a, st, &rcw)) return rcw;
+    int rcw = 0;                                           // 32 / 64 / 128-channel 3x3x3 layers: weight-stationary kernels
+    if (cwf_try_conv_wsp(op, x3, c.MT, c.WM, a, st, &rcw)) return rcw;   // split-bf16 forward, wave-specialised (conv_wsp.hip)
+    if (cwf_try_conv_ws(op, x3, a, st, &rcw)) return rcw;    // (conv_ws.hip)
   }
   if (op == CWF_CONV3_S1 && Cin <= 16 && Cout <= 16) c16_tap_order(a.g);
   if (op == CWF_CONV3_S1 && Cin <= 16 && Cout <= 16 && (int64_t)d.Do * d.Ho * d.Wo >= 32768) {

@@ -463,6 +463,7 @@ extern "C" int cwf_debug_ws_min_units(int v) { const int old = g_ws_min_units; g
 // 34) here.  cwf_debug_ws_x3(1) sends the split form here too (tests, experiments).
 static int g_ws_x3 = 0;
 extern "C" int cwf_debug_ws_x3(int v) { const int old = g_ws_x3; g_ws_x3 = v; return old; }
+int cwf_ws_takes_x3() { return g_ws_x3; }
 
 // Returns 1 and launches if the layer is one this kernel takes (3x3x3 stride 1, Cin a multiple of 16 and >= 32, Cout a multiple of 32,
 // extents multiples of the 4x4x16 tile, no per-channel output scale, enough tiles to occupy the chip); 0 = not eligible (the caller

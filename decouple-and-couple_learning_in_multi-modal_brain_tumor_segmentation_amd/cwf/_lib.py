@@ -100,6 +100,9 @@ SIGNATURES = {
     "cwf_hausdorff_workspace": [I, I, I, I, I],
     "cwf_hausdorff": [P, P, I, I, I, I, I, D, D, D, I, I, P, P, P, P, L, P],
     "cwf_prepare_batch": [P, I, I, I, I, P, L, P, L, P, L, P],
+    "cwf_window_gather": [P, P, P, I, I, P],
+    "cwf_window_blend": [P, P, P, P, I, I, I, P],
+    "cwf_window_finalize": [P, P, P, P, P],
     "cwf_normalize_nonzero": [P, L, P, P],
     "cwf_rng_advance": [P, P],
     "cwf_dropout_mask_rng": [P, L, F, F, P, U64, P],
@@ -167,6 +170,14 @@ class PrepSample(C.Structure):
     """struct cwf_prep_sample (include/cwf_hip.h)"""
     _fields_ = [("image", P), ("label", P), ("S0", I), ("S1", I), ("S2", I), ("o0", I), ("o1", I), ("o2", I), ("flip", I),
                 ("intensity", I), ("scale", F * 4), ("shift", F * 4)]
+
+
+WINDOW_MAX_STARTS = 128   # CWF_WINDOW_MAX_STARTS
+
+
+class WindowGrid(C.Structure):
+    """struct cwf_window_grid (include/cwf_hip.h)"""
+    _fields_ = [("B", I), ("S", I * 3), ("r", I * 3), ("n", I * 3), ("start", (I * WINDOW_MAX_STARTS) * 3)]
 
 
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES

@@ -1257,6 +1257,55 @@ class HipBackend:
                    int(bool(all_border)), hd.data_ptr(), hd95.data_ptr(), counts.data_ptr(), ws.data_ptr(), int(nbytes), self._stream())
         return hd, hd95, counts
 
+    # ------------------------------------------------------------------ N5 sliding-window inference over volumes of any size
+    @staticmethod
+    def window_grid(nb, shape, roi, starts):
+        """struct cwf_window_grid for nb samples of a volume `shape` (S0, S1, S2), windows `roi` (r0, r1, r2) at the per-axis `starts`
+        (three lists; window w = (i0 * n1 + i1) * n2 + i2).  The kernels check the grid; this only packs it."""
+        g = _lib.WindowGrid()
+        g.B = int(nb)
+        for a in range(3):
+            g.S[a], g.r[a], g.n[a] = int(shape[a]), int(roi[a]), len(starts[a])
+            if len(starts[a]) > _lib.WINDOW_MAX_STARTS:
+                raise ValueError("window grid: %d windows along axis %d, at most %d" % (len(starts[a]), a, _lib.WINDOW_MAX_STARTS))
+            for i, s in enumerate(starts[a]):
+                g.start[a][i] = int(s)
+        return g
+
+    def window_gather(self, x, grid, w0, count):
+        """x [B,4,S0,S1,S2] fp32 (made contiguous) -> windows w0 .. w0+count-1 of `grid` (window_grid), logical NCDHW
+        [count*B,4,r0,r1,r2] over channels-last memory (sample j*B + b = window w0+j of sample b), zeros outside the volume
+        (cwf_window_gather).  The model's permute(0,2,3,4,1).contiguous() of it copies nothing."""
+        x = x.contiguous()
+        assert x.dtype == _f32 and x.dim() == 5 and x.shape[1] == 4
+        r = tuple(grid.r)
+        win = torch.empty((int(count) * grid.B,) + r + (4,), dtype=_f32, device=x.device)
+        self._call("cwf_window_gather", x.data_ptr(), win.data_ptr(), ctypes.byref(grid), int(w0), int(count), self._stream())
+        return win.permute(0, 4, 1, 2, 3)
+
+    def window_blend(self, probs, weights, acc, grid, w0, count, accumulate):
+        """acc [B,S0,S1,S2,4] fp32 += the importance-weighted probabilities of windows w0 .. w0+count-1 (accumulate=False: the first
+        chunk, acc is overwritten).  probs: the model's [count*B,4,r0,r1,r2] output; a view that is not channels-last contiguous is
+        made one.  weights: the 1-D tables g0 | g1 | g2, fp32 [r0+r1+r2] on the device (cwf_window_blend)."""
+        p = probs.permute(0, 2, 3, 4, 1)
+        if not p.is_contiguous():
+            p = p.contiguous()
+        r = tuple(grid.r)
+        assert p.dtype == _f32 and tuple(p.shape) == (int(count) * grid.B,) + r + (4,), (tuple(probs.shape), r, count)
+        assert acc.is_contiguous() and tuple(acc.shape) == (grid.B,) + tuple(grid.S) + (4,)
+        assert weights.is_contiguous() and weights.dtype == _f32 and weights.numel() == sum(r)
+        self._call("cwf_window_blend", p.data_ptr(), weights.data_ptr(), acc.data_ptr(), ctypes.byref(grid), int(w0), int(count),
+                   int(bool(accumulate)), self._stream())
+        return acc
+
+    def window_finalize(self, acc, weights, grid):
+        """acc [B,S0,S1,S2,4] / per-voxel weight sum -> prob [B,4,S0,S1,S2] NCDHW (cwf_window_finalize)"""
+        assert acc.is_contiguous() and tuple(acc.shape) == (grid.B,) + tuple(grid.S) + (4,)
+        assert weights.is_contiguous() and weights.dtype == _f32 and weights.numel() == sum(grid.r)
+        y = torch.empty((grid.B, 4) + tuple(grid.S), dtype=_f32, device=acc.device)
+        self._call("cwf_window_finalize", acc.data_ptr(), weights.data_ptr(), y.data_ptr(), ctypes.byref(grid), self._stream())
+        return y
+
     # ------------------------------------------------------------------ N3 training-batch preparation
     def prepare_batch(self, images, labels, params, crop, out=None):
         """Training batch (x [B,4,C0,C1,C2] fp32, target [B,C0,C1,C2] int64, edge [B,C0,C1,C2] int64) from per-sample source volumes

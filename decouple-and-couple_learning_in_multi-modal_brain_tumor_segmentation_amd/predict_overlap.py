@@ -14,7 +14,16 @@ classes and the WT / TC / ET Dice of ``utils.tools.softmax_output_dice``; option
 mean over all subsets of the three spatial axes of ``softmax(model(flip(x))[0]).flip`` (the reference re-applies softmax to
 the model's already-normalised output; kept, ``resoftmax=True``).  The eight flipped copies are independent samples, so
 they run as batches instead of eight sequential B=1 forwards.
+
+``sliding_window_inference`` (N5): volumes of any size -- overlapping windows on the grid of ``window_grid``, each window's
+probabilities weighted by the separable ``importance_map`` (Gaussian or constant) and normalised by the per-voxel weight sum, in
+the manner of nnU-Net / MONAI (the grid and map rules are this project's own, stated below; no bit parity with either is claimed).
+Per chunk of windows: one gather launch, one model forward, one blend launch; one finalize launch at the end (csrc/window.hip).
 """
+import itertools
+import math
+
+import numpy as np
 import torch
 
 from utils import tools
@@ -67,36 +76,154 @@ def flip_tta(x, missing_modal, forward, resoftmax=True, batch=8):
     return acc / 8.0
 
 
+def window_grid(shape, roi_size, overlap):
+    """Per-axis window starts (three lists) for a volume of spatial `shape` and windows of `roi_size`; the windows are the Cartesian
+    product, ordered lexicographically with axis 0 slowest.  Along an axis of size S with window r: S <= r gives one window at 0 (the
+    volume is zero-padded to r); otherwise n = ceil((S - r) / (r (1 - overlap))) + 1 windows at round(i (S - r) / (n - 1)), the
+    first at 0 and the last at S - r.  overlap in [0, 1)."""
+    shape, roi = tuple(int(s) for s in shape), tuple(int(r) for r in roi_size)
+    if len(shape) != 3 or len(roi) != 3 or min(shape) <= 0 or min(roi) <= 0:
+        raise ValueError("window_grid: need three positive extents and three positive window sizes, got %r and %r" % (shape, roi))
+    if not 0.0 <= float(overlap) < 1.0:
+        raise ValueError("window_grid: overlap must lie in [0, 1), got %r" % (overlap,))
+    starts = []
+    for s, r in zip(shape, roi):
+        if s <= r:
+            starts.append([0])
+            continue
+        n = int(math.ceil((s - r) / (r * (1.0 - float(overlap))))) + 1
+        step = (s - r) / (n - 1)
+        starts.append([int(np.round(step * i)) for i in range(n)])
+    return tuple(starts)
+
+
+def importance_tables(roi_size, blend="gaussian", sigma_scale=0.125):
+    """The three fp32 1-D factors of the importance map: ones ("constant") or g_a(t) = exp(-(t - (r_a - 1) / 2)^2 / (2 sigma_a^2)),
+    sigma_a = sigma_scale * r_a, evaluated in float64 and rounded once to fp32 ("gaussian")."""
+    roi = tuple(int(r) for r in roi_size)
+    if len(roi) != 3 or min(roi) <= 0:
+        raise ValueError("importance map: need three positive window sizes, got %r" % (roi_size,))
+    if blend == "constant":
+        return tuple(np.ones(r, np.float32) for r in roi)
+    if blend != "gaussian":
+        raise ValueError("importance map: blend must be 'gaussian' or 'constant', got %r" % (blend,))
+    if not sigma_scale > 0:
+        raise ValueError("importance map: sigma_scale must be positive, got %r" % (sigma_scale,))
+    tabs = []
+    for r in roi:
+        t = np.arange(r, dtype=np.float64) - (r - 1) / 2.0
+        sig = float(sigma_scale) * r
+        tabs.append(np.exp(-t * t / (2.0 * sig * sig)).astype(np.float32))
+    if np.float32(np.float32(tabs[0].min() * tabs[1].min()) * tabs[2].min()) <= 0:   # the smallest weight (fp32 rounding is monotone)
+        raise ValueError("importance map: sigma_scale %r makes edge weights underflow to 0 in fp32" % (sigma_scale,))
+    return tuple(tabs)
+
+
+def importance_map(roi_size, blend="gaussian", sigma_scale=0.125):
+    """[r0, r1, r2] fp32 weights fp32(fp32(g0 * g1) * g2) of importance_tables -- what cwf_window_blend multiplies each window by."""
+    g0, g1, g2 = importance_tables(roi_size, blend, sigma_scale)
+    g01 = g0[:, None] * g1[None, :]                     # fp32 x fp32 -> fp32 (rounded once), as the kernel forms it
+    return g01[:, :, None] * g2[None, None, :]
+
+
+MIN_SEMANTIC_TOKENS = 128      # the model's top_num: (r0 / 16) (r1 / 16) (r2 / 8) tokens per window at least
+
+
+def check_roi(roi_size):
+    """Raise ValueError unless the model accepts windows of roi_size: sides multiples of 16 and >= 128 semantic tokens."""
+    roi = tuple(int(r) for r in roi_size)
+    if len(roi) != 3 or min(roi) <= 0 or any(r % 16 for r in roi):
+        raise ValueError("sliding window: roi_size must be three positive multiples of 16 (the model's down-sampling), got %r"
+                         % (tuple(roi_size),))
+    if (roi[0] // 16) * (roi[1] // 16) * (roi[2] // 8) < MIN_SEMANTIC_TOKENS:
+        raise ValueError("sliding window: roi_size %r yields %d semantic tokens, the model needs at least %d ((r0/16)(r1/16)(r2/8))"
+                         % (roi, (roi[0] // 16) * (roi[1] // 16) * (roi[2] // 8), MIN_SEMANTIC_TOKENS))
+    return roi
+
+
+_weights_cache = {}
+
+
+def _device_tables(roi, blend, sigma_scale, device):
+    key = (roi, blend, float(sigma_scale), str(device))
+    w = _weights_cache.get(key)
+    if w is None:
+        w = torch.from_numpy(np.concatenate(importance_tables(roi, blend, sigma_scale))).to(device)
+        _weights_cache[key] = w
+    return w
+
+
 @torch.no_grad()
-def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False, with_hd95=False):
+def sliding_window_inference(x, missing_modal, model, roi_size=(128, 128, 128), overlap=0.5, blend="gaussian", sigma_scale=0.125,
+                             sw_batch_size=8):
+    """x: CUDA fp32 [B,4,S0,S1,S2] of any extent; model(xb, missing_modal) -> (prob [n*B,4,r0,r1,r2], ...).  Returns the blended
+    probability volume [B,4,S0,S1,S2]: sum over covering windows of w(v - s) p / sum of w(v - s), with the windows of
+    window_grid(roi_size, overlap) (axes shorter than the window zero-padded) and w = importance_map(roi_size, blend, sigma_scale).
+    sw_batch_size windows (times B samples) go through the model per forward.  Results do not depend on sw_batch_size."""
+    roi = check_roi(roi_size)
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] == 4):
+        raise ValueError("sliding window: x must be a CUDA fp32 [B,4,S0,S1,S2] tensor, got %s %s"
+                         % (getattr(x, "dtype", type(x)), tuple(getattr(x, "shape", ()))))
+    if int(sw_batch_size) < 1:
+        raise ValueError("sliding window: sw_batch_size must be >= 1, got %r" % (sw_batch_size,))
+    from cwf.kernels import backend
+    be = backend()
+    nb, shape = int(x.shape[0]), tuple(int(s) for s in x.shape[2:])
+    starts = window_grid(shape, roi, overlap)
+    weights = _device_tables(roi, blend, sigma_scale, x.device)
+    grid = be.window_grid(nb, shape, roi, starts)
+    x = x.contiguous()
+    nw = len(starts[0]) * len(starts[1]) * len(starts[2])
+    acc = torch.empty((nb,) + shape + (4,), dtype=torch.float32, device=x.device)
+    for w0 in range(0, nw, int(sw_batch_size)):
+        cnt = min(int(sw_batch_size), nw - w0)
+        prob = model(be.window_gather(x, grid, w0, cnt), missing_modal)[0]
+        be.window_blend(prob, weights, acc, grid, w0, cnt, accumulate=w0 > 0)
+    return be.window_finalize(acc, weights, grid)
+
+
+def windows(starts):
+    """The window start triples of a window_grid result, in window order."""
+    return list(itertools.product(*starts))
+
+
+@torch.no_grad()
+def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False, with_hd95=False, window=None):
     """One subject: stitched probabilities -> label map (argmax; class 3 stands for BraTS label 4) -> [WT, TC, ET] Dice.
     ``deterministic`` zeroes the stem dropout that the reference leaves on in eval mode.  ``with_miou`` adds the per-class
     IoU list of tools.softmax_mIOU_score (what predict_simple.py reports next to Dice) as a fourth result.  ``with_hd95`` appends the
     BraTS surface HD95: a [B, 3] float64 tensor of per-sample WT / TC / ET HD95 between ``seg`` and the target, on 3-D surfaces (unit
     spacing, connectivity 1), 0 where either region is empty or full (the rule of utils.hausdorff.hausdorff_distance_95), computed on
     the device (cwf_hausdorff); None without a target.  Result order: (seg, prob, dice[, miou][, hd95]).  predict_simple.py's own numbers
-    come from utils.hausdorff on [1, ...] arrays, where every mask voxel counts as a border voxel."""
+    come from utils.hausdorff on [1, ...] arrays, where every mask voxel counts as a border voxel.
+    ``window``: None -- the reference's eight-window stitcher on a [B,4,240,240,>=155] volume, the target cut to depth 155; a dict of
+    sliding_window_inference keyword arguments (roi_size, overlap, blend, sigma_scale, sw_batch_size) -- blended windows over a volume
+    of any size, the target compared at the volume's own shape."""
     model.eval()
     saved = model.Unet_list.InitConv.dropout
     if deterministic:
         model.Unet_list.InitConv.dropout = 0.0
+    if window is None:
+        predict, cut = (lambda xb, mm: tailor_and_concat(xb, mm, model)), 155
+    else:
+        predict, cut = (lambda xb, mm: sliding_window_inference(xb, mm, model, **window)), None
     try:
-        if use_TTA:         # each flipped volume goes through the 8-window stitcher (one batch-8 forward per flip)
-            prob = flip_tta(x, None, lambda xb, mm: tailor_and_concat(xb, mm, model), batch=1)
+        if use_TTA:         # each flipped volume goes through the predictor (the 8-window stitcher: one batch-8 forward per flip)
+            prob = flip_tta(x, None, predict, batch=1)
         else:
-            prob = tailor_and_concat(x, None, model)
+            prob = predict(x, None)
     finally:
         model.Unet_list.InitConv.dropout = saved
-    res = _validate(prob, target, with_miou)
+    res = _validate(prob, target, with_miou, cut)
     if with_hd95:
-        res = res + ((None if target is None else hd95_regions(res[0], target[..., :155].long())),)
+        res = res + ((None if target is None else hd95_regions(res[0], target[..., :cut].long())),)
     return res
 
 
-def _validate(prob, target, with_miou):
+def _validate(prob, target, with_miou, cut=155):
     if prob.is_cuda and prob.dtype == torch.float32 and prob.dim() == 5 and prob.shape[1] == 4:
         from cwf.kernels import backend                     # argmax + WT/TC/ET counts in one launch (cwf_argmax_dice)
-        tgt = None if target is None else target[..., :155].long()
+        tgt = None if target is None else target[..., :cut].long()
         if with_miou and tgt is not None:
             seg, d, iou = backend().argmax_dice(prob, tgt, miou=True)          # argmax + Dice + IoU counts, still one launch
             return seg, prob, [d[0], d[1], d[2]], [iou[0], iou[1], iou[2]]
@@ -104,9 +231,9 @@ def _validate(prob, target, with_miou):
         res = (seg, prob, (None if d is None else [d[0], d[1], d[2]]))
         return res + (None,) if with_miou else res
     seg = prob.argmax(1)
-    dice = tools.softmax_output_dice(seg, target[..., :155]) if target is not None else None
+    dice = tools.softmax_output_dice(seg, target[..., :cut]) if target is not None else None
     if with_miou:
-        return seg, prob, dice, (tools.softmax_mIOU_score(seg, target[..., :155]) if target is not None else None)
+        return seg, prob, dice, (tools.softmax_mIOU_score(seg, target[..., :cut]) if target is not None else None)
     return seg, prob, dice
 
 

@@ -429,6 +429,38 @@ int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int 
                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * N5  sliding-window inference over volumes of any size (predict_overlap.sliding_window_inference): overlapping r0 x r1 x r2
+ *     windows on a Cartesian grid of starts, blended with a separable importance map.
+ * ---------------------------------------------------------------------------------------------- */
+#define CWF_WINDOW_MAX_STARTS 128
+/* The window grid (host memory, passed by pointer, copied into the launch).  Window w = (i0 * n1 + i1) * n2 + i2 (axis 0 slowest)
+ * covers voxels [start[a][i_a], start[a][i_a] + r[a]) of a [B][4][S0][S1][S2] volume along each axis a; every window must overlap
+ * the volume (-r[a] < start < S[a]); voxels of a window outside the volume are zero padding.                                       */
+struct cwf_window_grid {
+  int B;
+  int S[3];
+  int r[3];
+  int n[3];                                   /* 1 .. CWF_WINDOW_MAX_STARTS windows per axis */
+  int start[3][CWF_WINDOW_MAX_STARTS];
+};
+/* windows[(j*B + b)][r0][r1][r2][4] (channels-last, 16-B aligned) <- x[b][4][S0][S1][S2] (contiguous NCDHW) cut at window w0 + j,
+ * j < count, zeros outside the volume.  Viewed as NCDHW [count*B, 4, r0, r1, r2] it is the model's input with channels-last memory. */
+int cwf_window_gather(const float* x, float* windows, const struct cwf_window_grid* grid, int w0, int count, void* stream);
+/* acc[b][S0][S1][S2][4] (16-B aligned) += wt(v - s_w) * probs[(j*B + b)][v - s_w][4] for the windows w = w0 + j (j < count) that cover
+ * voxel v, in window order, added one after another into the value loaded (accumulate = 0: into 0; the first chunk's launch then
+ * also clears the voxels none of its windows covers).  probs: the model's output for the chunk in channels-last memory (16-B aligned).
+ * weights: the 1-D importance tables g0[r0], g1[r1], g2[r2] back to back; wt(l) = fp32(fp32(g0[l0] * g1[l1]) * g2[l2]).
+ * No atomics: the per-voxel sequence of fp32 operations does not depend on how the windows are split into chunks.                  */
+int cwf_window_blend(const float* probs, const float* weights, float* acc, const struct cwf_window_grid* grid, int w0, int count,
+                     int accumulate, void* stream);
+/* y[b][c][S0][S1][S2] (NCDHW) = acc[b][v][c] / (sum of wt over all windows covering v, in window order); 0 / 0 = NaN where no
+ * window covers v.                                                                                                                  */
+int cwf_window_finalize(const float* acc, const float* weights, float* y, const struct cwf_window_grid* grid, void* stream);
+/* CWF_E_BADARG (all three): a null pointer, a misaligned windows / probs / acc (16 B) or x / weights / y (4 B), B, S, r or n out of
+ * range, a window entirely outside the volume, count <= 0 or windows past the last; CWF_E_TOOLARGE: 2^31 voxels or more in the
+ * volume or a window, count * B > 65535.                                                                                             */
+
+/* ------------------------------------------------------------------------------------------------
  * N3  training-batch preparation (utils/data.py prepare_batch / DeviceBraTS: crop, flips, intensity, label remap, edge codes)
  * ---------------------------------------------------------------------------------------------- */
 /* One source subject: image fp32 [4][S0][S1][S2] and label uint8 [S0][S1][S2] (values 0..4), both contiguous device memory; crop

@@ -72,6 +72,8 @@ REL_SUMS = 1e-6                 # statistics / norm-backward sums, relative to t
 #       (wgrad_reduce_kernel) or four lanes of stride 4 combined as (l0 + l1) + (l2 + l3) (wgrad_reduce_batched_kernel), at most
 #       nsplit + 1 roundings; plus the product's own: wgrad_chain_fp32.
 #   statistics: per-thread fp32 sums of at most 16 stored values, shuffles, f64 across waves: REL_SUMS, as for the bf16 kernels.
+#       (This describes the sums fused into the conv epilogues only.  in_reduce_kernel of csrc/norm.hip adds up to 256 values per
+#       thread at 1024 channels; it is held to norm_ref.sum_rel(L) with L read from its launch rule, not to REL_SUMS.)
 U32 = 2.0 ** -24
 LAMBDA_FP32 = 8.0
 

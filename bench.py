@@ -5,10 +5,15 @@ volumes (BASELINE.json configs[1]; for N > 1 the same per-rank batch = weak scal
 cwf.trainer.Trainer's RCCL all-reduce of the flat gradient buffer, see its docstring for what overlaps with backward).
 Inputs are resident in HBM before the timed region.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5            (the headline figure and nothing else)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full     (plus every leg listed below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints ONE JSON line (rank 0) with the contract
+fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and what the timed region itself yields (final_loss,
+host_ms_per_step_in_timed_region, end_to_end, config).  Every other measurement takes runs of its own and waits behind --full, which
+leaves the timed region and the dumped arrays untouched (the legs run after both) and adds to the line
+  host_enqueue_ms_per_step -- median host time of issuing one step with the GPU idle, over 5 further steps
   roofline     -- the dominant kernel (3x3x3 conv 16->16 @128^3 x2, conv16s_kernel in the bf16 modes): ALGORITHMIC bytes per launch
                   (x read once + y written once, fp32) / average launch duration measured here with HIP events on the launch stream,
                   against the 8 TB/s HBM peak (fp32 mode: algorithmic FLOPs against the dense fp32 MFMA peak); `traffic` = HBM bytes
@@ -227,14 +232,18 @@ def write_outputs(outputs, path):
     log("dumped %d arrays (%.1f MB) to %s" % (len(outputs), sum(a.nbytes for a in outputs.values()) / 2 ** 20, path))
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="timed steps (100 x 23 ms: a timed region long enough for 1 Hz GPU-busy samplers)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=2, help="rank-local batch (independent B=1 samples, SURVEY F2)")
     ap.add_argument("--size", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and --dump-outputs), also run the legs that take runs of their own: the unthrottled host "
+                         "enqueue time, the dominant kernel's roofline, the CPU baseline and val_dice / max_rel_logit_err against the CPU "
+                         "oracle; off by default, so a plain run does only what its headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and the val_dice leg")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--mode", default="plan", choices=["plan", "eager", "hipgraph"],
                     help="plan: the step is captured once and re-issued by the library as a launch list (csrc/plan.hip: one plain launch per "
@@ -251,6 +260,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (loss, loss terms, updated parameters, applied "
                          "gradients; float32, a fixed sample of each tensor above %d elements) as DIR/<name>.npy" % DUMP_CAP)
+    return ap
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -322,16 +336,18 @@ def main():
     final_loss = float(loss)
     if args.dump_outputs and rank == 0:
         write_outputs(snapshot_outputs(trainer, loss, parts), args.dump_outputs)
-    # host cost of issuing one step, UNTHROTTLED: with the GPU idle at the start the launch queue never fills, so this is what the
-    # host spends (the figure above saturates at the GPU's step time once the host runs ahead and blocks on a full queue)
-    host_ms = []
-    for _ in range(5):
+    host_ms = None
+    if args.full:
+        # host cost of issuing one step, UNTHROTTLED: with the GPU idle at the start the launch queue never fills, so this is what the
+        # host spends (the figure above saturates at the GPU's step time once the host runs ahead and blocks on a full queue)
+        host_ms = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            trainer.step(x, target, edge, epoch=0)
+            host_ms.append((time.perf_counter() - t1) * 1e3)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        trainer.step(x, target, edge, epoch=0)
-        host_ms.append((time.perf_counter() - t1) * 1e3)
-    torch.cuda.synchronize()
-    host_ms = sorted(host_ms)[len(host_ms) // 2]
+        host_ms = sorted(host_ms)[len(host_ms) // 2]
     log("rank %d: timed %d steps in %.3f s" % (rank, args.steps, dt))
 
     if rank == 0:
@@ -352,17 +368,19 @@ def main():
                        "global_batch": world * args.batch, "parallelism": "dp%d" % world, "precision": args.precision, "dgrad_precision": args.dgrad_precision,
                        "wgrad_precision": args.wgrad_precision, "mode": ("hipgraph" if args.graph else args.mode) if trainer._graph is not None or args.mode == "eager" else "eager (not captured)",
                        "plan": trainer.plan_info},
-            "final_loss": round(final_loss, 5), "host_enqueue_ms_per_step": round(host_ms, 2), "host_ms_per_step_in_timed_region": round(host_dt / args.steps * 1e3, 2),
+            "final_loss": round(final_loss, 5), "full": bool(args.full), "host_ms_per_step_in_timed_region": round(host_dt / args.steps * 1e3, 2),
             "end_to_end": {"tflops": round(value * FLOP_PER_TRAIN_VOLUME * (args.size / 128.0) ** 3 / 1e12, 2),
                            "frac_mfma_peak_for_mode": round(value * FLOP_PER_TRAIN_VOLUME * (args.size / 128.0) ** 3 / 1e12 / world / MFMA_PEAK_TFLOPS[args.precision], 4)},
         }
-        out["roofline"] = dominant_kernel_roofline(dev, args.precision)
-        log("roofline leg done: %s" % json.dumps(out["roofline"]))
         if forced:
             out["comm_forced"] = True                    # one-rank RCCL group: the collective path ran (CWF_FORCE_COMM=1)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"], extra = cpu_baseline(args.cpu_steps, dev, args.precision)
-            out.update(extra)
+        if args.full:
+            out["host_enqueue_ms_per_step"] = round(host_ms, 2)
+            out["roofline"] = dominant_kernel_roofline(dev, args.precision)
+            log("roofline leg done: %s" % json.dumps(out["roofline"]))
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"], extra = cpu_baseline(args.cpu_steps, dev, args.precision)
+                out.update(extra)
         print(json.dumps(out))
     if use_dist:
         dist.barrier()

@@ -99,6 +99,10 @@ SIGNATURES = {
     "cwf_region_bits": [P, P, L, P],
     "cwf_hausdorff_workspace": [I, I, I, I, I],
     "cwf_hausdorff": [P, P, I, I, I, I, I, D, D, D, I, I, P, P, P, P, L, P],
+    "cwf_components_workspace": [I, I, I, I, I],
+    "cwf_components": [P, I, I, I, I, I, I, P, P, P, P, P, L, P],
+    "cwf_postprocess_labels": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
+    "cwf_label_metrics": [P, P, P, L, P],
     "cwf_prepare_batch": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_window_gather": [P, P, P, I, I, P],
     "cwf_window_blend": [P, P, P, P, I, I, I, P],
@@ -181,7 +185,7 @@ class WindowGrid(C.Structure):
 
 
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
-RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace"}
+RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace"}
 
 _lib = None
 

@@ -1257,6 +1257,75 @@ class HipBackend:
                    int(bool(all_border)), hd.data_ptr(), hd95.data_ptr(), counts.data_ptr(), ws.data_ptr(), int(nbytes), self._stream())
         return hd, hd95, counts
 
+    # ------------------------------------------------------------------ N6 connected components and label-map post-processing
+    def components(self, bits, R, connectivity=1):
+        """Connected components of every region of bits ([B, D0, D1, D2] uint8 region bits or bool, bit r = region r < R <= 8) under the
+        6/18/26-neighbour footprint (connectivity 1/2/3), numbered as scipy.ndimage.label numbers them (cwf_components):
+        -> (labels [B, R, D0, D1, D2] int32, sizes [B, R, cap] int32 with cap = (V + 1) // 2 and zeros beyond the last component,
+        count [B, R] int32, largest [B, R, 2] int32 = (label, size), ties to the lowest label).  No host synchronisation: the workspace
+        comes from torch's allocator on the current stream."""
+        if torch.is_tensor(bits) and bits.dtype == torch.bool:
+            bits = bits.view(torch.uint8)
+        if not torch.is_tensor(bits) or bits.dim() != 4 or bits.dtype != torch.uint8 or not bits.is_cuda or bits.numel() == 0:
+            raise ValueError("components: bits must be a non-empty CUDA uint8 / bool tensor of shape [B, D0, D1, D2]")
+        if not 1 <= int(R) <= 8:
+            raise ValueError("components: R must lie in 1..8, got %r" % (R,))
+        if int(connectivity) not in (1, 2, 3):
+            raise ValueError("components: connectivity must be 1, 2 or 3, got %r" % (connectivity,))
+        bits = bits.contiguous()
+        nb, d0, d1, d2 = (int(s) for s in bits.shape)
+        R, dev = int(R), bits.device
+        nbytes = self.lib.cwf_components_workspace(nb, R, d0, d1, d2)
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_components_workspace failed with status %d (B=%d R=%d %dx%dx%d)" % (nbytes, nb, R, d0, d1, d2))
+        cap = (d0 * d1 * d2 + 1) // 2
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        labels = torch.empty((nb, R, d0, d1, d2), dtype=torch.int32, device=dev)
+        sizes = torch.empty((nb, R, cap), dtype=torch.int32, device=dev)
+        count = torch.empty((nb, R), dtype=torch.int32, device=dev)
+        largest = torch.empty((nb, R, 2), dtype=torch.int32, device=dev)
+        self._call("cwf_components", bits.data_ptr(), nb, R, d0, d1, d2, int(connectivity), labels.data_ptr(), sizes.data_ptr(),
+                   count.data_ptr(), largest.data_ptr(), ws.data_ptr(), int(nbytes), self._stream())
+        return labels, sizes, count, largest
+
+    def postprocess_labels(self, seg, labels, sizes, largest, wt_region=0, et_region=2, min_component=0, keep_largest=False,
+                           et_min_component=0, et_min_voxels=0, et_replace=1):
+        """The post-processing policy of predict_overlap.postprocess on a CUDA int64 label map seg [B, D0, D1, D2] (classes 0..3), from
+        the `components` results of its region bits (cwf_postprocess_labels): -> (processed map, stats [B, 4] int64 = WT voxels removed,
+        WT components removed, ET voxels relabelled, ET voxels remaining).  No host synchronisation."""
+        if not torch.is_tensor(seg) or seg.dim() != 4 or seg.dtype != torch.int64 or not seg.is_cuda or seg.numel() == 0:
+            raise ValueError("postprocess_labels: seg must be a non-empty CUDA int64 tensor of shape [B, D0, D1, D2]")
+        nb, d0, d1, d2 = (int(s) for s in seg.shape)
+        if labels.dim() != 5 or labels.dtype != torch.int32 or labels.shape[0] != nb or tuple(labels.shape[2:]) != (d0, d1, d2):
+            raise ValueError("postprocess_labels: labels must be the int32 [B, R, D0, D1, D2] result of components for this map")
+        R, cap = int(labels.shape[1]), (d0 * d1 * d2 + 1) // 2
+        if tuple(sizes.shape) != (nb, R, cap) or sizes.dtype != torch.int32 or tuple(largest.shape) != (nb, R, 2) or largest.dtype != torch.int32:
+            raise ValueError("postprocess_labels: sizes / largest must be the int32 [B, R, cap] / [B, R, 2] results of components")
+        if not (0 <= int(wt_region) < R and 0 <= int(et_region) < R):
+            raise ValueError("postprocess_labels: region indices must lie in [0, %d), got %r and %r" % (R, wt_region, et_region))
+        if min(int(min_component), int(et_min_component), int(et_min_voxels)) < 0:
+            raise ValueError("postprocess_labels: thresholds must be >= 0")
+        if int(et_replace) not in (0, 1, 2):
+            raise ValueError("postprocess_labels: et_replace must be 0, 1 or 2, got %r" % (et_replace,))
+        seg, labels, sizes, largest = seg.contiguous(), labels.contiguous(), sizes.contiguous(), largest.contiguous()
+        out = torch.empty_like(seg)
+        stats = torch.empty((nb, 4), dtype=torch.int64, device=seg.device)
+        ws = torch.empty((nb, 4), dtype=torch.int64, device=seg.device)          # CWF_POSTPROCESS_WS_BYTES
+        self._call("cwf_postprocess_labels", seg.data_ptr(), out.data_ptr(), labels.data_ptr(), sizes.data_ptr(), largest.data_ptr(), nb, R,
+                   d0, d1, d2, int(wt_region), int(et_region), int(min_component), int(bool(keep_largest)), int(et_min_component),
+                   int(et_min_voxels), int(et_replace), stats.data_ptr(), ws.data_ptr(), self._stream())
+        return out, stats
+
+    def label_metrics(self, seg, target):
+        """(dice [3], iou [3]) float64 device tensors of two int64 label maps of one shape: WT / TC / ET Dice of tools.softmax_output_dice
+        and class 1 / 2 / 3 IoU of tools.softmax_mIOU_score, by the formulas of argmax_dice (cwf_label_metrics)."""
+        seg, target = seg.contiguous(), target.contiguous()
+        assert seg.dtype == torch.int64 and target.dtype == torch.int64 and seg.is_cuda and tuple(seg.shape) == tuple(target.shape)
+        counts = torch.zeros((6, 3), dtype=torch.int64, device=seg.device)
+        self._call("cwf_label_metrics", seg.data_ptr(), target.data_ptr(), counts.data_ptr(), seg.numel(), self._stream())
+        c = counts.double()
+        return (2 * c[:3, 0] + 1e-8) / (c[:3, 1] + c[:3, 2] + 1e-8), (c[3:, 0] + 1e-8) / (c[3:, 1] + c[3:, 2] - c[3:, 0] + 1e-8)
+
     # ------------------------------------------------------------------ N5 sliding-window inference over volumes of any size
     @staticmethod
     def window_grid(nb, shape, roi, starts):

@@ -19,6 +19,11 @@ they run as batches instead of eight sequential B=1 forwards.
 probabilities weighted by the separable ``importance_map`` (Gaussian or constant) and normalised by the per-voxel weight sum, in
 the manner of nnU-Net / MONAI (the grid and map rules are this project's own, stated below; no bit parity with either is claimed).
 Per chunk of windows: one gather launch, one model forward, one blend launch; one finalize launch at the end (csrc/window.hip).
+
+``postprocess`` (N6): connected-component post-processing of a predicted label map -- small whole-tumour components removed, only the
+largest kept, small enhancing-tumour components and a tiny enhancing-tumour total relabelled (the ``postprocess=True`` switch of the
+reference's predictors, whose 500-voxel rule is the preset ``REFERENCE_POSTPROCESS``).  On the device: region bits -> component labelling
+-> policy (csrc/components.hip), no host synchronisation; CPU tensors go through numpy and scipy.ndimage.label.
 """
 import itertools
 import math
@@ -188,7 +193,8 @@ def windows(starts):
 
 
 @torch.no_grad()
-def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False, with_hd95=False, window=None):
+def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False, with_hd95=False, window=None,
+                     postprocess=None):
     """One subject: stitched probabilities -> label map (argmax; class 3 stands for BraTS label 4) -> [WT, TC, ET] Dice.
     ``deterministic`` zeroes the stem dropout that the reference leaves on in eval mode.  ``with_miou`` adds the per-class
     IoU list of tools.softmax_mIOU_score (what predict_simple.py reports next to Dice) as a fourth result.  ``with_hd95`` appends the
@@ -198,7 +204,9 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
     come from utils.hausdorff on [1, ...] arrays, where every mask voxel counts as a border voxel.
     ``window``: None -- the reference's eight-window stitcher on a [B,4,240,240,>=155] volume, the target cut to depth 155; a dict of
     sliding_window_inference keyword arguments (roi_size, overlap, blend, sigma_scale, sw_batch_size) -- blended windows over a volume
-    of any size, the target compared at the volume's own shape."""
+    of any size, the target compared at the volume's own shape.
+    ``postprocess``: None -- the label map is the plain argmax; a dict of `postprocess` keyword arguments (REFERENCE_POSTPROCESS is
+    one) -- ``seg`` is the processed map and Dice, IoU and HD95 are all computed from it (Dice as tools.softmax_output_dice gives it)."""
     model.eval()
     saved = model.Unet_list.InitConv.dropout
     if deterministic:
@@ -215,6 +223,8 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
     finally:
         model.Unet_list.InitConv.dropout = saved
     res = _validate(prob, target, with_miou, cut)
+    if postprocess is not None:
+        res = _revalidate(_apply_postprocess(res[0], postprocess), prob, target, with_miou, cut)
     if with_hd95:
         res = res + ((None if target is None else hd95_regions(res[0], target[..., :cut].long())),)
     return res
@@ -237,6 +247,24 @@ def _validate(prob, target, with_miou, cut=155):
     return seg, prob, dice
 
 
+def _apply_postprocess(seg, policy):          # validate_softmax's keyword hides the function's name there
+    return postprocess(seg, **policy)
+
+
+def _revalidate(seg, prob, target, with_miou, cut):
+    """The result tuple of _validate for a label map that is already there (the post-processed one)."""
+    dice = miou = None
+    if target is not None:
+        tgt = target[..., :cut].long()
+        if seg.is_cuda:
+            from cwf.kernels import backend
+            d, iou = backend().label_metrics(seg, tgt.to(seg.device))
+            dice, miou = [d[0], d[1], d[2]], [iou[0], iou[1], iou[2]]
+        else:
+            dice, miou = tools.softmax_output_dice(seg, tgt), tools.softmax_mIOU_score(seg, tgt)
+    return (seg, prob, dice, miou) if with_miou else (seg, prob, dice)
+
+
 def hd95_regions(seg, target):
     """[B, 3] float64 WT / TC / ET surface HD95 of two [B, D0, D1, D2] int64 label maps on the device, 0 where either region is empty
     or full (utils.hausdorff's rule).  No host synchronisation."""
@@ -247,3 +275,77 @@ def hd95_regions(seg, target):
     nvox = seg[0].numel()
     degenerate = (counts[..., 0] == 0) | (counts[..., 1] == 0) | (counts[..., 0] == nvox) | (counts[..., 1] == nvox)
     return hd95.masked_fill(degenerate, 0.0)
+
+
+REFERENCE_POSTPROCESS = dict(et_min_voxels=500, et_replace=1)        # the 500-voxel enhancing-tumour rule of the reference's lineage
+
+
+def postprocess(seg, min_component=0, keep_largest=False, et_min_component=0, et_min_voxels=0, et_replace=1, connectivity=1,
+                with_stats=False):
+    """Connected-component post-processing of [B, D0, D1, D2] int64 label maps (classes 0..3; WT = seg > 0, ET = seg == 3), components
+    under the 6/18/26-neighbour footprint (connectivity 1/2/3).  Applied in this order, each rule off at 0 / False:
+      1  every WT component of fewer than min_component voxels is set to 0
+      2  keep_largest: only the largest WT component surviving rule 1 is kept (ties: the one met first in C order), the rest set to 0
+      3  every ET component of fewer than et_min_component voxels is relabelled et_replace (0, 1 or 2)
+      4  if fewer than et_min_voxels ET voxels remain after rules 1-3, all of them are relabelled et_replace
+    Returns the processed map (a new tensor), with_stats: and a [B, 4] int64 tensor of WT voxels removed, WT components removed, ET
+    voxels relabelled, ET voxels remaining.  CUDA tensors run region_bits -> components -> postprocess_labels on the device without a
+    host synchronisation; CPU tensors run numpy + scipy.ndimage.label."""
+    if not torch.is_tensor(seg) or seg.dim() != 4 or seg.dtype != torch.int64:
+        raise ValueError("postprocess: seg must be an int64 tensor of shape [B, D0, D1, D2], got %s %s"
+                         % (getattr(seg, "dtype", type(seg)), tuple(getattr(seg, "shape", ()))))
+    if seg.numel() == 0:
+        raise ValueError("postprocess: seg is empty, shape %r" % (tuple(seg.shape),))
+    thresholds = (int(min_component), int(et_min_component), int(et_min_voxels))
+    if min(thresholds) < 0:
+        raise ValueError("postprocess: min_component, et_min_component and et_min_voxels must be >= 0, got %r" % (thresholds,))
+    if et_replace not in (0, 1, 2):
+        raise ValueError("postprocess: et_replace must be 0, 1 or 2, got %r" % (et_replace,))
+    if connectivity not in (1, 2, 3):
+        raise ValueError("postprocess: connectivity must be 1, 2 or 3, got %r" % (connectivity,))
+    if seg.is_cuda:
+        from cwf.kernels import backend
+        be = backend()
+        labels, sizes, _, largest = be.components(be.region_bits(seg), 3, connectivity)
+        out, stats = be.postprocess_labels(seg, labels, sizes, largest, 0, 2, thresholds[0], keep_largest, thresholds[1], thresholds[2],
+                                           int(et_replace))
+    else:
+        out, stats = _postprocess_host(seg.numpy(), thresholds[0], bool(keep_largest), thresholds[1], thresholds[2], int(et_replace),
+                                       int(connectivity))
+        out, stats = torch.from_numpy(out), torch.from_numpy(stats)
+    return (out, stats) if with_stats else out
+
+
+def _postprocess_host(seg, min_component, keep_largest, et_min_component, et_min_voxels, et_replace, connectivity):
+    from scipy import ndimage                                   # only the CPU path needs scipy
+    footprint = ndimage.generate_binary_structure(3, connectivity)
+    out = seg.copy()
+    stats = np.zeros((seg.shape[0], 4), dtype=np.int64)
+    for b in range(seg.shape[0]):
+        s = out[b]
+        if min_component > 0 or keep_largest:
+            lab, k = ndimage.label(s > 0, structure=footprint)
+            size = np.bincount(lab.ravel(), minlength=k + 1)
+            drop = np.zeros(k + 1, dtype=bool)
+            if min_component > 0:
+                drop[1:] = size[1:] < min_component
+            if keep_largest and k:
+                drop[1:] |= np.arange(1, k + 1) != 1 + int(np.argmax(size[1:]))      # argmax: the first of equal sizes
+            gone = drop[lab]
+            stats[b, 0], stats[b, 1] = int(gone.sum()), int(drop[1:].sum())
+            s[gone] = 0
+        if et_min_component > 0:
+            lab, k = ndimage.label(s == 3, structure=footprint)
+            size = np.bincount(lab.ravel(), minlength=k + 1)
+            small = np.zeros(k + 1, dtype=bool)
+            small[1:] = size[1:] < et_min_component
+            hit = small[lab]
+            stats[b, 2] = int(hit.sum())
+            s[hit] = et_replace
+        left = int((s == 3).sum())
+        if et_min_voxels > 0 and left < et_min_voxels:
+            s[s == 3] = et_replace
+            stats[b, 2] += left
+            left = 0
+        stats[b, 3] = left
+    return out, stats

@@ -429,6 +429,41 @@ int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int 
                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * N6  connected-component post-processing of predicted label maps (predict_overlap.postprocess): 3-D connected-component labelling
+ *     of region-bit masks by block-based union-find, and the removal / relabelling policy on top of it.  All integer, exact.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of device workspace cwf_components needs (256-B aligned; about 4 bytes per voxel, sample and region), or a negative
+ * CWF_E_*: CWF_E_BADARG for B, R or an extent <= 0 or R > 8, CWF_E_TOOLARGE for 2^31 voxels or more or B * R > 65535. */
+int64_t cwf_components_workspace(int B, int R, int D0, int D1, int D2);
+/* For every sample b and region r < R of bits [B][D0][D1][D2] (region bits, as cwf_region_bits writes them), V = D0 D1 D2:
+ *   labels[b][r][V]   int32: 0 = background; components under the 6/18/26-neighbour footprint (connectivity 1/2/3) numbered 1..K
+ *                     in increasing order of their smallest linear (C-order) voxel index -- scipy.ndimage.label's numbering
+ *   sizes[b][r][cap]  cap = (V + 1) / 2: entry k - 1 = voxels of component k, entries >= K are 0
+ *   count[b][r]       K
+ *   largest[b][r][2]  (label, size) of the largest component, ties to the lowest label; (0, 0) for an empty mask.
+ * The result does not depend on launch geometry or on the order in which atomics land.  ws: cwf_components_workspace(...) bytes,
+ * 256-B aligned.  No kernel waits on another workgroup. */
+int cwf_components(const uint8_t* bits, int B, int R, int D0, int D1, int D2, int connectivity, int32_t* labels, int32_t* sizes,
+                   int32_t* count, int32_t* largest, void* ws, int64_t ws_bytes, void* stream);
+/* seg_out[b][V] <- seg_in[b][V] (int64 classes 0..3; may be the same memory) under the policy below, from cwf_components' labels,
+ * sizes and largest of R regions over the region bits of seg_in (wt_region: the region `seg > 0`, et_region: the region `seg == 3`).
+ * Applied in this order, each rule off at 0:
+ *   1  every WT component of fewer than min_component voxels is set to 0
+ *   2  keep_largest: only the largest WT component that survived rule 1 is kept (ties: lowest label), every other voxel set to 0
+ *   3  every ET component of fewer than et_min_component voxels is relabelled et_replace (0, 1 or 2)
+ *   4  if fewer than et_min_voxels ET voxels remain after rules 1-3, all of them are relabelled et_replace
+ * stats[b][4] (int64) = WT voxels removed, WT components removed, ET voxels relabelled (rules 3 and 4), ET voxels remaining.
+ * ws: CWF_POSTPROCESS_WS_BYTES(B) bytes, 8-B aligned.  Two launches, the ET count of rule 4 is reduced on the device between them;
+ * nothing is read back.  CWF_E_BADARG: a null pointer, a region index outside [0, R), a negative threshold, et_replace outside 0..2. */
+#define CWF_POSTPROCESS_WS_BYTES(B) ((int64_t)(B) * 32)
+int cwf_postprocess_labels(const int64_t* seg_in, int64_t* seg_out, const int32_t* labels, const int32_t* sizes, const int32_t* largest,
+                           int B, int R, int D0, int D1, int D2, int wt_region, int et_region, int min_component, int keep_largest,
+                           int et_min_component, int et_min_voxels, int et_replace, int64_t* stats, void* ws, void* stream);
+/* counts[6][3] (uint64, accumulated: zero it first) += (|o & t|, |o|, |t|) of WT, TC, ET, class 1, class 2, class 3 of the int64 label
+ * maps seg and target of n voxels: the counts of cwf_argmax_metrics for a label map that is already there. */
+int cwf_label_metrics(const int64_t* seg, const int64_t* target, uint64_t* counts, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N5  sliding-window inference over volumes of any size (predict_overlap.sliding_window_inference): overlapping r0 x r1 x r2
  *     windows on a Cartesian grid of starts, blended with a separable importance map.
  * ---------------------------------------------------------------------------------------------- */

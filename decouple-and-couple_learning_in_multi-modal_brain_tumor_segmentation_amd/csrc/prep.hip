@@ -18,6 +18,9 @@
 // quad and channel; target and edge with two 16-B stores per quad (two int64 voxels each).  Crops whose rows are not a multiple of
 // four voxels, or outputs without 16-B alignment, take the same kernel with per-voxel stores.
 //
+// cwf_prepare_batch_affine: the same outputs from a rotated and zoomed crop (trilinear image, nearest label), a kernel of its own
+// further down that shares the bit helpers and the pass structure.
+//
 // cwf_normalize_nonzero: per-channel z-score over the voxels whose four-channel sum ((x0 + x1) + x2) + x3 (float32) is > 0, float64
 // two-pass statistics (partials per workgroup, reduced in a fixed order by one thread: the result does not depend on scheduling).
 // This file is compiled with -ffp-contract=off.
@@ -229,6 +232,255 @@ extern "C" int cwf_prepare_batch(const struct cwf_prep_sample* h_samples, int B,
     ab.target = target + (int64_t)b0 * t_bstride;
     ab.edge = edge + (int64_t)b0 * e_bstride;
     hipLaunchKernelGGL(prep_batch_kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, st, ab);
+    CWF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ rotated / zoomed crops
+// cwf_prepare_batch_affine: the same outputs from a resampled crop (statement: include/cwf_hip.h, utils.data._prepare_one_cpu).  The
+// halo tile is filled through the nearest-neighbour map, after which the passes are those of prep_batch_kernel on a smaller tile:
+// 8 x 8 x 32 output voxels per 256-thread workgroup (two quads per thread).  Under a rotation a tile reads a box of the source that is
+// as large along every axis as the tile's longest side, so the tile is kept near-cubic: 8 x 8 x 32 touches about 43 KB of image
+// (four channels) where 4 x 16 x 64 would touch several times that, and its taps are served by the CU's vector cache and L2.  LDS:
+// halo [10][10][36 B], passes [10][10][8] and [10][8][8] words (9.4 KiB).
+#define AFF_T0 8
+#define AFF_T1 8
+#define AFF_T2 32
+#define AFF_Q2 (AFF_T2 / 4)
+#define AFF_H0 (AFF_T0 + 2)
+#define AFF_H1 (AFF_T1 + 2)
+#define AFF_H2 (AFF_T2 + 2)
+#define AFF_ROW 36                          // halo row bytes (34 used, padded to whole words)
+#define AFF_QUADS (AFF_T0 * AFF_T1 * AFF_Q2 / 256)
+#define AFF_QMAX 1073741824.f               // |q| at and beyond 2^30 (and NaN): the voxel lies outside every volume
+
+struct PrepAffSample {
+  const float* image;
+  const uint8_t* label;
+  int S0, S1, S2, o0, o1, o2, flip, intensity;
+  float scale[4], shift[4];
+  float m[9];
+};
+
+struct PrepAffArgs {
+  PrepAffSample s[PREP_MAXS];
+  float* x;
+  int64_t* target;
+  int64_t* edge;
+  int64_t x_bs, t_bs, e_bs;
+  int C0, C1, C2, vec;
+};
+
+// crop-local source coordinate of the (already flipped) output voxel (p0, p1, p2); false when it is not representable
+__device__ __forceinline__ bool aff_coord(const PrepAffSample& S, int p0, int p1, int p2, float c0, float c1, float c2, float q[3]) {
+  const float u0 = __fsub_rn((float)p0, c0), u1 = __fsub_rn((float)p1, c1), u2 = __fsub_rn((float)p2, c2);
+  const float c[3] = {c0, c1, c2};
+  bool ok = true;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    q[d] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(S.m[3 * d], u0), __fmul_rn(S.m[3 * d + 1], u1)), __fmul_rn(S.m[3 * d + 2], u2)), c[d]);
+    ok = ok && fabsf(q[d]) < AFF_QMAX;
+  }
+  return ok;
+}
+
+__device__ __forceinline__ float aff_lerp(float a, float b, float f) { return __fadd_rn(a, __fmul_rn(f, __fsub_rn(b, a))); }
+
+__global__ __launch_bounds__(256) void prep_affine_kernel(const PrepAffArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t H[AFF_H0][AFF_H1][AFF_ROW];
+  __shared__ uint32_t P1[AFF_H0][AFF_H1][AFF_Q2];
+  __shared__ uint32_t P2[AFF_H0][AFF_T1][AFF_Q2];
+  const PrepAffSample& S = a.s[blockIdx.y];
+  const int C0 = a.C0, C1 = a.C1, C2 = a.C2;
+  const int n2 = (C2 + AFF_T2 - 1) / AFF_T2, n1 = (C1 + AFF_T1 - 1) / AFF_T1;
+  const int t = blockIdx.x;
+  const int b2 = (t % n2) * AFF_T2, b1 = ((t / n2) % n1) * AFF_T1, b0 = (t / (n2 * n1)) * AFF_T0;
+  const int f0 = S.flip & 1, f1 = (S.flip >> 1) & 1, f2 = (S.flip >> 2) & 1;
+  const float c0 = 0.5f * (float)(C0 - 1), c1 = 0.5f * (float)(C1 - 1), c2 = 0.5f * (float)(C2 - 1);
+  const int64_t S0 = S.S0, S1 = S.S1, S2 = S.S2, plane = S1 * S2, V = S0 * plane;
+  const int tid = threadIdx.x;
+
+  // 1. label bits of the halo tile, through the nearest-neighbour map
+  for (int i = tid; i < AFF_H0 * AFF_H1 * AFF_H2; i += 256) {
+    const int h2 = i % AFF_H2, h1 = (i / AFF_H2) % AFF_H1, h0 = i / (AFF_H2 * AFF_H1);
+    const int p0 = b0 + h0 - 1, p1 = b1 + h1 - 1, p2 = b2 + h2 - 1;
+    uint32_t v = 0x38u;                                       // out of the crop: identity of OR and AND
+    if (p0 >= 0 && p0 < C0 && p1 >= 0 && p1 < C1 && p2 >= 0 && p2 < C2) {
+      float q[3];
+      v = 0u;
+      if (aff_coord(S, f0 ? C0 - 1 - p0 : p0, f1 ? C1 - 1 - p1 : p1, f2 ? C2 - 1 - p2 : p2, c0, c1, c2, q)) {
+        const int64_t s0 = S.o0 + (int64_t)floorf(__fadd_rn(q[0], 0.5f)), s1 = S.o1 + (int64_t)floorf(__fadd_rn(q[1], 0.5f)),
+                      s2 = S.o2 + (int64_t)floorf(__fadd_rn(q[2], 0.5f));
+        if (s0 >= 0 && s0 < S0 && s1 >= 0 && s1 < S1 && s2 >= 0 && s2 < S2) v = prep_bits(S.label[s0 * plane + s1 * S2 + s2]);
+      }
+    }
+    H[h0][h1][h2] = (uint8_t)v;
+  }
+
+  // 2. image: eight dword taps per voxel and channel
+  const bool inten = S.intensity != 0;
+  const int64_t V_out = (int64_t)C0 * C1 * C2;
+  float* xs = a.x + (int64_t)blockIdx.y * a.x_bs;
+#pragma unroll 1
+  for (int k = 0; k < AFF_QUADS; ++k) {
+    const int qd = tid + 256 * k;
+    const int w = qd % AFF_Q2, j = (qd / AFF_Q2) % AFF_T1, i = qd / (AFF_Q2 * AFF_T1);
+    const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
+    if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
+    const int64_t dst = ((int64_t)p0 * C1 + p1) * C2 + p2;
+    float v[4][4];                                            // [channel][voxel of the quad]
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float q[3];
+      const bool ok = p2 + e < C2 &&
+                      aff_coord(S, f0 ? C0 - 1 - p0 : p0, f1 ? C1 - 1 - p1 : p1, f2 ? C2 - 1 - (p2 + e) : p2 + e, c0, c1, c2, q);
+      float fr[3] = {0.f, 0.f, 0.f};
+      int64_t s[3] = {0, 0, 0};
+      if (ok) {
+        const int o[3] = {S.o0, S.o1, S.o2};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const float fl = floorf(q[d]);
+          fr[d] = __fsub_rn(q[d], fl);
+          s[d] = o[d] + (int64_t)fl;
+        }
+      }
+      const bool in0[2] = {ok && s[0] >= 0 && s[0] < S0, ok && s[0] + 1 >= 0 && s[0] + 1 < S0};
+      const bool in1[2] = {s[1] >= 0 && s[1] < S1, s[1] + 1 >= 0 && s[1] + 1 < S1};
+      const bool in2[2] = {s[2] >= 0 && s[2] < S2, s[2] + 1 >= 0 && s[2] + 1 < S2};
+      const int64_t base = s[0] * plane + s[1] * S2 + s[2];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float* src = S.image + c * V + base;
+        float r0[2];
+#pragma unroll
+        for (int d0 = 0; d0 < 2; ++d0) {
+          float r1[2];
+#pragma unroll
+          for (int d1 = 0; d1 < 2; ++d1) {
+            const bool row_in = in0[d0] && in1[d1];
+            const float* row = src + d0 * plane + d1 * S2;
+            const float t0 = (row_in && in2[0]) ? row[0] : 0.f;
+            const float t1 = (row_in && in2[1]) ? row[1] : 0.f;
+            r1[d1] = aff_lerp(t0, t1, fr[2]);
+          }
+          r0[d0] = aff_lerp(r1[0], r1[1], fr[1]);
+        }
+        float r = aff_lerp(r0[0], r0[1], fr[0]);
+        if (inten) r = __fadd_rn(__fmul_rn(r, S.scale[c]), S.shift[c]);
+        v[c][e] = r;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float* d = xs + c * V_out + dst;
+      if (a.vec) {
+        f32x4 o = {v[c][0], v[c][1], v[c][2], v[c][3]};
+        *reinterpret_cast<f32x4*>(d) = o;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (p2 + e < C2) d[e] = v[c][e];
+      }
+    }
+  }
+  __syncthreads();
+
+  // 3. axis-2 pass: [10][10][8 quads]
+  for (int i = tid; i < AFF_H0 * AFF_H1 * AFF_Q2; i += 256) {
+    const int w = i % AFF_Q2, h1 = (i / AFF_Q2) % AFF_H1, h0 = i / (AFF_Q2 * AFF_H1);
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(&H[h0][h1][0]);
+    const uint32_t w0 = row[w], w1 = row[w + 1];
+    P1[h0][h1][w] = prep_or_and(w0, (w0 >> 8) | (w1 << 24), (w0 >> 16) | (w1 << 16));
+  }
+  __syncthreads();
+  // 4. axis-1 pass: [10][8][8]
+  for (int i = tid; i < AFF_H0 * AFF_T1 * AFF_Q2; i += 256) {
+    const int w = i % AFF_Q2, j = (i / AFF_Q2) % AFF_T1, h0 = i / (AFF_Q2 * AFF_T1);
+    P2[h0][j][w] = prep_or_and(P1[h0][j][w], P1[h0][j + 1][w], P1[h0][j + 2][w]);
+  }
+  __syncthreads();
+
+  // 5. axis-0 pass in registers, target and edge codes
+  int64_t* ts = a.target + (int64_t)blockIdx.y * a.t_bs;
+  int64_t* es = a.edge + (int64_t)blockIdx.y * a.e_bs;
+#pragma unroll 1
+  for (int k = 0; k < AFF_QUADS; ++k) {
+    const int qd = tid + 256 * k;
+    const int w = qd % AFF_Q2, j = (qd / AFF_Q2) % AFF_T1, i = qd / (AFF_Q2 * AFF_T1);
+    const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
+    if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
+    const uint32_t r = prep_or_and(P2[i][j][w], P2[i + 1][j][w], P2[i + 2][j][w]);
+    const uint32_t band = (r & 0x07070707u) & ~((r >> 3) & 0x07070707u);
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(&H[i + 1][j + 1][0]);
+    const uint32_t centre = (row[w] >> 8) | (row[w + 1] << 24);
+    int64_t tl[4], ec[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      tl[e] = prep_label((centre >> (8 * e)) & 0xFFu);
+      ec[e] = prep_code((band >> (8 * e)) & 0xFFu);
+    }
+    const int64_t dst = ((int64_t)p0 * C1 + p1) * C2 + p2;
+    if (a.vec) {
+      typedef long long i64x2 __attribute__((ext_vector_type(2)));
+      i64x2* tp = reinterpret_cast<i64x2*>(ts + dst);
+      i64x2* ep = reinterpret_cast<i64x2*>(es + dst);
+      tp[0] = i64x2{tl[0], tl[1]};
+      tp[1] = i64x2{tl[2], tl[3]};
+      ep[0] = i64x2{ec[0], ec[1]};
+      ep[1] = i64x2{ec[2], ec[3]};
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (p2 + e < C2) {
+          ts[dst + e] = tl[e];
+          es[dst + e] = ec[e];
+        }
+    }
+  }
+}
+
+extern "C" int cwf_prepare_batch_affine(const struct cwf_prep_affine_sample* h_samples, int B, int C0, int C1, int C2, float* x,
+                                        int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride,
+                                        void* stream) {
+  if (!h_samples || B <= 0 || C0 <= 0 || C1 <= 0 || C2 <= 0 || !x || !target || !edge) return CWF_E_BADARG;
+  const int64_t V = (int64_t)C0 * C1 * C2;
+  if (V >= (int64_t(1) << 31)) return CWF_E_TOOLARGE;
+  if (((uintptr_t)x & 3) || ((uintptr_t)target & 7) || ((uintptr_t)edge & 7)) return CWF_E_BADARG;
+  if (x_bstride < 4 * V || t_bstride < V || e_bstride < V) return CWF_E_BADARG;
+  for (int b = 0; b < B; ++b) {
+    const cwf_prep_affine_sample& s = h_samples[b];
+    if (!s.image || !s.label || ((uintptr_t)s.image & 3) || s.flip < 0 || s.flip > 7) return CWF_E_BADARG;
+    if (s.S0 <= 0 || s.S1 <= 0 || s.S2 <= 0) return CWF_E_BADARG;
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(s.m[k])) return CWF_E_BADARG;
+  }
+  PrepAffArgs a;
+  a.x = x; a.target = target; a.edge = edge;
+  a.x_bs = x_bstride; a.t_bs = t_bstride; a.e_bs = e_bstride;
+  a.C0 = C0; a.C1 = C1; a.C2 = C2;
+  a.vec = (C2 % 4 == 0) && !((uintptr_t)x & 15) && !((uintptr_t)target & 15) && !((uintptr_t)edge & 15) && x_bstride % 4 == 0 &&
+          t_bstride % 2 == 0 && e_bstride % 2 == 0;
+  const int64_t tiles = (int64_t)cdiv(C0, AFF_T0) * cdiv(C1, AFF_T1) * cdiv(C2, AFF_T2);
+  hipStream_t st = cwf_stream(stream);
+  for (int b0 = 0; b0 < B; b0 += PREP_MAXS) {
+    const int nb = std::min(PREP_MAXS, B - b0);
+    for (int i = 0; i < PREP_MAXS; ++i) {
+      PrepAffSample& d = a.s[i];
+      if (i >= nb) { d = PrepAffSample{}; continue; }
+      const cwf_prep_affine_sample& s = h_samples[b0 + i];
+      d.image = s.image; d.label = s.label;
+      d.S0 = s.S0; d.S1 = s.S1; d.S2 = s.S2; d.o0 = s.o0; d.o1 = s.o1; d.o2 = s.o2;
+      d.flip = s.flip; d.intensity = s.intensity;
+      for (int c = 0; c < 4; ++c) { d.scale[c] = s.scale[c]; d.shift[c] = s.shift[c]; }
+      for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+    }
+    PrepAffArgs ab = a;
+    ab.x = x + (int64_t)b0 * x_bstride;
+    ab.target = target + (int64_t)b0 * t_bstride;
+    ab.edge = edge + (int64_t)b0 * e_bstride;
+    hipLaunchKernelGGL(prep_affine_kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, st, ab);
     CWF_LAUNCH_CHECK();
   }
   return 0;

@@ -104,6 +104,7 @@ SIGNATURES = {
     "cwf_postprocess_labels": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
     "cwf_label_metrics": [P, P, P, L, P],
     "cwf_prepare_batch": [P, I, I, I, I, P, L, P, L, P, L, P],
+    "cwf_prepare_batch_affine": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_window_gather": [P, P, P, I, I, P],
     "cwf_window_blend": [P, P, P, P, I, I, I, P],
     "cwf_window_finalize": [P, P, P, P, P],
@@ -174,6 +175,11 @@ class PrepSample(C.Structure):
     """struct cwf_prep_sample (include/cwf_hip.h)"""
     _fields_ = [("image", P), ("label", P), ("S0", I), ("S1", I), ("S2", I), ("o0", I), ("o1", I), ("o2", I), ("flip", I),
                 ("intensity", I), ("scale", F * 4), ("shift", F * 4)]
+
+
+class PrepAffineSample(C.Structure):
+    """struct cwf_prep_affine_sample (include/cwf_hip.h)"""
+    _fields_ = PrepSample._fields_ + [("m", F * 9)]
 
 
 WINDOW_MAX_STARTS = 128   # CWF_WINDOW_MAX_STARTS

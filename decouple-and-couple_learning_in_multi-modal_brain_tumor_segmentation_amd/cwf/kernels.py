@@ -1379,8 +1379,10 @@ class HipBackend:
     def prepare_batch(self, images, labels, params, crop, out=None):
         """Training batch (x [B,4,C0,C1,C2] fp32, target [B,C0,C1,C2] int64, edge [B,C0,C1,C2] int64) from per-sample source volumes
         (images[b] fp32 [4,S0,S1,S2], labels[b] uint8 [S0,S1,S2], contiguous, one device) in launches of eight samples (cwf_prepare_batch).
-        params[b]: .origin (3 ints), .flip (3 bools), .scale / .shift (4 floats each, or None: intensity off).  out: (x, target, edge)
-        to write into; each needs contiguous inner dimensions, its sample stride may be larger than one sample."""
+        params[b]: .origin (3 ints), .flip (3 bools), .scale / .shift (4 floats each, or None: intensity off), .matrix (9 floats, or
+        None).  When some sample has a matrix the batch goes through cwf_prepare_batch_affine (rotated / zoomed crops, any origin), the
+        samples without one with the identity.  out: (x, target, edge) to write into; each needs contiguous inner dimensions, its
+        sample stride may be larger than one sample."""
         crop = tuple(int(c) for c in crop)
         if len(crop) != 3:
             raise ValueError("prepare_batch: crop needs three extents, got %r" % (crop,))
@@ -1392,7 +1394,8 @@ class HipBackend:
         dev = images[0].device
         if dev.type != "cuda":
             raise ValueError("prepare_batch: the images must be on a GPU")
-        samples = (_lib.PrepSample * nb)()
+        affine = any(getattr(p, "matrix", None) is not None for p in params)
+        samples = ((_lib.PrepAffineSample if affine else _lib.PrepSample) * nb)()
         for b, (img, lab, p) in enumerate(zip(images, labels, params)):
             if img.dtype != _f32 or img.dim() != 4 or img.shape[0] != 4 or not img.is_contiguous() or img.device != dev:
                 raise ValueError("prepare_batch: images[%d] must be a contiguous float32 [4, S0, S1, S2] tensor on %s" % (b, dev))
@@ -1407,6 +1410,9 @@ class HipBackend:
             if p.scale is not None:
                 s.scale[:] = [float(v) for v in p.scale]
                 s.shift[:] = [float(v) for v in p.shift]
+            if affine:
+                m = getattr(p, "matrix", None)
+                s.m[:] = [float(v) for v in m] if m is not None else [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
         if out is None:
             # (a crop the library refuses -- an extent <= 0 or 2^31 voxels and more -- gets placeholders: the refusal comes from it)
             ok = all(c > 0 for c in crop) and crop[0] * crop[1] * crop[2] < (1 << 31)
@@ -1421,7 +1427,7 @@ class HipBackend:
                 inner = torch.empty(shape[1:], device="meta").stride()
                 if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or tuple(t.stride()[1:]) != inner:
                     raise ValueError("prepare_batch: out %s must be a %s %s tensor on %s with contiguous samples" % (name, dt, shape, dev))
-        self._call("cwf_prepare_batch", ctypes.addressof(samples), nb, crop[0], crop[1], crop[2], x.data_ptr(), x.stride(0),
+        self._call("cwf_prepare_batch_affine" if affine else "cwf_prepare_batch", ctypes.addressof(samples), nb, crop[0], crop[1], crop[2], x.data_ptr(), x.stride(0),
                    target.data_ptr(), target.stride(0), edge.data_ptr(), edge.stride(0), self._stream())
         return x, target, edge
 

@@ -94,6 +94,9 @@ def build_parser():
     p.add_argument("--aug_flip", default=False, type=_bool, help="(--device_data) flip each crop axis with probability 1/2")
     p.add_argument("--aug_intensity", default=0.0, type=float,
                    help="(--device_data) f > 0: per-channel x * U(1-f, 1+f) + U(-f, f)")
+    p.add_argument("--aug_rotate", default=0.0, type=float,
+                   help="(--device_data) r > 0: rotate the crop by three Euler angles ~ U(-r, r) degrees (trilinear image, nearest label)")
+    p.add_argument("--aug_scale", default=0.0, type=float, help="(--device_data) f > 0: isotropic zoom of the crop ~ U(1-f, 1+f)")
     p.add_argument("--normalize", default=False, type=_bool,
                    help="(--device_data) z-score each subject's channels over its brain mask (four-channel sum > 0) at load")
     return p
@@ -134,13 +137,18 @@ def make_device_dataset(args, device):
         lst = os.path.join(source, args.train_file)
         lst = lst if os.path.isfile(lst) else None
     return data.DeviceBraTS(source, device, crop, args.seed, flip=args.aug_flip, intensity=args.aug_intensity,
-                            normalize=args.normalize, cache=(args.device_data == "cache"), list_file=lst)
+                            normalize=args.normalize, cache=(args.device_data == "cache"), list_file=lst, rotate=args.aug_rotate,
+                            scale=args.aug_scale)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.device_data != "off" and args.mode != "train":
         raise SystemExit("--device_data %s prepares training batches: only --mode train is supported on that path" % args.device_data)
+    if args.device_data == "off" and (args.aug_rotate > 0.0 or args.aug_scale > 0.0):
+        raise SystemExit("--aug_rotate / --aug_scale resample the crop on the device: they need --device_data cache or staged")
+    if args.aug_rotate < 0.0 or not 0.0 <= args.aug_scale < 1.0:
+        raise SystemExit("--aug_rotate takes degrees >= 0 and --aug_scale a fraction in [0, 1)")
     from cwf import kernels
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint

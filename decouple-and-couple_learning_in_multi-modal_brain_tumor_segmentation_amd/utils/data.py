@@ -11,7 +11,8 @@ Two map-style datasets produce exactly that tuple from 240 x 240 x 155 volumes w
 Edge codes are derived from the label with utils.synthetic.edge_codes (boundary of each sub-region, coded per E1/E2/E4).
 
 ``DeviceBraTS`` / ``prepare_batch`` produce the same tuple on the GPU (csrc/prep.hip: crop, optional flips and intensity scale / shift,
-label remap and edge codes in one launch per eight samples), bit-equal to the CPU statement in this module."""
+label remap and edge codes in one launch per eight samples; with a matrix in the parameters the crop is rotated and zoomed, trilinear for
+the image and nearest for the label), bit-equal to the CPU statement in this module."""
 import glob
 import os
 
@@ -103,11 +104,12 @@ class NpzBraTS(Dataset):
 # loaders the reference descends from flip each axis and shift intensities per channel; the reference's own `data/` package is absent),
 # so they are opt-in and off by default.
 class AugParams:
-    """Per-sample batch parameters: crop origin (3 ints), flips of the three crop axes, and the per-channel intensity scale / shift
-    (float32 [4] each; None = intensity off)."""
-    __slots__ = ("origin", "flip", "scale", "shift")
+    """Per-sample batch parameters: crop origin (3 ints), flips of the three crop axes, the per-channel intensity scale / shift
+    (float32 [4] each; None = intensity off), and matrix: the linear part M[d][j] of the output -> source map about the crop centre
+    (nine float32 values, row-major; None = no resampling, the plain crop)."""
+    __slots__ = ("origin", "flip", "scale", "shift", "matrix")
 
-    def __init__(self, origin, flip=(False, False, False), scale=None, shift=None):
+    def __init__(self, origin, flip=(False, False, False), scale=None, shift=None, matrix=None):
         self.origin = tuple(int(o) for o in origin)
         self.flip = tuple(bool(f) for f in flip)
         if (scale is None) != (shift is None):
@@ -116,33 +118,144 @@ class AugParams:
         self.shift = None if shift is None else tuple(float(v) for v in np.asarray(shift, dtype=np.float32))
         if len(self.origin) != 3 or len(self.flip) != 3 or (self.scale is not None and (len(self.scale) != 4 or len(self.shift) != 4)):
             raise ValueError("AugParams: origin and flip take 3 values, scale and shift 4")
+        self.matrix = None if matrix is None else tuple(float(v) for v in np.asarray(matrix, dtype=np.float32).reshape(-1))
+        if self.matrix is not None and len(self.matrix) != 9:
+            raise ValueError("AugParams: matrix takes 9 values")
 
     def at_origin(self, origin):
-        return AugParams(origin, self.flip, self.scale, self.shift)
+        return AugParams(origin, self.flip, self.scale, self.shift, self.matrix)
+
+    def source_box(self, crop):
+        """Integer bounds ((lo_0, hi_0), ...) relative to the origin, hi exclusive, that contain every source index the crop reads
+        (both trilinear taps and the nearest label): the float64 range of q_d over the crop, widened by one voxel."""
+        c = [(int(n) - 1) / 2.0 for n in crop]
+        if self.matrix is None:
+            return tuple((0, int(n)) for n in crop)
+        m = np.asarray(self.matrix, dtype=np.float64).reshape(3, 3)
+        box = []
+        for d in range(3):
+            r = sum(abs(m[d, j]) * c[j] for j in range(3))
+            box.append((int(np.floor(c[d] - r)) - 1, int(np.floor(c[d] + r)) + 3))
+        return tuple(box)
 
     def __eq__(self, other):
         return isinstance(other, AugParams) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
 
     def __repr__(self):
-        return "AugParams(origin=%r, flip=%r, scale=%r, shift=%r)" % (self.origin, self.flip, self.scale, self.shift)
+        head = "AugParams(origin=%r, flip=%r, scale=%r, shift=%r" % (self.origin, self.flip, self.scale, self.shift)
+        return head + (")" if self.matrix is None else ", matrix=%r)" % (self.matrix,))
 
 
-def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0):
+def rotation_zoom_matrix(angles_deg, zoom=1.0):
+    """float32 [9] (row-major) of Rz(gamma) . Ry(beta) . Rx(alpha) / zoom for angles (alpha, beta, gamma) in degrees about the crop's
+    axes 0, 1, 2, computed in float64: the output -> source map of a patch rotated by the angles and magnified by `zoom`."""
+    al, be, ga = (np.deg2rad(float(v)) for v in angles_deg)
+    rx = np.array([[1, 0, 0], [0, np.cos(al), -np.sin(al)], [0, np.sin(al), np.cos(al)]], dtype=np.float64)
+    ry = np.array([[np.cos(be), 0, np.sin(be)], [0, 1, 0], [-np.sin(be), 0, np.cos(be)]], dtype=np.float64)
+    rz = np.array([[np.cos(ga), -np.sin(ga), 0], [np.sin(ga), np.cos(ga), 0], [0, 0, 1]], dtype=np.float64)
+    return ((rz @ ry @ rx) / float(zoom)).astype(np.float32).reshape(9)
+
+
+def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotate=0.0, scale=0.0):
     """Parameters of sample `index` in `epoch`: a pure function of the arguments, drawn from default_rng([seed, epoch, index]).  The
     origin is drawn first, by random_crop_origin's calls, so with augmentation off it is the origin NpzBraTS / SyntheticBraTS pick.
-    flip: three uniforms, each < 0.5 flipping that axis; intensity f > 0: scale ~ U(1-f, 1+f)[4], then shift ~ U(-f, f)[4] (float32)."""
+    flip: three uniforms, each < 0.5 flipping that axis; intensity f > 0: scale ~ U(1-f, 1+f)[4], then shift ~ U(-f, f)[4] (float32).
+    Drawn after all of those, so that they do not depend on it: rotate r > 0: three Euler angles ~ U(-r, r) degrees; scale f > 0: an
+    isotropic zoom ~ U(1-f, 1+f); matrix = rotation_zoom_matrix(angles, zoom), None with both off."""
     rng = np.random.default_rng([int(seed), int(epoch), int(index)])
     origin = random_crop_origin(tuple(full), tuple(crop), rng)
+    r, z = float(rotate), float(scale)
     fl = tuple(bool(u < 0.5) for u in rng.random(3)) if flip else (False, False, False)
     scale = shift = None
     f = float(intensity)
     if f > 0.0:
         scale = rng.uniform(1.0 - f, 1.0 + f, 4).astype(np.float32)
         shift = rng.uniform(-f, f, 4).astype(np.float32)
-    return AugParams(origin, fl, scale, shift)
+    matrix = None
+    if r > 0.0 or z > 0.0:
+        angles = rng.uniform(-r, r, 3) if r > 0.0 else np.zeros(3)
+        zoom = float(rng.uniform(1.0 - z, 1.0 + z)) if z > 0.0 else 1.0
+        matrix = rotation_zoom_matrix(angles, zoom)
+    return AugParams(origin, fl, scale, shift, matrix)
+
+
+_Q_MAX = np.float32(2.0 ** 30)      # |q| at and beyond it (and NaN): the voxel lies outside every volume
+
+
+def _affine_coords(p, crop):
+    """q [3, *crop] float32 of the statement in _resample_cpu, and ok [*crop]: every |q_d| < 2^30"""
+    q, ok = [], np.ones(tuple(crop), dtype=bool)
+    c = [np.float32(n - 1) * np.float32(0.5) for n in crop]
+    u = []
+    for d in range(3):
+        pd = np.arange(crop[d], dtype=np.int64)
+        if p.flip[d]:
+            pd = crop[d] - 1 - pd
+        u.append((pd.astype(np.float32) - c[d]).reshape([-1 if k == d else 1 for k in range(3)]))
+    m = np.asarray(p.matrix, dtype=np.float32).reshape(3, 3)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for d in range(3):
+            qd = ((m[d, 0] * u[0] + m[d, 1] * u[1]) + m[d, 2] * u[2]) + c[d]
+            ok &= np.abs(qd) < _Q_MAX               # (False for NaN)
+            q.append(qd)
+    return q, ok
+
+
+def _resample_cpu(img, lab, p, crop):
+    """The resampled crop, numpy float32 with one rounding per operation.  With c_d = (C_d - 1) / 2, o the origin, p the output voxel:
+        p'_d = flip_d ? C_d - 1 - p_d : p_d                       (resample, then torch.flip of the result)
+        u_d  = float(p'_d) - c_d
+        q_d  = ((M[d][0]*u_0 + M[d][1]*u_1) + M[d][2]*u_2) + c_d   crop-local source coordinate
+        image: i_d = floor(q_d), f_d = q_d - i_d, the eight taps at source index o_d + i_d + {0, 1}, 0.0 where an index leaves
+               [0, S_d); lerp(a, b, f) = a + f*(b - a) along axis 2, then axis 1, then axis 0
+        label: label[o + floor(q + 0.5)], 0 outside the volume
+    A voxel with some |q_d| >= 2^30 or NaN reads nothing: image 0.0, label 0.  The origin enters only as an integer added to the
+    indices, so the result does not change when the source is cut to a box and the origin moved with it."""
+    crop = tuple(int(c) for c in crop)
+    a, l = img.numpy(), lab.numpy()
+    S = l.shape
+    q, ok = _affine_coords(p, crop)
+    idx, fr, nn = [], [], []
+    for d in range(3):
+        qd = np.where(ok, q[d], np.float32(0.0)).astype(np.float32)
+        fl = np.floor(qd)
+        fr.append(qd - fl)
+        idx.append(fl.astype(np.int64) + p.origin[d])
+        nn.append(np.floor(qd + np.float32(0.5)).astype(np.int64) + p.origin[d])
+
+    def inside(i, d):
+        return (i >= 0) & (i < S[d])
+
+    x = np.empty((4,) + crop, dtype=np.float32)
+    taps = {}
+    for d0 in (0, 1):
+        for d1 in (0, 1):
+            for d2 in (0, 1):
+                i0, i1, i2 = idx[0] + d0, idx[1] + d1, idx[2] + d2
+                m = ok & inside(i0, 0) & inside(i1, 1) & inside(i2, 2)
+                taps[d0, d1, d2] = (m, np.clip(i0, 0, S[0] - 1), np.clip(i1, 0, S[1] - 1), np.clip(i2, 0, S[2] - 1))
+
+    def lerp(lo, hi, f):
+        return lo + f * (hi - lo)
+
+    for c in range(4):
+        v = {k: np.where(m, a[c][i0, i1, i2], np.float32(0.0)).astype(np.float32) for k, (m, i0, i1, i2) in taps.items()}
+        r1 = {(d0, d1): lerp(v[d0, d1, 0], v[d0, d1, 1], fr[2]) for d0 in (0, 1) for d1 in (0, 1)}
+        r0 = [lerp(r1[d0, 0], r1[d0, 1], fr[1]) for d0 in (0, 1)]
+        x[c] = lerp(r0[0], r0[1], fr[0])
+    m = ok & inside(nn[0], 0) & inside(nn[1], 1) & inside(nn[2], 2)
+    t = np.where(m, l[np.clip(nn[0], 0, S[0] - 1), np.clip(nn[1], 0, S[1] - 1), np.clip(nn[2], 0, S[2] - 1)], 0).astype(np.int64)
+    return torch.from_numpy(x), torch.from_numpy(t)
 
 
 def _prepare_one_cpu(img, lab, p, crop):
+    if p.matrix is not None:
+        x, t = _resample_cpu(img, lab, p, crop)
+        if p.scale is not None:
+            x = x * torch.tensor(p.scale, dtype=torch.float32).reshape(4, 1, 1, 1)
+            x = x + torch.tensor(p.shift, dtype=torch.float32).reshape(4, 1, 1, 1)
+        t[t == 4] = 3
+        return x, t, syn.edge_codes(t)
     x = crop_pad(img, p.origin, crop)
     t = crop_pad(lab.to(torch.int64), p.origin, crop)
     dims = [d for d in range(3) if p.flip[d]]
@@ -158,8 +271,9 @@ def _prepare_one_cpu(img, lab, p, crop):
 
 def prepare_batch(images, labels, params, crop, out=None):
     """(x [B,4,*crop] float32, target [B,*crop] int64, edge [B,*crop] int64) from source volumes images[b] float32 [4,S0,S1,S2] and
-    labels[b] uint8 [S0,S1,S2] (values 0..4): crop_pad at params[b].origin -> torch.flip of the flipped crop axes -> x * scale then
-    + shift in float32 -> label 4 -> 3 -> utils.synthetic.edge_codes.  On GPU tensors this is one HIP launch per eight samples
+    labels[b] uint8 [S0,S1,S2] (values 0..4): crop_pad at params[b].origin (with params[b].matrix: the resampled crop of
+    _resample_cpu, any origin) -> torch.flip of the flipped crop axes -> x * scale then + shift in float32 -> label 4 -> 3 ->
+    utils.synthetic.edge_codes.  On GPU tensors this is one HIP launch per eight samples
     (HipBackend.prepare_batch, bit-equal to the CPU statement); on CPU tensors it is the CPU statement itself.  out: (x, target, edge)
     to write into (sample stride free, samples contiguous)."""
     crop = tuple(int(c) for c in crop)
@@ -239,10 +353,13 @@ def _subject_arrays(img, lab, name):
 class NpzCropSource(Dataset):
     """Map-style dataset of the staged device path (DeviceBraTS(cache=False)), run in DataLoader workers: item i is the crop of subject
     i at draw_params' origin, before any flip or intensity -- (image float32 [4,*crop], label uint8 [*crop], index) -- from one
-    np.load + crop_pad (no edge codes).  `subjects`: .npz paths, or in-memory (image, label) pairs."""
+    np.load + crop_pad (no edge codes).  `subjects`: .npz paths, or in-memory (image, label) pairs.  With rotate / scale on, the
+    item is instead the part of the volume the resampled crop reads (staged_box: shapes differ from item to item); flip and
+    intensity are taken only because they move the matrix's place in draw_params' stream."""
 
-    def __init__(self, subjects, crop, seed=1000, normalize=False):
+    def __init__(self, subjects, crop, seed=1000, normalize=False, flip=False, intensity=0.0, rotate=0.0, scale=0.0):
         self.subjects, self.crop, self.seed, self.normalize, self.epoch = list(subjects), tuple(crop), int(seed), bool(normalize), 0
+        self.flip, self.intensity, self.rotate, self.scale = bool(flip), float(intensity), float(rotate), float(scale)
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -268,13 +385,33 @@ class NpzCropSource(Dataset):
 
     def __getitem__(self, i):
         img, lab = self.load(i)
+        if self.rotate > 0.0 or self.scale > 0.0:
+            p = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop, self.flip, self.intensity, self.rotate, self.scale)
+            (a0, b0), (a1, b1), (a2, b2) = staged_box(p, tuple(lab.shape), self.crop)
+            return img[:, a0:b0, a1:b1, a2:b2].contiguous(), lab[a0:b0, a1:b1, a2:b2].contiguous(), i
         o = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop).origin
         return crop_pad(img, o, self.crop), crop_pad(lab, o, self.crop), i
 
 
-def _collate_crops(items):
+def staged_box(p, extents, crop):
+    """((lo_0, hi_0), ...) in volume indices: origin + p.source_box(crop) clipped to the volume, never empty.  Every index the
+    resampled crop reads inside the volume lies in it, so preparing from volume[box] at origin - lo gives the same batch."""
+    box = []
+    for o, (lo, hi), s in zip(p.origin, p.source_box(crop), extents):
+        lo = min(max(o + lo, 0), s - 1)
+        box.append((lo, min(max(o + hi, lo + 1), s)))
+    return tuple(box)
+
+
+def _collate_crops(items, stack=True):
     imgs, labs, idx = zip(*items)
+    if not stack:                       # source boxes of resampled crops: one shape per item
+        return list(imgs), list(labs), list(idx)
     return torch.stack(imgs), torch.stack(labs), list(idx)
+
+
+def _collate_boxes(items):
+    return _collate_crops(items, stack=False)
 
 
 class DeviceBraTS:
@@ -282,21 +419,26 @@ class DeviceBraTS:
     samples for crop + flips + intensity + label remap + edge codes, written straight into caller-owned buffers with out=.
 
     source: a directory of .npz subjects (NpzBraTS's layout; `list_file` as NpzBraTS's) or a list of (image, label) pairs -- e.g.
-    utils.synthetic.synthetic_volume outputs.  Sample i of epoch e uses draw_params(seed, e, i, its extents, crop, flip, intensity);
-    with augmentation off a batch equals torch.stack of NpzBraTS / SyntheticBraTS items.
+    utils.synthetic.synthetic_volume outputs.  Sample i of epoch e uses draw_params(seed, e, i, its extents, crop, flip, intensity,
+    rotate, scale); with augmentation off a batch equals torch.stack of NpzBraTS / SyntheticBraTS items.  rotate (degrees) / scale
+    > 0 turn the crop into a randomly rotated / zoomed one (trilinear image, nearest label) in the same launch.
       cache=True   every subject is loaded once onto the device (fp32 image, uint8 label, optionally z-scored by normalize_nonzero)
       cache=False  "staged": NpzCropSource crops in DataLoader workers (batches()), the crops are uploaded from pinned memory and
-                   prepared at origin 0 -- 36 MB per 128^3 sample over the host link instead of a whole subject."""
+                   prepared at origin 0 -- 36 MB per 128^3 sample over the host link instead of a whole subject.  With rotate /
+                   scale the workers cut staged_box, the part of the volume the resampled crop reads, and the origin moves with it:
+                   the batch is bit-equal to cache=True."""
 
     def __init__(self, source, device, crop=(128, 128, 128), seed=1000, flip=False, intensity=0.0, normalize=False, cache=True,
-                 list_file=None):
+                 list_file=None, rotate=0.0, scale=0.0):
         self.device = torch.device(device)
         self.crop, self.seed, self.epoch = tuple(int(c) for c in crop), int(seed), 0
         self.flip, self.intensity, self.normalize, self.cache = bool(flip), float(intensity), bool(normalize), bool(cache)
+        self.rotate, self.scale = float(rotate), float(scale)
+        self.affine = self.rotate > 0.0 or self.scale > 0.0
         subjects = _npz_paths(source, list_file) if isinstance(source, str) else list(source)
         if not subjects:
             raise ValueError("DeviceBraTS: no subjects")
-        self.source = NpzCropSource(subjects, self.crop, self.seed, self.normalize)
+        self.source = NpzCropSource(subjects, self.crop, self.seed, self.normalize, self.flip, self.intensity, self.rotate, self.scale)
         self.images = self.labels = None
         if self.cache:
             self._load_all(subjects)
@@ -347,7 +489,7 @@ class DeviceBraTS:
         return tuple(_npz_shapes(s)[1]) if isinstance(s, str) else tuple(s[1].shape)
 
     def params(self, i):
-        return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity)
+        return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity, self.rotate, self.scale)
 
     def _missing(self, n):
         return torch.zeros((n, 4), dtype=torch.bool, device=self.device)
@@ -359,15 +501,24 @@ class DeviceBraTS:
             x, t, e = prepare_batch([self.images[i] for i in indices], [self.labels[i] for i in indices],
                                     [self.params(i) for i in indices], self.crop, out=out)
             return x, t, e, self._missing(len(indices))
-        return self.prepare_staged(_collate_crops([self.source[i] for i in indices]), out=out)
+        return self.prepare_staged(_collate_crops([self.source[i] for i in indices], stack=not self.affine), out=out)
 
     def prepare_staged(self, crops, out=None):
-        """(image crops [B,4,*crop] float32, label crops [B,*crop] uint8, indices) from NpzCropSource -> the prepared batch"""
+        """(image crops [B,4,*crop] float32, label crops [B,*crop] uint8, indices) from NpzCropSource -> the prepared batch; with
+        rotate / scale the crops are lists of source boxes and every sample is re-origined by its box's low corner"""
         imgs, labs, idx = crops
-        if self.device.type == "cuda":
-            imgs, labs = imgs.to(self.device, non_blocking=True), labs.to(self.device, non_blocking=True)
-        zero = (0, 0, 0)
-        x, t, e = prepare_batch(list(imgs), list(labs), [self.params(i).at_origin(zero) for i in idx], self.crop, out=out)
+        params = [self.params(i) for i in idx]
+        if self.affine:
+            if self.device.type == "cuda":
+                imgs = [v.to(self.device, non_blocking=True) for v in imgs]
+                labs = [v.to(self.device, non_blocking=True) for v in labs]
+            params = [p.at_origin([o - b[0] for o, b in zip(p.origin, staged_box(p, self.extents(i), self.crop))])
+                      for p, i in zip(params, idx)]
+        else:
+            if self.device.type == "cuda":
+                imgs, labs = imgs.to(self.device, non_blocking=True), labs.to(self.device, non_blocking=True)
+            params = [p.at_origin((0, 0, 0)) for p in params]
+        x, t, e = prepare_batch(list(imgs), list(labs), params, self.crop, out=out)
         return x, t, e, self._missing(len(idx))
 
     def batches(self, index_batches, num_workers=0, out=None):
@@ -380,6 +531,7 @@ class DeviceBraTS:
                 yield self.batch(b, out=get_out())
             return
         loader = torch.utils.data.DataLoader(self.source, batch_sampler=index_batches, num_workers=int(num_workers),
-                                             collate_fn=_collate_crops, pin_memory=self.device.type == "cuda")
+                                             collate_fn=_collate_crops if not self.affine else _collate_boxes,
+                                             pin_memory=self.device.type == "cuda")
         for crops in loader:
             yield self.prepare_staged(crops, out=get_out())

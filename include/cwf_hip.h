@@ -514,6 +514,26 @@ struct cwf_prep_sample {
  * misaligned pointer (image / x 4 B, target / edge 8 B), a stride smaller than one sample; CWF_E_TOOLARGE: 2^31 output voxels or more. */
 int cwf_prepare_batch(const struct cwf_prep_sample* h_samples, int B, int C0, int C1, int C2, float* x, int64_t x_bstride,
                       int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream);
+/* cwf_prep_sample plus the linear part m[3*d + j] = M[d][j] of the output -> source map (rotation and zoom about the crop centre);
+ * the origin may be any integer. */
+struct cwf_prep_affine_sample {
+  const float* image; const uint8_t* label;
+  int S0, S1, S2, o0, o1, o2, flip, intensity;
+  float scale[4], shift[4];
+  float m[9];
+};
+/* cwf_prepare_batch with a resampled crop.  With c_d = (C_d - 1) / 2, p'_d = flip_d ? C_d-1-p_d : p_d, u_d = float(p'_d) - c_d and
+ * every operation a float32 round-to-nearest one in the association written (no fused multiply-add):
+ *   q_d    = ((m[3d]*u_0 + m[3d+1]*u_1) + m[3d+2]*u_2) + c_d                    crop-local source coordinate
+ *   x      trilinear: i_d = floor(q_d), f_d = q_d - i_d, taps image[c][o + i + {0,1}^3] (0.0 where an index leaves [0, S_d)),
+ *          lerp(a, b, f) = a + f*(b - a) along axis 2, then 1, then 0; then the intensity map of cwf_prepare_batch
+ *   target label[o + floor(q + 0.5f)] with 4 -> 3 (0 outside the volume), int64
+ *   edge   utils.synthetic.edge_codes of that target within the crop, int64
+ * A voxel with some |q_d| >= 2^30 or NaN has every tap and its label outside the volume.  An identity m reproduces
+ * cwf_prepare_batch's values.  Eight samples per launch, passed by value as there.  CWF_E_BADARG as for cwf_prepare_batch except
+ * that every origin is accepted, and for a non-finite m entry; CWF_E_TOOLARGE: 2^31 output voxels or more. */
+int cwf_prepare_batch_affine(const struct cwf_prep_affine_sample* h_samples, int B, int C0, int C1, int C2, float* x,
+                             int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream);
 /* In place on one subject image fp32 [4][V]: over the voxels whose ((x0 + x1) + x2) + x3 > 0 (float32), each channel becomes
  * float32((x - mean_c) / std_c) with the float64 mean and population std of that channel over those voxels (two passes); other voxels,
  * and channels with std 0, are untouched.  ws: CWF_NORM_WS_DOUBLES doubles of device scratch. */

@@ -103,6 +103,9 @@ SIGNATURES = {
     "cwf_components": [P, I, I, I, I, I, I, P, P, P, P, P, L, P],
     "cwf_postprocess_labels": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
     "cwf_label_metrics": [P, P, P, L, P],
+    "cwf_dilate_bits": [P, P, I, I, I, I, I, I, P, L, P],
+    "cwf_lesionwise_workspace": [I, I, I, I, I],
+    "cwf_lesionwise": [P, P, I, I, I, I, I, I, L, D, P, P, P, P, P, P, L, P],
     "cwf_prepare_batch": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_prepare_batch_affine": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_window_gather": [P, P, P, I, I, P],
@@ -191,7 +194,8 @@ class WindowGrid(C.Structure):
 
 
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
-RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace"}
+RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
+                 "cwf_lesionwise_workspace"}
 
 _lib = None
 

@@ -1326,6 +1326,66 @@ class HipBackend:
         c = counts.double()
         return (2 * c[:3, 0] + 1e-8) / (c[:3, 1] + c[:3, 2] + 1e-8), (c[3:, 0] + 1e-8) / (c[3:, 1] + c[3:, 2] - c[3:, 0] + 1e-8)
 
+    # ------------------------------------------------------------------ N7 lesion-wise Dice and HD95
+    @staticmethod
+    def _region_bits_arg(name, bits):
+        if torch.is_tensor(bits) and bits.dtype == torch.bool:
+            bits = bits.view(torch.uint8)
+        if not torch.is_tensor(bits) or bits.dim() != 4 or bits.dtype != torch.uint8 or not bits.is_cuda or bits.numel() == 0:
+            raise ValueError("%s: bits must be a non-empty CUDA uint8 / bool tensor of shape [B, D0, D1, D2]" % name)
+        return bits.contiguous()
+
+    def dilate_bits(self, bits, connectivity=2, iterations=1):
+        """bits ([B, D0, D1, D2] uint8 region bits or bool) dilated `iterations` (0..8) times with the 6/18/26-neighbour footprint
+        (connectivity 1/2/3), every bit on its own, out-of-volume voxels unset: scipy.ndimage.binary_dilation(..., iterations) per bit
+        (cwf_dilate_bits).  Returns a new uint8 tensor.  No host synchronisation."""
+        bits = self._region_bits_arg("dilate_bits", bits)
+        if int(connectivity) not in (1, 2, 3):
+            raise ValueError("dilate_bits: connectivity must be 1, 2 or 3, got %r" % (connectivity,))
+        if not 0 <= int(iterations) <= 8:
+            raise ValueError("dilate_bits: iterations must lie in 0..8, got %r" % (iterations,))
+        nb, d0, d1, d2 = (int(s) for s in bits.shape)
+        out = torch.empty_like(bits)
+        ws = torch.empty(bits.numel() if int(iterations) >= 2 else 0, dtype=torch.uint8, device=bits.device)
+        self._call("cwf_dilate_bits", bits.data_ptr(), out.data_ptr(), nb, d0, d1, d2, int(connectivity), int(iterations),
+                   ws.data_ptr() if ws.numel() else None, ws.numel(), self._stream())
+        return out
+
+    def lesionwise(self, pred_bits, gt_bits, R, dilation=3, min_lesion_voxels=50, penalty=374.0):
+        """Lesion-wise Dice and HD95 of every sample and region r < R <= 8 of two [B, D0, D1, D2] uint8 region-bit tensors, as
+        predict_overlap.lesionwise_metrics defines them (cwf_lesionwise): -> (summary [B, R, 2] float64 = lw_dice, lw_hd95;
+        counts [B, R, 6] int64 = G, kept, matched components, FP, FN, P; overflow [B, R] int32; table [B, R, 64, 4] int64 = gt_vol,
+        pred_vol, inter, touching components per lesion; lesion_hd95 [B, R, 64] float64).  Where a (sample, region) has more than 64
+        lesions its overflow flag is 1 and its other outputs stay zero.  The call waits on the stream once (the lesion counts size the
+        HD95 launches), so it cannot be captured into a graph."""
+        pred_bits = self._region_bits_arg("lesionwise", pred_bits)
+        gt_bits = self._region_bits_arg("lesionwise", gt_bits)
+        if tuple(pred_bits.shape) != tuple(gt_bits.shape) or pred_bits.device != gt_bits.device:
+            raise ValueError("lesionwise: pred_bits and gt_bits must have one shape and device, got %r and %r"
+                             % (tuple(pred_bits.shape), tuple(gt_bits.shape)))
+        if not 1 <= int(R) <= 8:
+            raise ValueError("lesionwise: R must lie in 1..8, got %r" % (R,))
+        if not 0 <= int(dilation) <= 8:
+            raise ValueError("lesionwise: dilation must lie in 0..8, got %r" % (dilation,))
+        if int(min_lesion_voxels) < 0 or not 0.0 <= float(penalty) < 1e300:
+            raise ValueError("lesionwise: min_lesion_voxels and penalty must be >= 0 (and finite), got %r and %r"
+                             % (min_lesion_voxels, penalty))
+        nb, d0, d1, d2 = (int(s) for s in pred_bits.shape)
+        R, dev = int(R), pred_bits.device
+        nbytes = self.lib.cwf_lesionwise_workspace(nb, R, d0, d1, d2)
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_lesionwise_workspace failed with status %d (B=%d R=%d %dx%dx%d)" % (nbytes, nb, R, d0, d1, d2))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        summary = torch.zeros((nb, R, 2), dtype=torch.float64, device=dev)
+        counts = torch.zeros((nb, R, 6), dtype=torch.int64, device=dev)
+        overflow = torch.zeros((nb, R), dtype=torch.int32, device=dev)
+        table = torch.zeros((nb, R, 64, 4), dtype=torch.int64, device=dev)
+        lesion_hd95 = torch.zeros((nb, R, 64), dtype=torch.float64, device=dev)
+        self._call("cwf_lesionwise", pred_bits.data_ptr(), gt_bits.data_ptr(), nb, R, d0, d1, d2, int(dilation), int(min_lesion_voxels),
+                   float(penalty), summary.data_ptr(), counts.data_ptr(), overflow.data_ptr(), table.data_ptr(), lesion_hd95.data_ptr(),
+                   ws.data_ptr(), int(nbytes), self._stream())
+        return summary, counts, overflow, table, lesion_hd95
+
     # ------------------------------------------------------------------ N5 sliding-window inference over volumes of any size
     @staticmethod
     def window_grid(nb, shape, roi, starts):

@@ -24,6 +24,10 @@ Per chunk of windows: one gather launch, one model forward, one blend launch; on
 largest kept, small enhancing-tumour components and a tiny enhancing-tumour total relabelled (the ``postprocess=True`` switch of the
 reference's predictors, whose 500-voxel rule is the preset ``REFERENCE_POSTPROCESS``).  On the device: region bits -> component labelling
 -> policy (csrc/components.hip), no host synchronisation; CPU tensors go through numpy and scipy.ndimage.label.
+
+``lesionwise_metrics`` (N7): lesion-wise Dice and HD95, the numbers BraTS has ranked by since 2023 -- every ground-truth lesion scored on
+its own, every missed lesion and every spurious predicted component penalised.  On the device: region bits -> dilation -> two
+labellings -> touch / count passes -> HD95 of eight lesions per call -> aggregate (csrc/lesions.hip); CPU tensors go through numpy and scipy.
 """
 import itertools
 import math
@@ -194,7 +198,7 @@ def windows(starts):
 
 @torch.no_grad()
 def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False, with_hd95=False, window=None,
-                     postprocess=None):
+                     postprocess=None, lesionwise=None):
     """One subject: stitched probabilities -> label map (argmax; class 3 stands for BraTS label 4) -> [WT, TC, ET] Dice.
     ``deterministic`` zeroes the stem dropout that the reference leaves on in eval mode.  ``with_miou`` adds the per-class
     IoU list of tools.softmax_mIOU_score (what predict_simple.py reports next to Dice) as a fourth result.  ``with_hd95`` appends the
@@ -206,7 +210,9 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
     sliding_window_inference keyword arguments (roi_size, overlap, blend, sigma_scale, sw_batch_size) -- blended windows over a volume
     of any size, the target compared at the volume's own shape.
     ``postprocess``: None -- the label map is the plain argmax; a dict of `postprocess` keyword arguments (REFERENCE_POSTPROCESS is
-    one) -- ``seg`` is the processed map and Dice, IoU and HD95 are all computed from it (Dice as tools.softmax_output_dice gives it)."""
+    one) -- ``seg`` is the processed map and Dice, IoU and HD95 are all computed from it (Dice as tools.softmax_output_dice gives it).
+    ``lesionwise``: None -- the result tuple is as above; True or a dict of `lesionwise_metrics` keyword arguments -- the dict that
+    lesionwise_metrics(seg, target) returns for the final ``seg`` is appended as the last element (None without a target)."""
     model.eval()
     saved = model.Unet_list.InitConv.dropout
     if deterministic:
@@ -227,6 +233,9 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
         res = _revalidate(_apply_postprocess(res[0], postprocess), prob, target, with_miou, cut)
     if with_hd95:
         res = res + ((None if target is None else hd95_regions(res[0], target[..., :cut].long())),)
+    if lesionwise is not None and lesionwise is not False:
+        kw = {} if lesionwise is True else dict(lesionwise)
+        res = res + ((None if target is None else lesionwise_metrics(res[0], target[..., :cut].long().to(res[0].device), **kw)),)
     return res
 
 
@@ -349,3 +358,132 @@ def _postprocess_host(seg, min_component, keep_largest, et_min_component, et_min
             left = 0
         stats[b, 3] = left
     return out, stats
+
+
+LESIONWISE_MAX = 64            # CWF_LESIONWISE_MAX: lesions per (sample, region) on the device path
+
+
+def lesionwise_metrics(seg, target, dilation=3, min_lesion_voxels=50, penalty=374.0, with_table=False):
+    """Lesion-wise Dice and HD95 (the BraTS 2023 ranking metrics) of [B, D0, D1, D2] int64 label maps, per sample and region
+    (WT = label > 0, TC = label in {1, 3}, ET = label == 3).  For the binary masks pred, gt of one sample and region:
+      1  pred_cc = components of pred under the 26-neighbour footprint, numbered 1..P as scipy.ndimage.label numbers them
+      2  gt_dil = gt dilated `dilation` times with the 18-neighbour footprint (out-of-volume voxels unset; 0 leaves gt as it is)
+      3  dil_cc = 26-neighbour components of gt_dil, 1..G; lesion g = gt & (dil_cc == g): ground-truth parts whose dilations touch are
+         one lesion
+      4  component p touches lesion g if some voxel has pred_cc == p and dil_cc == g; a component may touch several lesions and counts
+         for each; pred_g = the union of the components touching g
+      5  per lesion gt_vol = |lesion g|, pred_vol = |pred_g|, inter = |pred_g & lesion g|; if nothing touches it, it is a false negative
+         with dice_g = 0 and hd95_g = penalty; otherwise dice_g = 2 inter / (pred_vol + gt_vol) and hd95_g = the HD95 of (pred_g,
+         lesion g) that this project computes everywhere (medpy's hd95 on 3-D surfaces, connectivity 1, unit spacing)
+      6  FP = predicted components touching no lesion (lesions below the volume threshold take part in the touching)
+      7  kept = lesions with gt_vol > min_lesion_voxels, n = |kept| + FP; lw_dice = sum over kept of dice_g / n and
+         lw_hd95 = (sum over kept of hd95_g + FP penalty) / n, summed in increasing g in float64; (1, 0) if n == 0 (both masks empty
+         included)
+    This follows the published BraTS 2023 lesion-wise procedure except that HD95 is this project's, not the challenge tool's
+    surface-distance library: parity is claimed with this definition only, not with the challenge tool's numbers.
+    Returns a dict: dice [B, 3] and hd95 [B, 3] float64, counts [B, 3, 6] int64 = G, kept, matched predicted components (P - FP), FP,
+    FN (kept lesions that nothing touches), P; with_table also table [B, 3, L, 4] int64 = gt_vol, pred_vol, inter, touching components
+    of lesion g at row g - 1 and lesion_hd95 [B, 3, L] float64 (zeros past G), L = 64 or the largest G if that is more.
+    CUDA tensors take the device path (backend().lesionwise): it needs one device-to-host readback of the B x 3 lesion counts, to
+    launch only the HD95 calls that hold a lesion, and this function reads the overflow flags back; a (sample, region) with more than 64
+    lesions is recomputed by the host path and patched in.  CPU tensors go through numpy and scipy.  Results are on seg's device."""
+    for name, t in (("seg", seg), ("target", target)):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.int64:
+            raise ValueError("lesionwise_metrics: %s must be an int64 tensor of shape [B, D0, D1, D2], got %s %s"
+                             % (name, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if tuple(seg.shape) != tuple(target.shape) or seg.numel() == 0:
+        raise ValueError("lesionwise_metrics: seg and target must have one non-empty shape, got %r and %r"
+                         % (tuple(seg.shape), tuple(target.shape)))
+    dilation, min_lesion_voxels, penalty = int(dilation), int(min_lesion_voxels), float(penalty)
+    if not 0 <= dilation <= 8:
+        raise ValueError("lesionwise_metrics: dilation must lie in 0..8, got %r" % (dilation,))
+    if min_lesion_voxels < 0 or not 0.0 <= penalty < 1e300:
+        raise ValueError("lesionwise_metrics: min_lesion_voxels and penalty must be >= 0 (and finite), got %r and %r"
+                         % (min_lesion_voxels, penalty))
+    nb = int(seg.shape[0])
+    if seg.is_cuda:
+        from cwf.kernels import backend
+        be = backend()
+        summary, counts, overflow, table, lesion_hd95 = be.lesionwise(be.region_bits(seg), be.region_bits(target.to(seg.device)), 3,
+                                                                      dilation, min_lesion_voxels, penalty)
+        over = overflow.cpu().numpy()
+        if over.any():
+            width = LESIONWISE_MAX
+            patches = []
+            for b in np.nonzero(over.any(axis=1))[0]:            # one copy to the host per overflowing sample
+                s, t = seg[b].cpu().numpy(), target[b].cpu().numpy()
+                for r in np.nonzero(over[b])[0]:
+                    masks = [(s > 0, t > 0), ((s == 1) | (s == 3), (t == 1) | (t == 3)), (s == 3, t == 3)][r]
+                    patches.append((int(b), int(r), _lesionwise_host(masks[0], masks[1], dilation, min_lesion_voxels, penalty)))
+                    width = max(width, patches[-1][2][2].shape[0])
+            if width > LESIONWISE_MAX:
+                table = torch.nn.functional.pad(table, (0, 0, 0, width - LESIONWISE_MAX))
+                lesion_hd95 = torch.nn.functional.pad(lesion_hd95, (0, width - LESIONWISE_MAX))
+            for b, r, (sm, cn, tb, lh) in patches:
+                summary[b, r] = torch.tensor(sm, dtype=torch.float64)
+                counts[b, r] = torch.tensor(cn, dtype=torch.int64)
+                table[b, r, :tb.shape[0]] = torch.from_numpy(tb).to(table.device)
+                lesion_hd95[b, r, :lh.shape[0]] = torch.from_numpy(lh).to(table.device)
+    else:
+        s, t = seg.numpy(), target.numpy()
+        res = [[_lesionwise_host(o, g, dilation, min_lesion_voxels, penalty) for o, g in zip(_regions(s[b]), _regions(t[b]))]
+               for b in range(nb)]
+        width = max([LESIONWISE_MAX] + [x[2].shape[0] for row in res for x in row])
+        summary = torch.tensor([[x[0] for x in row] for row in res], dtype=torch.float64)
+        counts = torch.tensor([[x[1] for x in row] for row in res], dtype=torch.int64)
+        table = torch.zeros((nb, 3, width, 4), dtype=torch.int64)
+        lesion_hd95 = torch.zeros((nb, 3, width), dtype=torch.float64)
+        for b, row in enumerate(res):
+            for r, x in enumerate(row):
+                table[b, r, :x[2].shape[0]] = torch.from_numpy(x[2])
+                lesion_hd95[b, r, :x[3].shape[0]] = torch.from_numpy(x[3])
+    out = {"dice": summary[..., 0].contiguous(), "hd95": summary[..., 1].contiguous(), "counts": counts}
+    if with_table:
+        out["table"], out["lesion_hd95"] = table, lesion_hd95
+    return out
+
+
+def _regions(labels):
+    return [labels > 0, (labels == 1) | (labels == 3), labels == 3]
+
+
+def _hd95_host(a, b):
+    """medpy's hd95 (connectivity 1, unit spacing) of two non-empty 3-D masks with scipy, on the bounding box of a | b grown by one
+    voxel inside the volume: every border voxel of either mask lies in it, and what lies beyond it is unset in both."""
+    from scipy import ndimage
+    box = tuple(slice(max(int(i.min()) - 1, 0), int(i.max()) + 2) for i in np.nonzero(a | b))
+    a, b = a[box], b[box]
+    ba, bb = a & ~ndimage.binary_erosion(a), b & ~ndimage.binary_erosion(b)
+    d = np.hstack((ndimage.distance_transform_edt(~bb)[ba], ndimage.distance_transform_edt(~ba)[bb]))
+    return float(np.percentile(d, 95))
+
+
+def _lesionwise_host(pred, gt, dilation, min_lesion_voxels, penalty):
+    """One sample and region on the host: ((lw_dice, lw_hd95), counts [6], table [G, 4] int64, lesion_hd95 [G] float64)."""
+    from scipy import ndimage                                   # only the CPU path needs scipy
+    full = ndimage.generate_binary_structure(3, 3)
+    pred_cc, npred = ndimage.label(pred, structure=full)
+    gt_dil = ndimage.binary_dilation(gt, ndimage.generate_binary_structure(3, 2), iterations=dilation) if dilation > 0 else gt
+    dil_cc, ng = ndimage.label(gt_dil, structure=full)
+    sizes = np.bincount(pred_cc.ravel(), minlength=npred + 1)
+    pairs = np.unique(np.stack([pred_cc[(pred_cc > 0) & (dil_cc > 0)], dil_cc[(pred_cc > 0) & (dil_cc > 0)]]), axis=1)
+    gt_vol = np.bincount(dil_cc[gt], minlength=ng + 1)
+    inter = np.bincount(dil_cc[gt & pred], minlength=ng + 1)
+    table = np.zeros((ng, 4), dtype=np.int64)
+    hd = np.zeros(ng, dtype=np.float64)
+    sdice = shd = 0.0
+    kept = fn = 0
+    for g in range(1, ng + 1):
+        comps = pairs[0][pairs[1] == g]
+        table[g - 1] = (gt_vol[g], sizes[comps].sum(), inter[g], len(comps))
+        if len(comps):
+            dice = 2.0 * float(inter[g]) / float(table[g - 1, 1] + gt_vol[g])
+            hd[g - 1] = _hd95_host(np.isin(pred_cc, comps), gt & (dil_cc == g))
+        else:
+            dice, hd[g - 1] = 0.0, penalty
+        if gt_vol[g] > min_lesion_voxels:
+            sdice, shd, kept, fn = sdice + dice, shd + hd[g - 1], kept + 1, fn + (len(comps) == 0)
+    fp = npred - len(np.unique(pairs[0]))
+    n = kept + fp
+    summary = (sdice / n, (shd + fp * penalty) / n) if n else (1.0, 0.0)
+    return summary, (ng, kept, npred - fp, fp, fn, npred), table, hd

@@ -464,6 +464,44 @@ int cwf_postprocess_labels(const int64_t* seg_in, int64_t* seg_out, const int32_
 int cwf_label_metrics(const int64_t* seg, const int64_t* target, uint64_t* counts, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * N7  lesion-wise Dice and HD95 (the BraTS 2023 ranking metrics; predict_overlap.lesionwise_metrics states the definition):
+ *     binary dilation of region bits, and the per-lesion matching, counts, surface distances and aggregate built on
+ *     cwf_components and cwf_hausdorff.  All integer up to the per-lesion ratios; the aggregate is float64.
+ * ---------------------------------------------------------------------------------------------- */
+/* out[B][D0][D1][D2] <- bits dilated `iterations` (0..8) times with the 6/18/26-neighbour footprint (connectivity 1/2/3), every bit
+ * of the byte on its own and out-of-volume voxels unset: scipy.ndimage.binary_dilation(..., iterations) per bit.  0 iterations copy.
+ * bits and out are distinct buffers.  ws: B * D0 * D1 * D2 bytes, distinct from both, needed from 2 iterations on (else may be
+ * null).  CWF_E_BADARG: a null or aliased pointer, B or an extent <= 0, B > 65535, connectivity or iterations out of range;
+ * CWF_E_TOOLARGE: 2^31 voxels or more, or ws_bytes too small. */
+int cwf_dilate_bits(const uint8_t* bits, uint8_t* out, int B, int D0, int D1, int D2, int connectivity, int iterations, void* ws,
+                    int64_t ws_bytes, void* stream);
+/* Bytes of device workspace cwf_lesionwise needs (256-B aligned; about 4 bytes per voxel and sample plus 14 per voxel, sample and
+ * region, plus the larger of the cwf_components (B, R) and cwf_hausdorff (B, 8) workspaces), or a negative CWF_E_* as those two
+ * give it. */
+int64_t cwf_lesionwise_workspace(int B, int R, int D0, int D1, int D2);
+#define CWF_LESIONWISE_MAX 64
+/* For every sample b and region r < R <= 8 of the region bits pred, gt [B][D0][D1][D2]:
+ *   pred_cc = 26-neighbour components of pred, 1..P;  dil_cc = 26-neighbour components of gt dilated `dilation` (0..8) times with the
+ *   18-neighbour footprint, 1..G;  lesion g = gt & (dil_cc == g);  component p touches lesion g if a voxel has pred_cc == p and
+ *   dil_cc == g;  pred_g = the union of the components touching g.  Per lesion: gt_vol, pred_vol = |pred_g|, inter = |pred_g & lesion g|,
+ *   dice_g = 2 inter / (pred_vol + gt_vol) and hd95_g = cwf_hausdorff's hd95 of (pred_g, lesion g) (unit spacing, connectivity 1), or
+ *   0 and `penalty` if nothing touches it.  FP = components touching no lesion; kept = lesions with gt_vol > min_lesion_voxels;
+ *   n = kept + FP.
+ *   summary[b][r][2]      lw_dice = sum over kept of dice_g / n, lw_hd95 = (sum over kept of hd95_g + FP * penalty) / n, summed in
+ *                         increasing g in float64; (1, 0) if n == 0
+ *   counts[b][r][6]       G, kept, matched components (P - FP), FP, FN (kept lesions that nothing touches), P
+ *   overflow[b][r]        1 if G > CWF_LESIONWISE_MAX: every other output of that (b, r) is then left untouched; else 0
+ *   table[b][r][64][4]    gt_vol, pred_vol, inter, touching components of lesion g at row g - 1; rows >= G are 0
+ *   lesion_hd95[b][r][64] hd95_g (penalty for a lesion nothing touches); entries >= G are 0
+ * ws: cwf_lesionwise_workspace(...) bytes, 256-B aligned.  The call waits on the stream once, to read the B * R lesion counts that
+ * size the cwf_hausdorff calls (eight lesions per call), so it cannot be captured into a graph.  No kernel waits on another workgroup.
+ * CWF_E_BADARG: a null pointer, R > 8, B, R or an extent <= 0, dilation outside 0..8, a negative min_lesion_voxels, a negative or
+ * non-finite penalty; CWF_E_TOOLARGE: 2^31 voxels or more, D2 > 4096, B * R > 65535 or ws_bytes too small. */
+int cwf_lesionwise(const uint8_t* pred, const uint8_t* gt, int B, int R, int D0, int D1, int D2, int dilation, int64_t min_lesion_voxels,
+                   double penalty, double* summary, int64_t* counts, int32_t* overflow, int64_t* table, double* lesion_hd95, void* ws,
+                   int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N5  sliding-window inference over volumes of any size (predict_overlap.sliding_window_inference): overlapping r0 x r1 x r2
  *     windows on a Cartesian grid of starts, blended with a separable importance map.
  * ---------------------------------------------------------------------------------------------- */

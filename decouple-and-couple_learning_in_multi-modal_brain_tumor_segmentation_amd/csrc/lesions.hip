@@ -17,11 +17,17 @@
 // Every accumulation is an integer add or a bitwise OR, so no output depends on the order in which atomics land.  No kernel waits on
 // another workgroup.  The host reads the lesion counts back once (B * R ints) to size the HD95 calls.  This file is compiled with
 // -ffp-contract=off: the aggregate is formed operation by operation as the float64 restatement forms it.
+//
+// cwf_lesionwise_ex adds the lesion-wise normalised surface Dice at T <= 4 tolerances: it calls cwf_surface_metrics where
+// cwf_lesionwise calls cwf_hausdorff (same masks, eight lesions per call), takes nsd_g of (pred_g, lesion g) from it -- 0 for a lesion
+// nothing touches -- and lw_final_kernel forms lw_nsd[t] = (sum over kept lesions of nsd_g[t]) / (kept + FP) in increasing g, 1 if
+// kept + FP == 0, as it forms lw_dice.  Every nsd_g is a ratio of two integers, so lw_nsd does not depend on the order of atomics either.
 #include <algorithm>
 #include <vector>
 #include "common.h"
 
 #define LW_MAX 64             // lesions per (sample, region) on the device: one bit of a touch word each
+#define LW_MAX_TAU 4          // tolerances of cwf_lesionwise_ex (cwf_surface_metrics' limit)
 
 // out = in dilated once; one thread per voxel, one sample per blockIdx.y.  Out-of-volume voxels are unset.
 __global__ __launch_bounds__(256) void lw_dilate_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int D0, int D1, int D2,
@@ -186,13 +192,15 @@ struct LwFinal {
 };
 
 // One workgroup of LW_MAX threads per (sample, region).  hd95 of lesion g = 8 k + j was written by the call for (r, k) at
-// hdt[(r * 8 + k) * B * 8 + b * Rk + j], Rk = min(8, maxg[r] - 8 k) regions in that call.
+// hdt[(r * 8 + k) * B * 8 + b * Rk + j], Rk = min(8, maxg[r] - 8 k) regions in that call; its nsd, with T > 0, at
+// nsdt[((r * 8 + k) * B * 8 + b * Rk + j) * T + t].  With T == 0 nsdt, lesion_nsd and lw_nsd are not touched.
 __global__ __launch_bounds__(LW_MAX) void lw_final_kernel(const unsigned long long* __restrict__ acc, const unsigned long long* __restrict__ fp,
                                                           const int* __restrict__ pcount, const int* __restrict__ dcount,
                                                           const double* __restrict__ hdt, LwFinal a, double* __restrict__ summary,
                                                           int64_t* __restrict__ counts, int* __restrict__ overflow, int64_t* __restrict__ table,
-                                                          double* __restrict__ lesion_hd95) {
-  __shared__ double sd[LW_MAX], sh[LW_MAX];
+                                                          double* __restrict__ lesion_hd95, const double* __restrict__ nsdt, int T,
+                                                          double* __restrict__ lesion_nsd, double* __restrict__ lw_nsd) {
+  __shared__ double sd[LW_MAX], sh[LW_MAX], sn[LW_MAX_TAU][LW_MAX];
   __shared__ int keep[LW_MAX], miss[LW_MAX];
   const int br = blockIdx.x, b = br / a.R, r = br % a.R, g = threadIdx.x;
   const int G = dcount[br];
@@ -202,7 +210,7 @@ __global__ __launch_bounds__(LW_MAX) void lw_final_kernel(const unsigned long lo
   }
   const unsigned long long* t = acc + ((int64_t)br * LW_MAX + g) * 4;
   const long long gv = (long long)t[0], pv = (long long)t[1], in = (long long)t[2], nt = (long long)t[3];
-  double dice = 0.0, hd = 0.0;
+  double dice = 0.0, hd = 0.0, ns[LW_MAX_TAU] = {0.0, 0.0, 0.0, 0.0};
   if (g < G) {
     if (nt == 0) {
       hd = a.penalty;
@@ -210,9 +218,14 @@ __global__ __launch_bounds__(LW_MAX) void lw_final_kernel(const unsigned long lo
       const int k = g >> 3, j = g & 7, rk = min(8, a.maxg[r] - 8 * k);
       dice = (double)(2 * in) / (double)(pv + gv);
       hd = hdt[((int64_t)r * 8 + k) * a.B * 8 + (int64_t)b * rk + j];
+      for (int t = 0; t < T; ++t) ns[t] = nsdt[(((int64_t)r * 8 + k) * a.B * 8 + (int64_t)b * rk + j) * T + t];
     }
   }
   sd[g] = dice; sh[g] = hd;
+  for (int t = 0; t < T; ++t) {
+    sn[t][g] = ns[t];
+    lesion_nsd[((int64_t)br * LW_MAX + g) * T + t] = ns[t];
+  }
   keep[g] = g < G && gv > a.min_lesion;
   miss[g] = g < G && gv > a.min_lesion && nt == 0;
   int64_t* row = table + ((int64_t)br * LW_MAX + g) * 4;
@@ -228,6 +241,12 @@ __global__ __launch_bounds__(LW_MAX) void lw_final_kernel(const unsigned long lo
   const long long n = kept + nfp;
   summary[br * 2 + 0] = n ? sdice / (double)n : 1.0;
   summary[br * 2 + 1] = n ? (shd + (double)nfp * a.penalty) / (double)n : 0.0;
+  for (int t = 0; t < T; ++t) {
+    double snsd = 0.0;
+    for (int i = 0; i < G; ++i)
+      if (keep[i]) snsd += sn[t][i];
+    lw_nsd[br * T + t] = n ? snsd / (double)n : 1.0;
+  }
   int64_t* c = counts + (int64_t)br * 6;
   c[0] = G; c[1] = kept; c[2] = P - nfp; c[3] = nfp; c[4] = fn; c[5] = P;
   overflow[br] = 0;
@@ -239,12 +258,13 @@ static inline int64_t lw_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
 // [B][R][cap] ints | touch [B][R][cap] uint64 (first the sizes output of the second labelling, which nothing reads) | pred count, dilated
 // count [B][R], largest [B][R][2] ints | acc [B][R][64][4], fp [B][R] uint64 | packed a, b [B][V] | hd95 per call [R][8][B][8], hd
 // scratch [B][8] doubles, counts scratch [B][8][4] int64 | the workspace of cwf_components or of cwf_hausdorff, whichever is larger
-// (they are used one after the other on one stream)
-struct LwLayout { int64_t dil, tmp, plab, dlab, psizes, touch, pcount, dcount, largest, acc, fp, pa, pb, hdt, hds, hdc, sub, sub_bytes, total; };
-static int lw_layout(int B, int R, int D0, int D1, int D2, LwLayout& L) {
+// (they are used one after the other on one stream).  cwf_lesionwise_ex: nsd per call [R][8][B][8][4] and asd [B][8][2], assd [B][8],
+// within [B][8][4][2] scratch go before the last block, which then holds cwf_surface_metrics' workspace in cwf_hausdorff's place.
+struct LwLayout { int64_t dil, tmp, plab, dlab, psizes, touch, pcount, dcount, largest, acc, fp, pa, pb, hdt, hds, hdc, nsdt, asd, assd, within, sub, sub_bytes, total; };
+static int lw_layout(int B, int R, int D0, int D1, int D2, bool ex, LwLayout& L) {
   const int64_t cc = cwf_components_workspace(B, R, D0, D1, D2);
   if (cc < 0) return (int)cc;
-  const int64_t hd = cwf_hausdorff_workspace(B, 8, D0, D1, D2);
+  const int64_t hd = ex ? cwf_surface_metrics_workspace(B, 8, D0, D1, D2) : cwf_hausdorff_workspace(B, 8, D0, D1, D2);
   if (hd < 0) return (int)hd;
   const int64_t V = (int64_t)D0 * D1 * D2, cap = (V + 1) / 2, BR = (int64_t)B * R;
   L.dil = 0;
@@ -263,7 +283,14 @@ static int lw_layout(int B, int R, int D0, int D1, int D2, LwLayout& L) {
   L.hdt = lw_align(L.pb + B * V);
   L.hds = lw_align(L.hdt + (int64_t)R * 8 * B * 8 * 8);
   L.hdc = lw_align(L.hds + (int64_t)B * 8 * 8);
-  L.sub = lw_align(L.hdc + (int64_t)B * 8 * 4 * 8);
+  L.nsdt = lw_align(L.hdc + (int64_t)B * 8 * 4 * 8);
+  L.asd = L.assd = L.within = L.sub = L.nsdt;
+  if (ex) {
+    L.asd = lw_align(L.nsdt + (int64_t)R * 8 * B * 8 * LW_MAX_TAU * 8);
+    L.assd = lw_align(L.asd + (int64_t)B * 8 * 2 * 8);
+    L.within = lw_align(L.assd + (int64_t)B * 8 * 8);
+    L.sub = lw_align(L.within + (int64_t)B * 8 * LW_MAX_TAU * 2 * 8);
+  }
   L.sub_bytes = std::max(cc, hd);
   L.total = lw_align(L.sub + L.sub_bytes);
   return 0;
@@ -271,17 +298,30 @@ static int lw_layout(int B, int R, int D0, int D1, int D2, LwLayout& L) {
 
 extern "C" int64_t cwf_lesionwise_workspace(int B, int R, int D0, int D1, int D2) {
   LwLayout L;
-  const int rc = lw_layout(B, R, D0, D1, D2, L);
+  const int rc = lw_layout(B, R, D0, D1, D2, false, L);
   return rc ? rc : L.total;
 }
 
-extern "C" int cwf_lesionwise(const uint8_t* pred, const uint8_t* gt, int B, int R, int D0, int D1, int D2, int dilation,
-                              int64_t min_lesion_voxels, double penalty, double* summary, int64_t* counts, int32_t* overflow, int64_t* table,
-                              double* lesion_hd95, void* ws, int64_t ws_bytes, void* stream) {
+extern "C" int64_t cwf_lesionwise_ex_workspace(int B, int R, int D0, int D1, int D2) {
   LwLayout L;
-  int rc = lw_layout(B, R, D0, D1, D2, L);
+  const int rc = lw_layout(B, R, D0, D1, D2, true, L);
+  return rc ? rc : L.total;
+}
+
+// cwf_lesionwise (ex == false: the workspace of cwf_lesionwise_workspace, cwf_hausdorff per group of lesions, T == 0) and
+// cwf_lesionwise_ex (the workspace of cwf_lesionwise_ex_workspace, cwf_surface_metrics per group)
+static int lw_run(const uint8_t* pred, const uint8_t* gt, int B, int R, int D0, int D1, int D2, int dilation, int64_t min_lesion_voxels,
+                  double penalty, bool ex, const double* tau, int T, double* summary, int64_t* counts, int32_t* overflow, int64_t* table,
+                  double* lesion_hd95, double* lesion_nsd, double* lw_nsd, void* ws, int64_t ws_bytes, void* stream) {
+  LwLayout L;
+  int rc = lw_layout(B, R, D0, D1, D2, ex, L);
   if (rc) return rc;
   if (!pred || !gt || !summary || !counts || !overflow || !table || !lesion_hd95 || !ws) return CWF_E_BADARG;
+  if (ex) {
+    if (T < 0 || T > LW_MAX_TAU || (T > 0 && (!tau || !lesion_nsd || !lw_nsd))) return CWF_E_BADARG;
+    for (int t = 0; t < T; ++t)
+      if (!(tau[t] >= 0.0)) return CWF_E_BADARG;
+  }
   if (dilation < 0 || dilation > 8 || min_lesion_voxels < 0 || !(penalty >= 0.0 && penalty < 1e300)) return CWF_E_BADARG;
   if (ws_bytes < L.total) return CWF_E_TOOLARGE;
   if ((uintptr_t)ws & 255) return CWF_E_ALIGN;
@@ -304,6 +344,7 @@ extern "C" int cwf_lesionwise(const uint8_t* pred, const uint8_t* gt, int B, int
   double* hdt = (double*)(w + L.hdt);
   double* hds = (double*)(w + L.hds);
   int64_t* hdc = (int64_t*)(w + L.hdc);
+  double* nsdt = (double*)(w + L.nsdt);
   void* sub = w + L.sub;
 
   rc = cwf_dilate_bits(gt, dil, B, D0, D1, D2, 2, dilation, w + L.tmp, (int64_t)B * V, stream);
@@ -343,11 +384,32 @@ extern "C" int cwf_lesionwise(const uint8_t* pred, const uint8_t* gt, int B, int
       hipLaunchKernelGGL(lw_pack_kernel, dim3((unsigned)cdiv64(V, 256), B), dim3(256), 0, st, gt, (const int*)plab, (const int*)dlab,
                          (const int*)dcount, (const unsigned long long*)touch, pa, pb, R, r, k, V, cap);
       CWF_LAUNCH_CHECK();
-      rc = cwf_hausdorff(pa, pb, B, rk, D0, D1, D2, 1.0, 1.0, 1.0, 1, 0, hds, hdt + ((int64_t)r * 8 + k) * B * 8, hdc, sub, L.sub_bytes, stream);
+      const int64_t o = ((int64_t)r * 8 + k) * B * 8;
+      if (ex)
+        rc = cwf_surface_metrics(pa, pb, B, rk, D0, D1, D2, 1.0, 1.0, 1.0, 1, 0, tau, T, hds, hdt + o, (double*)(w + L.asd), (double*)(w + L.assd),
+                                 (int64_t*)(w + L.within), nsdt + o * T, hdc, sub, L.sub_bytes, stream);
+      else
+        rc = cwf_hausdorff(pa, pb, B, rk, D0, D1, D2, 1.0, 1.0, 1.0, 1, 0, hds, hdt + o, hdc, sub, L.sub_bytes, stream);
       if (rc) return rc;
     }
   hipLaunchKernelGGL(lw_final_kernel, dim3(BR), dim3(LW_MAX), 0, st, (const unsigned long long*)acc, (const unsigned long long*)fp,
-                     (const int*)pcount, (const int*)dcount, (const double*)hdt, fa, summary, counts, overflow, table, lesion_hd95);
+                     (const int*)pcount, (const int*)dcount, (const double*)hdt, fa, summary, counts, overflow, table, lesion_hd95,
+                     (const double*)nsdt, T, lesion_nsd, lw_nsd);
   CWF_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int cwf_lesionwise(const uint8_t* pred, const uint8_t* gt, int B, int R, int D0, int D1, int D2, int dilation,
+                              int64_t min_lesion_voxels, double penalty, double* summary, int64_t* counts, int32_t* overflow, int64_t* table,
+                              double* lesion_hd95, void* ws, int64_t ws_bytes, void* stream) {
+  return lw_run(pred, gt, B, R, D0, D1, D2, dilation, min_lesion_voxels, penalty, false, nullptr, 0, summary, counts, overflow, table,
+                lesion_hd95, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int cwf_lesionwise_ex(const uint8_t* pred, const uint8_t* gt, int B, int R, int D0, int D1, int D2, int dilation,
+                                 int64_t min_lesion_voxels, double penalty, const double* tau, int T, double* summary, int64_t* counts,
+                                 int32_t* overflow, int64_t* table, double* lesion_hd95, double* lesion_nsd, double* lw_nsd, void* ws,
+                                 int64_t ws_bytes, void* stream) {
+  return lw_run(pred, gt, B, R, D0, D1, D2, dilation, min_lesion_voxels, penalty, true, tau, T, summary, counts, overflow, table, lesion_hd95,
+                lesion_nsd, lw_nsd, ws, ws_bytes, stream);
 }

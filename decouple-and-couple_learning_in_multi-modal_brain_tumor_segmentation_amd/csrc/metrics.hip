@@ -18,6 +18,22 @@
 // Every term is formed as (s * d)^2 and summed in axis order 0, 1, 2, exactly as scipy's distance_transform_edt, and the minimum
 // commutes with the monotone rounding of each addition, so the result is the correctly rounded minimum over all border voxels: with unit
 // spacing every value is an exact integer.  This file is compiled with -ffp-contract=off (no fused multiply-adds).
+//
+// N8 -- normalised surface Dice and average surface distance (cwf_surface_metrics), on the same border / EDT / gather / select kernels.
+// With q the float64 squared distance above and d(p) = sqrt(q), correctly rounded, for p in dA (to dB) and for p in dB (to dA):
+//   within[t][0] = |{p in dA : d(p) <= tau_t}|, within[t][1] the same over dB          (a float64 <= on d)
+//   nsd[t]       = (within[t][0] + within[t][1]) / (|dA| + |dB|)                        (one float64 division of two exact integers)
+//   asd[0]       = mean of d over dA, asd[1] = mean of d over dB (medpy asd(A, B), asd(B, A));  assd = (asd[0] + asd[1]) / 2 (medpy assd)
+//   either mask empty: every float output of that (sample, region) is NaN and within is 0, as for hd / hd95.
+// This is the voxel-border NSD (MONAI's compute_surface_dice without sub-voxel handling), not the area-weighted surface-element form of
+// DeepMind's surface-distance; with unit spacing every tau < 1 counts coincident border voxels only (d is 0 or >= 1).
+// The compact array is filled through an atomic cursor and mixes both directions, so neither output is taken from it.  The surface
+// variant of hd_edt_gather_kernel (one wave per line) instead leaves, per line and direction, the sum of d and the T counts in a slot
+// of their own: lane l adds its voxels l, l + 64, ... in increasing order, the 64 lane sums go through a fixed xor butterfly, and a line
+// without a gather voxel writes zeros.  hd_surface_final_kernel then adds the D0 * D1 slots of a direction with 512 threads, thread i
+// taking slots i, i + 512, ... in increasing order, and a fixed binary tree over the 512 partial sums.  Every addition has fixed
+// operands whatever order workgroups run or atomics land in, and the shape depends on D0, D1, D2 alone, so asd is bit-identical from
+// run to run and from batch to batch; the counts are integers.
 #include <algorithm>
 #include "common.h"
 
@@ -28,6 +44,15 @@ struct HdSmall {              // per (sample, region) scratch, zeroed by cwf_hau
   unsigned long long hdmax;   // max squared distance, as its bit pattern
   unsigned long long state[9][2][2];    // radix select: (prefix, remaining rank) of the two target ranks before pass p
   unsigned int hist[8][2][256];         // digit histograms of pass p for the two target ranks
+};
+
+#define HD_MAX_TAU 4          // tolerances per cwf_surface_metrics call
+
+struct HdSurface {            // what the surface variant of the gather pass adds; passed by value
+  double tau[HD_MAX_TAU];
+  int T;
+  double* lsum;               // [2][D0 * D1]: per direction and line, the sum of d over the line's gather voxels
+  unsigned int* lcnt;         // [2][D0 * D1][HD_MAX_TAU]: the line's voxels with d <= tau[t]
 };
 
 __device__ __forceinline__ double hd_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
@@ -134,9 +159,11 @@ __global__ __launch_bounds__(256) void hd_edt_axis0_kernel(const uint8_t* __rest
 // dA, t = 1 that of dA at dB.  Lines without a gather voxel leave at once.  Both minimum passes search outward from q and stop at the
 // first offset k whose own term (s k)^2 already reaches the best value found: every farther candidate is at least that large, as the
 // rounding of s * k, of its square and of g + (s k)^2 is monotone and g >= 0.
+// SURF: also the line's slot of sv.lsum / sv.lcnt (see the header); without it sv is not touched and the code is what it was.
+template <bool SURF>
 __global__ __launch_bounds__(64) void hd_edt_gather_kernel(const uint8_t* __restrict__ ba, const uint8_t* __restrict__ bb, int r, int D0, int D1,
                                                            int D2, double s1, double s2, const double* __restrict__ g, const int* __restrict__ range,
-                                                           double* __restrict__ compact, int64_t cap, HdSmall* __restrict__ sm) {
+                                                           double* __restrict__ compact, int64_t cap, HdSmall* __restrict__ sm, HdSurface sv) {
   extern __shared__ double line[];                 // [D2]
   const int t = blockIdx.y;
   const int64_t plane = (int64_t)D1 * D2, V = (int64_t)D0 * plane;
@@ -150,7 +177,13 @@ __global__ __launch_bounds__(64) void hd_edt_gather_kernel(const uint8_t* __rest
   const int lane = threadIdx.x;
   bool any = false;
   for (int i2 = lane; i2 < D2; i2 += 64) any |= ((gm[i2] >> r) & 1) != 0;
-  if (!__any(any)) return;
+  if (!__any(any)) {
+    if constexpr (SURF) {
+      if (lane == 0) sv.lsum[(int64_t)t * D0 * D1 + lidx] = 0.0;
+      if (lane < HD_MAX_TAU) sv.lcnt[((int64_t)t * D0 * D1 + lidx) * HD_MAX_TAU + lane] = 0u;
+    }
+    return;
+  }
   const double inf = hd_inf();
   // axis 1: g1(i0, i1, i2) = min_p g0(i0, p, i2) + (s1 (i1 - p))^2 over the columns p in [lo, hi] that hold a border voxel
   for (int i2 = lane; i2 < D2; i2 += 64) {
@@ -172,6 +205,8 @@ __global__ __launch_bounds__(64) void hd_edt_gather_kernel(const uint8_t* __rest
   __syncthreads();
   // axis 2 at the gather voxels, appended to the compact array
   unsigned long long mx = 0;
+  double dsum = 0.0;                               // SURF: this lane's sum of d and counts of d <= tau[t]
+  unsigned int dcnt[HD_MAX_TAU] = {0u, 0u, 0u, 0u};
   for (int base = 0; base < D2; base += 64) {
     const int q = base + lane;
     const bool on = q < D2 && ((gm[q] >> r) & 1);
@@ -196,6 +231,27 @@ __global__ __launch_bounds__(64) void hd_edt_gather_kernel(const uint8_t* __rest
       compact[slot] = best;
       const unsigned long long bits = (unsigned long long)__double_as_longlong(best);
       mx = bits > mx ? bits : mx;
+    }
+    if constexpr (SURF) {
+      if (on) {
+        const double d = sqrt(best);
+        dsum += d;
+#pragma unroll
+        for (int j = 0; j < HD_MAX_TAU; ++j) dcnt[j] += (j < sv.T && d <= sv.tau[j]) ? 1u : 0u;
+      }
+    }
+  }
+  if constexpr (SURF) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      dsum += __shfl_xor(dsum, o, 64);
+#pragma unroll
+      for (int j = 0; j < HD_MAX_TAU; ++j) dcnt[j] += __shfl_xor(dcnt[j], o, 64);
+    }
+    if (lane == 0) {
+      sv.lsum[(int64_t)t * D0 * D1 + lidx] = dsum;
+#pragma unroll
+      for (int j = 0; j < HD_MAX_TAU; ++j) sv.lcnt[((int64_t)t * D0 * D1 + lidx) * HD_MAX_TAU + j] = dcnt[j];
     }
   }
 #pragma unroll
@@ -296,10 +352,67 @@ __global__ __launch_bounds__(256) void hd_radix_kernel(const unsigned long long*
     if (lh[t][tid]) atomicAdd(&sm->hist[pass][t][tid], lh[t][tid]);
 }
 
+// cwf_surface_metrics zeroes counts and the HdSmall / range part of the workspace with this kernel, not with memset nodes: in a captured
+// graph the runtime's node for the small memset of counts was seen to write a wrong pattern from the second replay on.  n0, n1: 8-byte words.
+__global__ __launch_bounds__(256) void hd_zero_kernel(unsigned long long* __restrict__ p0, int64_t n0, unsigned long long* __restrict__ p1,
+                                                      int64_t n1) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n0 + n1; i += (int64_t)gridDim.x * 256) {
+    if (i < n0) p0[i] = 0ull;
+    else p1[i - n0] = 0ull;
+  }
+}
+
+// One workgroup of 1024 threads per (sample, region), after the gather pass: threads 0..511 add the line slots of direction 0 (dA to
+// dB), threads 512..1023 those of direction 1, thread i taking slots i, i + 512, ... in increasing order; then a binary tree over the
+// 512 partial sums of each half.  The operands of every addition are fixed by L = D0 * D1 alone.  c = |dA|, |dB|.
+__global__ __launch_bounds__(1024) void hd_surface_final_kernel(HdSurface sv, int64_t L, const unsigned long long* __restrict__ c,
+                                                                double* __restrict__ asd, double* __restrict__ assd,
+                                                                long long* __restrict__ within, double* __restrict__ nsd) {
+  __shared__ double ss[1024];
+  __shared__ unsigned long long sc[HD_MAX_TAU][1024];
+  const int tid = threadIdx.x, dir = tid >> 9, i = tid & 511;
+  const double* ls = sv.lsum + (int64_t)dir * L;
+  const uint4* lc = reinterpret_cast<const uint4*>(sv.lcnt) + (int64_t)dir * L;
+  double a = 0.0;
+  unsigned long long n[HD_MAX_TAU] = {0ull, 0ull, 0ull, 0ull};
+  for (int64_t l = i; l < L; l += 512) {
+    a += ls[l];
+    if (sv.T > 0) {
+      const uint4 k = lc[l];
+      n[0] += k.x; n[1] += k.y; n[2] += k.z; n[3] += k.w;
+    }
+  }
+  ss[tid] = a;
+#pragma unroll
+  for (int j = 0; j < HD_MAX_TAU; ++j) sc[j][tid] = n[j];
+  __syncthreads();
+  for (int o = 256; o > 0; o >>= 1) {
+    if (i < o) {
+      ss[tid] += ss[tid + o];
+#pragma unroll
+      for (int j = 0; j < HD_MAX_TAU; ++j) sc[j][tid] += sc[j][tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const unsigned long long na = c[0], nb = c[1];
+  const bool empty = na == 0 || nb == 0;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double a0 = empty ? nan : ss[0] / (double)na, a1 = empty ? nan : ss[512] / (double)nb;
+  asd[0] = a0; asd[1] = a1;
+  *assd = empty ? nan : (a0 + a1) / 2.0;
+  for (int j = 0; j < sv.T; ++j) {
+    const unsigned long long w0 = empty ? 0ull : sc[j][0], w1 = empty ? 0ull : sc[j][512];
+    within[j * 2 + 0] = (long long)w0; within[j * 2 + 1] = (long long)w1;
+    nsd[j] = empty ? nan : (double)(w0 + w1) / (double)(na + nb);
+  }
+}
+
 static inline int64_t hd_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 // Workspace layout: border bytes [2][B][V] | g [2][V] doubles | compact [2V] doubles | HdSmall [B][R] | range [B][R][4][D2] ints
-struct HdLayout { int64_t border, g, compact, small, range, total; };
+// cwf_surface_metrics appends: line sums [2][D0 D1] doubles | line counts [2][D0 D1][HD_MAX_TAU] uints
+struct HdLayout { int64_t border, g, compact, small, range, total, lsum, lcnt, total_surface; };
 static int hd_layout(int B, int R, int D0, int D1, int D2, HdLayout& L) {
   if (B <= 0 || R <= 0 || R > 8 || D0 <= 0 || D1 <= 0 || D2 <= 0) return CWF_E_BADARG;
   if (D2 > HD_MAX_D2) return CWF_E_TOOLARGE;
@@ -311,6 +424,9 @@ static int hd_layout(int B, int R, int D0, int D1, int D2, HdLayout& L) {
   L.small = hd_align(L.compact + 2 * V * 8);
   L.range = hd_align(L.small + (int64_t)B * R * (int64_t)sizeof(HdSmall));
   L.total = hd_align(L.range + (int64_t)B * R * 4 * D2 * 4);
+  L.lsum = L.total;
+  L.lcnt = hd_align(L.lsum + 2 * (int64_t)D0 * D1 * 8);
+  L.total_surface = hd_align(L.lcnt + 2 * (int64_t)D0 * D1 * HD_MAX_TAU * 4);
   return 0;
 }
 
@@ -320,6 +436,12 @@ extern "C" int64_t cwf_hausdorff_workspace(int B, int R, int D0, int D1, int D2)
   return rc ? rc : L.total;
 }
 
+extern "C" int64_t cwf_surface_metrics_workspace(int B, int R, int D0, int D1, int D2) {
+  HdLayout L;
+  const int rc = hd_layout(B, R, D0, D1, D2, L);
+  return rc ? rc : L.total_surface;
+}
+
 extern "C" int cwf_region_bits(const int64_t* labels, uint8_t* bits, int64_t n, void* stream) {
   if (!labels || !bits || n <= 0) return CWF_E_BADARG;
   hipLaunchKernelGGL(hd_region_bits_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, cwf_stream(stream), labels, bits, n);
@@ -327,28 +449,46 @@ extern "C" int cwf_region_bits(const int64_t* labels, uint8_t* bits, int64_t n, 
   return 0;
 }
 
-extern "C" int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int D1, int D2, double s0, double s1, double s2,
-                             int connectivity, int all_border, double* hd, double* hd95, int64_t* counts, void* ws, int64_t ws_bytes,
-                             void* stream) {
+// The launches of cwf_hausdorff; with surf, the surface variant of the gather pass and one more launch per (sample, region).
+static int hd_run(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int D1, int D2, double s0, double s1, double s2, int connectivity,
+                  int all_border, double* hd, double* hd95, int64_t* counts, void* ws, int64_t ws_bytes, void* stream, bool surf,
+                  const double* tau, int T, double* asd, double* assd, int64_t* within, double* nsd) {
   HdLayout L;
   const int rc = hd_layout(B, R, D0, D1, D2, L);
   if (rc) return rc;
   if (!a || !b || !hd || !hd95 || !counts || !ws || connectivity < 1 || connectivity > 3) return CWF_E_BADARG;
   if (!(s0 > 0.0 && s1 > 0.0 && s2 > 0.0 && s0 < 1e300 && s1 < 1e300 && s2 < 1e300)) return CWF_E_BADARG;
-  if (ws_bytes < L.total) return CWF_E_TOOLARGE;
+  HdSurface sv = {};
+  if (surf) {
+    if (T < 0 || T > HD_MAX_TAU || !asd || !assd || (T > 0 && (!tau || !within || !nsd))) return CWF_E_BADARG;
+    for (int j = 0; j < T; ++j) {
+      if (!(tau[j] >= 0.0)) return CWF_E_BADARG;               // negative or NaN; +inf counts every border voxel
+      sv.tau[j] = tau[j];
+    }
+    sv.T = T;
+  }
+  if (ws_bytes < (surf ? L.total_surface : L.total)) return CWF_E_TOOLARGE;
   if ((uintptr_t)ws & 255) return CWF_E_ALIGN;
   hipStream_t st = cwf_stream(stream);
   uint8_t* w = (uint8_t*)ws;
-  const int64_t V = (int64_t)D0 * D1 * D2, plane = (int64_t)D1 * D2;
+  const int64_t V = (int64_t)D0 * D1 * D2, plane = (int64_t)D1 * D2, lines = (int64_t)D0 * D1;
   uint8_t* ba = w + L.border;
   uint8_t* bb = ba + (int64_t)B * V;
   double* g = (double*)(w + L.g);
   double* compact = (double*)(w + L.compact);
   HdSmall* small = (HdSmall*)(w + L.small);
   int* range = (int*)(w + L.range);
+  if (surf) { sv.lsum = (double*)(w + L.lsum); sv.lcnt = (unsigned int*)(w + L.lcnt); }
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
-  if (hipMemsetAsync(counts, 0, (size_t)B * R * 4 * sizeof(int64_t), st) != hipSuccess) return (int)hipErrorInvalidValue;
-  if (hipMemsetAsync(w + L.small, 0, (size_t)(L.total - L.small), st) != hipSuccess) return (int)hipErrorInvalidValue;
+  if (surf) {
+    const int64_t n0 = (int64_t)B * R * 4, n1 = (L.total - L.small) / 8;               // L.small and L.total are multiples of 256
+    hipLaunchKernelGGL(hd_zero_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(n0 + n1, 256), 1024)), dim3(256), 0, st, cnt, n0,
+                       reinterpret_cast<unsigned long long*>(w + L.small), n1);
+    CWF_LAUNCH_CHECK();
+  } else {
+    if (hipMemsetAsync(counts, 0, (size_t)B * R * 4 * sizeof(int64_t), st) != hipSuccess) return (int)hipErrorInvalidValue;
+    if (hipMemsetAsync(w + L.small, 0, (size_t)(L.total - L.small), st) != hipSuccess) return (int)hipErrorInvalidValue;
+  }
   const unsigned gx = (unsigned)std::min<int64_t>(cdiv64(V, 256), 1024);
   hipLaunchKernelGGL(hd_border_kernel, dim3(gx, B), dim3(256), 0, st, a, b, ba, bb, cnt, R, D0, D1, D2, connectivity, all_border);
   CWF_LAUNCH_CHECK();
@@ -360,8 +500,12 @@ extern "C" int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, i
       int* rg = range + ((int64_t)s * R + r) * 4 * D2;
       hipLaunchKernelGGL(hd_edt_axis0_kernel, dim3((unsigned)cdiv64(plane, 256), 2), dim3(256), 0, st, ba + s * V, bb + s * V, r, D0, D1, D2, s0, g, rg);
       CWF_LAUNCH_CHECK();
-      hipLaunchKernelGGL(hd_edt_gather_kernel, dim3((unsigned)((int64_t)D0 * D1), 2), dim3(64), (size_t)D2 * sizeof(double), st, ba + s * V, bb + s * V, r, D0, D1, D2, s1, s2,
-                         (const double*)g, (const int*)rg, compact, cap, sm);
+      if (surf)
+        hipLaunchKernelGGL(hd_edt_gather_kernel<true>, dim3((unsigned)lines, 2), dim3(64), (size_t)D2 * sizeof(double), st, ba + s * V, bb + s * V, r, D0, D1, D2,
+                           s1, s2, (const double*)g, (const int*)rg, compact, cap, sm, sv);
+      else
+        hipLaunchKernelGGL(hd_edt_gather_kernel<false>, dim3((unsigned)lines, 2), dim3(64), (size_t)D2 * sizeof(double), st, ba + s * V, bb + s * V, r, D0, D1, D2,
+                           s1, s2, (const double*)g, (const int*)rg, compact, cap, sm, sv);
       CWF_LAUNCH_CHECK();
       const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(compact);
       const unsigned long long* c = cnt + ((int64_t)s * R + r) * 4 + 2;          // |dA|, |dB|
@@ -371,6 +515,26 @@ extern "C" int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, i
       }
       hipLaunchKernelGGL(hd_radix_kernel, dim3(1), dim3(256), 0, st, keys, cap, sm, 8, c, hd + s * R + r, hd95 + s * R + r);
       CWF_LAUNCH_CHECK();
+      if (surf) {
+        const int64_t o = (int64_t)s * R + r;
+        hipLaunchKernelGGL(hd_surface_final_kernel, dim3(1), dim3(1024), 0, st, sv, lines, c, asd + o * 2, assd + o,
+                           reinterpret_cast<long long*>(within) + o * T * 2, nsd + o * T);
+        CWF_LAUNCH_CHECK();
+      }
     }
   return 0;
+}
+
+extern "C" int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int D1, int D2, double s0, double s1, double s2,
+                             int connectivity, int all_border, double* hd, double* hd95, int64_t* counts, void* ws, int64_t ws_bytes,
+                             void* stream) {
+  return hd_run(a, b, B, R, D0, D1, D2, s0, s1, s2, connectivity, all_border, hd, hd95, counts, ws, ws_bytes, stream, false, nullptr, 0,
+                nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int cwf_surface_metrics(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int D1, int D2, double s0, double s1, double s2,
+                                   int connectivity, int all_border, const double* tau, int T, double* hd, double* hd95, double* asd,
+                                   double* assd, int64_t* within, double* nsd, int64_t* counts, void* ws, int64_t ws_bytes, void* stream) {
+  return hd_run(a, b, B, R, D0, D1, D2, s0, s1, s2, connectivity, all_border, hd, hd95, counts, ws, ws_bytes, stream, true, tau, T, asd, assd,
+                within, nsd);
 }

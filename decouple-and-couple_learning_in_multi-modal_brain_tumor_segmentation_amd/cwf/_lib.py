@@ -99,6 +99,8 @@ SIGNATURES = {
     "cwf_region_bits": [P, P, L, P],
     "cwf_hausdorff_workspace": [I, I, I, I, I],
     "cwf_hausdorff": [P, P, I, I, I, I, I, D, D, D, I, I, P, P, P, P, L, P],
+    "cwf_surface_metrics_workspace": [I, I, I, I, I],
+    "cwf_surface_metrics": [P, P, I, I, I, I, I, D, D, D, I, I, P, I, P, P, P, P, P, P, P, P, L, P],
     "cwf_components_workspace": [I, I, I, I, I],
     "cwf_components": [P, I, I, I, I, I, I, P, P, P, P, P, L, P],
     "cwf_postprocess_labels": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
@@ -106,6 +108,8 @@ SIGNATURES = {
     "cwf_dilate_bits": [P, P, I, I, I, I, I, I, P, L, P],
     "cwf_lesionwise_workspace": [I, I, I, I, I],
     "cwf_lesionwise": [P, P, I, I, I, I, I, I, L, D, P, P, P, P, P, P, L, P],
+    "cwf_lesionwise_ex_workspace": [I, I, I, I, I],
+    "cwf_lesionwise_ex": [P, P, I, I, I, I, I, I, L, D, P, I, P, P, P, P, P, P, P, P, L, P],
     "cwf_prepare_batch": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_prepare_batch_affine": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_window_gather": [P, P, P, I, I, P],
@@ -195,7 +199,7 @@ class WindowGrid(C.Structure):
 
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
 RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
-                 "cwf_lesionwise_workspace"}
+                 "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace"}
 
 _lib = None
 

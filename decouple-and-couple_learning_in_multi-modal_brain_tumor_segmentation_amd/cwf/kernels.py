@@ -1257,6 +1257,64 @@ class HipBackend:
                    int(bool(all_border)), hd.data_ptr(), hd95.data_ptr(), counts.data_ptr(), ws.data_ptr(), int(nbytes), self._stream())
         return hd, hd95, counts
 
+    @staticmethod
+    def _tolerances(name, tolerances):
+        """NSD tolerances -> (tuple of floats, ctypes double array or None); at most 4, each >= 0 (+inf allowed), no NaN."""
+        tol = tuple(float(t) for t in (tolerances if tolerances is not None else ()))
+        if len(tol) > 4:
+            raise ValueError("%s: at most 4 tolerances per call, got %d" % (name, len(tol)))
+        if any(not t >= 0.0 for t in tol):
+            raise ValueError("%s: tolerances must be >= 0 (and not NaN), got %r" % (name, tol))
+        return tol, ((ctypes.c_double * len(tol))(*tol) if tol else None)
+
+    def surface_metrics(self, a_bits, b_bits, R, tolerances=(), spacing=None, connectivity=1, all_border=False):
+        """Normalised surface Dice at up to four `tolerances` and medpy's asd / assd of the masks a, b, with hd / hd95, on the borders
+        and exact distances of `hausdorff` (same arguments; cwf_surface_metrics): -> dict of hd, hd95 [B, R], asd [B, R, 2] = mean
+        distance dA -> dB, dB -> dA, assd [B, R], nsd [B, R, T] float64, within [B, R, T, 2] int64 = border voxels of A, of B within the
+        tolerance, counts [B, R, 4] int64 = |A|, |B|, |dA|, |dB|.  nsd = (within[..., 0] + within[..., 1]) / (|dA| + |dB|): the
+        voxel-border form, with unit spacing every tolerance < 1 counts coincident border voxels only.  NaN floats and zero within
+        where a mask is empty.  Every output is bit-identical from run to run.  No host synchronisation: the workspace comes from
+        torch's allocator on the current stream."""
+        if torch.is_tensor(a_bits) and a_bits.dtype == torch.bool:
+            a_bits = a_bits.view(torch.uint8)
+        if torch.is_tensor(b_bits) and b_bits.dtype == torch.bool:
+            b_bits = b_bits.view(torch.uint8)
+        if not torch.is_tensor(a_bits) or not torch.is_tensor(b_bits) or a_bits.dim() != 4 or tuple(a_bits.shape) != tuple(b_bits.shape) \
+                or a_bits.dtype != torch.uint8 or b_bits.dtype != torch.uint8:
+            raise ValueError("surface_metrics: a_bits and b_bits must be uint8 / bool tensors of one [B, D0, D1, D2] shape")
+        if not a_bits.is_cuda or a_bits.device != b_bits.device or a_bits.numel() == 0:
+            raise ValueError("surface_metrics: a_bits and b_bits must be non-empty CUDA tensors on one device")
+        if not 1 <= int(R) <= 8:
+            raise ValueError("surface_metrics: R must lie in 1..8, got %r" % (R,))
+        if int(connectivity) not in (1, 2, 3):
+            raise ValueError("surface_metrics: connectivity must be 1, 2 or 3, got %r" % (connectivity,))
+        tol, tau = self._tolerances("surface_metrics", tolerances)
+        if spacing is None:
+            sp = (1.0, 1.0, 1.0)
+        elif isinstance(spacing, (int, float)):
+            sp = (float(spacing),) * 3
+        else:
+            sp = tuple(float(s) for s in spacing)
+            if len(sp) != 3:
+                raise ValueError("surface_metrics: spacing needs one value per axis, got %r" % (spacing,))
+        a_bits, b_bits = a_bits.contiguous(), b_bits.contiguous()
+        nb, d0, d1, d2 = (int(s) for s in a_bits.shape)
+        R, T, dev = int(R), len(tol), a_bits.device
+        nbytes = self.lib.cwf_surface_metrics_workspace(nb, R, d0, d1, d2)
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_surface_metrics_workspace failed with status %d (B=%d R=%d %dx%dx%d)" % (nbytes, nb, R, d0, d1, d2))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        out = {"hd": torch.empty((nb, R), dtype=torch.float64, device=dev), "hd95": torch.empty((nb, R), dtype=torch.float64, device=dev),
+               "asd": torch.empty((nb, R, 2), dtype=torch.float64, device=dev), "assd": torch.empty((nb, R), dtype=torch.float64, device=dev),
+               "nsd": torch.empty((nb, R, T), dtype=torch.float64, device=dev),
+               "within": torch.empty((nb, R, T, 2), dtype=torch.int64, device=dev),
+               "counts": torch.empty((nb, R, 4), dtype=torch.int64, device=dev)}
+        self._call("cwf_surface_metrics", a_bits.data_ptr(), b_bits.data_ptr(), nb, R, d0, d1, d2, sp[0], sp[1], sp[2], int(connectivity),
+                   int(bool(all_border)), tau, T, out["hd"].data_ptr(), out["hd95"].data_ptr(), out["asd"].data_ptr(),
+                   out["assd"].data_ptr(), out["within"].data_ptr() if T else None, out["nsd"].data_ptr() if T else None,
+                   out["counts"].data_ptr(), ws.data_ptr(), int(nbytes), self._stream())
+        return out
+
     # ------------------------------------------------------------------ N6 connected components and label-map post-processing
     def components(self, bits, R, connectivity=1):
         """Connected components of every region of bits ([B, D0, D1, D2] uint8 region bits or bool, bit r = region r < R <= 8) under the
@@ -1351,13 +1409,16 @@ class HipBackend:
                    ws.data_ptr() if ws.numel() else None, ws.numel(), self._stream())
         return out
 
-    def lesionwise(self, pred_bits, gt_bits, R, dilation=3, min_lesion_voxels=50, penalty=374.0):
+    def lesionwise(self, pred_bits, gt_bits, R, dilation=3, min_lesion_voxels=50, penalty=374.0, nsd_tolerances=()):
         """Lesion-wise Dice and HD95 of every sample and region r < R <= 8 of two [B, D0, D1, D2] uint8 region-bit tensors, as
         predict_overlap.lesionwise_metrics defines them (cwf_lesionwise): -> (summary [B, R, 2] float64 = lw_dice, lw_hd95;
         counts [B, R, 6] int64 = G, kept, matched components, FP, FN, P; overflow [B, R] int32; table [B, R, 64, 4] int64 = gt_vol,
         pred_vol, inter, touching components per lesion; lesion_hd95 [B, R, 64] float64).  Where a (sample, region) has more than 64
         lesions its overflow flag is 1 and its other outputs stay zero.  The call waits on the stream once (the lesion counts size the
-        HD95 launches), so it cannot be captured into a graph."""
+        HD95 launches), so it cannot be captured into a graph.
+        nsd_tolerances: up to four tolerances; non-empty -> cwf_lesionwise_ex, and the tuple gains lesion_nsd [B, R, 64, T] float64 (the
+        normalised surface Dice of (pred_g, lesion g) as `surface_metrics` defines it, 0 for a lesion nothing touches) and lw_nsd
+        [B, R, T] float64 ((sum over kept lesions of nsd_g) / (kept + FP), 1 if that is 0 / 0); the first five are unchanged."""
         pred_bits = self._region_bits_arg("lesionwise", pred_bits)
         gt_bits = self._region_bits_arg("lesionwise", gt_bits)
         if tuple(pred_bits.shape) != tuple(gt_bits.shape) or pred_bits.device != gt_bits.device:
@@ -1370,17 +1431,27 @@ class HipBackend:
         if int(min_lesion_voxels) < 0 or not 0.0 <= float(penalty) < 1e300:
             raise ValueError("lesionwise: min_lesion_voxels and penalty must be >= 0 (and finite), got %r and %r"
                              % (min_lesion_voxels, penalty))
+        tol, tau = self._tolerances("lesionwise", nsd_tolerances)
         nb, d0, d1, d2 = (int(s) for s in pred_bits.shape)
         R, dev = int(R), pred_bits.device
-        nbytes = self.lib.cwf_lesionwise_workspace(nb, R, d0, d1, d2)
+        workspace = "cwf_lesionwise_ex_workspace" if tol else "cwf_lesionwise_workspace"
+        nbytes = getattr(self.lib, workspace)(nb, R, d0, d1, d2)
         if nbytes < 0:
-            raise _lib.CwfError("cwf_lesionwise_workspace failed with status %d (B=%d R=%d %dx%dx%d)" % (nbytes, nb, R, d0, d1, d2))
+            raise _lib.CwfError("%s failed with status %d (B=%d R=%d %dx%dx%d)" % (workspace, nbytes, nb, R, d0, d1, d2))
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
         summary = torch.zeros((nb, R, 2), dtype=torch.float64, device=dev)
         counts = torch.zeros((nb, R, 6), dtype=torch.int64, device=dev)
         overflow = torch.zeros((nb, R), dtype=torch.int32, device=dev)
         table = torch.zeros((nb, R, 64, 4), dtype=torch.int64, device=dev)
         lesion_hd95 = torch.zeros((nb, R, 64), dtype=torch.float64, device=dev)
+        if tol:
+            lesion_nsd = torch.zeros((nb, R, 64, len(tol)), dtype=torch.float64, device=dev)
+            lw_nsd = torch.zeros((nb, R, len(tol)), dtype=torch.float64, device=dev)
+            self._call("cwf_lesionwise_ex", pred_bits.data_ptr(), gt_bits.data_ptr(), nb, R, d0, d1, d2, int(dilation),
+                       int(min_lesion_voxels), float(penalty), tau, len(tol), summary.data_ptr(), counts.data_ptr(), overflow.data_ptr(),
+                       table.data_ptr(), lesion_hd95.data_ptr(), lesion_nsd.data_ptr(), lw_nsd.data_ptr(), ws.data_ptr(), int(nbytes),
+                       self._stream())
+            return summary, counts, overflow, table, lesion_hd95, lesion_nsd, lw_nsd
         self._call("cwf_lesionwise", pred_bits.data_ptr(), gt_bits.data_ptr(), nb, R, d0, d1, d2, int(dilation), int(min_lesion_voxels),
                    float(penalty), summary.data_ptr(), counts.data_ptr(), overflow.data_ptr(), table.data_ptr(), lesion_hd95.data_ptr(),
                    ws.data_ptr(), int(nbytes), self._stream())

@@ -28,6 +28,10 @@ reference's predictors, whose 500-voxel rule is the preset ``REFERENCE_POSTPROCE
 ``lesionwise_metrics`` (N7): lesion-wise Dice and HD95, the numbers BraTS has ranked by since 2023 -- every ground-truth lesion scored on
 its own, every missed lesion and every spurious predicted component penalised.  On the device: region bits -> dilation -> two
 labellings -> touch / count passes -> HD95 of eight lesions per call -> aggregate (csrc/lesions.hip); CPU tensors go through numpy and scipy.
+
+``surface_regions`` (N8): the normalised surface Dice at given tolerances and medpy's average symmetric surface distance per region, on
+the borders and exact distances of the HD95 kernels (cwf_surface_metrics); ``lesionwise_metrics(nsd_tolerances=...)`` scores the NSD
+per lesion as well.
 """
 import itertools
 import math
@@ -36,6 +40,7 @@ import numpy as np
 import torch
 
 from utils import tools
+from utils.hausdorff import surface_host as _surface_host
 
 WINDOWS = [(0, 0, 0), (0, 112, 0), (112, 0, 0), (112, 112, 0), (0, 0, 27), (0, 112, 27), (112, 0, 27), (112, 112, 27)]
 
@@ -198,7 +203,7 @@ def windows(starts):
 
 @torch.no_grad()
 def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False, with_hd95=False, window=None,
-                     postprocess=None, lesionwise=None):
+                     postprocess=None, lesionwise=None, with_nsd=None):
     """One subject: stitched probabilities -> label map (argmax; class 3 stands for BraTS label 4) -> [WT, TC, ET] Dice.
     ``deterministic`` zeroes the stem dropout that the reference leaves on in eval mode.  ``with_miou`` adds the per-class
     IoU list of tools.softmax_mIOU_score (what predict_simple.py reports next to Dice) as a fourth result.  ``with_hd95`` appends the
@@ -212,7 +217,9 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
     ``postprocess``: None -- the label map is the plain argmax; a dict of `postprocess` keyword arguments (REFERENCE_POSTPROCESS is
     one) -- ``seg`` is the processed map and Dice, IoU and HD95 are all computed from it (Dice as tools.softmax_output_dice gives it).
     ``lesionwise``: None -- the result tuple is as above; True or a dict of `lesionwise_metrics` keyword arguments -- the dict that
-    lesionwise_metrics(seg, target) returns for the final ``seg`` is appended as the last element (None without a target)."""
+    lesionwise_metrics(seg, target) returns for the final ``seg`` is appended as the last element (None without a target).
+    ``with_nsd``: None -- nothing more; a tuple of tolerances -- the dict that surface_regions(seg, target, tolerances) returns for the
+    final ``seg`` (the post-processed map when ``postprocess`` is given) is appended after everything above (None without a target)."""
     model.eval()
     saved = model.Unet_list.InitConv.dropout
     if deterministic:
@@ -236,6 +243,8 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
     if lesionwise is not None and lesionwise is not False:
         kw = {} if lesionwise is True else dict(lesionwise)
         res = res + ((None if target is None else lesionwise_metrics(res[0], target[..., :cut].long().to(res[0].device), **kw)),)
+    if with_nsd is not None:
+        res = res + ((None if target is None else surface_regions(res[0], target[..., :cut].long().to(res[0].device), tuple(with_nsd))),)
     return res
 
 
@@ -284,6 +293,47 @@ def hd95_regions(seg, target):
     nvox = seg[0].numel()
     degenerate = (counts[..., 0] == 0) | (counts[..., 1] == 0) | (counts[..., 0] == nvox) | (counts[..., 1] == nvox)
     return hd95.masked_fill(degenerate, 0.0)
+
+
+def surface_regions(seg, target, tolerances=(1.0,), spacing=None):
+    """Per-region (WT, TC, ET) normalised surface Dice and average symmetric surface distance of two [B, D0, D1, D2] int64 label maps:
+    a dict of nsd [B, 3, T] (T = len(tolerances) <= 4) and assd [B, 3] float64, on seg's device.  With dA, dB the connectivity-1
+    borders of the two regions and d(p) the Euclidean distance (in `spacing` units; None = 1) from a border voxel to the nearest
+    voxel of the other border: nsd[t] = (|{p in dA: d(p) <= tol_t}| + |{p in dB: d(p) <= tol_t}|) / (|dA| + |dB|) -- the voxel-border
+    form (MONAI's compute_surface_dice without sub-voxel handling), not the area-weighted surface-element form of DeepMind's
+    surface-distance; with unit spacing every tolerance < 1 counts coincident border voxels only -- and assd = medpy's assd, the mean
+    of the two directed mean distances.  NaN where either region is empty.  CUDA tensors run on the device (cwf_surface_metrics)
+    without a host synchronisation; CPU tensors go through numpy and scipy."""
+    for name, t in (("seg", seg), ("target", target)):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.int64:
+            raise ValueError("surface_regions: %s must be an int64 tensor of shape [B, D0, D1, D2], got %s %s"
+                             % (name, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if tuple(seg.shape) != tuple(target.shape) or seg.numel() == 0:
+        raise ValueError("surface_regions: seg and target must have one non-empty shape, got %r and %r"
+                         % (tuple(seg.shape), tuple(target.shape)))
+    tol = _tolerances("surface_regions", tolerances)
+    if seg.is_cuda:
+        from cwf.kernels import backend
+        be = backend()
+        out = be.surface_metrics(be.region_bits(seg), be.region_bits(target.to(seg.device)), 3, tol, spacing)
+        return {"nsd": out["nsd"], "assd": out["assd"]}
+    s, t = seg.numpy(), target.cpu().numpy()
+    nsd = torch.full((seg.shape[0], 3, len(tol)), math.nan, dtype=torch.float64)
+    assd = torch.full((seg.shape[0], 3), math.nan, dtype=torch.float64)
+    for b in range(seg.shape[0]):
+        for r, (o, g) in enumerate(zip(_regions(s[b]), _regions(t[b]))):
+            if o.any() and g.any():
+                _, m, _, n, _ = _surface_host(o, g, tol, spacing)
+                assd[b, r] = m
+                nsd[b, r] = torch.tensor(n, dtype=torch.float64)
+    return {"nsd": nsd, "assd": assd}
+
+
+def _tolerances(name, tolerances):
+    tol = tuple(float(t) for t in tolerances)
+    if len(tol) > 4 or any(not t >= 0.0 for t in tol):
+        raise ValueError("%s: at most 4 tolerances, each >= 0 and not NaN, got %r" % (name, tol))
+    return tol
 
 
 REFERENCE_POSTPROCESS = dict(et_min_voxels=500, et_replace=1)        # the 500-voxel enhancing-tumour rule of the reference's lineage
@@ -363,7 +413,7 @@ def _postprocess_host(seg, min_component, keep_largest, et_min_component, et_min
 LESIONWISE_MAX = 64            # CWF_LESIONWISE_MAX: lesions per (sample, region) on the device path
 
 
-def lesionwise_metrics(seg, target, dilation=3, min_lesion_voxels=50, penalty=374.0, with_table=False):
+def lesionwise_metrics(seg, target, dilation=3, min_lesion_voxels=50, penalty=374.0, with_table=False, nsd_tolerances=None):
     """Lesion-wise Dice and HD95 (the BraTS 2023 ranking metrics) of [B, D0, D1, D2] int64 label maps, per sample and region
     (WT = label > 0, TC = label in {1, 3}, ET = label == 3).  For the binary masks pred, gt of one sample and region:
       1  pred_cc = components of pred under the 26-neighbour footprint, numbered 1..P as scipy.ndimage.label numbers them
@@ -386,7 +436,11 @@ def lesionwise_metrics(seg, target, dilation=3, min_lesion_voxels=50, penalty=37
     of lesion g at row g - 1 and lesion_hd95 [B, 3, L] float64 (zeros past G), L = 64 or the largest G if that is more.
     CUDA tensors take the device path (backend().lesionwise): it needs one device-to-host readback of the B x 3 lesion counts, to
     launch only the HD95 calls that hold a lesion, and this function reads the overflow flags back; a (sample, region) with more than 64
-    lesions is recomputed by the host path and patched in.  CPU tensors go through numpy and scipy.  Results are on seg's device."""
+    lesions is recomputed by the host path and patched in.  CPU tensors go through numpy and scipy.  Results are on seg's device.
+    nsd_tolerances: None -- the dict above; a tuple of up to four tolerances -- also lw_nsd [B, 3, T] float64, the lesion-wise
+    normalised surface Dice: nsd_g = the NSD of (pred_g, lesion g) as `surface_regions` defines it (unit spacing), 0 for a lesion that
+    nothing touches, and lw_nsd = sum over kept of nsd_g / n, summed in increasing g, 1 if n == 0 (a false-positive component
+    contributes 0, as to lw_dice); with_table also lesion_nsd [B, 3, L, T] (zeros past G)."""
     for name, t in (("seg", seg), ("target", target)):
         if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.int64:
             raise ValueError("lesionwise_metrics: %s must be an int64 tensor of shape [B, D0, D1, D2], got %s %s"
@@ -401,11 +455,15 @@ def lesionwise_metrics(seg, target, dilation=3, min_lesion_voxels=50, penalty=37
         raise ValueError("lesionwise_metrics: min_lesion_voxels and penalty must be >= 0 (and finite), got %r and %r"
                          % (min_lesion_voxels, penalty))
     nb = int(seg.shape[0])
+    tol = () if nsd_tolerances is None else _tolerances("lesionwise_metrics", nsd_tolerances)
+    nt = len(tol)
     if seg.is_cuda:
         from cwf.kernels import backend
         be = backend()
-        summary, counts, overflow, table, lesion_hd95 = be.lesionwise(be.region_bits(seg), be.region_bits(target.to(seg.device)), 3,
-                                                                      dilation, min_lesion_voxels, penalty)
+        dev_out = be.lesionwise(be.region_bits(seg), be.region_bits(target.to(seg.device)), 3, dilation, min_lesion_voxels, penalty, tol)
+        summary, counts, overflow, table, lesion_hd95 = dev_out[:5]
+        lesion_nsd, lw_nsd = dev_out[5:] if nt else (torch.zeros((nb, 3, LESIONWISE_MAX, 0), dtype=torch.float64, device=seg.device),
+                                                     torch.zeros((nb, 3, 0), dtype=torch.float64, device=seg.device))
         over = overflow.cpu().numpy()
         if over.any():
             width = LESIONWISE_MAX
@@ -414,32 +472,43 @@ def lesionwise_metrics(seg, target, dilation=3, min_lesion_voxels=50, penalty=37
                 s, t = seg[b].cpu().numpy(), target[b].cpu().numpy()
                 for r in np.nonzero(over[b])[0]:
                     masks = [(s > 0, t > 0), ((s == 1) | (s == 3), (t == 1) | (t == 3)), (s == 3, t == 3)][r]
-                    patches.append((int(b), int(r), _lesionwise_host(masks[0], masks[1], dilation, min_lesion_voxels, penalty)))
+                    patches.append((int(b), int(r), _lesionwise_host(masks[0], masks[1], dilation, min_lesion_voxels, penalty, tol)))
                     width = max(width, patches[-1][2][2].shape[0])
             if width > LESIONWISE_MAX:
                 table = torch.nn.functional.pad(table, (0, 0, 0, width - LESIONWISE_MAX))
                 lesion_hd95 = torch.nn.functional.pad(lesion_hd95, (0, width - LESIONWISE_MAX))
-            for b, r, (sm, cn, tb, lh) in patches:
+                lesion_nsd = torch.nn.functional.pad(lesion_nsd, (0, 0, 0, width - LESIONWISE_MAX))
+            for b, r, (sm, cn, tb, lh, ln, wn) in patches:
                 summary[b, r] = torch.tensor(sm, dtype=torch.float64)
                 counts[b, r] = torch.tensor(cn, dtype=torch.int64)
                 table[b, r, :tb.shape[0]] = torch.from_numpy(tb).to(table.device)
                 lesion_hd95[b, r, :lh.shape[0]] = torch.from_numpy(lh).to(table.device)
+                if nt:
+                    lesion_nsd[b, r, :ln.shape[0]] = torch.from_numpy(ln).to(table.device)
+                    lw_nsd[b, r] = torch.tensor(wn, dtype=torch.float64)
     else:
         s, t = seg.numpy(), target.numpy()
-        res = [[_lesionwise_host(o, g, dilation, min_lesion_voxels, penalty) for o, g in zip(_regions(s[b]), _regions(t[b]))]
+        res = [[_lesionwise_host(o, g, dilation, min_lesion_voxels, penalty, tol) for o, g in zip(_regions(s[b]), _regions(t[b]))]
                for b in range(nb)]
         width = max([LESIONWISE_MAX] + [x[2].shape[0] for row in res for x in row])
         summary = torch.tensor([[x[0] for x in row] for row in res], dtype=torch.float64)
         counts = torch.tensor([[x[1] for x in row] for row in res], dtype=torch.int64)
         table = torch.zeros((nb, 3, width, 4), dtype=torch.int64)
         lesion_hd95 = torch.zeros((nb, 3, width), dtype=torch.float64)
+        lesion_nsd = torch.zeros((nb, 3, width, nt), dtype=torch.float64)
+        lw_nsd = torch.tensor([[list(x[5]) for x in row] for row in res], dtype=torch.float64).reshape(nb, 3, nt)
         for b, row in enumerate(res):
             for r, x in enumerate(row):
                 table[b, r, :x[2].shape[0]] = torch.from_numpy(x[2])
                 lesion_hd95[b, r, :x[3].shape[0]] = torch.from_numpy(x[3])
+                lesion_nsd[b, r, :x[4].shape[0]] = torch.from_numpy(x[4])
     out = {"dice": summary[..., 0].contiguous(), "hd95": summary[..., 1].contiguous(), "counts": counts}
+    if nsd_tolerances is not None:
+        out["lw_nsd"] = lw_nsd
     if with_table:
         out["table"], out["lesion_hd95"] = table, lesion_hd95
+        if nsd_tolerances is not None:
+            out["lesion_nsd"] = lesion_nsd
     return out
 
 
@@ -458,8 +527,9 @@ def _hd95_host(a, b):
     return float(np.percentile(d, 95))
 
 
-def _lesionwise_host(pred, gt, dilation, min_lesion_voxels, penalty):
-    """One sample and region on the host: ((lw_dice, lw_hd95), counts [6], table [G, 4] int64, lesion_hd95 [G] float64)."""
+def _lesionwise_host(pred, gt, dilation, min_lesion_voxels, penalty, tolerances=()):
+    """One sample and region on the host: ((lw_dice, lw_hd95), counts [6], table [G, 4] int64, lesion_hd95 [G] float64,
+    lesion_nsd [G, T] float64, lw_nsd [T]) for the T tolerances."""
     from scipy import ndimage                                   # only the CPU path needs scipy
     full = ndimage.generate_binary_structure(3, 3)
     pred_cc, npred = ndimage.label(pred, structure=full)
@@ -471,6 +541,8 @@ def _lesionwise_host(pred, gt, dilation, min_lesion_voxels, penalty):
     inter = np.bincount(dil_cc[gt & pred], minlength=ng + 1)
     table = np.zeros((ng, 4), dtype=np.int64)
     hd = np.zeros(ng, dtype=np.float64)
+    nsd = np.zeros((ng, len(tolerances)), dtype=np.float64)
+    snsd = [0.0] * len(tolerances)
     sdice = shd = 0.0
     kept = fn = 0
     for g in range(1, ng + 1):
@@ -479,11 +551,14 @@ def _lesionwise_host(pred, gt, dilation, min_lesion_voxels, penalty):
         if len(comps):
             dice = 2.0 * float(inter[g]) / float(table[g - 1, 1] + gt_vol[g])
             hd[g - 1] = _hd95_host(np.isin(pred_cc, comps), gt & (dil_cc == g))
+            if tolerances:
+                nsd[g - 1] = _surface_host(np.isin(pred_cc, comps), gt & (dil_cc == g), tolerances)[3]
         else:
             dice, hd[g - 1] = 0.0, penalty
         if gt_vol[g] > min_lesion_voxels:
             sdice, shd, kept, fn = sdice + dice, shd + hd[g - 1], kept + 1, fn + (len(comps) == 0)
+            snsd = [x + float(y) for x, y in zip(snsd, nsd[g - 1])]
     fp = npred - len(np.unique(pairs[0]))
     n = kept + fp
     summary = (sdice / n, (shd + fp * penalty) / n) if n else (1.0, 0.0)
-    return summary, (ng, kept, npred - fp, fp, fn, npred), table, hd
+    return summary, (ng, kept, npred - fp, fp, fn, npred), table, hd, nsd, [(x / n if n else 1.0) for x in snsd]

@@ -3,6 +3,10 @@ with the reference's signatures and wrapper rules, and medpy's ``hd`` / ``hd95``
 ``cwf_hausdorff``): border extraction, an exact float64 Euclidean distance transform and the order statistics all run in HIP, and
 only the scalar results come back to the host.
 
+``avg_surface_distance`` (medpy ``asd``), ``avg_surface_distance_symmetric`` (medpy ``assd``) and ``normalized_surface_dice`` follow
+the same wrapper rules on the same borders and distances (``cwf_surface_metrics``).  These three run on the device for CUDA tensors
+and with numpy + scipy for everything else.
+
 Inputs are numpy arrays or torch tensors on any device (host inputs are moved to the current GPU); the results are Python floats.
 The empty / full rules come from the masks alone, before any GPU call.
 
@@ -166,6 +170,93 @@ def hausdorff_distance_95(test=None, reference=None, confusion_matrix=None, nan_
                           **kwargs):
     """medpy's hd95 of the two masks; 0 (NaN with nan_for_nonexisting) when either mask is empty or full."""
     return _wrapped(1, test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity)
+
+
+def surface_host(a, b, tolerances=(), spacing=None, connectivity=1, all_border=False):
+    """The surface metrics of two non-empty 3-D masks with scipy: (asd (2,), assd, within [T][2], nsd [T], (|dA|, |dB|)) as
+    cwf_surface_metrics defines them, the means correctly rounded (math.fsum).  Computed on the bounding box of a | b grown by one
+    voxel inside the volume (every border voxel of either mask lies in it, and what lies beyond it is unset in both)."""
+    from scipy import ndimage
+    box = tuple(slice(max(int(i.min()) - 1, 0), int(i.max()) + 2) for i in np.nonzero(a | b))
+    a, b = a[box], b[box]
+    if all_border:
+        ba, bb = a, b
+    else:
+        fp = ndimage.generate_binary_structure(3, connectivity)
+        ba, bb = a & ~ndimage.binary_erosion(a, structure=fp), b & ~ndimage.binary_erosion(b, structure=fp)
+    sp = (1.0, 1.0, 1.0) if spacing is None else ((float(spacing),) * 3 if np.isscalar(spacing) else tuple(float(v) for v in spacing))
+    da = ndimage.distance_transform_edt(~bb, sampling=sp)[ba]
+    db = ndimage.distance_transform_edt(~ba, sampling=sp)[bb]
+    asd = (math.fsum(da.tolist()) / da.size, math.fsum(db.tolist()) / db.size)
+    within = [[int((da <= t).sum()), int((db <= t).sum())] for t in tolerances]
+    nsd = [float(w[0] + w[1]) / float(da.size + db.size) for w in within]
+    return asd, (asd[0] + asd[1]) / 2.0, within, nsd, (int(da.size), int(db.size))
+
+def surface_stats(test, reference, tolerances=(), voxel_spacing=None, connectivity=1):
+    """(asd(test, reference), asd(reference, test), assd, [nsd per tolerance]) of two masks of one shape as Python floats, under the
+    rank rules above; RuntimeError (medpy's) if either is empty.  CUDA tensors run cwf_surface_metrics, everything else surface_host."""
+    if tuple(test.shape) != tuple(reference.shape):
+        raise ValueError("Shape mismatch: %s and %s" % (tuple(test.shape), tuple(reference.shape)))
+    all_border, vol = volume_mode(test.shape)
+    sp = spacing3(voxel_spacing, len(test.shape))
+    tol = tuple(float(t) for t in tolerances)
+    if isinstance(test, torch.Tensor) and test.is_cuda:
+        from cwf.kernels import backend
+        a = _device_mask(test)
+        with torch.cuda.device(a.device):
+            b = _device_mask(reference).to(a.device)
+            out = backend().surface_metrics(a, b, 1, tol, spacing=sp, connectivity=connectivity, all_border=all_border)
+            res = torch.cat([out["asd"].reshape(-1), out["assd"].reshape(-1), out["nsd"].reshape(-1),
+                             out["counts"].reshape(-1)[:2].double()]).cpu().tolist()
+        if res[-2] == 0:
+            raise RuntimeError(_EMPTY_FIRST)
+        if res[-1] == 0:
+            raise RuntimeError(_EMPTY_SECOND)
+        return res[0], res[1], res[2], res[3:3 + len(tol)]
+    a = np.asarray(_nonzero(test.cpu() if isinstance(test, torch.Tensor) else np.asarray(test))).reshape(vol)
+    b = np.asarray(_nonzero(reference.cpu() if isinstance(reference, torch.Tensor) else np.asarray(reference))).reshape(vol)
+    if not a.any():
+        raise RuntimeError(_EMPTY_FIRST)
+    if not b.any():
+        raise RuntimeError(_EMPTY_SECOND)
+    asd, assd, _, nsd, _ = surface_host(a, b, tol, sp, connectivity, all_border)
+    return asd[0], asd[1], assd, nsd
+
+
+def _wrapped_surface(pick, test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, tolerances=()):
+    if confusion_matrix is None:
+        confusion_matrix = ConfusionMatrix(test, reference)
+    if confusion_matrix.test is not None:
+        volume_mode(confusion_matrix.test.shape)
+    test_empty, test_full, reference_empty, reference_full = confusion_matrix.get_existence()
+    if test_empty or test_full or reference_empty or reference_full:
+        return math.nan if nan_for_nonexisting else 0.0
+    return pick(surface_stats(confusion_matrix.test, confusion_matrix.reference, tolerances, voxel_spacing, connectivity))
+
+
+def avg_surface_distance(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=False, voxel_spacing=None, connectivity=1,
+                         **kwargs):
+    """medpy's asd(test, reference): the mean distance from the border voxels of test to the border of reference; 0 (NaN with
+    nan_for_nonexisting) when either mask is empty or full."""
+    return _wrapped_surface(lambda s: s[0], test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity)
+
+
+def avg_surface_distance_symmetric(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=False, voxel_spacing=None,
+                                   connectivity=1, **kwargs):
+    """medpy's assd: the mean of asd(test, reference) and asd(reference, test); 0 (NaN with nan_for_nonexisting) when either mask is
+    empty or full."""
+    return _wrapped_surface(lambda s: s[2], test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity)
+
+
+def normalized_surface_dice(test=None, reference=None, tolerance=1.0, confusion_matrix=None, nan_for_nonexisting=False, voxel_spacing=None,
+                            connectivity=1, **kwargs):
+    """The normalised surface Dice at `tolerance` (in voxel_spacing units): the share of the border voxels of both masks that lie
+    within the tolerance of the other mask's border -- the voxel-border form, not the area-weighted surface-element one; with unit
+    spacing a tolerance < 1 counts coincident border voxels only.  0 (NaN with nan_for_nonexisting) when either mask is empty or full."""
+    if not float(tolerance) >= 0.0:
+        raise ValueError("normalized_surface_dice: tolerance must be >= 0 (and not NaN), got %r" % (tolerance,))
+    return _wrapped_surface(lambda s: s[3][0], test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity,
+                            (float(tolerance),))
 
 
 def softmax_hd(output, target):

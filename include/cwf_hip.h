@@ -427,6 +427,27 @@ int64_t cwf_hausdorff_workspace(int B, int R, int D0, int D1, int D2);
 int cwf_hausdorff(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int D1, int D2, double s0, double s1, double s2,
                   int connectivity, int all_border, double* hd, double* hd95, int64_t* counts, void* ws, int64_t ws_bytes,
                   void* stream);
+/* N8  normalised surface Dice (NSD) and average surface distance on the borders and distances of cwf_hausdorff (same arguments, same
+ * kernels; hd, hd95 and counts are bit-equal to that function's).  With q the float64 squared distance of the transform and
+ * d(p) = sqrt(q), correctly rounded, for p in dA (to the nearest voxel of dB) and for p in dB (to dA), and tolerances tau[0..T):
+ *   within[b][r][t][2]  int64: |{p in dA : d(p) <= tau[t]}|, the same over dB (a float64 <= on d)
+ *   nsd[b][r][t]        (within[t][0] + within[t][1]) / (|dA| + |dB|): one float64 division of two integers converted exactly
+ *   asd[b][r][2]        mean of d over dA, mean of d over dB (medpy asd(A, B), asd(B, A))
+ *   assd[b][r]          (asd[0] + asd[1]) / 2 (medpy assd)
+ * If either mask is empty every float output of that (b, r) is NaN and within is 0.  This is the voxel-border NSD (MONAI's
+ * compute_surface_dice without sub-voxel handling), not the area-weighted surface-element form of DeepMind's surface-distance; with unit
+ * spacing every tau < 1 counts coincident border voxels only.  within and nsd are exact.  asd is a float64 sum whose every addition has
+ * fixed operands (per-line slots, then a fixed tree: csrc/metrics.hip), so it is bit-identical from run to run and does not depend on
+ * B, R or the order in which atomics land; it lies within 2 n 2^-53 relative of the exact mean of the rounded d (n = border voxels).
+ * tau: T values in host memory, copied into the launches; 0 <= T <= 4 (with T == 0 tau, within and nsd may be null).
+ * ws: cwf_surface_metrics_workspace(...) bytes (cwf_hausdorff's plus 48 bytes per axis-(0, 1) line), 256-B aligned.  No host
+ * synchronisation, no kernel waits on another workgroup: the call can be captured into a graph.
+ * CWF_E_BADARG: T outside 0..4, a negative or NaN tau (+inf is allowed and counts every border voxel), a null pointer; otherwise as
+ * cwf_hausdorff. */
+int64_t cwf_surface_metrics_workspace(int B, int R, int D0, int D1, int D2);
+int cwf_surface_metrics(const uint8_t* a, const uint8_t* b, int B, int R, int D0, int D1, int D2, double s0, double s1, double s2,
+                        int connectivity, int all_border, const double* tau, int T, double* hd, double* hd95, double* asd, double* assd,
+                        int64_t* within, double* nsd, int64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * N6  connected-component post-processing of predicted label maps (predict_overlap.postprocess): 3-D connected-component labelling
@@ -500,6 +521,17 @@ int64_t cwf_lesionwise_workspace(int B, int R, int D0, int D1, int D2);
 int cwf_lesionwise(const uint8_t* pred, const uint8_t* gt, int B, int R, int D0, int D1, int D2, int dilation, int64_t min_lesion_voxels,
                    double penalty, double* summary, int64_t* counts, int32_t* overflow, int64_t* table, double* lesion_hd95, void* ws,
                    int64_t ws_bytes, void* stream);
+/* cwf_lesionwise plus the lesion-wise normalised surface Dice at tau[0..T), 0 <= T <= 4 (host memory): cwf_surface_metrics takes
+ * cwf_hausdorff's place (unit spacing, connectivity 1, eight lesions per call), every other output is what cwf_lesionwise gives.
+ *   lesion_nsd[b][r][64][T]  nsd of (pred_g, lesion g) as cwf_surface_metrics defines it; 0 for a lesion nothing touches; rows >= G are 0
+ *   lw_nsd[b][r][T]          (sum over kept lesions of nsd_g) / (kept + FP), summed in increasing g in float64; 1 if kept + FP == 0
+ *                            (false-positive components contribute 0, as to lw_dice)
+ * Both are left untouched where overflow[b][r] is 1; with T == 0 tau and both may be null.  ws: cwf_lesionwise_ex_workspace(...)
+ * bytes, 256-B aligned.  CWF_E_BADARG also for T outside 0..4 and a negative or NaN tau. */
+int64_t cwf_lesionwise_ex_workspace(int B, int R, int D0, int D1, int D2);
+int cwf_lesionwise_ex(const uint8_t* pred, const uint8_t* gt, int B, int R, int D0, int D1, int D2, int dilation, int64_t min_lesion_voxels,
+                      double penalty, const double* tau, int T, double* summary, int64_t* counts, int32_t* overflow, int64_t* table,
+                      double* lesion_hd95, double* lesion_nsd, double* lw_nsd, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * N5  sliding-window inference over volumes of any size (predict_overlap.sliding_window_inference): overlapping r0 x r1 x r2

@@ -19,7 +19,8 @@
 // four voxels, or outputs without 16-B alignment, take the same kernel with per-voxel stores.
 //
 // cwf_prepare_batch_affine: the same outputs from a rotated and zoomed crop (trilinear image, nearest label), a kernel of its own
-// further down that shares the bit helpers and the pass structure.
+// further down that shares the bit helpers and the pass structure.  cwf_prepare_batch_elastic: that kernel's second instantiation,
+// which adds a cubic B-spline displacement to every source coordinate.
 //
 // cwf_normalize_nonzero: per-channel z-score over the voxels whose four-channel sum ((x0 + x1) + x2) + x3 (float32) is > 0, float64
 // two-pass statistics (partials per workgroup, reduced in a fixed order by one thread: the result does not depend on scheduling).
@@ -263,14 +264,25 @@ struct PrepAffSample {
   float m[9];
 };
 
-struct PrepAffArgs {
-  PrepAffSample s[PREP_MAXS];
+// the elastic entry's sample: disp == nullptr adds nothing; k[d] = float(G_d - 3) / float(C_d - 1), divided on the host
+struct PrepElaSample : PrepAffSample {
+  const float* disp;
+  int G0, G1, G2;
+  float k[3];
+};
+
+template <class Sample>
+struct PrepResArgs {
+  Sample s[PREP_MAXS];
   float* x;
   int64_t* target;
   int64_t* edge;
   int64_t x_bs, t_bs, e_bs;
   int C0, C1, C2, vec;
 };
+typedef PrepResArgs<PrepAffSample> PrepAffArgs;
+typedef PrepResArgs<PrepElaSample> PrepElaArgs;
+static_assert(sizeof(PrepElaArgs) <= 4096, "the samples travel by value in the kernel-argument block");
 
 // crop-local source coordinate of the (already flipped) output voxel (p0, p1, p2); false when it is not representable
 __device__ __forceinline__ bool aff_coord(const PrepAffSample& S, int p0, int p1, int p2, float c0, float c1, float c2, float q[3]) {
@@ -287,19 +299,126 @@ __device__ __forceinline__ bool aff_coord(const PrepAffSample& S, int p0, int p1
 
 __device__ __forceinline__ float aff_lerp(float a, float b, float f) { return __fadd_rn(a, __fmul_rn(f, __fsub_rn(b, a))); }
 
-__global__ __launch_bounds__(256) void prep_affine_kernel(const PrepAffArgs a) {
+// Elastic deformation (statement: include/cwf_hip.h).  The spline is separable, so a workgroup evaluates the four weights and the four
+// clamped control indices (times the grid stride of their axis) of its 10 + 10 + 34 halo coordinates once; a voxel then needs three
+// table rows and 64 control points.  The sample's whole grid (at most 8^3 points, the three components of a point side by side) is
+// staged in LDS, so no control index ever forms a global address: 8 KiB for the grid and 1.7 KiB for the tables.
+#define ELA_GMAX 8
+#define ELA_ROWS (AFF_H0 + AFF_H1 + AFF_H2)
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+struct ElaTables {
+  f32x4 cg[ELA_GMAX * ELA_GMAX * ELA_GMAX];   // control point [i0][i1][i2] -> (disp[0], disp[1], disp[2], 0)
+  f32x4 w[ELA_ROWS];                          // rows 0..9 axis 0, 10..19 axis 1, 20..53 axis 2 (halo coordinate h = p - b + 1)
+  i32x4 ix[ELA_ROWS];
+};
+
+// ((w0*a + w1*b) + w2*c) + w3*d
+__device__ __forceinline__ float ela_sum4(f32x4 w, float a, float b, float c, float d) {
+  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w[0], a), __fmul_rn(w[1], b)), __fmul_rn(w[2], c)), __fmul_rn(w[3], d));
+}
+
+// weights and control indices of the output index p (not yet flipped) along an axis of C voxels and G control points
+__device__ __forceinline__ void ela_axis(int p, int C, bool flip, int G, float k, int stride, f32x4& w, i32x4& ix) {
+  w = f32x4{0.f, 0.f, 0.f, 0.f};
+  ix = i32x4{0, 0, 0, 0};
+  if (p < 0 || p >= C) return;                                // a halo coordinate outside the crop: never looked up
+  const float g = __fadd_rn(__fmul_rn((float)(flip ? C - 1 - p : p), k), 1.f);
+  const float fl = floorf(g);
+  const float t = __fsub_rn(g, fl), s = __fsub_rn(1.f, t), h = 0.16666667163372040f;
+  w[0] = __fmul_rn(__fmul_rn(__fmul_rn(s, s), s), h);
+  w[1] = __fmul_rn(__fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(3.f, t), 6.f), t), t), 4.f), h);
+  w[2] = __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(-3.f, t), 3.f), t), 3.f), t), 1.f), h);
+  w[3] = __fmul_rn(__fmul_rn(__fmul_rn(t, t), t), h);
+  const int i = (int)fl;                                      // 1 <= g <= G - 2 + one rounding: i is in [1, G - 2]
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ix[j] = min(max(i - 1 + j, 0), G - 1) * stride;
+}
+
+__device__ __forceinline__ void ela_setup(const PrepElaSample& S, ElaTables& T, int b0, int b1, int b2, int C0, int C1, int C2, int tid) {
+  const int n = S.G0 * S.G1 * S.G2;                           // <= 512 (checked on the host)
+  for (int i = tid; i < n; i += 256) T.cg[i] = f32x4{S.disp[i], S.disp[n + i], S.disp[2 * n + i], 0.f};
+  if (tid >= ELA_ROWS) return;
+  f32x4 w;
+  i32x4 ix;
+  if (tid < AFF_H0)
+    ela_axis(b0 + tid - 1, C0, S.flip & 1, S.G0, S.k[0], S.G1 * S.G2, w, ix);
+  else if (tid < AFF_H0 + AFF_H1)
+    ela_axis(b1 + (tid - AFF_H0) - 1, C1, (S.flip >> 1) & 1, S.G1, S.k[1], S.G2, w, ix);
+  else
+    ela_axis(b2 + (tid - AFF_H0 - AFF_H1) - 1, C2, (S.flip >> 2) & 1, S.G2, S.k[2], 1, w, ix);
+  T.w[tid] = w;
+  T.ix[tid] = ix;
+}
+
+// q += D at the halo coordinate (h0, h1, h2) of the tile, then the |q| < 2^30 test on the result.  The outer sum runs as a loop that
+// is not unrolled (a running ((a + b) + c) + d is the same association): unrolled, the 64 control points of each of a thread's four
+// voxels are all fetched ahead and the kernel needs several times the registers.
+__device__ __forceinline__ bool ela_displace(const ElaTables& T, int h0, int h1, int h2, float q[3]) {
+  const f32x4 w1 = T.w[AFF_H0 + h1], w2 = T.w[AFF_H0 + AFF_H1 + h2];
+  const i32x4 i1 = T.ix[AFF_H0 + h1], i2 = T.ix[AFF_H0 + AFF_H1 + h2];
+  const float* w0 = reinterpret_cast<const float*>(&T.w[h0]);
+  const int* i0 = reinterpret_cast<const int*>(&T.ix[h0]);
+  float D[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int j0 = 0; j0 < 4; ++j0) {
+    float r1[3][4];
+#pragma unroll
+    for (int j1 = 0; j1 < 4; ++j1) {
+      const int row = i0[j0] + i1[j1];
+      const f32x4 a = T.cg[row + i2[0]], b = T.cg[row + i2[1]], c = T.cg[row + i2[2]], d = T.cg[row + i2[3]];
+#pragma unroll
+      for (int e = 0; e < 3; ++e) r1[e][j1] = ela_sum4(w2, a[e], b[e], c[e], d[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      const float v = __fmul_rn(w0[j0], ela_sum4(w1, r1[e][0], r1[e][1], r1[e][2], r1[e][3]));
+      D[e] = j0 == 0 ? v : __fadd_rn(D[e], v);
+    }
+  }
+  bool ok = true;
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    q[e] = __fadd_rn(q[e], D[e]);
+    ok = ok && fabsf(q[e]) < AFF_QMAX;
+  }
+  return ok;
+}
+
+// the source coordinate of the (unflipped) output voxel (p0, p1, p2) = halo coordinate (h0, h1, h2): the one place both the label
+// pass and the image pass take it from
+template <bool DISP, class Sample>
+__device__ __forceinline__ bool res_coord(const Sample& S, const ElaTables* T, bool disp, int p0, int p1, int p2, int h0, int h1, int h2,
+                                          int C0, int C1, int C2, float c0, float c1, float c2, float q[3]) {
+  const bool ok = aff_coord(S, (S.flip & 1) ? C0 - 1 - p0 : p0, (S.flip & 2) ? C1 - 1 - p1 : p1, (S.flip & 4) ? C2 - 1 - p2 : p2, c0, c1, c2, q);
+  if constexpr (DISP) {
+    if (disp) return ela_displace(*T, h0, h1, h2, q);          // the test is on the final q alone
+  }
+  return ok;
+}
+
+template <bool DISP, class Args>
+__global__ __launch_bounds__(256) void prep_affine_kernel(const Args a) {
   __shared__ __attribute__((aligned(16))) uint8_t H[AFF_H0][AFF_H1][AFF_ROW];
   __shared__ uint32_t P1[AFF_H0][AFF_H1][AFF_Q2];
   __shared__ uint32_t P2[AFF_H0][AFF_T1][AFF_Q2];
-  const PrepAffSample& S = a.s[blockIdx.y];
+  const auto& S = a.s[blockIdx.y];
   const int C0 = a.C0, C1 = a.C1, C2 = a.C2;
   const int n2 = (C2 + AFF_T2 - 1) / AFF_T2, n1 = (C1 + AFF_T1 - 1) / AFF_T1;
   const int t = blockIdx.x;
   const int b2 = (t % n2) * AFF_T2, b1 = ((t / n2) % n1) * AFF_T1, b0 = (t / (n2 * n1)) * AFF_T0;
-  const int f0 = S.flip & 1, f1 = (S.flip >> 1) & 1, f2 = (S.flip >> 2) & 1;
   const float c0 = 0.5f * (float)(C0 - 1), c1 = 0.5f * (float)(C1 - 1), c2 = 0.5f * (float)(C2 - 1);
   const int64_t S0 = S.S0, S1 = S.S1, S2 = S.S2, plane = S1 * S2, V = S0 * plane;
   const int tid = threadIdx.x;
+  const ElaTables* T = nullptr;
+  bool disp = false;
+  if constexpr (DISP) {
+    __shared__ ElaTables tables;
+    T = &tables;
+    disp = S.disp != nullptr;                                 // uniform over the workgroup
+    if (disp) ela_setup(S, tables, b0, b1, b2, C0, C1, C2, tid);
+    __syncthreads();
+  }
 
   // 1. label bits of the halo tile, through the nearest-neighbour map
   for (int i = tid; i < AFF_H0 * AFF_H1 * AFF_H2; i += 256) {
@@ -309,7 +428,7 @@ __global__ __launch_bounds__(256) void prep_affine_kernel(const PrepAffArgs a) {
     if (p0 >= 0 && p0 < C0 && p1 >= 0 && p1 < C1 && p2 >= 0 && p2 < C2) {
       float q[3];
       v = 0u;
-      if (aff_coord(S, f0 ? C0 - 1 - p0 : p0, f1 ? C1 - 1 - p1 : p1, f2 ? C2 - 1 - p2 : p2, c0, c1, c2, q)) {
+      if (res_coord<DISP>(S, T, disp, p0, p1, p2, h0, h1, h2, C0, C1, C2, c0, c1, c2, q)) {
         const int64_t s0 = S.o0 + (int64_t)floorf(__fadd_rn(q[0], 0.5f)), s1 = S.o1 + (int64_t)floorf(__fadd_rn(q[1], 0.5f)),
                       s2 = S.o2 + (int64_t)floorf(__fadd_rn(q[2], 0.5f));
         if (s0 >= 0 && s0 < S0 && s1 >= 0 && s1 < S1 && s2 >= 0 && s2 < S2) v = prep_bits(S.label[s0 * plane + s1 * S2 + s2]);
@@ -333,8 +452,7 @@ __global__ __launch_bounds__(256) void prep_affine_kernel(const PrepAffArgs a) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float q[3];
-      const bool ok = p2 + e < C2 &&
-                      aff_coord(S, f0 ? C0 - 1 - p0 : p0, f1 ? C1 - 1 - p1 : p1, f2 ? C2 - 1 - (p2 + e) : p2 + e, c0, c1, c2, q);
+      const bool ok = p2 + e < C2 && res_coord<DISP>(S, T, disp, p0, p1, p2 + e, i + 1, j + 1, 4 * w + e + 1, C0, C1, C2, c0, c1, c2, q);
       float fr[3] = {0.f, 0.f, 0.f};
       int64_t s[3] = {0, 0, 0};
       if (ok) {
@@ -441,22 +559,28 @@ __global__ __launch_bounds__(256) void prep_affine_kernel(const PrepAffArgs a) {
   }
 }
 
-extern "C" int cwf_prepare_batch_affine(const struct cwf_prep_affine_sample* h_samples, int B, int C0, int C1, int C2, float* x,
-                                        int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride,
-                                        void* stream) {
+// both entries: the argument checks, then one launch per eight samples
+template <bool DISP, class HostSample>
+static int prep_resampled(const HostSample* h_samples, int B, int C0, int C1, int C2, float* x, int64_t x_bstride, int64_t* target,
+                          int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream) {
+  typedef typename std::conditional<DISP, PrepElaSample, PrepAffSample>::type Sample;
   if (!h_samples || B <= 0 || C0 <= 0 || C1 <= 0 || C2 <= 0 || !x || !target || !edge) return CWF_E_BADARG;
   const int64_t V = (int64_t)C0 * C1 * C2;
   if (V >= (int64_t(1) << 31)) return CWF_E_TOOLARGE;
   if (((uintptr_t)x & 3) || ((uintptr_t)target & 7) || ((uintptr_t)edge & 7)) return CWF_E_BADARG;
   if (x_bstride < 4 * V || t_bstride < V || e_bstride < V) return CWF_E_BADARG;
   for (int b = 0; b < B; ++b) {
-    const cwf_prep_affine_sample& s = h_samples[b];
+    const HostSample& s = h_samples[b];
     if (!s.image || !s.label || ((uintptr_t)s.image & 3) || s.flip < 0 || s.flip > 7) return CWF_E_BADARG;
     if (s.S0 <= 0 || s.S1 <= 0 || s.S2 <= 0) return CWF_E_BADARG;
     for (int k = 0; k < 9; ++k)
       if (!std::isfinite(s.m[k])) return CWF_E_BADARG;
+    if constexpr (DISP) {
+      if (s.disp && (((uintptr_t)s.disp & 3) || s.G0 < 4 || s.G0 > ELA_GMAX || s.G1 < 4 || s.G1 > ELA_GMAX || s.G2 < 4 || s.G2 > ELA_GMAX))
+        return CWF_E_BADARG;
+    }
   }
-  PrepAffArgs a;
+  PrepResArgs<Sample> a;
   a.x = x; a.target = target; a.edge = edge;
   a.x_bs = x_bstride; a.t_bs = t_bstride; a.e_bs = e_bstride;
   a.C0 = C0; a.C1 = C1; a.C2 = C2;
@@ -467,23 +591,41 @@ extern "C" int cwf_prepare_batch_affine(const struct cwf_prep_affine_sample* h_s
   for (int b0 = 0; b0 < B; b0 += PREP_MAXS) {
     const int nb = std::min(PREP_MAXS, B - b0);
     for (int i = 0; i < PREP_MAXS; ++i) {
-      PrepAffSample& d = a.s[i];
-      if (i >= nb) { d = PrepAffSample{}; continue; }
-      const cwf_prep_affine_sample& s = h_samples[b0 + i];
+      Sample& d = a.s[i];
+      if (i >= nb) { d = Sample{}; continue; }
+      const HostSample& s = h_samples[b0 + i];
       d.image = s.image; d.label = s.label;
       d.S0 = s.S0; d.S1 = s.S1; d.S2 = s.S2; d.o0 = s.o0; d.o1 = s.o1; d.o2 = s.o2;
       d.flip = s.flip; d.intensity = s.intensity;
       for (int c = 0; c < 4; ++c) { d.scale[c] = s.scale[c]; d.shift[c] = s.shift[c]; }
       for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+      if constexpr (DISP) {
+        d.disp = s.disp;
+        d.G0 = s.disp ? s.G0 : 0; d.G1 = s.disp ? s.G1 : 0; d.G2 = s.disp ? s.G2 : 0;
+        const int G[3] = {d.G0, d.G1, d.G2}, C[3] = {C0, C1, C2};
+        for (int k = 0; k < 3; ++k) d.k[k] = (s.disp && C[k] > 1) ? (float)(G[k] - 3) / (float)(C[k] - 1) : 0.f;
+      }
     }
-    PrepAffArgs ab = a;
+    PrepResArgs<Sample> ab = a;
     ab.x = x + (int64_t)b0 * x_bstride;
     ab.target = target + (int64_t)b0 * t_bstride;
     ab.edge = edge + (int64_t)b0 * e_bstride;
-    hipLaunchKernelGGL(prep_affine_kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, st, ab);
+    hipLaunchKernelGGL((prep_affine_kernel<DISP, PrepResArgs<Sample>>), dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, st, ab);
     CWF_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int cwf_prepare_batch_affine(const struct cwf_prep_affine_sample* h_samples, int B, int C0, int C1, int C2, float* x,
+                                        int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride,
+                                        void* stream) {
+  return prep_resampled<false>(h_samples, B, C0, C1, C2, x, x_bstride, target, t_bstride, edge, e_bstride, stream);
+}
+
+extern "C" int cwf_prepare_batch_elastic(const struct cwf_prep_elastic_sample* h_samples, int B, int C0, int C1, int C2, float* x,
+                                         int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride,
+                                         void* stream) {
+  return prep_resampled<true>(h_samples, B, C0, C1, C2, x, x_bstride, target, t_bstride, edge, e_bstride, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ brain-mask z-score

@@ -112,6 +112,7 @@ SIGNATURES = {
     "cwf_lesionwise_ex": [P, P, I, I, I, I, I, I, L, D, P, I, P, P, P, P, P, P, P, P, L, P],
     "cwf_prepare_batch": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_prepare_batch_affine": [P, I, I, I, I, P, L, P, L, P, L, P],
+    "cwf_prepare_batch_elastic": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_window_gather": [P, P, P, I, I, P],
     "cwf_window_blend": [P, P, P, P, I, I, I, P],
     "cwf_window_finalize": [P, P, P, P, P],
@@ -187,6 +188,11 @@ class PrepSample(C.Structure):
 class PrepAffineSample(C.Structure):
     """struct cwf_prep_affine_sample (include/cwf_hip.h)"""
     _fields_ = PrepSample._fields_ + [("m", F * 9)]
+
+
+class PrepElasticSample(C.Structure):
+    """struct cwf_prep_elastic_sample (include/cwf_hip.h)"""
+    _fields_ = PrepAffineSample._fields_ + [("disp", P), ("G0", I), ("G1", I), ("G2", I)]
 
 
 WINDOW_MAX_STARTS = 128   # CWF_WINDOW_MAX_STARTS

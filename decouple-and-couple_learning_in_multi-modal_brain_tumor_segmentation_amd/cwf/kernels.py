@@ -11,6 +11,7 @@ import ctypes
 
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1512,8 +1513,11 @@ class HipBackend:
         (images[b] fp32 [4,S0,S1,S2], labels[b] uint8 [S0,S1,S2], contiguous, one device) in launches of eight samples (cwf_prepare_batch).
         params[b]: .origin (3 ints), .flip (3 bools), .scale / .shift (4 floats each, or None: intensity off), .matrix (9 floats, or
         None).  When some sample has a matrix the batch goes through cwf_prepare_batch_affine (rotated / zoomed crops, any origin), the
-        samples without one with the identity.  out: (x, target, edge) to write into; each needs contiguous inner dimensions, its
-        sample stride may be larger than one sample."""
+        samples without one with the identity.  .disp (float32 [3, G0, G1, G2] control grid, or None): when some sample has one the
+        batch goes through cwf_prepare_batch_elastic, the samples without one with disp = NULL.  The grids of the call are packed into
+        one pinned host buffer and copied to the device by one non-blocking copy on the current stream ahead of the launches (no host
+        synchronisation; both buffers are handed back to torch's stream-ordered allocators once the launches are enqueued).  out:
+        (x, target, edge) to write into; each needs contiguous inner dimensions, its sample stride may be larger than one sample."""
         crop = tuple(int(c) for c in crop)
         if len(crop) != 3:
             raise ValueError("prepare_batch: crop needs three extents, got %r" % (crop,))
@@ -1525,8 +1529,24 @@ class HipBackend:
         dev = images[0].device
         if dev.type != "cuda":
             raise ValueError("prepare_batch: the images must be on a GPU")
-        affine = any(getattr(p, "matrix", None) is not None for p in params)
-        samples = ((_lib.PrepAffineSample if affine else _lib.PrepSample) * nb)()
+        grids = [getattr(p, "disp", None) for p in params]
+        elastic = any(g is not None for g in grids)
+        affine = elastic or any(getattr(p, "matrix", None) is not None for p in params)
+        samples = ((_lib.PrepElasticSample if elastic else _lib.PrepAffineSample if affine else _lib.PrepSample) * nb)()
+        entry = "cwf_prepare_batch_elastic" if elastic else "cwf_prepare_batch_affine" if affine else "cwf_prepare_batch"
+        disp_dev = None
+        if elastic:
+            sizes = [0 if g is None else int(g.size) for g in grids]
+            host = torch.empty(sum(sizes), dtype=_f32, pin_memory=True)
+            view, at = host.numpy(), 0
+            for g, n in zip(grids, sizes):
+                if g is not None:
+                    if g.dtype != np.float32 or g.ndim != 4 or g.shape[0] != 3:
+                        raise ValueError("prepare_batch: disp must be a float32 [3, G0, G1, G2] array, got %s %r" % (g.dtype, g.shape))
+                    view[at:at + n] = g.reshape(-1)
+                    at += n
+            disp_dev = torch.empty(host.numel(), dtype=_f32, device=dev)
+            disp_dev.copy_(host, non_blocking=True)
         for b, (img, lab, p) in enumerate(zip(images, labels, params)):
             if img.dtype != _f32 or img.dim() != 4 or img.shape[0] != 4 or not img.is_contiguous() or img.device != dev:
                 raise ValueError("prepare_batch: images[%d] must be a contiguous float32 [4, S0, S1, S2] tensor on %s" % (b, dev))
@@ -1544,6 +1564,9 @@ class HipBackend:
             if affine:
                 m = getattr(p, "matrix", None)
                 s.m[:] = [float(v) for v in m] if m is not None else [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+            if elastic and grids[b] is not None:
+                s.disp = disp_dev.data_ptr() + 4 * sum(sizes[:b])
+                s.G0, s.G1, s.G2 = (int(v) for v in grids[b].shape[1:])
         if out is None:
             # (a crop the library refuses -- an extent <= 0 or 2^31 voxels and more -- gets placeholders: the refusal comes from it)
             ok = all(c > 0 for c in crop) and crop[0] * crop[1] * crop[2] < (1 << 31)
@@ -1558,7 +1581,7 @@ class HipBackend:
                 inner = torch.empty(shape[1:], device="meta").stride()
                 if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or tuple(t.stride()[1:]) != inner:
                     raise ValueError("prepare_batch: out %s must be a %s %s tensor on %s with contiguous samples" % (name, dt, shape, dev))
-        self._call("cwf_prepare_batch_affine" if affine else "cwf_prepare_batch", ctypes.addressof(samples), nb, crop[0], crop[1], crop[2], x.data_ptr(), x.stride(0),
+        self._call(entry, ctypes.addressof(samples), nb, crop[0], crop[1], crop[2], x.data_ptr(), x.stride(0),
                    target.data_ptr(), target.stride(0), edge.data_ptr(), edge.stride(0), self._stream())
         return x, target, edge
 

@@ -97,6 +97,9 @@ def build_parser():
     p.add_argument("--aug_rotate", default=0.0, type=float,
                    help="(--device_data) r > 0: rotate the crop by three Euler angles ~ U(-r, r) degrees (trilinear image, nearest label)")
     p.add_argument("--aug_scale", default=0.0, type=float, help="(--device_data) f > 0: isotropic zoom of the crop ~ U(1-f, 1+f)")
+    p.add_argument("--aug_elastic", default=0.0, type=float,
+                   help="(--device_data) e > 0: deform the crop by a cubic B-spline of control displacements ~ U(-e, e) voxels")
+    p.add_argument("--aug_elastic_grid", default=7, type=int, help="(--aug_elastic) control points per axis, 4..8")
     p.add_argument("--normalize", default=False, type=_bool,
                    help="(--device_data) z-score each subject's channels over its brain mask (four-channel sum > 0) at load")
     return p
@@ -138,7 +141,7 @@ def make_device_dataset(args, device):
         lst = lst if os.path.isfile(lst) else None
     return data.DeviceBraTS(source, device, crop, args.seed, flip=args.aug_flip, intensity=args.aug_intensity,
                             normalize=args.normalize, cache=(args.device_data == "cache"), list_file=lst, rotate=args.aug_rotate,
-                            scale=args.aug_scale)
+                            scale=args.aug_scale, elastic=args.aug_elastic, elastic_grid=args.aug_elastic_grid)
 
 
 def main(argv=None):
@@ -149,6 +152,10 @@ def main(argv=None):
         raise SystemExit("--aug_rotate / --aug_scale resample the crop on the device: they need --device_data cache or staged")
     if args.aug_rotate < 0.0 or not 0.0 <= args.aug_scale < 1.0:
         raise SystemExit("--aug_rotate takes degrees >= 0 and --aug_scale a fraction in [0, 1)")
+    if args.device_data == "off" and args.aug_elastic > 0.0:
+        raise SystemExit("--aug_elastic deforms the crop on the device: it needs --device_data cache or staged")
+    if args.aug_elastic < 0.0 or not 4 <= args.aug_elastic_grid <= 8:
+        raise SystemExit("--aug_elastic takes voxels >= 0 and --aug_elastic_grid 4 to 8 control points per axis")
     from cwf import kernels
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint

@@ -12,7 +12,8 @@ Edge codes are derived from the label with utils.synthetic.edge_codes (boundary 
 
 ``DeviceBraTS`` / ``prepare_batch`` produce the same tuple on the GPU (csrc/prep.hip: crop, optional flips and intensity scale / shift,
 label remap and edge codes in one launch per eight samples; with a matrix in the parameters the crop is rotated and zoomed, trilinear for
-the image and nearest for the label), bit-equal to the CPU statement in this module."""
+the image and nearest for the label; with a control grid it is deformed elastically on top of that), bit-equal to the CPU statement in
+this module."""
 import glob
 import os
 
@@ -103,13 +104,19 @@ class NpzBraTS(Dataset):
 # Training batches prepared on the device.  The flip and intensity augmentations are this project's definitions (the TransBTS-family
 # loaders the reference descends from flip each axis and shift intensities per channel; the reference's own `data/` package is absent),
 # so they are opt-in and off by default.
+ELASTIC_GRID_MIN, ELASTIC_GRID_MAX = 4, 8     # control points per axis of AugParams.disp
+_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+
+
 class AugParams:
     """Per-sample batch parameters: crop origin (3 ints), flips of the three crop axes, the per-channel intensity scale / shift
-    (float32 [4] each; None = intensity off), and matrix: the linear part M[d][j] of the output -> source map about the crop centre
-    (nine float32 values, row-major; None = no resampling, the plain crop)."""
-    __slots__ = ("origin", "flip", "scale", "shift", "matrix")
+    (float32 [4] each; None = intensity off), matrix: the linear part M[d][j] of the output -> source map about the crop centre
+    (nine float32 values, row-major; None = no resampling, the plain crop), and disp: the control grid of the elastic deformation,
+    float32 [3, G0, G1, G2] with 4 <= G_d <= 8, displacements in voxels of the crop-local source coordinate (a read-only array; None =
+    no deformation.  Non-finite control values are allowed: the voxels they reach read nothing)."""
+    __slots__ = ("origin", "flip", "scale", "shift", "matrix", "disp")
 
-    def __init__(self, origin, flip=(False, False, False), scale=None, shift=None, matrix=None):
+    def __init__(self, origin, flip=(False, False, False), scale=None, shift=None, matrix=None, disp=None):
         self.origin = tuple(int(o) for o in origin)
         self.flip = tuple(bool(f) for f in flip)
         if (scale is None) != (shift is None):
@@ -121,29 +128,51 @@ class AugParams:
         self.matrix = None if matrix is None else tuple(float(v) for v in np.asarray(matrix, dtype=np.float32).reshape(-1))
         if self.matrix is not None and len(self.matrix) != 9:
             raise ValueError("AugParams: matrix takes 9 values")
+        if disp is not None:
+            disp = np.array(disp, dtype=np.float32, order="C")
+            if disp.ndim != 4 or disp.shape[0] != 3 or not all(ELASTIC_GRID_MIN <= g <= ELASTIC_GRID_MAX for g in disp.shape[1:]):
+                raise ValueError("AugParams: disp takes a [3, G0, G1, G2] grid with %d <= G_d <= %d, got shape %r"
+                                 % (ELASTIC_GRID_MIN, ELASTIC_GRID_MAX, tuple(disp.shape)))
+            disp.setflags(write=False)
+        self.disp = disp
 
     def at_origin(self, origin):
-        return AugParams(origin, self.flip, self.scale, self.shift, self.matrix)
+        return AugParams(origin, self.flip, self.scale, self.shift, self.matrix, self.disp)
 
     def source_box(self, crop):
         """Integer bounds ((lo_0, hi_0), ...) relative to the origin, hi exclusive, that contain every source index the crop reads
-        (both trilinear taps and the nearest label): the float64 range of q_d over the crop, widened by one voxel."""
+        (both trilinear taps and the nearest label): the float64 range of q_d over the crop, widened by one voxel.  With a control
+        grid axis d is widened further by ceil(max |disp[d]|) + 1 on both sides: the spline weights are non-negative and sum to 1
+        within rounding, so |D_d| <= max |disp[d]| up to a few ulps (over the finite control values: a voxel that a non-finite one
+        reaches reads nothing, and neither does one moved by 2^30 voxels or more)."""
         c = [(int(n) - 1) / 2.0 for n in crop]
-        if self.matrix is None:
+        if self.matrix is None and self.disp is None:
             return tuple((0, int(n)) for n in crop)
-        m = np.asarray(self.matrix, dtype=np.float64).reshape(3, 3)
+        m = np.asarray(self.matrix if self.matrix is not None else _IDENTITY, dtype=np.float64).reshape(3, 3)
         box = []
         for d in range(3):
             r = sum(abs(m[d, j]) * c[j] for j in range(3))
-            box.append((int(np.floor(c[d] - r)) - 1, int(np.floor(c[d] + r)) + 3))
+            w = 0
+            if self.disp is not None:
+                a = np.abs(self.disp[d].astype(np.float64))
+                a = a[np.isfinite(a)]
+                w = int(min(np.ceil(a.max()) if a.size else 0.0, 2.0 ** 31)) + 1
+            box.append((int(np.floor(c[d] - r)) - 1 - w, int(np.floor(c[d] + r)) + 3 + w))
         return tuple(box)
 
     def __eq__(self, other):
-        return isinstance(other, AugParams) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+        if not isinstance(other, AugParams) or not all(getattr(self, k) == getattr(other, k) for k in self.__slots__[:-1]):
+            return False
+        if self.disp is None or other.disp is None:
+            return self.disp is other.disp
+        return self.disp.shape == other.disp.shape and self.disp.tobytes() == other.disp.tobytes()      # bit for bit (NaN included)
 
     def __repr__(self):
         head = "AugParams(origin=%r, flip=%r, scale=%r, shift=%r" % (self.origin, self.flip, self.scale, self.shift)
-        return head + (")" if self.matrix is None else ", matrix=%r)" % (self.matrix,))
+        head += "" if self.matrix is None else ", matrix=%r" % (self.matrix,)
+        if self.disp is not None:
+            head += ", disp=float32%r max |.| %r" % (list(self.disp.shape), float(np.max(np.abs(self.disp))))
+        return head + ")"
 
 
 def rotation_zoom_matrix(angles_deg, zoom=1.0):
@@ -156,12 +185,13 @@ def rotation_zoom_matrix(angles_deg, zoom=1.0):
     return ((rz @ ry @ rx) / float(zoom)).astype(np.float32).reshape(9)
 
 
-def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotate=0.0, scale=0.0):
+def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7):
     """Parameters of sample `index` in `epoch`: a pure function of the arguments, drawn from default_rng([seed, epoch, index]).  The
     origin is drawn first, by random_crop_origin's calls, so with augmentation off it is the origin NpzBraTS / SyntheticBraTS pick.
     flip: three uniforms, each < 0.5 flipping that axis; intensity f > 0: scale ~ U(1-f, 1+f)[4], then shift ~ U(-f, f)[4] (float32).
     Drawn after all of those, so that they do not depend on it: rotate r > 0: three Euler angles ~ U(-r, r) degrees; scale f > 0: an
-    isotropic zoom ~ U(1-f, 1+f); matrix = rotation_zoom_matrix(angles, zoom), None with both off."""
+    isotropic zoom ~ U(1-f, 1+f); matrix = rotation_zoom_matrix(angles, zoom), None with both off.  Last of all, elastic e > 0: the
+    control grid disp ~ U(-e, e) voxels, float32 [3, g, g, g] with g = elastic_grid; None with e = 0."""
     rng = np.random.default_rng([int(seed), int(epoch), int(index)])
     origin = random_crop_origin(tuple(full), tuple(crop), rng)
     r, z = float(rotate), float(scale)
@@ -176,14 +206,19 @@ def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotat
         angles = rng.uniform(-r, r, 3) if r > 0.0 else np.zeros(3)
         zoom = float(rng.uniform(1.0 - z, 1.0 + z)) if z > 0.0 else 1.0
         matrix = rotation_zoom_matrix(angles, zoom)
-    return AugParams(origin, fl, scale, shift, matrix)
+    disp = None
+    e, g = float(elastic), int(elastic_grid)
+    if e > 0.0:
+        disp = rng.uniform(-e, e, (3, g, g, g)).astype(np.float32)
+    return AugParams(origin, fl, scale, shift, matrix, disp)
 
 
 _Q_MAX = np.float32(2.0 ** 30)      # |q| at and beyond it (and NaN): the voxel lies outside every volume
 
 
 def _affine_coords(p, crop):
-    """q [3, *crop] float32 of the statement in _resample_cpu, and ok [*crop]: every |q_d| < 2^30"""
+    """q [3, *crop] float32 of the affine part of the statement in _resample_cpu (the identity matrix when p has none), and
+    ok [*crop]: every |q_d| < 2^30"""
     q, ok = [], np.ones(tuple(crop), dtype=bool)
     c = [np.float32(n - 1) * np.float32(0.5) for n in crop]
     u = []
@@ -192,7 +227,7 @@ def _affine_coords(p, crop):
         if p.flip[d]:
             pd = crop[d] - 1 - pd
         u.append((pd.astype(np.float32) - c[d]).reshape([-1 if k == d else 1 for k in range(3)]))
-    m = np.asarray(p.matrix, dtype=np.float32).reshape(3, 3)
+    m = np.asarray(p.matrix if p.matrix is not None else _IDENTITY, dtype=np.float32).reshape(3, 3)
     with np.errstate(over="ignore", invalid="ignore"):
         for d in range(3):
             qd = ((m[d, 0] * u[0] + m[d, 1] * u[1]) + m[d, 2] * u[2]) + c[d]
@@ -201,20 +236,79 @@ def _affine_coords(p, crop):
     return q, ok
 
 
+def _spline_axis(n, flip, g):
+    """(w float32 [n, 4], index int64 [n, 4]) of the cubic B-spline along one crop axis of n voxels and g control points"""
+    f32 = np.float32
+    pd = np.arange(n, dtype=np.int64)
+    if flip:
+        pd = n - 1 - pd
+    k = f32(g - 3) / f32(n - 1) if n > 1 else f32(0.0)
+    gd = pd.astype(f32) * k + f32(1.0)
+    fl = np.floor(gd)
+    t = gd - fl
+    s = f32(1.0) - t
+    h = f32(1.0 / 6.0)
+    w = np.stack([((s * s) * s) * h,
+                  ((((f32(3.0) * t - f32(6.0)) * t) * t) + f32(4.0)) * h,
+                  ((((f32(-3.0) * t + f32(3.0)) * t + f32(3.0)) * t) + f32(1.0)) * h,
+                  ((t * t) * t) * h], axis=1).astype(f32)
+    idx = np.clip(fl.astype(np.int64)[:, None] - 1 + np.arange(4, dtype=np.int64)[None, :], 0, g - 1)
+    return w, idx
+
+
+def _elastic_disp(p, crop):
+    """D [3][*crop] float32 of the statement in _resample_cpu.  The nested sums are taken axis by axis -- axis 2 over the whole control
+    grid, then axis 1, then axis 0 -- which forms, for every voxel, the same products and sums in the same order."""
+    w, idx = zip(*(_spline_axis(crop[d], p.flip[d], p.disp.shape[1 + d]) for d in range(3)))
+
+    def sum4(term):
+        return ((term(0) + term(1)) + term(2)) + term(3)
+
+    out = []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for c in range(3):
+            a = sum4(lambda j: w[2][:, j] * p.disp[c][:, :, idx[2][:, j]])                               # [G0, G1, C2]
+            b = sum4(lambda j: w[1][:, j, None] * a[:, idx[1][:, j], :])                                 # [G0, C1, C2]
+            out.append(sum4(lambda j: w[0][:, j, None, None] * b[idx[0][:, j], :, :]).astype(np.float32))   # [C0, C1, C2]
+    return out
+
+
+def _source_coords(p, crop):
+    """q [3][*crop] float32 of the statement in _resample_cpu, and ok [*crop]: every |q_d| < 2^30"""
+    q, ok = _affine_coords(p, crop)
+    if p.disp is None:
+        return q, ok
+    D = _elastic_disp(p, crop)
+    ok = np.ones(tuple(crop), dtype=bool)
+    with np.errstate(over="ignore", invalid="ignore"):
+        q = [np.broadcast_to(q[d], tuple(crop)) + D[d] for d in range(3)]
+        for d in range(3):
+            ok &= np.abs(q[d]) < _Q_MAX
+    return q, ok
+
+
 def _resample_cpu(img, lab, p, crop):
     """The resampled crop, numpy float32 with one rounding per operation.  With c_d = (C_d - 1) / 2, o the origin, p the output voxel:
         p'_d = flip_d ? C_d - 1 - p_d : p_d                       (resample, then torch.flip of the result)
         u_d  = float(p'_d) - c_d
-        q_d  = ((M[d][0]*u_0 + M[d][1]*u_1) + M[d][2]*u_2) + c_d   crop-local source coordinate
+        q_d  = ((M[d][0]*u_0 + M[d][1]*u_1) + M[d][2]*u_2) + c_d   crop-local source coordinate (M = identity without a matrix)
+      with a control grid disp [3, G0, G1, G2] (a uniform cubic B-spline of p', displacements in voxels of q), along each axis d
+        k_d  = float32(G_d - 3) / float32(C_d - 1)                 (correctly rounded; 0 when C_d == 1)
+        g_d  = p'_d * k_d + 1;  i_d = floor(g_d);  t = g_d - i_d;  s = 1 - t;  h = float32(1/6)
+        w0 = ((s*s)*s)*h   w1 = ((((3*t - 6)*t)*t) + 4)*h   w2 = ((((-3*t + 3)*t + 3)*t) + 1)*h   w3 = ((t*t)*t)*h
+        control index for j = 0..3: clamp(i_d - 1 + j, 0, G_d - 1)  (only i_d + 2 == G_d is ever clamped, where w3 is 0 or one
+                                                                    rounding away from it)
+        D_c  = sum_j0 w[0][j0] * (sum_j1 w[1][j1] * (sum_j2 w[2][j2] * disp[c][..][..][..])), every 4-term sum as ((a + b) + c) + d
+        q_c  = q_c + D_c                                           (no grid: nothing is added)
         image: i_d = floor(q_d), f_d = q_d - i_d, the eight taps at source index o_d + i_d + {0, 1}, 0.0 where an index leaves
                [0, S_d); lerp(a, b, f) = a + f*(b - a) along axis 2, then axis 1, then axis 0
         label: label[o + floor(q + 0.5)], 0 outside the volume
-    A voxel with some |q_d| >= 2^30 or NaN reads nothing: image 0.0, label 0.  The origin enters only as an integer added to the
+    A voxel with some final |q_d| >= 2^30 or NaN (a NaN or huge control value gives one) reads nothing: image 0.0, label 0.  The origin enters only as an integer added to the
     indices, so the result does not change when the source is cut to a box and the origin moved with it."""
     crop = tuple(int(c) for c in crop)
     a, l = img.numpy(), lab.numpy()
     S = l.shape
-    q, ok = _affine_coords(p, crop)
+    q, ok = _source_coords(p, crop)
     idx, fr, nn = [], [], []
     for d in range(3):
         qd = np.where(ok, q[d], np.float32(0.0)).astype(np.float32)
@@ -249,7 +343,7 @@ def _resample_cpu(img, lab, p, crop):
 
 
 def _prepare_one_cpu(img, lab, p, crop):
-    if p.matrix is not None:
+    if p.matrix is not None or p.disp is not None:
         x, t = _resample_cpu(img, lab, p, crop)
         if p.scale is not None:
             x = x * torch.tensor(p.scale, dtype=torch.float32).reshape(4, 1, 1, 1)
@@ -271,7 +365,7 @@ def _prepare_one_cpu(img, lab, p, crop):
 
 def prepare_batch(images, labels, params, crop, out=None):
     """(x [B,4,*crop] float32, target [B,*crop] int64, edge [B,*crop] int64) from source volumes images[b] float32 [4,S0,S1,S2] and
-    labels[b] uint8 [S0,S1,S2] (values 0..4): crop_pad at params[b].origin (with params[b].matrix: the resampled crop of
+    labels[b] uint8 [S0,S1,S2] (values 0..4): crop_pad at params[b].origin (with params[b].matrix or .disp: the resampled crop of
     _resample_cpu, any origin) -> torch.flip of the flipped crop axes -> x * scale then + shift in float32 -> label 4 -> 3 ->
     utils.synthetic.edge_codes.  On GPU tensors this is one HIP launch per eight samples
     (HipBackend.prepare_batch, bit-equal to the CPU statement); on CPU tensors it is the CPU statement itself.  out: (x, target, edge)
@@ -353,13 +447,15 @@ def _subject_arrays(img, lab, name):
 class NpzCropSource(Dataset):
     """Map-style dataset of the staged device path (DeviceBraTS(cache=False)), run in DataLoader workers: item i is the crop of subject
     i at draw_params' origin, before any flip or intensity -- (image float32 [4,*crop], label uint8 [*crop], index) -- from one
-    np.load + crop_pad (no edge codes).  `subjects`: .npz paths, or in-memory (image, label) pairs.  With rotate / scale on, the
+    np.load + crop_pad (no edge codes).  `subjects`: .npz paths, or in-memory (image, label) pairs.  With rotate / scale / elastic on, the
     item is instead the part of the volume the resampled crop reads (staged_box: shapes differ from item to item); flip and
     intensity are taken only because they move the matrix's place in draw_params' stream."""
 
-    def __init__(self, subjects, crop, seed=1000, normalize=False, flip=False, intensity=0.0, rotate=0.0, scale=0.0):
+    def __init__(self, subjects, crop, seed=1000, normalize=False, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0,
+                 elastic_grid=7):
         self.subjects, self.crop, self.seed, self.normalize, self.epoch = list(subjects), tuple(crop), int(seed), bool(normalize), 0
         self.flip, self.intensity, self.rotate, self.scale = bool(flip), float(intensity), float(rotate), float(scale)
+        self.elastic, self.elastic_grid = float(elastic), int(elastic_grid)
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -385,8 +481,9 @@ class NpzCropSource(Dataset):
 
     def __getitem__(self, i):
         img, lab = self.load(i)
-        if self.rotate > 0.0 or self.scale > 0.0:
-            p = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop, self.flip, self.intensity, self.rotate, self.scale)
+        if self.rotate > 0.0 or self.scale > 0.0 or self.elastic > 0.0:
+            p = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop, self.flip, self.intensity, self.rotate, self.scale,
+                            self.elastic, self.elastic_grid)
             (a0, b0), (a1, b1), (a2, b2) = staged_box(p, tuple(lab.shape), self.crop)
             return img[:, a0:b0, a1:b1, a2:b2].contiguous(), lab[a0:b0, a1:b1, a2:b2].contiguous(), i
         o = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop).origin
@@ -420,25 +517,30 @@ class DeviceBraTS:
 
     source: a directory of .npz subjects (NpzBraTS's layout; `list_file` as NpzBraTS's) or a list of (image, label) pairs -- e.g.
     utils.synthetic.synthetic_volume outputs.  Sample i of epoch e uses draw_params(seed, e, i, its extents, crop, flip, intensity,
-    rotate, scale); with augmentation off a batch equals torch.stack of NpzBraTS / SyntheticBraTS items.  rotate (degrees) / scale
-    > 0 turn the crop into a randomly rotated / zoomed one (trilinear image, nearest label) in the same launch.
+    rotate, scale, elastic, elastic_grid); with augmentation off a batch equals torch.stack of NpzBraTS / SyntheticBraTS items.
+    rotate (degrees) / scale > 0 turn the crop into a randomly rotated / zoomed one (trilinear image, nearest label) in the same
+    launch; elastic (voxels) > 0 deforms it by a cubic B-spline of elastic_grid^3 control displacements ~ U(-elastic, elastic).
       cache=True   every subject is loaded once onto the device (fp32 image, uint8 label, optionally z-scored by normalize_nonzero)
       cache=False  "staged": NpzCropSource crops in DataLoader workers (batches()), the crops are uploaded from pinned memory and
                    prepared at origin 0 -- 36 MB per 128^3 sample over the host link instead of a whole subject.  With rotate /
-                   scale the workers cut staged_box, the part of the volume the resampled crop reads, and the origin moves with it:
+                   scale / elastic the workers cut staged_box, the part of the volume the resampled crop reads, and the origin moves with it:
                    the batch is bit-equal to cache=True."""
 
     def __init__(self, source, device, crop=(128, 128, 128), seed=1000, flip=False, intensity=0.0, normalize=False, cache=True,
-                 list_file=None, rotate=0.0, scale=0.0):
+                 list_file=None, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7):
         self.device = torch.device(device)
         self.crop, self.seed, self.epoch = tuple(int(c) for c in crop), int(seed), 0
         self.flip, self.intensity, self.normalize, self.cache = bool(flip), float(intensity), bool(normalize), bool(cache)
         self.rotate, self.scale = float(rotate), float(scale)
-        self.affine = self.rotate > 0.0 or self.scale > 0.0
+        self.elastic, self.elastic_grid = float(elastic), int(elastic_grid)
+        if self.elastic > 0.0 and not ELASTIC_GRID_MIN <= self.elastic_grid <= ELASTIC_GRID_MAX:
+            raise ValueError("DeviceBraTS: elastic_grid takes %d..%d control points per axis" % (ELASTIC_GRID_MIN, ELASTIC_GRID_MAX))
+        self.affine = self.rotate > 0.0 or self.scale > 0.0 or self.elastic > 0.0      # the crop is resampled
         subjects = _npz_paths(source, list_file) if isinstance(source, str) else list(source)
         if not subjects:
             raise ValueError("DeviceBraTS: no subjects")
-        self.source = NpzCropSource(subjects, self.crop, self.seed, self.normalize, self.flip, self.intensity, self.rotate, self.scale)
+        self.source = NpzCropSource(subjects, self.crop, self.seed, self.normalize, self.flip, self.intensity, self.rotate, self.scale,
+                                    self.elastic, self.elastic_grid)
         self.images = self.labels = None
         if self.cache:
             self._load_all(subjects)
@@ -489,7 +591,8 @@ class DeviceBraTS:
         return tuple(_npz_shapes(s)[1]) if isinstance(s, str) else tuple(s[1].shape)
 
     def params(self, i):
-        return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity, self.rotate, self.scale)
+        return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity, self.rotate, self.scale,
+                           self.elastic, self.elastic_grid)
 
     def _missing(self, n):
         return torch.zeros((n, 4), dtype=torch.bool, device=self.device)
@@ -505,7 +608,7 @@ class DeviceBraTS:
 
     def prepare_staged(self, crops, out=None):
         """(image crops [B,4,*crop] float32, label crops [B,*crop] uint8, indices) from NpzCropSource -> the prepared batch; with
-        rotate / scale the crops are lists of source boxes and every sample is re-origined by its box's low corner"""
+        rotate / scale / elastic the crops are lists of source boxes and every sample is re-origined by its box's low corner"""
         imgs, labs, idx = crops
         params = [self.params(i) for i in idx]
         if self.affine:

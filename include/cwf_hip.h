@@ -604,6 +604,32 @@ struct cwf_prep_affine_sample {
  * that every origin is accepted, and for a non-finite m entry; CWF_E_TOOLARGE: 2^31 output voxels or more. */
 int cwf_prepare_batch_affine(const struct cwf_prep_affine_sample* h_samples, int B, int C0, int C1, int C2, float* x,
                              int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream);
+/* cwf_prep_affine_sample plus the control grid of an elastic deformation: disp is DEVICE memory, fp32 [3][G0][G1][G2] (4-byte
+ * aligned), displacements in voxels of the crop-local source coordinate q; 4 <= G_d <= 8.  disp == NULL: no deformation, G* unused. */
+struct cwf_prep_elastic_sample {
+  const float* image; const uint8_t* label;
+  int S0, S1, S2, o0, o1, o2, flip, intensity;
+  float scale[4], shift[4];
+  float m[9];
+  const float* disp;
+  int G0, G1, G2;
+};
+/* cwf_prepare_batch_affine with D added to the source coordinate, D a uniform cubic B-spline of the flipped output index p' over the
+ * control grid.  Every operation is a float32 round-to-nearest one in the association written (no fused multiply-add); along axis d
+ *   k_d  = float(G_d - 3) / float(C_d - 1)                      (correctly rounded; 0 when C_d == 1)
+ *   g_d  = p'_d * k_d + 1;  i_d = floor(g_d);  t = g_d - i_d;  s = 1 - t;  h = float(1/6)
+ *   w0 = ((s*s)*s)*h   w1 = ((((3*t - 6)*t)*t) + 4)*h   w2 = ((((-3*t + 3)*t + 3)*t) + 1)*h   w3 = ((t*t)*t)*h
+ *   control index along d for j = 0..3: clamp(i_d - 1 + j, 0, G_d - 1)   (only i_d + 2 == G_d is ever clamped, where w3 is 0 or one
+ *                                                                        rounding away from it)
+ *   D_c  = sum_j0 w[0][j0] * (sum_j1 w[1][j1] * (sum_j2 w[2][j2] * disp[c][..][..][..])),  every 4-term sum as ((a + b) + c) + d
+ *   q_c  = (cwf_prepare_batch_affine's q_c) + D_c
+ * and x, target and edge follow from q as there, the |q_d| < 2^30 test being made on this final q: a NaN or huge control value makes
+ * the voxels it reaches read nothing (image 0, label 0), and no value of disp can cause a read outside the volumes or the grid.  A
+ * sample with disp == NULL gets no addition at all and is bit-equal to cwf_prepare_batch_affine's output for it.  The grids are read
+ * when the kernel runs: they must stay valid until then.  CWF_E_BADARG as for cwf_prepare_batch_affine, and for a non-NULL disp that
+ * is misaligned or comes with some G_d outside 4..8. */
+int cwf_prepare_batch_elastic(const struct cwf_prep_elastic_sample* h_samples, int B, int C0, int C1, int C2, float* x,
+                              int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream);
 /* In place on one subject image fp32 [4][V]: over the voxels whose ((x0 + x1) + x2) + x3 > 0 (float32), each channel becomes
  * float32((x - mean_c) / std_c) with the float64 mean and population std of that channel over those voxels (two passes); other voxels,
  * and channels with std 0, are untouched.  ws: CWF_NORM_WS_DOUBLES doubles of device scratch. */

@@ -19,33 +19,36 @@
 // four voxels, or outputs without 16-B alignment, take the same kernel with per-voxel stores.
 //
 // cwf_prepare_batch_affine: the same outputs from a rotated and zoomed crop (trilinear image, nearest label), a kernel of its own
-// further down that shares the bit helpers and the pass structure.  cwf_prepare_batch_elastic: that kernel's second instantiation,
-// which adds a cubic B-spline displacement to every source coordinate.
+// further down on an 8 x 8 x 32 tile.  cwf_prepare_batch_elastic: that kernel's second instantiation, which adds a cubic B-spline
+// displacement to every source coordinate.
+//
+// What the kernels share is written once: the tile description (PrepTile), the three passes with the target / edge store
+// (prep_tail), the image-quad store (prep_store_quad) and, on the host, the checks and the launch loop of all three entries
+// (prep_launch).  A kernel keeps its own halo fill and image pass.  The samples travel as the public structs of include/cwf_hip.h.
 //
 // cwf_normalize_nonzero: per-channel z-score over the voxels whose four-channel sum ((x0 + x1) + x2) + x3 (float32) is > 0, float64
 // two-pass statistics (partials per workgroup, reduced in a fixed order by one thread: the result does not depend on scheduling).
 // This file is compiled with -ffp-contract=off.
 #include "common.h"
 
-#define PREP_T0 4
-#define PREP_T1 16
-#define PREP_T2 64
-#define PREP_Q2 (PREP_T2 / 4)              // quads per tile row
-#define PREP_H0 (PREP_T0 + 2)
-#define PREP_H1 (PREP_T1 + 2)
-#define PREP_H2 (PREP_T2 + 2)
-#define PREP_ROW 68                         // halo row bytes (66 used, padded to whole words)
 #define PREP_MAXS 8                         // samples per launch
 
-struct PrepSample {
-  const float* image;
-  const uint8_t* label;
-  int S0, S1, S2, o0, o1, o2, flip, intensity;
-  float scale[4], shift[4];
+// the T0 x T1 x T2 output voxels of a 256-thread workgroup and what follows from them
+template <int T0_, int T1_, int T2_>
+struct PrepTile {
+  static constexpr int T0 = T0_, T1 = T1_, T2 = T2_;
+  static constexpr int Q2 = T2 / 4;                           // quads per tile row
+  static constexpr int H0 = T0 + 2, H1 = T1 + 2, H2 = T2 + 2; // the tile with its one-voxel halo
+  static constexpr int ROW = (H2 + 3) / 4 * 4;                // halo row bytes (H2 used, padded to whole words)
+  static constexpr int QUADS = T0 * T1 * Q2 / 256;            // quads per thread
+  static_assert(T2 % 4 == 0 && QUADS * 256 == T0 * T1 * Q2, "whole quads, the same number for every thread");
 };
+typedef PrepTile<4, 16, 64> PlainTile;      // 68-byte halo row, one quad per thread and axis-0 slice
+typedef PrepTile<8, 8, 32> AffTile;         // 36-byte halo row (the choice: further down)
 
+template <class Sample>
 struct PrepArgs {
-  PrepSample s[PREP_MAXS];
+  Sample s[PREP_MAXS];
   float* x;
   int64_t* target;
   int64_t* edge;
@@ -71,97 +74,47 @@ __device__ __forceinline__ int64_t prep_code(uint32_t band) {
   return (int64_t)((0x58746210u >> (4u * band)) & 0xFu);
 }
 
-__global__ __launch_bounds__(256) void prep_batch_kernel(const PrepArgs a) {
-  __shared__ __attribute__((aligned(16))) uint8_t H[PREP_H0][PREP_H1][PREP_ROW];
-  __shared__ uint32_t P1[PREP_H0][PREP_H1][PREP_Q2];
-  __shared__ uint32_t P2[PREP_H0][PREP_T1][PREP_Q2];
-  const PrepSample& S = a.s[blockIdx.y];
+// one channel's quad of image voxels at d, the quad starting at output index p2 of a row of C2 voxels
+__device__ __forceinline__ void prep_store_quad(float* d, const float (&v)[4], int vec, int p2, int C2) {
+  if (vec) {
+    f32x4 o = {v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(d) = o;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (p2 + e < C2) d[e] = v[e];
+  }
+}
+
+// The part every kernel ends with, entered after the barrier that completes the label-bit halo H of the tile at (b0, b1, b2): the
+// axis-2 and axis-1 passes through P1 and P2, the axis-0 pass in registers, and target and edge of the tile's voxels.
+template <class T, class Args>
+__device__ __forceinline__ void prep_tail(uint8_t (&H)[T::H0][T::H1][T::ROW], uint32_t (&P1)[T::H0][T::H1][T::Q2],
+                                                 uint32_t (&P2)[T::H0][T::T1][T::Q2], const Args& a, int b0, int b1, int b2) {
   const int C0 = a.C0, C1 = a.C1, C2 = a.C2;
-  const int n2 = (C2 + PREP_T2 - 1) / PREP_T2, n1 = (C1 + PREP_T1 - 1) / PREP_T1;
-  const int t = blockIdx.x;
-  const int b2 = (t % n2) * PREP_T2, b1 = ((t / n2) % n1) * PREP_T1, b0 = (t / (n2 * n1)) * PREP_T0;
-  const int f0 = S.flip & 1, f1 = (S.flip >> 1) & 1, f2 = (S.flip >> 2) & 1;
-  const int64_t plane = (int64_t)S.S1 * S.S2, V = (int64_t)S.S0 * plane;
   const int tid = threadIdx.x;
-
-  // 1. label bits of the halo tile
-  for (int i = tid; i < PREP_H0 * PREP_H1 * PREP_H2; i += 256) {
-    const int h2 = i % PREP_H2, h1 = (i / PREP_H2) % PREP_H1, h0 = i / (PREP_H2 * PREP_H1);
-    const int p0 = b0 + h0 - 1, p1 = b1 + h1 - 1, p2 = b2 + h2 - 1;
-    uint32_t v = 0x38u;                                       // out of the crop: identity of OR and AND
-    if (p0 >= 0 && p0 < C0 && p1 >= 0 && p1 < C1 && p2 >= 0 && p2 < C2) {
-      const int s0 = S.o0 + (f0 ? C0 - 1 - p0 : p0), s1 = S.o1 + (f1 ? C1 - 1 - p1 : p1), s2 = S.o2 + (f2 ? C2 - 1 - p2 : p2);
-      v = (s0 < S.S0 && s1 < S.S1 && s2 < S.S2) ? prep_bits(S.label[s0 * plane + (int64_t)s1 * S.S2 + s2]) : 0u;
-    }
-    H[h0][h1][h2] = (uint8_t)v;
-  }
-
-  // 2. image: independent of the label tile, issued before the first barrier's wait
-  const bool inten = S.intensity != 0;
-  const int64_t V_out = (int64_t)C0 * C1 * C2;
-  float* xs = a.x + (int64_t)blockIdx.y * a.x_bs;
-#pragma unroll 1
-  for (int k = 0; k < PREP_T0; ++k) {
-    const int q = tid + 256 * k;
-    const int w = q % PREP_Q2, j = (q / PREP_Q2) % PREP_T1, i = q / (PREP_Q2 * PREP_T1);
-    const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
-    if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
-    const int s0 = S.o0 + (f0 ? C0 - 1 - p0 : p0), s1 = S.o1 + (f1 ? C1 - 1 - p1 : p1);
-    const bool row_in = s0 < S.S0 && s1 < S.S1;
-    const int64_t src_row = s0 * plane + (int64_t)s1 * S.S2;
-    const int64_t dst = ((int64_t)p0 * C1 + p1) * C2 + p2;
-    int s2[4];
-    bool in[4], out_ok[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      out_ok[e] = p2 + e < C2;
-      s2[e] = S.o2 + (f2 ? C2 - 1 - (p2 + e) : p2 + e);
-      in[e] = row_in && out_ok[e] && s2[e] < S.S2;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float* src = S.image + c * V + src_row;
-      float v[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = in[e] ? src[s2[e]] : 0.f;
-        if (inten) v[e] = __fadd_rn(__fmul_rn(v[e], S.scale[c]), S.shift[c]);
-      }
-      float* d = xs + c * V_out + dst;
-      if (a.vec) {
-        f32x4 o = {v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(d) = o;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (out_ok[e]) d[e] = v[e];
-      }
-    }
-  }
-  __syncthreads();
-
-  // 3. axis-2 pass: [6][18][16 quads]
-  for (int i = tid; i < PREP_H0 * PREP_H1 * PREP_Q2; i += 256) {
-    const int w = i % PREP_Q2, h1 = (i / PREP_Q2) % PREP_H1, h0 = i / (PREP_Q2 * PREP_H1);
+  // axis-2 pass: [H0][H1][Q2 quads]
+  for (int i = tid; i < T::H0 * T::H1 * T::Q2; i += 256) {
+    const int w = i % T::Q2, h1 = (i / T::Q2) % T::H1, h0 = i / (T::Q2 * T::H1);
     const uint32_t* row = reinterpret_cast<const uint32_t*>(&H[h0][h1][0]);
     const uint32_t w0 = row[w], w1 = row[w + 1];
     P1[h0][h1][w] = prep_or_and(w0, (w0 >> 8) | (w1 << 24), (w0 >> 16) | (w1 << 16));
   }
   __syncthreads();
-  // 4. axis-1 pass: [6][16][16]
-  for (int i = tid; i < PREP_H0 * PREP_T1 * PREP_Q2; i += 256) {
-    const int w = i % PREP_Q2, j = (i / PREP_Q2) % PREP_T1, h0 = i / (PREP_Q2 * PREP_T1);
+  // axis-1 pass: [H0][T1][Q2]
+  for (int i = tid; i < T::H0 * T::T1 * T::Q2; i += 256) {
+    const int w = i % T::Q2, j = (i / T::Q2) % T::T1, h0 = i / (T::Q2 * T::T1);
     P2[h0][j][w] = prep_or_and(P1[h0][j][w], P1[h0][j + 1][w], P1[h0][j + 2][w]);
   }
   __syncthreads();
 
-  // 5. axis-0 pass in registers, target and edge codes
+  // axis-0 pass in registers, target and edge codes
   int64_t* ts = a.target + (int64_t)blockIdx.y * a.t_bs;
   int64_t* es = a.edge + (int64_t)blockIdx.y * a.e_bs;
 #pragma unroll 1
-  for (int k = 0; k < PREP_T0; ++k) {
+  for (int k = 0; k < T::QUADS; ++k) {
     const int q = tid + 256 * k;
-    const int w = q % PREP_Q2, j = (q / PREP_Q2) % PREP_T1, i = q / (PREP_Q2 * PREP_T1);
+    const int w = q % T::Q2, j = (q / T::Q2) % T::T1, i = q / (T::Q2 * T::T1);
     const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
     if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
     const uint32_t r = prep_or_and(P2[i][j][w], P2[i + 1][j][w], P2[i + 2][j][w]);
@@ -194,48 +147,67 @@ __global__ __launch_bounds__(256) void prep_batch_kernel(const PrepArgs a) {
   }
 }
 
-extern "C" int cwf_prepare_batch(const struct cwf_prep_sample* h_samples, int B, int C0, int C1, int C2, float* x, int64_t x_bstride,
-                                 int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream) {
-  if (!h_samples || B <= 0 || C0 <= 0 || C1 <= 0 || C2 <= 0 || !x || !target || !edge) return CWF_E_BADARG;
-  const int64_t V = (int64_t)C0 * C1 * C2;
-  if (V >= (int64_t(1) << 31)) return CWF_E_TOOLARGE;
-  if (((uintptr_t)x & 3) || ((uintptr_t)target & 7) || ((uintptr_t)edge & 7)) return CWF_E_BADARG;
-  if (x_bstride < 4 * V || t_bstride < V || e_bstride < V) return CWF_E_BADARG;
-  const int C[3] = {C0, C1, C2};
-  for (int b = 0; b < B; ++b) {
-    const cwf_prep_sample& s = h_samples[b];
-    if (!s.image || !s.label || ((uintptr_t)s.image & 3) || s.flip < 0 || s.flip > 7) return CWF_E_BADARG;
-    const int Sx[3] = {s.S0, s.S1, s.S2}, o[3] = {s.o0, s.o1, s.o2};
-    for (int d = 0; d < 3; ++d)
-      if (Sx[d] <= 0 || o[d] < 0 || o[d] > std::max(Sx[d] - C[d], 0)) return CWF_E_BADARG;
-  }
-  PrepArgs a;
-  a.x = x; a.target = target; a.edge = edge;
-  a.x_bs = x_bstride; a.t_bs = t_bstride; a.e_bs = e_bstride;
-  a.C0 = C0; a.C1 = C1; a.C2 = C2;
-  a.vec = (C2 % 4 == 0) && !((uintptr_t)x & 15) && !((uintptr_t)target & 15) && !((uintptr_t)edge & 15) && x_bstride % 4 == 0 &&
-          t_bstride % 2 == 0 && e_bstride % 2 == 0;
-  const int64_t tiles = (int64_t)cdiv(C0, PREP_T0) * cdiv(C1, PREP_T1) * cdiv(C2, PREP_T2);
-  hipStream_t st = cwf_stream(stream);
-  for (int b0 = 0; b0 < B; b0 += PREP_MAXS) {
-    const int nb = std::min(PREP_MAXS, B - b0);
-    for (int i = 0; i < PREP_MAXS; ++i) {
-      PrepSample& d = a.s[i];
-      if (i >= nb) { d = PrepSample{}; continue; }
-      const cwf_prep_sample& s = h_samples[b0 + i];
-      d.image = s.image; d.label = s.label;
-      d.S0 = s.S0; d.S1 = s.S1; d.S2 = s.S2; d.o0 = s.o0; d.o1 = s.o1; d.o2 = s.o2;
-      d.flip = s.flip; d.intensity = s.intensity;
-      for (int c = 0; c < 4; ++c) { d.scale[c] = s.scale[c]; d.shift[c] = s.shift[c]; }
+__global__ __launch_bounds__(256) void prep_batch_kernel(const PrepArgs<cwf_prep_sample> a) {
+  typedef PlainTile T;
+  __shared__ __attribute__((aligned(16))) uint8_t H[T::H0][T::H1][T::ROW];
+  __shared__ uint32_t P1[T::H0][T::H1][T::Q2];
+  __shared__ uint32_t P2[T::H0][T::T1][T::Q2];
+  const cwf_prep_sample& S = a.s[blockIdx.y];
+  const int C0 = a.C0, C1 = a.C1, C2 = a.C2;
+  const int n2 = (C2 + T::T2 - 1) / T::T2, n1 = (C1 + T::T1 - 1) / T::T1;
+  const int t = blockIdx.x;
+  const int b2 = (t % n2) * T::T2, b1 = ((t / n2) % n1) * T::T1, b0 = (t / (n2 * n1)) * T::T0;
+  const int f0 = S.flip & 1, f1 = (S.flip >> 1) & 1, f2 = (S.flip >> 2) & 1;
+  const int64_t plane = (int64_t)S.S1 * S.S2, V = (int64_t)S.S0 * plane;
+  const int tid = threadIdx.x;
+
+  // 1. label bits of the halo tile
+  for (int i = tid; i < T::H0 * T::H1 * T::H2; i += 256) {
+    const int h2 = i % T::H2, h1 = (i / T::H2) % T::H1, h0 = i / (T::H2 * T::H1);
+    const int p0 = b0 + h0 - 1, p1 = b1 + h1 - 1, p2 = b2 + h2 - 1;
+    uint32_t v = 0x38u;                                       // out of the crop: identity of OR and AND
+    if (p0 >= 0 && p0 < C0 && p1 >= 0 && p1 < C1 && p2 >= 0 && p2 < C2) {
+      const int s0 = S.o0 + (f0 ? C0 - 1 - p0 : p0), s1 = S.o1 + (f1 ? C1 - 1 - p1 : p1), s2 = S.o2 + (f2 ? C2 - 1 - p2 : p2);
+      v = (s0 < S.S0 && s1 < S.S1 && s2 < S.S2) ? prep_bits(S.label[s0 * plane + (int64_t)s1 * S.S2 + s2]) : 0u;
     }
-    PrepArgs ab = a;
-    ab.x = x + (int64_t)b0 * x_bstride;
-    ab.target = target + (int64_t)b0 * t_bstride;
-    ab.edge = edge + (int64_t)b0 * e_bstride;
-    hipLaunchKernelGGL(prep_batch_kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, st, ab);
-    CWF_LAUNCH_CHECK();
+    H[h0][h1][h2] = (uint8_t)v;
   }
-  return 0;
+
+  // 2. image: independent of the label tile, issued before the first barrier's wait
+  const bool inten = S.intensity != 0;
+  const int64_t V_out = (int64_t)C0 * C1 * C2;
+  float* xs = a.x + (int64_t)blockIdx.y * a.x_bs;
+#pragma unroll 1
+  for (int k = 0; k < T::QUADS; ++k) {
+    const int q = tid + 256 * k;
+    const int w = q % T::Q2, j = (q / T::Q2) % T::T1, i = q / (T::Q2 * T::T1);
+    const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
+    if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
+    const int s0 = S.o0 + (f0 ? C0 - 1 - p0 : p0), s1 = S.o1 + (f1 ? C1 - 1 - p1 : p1);
+    const bool row_in = s0 < S.S0 && s1 < S.S1;
+    const int64_t src_row = s0 * plane + (int64_t)s1 * S.S2;
+    const int64_t dst = ((int64_t)p0 * C1 + p1) * C2 + p2;
+    int s2[4];
+    bool in[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s2[e] = S.o2 + (f2 ? C2 - 1 - (p2 + e) : p2 + e);
+      in[e] = row_in && p2 + e < C2 && s2[e] < S.S2;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float* src = S.image + c * V + src_row;
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[e] = in[e] ? src[s2[e]] : 0.f;
+        if (inten) v[e] = __fadd_rn(__fmul_rn(v[e], S.scale[c]), S.shift[c]);
+      }
+      prep_store_quad(xs + c * V_out + dst, v, a.vec, p2, C2);
+    }
+  }
+  __syncthreads();
+  prep_tail<T>(H, P1, P2, a, b0, b1, b2);
 }
 
 // ------------------------------------------------------------------------------------------------ rotated / zoomed crops
@@ -245,53 +217,23 @@ extern "C" int cwf_prepare_batch(const struct cwf_prep_sample* h_samples, int B,
 // as large along every axis as the tile's longest side, so the tile is kept near-cubic: 8 x 8 x 32 touches about 43 KB of image
 // (four channels) where 4 x 16 x 64 would touch several times that, and its taps are served by the CU's vector cache and L2.  LDS:
 // halo [10][10][36 B], passes [10][10][8] and [10][8][8] words (9.4 KiB).
-#define AFF_T0 8
-#define AFF_T1 8
-#define AFF_T2 32
-#define AFF_Q2 (AFF_T2 / 4)
-#define AFF_H0 (AFF_T0 + 2)
-#define AFF_H1 (AFF_T1 + 2)
-#define AFF_H2 (AFF_T2 + 2)
-#define AFF_ROW 36                          // halo row bytes (34 used, padded to whole words)
-#define AFF_QUADS (AFF_T0 * AFF_T1 * AFF_Q2 / 256)
 #define AFF_QMAX 1073741824.f               // |q| at and beyond 2^30 (and NaN): the voxel lies outside every volume
 
-struct PrepAffSample {
-  const float* image;
-  const uint8_t* label;
-  int S0, S1, S2, o0, o1, o2, flip, intensity;
-  float scale[4], shift[4];
-  float m[9];
-};
-
-// the elastic entry's sample: disp == nullptr adds nothing; k[d] = float(G_d - 3) / float(C_d - 1), divided on the host
-struct PrepElaSample : PrepAffSample {
-  const float* disp;
-  int G0, G1, G2;
+// the elastic entry's sample on the device: G* zeroed when disp == nullptr (nothing is added); k[d] = float(G_d - 3) / float(C_d - 1),
+// divided on the host
+struct PrepElaSample : cwf_prep_elastic_sample {
   float k[3];
 };
-
-template <class Sample>
-struct PrepResArgs {
-  Sample s[PREP_MAXS];
-  float* x;
-  int64_t* target;
-  int64_t* edge;
-  int64_t x_bs, t_bs, e_bs;
-  int C0, C1, C2, vec;
-};
-typedef PrepResArgs<PrepAffSample> PrepAffArgs;
-typedef PrepResArgs<PrepElaSample> PrepElaArgs;
-static_assert(sizeof(PrepElaArgs) <= 4096, "the samples travel by value in the kernel-argument block");
+static_assert(sizeof(PrepArgs<PrepElaSample>) <= 4096, "the samples travel by value in the kernel-argument block");
 
 // crop-local source coordinate of the (already flipped) output voxel (p0, p1, p2); false when it is not representable
-__device__ __forceinline__ bool aff_coord(const PrepAffSample& S, int p0, int p1, int p2, float c0, float c1, float c2, float q[3]) {
+__device__ __forceinline__ bool aff_coord(const float (&m)[9], int p0, int p1, int p2, float c0, float c1, float c2, float q[3]) {
   const float u0 = __fsub_rn((float)p0, c0), u1 = __fsub_rn((float)p1, c1), u2 = __fsub_rn((float)p2, c2);
   const float c[3] = {c0, c1, c2};
   bool ok = true;
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
-    q[d] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(S.m[3 * d], u0), __fmul_rn(S.m[3 * d + 1], u1)), __fmul_rn(S.m[3 * d + 2], u2)), c[d]);
+    q[d] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[3 * d], u0), __fmul_rn(m[3 * d + 1], u1)), __fmul_rn(m[3 * d + 2], u2)), c[d]);
     ok = ok && fabsf(q[d]) < AFF_QMAX;
   }
   return ok;
@@ -304,7 +246,7 @@ __device__ __forceinline__ float aff_lerp(float a, float b, float f) { return __
 // table rows and 64 control points.  The sample's whole grid (at most 8^3 points, the three components of a point side by side) is
 // staged in LDS, so no control index ever forms a global address: 8 KiB for the grid and 1.7 KiB for the tables.
 #define ELA_GMAX 8
-#define ELA_ROWS (AFF_H0 + AFF_H1 + AFF_H2)
+#define ELA_ROWS (AffTile::H0 + AffTile::H1 + AffTile::H2)
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct ElaTables {
@@ -341,12 +283,12 @@ __device__ __forceinline__ void ela_setup(const PrepElaSample& S, ElaTables& T, 
   if (tid >= ELA_ROWS) return;
   f32x4 w;
   i32x4 ix;
-  if (tid < AFF_H0)
+  if (tid < AffTile::H0)
     ela_axis(b0 + tid - 1, C0, S.flip & 1, S.G0, S.k[0], S.G1 * S.G2, w, ix);
-  else if (tid < AFF_H0 + AFF_H1)
-    ela_axis(b1 + (tid - AFF_H0) - 1, C1, (S.flip >> 1) & 1, S.G1, S.k[1], S.G2, w, ix);
+  else if (tid < AffTile::H0 + AffTile::H1)
+    ela_axis(b1 + (tid - AffTile::H0) - 1, C1, (S.flip >> 1) & 1, S.G1, S.k[1], S.G2, w, ix);
   else
-    ela_axis(b2 + (tid - AFF_H0 - AFF_H1) - 1, C2, (S.flip >> 2) & 1, S.G2, S.k[2], 1, w, ix);
+    ela_axis(b2 + (tid - AffTile::H0 - AffTile::H1) - 1, C2, (S.flip >> 2) & 1, S.G2, S.k[2], 1, w, ix);
   T.w[tid] = w;
   T.ix[tid] = ix;
 }
@@ -355,8 +297,8 @@ __device__ __forceinline__ void ela_setup(const PrepElaSample& S, ElaTables& T, 
 // is not unrolled (a running ((a + b) + c) + d is the same association): unrolled, the 64 control points of each of a thread's four
 // voxels are all fetched ahead and the kernel needs several times the registers.
 __device__ __forceinline__ bool ela_displace(const ElaTables& T, int h0, int h1, int h2, float q[3]) {
-  const f32x4 w1 = T.w[AFF_H0 + h1], w2 = T.w[AFF_H0 + AFF_H1 + h2];
-  const i32x4 i1 = T.ix[AFF_H0 + h1], i2 = T.ix[AFF_H0 + AFF_H1 + h2];
+  const f32x4 w1 = T.w[AffTile::H0 + h1], w2 = T.w[AffTile::H0 + AffTile::H1 + h2];
+  const i32x4 i1 = T.ix[AffTile::H0 + h1], i2 = T.ix[AffTile::H0 + AffTile::H1 + h2];
   const float* w0 = reinterpret_cast<const float*>(&T.w[h0]);
   const int* i0 = reinterpret_cast<const int*>(&T.ix[h0]);
   float D[3] = {0.f, 0.f, 0.f};
@@ -390,23 +332,24 @@ __device__ __forceinline__ bool ela_displace(const ElaTables& T, int h0, int h1,
 template <bool DISP, class Sample>
 __device__ __forceinline__ bool res_coord(const Sample& S, const ElaTables* T, bool disp, int p0, int p1, int p2, int h0, int h1, int h2,
                                           int C0, int C1, int C2, float c0, float c1, float c2, float q[3]) {
-  const bool ok = aff_coord(S, (S.flip & 1) ? C0 - 1 - p0 : p0, (S.flip & 2) ? C1 - 1 - p1 : p1, (S.flip & 4) ? C2 - 1 - p2 : p2, c0, c1, c2, q);
+  const bool ok = aff_coord(S.m, (S.flip & 1) ? C0 - 1 - p0 : p0, (S.flip & 2) ? C1 - 1 - p1 : p1, (S.flip & 4) ? C2 - 1 - p2 : p2, c0, c1, c2, q);
   if constexpr (DISP) {
     if (disp) return ela_displace(*T, h0, h1, h2, q);          // the test is on the final q alone
   }
   return ok;
 }
 
-template <bool DISP, class Args>
-__global__ __launch_bounds__(256) void prep_affine_kernel(const Args a) {
-  __shared__ __attribute__((aligned(16))) uint8_t H[AFF_H0][AFF_H1][AFF_ROW];
-  __shared__ uint32_t P1[AFF_H0][AFF_H1][AFF_Q2];
-  __shared__ uint32_t P2[AFF_H0][AFF_T1][AFF_Q2];
-  const auto& S = a.s[blockIdx.y];
+template <class Sample>
+__global__ __launch_bounds__(256) void prep_affine_kernel(const PrepArgs<Sample> a) {
+  constexpr bool DISP = std::is_same<Sample, PrepElaSample>::value;
+  __shared__ __attribute__((aligned(16))) uint8_t H[AffTile::H0][AffTile::H1][AffTile::ROW];
+  __shared__ uint32_t P1[AffTile::H0][AffTile::H1][AffTile::Q2];
+  __shared__ uint32_t P2[AffTile::H0][AffTile::T1][AffTile::Q2];
+  const Sample& S = a.s[blockIdx.y];
   const int C0 = a.C0, C1 = a.C1, C2 = a.C2;
-  const int n2 = (C2 + AFF_T2 - 1) / AFF_T2, n1 = (C1 + AFF_T1 - 1) / AFF_T1;
+  const int n2 = (C2 + AffTile::T2 - 1) / AffTile::T2, n1 = (C1 + AffTile::T1 - 1) / AffTile::T1;
   const int t = blockIdx.x;
-  const int b2 = (t % n2) * AFF_T2, b1 = ((t / n2) % n1) * AFF_T1, b0 = (t / (n2 * n1)) * AFF_T0;
+  const int b2 = (t % n2) * AffTile::T2, b1 = ((t / n2) % n1) * AffTile::T1, b0 = (t / (n2 * n1)) * AffTile::T0;
   const float c0 = 0.5f * (float)(C0 - 1), c1 = 0.5f * (float)(C1 - 1), c2 = 0.5f * (float)(C2 - 1);
   const int64_t S0 = S.S0, S1 = S.S1, S2 = S.S2, plane = S1 * S2, V = S0 * plane;
   const int tid = threadIdx.x;
@@ -421,8 +364,8 @@ __global__ __launch_bounds__(256) void prep_affine_kernel(const Args a) {
   }
 
   // 1. label bits of the halo tile, through the nearest-neighbour map
-  for (int i = tid; i < AFF_H0 * AFF_H1 * AFF_H2; i += 256) {
-    const int h2 = i % AFF_H2, h1 = (i / AFF_H2) % AFF_H1, h0 = i / (AFF_H2 * AFF_H1);
+  for (int i = tid; i < AffTile::H0 * AffTile::H1 * AffTile::H2; i += 256) {
+    const int h2 = i % AffTile::H2, h1 = (i / AffTile::H2) % AffTile::H1, h0 = i / (AffTile::H2 * AffTile::H1);
     const int p0 = b0 + h0 - 1, p1 = b1 + h1 - 1, p2 = b2 + h2 - 1;
     uint32_t v = 0x38u;                                       // out of the crop: identity of OR and AND
     if (p0 >= 0 && p0 < C0 && p1 >= 0 && p1 < C1 && p2 >= 0 && p2 < C2) {
@@ -442,9 +385,9 @@ __global__ __launch_bounds__(256) void prep_affine_kernel(const Args a) {
   const int64_t V_out = (int64_t)C0 * C1 * C2;
   float* xs = a.x + (int64_t)blockIdx.y * a.x_bs;
 #pragma unroll 1
-  for (int k = 0; k < AFF_QUADS; ++k) {
+  for (int k = 0; k < AffTile::QUADS; ++k) {
     const int qd = tid + 256 * k;
-    const int w = qd % AFF_Q2, j = (qd / AFF_Q2) % AFF_T1, i = qd / (AFF_Q2 * AFF_T1);
+    const int w = qd % AffTile::Q2, j = (qd / AffTile::Q2) % AffTile::T1, i = qd / (AffTile::Q2 * AffTile::T1);
     const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
     if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
     const int64_t dst = ((int64_t)p0 * C1 + p1) * C2 + p2;
@@ -491,141 +434,97 @@ __global__ __launch_bounds__(256) void prep_affine_kernel(const Args a) {
       }
     }
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float* d = xs + c * V_out + dst;
-      if (a.vec) {
-        f32x4 o = {v[c][0], v[c][1], v[c][2], v[c][3]};
-        *reinterpret_cast<f32x4*>(d) = o;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (p2 + e < C2) d[e] = v[c][e];
-      }
-    }
+    for (int c = 0; c < 4; ++c) prep_store_quad(xs + c * V_out + dst, v[c], a.vec, p2, C2);
   }
   __syncthreads();
-
-  // 3. axis-2 pass: [10][10][8 quads]
-  for (int i = tid; i < AFF_H0 * AFF_H1 * AFF_Q2; i += 256) {
-    const int w = i % AFF_Q2, h1 = (i / AFF_Q2) % AFF_H1, h0 = i / (AFF_Q2 * AFF_H1);
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(&H[h0][h1][0]);
-    const uint32_t w0 = row[w], w1 = row[w + 1];
-    P1[h0][h1][w] = prep_or_and(w0, (w0 >> 8) | (w1 << 24), (w0 >> 16) | (w1 << 16));
-  }
-  __syncthreads();
-  // 4. axis-1 pass: [10][8][8]
-  for (int i = tid; i < AFF_H0 * AFF_T1 * AFF_Q2; i += 256) {
-    const int w = i % AFF_Q2, j = (i / AFF_Q2) % AFF_T1, h0 = i / (AFF_Q2 * AFF_T1);
-    P2[h0][j][w] = prep_or_and(P1[h0][j][w], P1[h0][j + 1][w], P1[h0][j + 2][w]);
-  }
-  __syncthreads();
-
-  // 5. axis-0 pass in registers, target and edge codes
-  int64_t* ts = a.target + (int64_t)blockIdx.y * a.t_bs;
-  int64_t* es = a.edge + (int64_t)blockIdx.y * a.e_bs;
-#pragma unroll 1
-  for (int k = 0; k < AFF_QUADS; ++k) {
-    const int qd = tid + 256 * k;
-    const int w = qd % AFF_Q2, j = (qd / AFF_Q2) % AFF_T1, i = qd / (AFF_Q2 * AFF_T1);
-    const int p0 = b0 + i, p1 = b1 + j, p2 = b2 + 4 * w;
-    if (p0 >= C0 || p1 >= C1 || p2 >= C2) continue;
-    const uint32_t r = prep_or_and(P2[i][j][w], P2[i + 1][j][w], P2[i + 2][j][w]);
-    const uint32_t band = (r & 0x07070707u) & ~((r >> 3) & 0x07070707u);
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(&H[i + 1][j + 1][0]);
-    const uint32_t centre = (row[w] >> 8) | (row[w + 1] << 24);
-    int64_t tl[4], ec[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      tl[e] = prep_label((centre >> (8 * e)) & 0xFFu);
-      ec[e] = prep_code((band >> (8 * e)) & 0xFFu);
-    }
-    const int64_t dst = ((int64_t)p0 * C1 + p1) * C2 + p2;
-    if (a.vec) {
-      typedef long long i64x2 __attribute__((ext_vector_type(2)));
-      i64x2* tp = reinterpret_cast<i64x2*>(ts + dst);
-      i64x2* ep = reinterpret_cast<i64x2*>(es + dst);
-      tp[0] = i64x2{tl[0], tl[1]};
-      tp[1] = i64x2{tl[2], tl[3]};
-      ep[0] = i64x2{ec[0], ec[1]};
-      ep[1] = i64x2{ec[2], ec[3]};
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (p2 + e < C2) {
-          ts[dst + e] = tl[e];
-          es[dst + e] = ec[e];
-        }
-    }
-  }
+  prep_tail<AffTile>(H, P1, P2, a, b0, b1, b2);
 }
 
-// both entries: the argument checks, then one launch per eight samples
-template <bool DISP, class HostSample>
-static int prep_resampled(const HostSample* h_samples, int B, int C0, int C1, int C2, float* x, int64_t x_bstride, int64_t* target,
-                          int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream) {
-  typedef typename std::conditional<DISP, PrepElaSample, PrepAffSample>::type Sample;
+// ------------------------------------------------------------------------------------------------ the three entries
+// what an entry asks of a sample beyond the common checks of prep_launch
+static bool prep_all_finite(const float (&m)[9]) {
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(m[k])) return false;
+  return true;
+}
+static bool prep_sample_ok(const cwf_prep_sample& s, const int (&C)[3]) {
+  const int S[3] = {s.S0, s.S1, s.S2}, o[3] = {s.o0, s.o1, s.o2};
+  for (int d = 0; d < 3; ++d)
+    if (o[d] < 0 || o[d] > std::max(S[d] - C[d], 0)) return false;
+  return true;
+}
+static bool prep_sample_ok(const cwf_prep_affine_sample& s, const int (&)[3]) { return prep_all_finite(s.m); }
+static bool prep_sample_ok(const cwf_prep_elastic_sample& s, const int (&)[3]) {
+  const int G[3] = {s.G0, s.G1, s.G2};
+  for (int d = 0; d < 3; ++d)
+    if (s.disp && (((uintptr_t)s.disp & 3) || G[d] < 4 || G[d] > ELA_GMAX)) return false;
+  return prep_all_finite(s.m);
+}
+
+// the sample as the kernel takes it: the public struct itself, for the elastic kernel with what PrepElaSample adds
+template <class Sample>
+static void prep_pack(Sample& d, const Sample& s, const int (&)[3]) { d = s; }
+static void prep_pack(PrepElaSample& d, const cwf_prep_elastic_sample& s, const int (&C)[3]) {
+  static_cast<cwf_prep_elastic_sample&>(d) = s;
+  if (!s.disp) d.G0 = d.G1 = d.G2 = 0;
+  const int G[3] = {d.G0, d.G1, d.G2};
+  for (int k = 0; k < 3; ++k) d.k[k] = (s.disp && C[k] > 1) ? (float)(G[k] - 3) / (float)(C[k] - 1) : 0.f;
+}
+
+// every entry: the argument checks (nothing is launched on a refusal), then one launch of kernel, which works on Tile, per eight samples
+template <class Tile, class Sample, class HostSample>
+static int prep_launch(void (*kernel)(PrepArgs<Sample>), const HostSample* h_samples, int B, int C0, int C1, int C2, float* x,
+                       int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream) {
   if (!h_samples || B <= 0 || C0 <= 0 || C1 <= 0 || C2 <= 0 || !x || !target || !edge) return CWF_E_BADARG;
   const int64_t V = (int64_t)C0 * C1 * C2;
   if (V >= (int64_t(1) << 31)) return CWF_E_TOOLARGE;
   if (((uintptr_t)x & 3) || ((uintptr_t)target & 7) || ((uintptr_t)edge & 7)) return CWF_E_BADARG;
   if (x_bstride < 4 * V || t_bstride < V || e_bstride < V) return CWF_E_BADARG;
+  const int C[3] = {C0, C1, C2};
   for (int b = 0; b < B; ++b) {
     const HostSample& s = h_samples[b];
     if (!s.image || !s.label || ((uintptr_t)s.image & 3) || s.flip < 0 || s.flip > 7) return CWF_E_BADARG;
-    if (s.S0 <= 0 || s.S1 <= 0 || s.S2 <= 0) return CWF_E_BADARG;
-    for (int k = 0; k < 9; ++k)
-      if (!std::isfinite(s.m[k])) return CWF_E_BADARG;
-    if constexpr (DISP) {
-      if (s.disp && (((uintptr_t)s.disp & 3) || s.G0 < 4 || s.G0 > ELA_GMAX || s.G1 < 4 || s.G1 > ELA_GMAX || s.G2 < 4 || s.G2 > ELA_GMAX))
-        return CWF_E_BADARG;
-    }
+    if (s.S0 <= 0 || s.S1 <= 0 || s.S2 <= 0 || !prep_sample_ok(s, C)) return CWF_E_BADARG;
   }
-  PrepResArgs<Sample> a;
-  a.x = x; a.target = target; a.edge = edge;
+  PrepArgs<Sample> a;
   a.x_bs = x_bstride; a.t_bs = t_bstride; a.e_bs = e_bstride;
   a.C0 = C0; a.C1 = C1; a.C2 = C2;
   a.vec = (C2 % 4 == 0) && !((uintptr_t)x & 15) && !((uintptr_t)target & 15) && !((uintptr_t)edge & 15) && x_bstride % 4 == 0 &&
           t_bstride % 2 == 0 && e_bstride % 2 == 0;
-  const int64_t tiles = (int64_t)cdiv(C0, AFF_T0) * cdiv(C1, AFF_T1) * cdiv(C2, AFF_T2);
+  const int64_t tiles = (int64_t)cdiv(C0, Tile::T0) * cdiv(C1, Tile::T1) * cdiv(C2, Tile::T2);
   hipStream_t st = cwf_stream(stream);
   for (int b0 = 0; b0 < B; b0 += PREP_MAXS) {
     const int nb = std::min(PREP_MAXS, B - b0);
     for (int i = 0; i < PREP_MAXS; ++i) {
-      Sample& d = a.s[i];
-      if (i >= nb) { d = Sample{}; continue; }
-      const HostSample& s = h_samples[b0 + i];
-      d.image = s.image; d.label = s.label;
-      d.S0 = s.S0; d.S1 = s.S1; d.S2 = s.S2; d.o0 = s.o0; d.o1 = s.o1; d.o2 = s.o2;
-      d.flip = s.flip; d.intensity = s.intensity;
-      for (int c = 0; c < 4; ++c) { d.scale[c] = s.scale[c]; d.shift[c] = s.shift[c]; }
-      for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
-      if constexpr (DISP) {
-        d.disp = s.disp;
-        d.G0 = s.disp ? s.G0 : 0; d.G1 = s.disp ? s.G1 : 0; d.G2 = s.disp ? s.G2 : 0;
-        const int G[3] = {d.G0, d.G1, d.G2}, C[3] = {C0, C1, C2};
-        for (int k = 0; k < 3; ++k) d.k[k] = (s.disp && C[k] > 1) ? (float)(G[k] - 3) / (float)(C[k] - 1) : 0.f;
-      }
+      if (i < nb) prep_pack(a.s[i], h_samples[b0 + i], C);
+      else a.s[i] = Sample{};
     }
-    PrepResArgs<Sample> ab = a;
-    ab.x = x + (int64_t)b0 * x_bstride;
-    ab.target = target + (int64_t)b0 * t_bstride;
-    ab.edge = edge + (int64_t)b0 * e_bstride;
-    hipLaunchKernelGGL((prep_affine_kernel<DISP, PrepResArgs<Sample>>), dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, st, ab);
+    a.x = x + (int64_t)b0 * x_bstride;
+    a.target = target + (int64_t)b0 * t_bstride;
+    a.edge = edge + (int64_t)b0 * e_bstride;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, st, a);
     CWF_LAUNCH_CHECK();
   }
   return 0;
 }
 
+extern "C" int cwf_prepare_batch(const struct cwf_prep_sample* h_samples, int B, int C0, int C1, int C2, float* x, int64_t x_bstride,
+                                 int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream) {
+  return prep_launch<PlainTile>(prep_batch_kernel, h_samples, B, C0, C1, C2, x, x_bstride, target, t_bstride, edge, e_bstride, stream);
+}
+
 extern "C" int cwf_prepare_batch_affine(const struct cwf_prep_affine_sample* h_samples, int B, int C0, int C1, int C2, float* x,
                                         int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride,
                                         void* stream) {
-  return prep_resampled<false>(h_samples, B, C0, C1, C2, x, x_bstride, target, t_bstride, edge, e_bstride, stream);
+  return prep_launch<AffTile>(prep_affine_kernel<cwf_prep_affine_sample>, h_samples, B, C0, C1, C2, x, x_bstride, target, t_bstride,
+                              edge, e_bstride, stream);
 }
 
 extern "C" int cwf_prepare_batch_elastic(const struct cwf_prep_elastic_sample* h_samples, int B, int C0, int C1, int C2, float* x,
                                          int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride,
                                          void* stream) {
-  return prep_resampled<true>(h_samples, B, C0, C1, C2, x, x_bstride, target, t_bstride, edge, e_bstride, stream);
+  return prep_launch<AffTile>(prep_affine_kernel<PrepElaSample>, h_samples, B, C0, C1, C2, x, x_bstride, target, t_bstride, edge,
+                              e_bstride, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ brain-mask z-score

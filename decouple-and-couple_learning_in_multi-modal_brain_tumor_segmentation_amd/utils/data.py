@@ -345,17 +345,13 @@ def _resample_cpu(img, lab, p, crop):
 def _prepare_one_cpu(img, lab, p, crop):
     if p.matrix is not None or p.disp is not None:
         x, t = _resample_cpu(img, lab, p, crop)
-        if p.scale is not None:
-            x = x * torch.tensor(p.scale, dtype=torch.float32).reshape(4, 1, 1, 1)
-            x = x + torch.tensor(p.shift, dtype=torch.float32).reshape(4, 1, 1, 1)
-        t[t == 4] = 3
-        return x, t, syn.edge_codes(t)
-    x = crop_pad(img, p.origin, crop)
-    t = crop_pad(lab.to(torch.int64), p.origin, crop)
-    dims = [d for d in range(3) if p.flip[d]]
-    if dims:
-        x = torch.flip(x, [d + 1 for d in dims])
-        t = torch.flip(t, dims)
+    else:
+        x = crop_pad(img, p.origin, crop)
+        t = crop_pad(lab.to(torch.int64), p.origin, crop)
+        dims = [d for d in range(3) if p.flip[d]]
+        if dims:
+            x = torch.flip(x, [d + 1 for d in dims])
+            t = torch.flip(t, dims)
     if p.scale is not None:
         x = x * torch.tensor(p.scale, dtype=torch.float32).reshape(4, 1, 1, 1)
         x = x + torch.tensor(p.shift, dtype=torch.float32).reshape(4, 1, 1, 1)

@@ -1599,6 +1599,42 @@ class HipBackend:
         self._call("cwf_adam_amsgrad_scaled", table.data_ptr(), ntensors, max_n, lr, beta1, beta2, eps, wd, step, int(amsgrad),
                    _p(hyper_dev), float(grad_scale), self._stream())
 
+    # ------------------------------------------------------------------ K13 step controls (csrc/grad_step.hip)
+    @staticmethod
+    def _flat_f32(name, t):
+        if t.dtype != _f32 or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("%s: a contiguous 1-D float32 tensor on a GPU is required" % name)
+
+    def grad_add(self, a, b, y):
+        """y = a + b on flat float32 slices (b None: y = a); y may be a or b.  Returns y."""
+        for t in (a, y) + (() if b is None else (b,)):
+            self._flat_f32("grad_add", t)
+            if t.numel() != y.numel():
+                raise ValueError("grad_add: operands differ in length")
+        self._call("cwf_grad_add", a.data_ptr(), _p(b), y.data_ptr(), y.numel(), self._stream())
+        return y
+
+    def grad_norm_clip(self, g, grad_scale, max_norm, ws, out2):
+        """out2 = {grad_scale * min(1, max_norm / (norm + 1e-6)), norm}, norm = grad_scale * |g|_2 with a double sum; nothing is
+        read back.  ws: float64 [GRADNORM_WS_DOUBLES] scratch (holds the per-workgroup partial sums afterwards)."""
+        self._flat_f32("grad_norm_clip", g)
+        self._flat_f32("grad_norm_clip", out2)
+        if out2.numel() != 2 or ws.dtype != torch.float64 or ws.numel() < _lib.GRADNORM_WS_DOUBLES or not ws.is_contiguous() \
+                or ws.device != g.device or out2.device != g.device:
+            raise ValueError("grad_norm_clip: out2 must be float32 [2] and ws float64 [%d] on g's device" % _lib.GRADNORM_WS_DOUBLES)
+        self._call("cwf_grad_norm_clip", g.data_ptr(), g.numel(), float(grad_scale), float(max_norm), ws.data_ptr(), out2.data_ptr(),
+                   self._stream())
+        return out2
+
+    def adam_ex(self, table, ntensors, max_n, lr, beta1, beta2, eps, wd, step, amsgrad, hyper_dev=None, grad_scale=1.0,
+                gscale_dev=None, ema_table=None, ema_weight=0.0):
+        """adam() with the gradient scale read from the device (gscale_dev: float32 [>= 1]) and / or an EMA of the new weights
+        (ema_table: int64 [ntensors] of device addresses parallel to table, ema_weight = 1 - decay)."""
+        if ema_table is not None and (ema_table.dtype != torch.int64 or ema_table.numel() != ntensors or not ema_table.is_cuda):
+            raise ValueError("adam_ex: ema_table must hold one int64 device address per tensor, on the GPU")
+        self._call("cwf_adam_amsgrad_ex", table.data_ptr(), ntensors, max_n, lr, beta1, beta2, eps, wd, step, int(amsgrad),
+                   _p(hyper_dev), float(grad_scale), _p(gscale_dev), _p(ema_table), float(ema_weight), self._stream())
+
     def dropout_mask(self, shape, p, device, p2=0.0):
         """Pre-scaled keep mask(s) in one launch from the device generator state (capturable: the state advances by a kernel)."""
         m = torch.empty(shape, dtype=_f32, device=device)

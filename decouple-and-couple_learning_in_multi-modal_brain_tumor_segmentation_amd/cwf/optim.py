@@ -7,7 +7,16 @@ the checkpoint's 'optim_dict' (train_no_amp.py:252) stays interchangeable.  ``po
 train_no_amp.adjust_learning_rate (:270-273).
 
 Gradients are gathered into ONE persistent flat fp32 buffer (``flat_grad``, 67 MB): the kernel's descriptor table is
-then static (safe for hipGraph capture / replay) and data-parallel training all-reduces that single buffer."""
+then static (safe for hipGraph capture / replay) and data-parallel training all-reduces that single buffer.
+
+Three optional controls act on that buffer and inside the launch (csrc/grad_step.hip); with all of them off the step is the one
+``cwf_adam_amsgrad_scaled`` launch it always was:
+  * accumulation over micro-batches: ``accumulate(first)`` keeps the running sum of the flat gradient in a second buffer ``acc``,
+    ``fold(lo, hi)`` adds it to (a slice of) the flat buffer before the update -- fp32, in micro-step order;
+  * ``max_grad_norm``: clipping by global norm as ``torch.nn.utils.clip_grad_norm_`` does it; norm and coefficient stay on the
+    device (``grad_norm``), the Adam launch reads the coefficient there;
+  * ``ema_decay``: an exponential moving average of the weights (``ema``), updated by the Adam launch from the new value it holds
+    in a register.  The EMA is not optimizer state: ``state_dict()`` keeps torch's layout."""
 import numpy as np
 import torch
 
@@ -90,10 +99,22 @@ class GradSink:
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, phases=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, phases=None,
+                 max_grad_norm=None, ema_decay=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad))
         if len(self.param_groups) != 1:
             raise ValueError("FusedAdam supports one parameter group (the reference uses one, train_no_amp.py:136)")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be > 0 (float('inf'): measure the norm, never clip) or None")
+        if ema_decay is not None and not 0.5 <= float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must lie in [0.5, 1) or be None")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.acc = None                 # running sum of the flat gradient over the micro-steps of a window (accumulate / fold)
+        self.ema = None                 # fp32 tensors parallel to the parameter list (built with the descriptor table)
+        self._ema_table = None
+        self._clip = None               # device float32 [2] = {clip coefficient * grad_scale, pre-clip norm}
+        self._clip_ws = None
         self._plist = [p for p in self.param_groups[0]["params"] if p.requires_grad]
         self._phases = phases
         self.sink = None
@@ -143,8 +164,52 @@ class FusedAdam(torch.optim.Optimizer):
             rows.append([p.data_ptr(), self.sink.view(p).data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                          st["max_exp_avg_sq"].data_ptr() if "max_exp_avg_sq" in st else 0, n])
         self._table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        if self.ema_decay is not None:
+            if self.ema is None or any(e.device != p.device or e.shape != p.shape for e, p in zip(self.ema, self._plist)):
+                self.ema = [p.detach().clone(memory_format=torch.contiguous_format).float() for p in self._plist]
+            self._ema_table = torch.tensor([e.data_ptr() for e in self.ema], dtype=torch.int64).to(dev)
+        if self.max_grad_norm is not None and (self._clip is None or self._clip.device != dev):
+            from . import _lib
+            self._clip = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._clip_ws = torch.zeros(_lib.GRADNORM_WS_DOUBLES, dtype=torch.float64, device=dev)
         self._table_key = self._key()
         self._max_n = max(r[5] for r in rows)
+
+    # ------------------------------------------------------------------ step controls
+    @property
+    def grad_norm(self):
+        """0-dim device tensor: L2 norm of the gradient the last update used (averaged over ranks and micro-batches), before
+        clipping.  None when clipping is off.  Reading it on the host is the caller's synchronisation, not the step's."""
+        if self.max_grad_norm is None:
+            return None
+        self._ensure()
+        return self._clip[1]
+
+    def accumulate(self, first):
+        """One micro-step of an accumulation window is done: acc = flat if `first` else acc + flat (one launch, current stream)."""
+        self._ensure()
+        if self.acc is None or self.acc.numel() != self.flat_grad.numel() or self.acc.device != self.flat_grad.device:
+            if not first:
+                raise RuntimeError("accumulate(first=False) before any accumulate(first=True)")
+            self.acc = torch.empty_like(self.flat_grad)
+        backend().grad_add(self.flat_grad, None if first else self.acc, self.acc)
+
+    def fold(self, lo=0, hi=None):
+        """flat[lo:hi] += acc[lo:hi]: the last micro-step's gradient joins the window's sum (current stream; per phase slice when the
+        slices are all-reduced one by one).  Every element must be folded exactly once before the update reads it."""
+        if self.acc is None:
+            raise RuntimeError("fold() without a preceding accumulate()")
+        hi = self.flat_grad.numel() if hi is None else hi
+        if hi > lo:
+            backend().grad_add(self.flat_grad[lo:hi], self.acc[lo:hi], self.flat_grad[lo:hi])
+
+    def reset_ema(self):
+        """EMA := the current weights (e.g. after loading a checkpoint that carries none)."""
+        if self.ema_decay is None:
+            raise RuntimeError("this optimizer keeps no EMA (ema_decay=None)")
+        self._ensure()
+        with torch.no_grad():
+            torch._foreach_copy_(self.ema, [p.detach() for p in self._plist])
 
     # ------------------------------------------------------------------ the three phases of a step
     def gather_grads(self):
@@ -167,8 +232,19 @@ class FusedAdam(torch.optim.Optimizer):
         any number of steps may be in flight.  The launch is issued eagerly after a graph replay (it is not captured)."""
         group = self.param_groups[0]
         b1, b2 = group["betas"]
-        backend().adam(self._table, len(self._plist), self._max_n, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                       self._steps, group["amsgrad"], hyper_dev=None, grad_scale=self.grad_scale)
+        if self.max_grad_norm is None and self.ema_decay is None:
+            backend().adam(self._table, len(self._plist), self._max_n, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
+                           self._steps, group["amsgrad"], hyper_dev=None, grad_scale=self.grad_scale)
+            return
+        K = backend()
+        if self.max_grad_norm is not None:
+            # norm of the averaged gradient and grad_scale * clip coefficient, left on the device for the launch below
+            K.grad_norm_clip(self.flat_grad, self.grad_scale, self.max_grad_norm, self._clip_ws, self._clip)
+        K.adam_ex(self._table, len(self._plist), self._max_n, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
+                  self._steps, group["amsgrad"], hyper_dev=None, grad_scale=self.grad_scale,
+                  gscale_dev=self._clip if self.max_grad_norm is not None else None,
+                  ema_table=self._ema_table if self.ema_decay is not None else None,
+                  ema_weight=(1.0 - self.ema_decay) if self.ema_decay is not None else 0.0)
 
     @torch.no_grad()
     def step(self, closure=None):

@@ -24,6 +24,15 @@ launch list is issued up to a marker, the phase's all-reduce is enqueued behind 
 the collective follows the replay (4 chunks of the flat buffer).
 CWF_FORCE_COMM=1 keeps the whole collective path on at world size 1 (a one-rank RCCL group): the way to exercise and profile it on a
 one-GPU box.
+Step controls (all off by default; then the step issues exactly the launches described above):
+  * accum_steps = N: step() is called once per micro-batch; micro-steps 1..N-1 run forward and backward, issue NO collective and
+    add the flat gradient to the optimizer's accumulator (one launch on the main stream, after the weight-gradient stream has been
+    joined); micro-step N adds the accumulator to the flat buffer -- per phase slice on the communication stream just before that
+    slice's all-reduce when communication is overlapped, else in one launch after backward -- and updates with the gradient
+    1/(world N) sum_ranks sum_micro g: N independent forwards whose gradients are averaged, the reference's only batch semantics
+    (SURVEY.md F2).  Accumulate and fold launches are never captured: the captured step is the same for every micro-step.
+  * max_grad_norm: the averaged gradient is clipped by its global norm inside the Adam launch (cwf.optim); no host sync.
+  * ema_decay: the Adam launch also maintains an EMA copy of the weights (ema_state_dict() for validation / checkpoints).
 Checkpoints use the reference layout {'epoch', 'state_dict' with 'module.' prefix, 'optim_dict'} (:248-253)."""
 from __future__ import annotations
 
@@ -51,15 +60,22 @@ def kernels_backend():
 
 class Trainer:
     def __init__(self, model, lr=2e-4, weight_decay=1e-5, amsgrad=True, end_epoch=1000, use_graph=False,
-                 graph_warmup=2, overlap_comm=True, wgrad_async=True):
+                 graph_warmup=2, overlap_comm=True, wgrad_async=True, accum_steps=1, max_grad_norm=None, ema_decay=None):
         self.model = model
         self.init_lr, self.end_epoch = lr, end_epoch
+        if int(accum_steps) != accum_steps or accum_steps < 1:
+            raise ValueError("accum_steps must be an integer >= 1")
+        self.accum_steps = int(accum_steps)
+        self._micro = 0                                 # micro-steps of the current window already accumulated
+        self._last_micro = True                         # this call ends its window: fold, collectives, update
         phases = model.grad_phases() if hasattr(model, "grad_phases") else None
-        self.opt = FusedAdam(model.parameters(), lr=lr, weight_decay=weight_decay, amsgrad=amsgrad, phases=phases)
+        self.opt = FusedAdam(model.parameters(), lr=lr, weight_decay=weight_decay, amsgrad=amsgrad, phases=phases,
+                             max_grad_norm=max_grad_norm, ema_decay=ema_decay)
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # collectives on: more than one rank, or a one-rank group with CWF_FORCE_COMM=1 (exercises the RCCL path on a one-GPU box)
         self.comm = self.world > 1 or (dist.is_available() and dist.is_initialized() and os.environ.get("CWF_FORCE_COMM", "0") == "1")
-        self.opt.grad_scale = 1.0 / self.world          # the all-reduce SUMS; Adam reads g / world (the DDP average, train_no_amp.py:133)
+        # the all-reduce SUMS, the accumulator sums: Adam reads g / (world * micro-batches) (the DDP average, train_no_amp.py:133)
+        self.opt.grad_scale = 1.0 / (self.world * self.accum_steps)
         if use_graph not in (False, True, None, "plan", "hipgraph"):
             raise ValueError("use_graph must be False, True, 'plan' or 'hipgraph'")
         self.graph_mode = {True: "plan", False: None, None: None}.get(use_graph, use_graph)
@@ -114,6 +130,8 @@ class Trainer:
         lo, hi = self.opt.sink.chunks[k]
         if hi <= lo:
             return
+        if not self._last_micro and not _capturing():
+            return                                               # inside an accumulation window: no collective
         chunk = self.opt.flat_grad[lo:hi]
         if self._comm_stream is not None:
             K = kernels_backend()
@@ -127,8 +145,12 @@ class Trainer:
                     # stream by _run_plan when the launch list reaches the marker
                     K._call("cwf_plan_marker", int(k), K._stream())
                 else:
+                    if self._micro:
+                        self.opt.fold(lo, hi)                    # the window's earlier micro-steps, before the collective reads the slice
                     self._works.append(dist.all_reduce(chunk, async_op=True))
         elif not _capturing():
+            if self._micro:
+                self.opt.fold(lo, hi)
             self._works.append(dist.all_reduce(chunk, async_op=True))
 
     def _fwd_bwd(self, x, target, edge):
@@ -219,8 +241,10 @@ class Trainer:
             if mk.value < 0:
                 break
             lo, hi = self.opt.sink.chunks[mk.value]
-            if hi > lo and self.comm:
+            if hi > lo and self.comm and self._last_micro:       # (inside an accumulation window the list just continues)
                 with torch.cuda.stream(cs):
+                    if self._micro:
+                        self.opt.fold(lo, hi)
                     self._works.append(dist.all_reduce(self.opt.flat_grad[lo:hi], async_op=True))
             pos = nxt.value
 
@@ -239,8 +263,12 @@ class Trainer:
         return self._static if self._graph is not None else None
 
     def step(self, x, target, edge, epoch=0):
-        """One optimisation step on a rank-local batch.  Returns (loss, [five parts]) as device tensors (no host sync)."""
-        self.opt.param_groups[0]["lr"] = float(poly_lr(self.init_lr, epoch, self.end_epoch))   # plain float: checkpoints stay weights_only-loadable
+        """One optimisation step on a rank-local batch -- with accum_steps = N > 1 one MICRO-step: every N-th call updates the weights
+        (learning rate of that call's epoch), the calls before it only accumulate.  Returns this batch's (loss, [five parts]) as
+        device tensors (no host sync)."""
+        self._last_micro = self._micro + 1 >= self.accum_steps
+        if self._last_micro:
+            self.opt.param_groups[0]["lr"] = float(poly_lr(self.init_lr, epoch, self.end_epoch))   # plain float: checkpoints stay weights_only-loadable
         if self.use_graph and self._graph is None and self._eager_steps >= self._graph_warmup:
             torch.cuda.synchronize()
             self._capture(x, target, edge)
@@ -263,25 +291,72 @@ class Trainer:
         else:
             loss, parts = self._fwd_bwd(x, target, edge)
             self._eager_steps += 1
+        if not self._last_micro:
+            self.opt.accumulate(first=self._micro == 0)
+            self._micro += 1
+            self._last_micro = True                     # (direct _fwd_bwd calls outside step() behave as a plain step)
+            return loss, parts
+        if self._micro and not self._folds_per_chunk():
+            self.opt.fold()                             # no collective, or one over the whole buffer after the step: one fold
         self._finish_comm()
+        self._micro = 0
         self.opt.advance_host()
         self.opt.launch()
         return loss, parts
+
+    def _folds_per_chunk(self):
+        """the phase slices are all-reduced one by one (each behind its own fold): the condition _finish_comm waits under"""
+        return self.comm and self.overlap_comm and (self._graph is None or self._plan is not None)
+
+    def ema_state_dict(self):
+        """The model's state_dict() with every parameter replaced by its EMA (buffers copied): what validation and checkpoints
+        load in place of the raw weights."""
+        if self.opt.ema_decay is None:
+            raise RuntimeError("this Trainer keeps no EMA (ema_decay=None)")
+        self.opt._ensure()
+        ema = {id(p): e for p, e in zip(self.opt._plist, self.opt.ema)}
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for name, p in self.model.named_parameters():
+            if id(p) in ema and name in sd:
+                sd[name] = ema[id(p)].detach().clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """EMA := the parameter entries of `sd` (keys as in the model's state_dict(), with or without the 'module.' prefix)."""
+        if self.opt.ema_decay is None:
+            raise RuntimeError("this Trainer keeps no EMA (ema_decay=None)")
+        self.opt._ensure()
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+        ema = {id(p): e for p, e in zip(self.opt._plist, self.opt.ema)}
+        with torch.no_grad():
+            for name, p in self.model.named_parameters():
+                if id(p) in ema:
+                    if name not in sd:
+                        raise KeyError("EMA state lacks parameter %r" % name)
+                    ema[id(p)].copy_(sd[name])
 
 
 def _capturing():
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
-def save_checkpoint(path, model, optimizer, epoch):
-    """train_no_amp.py:248-253: the reference saves the DDP-wrapped model, hence the 'module.' key prefix."""
+def save_checkpoint(path, model, optimizer, epoch, ema=None):
+    """train_no_amp.py:248-253: the reference saves the DDP-wrapped model, hence the 'module.' key prefix.  `ema`
+    (Trainer.ema_state_dict()) adds a fourth key 'ema_state_dict' with the same prefix; the reference's three stay as they are."""
     sd = {"module." + k: v for k, v in model.state_dict().items()}
-    torch.save({"epoch": epoch, "state_dict": sd, "optim_dict": optimizer.state_dict()}, path)
+    ck = {"epoch": epoch, "state_dict": sd, "optim_dict": optimizer.state_dict()}
+    if ema is not None:
+        ck["ema_state_dict"] = {"module." + k: v for k, v in ema.items()}
+    torch.save(ck, path)
 
 
-def load_checkpoint(path, model, map_location="cpu"):
-    """train_no_amp.py:147-151 (weights only; the reference never restores 'optim_dict' or 'epoch')."""
+def load_checkpoint(path, model, map_location="cpu", use_ema=False):
+    """train_no_amp.py:147-151 (weights only; the reference never restores 'optim_dict' or 'epoch').  use_ema: load the EMA weights
+    the checkpoint carries instead of the raw ones."""
     ck = torch.load(path, map_location=map_location, weights_only=True)
-    sd = {(k[7:] if k.startswith("module.") else k): v for k, v in ck["state_dict"].items()}
+    key = "ema_state_dict" if use_ema else "state_dict"
+    if use_ema and key not in ck:
+        raise KeyError("checkpoint %s carries no 'ema_state_dict' (it was written without --ema_decay): load it with use_ema=False" % path)
+    sd = {(k[7:] if k.startswith("module.") else k): v for k, v in ck[key].items()}
     model.load_state_dict(sd)
     return ck.get("epoch", 0)

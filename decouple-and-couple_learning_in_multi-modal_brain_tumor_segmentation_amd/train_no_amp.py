@@ -102,7 +102,29 @@ def build_parser():
     p.add_argument("--aug_elastic_grid", default=7, type=int, help="(--aug_elastic) control points per axis, 4..8")
     p.add_argument("--normalize", default=False, type=_bool,
                    help="(--device_data) z-score each subject's channels over its brain mask (four-channel sum > 0) at load")
+    p.add_argument("--accum_steps", default=1, type=int,
+                   help="N >= 1: update the weights every N iterations with the gradient averaged over those N batches (and over ranks) "
+                        "-- N independent forwards, the reference's batch semantics, so global batch = ranks x N x --batch_size.  A window "
+                        "continues across an epoch boundary (its update uses the learning rate of its last iteration's epoch); a final "
+                        "partial window at the end of training is dropped")
+    p.add_argument("--clip_grad_norm", default=None, type=float,
+                   help="c > 0: clip the averaged gradient to global L2 norm c before the update (torch.nn.utils.clip_grad_norm_ "
+                        "semantics, on the device); the log line gains grad_norm, the norm before clipping.  Default: off")
+    p.add_argument("--ema_decay", default=None, type=float,
+                   help="0.5 <= d < 1: keep ema = d * ema + (1 - d) * weights, updated at every weight update (with --accum_steps N "
+                        "once per window; iterations of a partial window dropped at the end of training never reach it); checkpoints "
+                        "carry it as 'ema_state_dict' and --resume restores it when present.  Default: off")
     return p
+
+
+def check_step_controls(args):
+    """the values of --accum_steps / --clip_grad_norm / --ema_decay (SystemExit with the rule, like the --aug_* checks)"""
+    if args.accum_steps < 1:
+        raise SystemExit("--accum_steps takes an integer >= 1")
+    if args.clip_grad_norm is not None and not args.clip_grad_norm > 0.0:
+        raise SystemExit("--clip_grad_norm takes a norm > 0 (leave the flag out for no clipping)")
+    if args.ema_decay is not None and not 0.5 <= args.ema_decay < 1.0:
+        raise SystemExit("--ema_decay takes a decay in [0.5, 1) (leave the flag out for no EMA)")
 
 
 def should_save(epoch, end_epoch, save_freq):
@@ -156,6 +178,7 @@ def main(argv=None):
         raise SystemExit("--aug_elastic deforms the crop on the device: it needs --device_data cache or staged")
     if args.aug_elastic < 0.0 or not 4 <= args.aug_elastic_grid <= 8:
         raise SystemExit("--aug_elastic takes voxels >= 0 and --aug_elastic_grid 4 to 8 control points per axis")
+    check_step_controls(args)
     from cwf import kernels
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint
@@ -197,7 +220,17 @@ def main(argv=None):
     elif is_printer:
         log.info("re-training!!!")
     trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, amsgrad=args.amsgrad, end_epoch=args.end_epoch,
-                      use_graph={"eager": False, "plan": "plan", "hipgraph": "hipgraph"}[args.step_mode] if use_cuda else False)
+                      use_graph={"eager": False, "plan": "plan", "hipgraph": "hipgraph"}[args.step_mode] if use_cuda else False,
+                      accum_steps=args.accum_steps, max_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay)
+    clip, use_ema = args.clip_grad_norm is not None, args.ema_decay is not None
+    if use_ema and os.path.isfile(args.resume) and args.load:
+        ck = torch.load(args.resume, map_location="cpu", weights_only=True)
+        if "ema_state_dict" in ck:
+            trainer.load_ema_state_dict(ck["ema_state_dict"])
+        elif is_printer:
+            log.info("checkpoint %s carries no EMA: it starts from the loaded weights", args.resume)
+        del ck
+    ema_sd = (lambda: trainer.ema_state_dict()) if use_ema else (lambda: None)
 
     ckpt_dir = os.path.join(args.project_root, "checkpoint", args.experiment + args.date)
     if is_printer:
@@ -229,11 +262,12 @@ def main(argv=None):
                     ev, host, tag = pending
                     ev.synchronize() if ev is not None else None
                     v = host.tolist()
-                    log.info("Epoch: %d_Iter:%d  loss: %.5f || end_loss: %.5f || s_loss:%.4f || edge_loss:%.4f || mid_s_loss:%.4f || mid_edge_loss:%.4f ||",
-                             tag[0], tag[1], v[0], v[1], v[2], v[3], v[4], v[5])
-                snap = torch.stack([loss] + list(parts)).float()
+                    log.info("Epoch: %d_Iter:%d  loss: %.5f || end_loss: %.5f || s_loss:%.4f || edge_loss:%.4f || mid_s_loss:%.4f || mid_edge_loss:%.4f ||"
+                             + (" grad_norm: %.4f" if clip else ""), tag[0], tag[1], *v)
+                # (grad_norm: of the last update -- inside an accumulation window that is the previous window's)
+                snap = torch.stack([loss] + list(parts) + ([trainer.opt.grad_norm] if clip else [])).float()
                 if use_cuda:
-                    host = torch.empty(6, dtype=torch.float32).pin_memory()
+                    host = torch.empty(snap.numel(), dtype=torch.float32).pin_memory()
                     host.copy_(snap, non_blocking=True)
                     ev = torch.cuda.Event(); ev.record()
                 else:
@@ -243,7 +277,7 @@ def main(argv=None):
                 done = True
                 break
         if is_printer and should_save(epoch, args.end_epoch, args.save_freq):
-            save_checkpoint(os.path.join(ckpt_dir, "model_epoch_%d.pth" % epoch), model, trainer.opt, epoch)
+            save_checkpoint(os.path.join(ckpt_dir, "model_epoch_%d.pth" % epoch), model, trainer.opt, epoch, ema=ema_sd())
         if done:
             break
     if is_printer:
@@ -251,7 +285,7 @@ def main(argv=None):
             ev, host, tag = pending
             ev.synchronize() if ev is not None else None
             log.info("Epoch: %d_Iter:%d  loss: %.5f (last logged)", tag[0], tag[1], host.tolist()[0])
-        save_checkpoint(os.path.join(ckpt_dir, "model_epoch_last.pth"), model, trainer.opt, args.end_epoch)       # :255-262
+        save_checkpoint(os.path.join(ckpt_dir, "model_epoch_last.pth"), model, trainer.opt, args.end_epoch, ema=ema_sd())       # :255-262
         log.info("The total training time is %.2f hours", (time.time() - t_start) / 3600.0)
         log.info("----------------------------------The training process finished!-----------------------------------")
     if world > 1 and dist.is_initialized():

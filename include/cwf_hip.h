@@ -653,6 +653,32 @@ int cwf_adam_amsgrad_scaled(const struct cwf_adam_desc* table, int ntensors, int
  * launch be captured in a hipGraph and replayed while the host advances the schedule.                                  */
 
 /* ------------------------------------------------------------------------------------------------
+ * K13 step controls on the flat gradient buffer: accumulation over micro-batches, clipping by global norm, EMA weights
+ * ---------------------------------------------------------------------------------------------- */
+/* y[i] = a[i] + b[i], one rounded fp32 addition each; b == NULL: y[i] = a[i].  y may be a or b themselves (not a shifted overlap).
+ * Pointers need 4-byte alignment only (slices of the flat buffer): 16-byte accesses when a, b and y are congruent mod 16, between
+ * a scalar head and tail; grid-stride with a capped grid.  CWF_E_BADARG: a or y null, n <= 0; CWF_E_ALIGN: a pointer off 4 bytes. */
+int cwf_grad_add(const float* a, const float* b, float* y, int64_t n, void* stream);
+/* Global L2 norm of g * grad_scale and the clip coefficient of torch.nn.utils.clip_grad_norm_, both left on the device:
+ *   out2[1] = grad_scale * sqrt(S),  S = sum g[i]^2 (every value widened to double before squaring, summed in double)
+ *   out2[0] = grad_scale * min(1, max_norm / (out2[1] + 1e-6))      -- what cwf_adam_amsgrad_ex reads as its gradient scale
+ * Two launches: CWF_GRADNORM_WS_DOUBLES workgroups each store the sum over a fixed contiguous range into ws (plain stores, no
+ * atomics), one workgroup adds those partials in a fixed order: bit-identical from run to run.  max_norm = +inf gives
+ * out2[0] = grad_scale (norm only).  A non-finite S propagates (inf: coefficient 0, NaN: NaN) as in torch; no step is skipped.
+ * ws: CWF_GRADNORM_WS_DOUBLES doubles of device scratch, fully rewritten.  CWF_E_BADARG: a null pointer, n <= 0, a negative or NaN
+ * max_norm, a NaN grad_scale; CWF_E_ALIGN: g / out2 off 4 bytes, ws off 8. */
+#define CWF_GRADNORM_WS_DOUBLES 1024
+int cwf_grad_norm_clip(const float* g, int64_t n, float grad_scale, float max_norm, double* ws, float* out2, void* stream);
+/* cwf_adam_amsgrad_scaled with two optional additions.  gscale_dev (nullable): device float whose value replaces grad_scale, read
+ * by the kernel (out2 of cwf_grad_norm_clip).  ema_table (nullable): device array of ntensors float pointers parallel to table;
+ * after the update ema[i] += ema_weight * (p_new[i] - ema[i]), ema_weight = 1 - decay in (0, 0.5] (Tensor.lerp_, weight < 0.5).
+ * CWF_E_BADARG: a null table, ema_weight outside (0, 0.5] with an ema_table, step <= 0 without hyper_dev. */
+int cwf_adam_amsgrad_ex(const struct cwf_adam_desc* table, int ntensors, int64_t max_n,
+                        double lr, double beta1, double beta2, double eps, double weight_decay, int step, int amsgrad,
+                        const float* hyper_dev, float grad_scale, const float* gscale_dev, float* const* ema_table, float ema_weight,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K12 / misc elementwise
  * ---------------------------------------------------------------------------------------------- */
 /* y[i] = a[i]*b[i]  (dropout masks) ; y = a + b ; y[n][v][c] = x[n][v][c]*s[n][c] (dropout3d) ; fill */

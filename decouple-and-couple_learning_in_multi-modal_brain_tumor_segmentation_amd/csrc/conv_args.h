@@ -23,7 +23,8 @@ struct ConvArgsB {
   // own packed weights and bias; blockIdx.z = (group * N + n) * ncls + class.  groups == 0: an ordinary launch.
   int groups, x_goff, y_goff;
   const uint4* wpk_g[3]; const float* bias_g[3];
-  // conv16s, IN16 instantiation: the input as a bf16 image (16-byte granules, two per voxel) and the 16-byte zero page of its loaders
+  // conv16s / convws, IN16 instantiations: the input as a bf16 image [N][D][H][W][Cin] (16-byte granules) and the 16-byte zero page of
+  // their loaders
   const uint4* x16; const uint4* zero16;
   // pointwise stream kernel (1x1x1 forward): the output also as a bf16 image [N][V][Cout] (the operand image of a consuming layer's weight
   // gradient, see cwf_conv_args.y16): one extra 8-byte store per lane
@@ -59,6 +60,8 @@ static inline int cfg_extent(int op, int Di, int Hi, int Wi, int Do, int Ho, int
 
 // conv_ws.hip: launches the weight-stationary kernel when the layer is one it takes (returns 1, status in *rc); 0 = not eligible.
 int cwf_try_conv_ws(int op, int x3, ConvArgsB& a, hipStream_t st, int* rc);
+// conv_ws.hip: 1 if its bf16-image instantiation takes a single-bf16 launch of these dimensions (the eligibility code of the dispatch)
+int cwf_ws_takes_x16(int op, int N, int D, int H, int W, int Cin, int Cout);
 // conv_ws.hip: 1 while cwf_debug_ws_x3 sends split-bf16 launches to the weight-stationary kernel
 int cwf_ws_takes_x3();
 // conv_wsp.hip: the wave-specialised split-bf16 forward of the 32-256-channel 3x3x3 layers (same contract as cwf_try_conv_ws; cfg_mt /

@@ -1287,9 +1287,9 @@ static void c16_tap_order(ConvGeom& g) {
 // the weight-stationary kernels (conv_wsp, conv_ws), conv16s, the tap-table kernel.
 static int conv_bf16_impl(const cwf_conv_args& d, hipStream_t st) {
   const int op = d.op, x3 = d.precision == CWF_BF16X3, N = d.N, Cin = d.Cin, Cout = d.Cout, y_ldc = d.y_ldc;
-  // a bf16 input image stands in for x: conv16s reads it through its LDS-DMA loaders (16-byte granules, two per voxel)
+  // a bf16 input image stands in for x: conv16s / convws read it through LDS-DMA (16-byte granules, Cin / 8 per voxel)
   const float* x = d.x16 ? reinterpret_cast<const float*>(d.x16) : d.x;
-  const int x_ldc = d.x16 ? 16 : d.x_ldc;
+  const int x_ldc = d.x16 ? Cin : d.x_ldc;
   if (!x || !d.wpk || !d.y || N <= 0 || Cin <= 0 || Cout <= 0) return CWF_E_BADARG;
   if (d.nb_x && (!d.stats || !d.nb_scale || !d.nb_shift || d.nb_ldc < Cout)) return CWF_E_BADARG;
   if ((Cin & 3) || (x_ldc & 3) || x_ldc < Cin || y_ldc < Cout) return CWF_E_ALIGN;
@@ -1308,7 +1308,11 @@ static int conv_bf16_impl(const cwf_conv_args& d, hipStream_t st) {
   a.x16 = reinterpret_cast<const uint4*>(d.x16); a.zero16 = reinterpret_cast<const uint4*>(d.zero16);
   a.y16 = reinterpret_cast<unsigned short*>(d.y16);
   for (int q = 0; q < 3; ++q) { a.wpk_g[q] = nullptr; a.bias_g[q] = nullptr; }
-  if (d.x16) {                                         // (cwf_conv has checked the layer)
+  if (d.x16 && Cin != 16) {                            // (cwf_conv has checked the layer: cwf_conv_x16_ok)
+    int rcw = 0;
+    return cwf_try_conv_ws(op, 0, a, st, &rcw) ? rcw : CWF_E_BADARG;
+  }
+  if (d.x16) {
     c16_tap_order(a.g);
     rc = cwf_build_geom(a.g, op, N, d.Di, d.Hi, d.Wi, Cin, x_ldc, d.Do, d.Ho, d.Wo, Cout, y_ldc, 16);
     if (rc) return rc;
@@ -1372,6 +1376,15 @@ static int conv_grouped_impl(const cwf_conv_args& d, hipStream_t st) {
   return CWF_E_BADARG;
 }
 
+// The layers whose single-bf16 launch (no prologue, no output scale, no groups) takes its input as a bf16 image (cwf_conv_args.x16):
+// the full-resolution 16 -> 16 layers (conv16s) and what the weight-stationary kernel takes (conv_ws.hip).  cwf_conv checks a launch
+// with this function, and the Python side asks it before it leaves an fp32 gradient unwritten.
+extern "C" int cwf_conv_x16_ok(int op, int N, int D, int H, int W, int Cin, int Cout) {
+  if (op != CWF_CONV3_S1 || N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+  if (Cin == 16 && Cout == 16) return (int64_t)D * H * W >= 32768 && (int64_t)N * D * H * W < (1ll << 30);
+  return cwf_ws_takes_x16(op, N, D, H, W, Cin, Cout);
+}
+
 // The one place that chooses a forward / data-gradient kernel (include/cwf_hip.h, struct cwf_conv_args).
 extern "C" int cwf_conv(const struct cwf_conv_args* args, void* stream) {
   if (!args) return CWF_E_BADARG;
@@ -1395,8 +1408,7 @@ extern "C" int cwf_conv(const struct cwf_conv_args* args, void* stream) {
   if (d.x16) {
     if (d.precision != CWF_BF16 || d.in_scale || d.out_scale || d.y16 || !d.zero16 || ((uintptr_t)d.x16 & 15) || ((uintptr_t)d.zero16 & 15))
       return CWF_E_BADARG;
-    if (d.op != CWF_CONV3_S1 || d.Cin != 16 || d.Cout != 16 || d.Do != d.Di || d.Ho != d.Hi || d.Wo != d.Wi ||
-        (int64_t)d.Di * d.Hi * d.Wi < 32768 || (int64_t)d.N * d.Di * d.Hi * d.Wi >= (1ll << 30))
+    if (d.Do != d.Di || d.Ho != d.Hi || d.Wo != d.Wi || !cwf_conv_x16_ok(d.op, d.N, d.Di, d.Hi, d.Wi, d.Cin, d.Cout))
       return CWF_E_BADARG;
     return conv_bf16_impl(d, st);
   }

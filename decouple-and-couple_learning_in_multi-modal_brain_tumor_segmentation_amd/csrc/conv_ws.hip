@@ -28,13 +28,24 @@
 #define WS_NVOX (WS_ID * WS_IH * WS_IW)      // 648 halo voxels of a 4x4x16 tile
 #define WS_SLOTS 11                          // staging slots per thread of a group: 648 voxels x 4 channel quads / 256 threads
 #define WS_NT 2                              // output-channel tiles (of 16) per workgroup
+#define WS_A16_PIECES 21                     // IN16: the halo image as LDS-DMA pieces of 64 granules (1296 granules + a zero tail)
 
 struct WsWork { int ngroups, slots, tiles, xcd_perm; };
 
 __host__ __device__ constexpr int ws_tap_bytes(int t) { return (((t / 9) * WS_IH + (t / 3) % 3) * WS_IW + t % 3) * 32; }
 
-template <bool X3>
-__global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const WsWork wk) {
+// IN16 = true (single-bf16 data-gradient launches whose input gradient exists as a bf16 image [N][D][H][W][Cin], a.x16): nothing is
+// converted and nothing is staged in registers.  The halo of a (tile, chunk) item -- 648 voxels x 32 B = 1296 granules of 16 B, in
+// exactly the voxel-major order of the A image -- and the chunk's packed weights come global -> LDS by LDS-DMA in lane-linear 1-KiB
+// pieces (out-of-volume voxels and the tail of the last piece read the 16-byte zero page a.zero16).  Each group has TWO A images and
+// the workgroup two weight buffers: both groups run the MFMA phase of block b while four LOADER waves (waves 8..11, one per SIMD; 768
+// threads) have the DMA of block b + 1 in flight; one raw s_barrier per block hands over, behind the loaders' s_waitcnt vmcnt(0) (a
+// buffer is read one phase after the wait that retires it, and refilled after the barrier that every reader of it has passed).
+// Loaders are waves of their own because hipcc drains every pending LDS-DMA (vmcnt(0)) in front of the first ds_read of a wave that
+// has issued one.  With two chunks (Cin = 32) both stay resident: weights are loaded once.
+template <bool X3, bool IN16 = false>
+__global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgsB a, const WsWork wk) {
+  static_assert(!(IN16 && X3), "the bf16 input image is a single-bf16 operand");
   constexpr int NT = WS_NT;
   constexpr int T = 1;                                     // tiles per group and round (two per group do not fit the register file beside the prefetch)
   extern __shared__ float4 lds4[];
@@ -43,17 +54,18 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
   char* lds = reinterpret_cast<char*>(lds4);
   constexpr int B_IMG = 14 * NT * 1024;                    // one chunk of one image (hi or lo)
   constexpr int B_ALL = B_IMG * (X3 ? 2 : 1);
-  constexpr int A_IMG = WS_NVOX * 32;
-  constexpr int A_GRP = A_IMG * (X3 ? 2 : 1);
+  constexpr int A_IMG = IN16 ? WS_A16_PIECES * 1024 : WS_NVOX * 32;
+  constexpr int A_GRP = A_IMG * ((X3 || IN16) ? 2 : 1);  // hi + lo images, or (IN16) the images of two consecutive items
+  constexpr int B_RES = B_ALL * (IN16 ? 2 : 1);            // weights in LDS (IN16: two chunks)
   constexpr int NB = (B_ALL + 4095) / 4096;                // uint4 per thread of GROUP 0 for one chunk's weights
   char* Bh = lds;
   char* Bl = lds + B_IMG;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2, wl = wave & 3, tg = tid & 255;      // group (0 / 1), wave in group, thread in group
-  char* Ah = lds + B_ALL + grp * A_GRP;
+  char* Ah = lds + B_RES + grp * A_GRP;
   char* Al = Ah + A_IMG;
-  float* red = reinterpret_cast<float*>(lds + B_ALL + 2 * A_GRP);
+  float* red = reinterpret_cast<float*>(lds + B_RES + 2 * A_GRP);
   const int r = lane & 15, kq = lane >> 4;
   const bool second = (kq >> 1) != 0;
 
@@ -283,9 +295,10 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
     const int round = block / nch, chunk = block - round * nch;
     const int tile = item_tile(round, k);
     if (tile < 0) return false;
-    const char* bh = Bh + b_lane;
+    const int par = IN16 ? (block & 1) : 0;               // IN16: block b lives in weight buffer and A image b & 1
+    const char* bh = Bh + par * B_ALL + b_lane;
     const char* bl = Bl + b_lane;
-    const char* ah0 = Ah + a_lane;
+    const char* ah0 = Ah + par * A_IMG + a_lane;
     const char* al0 = Al + a_lane;
     // Fragment reads are pipelined by hand; the scheduling barrier per step keeps hipcc from hoisting further steps' reads on top
     // (three steps of split-bf16 fragments in flight spilled registers).  The hi fragments of step s + 1 are requested before the
@@ -369,7 +382,75 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
     asm volatile("" : "+v"(pf_sc), "+v"(pf_sh));
     convert_write(tile, blk - round * nch, pf_sc, pf_sh);
   };
-  if (n_blocks > 0) {
+  if constexpr (IN16) {
+    using K0 = std::integral_constant<int, 0>;
+    if (wave < 8) {
+      // =============================================================== MFMA waves: block b on weight buffer / A image b & 1
+      for (int blk = 0; blk < n_blocks; ++blk) {
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // block blk has landed; (stores of an epilogue stay in flight)
+        mfma_item(blk, K0{});
+      }
+    } else {
+      // =============================================================== loader waves (one per SIMD): LDS-DMA only
+      // Wave lw fills the A images of group lw >> 1 -- pieces (lw & 1), (lw & 1) + 2, ... of the 21 -- and the weight pieces lw, lw + 4, ...
+      // of the 28.  Block b + 1 is issued right after barrier b (its buffers were last read in block b - 1, which every MFMA wave
+      // left before that barrier); before barrier b + 1 this wave waits for all its pieces.
+      typedef __attribute__((address_space(3))) void* lds_vp;
+      typedef __attribute__((address_space(1))) const void* glb_vp;
+      const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds4;
+      const int lw = wave - 8, lgrp = lw >> 1, lp0 = lw & 1;
+      constexpr int NA = (WS_A16_PIECES + 1) / 2;
+      unsigned aoff[NA], acrd[NA];                         // lane -> granule -> halo voxel and channel half, per piece
+      const unsigned cin2 = (unsigned)g.Cin * 2u;
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int gi = (lp0 + 2 * i) * 64 + lane, v = gi >> 1, half = gi & 1;
+        const int idd = v / (WS_IH * WS_IW), rem = v % (WS_IH * WS_IW), ih = rem / WS_IW, iw = rem % WS_IW;
+        aoff[i] = (unsigned)((idd * g.Hi + ih) * g.Wi + iw) * cin2 + (unsigned)half * 16u;     // (bytes; the host keeps the image below 4 GiB)
+        acrd[i] = (unsigned)idd | ((unsigned)ih << 3) | ((unsigned)iw << 6) | (v < WS_NVOX ? 1u << 11 : 0u);
+      }
+      auto issue_a = [&](int tile, int chunk, int buf) {
+        const int n = tile / tiles_per_n;
+        int bx = tile - n * tiles_per_n;
+        const int tw = bx % g.tiles_w; bx /= g.tiles_w;
+        const int th = bx % g.tiles_h, td = bx / g.tiles_h;
+        const int id0 = td * 4 - 1, ih0 = th * 4 - 1, iw0 = tw * 16 - 1;
+        // (wave-uniform; it may point in front of the image: only in-volume lanes add their offset to it)
+        const char* xb = reinterpret_cast<const char*>(a.x16) + ((((int64_t)n * g.Di + id0) * g.Hi + ih0) * g.Wi + iw0) * (int64_t)cin2 + chunk * 32;
+        const unsigned limg = lds_base + (unsigned)(B_RES + lgrp * A_GRP + buf * A_IMG);
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+          if (lp0 + 2 * i < WS_A16_PIECES) {               // (wave-uniform)
+            const int gd = id0 + (int)(acrd[i] & 7u), gh = ih0 + (int)((acrd[i] >> 3) & 7u), gw = iw0 + (int)((acrd[i] >> 6) & 31u);
+            const bool ok = (acrd[i] >> 11) != 0u && (unsigned)gd < (unsigned)g.Di && (unsigned)gh < (unsigned)g.Hi && (unsigned)gw < (unsigned)g.Wi;
+            const char* src = ok ? xb + aoff[i] : reinterpret_cast<const char*>(a.zero16);   // zero padding, and the tail of piece 20
+            __builtin_amdgcn_global_load_lds((glb_vp)src, (lds_vp)(uintptr_t)(limg + (unsigned)((lp0 + 2 * i) * 1024)), 16, 0, 0);
+          }
+        }
+      };
+      // the 14 * NT weight pieces (step, output tile) of a chunk: the hi image of [step][tile][lane][hi, lo]
+      auto issue_b = [&](int chunk, int buf) {
+#pragma unroll
+        for (int i = 0; i < 14 * NT / 4; ++i) {
+          const int p = lw + 4 * i, s = p / NT, j = p % NT;       // (wave-uniform)
+          const uint4* src = wsrc + ((int64_t)(chunk * 14 + s) * g.ntiles + nt0 + j) * 128 + lane * 2;
+          __builtin_amdgcn_global_load_lds((glb_vp)src, (lds_vp)(uintptr_t)(lds_base + (unsigned)(buf * B_ALL + p * 1024)), 16, 0, 0);
+        }
+      };
+      auto issue_block = [&](int blk) {
+        const int round = blk / nch, chunk = blk - round * nch;
+        const int t = t_begin + round * 2 * T + lgrp;      // (item_tile of the group this wave loads for)
+        if (nch != 2 || blk < 2) issue_b(chunk, blk & 1);  // (two chunks: chunk c stays in buffer c)
+        if (t < t_end) issue_a(t, chunk, blk & 1);
+      };
+      static_assert(14 * NT % 4 == 0, "weight pieces per loader wave");
+      if (n_blocks > 0) issue_block(0);
+      for (int blk = 0; blk < n_blocks; ++blk) {
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");       // block blk handed over
+        if (blk + 1 < n_blocks) issue_block(blk + 1);
+      }
+    }
+  } else if (n_blocks > 0) {
     // the first item of either group: requested AND waited for before the code of the two groups parts (hipcc hoists the common
     // request above the branch and copies the destination registers into each side's own: after the wait that is harmless; the
     // latency of this one fetch is exposed once per launch)
@@ -420,13 +501,13 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
       float u1 = s1[j], u2 = s2[j];
       u1 += __shfl_xor(u1, 16, 64); u1 += __shfl_xor(u1, 32, 64);
       u2 += __shfl_xor(u2, 16, 64); u2 += __shfl_xor(u2, 32, 64);
-      if (kq == 0) {
+      if (kq == 0 && (!IN16 || wave < 8)) {                // (IN16: the loader waves have no sums)
         red[((wave * NT + j) * 16 + r) * 2 + 0] = u1;
         red[((wave * NT + j) * 16 + r) * 2 + 1] = u2;
       }
     }
     int* red_n = reinterpret_cast<int*>(red + 8 * NT * 16 * 2);
-    if (lane == 0) red_n[wave] = stats_n;
+    if (lane == 0 && (!IN16 || wave < 8)) red_n[wave] = stats_n;
     __syncthreads();
     if (tid < 2 * NT * 16 * 2) {
       const int gsel = tid / (NT * 16 * 2), t2 = tid % (NT * 16 * 2);
@@ -444,12 +525,14 @@ __global__ __launch_bounds__(512) void convws_kernel(const ConvArgsB a, const Ws
 }
 
 namespace {
-template <bool X3>
+template <bool X3, bool IN16 = false>
 int launch_ws(const ConvArgsB& a, const WsWork& wk, int grid, hipStream_t st) {
-  const size_t lds = (size_t)14 * WS_NT * 1024 * (X3 ? 2 : 1) + (size_t)2 * WS_NVOX * 32 * (X3 ? 2 : 1) + 8 * WS_NT * 16 * 2 * sizeof(float) + 64;
+  const size_t lds = (IN16 ? (size_t)2 * 14 * WS_NT * 1024 + (size_t)4 * WS_A16_PIECES * 1024      // two weight chunks, two A images per group
+                           : (size_t)14 * WS_NT * 1024 * (X3 ? 2 : 1) + (size_t)2 * WS_NVOX * 32 * (X3 ? 2 : 1)) +
+                     8 * WS_NT * 16 * 2 * sizeof(float) + 64;
   if (lds > 160 * 1024) return CWF_E_TOOLARGE;
-  CWF_MAX_LDS_ONCE((&convws_kernel<X3>));
-  hipLaunchKernelGGL((convws_kernel<X3>), dim3(grid), dim3(512), lds, st, a, wk);
+  CWF_MAX_LDS_ONCE((&convws_kernel<X3, IN16>));
+  hipLaunchKernelGGL((convws_kernel<X3, IN16>), dim3(grid), dim3(IN16 ? 768 : 512), lds, st, a, wk);
   CWF_LAUNCH_CHECK();
   return 0;
 }
@@ -465,31 +548,51 @@ static int g_ws_x3 = 0;
 extern "C" int cwf_debug_ws_x3(int v) { const int old = g_ws_x3; g_ws_x3 = v; return old; }
 int cwf_ws_takes_x3() { return g_ws_x3; }
 
-// Returns 1 and launches if the layer is one this kernel takes (3x3x3 stride 1, Cin a multiple of 16 and >= 32, Cout a multiple of 32,
-// extents multiples of the 4x4x16 tile, no per-channel output scale, enough tiles to occupy the chip); 0 = not eligible (the caller
-// falls through to the tap-table kernel).  The launch status is returned through *rc.
-int cwf_try_conv_ws(int op, int x3, ConvArgsB& a, hipStream_t st, int* rc) {
-  const ConvGeom& g = a.g;
-  if (op != CWF_CONV3_S1 || a.groups || a.out_scale || (x3 && !g_ws_x3)) return 0;
-  if (g.Cin < 32 || (g.Cin & 15) || (g.Cout & 31)) return 0;
-  if ((g.Do & 3) || (g.Ho & 3) || (g.Wo & 15)) return 0;
-  if (g.x_ldc < g.Cin || (g.x_ldc & 3)) return 0;
-  WsWork wk;
-  wk.ngroups = g.Cout / 32;
-  if (wk.ngroups > 32) return 0;
-  const int64_t tiles = (int64_t)g.N * (g.Do / 4) * (g.Ho / 4) * (g.Wo / 16);
+// The layers this kernel takes: 3x3x3 stride 1, Cin a multiple of 16 and >= 32, Cout a multiple of 32, extents multiples of the 4x4x16
+// tile, enough tiles to occupy the chip.  ONE function for the dispatch below and for cwf_conv_x16_ok (conv_bf16.hip), which tells the
+// Python side whether a data gradient may be handed a bf16 image alone.  Fills the work split.
+static bool ws_takes(int op, int N, int Do, int Ho, int Wo, int Cin, int Cout, WsWork& wk) {
+  if (op != CWF_CONV3_S1 || N <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0) return false;
+  if (Cin < 32 || (Cin & 15) || (Cout & 31) || Cout <= 0) return false;
+  if ((Do & 3) || (Ho & 3) || (Wo & 15)) return false;
+  wk.ngroups = Cout / 32;
+  if (wk.ngroups > 32) return false;
+  const int64_t tiles = (int64_t)N * (Do / 4) * (Ho / 4) * (Wo / 16);
   // small layers (fewer (tile, output group) units than CUs; measured at 128 ch @ 16^3: 68 us here against 48): the tap-table kernel's
   // many small workgroups fill the chip better
-  if (tiles * wk.ngroups < g_ws_min_units) return 0;
-  // the geometry of a 4x4x16 tile (the caller built it for its own tile choice)
-  int e = cwf_build_geom(a.g, op, g.N, g.Di, g.Hi, g.Wi, g.Cin, g.x_ldc, g.Do, g.Ho, g.Wo, g.Cout, g.y_ldc, 16);
-  if (e) { *rc = e; return 1; }
+  if (tiles * wk.ngroups < g_ws_min_units || tiles > 0x7fffffff) return false;
   wk.tiles = (int)tiles;
   int per = (32 / wk.ngroups) * wk.ngroups;               // workgroups per XCD, a multiple of the group count
   wk.slots = 8 * (per / wk.ngroups);
   wk.xcd_perm = 1;
   if (wk.slots * 2 > wk.tiles) { wk.slots = (wk.tiles + 1) / 2; wk.xcd_perm = 0; }      // at least two tiles per workgroup (one per group)
+  return true;
+}
+
+// 1 if a single-bf16 launch of this layer (no prologue, no output scale, no groups) can read its input as a bf16 image [N][D][H][W][Cin]
+// (convws_kernel<false, true>; the kernel forms 32-bit byte offsets into the image)
+int cwf_ws_takes_x16(int op, int N, int D, int H, int W, int Cin, int Cout) {
+  WsWork wk;
+  return ws_takes(op, N, D, H, W, Cin, Cout, wk) && (int64_t)N * D * H * W * Cin * 2 < (1ll << 32);
+}
+
+// Returns 1 and launches if the layer is one this kernel takes (ws_takes; no per-channel output scale, no groups); 0 = not eligible (the
+// caller falls through to the tap-table kernel).  With a.x16 set the input is that bf16 image.  The launch status is returned through *rc.
+int cwf_try_conv_ws(int op, int x3, ConvArgsB& a, hipStream_t st, int* rc) {
+  const ConvGeom& g = a.g;
+  const bool in16 = a.x16 != nullptr;
+  if (a.groups || a.out_scale || (x3 && !g_ws_x3)) return 0;
+  WsWork wk;
+  if (!ws_takes(op, g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, wk)) return 0;
+  if (in16) {
+    if (x3 || a.in_scale || a.in_slope != 1.f || !a.zero16 || g.Di != g.Do || g.Hi != g.Ho || g.Wi != g.Wo ||
+        !cwf_ws_takes_x16(op, g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout))
+      return 0;
+  } else if (g.x_ldc < g.Cin || (g.x_ldc & 3)) return 0;
+  // the geometry of a 4x4x16 tile (the caller built it for its own tile choice)
+  int e = cwf_build_geom(a.g, op, g.N, g.Di, g.Hi, g.Wi, g.Cin, g.x_ldc, g.Do, g.Ho, g.Wo, g.Cout, g.y_ldc, 16);
+  if (e) { *rc = e; return 1; }
   const int grid = wk.slots * wk.ngroups;
-  *rc = x3 ? launch_ws<true>(a, wk, grid, st) : launch_ws<false>(a, wk, grid, st);
+  *rc = in16 ? launch_ws<false, true>(a, wk, grid, st) : x3 ? launch_ws<true>(a, wk, grid, st) : launch_ws<false>(a, wk, grid, st);
   return 1;
 }

@@ -20,6 +20,7 @@ D = C.c_double
 SIGNATURES = {
     "cwf_version": [],
     "cwf_conv": [P, P],
+    "cwf_conv_x16_ok": [I, I, I, I, I, I, I],
     "cwf_wgrad": [P, P, P],
     "cwf_gather_split_bf16": [P, I, L, P],
     "cwf_wgrad_nsplit": [I, I, I, I, I, I, I],

@@ -255,8 +255,8 @@ class _ConvFn(torch.autograd.Function):
         # (no producer wrote a bf16 image of a gradient that comes out of a stride-2 data gradient: the weight gradient converts it on
         # the side stream -- one conversion here on the main stream, for both gradients, measured 0.3 % slower)
         dy16 = getattr(dy, "_cwf16", None) if out_scale is None else None
-        dg16 = dy16 if (dy16 is not None and getattr(K, "bf16_dgrad_ok", lambda *a: False)(
-            spec.op, spec.cin, spec.cout, dy.shape[1] * dy.shape[2] * dy.shape[3])) else None     # the data gradient reads the bf16 image
+        dg16 = dy16 if (dy16 is not None and dy.shape[-1] == spec.cout and getattr(K, "bf16_dgrad_ok", lambda *a: False)(
+            spec.op, spec.cin, spec.cout, dy.shape)) else None     # the data gradient reads the bf16 image
         if getattr(dy, "_cwf_f32_missing", False) and not (use16 and dy16 is not None and (dg16 is not None or not ctx.needs_input_grad[0])
                                                            and not ctx.has_res):
             dy = _dy_f32(K, dy)                         # some consumer below reads the fp32 tensor
@@ -471,7 +471,7 @@ def conv(x, w, b, spec, in_norm=None, slope=1.0, residual=None, out_scale=None, 
         okd = getattr(backend(), "bf16_dgrad_ok", None)
         # (with a residual the fp32 gradient is needed as well: it is the residual's gradient)
         y._cwf_want16 = "only" if (_SINGLE_CONSUMER and residual is None and okd is not None and
-                                   okd(spec.op, spec.cin, spec.cout, y.shape[1] * y.shape[2] * y.shape[3])) else True
+                                   y.shape[-1] == spec.cout and okd(spec.op, spec.cin, spec.cout, y.shape)) else True
     st = (s1, s2) if want_stats else None
     return (y, st, xc) if carry else (y, st)
 

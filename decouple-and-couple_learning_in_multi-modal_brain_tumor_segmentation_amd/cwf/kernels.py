@@ -244,7 +244,7 @@ class HipBackend:
             a.nb_x, a.nb_scale, a.nb_shift = nb_x.data_ptr(), nb_scale.data_ptr(), nb_shift.data_ptr()
         if x16 is not None:
             # the input as a bf16 image (bf16_dgrad_ok): x itself is not read
-            assert x16.dtype == torch.bfloat16 and x16.is_contiguous() and tuple(x16.shape) == (n, di, hi, wi, 16)
+            assert x16.dtype == torch.bfloat16 and x16.is_contiguous() and tuple(x16.shape) == (n, di, hi, wi, cin)
             a.x16, a.zero16 = x16.data_ptr(), self.zero16(x.device).data_ptr()
         if y16 is not None:
             # the output also as a bf16 image (y16 [N,D,H,W,cout] bfloat16)
@@ -291,9 +291,13 @@ class HipBackend:
             return 32                                      # wgrad_s1d_kernel (32-channel output groups)
         return 0
 
-    def bf16_dgrad_ok(self, op, cin, cout, nvox):
-        """the data gradient of such a layer can read its incoming gradient as a bf16 image (conv(..., x16=))"""
-        return op == pk.CONV3_S1 and cin == 16 and cout == 16 and nvox >= 32768 and (_DGRAD_PRECISION or _PRECISION) == "bf16"
+    def bf16_dgrad_ok(self, op, cin, cout, shape):
+        """the data gradient of such a layer (cin -> cout, output [n, d, h, w, cout] = shape) can read its incoming gradient as a bf16 image
+        (conv(..., x16=)): the library's own answer for that launch, whose input channels are the forward layer's outputs"""
+        if op != pk.CONV3_S1 or (_DGRAD_PRECISION or _PRECISION) != "bf16":
+            return False
+        n, d, h, w = shape[:4]
+        return bool(self.lib.cwf_conv_x16_ok(op, n, d, h, w, cout, cin))
 
     def zero16(self, device):
         z = getattr(self, "_zero16", None)

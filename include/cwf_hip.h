@@ -68,9 +68,11 @@ enum { CWF_FP32 = 0, CWF_BF16X3 = 1, CWF_BF16 = 2 };
  *            cls_wise_former.py:157-204): stats receives per (n, channel) S1 = sum g*act'(h), S2 = sum g*act'(h)*h with
  *            h = nb_x*nb_scale + nb_shift (what cwf_in_bwd_stats computes in a pass of its own) instead of (sum y, sum y^2).
  *            bf16 forms only; stats required.
- *   x16      the input as a bf16 image [N][D][H][W][16] (x is then not read), zero16 = 16 zero bytes: the single-bf16 data gradient
- *            of a 3x3x3 stride-1 16 -> 16 layer of >= 32768 voxels reading the image of dy that cwf_in_bwd_apply_ex wrote
- *            (EnBlock1 / EnBlock1_1 / DeBlock2 / DeBlock2_1).  No prologue, no out_scale.
+ *   x16      the input as a bf16 image [N][D][H][W][Cin] (x is then not read), zero16 = 16 zero bytes: the single-bf16 data gradient
+ *            of a 3x3x3 stride-1 layer reading the image of dy that cwf_in_bwd_apply_ex wrote -- the 16 -> 16 layers of >= 32768
+ *            voxels (EnBlock1 / EnBlock1_1 / DeBlock2 / DeBlock2_1) and the 32- / 64-channel layers at 64^3 / 32^3 that the
+ *            weight-stationary kernel takes: exactly the layers for which cwf_conv_x16_ok answers 1; any other layer returns
+ *            CWF_E_BADARG.  No prologue, no out_scale.  Results are those of the same launch reading the fp32 tensor.
  *   y16      also write the output as a bf16 image [N][Do*Ho*Wo][Cout] (DeUp_Cat.conv3, cls_wise_former.py:716-729: the input of the
  *            next block's first conv, whose weight gradient reads that image): in the same launch where the pointwise stream
  *            kernel takes the layer, otherwise by a cwf_to_bf16 pass after it.  No nb_x, no out_scale.
@@ -92,6 +94,9 @@ struct cwf_conv_args {
   int N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout;
 };
 int cwf_conv(const struct cwf_conv_args* args /* host */, void* stream);
+/* 1 if cwf_conv takes a single-bf16 3x3x3 stride-1 launch of these dimensions (Cin / Cout of the LAUNCH: for a data gradient the forward
+ * layer's Cout / Cin) with its input as a bf16 image (x16); 0 otherwise.  Host code only; the same code the dispatch evaluates. */
+int cwf_conv_x16_ok(int op, int N, int D, int H, int W, int Cin, int Cout);
 
 /* Weight gradient (+ bias gradient) of the same family (op in {CONV3_S1, CONV3_S2, CONV1, CONVT2}):
  *   dW[tap][ci][co] = sum_{n,vox} act(x*in_scale+in_shift)[n, vox*is+tap, ci] * dy[n, vox, co]

@@ -117,6 +117,7 @@ SIGNATURES = {
     "cwf_prepare_batch": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_prepare_batch_affine": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_prepare_batch_elastic": [P, I, I, I, I, P, L, P, L, P, L, P],
+    "cwf_augment_intensity": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_window_gather": [P, P, P, I, I, P],
     "cwf_window_blend": [P, P, P, P, I, I, I, P],
     "cwf_window_finalize": [P, P, P, P, P],
@@ -197,6 +198,22 @@ class PrepAffineSample(C.Structure):
 class PrepElasticSample(C.Structure):
     """struct cwf_prep_elastic_sample (include/cwf_hip.h)"""
     _fields_ = PrepAffineSample._fields_ + [("disp", P), ("G0", I), ("G1", I), ("G2", I)]
+
+
+class IntensitySample(C.Structure):
+    """struct cwf_intensity_sample (include/cwf_hip.h)"""
+    _fields_ = [("taps", (F * 7) * 4), ("amp", F * 4), ("key", U64), ("gamma", F * 4), ("blur", I), ("noise", I), ("gam", I)]
+
+
+INTENSITY_TILE = (10, 10, 32)   # CWF_INTENSITY_T0, _T1, _T2: the blur's output tile (3-voxel halo on every side)
+
+
+def intensity_ws_floats(nb, crop):
+    """floats of device scratch cwf_augment_intensity needs for nb samples of `crop` voxels when some gamma bit is set"""
+    tiles = 1
+    for c, t in zip(crop, INTENSITY_TILE):
+        tiles *= (int(c) + t - 1) // t
+    return 8 * int(nb) * tiles
 
 
 WINDOW_MAX_STARTS = 128   # CWF_WINDOW_MAX_STARTS

@@ -1521,7 +1521,10 @@ class HipBackend:
         batch goes through cwf_prepare_batch_elastic, the samples without one with disp = NULL.  The grids of the call are packed into
         one pinned host buffer and copied to the device by one non-blocking copy on the current stream ahead of the launches (no host
         synchronisation; both buffers are handed back to torch's stream-ordered allocators once the launches are enqueued).  out:
-        (x, target, edge) to write into; each needs contiguous inner dimensions, its sample stride may be larger than one sample."""
+        (x, target, edge) to write into; each needs contiguous inner dimensions, its sample stride may be larger than one sample.
+        .blur / .noise / .noise_key / .gamma (utils.data.AugParams): when some channel of some sample has one on, the intensity stage
+        (cwf_augment_intensity) follows on x: in place without a blur; with one the prepare kernel writes x into a workspace from
+        torch's allocator and the stage writes the batch's x.  With all of them off nothing but the prepare entry is called."""
         crop = tuple(int(c) for c in crop)
         if len(crop) != 3:
             raise ValueError("prepare_batch: crop needs three extents, got %r" % (crop,))
@@ -1585,9 +1588,40 @@ class HipBackend:
                 inner = torch.empty(shape[1:], device="meta").stride()
                 if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or tuple(t.stride()[1:]) != inner:
                     raise ValueError("prepare_batch: out %s must be a %s %s tensor on %s with contiguous samples" % (name, dt, shape, dev))
-        self._call(entry, ctypes.addressof(samples), nb, crop[0], crop[1], crop[2], x.data_ptr(), x.stride(0),
+        stage = self._intensity_samples(params)
+        x_prep = x
+        if stage is not None and any(s.blur for s in stage):      # a blur reads its neighbours: not in place
+            x_prep = torch.empty((nb, 4) + tuple(x.shape[2:]), dtype=_f32, device=dev)
+        self._call(entry, ctypes.addressof(samples), nb, crop[0], crop[1], crop[2], x_prep.data_ptr(), x_prep.stride(0),
                    target.data_ptr(), target.stride(0), edge.data_ptr(), edge.stride(0), self._stream())
+        if stage is not None:
+            nws = _lib.intensity_ws_floats(nb, crop) if any(s.gam for s in stage) else 0
+            ws = torch.empty(nws, dtype=_f32, device=dev) if nws else None
+            self._call("cwf_augment_intensity", ctypes.addressof(stage), nb, crop[0], crop[1], crop[2], x_prep.data_ptr(),
+                       x_prep.stride(0), x.data_ptr(), x.stride(0), _p(ws), nws, self._stream())
         return x, target, edge
+
+    @staticmethod
+    def _intensity_samples(params):
+        """cwf_intensity_sample [len(params)] of the samples' blur / noise / gamma, or None when every channel of every one is off"""
+        from utils import data
+        stage = (_lib.IntensitySample * len(params))()
+        on = False
+        for s, p in zip(stage, params):
+            blur, noise, gamma = (getattr(p, k, None) for k in ("blur", "noise", "gamma"))
+            s.key = int(getattr(p, "noise_key", 0) or 0)
+            for c in range(4):
+                if blur is not None and blur[c] > 0.0:
+                    s.taps[c][:] = data.blur_taps64(blur[c])              # (ctypes rounds to float32, to nearest)
+                    s.blur |= 1 << c
+                if noise is not None and noise[c] > 0.0:
+                    s.amp[c] = data.noise_amp64(noise[c])
+                    s.noise |= 1 << c
+                if gamma is not None and gamma[c] > 0.0:
+                    s.gamma[c] = float(gamma[c])
+                    s.gam |= 1 << c
+            on = on or bool(s.blur or s.noise or s.gam)
+        return stage if on else None
 
     def normalize_nonzero(self, image):
         """In place: per-channel z-score of one subject image (contiguous fp32 [4, H, W, D] on a GPU) over the voxels whose

@@ -100,6 +100,12 @@ def build_parser():
     p.add_argument("--aug_elastic", default=0.0, type=float,
                    help="(--device_data) e > 0: deform the crop by a cubic B-spline of control displacements ~ U(-e, e) voxels")
     p.add_argument("--aug_elastic_grid", default=7, type=int, help="(--aug_elastic) control points per axis, 4..8")
+    p.add_argument("--aug_blur", default=0.0, type=float,
+                   help="(--device_data) s in [0.5, 1.5]: Gaussian blur (radius 3) of each channel with probability 1/2, sigma ~ U(0.5, s)")
+    p.add_argument("--aug_noise", default=0.0, type=float,
+                   help="(--device_data) n > 0: additive noise on each channel with probability 1/2, sigma ~ U(0, n)")
+    p.add_argument("--aug_gamma", default=0.0, type=float,
+                   help="(--device_data) g in (0, 1): gamma map of each channel's range with probability 1/2, exponent ~ U(1-g, 1+g)")
     p.add_argument("--normalize", default=False, type=_bool,
                    help="(--device_data) z-score each subject's channels over its brain mask (four-channel sum > 0) at load")
     p.add_argument("--accum_steps", default=1, type=int,
@@ -125,6 +131,19 @@ def check_step_controls(args):
         raise SystemExit("--clip_grad_norm takes a norm > 0 (leave the flag out for no clipping)")
     if args.ema_decay is not None and not 0.5 <= args.ema_decay < 1.0:
         raise SystemExit("--ema_decay takes a decay in [0.5, 1) (leave the flag out for no EMA)")
+
+
+def check_intensity_aug(args):
+    """the values of --aug_blur / --aug_noise / --aug_gamma (SystemExit with the rule, like the other --aug_* checks)"""
+    if args.device_data == "off" and (args.aug_blur != 0.0 or args.aug_noise != 0.0 or args.aug_gamma != 0.0):
+        raise SystemExit("--aug_blur / --aug_noise / --aug_gamma run on the prepared crop on the device: they need --device_data cache "
+                         "or staged")
+    if args.aug_blur != 0.0 and not 0.5 <= args.aug_blur <= 1.5:
+        raise SystemExit("--aug_blur takes 0 (off) or a largest sigma in [0.5, 1.5] voxels")
+    if not 0.0 <= args.aug_noise < float("inf"):
+        raise SystemExit("--aug_noise takes a finite largest sigma >= 0")
+    if not 0.0 <= args.aug_gamma < 1.0:
+        raise SystemExit("--aug_gamma takes a half-width in [0, 1) of the exponent's range about 1")
 
 
 def should_save(epoch, end_epoch, save_freq):
@@ -163,7 +182,8 @@ def make_device_dataset(args, device):
         lst = lst if os.path.isfile(lst) else None
     return data.DeviceBraTS(source, device, crop, args.seed, flip=args.aug_flip, intensity=args.aug_intensity,
                             normalize=args.normalize, cache=(args.device_data == "cache"), list_file=lst, rotate=args.aug_rotate,
-                            scale=args.aug_scale, elastic=args.aug_elastic, elastic_grid=args.aug_elastic_grid)
+                            scale=args.aug_scale, elastic=args.aug_elastic, elastic_grid=args.aug_elastic_grid,
+                            blur=args.aug_blur, noise=args.aug_noise, gamma=args.aug_gamma)
 
 
 def main(argv=None):
@@ -178,6 +198,7 @@ def main(argv=None):
         raise SystemExit("--aug_elastic deforms the crop on the device: it needs --device_data cache or staged")
     if args.aug_elastic < 0.0 or not 4 <= args.aug_elastic_grid <= 8:
         raise SystemExit("--aug_elastic takes voxels >= 0 and --aug_elastic_grid 4 to 8 control points per axis")
+    check_intensity_aug(args)
     check_step_controls(args)
     from cwf import kernels
     from cwf.parallel import shard_indices

@@ -12,9 +12,11 @@ Edge codes are derived from the label with utils.synthetic.edge_codes (boundary 
 
 ``DeviceBraTS`` / ``prepare_batch`` produce the same tuple on the GPU (csrc/prep.hip: crop, optional flips and intensity scale / shift,
 label remap and edge codes in one launch per eight samples; with a matrix in the parameters the crop is rotated and zoomed, trilinear for
-the image and nearest for the label; with a control grid it is deformed elastically on top of that), bit-equal to the CPU statement in
-this module."""
+the image and nearest for the label; with a control grid it is deformed elastically on top of that; with blur, noise or gamma in the
+parameters csrc/intensity.hip then runs the intensity stage on the prepared crop), bit-equal to the CPU statement in this module,
+except gamma-mapped channels, which are bounded (below: _intensity_stage_cpu)."""
 import glob
+import math
 import os
 
 import numpy as np
@@ -113,10 +115,14 @@ class AugParams:
     (float32 [4] each; None = intensity off), matrix: the linear part M[d][j] of the output -> source map about the crop centre
     (nine float32 values, row-major; None = no resampling, the plain crop), and disp: the control grid of the elastic deformation,
     float32 [3, G0, G1, G2] with 4 <= G_d <= 8, displacements in voxels of the crop-local source coordinate (a read-only array; None =
-    no deformation.  Non-finite control values are allowed: the voxels they reach read nothing)."""
-    __slots__ = ("origin", "flip", "scale", "shift", "matrix", "disp")
+    no deformation.  Non-finite control values are allowed: the voxels they reach read nothing).  The intensity stage on the prepared
+    crop (_intensity_stage_cpu), per channel: blur, the Gaussian's sigma in voxels (float32 [4], 0 = off; None = all off); noise, the
+    sigma of the additive noise (float32 [4], 0 = off) with noise_key, an int in [0, 2^63), the key of its counter-based stream;
+    gamma, the exponent (float32 [4], 0 = off)."""
+    __slots__ = ("origin", "flip", "scale", "shift", "matrix", "blur", "noise", "noise_key", "gamma", "disp")
 
-    def __init__(self, origin, flip=(False, False, False), scale=None, shift=None, matrix=None, disp=None):
+    def __init__(self, origin, flip=(False, False, False), scale=None, shift=None, matrix=None, disp=None, *, blur=None, noise=None,
+                 noise_key=None, gamma=None):
         self.origin = tuple(int(o) for o in origin)
         self.flip = tuple(bool(f) for f in flip)
         if (scale is None) != (shift is None):
@@ -135,9 +141,23 @@ class AugParams:
                                  % (ELASTIC_GRID_MIN, ELASTIC_GRID_MAX, tuple(disp.shape)))
             disp.setflags(write=False)
         self.disp = disp
+        for name, val in (("blur", blur), ("noise", noise), ("gamma", gamma)):
+            if val is not None:
+                val = tuple(float(v) for v in np.asarray(val, dtype=np.float32).reshape(-1))
+                if len(val) != 4 or not all(np.isfinite(v) and v >= 0.0 for v in val):
+                    raise ValueError("AugParams: %s takes 4 finite values >= 0 (0 = off), got %r" % (name, val))
+            setattr(self, name, val)
+        if noise_key is not None and not 0 <= int(noise_key) < 2 ** 63:
+            raise ValueError("AugParams: noise_key must lie in [0, 2^63), got %r" % (noise_key,))
+        self.noise_key = 0 if noise_key is None else int(noise_key)
 
     def at_origin(self, origin):
-        return AugParams(origin, self.flip, self.scale, self.shift, self.matrix, self.disp)
+        return AugParams(origin, self.flip, self.scale, self.shift, self.matrix, self.disp, blur=self.blur, noise=self.noise,
+                         noise_key=self.noise_key, gamma=self.gamma)
+
+    def intensity_stage(self):
+        """True when blur, noise or gamma is on for some channel"""
+        return any(v is not None and any(c > 0.0 for c in v) for v in (self.blur, self.noise, self.gamma))
 
     def source_box(self, crop):
         """Integer bounds ((lo_0, hi_0), ...) relative to the origin, hi exclusive, that contain every source index the crop reads
@@ -170,6 +190,9 @@ class AugParams:
     def __repr__(self):
         head = "AugParams(origin=%r, flip=%r, scale=%r, shift=%r" % (self.origin, self.flip, self.scale, self.shift)
         head += "" if self.matrix is None else ", matrix=%r" % (self.matrix,)
+        head += "" if self.blur is None else ", blur=%r" % (self.blur,)
+        head += "" if self.noise is None else ", noise=%r, noise_key=%r" % (self.noise, self.noise_key)
+        head += "" if self.gamma is None else ", gamma=%r" % (self.gamma,)
         if self.disp is not None:
             head += ", disp=float32%r max |.| %r" % (list(self.disp.shape), float(np.max(np.abs(self.disp))))
         return head + ")"
@@ -185,13 +208,18 @@ def rotation_zoom_matrix(angles_deg, zoom=1.0):
     return ((rz @ ry @ rx) / float(zoom)).astype(np.float32).reshape(9)
 
 
-def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7):
+def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7,
+                blur=0.0, noise=0.0, gamma=0.0):
     """Parameters of sample `index` in `epoch`: a pure function of the arguments, drawn from default_rng([seed, epoch, index]).  The
     origin is drawn first, by random_crop_origin's calls, so with augmentation off it is the origin NpzBraTS / SyntheticBraTS pick.
     flip: three uniforms, each < 0.5 flipping that axis; intensity f > 0: scale ~ U(1-f, 1+f)[4], then shift ~ U(-f, f)[4] (float32).
     Drawn after all of those, so that they do not depend on it: rotate r > 0: three Euler angles ~ U(-r, r) degrees; scale f > 0: an
     isotropic zoom ~ U(1-f, 1+f); matrix = rotation_zoom_matrix(angles, zoom), None with both off.  Last of all, elastic e > 0: the
-    control grid disp ~ U(-e, e) voxels, float32 [3, g, g, g] with g = elastic_grid; None with e = 0."""
+    control grid disp ~ U(-e, e) voxels, float32 [3, g, g, g] with g = elastic_grid; None with e = 0.  After everything above, so that
+    no earlier field depends on them, the intensity stage, each transform switching a channel on where its u < 0.5 and making all its
+    draws whatever the outcome: blur s (0, or 0.5 <= s <= 1.5): u = random(4), sigma ~ U(0.5, s)[4]; noise n > 0: u = random(4),
+    sigma ~ U(0, n)[4], noise_key = integers(0, 2^63); gamma g (0 < g < 1): u = random(4), exponent ~ U(1-g, 1+g)[4].  A channel that
+    is off has the value 0; a transform that is off is None."""
     rng = np.random.default_rng([int(seed), int(epoch), int(index)])
     origin = random_crop_origin(tuple(full), tuple(crop), rng)
     r, z = float(rotate), float(scale)
@@ -210,7 +238,24 @@ def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotat
     e, g = float(elastic), int(elastic_grid)
     if e > 0.0:
         disp = rng.uniform(-e, e, (3, g, g, g)).astype(np.float32)
-    return AugParams(origin, fl, scale, shift, matrix, disp)
+    bl = ns = gm = key = None
+    s, n, g = float(blur), float(noise), float(gamma)
+    if s != 0.0 and not 0.5 <= s <= 1.5:
+        raise ValueError("draw_params: blur takes 0 or a largest sigma in [0.5, 1.5], got %r" % (blur,))
+    if n < 0.0 or not np.isfinite(n):
+        raise ValueError("draw_params: noise takes a finite sigma >= 0, got %r" % (noise,))
+    if not 0.0 <= g < 1.0:
+        raise ValueError("draw_params: gamma takes a half-width in [0, 1), got %r" % (gamma,))
+    if s > 0.0:
+        u, sig = rng.random(4), rng.uniform(0.5, s, 4)
+        bl = np.where(u < 0.5, sig, 0.0).astype(np.float32)
+    if n > 0.0:
+        u, sg, key = rng.random(4), rng.uniform(0.0, n, 4), int(rng.integers(0, 2 ** 63))
+        ns = np.where(u < 0.5, sg, 0.0).astype(np.float32)
+    if g > 0.0:
+        u, ex = rng.random(4), rng.uniform(1.0 - g, 1.0 + g, 4)
+        gm = np.where(u < 0.5, ex, 0.0).astype(np.float32)
+    return AugParams(origin, fl, scale, shift, matrix, disp, blur=bl, noise=ns, noise_key=key, gamma=gm)
 
 
 _Q_MAX = np.float32(2.0 ** 30)      # |q| at and beyond it (and NaN): the voxel lies outside every volume
@@ -342,6 +387,86 @@ def _resample_cpu(img, lab, p, crop):
     return torch.from_numpy(x), torch.from_numpy(t)
 
 
+BLUR_RADIUS = 3                                 # the Gaussian is truncated here: seven taps
+NOISE_DIV = np.sqrt((65536.0 ** 2 - 1.0) / 3.0)   # the standard deviation of the sum of four uniform 16-bit integers
+
+
+def blur_taps64(sigma):
+    """the seven taps before their rounding to float32, as Python floats (the per-batch path of HipBackend.prepare_batch takes them
+    from here: a few microseconds per channel)"""
+    sg = float(np.float32(sigma))
+    e = [math.exp(-0.5 * ((j / sg) * (j / sg))) for j in range(-BLUR_RADIUS, BLUR_RADIUS + 1)]
+    total = sum(e)
+    return [v / total for v in e]
+
+
+def blur_taps(sigma):
+    """float32 [7]: w[j] = exp(-0.5 ((j - 3) / sigma)^2) / sum_j exp(...), in float64 from the float32 sigma"""
+    return np.array(blur_taps64(sigma), dtype=np.float64).astype(np.float32)
+
+
+def noise_amp64(sigma):
+    return float(np.float32(sigma)) / NOISE_DIV
+
+
+def noise_amp(sigma):
+    """float32(sigma / D), D = sqrt((65536^2 - 1) / 3), in float64 from the float32 sigma"""
+    return np.float32(noise_amp64(sigma))
+
+
+def noise_ints(key, start, n):
+    """int64 [n]: s of the statement in _intensity_stage_cpu for the counters key + start .. key + start + n - 1 (wrapping)"""
+    with np.errstate(over="ignore"):
+        ctr = np.arange(int(start), int(start) + int(n), dtype=np.uint64) + np.uint64(int(key))
+    h = syn._splitmix64(ctr)
+    m = np.uint64(0xFFFF)
+    s = (h & m) + ((h >> np.uint64(16)) & m) + ((h >> np.uint64(32)) & m) + (h >> np.uint64(48))
+    return s.astype(np.int64) - 131070
+
+
+def _blur_axis_cpu(a, w, axis):
+    n = a.shape[axis]
+    pad = np.take(a, np.clip(np.arange(-BLUR_RADIUS, n + BLUR_RADIUS), 0, n - 1), axis=axis)
+    tap = [w[j] * np.take(pad, np.arange(j, j + n), axis=axis) for j in range(2 * BLUR_RADIUS + 1)]
+    y = tap[0] + tap[1]
+    for j in range(2, 2 * BLUR_RADIUS + 1):
+        y = y + tap[j]
+    return y.astype(np.float32)
+
+
+def _intensity_stage_cpu(x, p):
+    """The intensity stage on the prepared crop x [4, C0, C1, C2] (numpy float32, changed in place), every operation a float32
+    round-to-nearest one in the association written.  With V = C0*C1*C2 and v = (p0*C1 + p1)*C2 + p2, per channel c, in this order:
+      blur (sigma_c > 0): taps w = blur_taps(sigma_c) (radius 3: this project's definition); along axis 2, then 1, then 0
+          y[p] = (((((w0*a[p-3] + w1*a[p-2]) + w2*a[p-1]) + w3*a[p]) + w4*a[p+1]) + w5*a[p+2]) + w6*a[p+3]
+        with indices clamped to [0, C_d - 1]: the border is the crop's own (replicate); zeros from padding outside the volume are data
+      noise (sigma_c > 0): h = splitmix64(noise_key + uint64(c*V + v)), s = the sum of h's four 16-bit fields - 131070,
+          x = x + float32(s) * amp_c, amp_c = noise_amp(sigma_c): a sum of four uniforms, bounded at +-3.46 sigma, not a true normal
+      gamma (gamma_c > 0): mn, mx the NaN-ignoring minimum and maximum of the channel after the steps above, r = mx - mn; when r is
+          finite and > 0: u = (x - mn) / r, x = pow(u, gamma_c) * r + mn with a float32 power
+    A step that is off leaves the channel's bits alone.  The device differs from this only in the power: its powf is within a few
+    ulps of the correctly rounded one, so a gamma-mapped channel is bounded, not bit-equal."""
+    V = int(x[0].size)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for c in range(4):
+            if p.blur is not None and p.blur[c] > 0.0:
+                w = blur_taps(p.blur[c])
+                a = x[c]
+                for axis in (2, 1, 0):
+                    a = _blur_axis_cpu(a, w, axis)
+                x[c] = a
+            if p.noise is not None and p.noise[c] > 0.0:
+                s = noise_ints(p.noise_key, c * V, V).astype(np.float32).reshape(x[c].shape)
+                x[c] = x[c] + s * noise_amp(p.noise[c])
+            if p.gamma is not None and p.gamma[c] > 0.0:
+                mn, mx = np.fmin.reduce(x[c], axis=None), np.fmax.reduce(x[c], axis=None)
+                r = np.float32(mx - mn)
+                if np.isfinite(r) and r > 0:
+                    u = ((x[c] - mn) / r).astype(np.float32)
+                    x[c] = np.power(u, np.float32(p.gamma[c])).astype(np.float32) * r + mn
+    return x
+
+
 def _prepare_one_cpu(img, lab, p, crop):
     if p.matrix is not None or p.disp is not None:
         x, t = _resample_cpu(img, lab, p, crop)
@@ -355,6 +480,8 @@ def _prepare_one_cpu(img, lab, p, crop):
     if p.scale is not None:
         x = x * torch.tensor(p.scale, dtype=torch.float32).reshape(4, 1, 1, 1)
         x = x + torch.tensor(p.shift, dtype=torch.float32).reshape(4, 1, 1, 1)
+    if p.intensity_stage():
+        x = torch.from_numpy(_intensity_stage_cpu(np.array(x.numpy(), dtype=np.float32, order="C"), p))
     t[t == 4] = 3
     return x, t, syn.edge_codes(t)
 
@@ -363,8 +490,9 @@ def prepare_batch(images, labels, params, crop, out=None):
     """(x [B,4,*crop] float32, target [B,*crop] int64, edge [B,*crop] int64) from source volumes images[b] float32 [4,S0,S1,S2] and
     labels[b] uint8 [S0,S1,S2] (values 0..4): crop_pad at params[b].origin (with params[b].matrix or .disp: the resampled crop of
     _resample_cpu, any origin) -> torch.flip of the flipped crop axes -> x * scale then + shift in float32 -> label 4 -> 3 ->
-    utils.synthetic.edge_codes.  On GPU tensors this is one HIP launch per eight samples
-    (HipBackend.prepare_batch, bit-equal to the CPU statement); on CPU tensors it is the CPU statement itself.  out: (x, target, edge)
+    utils.synthetic.edge_codes; with params[b].blur / .noise / .gamma the intensity stage
+    (_intensity_stage_cpu) then acts on x.  On GPU tensors this is one HIP launch per eight samples, plus the stage's when it is on
+    (HipBackend.prepare_batch, bit-equal to the CPU statement except gamma-mapped channels); on CPU tensors it is the CPU statement itself.  out: (x, target, edge)
     to write into (sample stride free, samples contiguous)."""
     crop = tuple(int(c) for c in crop)
     if len(images) and images[0].is_cuda:
@@ -445,7 +573,9 @@ class NpzCropSource(Dataset):
     i at draw_params' origin, before any flip or intensity -- (image float32 [4,*crop], label uint8 [*crop], index) -- from one
     np.load + crop_pad (no edge codes).  `subjects`: .npz paths, or in-memory (image, label) pairs.  With rotate / scale / elastic on, the
     item is instead the part of the volume the resampled crop reads (staged_box: shapes differ from item to item); flip and
-    intensity are taken only because they move the matrix's place in draw_params' stream."""
+    intensity are taken only because they move the matrix's place in draw_params' stream.  DeviceBraTS's blur / noise / gamma are not
+    taken: draw_params draws them after the matrix and the grid, so they move nothing this class reads, and they act on the prepared
+    crop only, so the item is the same with and without them."""
 
     def __init__(self, subjects, crop, seed=1000, normalize=False, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0,
                  elastic_grid=7):
@@ -516,6 +646,8 @@ class DeviceBraTS:
     rotate, scale, elastic, elastic_grid); with augmentation off a batch equals torch.stack of NpzBraTS / SyntheticBraTS items.
     rotate (degrees) / scale > 0 turn the crop into a randomly rotated / zoomed one (trilinear image, nearest label) in the same
     launch; elastic (voxels) > 0 deforms it by a cubic B-spline of elastic_grid^3 control displacements ~ U(-elastic, elastic).
+    blur (largest sigma, 0.5..1.5) / noise (largest sigma) / gamma (half-width of the exponent's range about 1) > 0 switch the
+    intensity stage on per channel (draw_params), which runs on the prepared crop in launches of its own.
       cache=True   every subject is loaded once onto the device (fp32 image, uint8 label, optionally z-scored by normalize_nonzero)
       cache=False  "staged": NpzCropSource crops in DataLoader workers (batches()), the crops are uploaded from pinned memory and
                    prepared at origin 0 -- 36 MB per 128^3 sample over the host link instead of a whole subject.  With rotate /
@@ -523,12 +655,13 @@ class DeviceBraTS:
                    the batch is bit-equal to cache=True."""
 
     def __init__(self, source, device, crop=(128, 128, 128), seed=1000, flip=False, intensity=0.0, normalize=False, cache=True,
-                 list_file=None, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7):
+                 list_file=None, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7, blur=0.0, noise=0.0, gamma=0.0):
         self.device = torch.device(device)
         self.crop, self.seed, self.epoch = tuple(int(c) for c in crop), int(seed), 0
         self.flip, self.intensity, self.normalize, self.cache = bool(flip), float(intensity), bool(normalize), bool(cache)
         self.rotate, self.scale = float(rotate), float(scale)
         self.elastic, self.elastic_grid = float(elastic), int(elastic_grid)
+        self.blur, self.noise, self.gamma = float(blur), float(noise), float(gamma)
         if self.elastic > 0.0 and not ELASTIC_GRID_MIN <= self.elastic_grid <= ELASTIC_GRID_MAX:
             raise ValueError("DeviceBraTS: elastic_grid takes %d..%d control points per axis" % (ELASTIC_GRID_MIN, ELASTIC_GRID_MAX))
         self.affine = self.rotate > 0.0 or self.scale > 0.0 or self.elastic > 0.0      # the crop is resampled
@@ -588,7 +721,7 @@ class DeviceBraTS:
 
     def params(self, i):
         return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity, self.rotate, self.scale,
-                           self.elastic, self.elastic_grid)
+                           self.elastic, self.elastic_grid, self.blur, self.noise, self.gamma)
 
     def _missing(self, n):
         return torch.zeros((n, 4), dtype=torch.bool, device=self.device)

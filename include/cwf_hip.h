@@ -635,6 +635,39 @@ struct cwf_prep_elastic_sample {
  * is misaligned or comes with some G_d outside 4..8. */
 int cwf_prepare_batch_elastic(const struct cwf_prep_elastic_sample* h_samples, int B, int C0, int C1, int C2, float* x,
                               int64_t x_bstride, int64_t* target, int64_t t_bstride, int64_t* edge, int64_t e_bstride, void* stream);
+/* The intensity stage of one prepared sample x [4][C0][C1][C2] (utils/data.py: blur, noise, gamma).  blur / noise / gam are 4-bit
+ * channel masks (bit c = channel c); taps[c] are the seven blur weights, amp[c] the noise amplitude, gamma[c] the exponent.  Values
+ * of a channel whose bit is off are not used (taps and amp must still be finite, amp >= 0). */
+struct cwf_intensity_sample {
+  float taps[4][7];
+  float amp[4];
+  uint64_t key;
+  float gamma[4];
+  int blur, noise, gam;
+};
+#define CWF_INTENSITY_T0 10   /* the blur's tile: output voxels per workgroup along axis 0, 1, 2 (3-voxel halo on every side) */
+#define CWF_INTENSITY_T1 10
+#define CWF_INTENSITY_T2 32
+/* dst[b][c] = the stage applied to src[b][c], for each of the B samples (h_samples is HOST memory, passed by value, eight samples
+ * per launch: the call can be captured).  With V = C0*C1*C2, v = (p0*C1 + p1)*C2 + p2 and every operation a float32
+ * round-to-nearest one in the association written (no fused multiply-add), per channel c, in this order:
+ *   blur  (bit c of blur):  along axis 2, then 1, then 0, each pass rounded to float32,
+ *           y[p] = (((((w0*a[p-3] + w1*a[p-2]) + w2*a[p-1]) + w3*a[p]) + w4*a[p+1]) + w5*a[p+2]) + w6*a[p+3],  w = taps[c],
+ *           indices clamped to [0, C_d - 1] (replicate)
+ *   noise (bit c of noise): h = splitmix64(key + uint64(c*V + v)) (wrapping),
+ *           s = (h & 0xFFFF) + ((h >> 16) & 0xFFFF) + ((h >> 32) & 0xFFFF) + (h >> 48) - 131070,  x = x + float(s) * amp[c]
+ *   gamma (bit c of gam):   mn, mx = the NaN-ignoring minimum and maximum of the channel after the two steps above, r = mx - mn;
+ *           r not finite or not > 0: nothing; otherwise u = (x - mn) / r (correctly rounded), x = powf(u, gamma[c]) * r + mn
+ * A channel with a bit off keeps its bits through that step (with all three off it is copied, or left alone when src == dst).
+ * src and dst have their own sample strides (elements).  With a blur bit set anywhere src and dst must not overlap; without one
+ * they may be the same buffer (in place) or disjoint.  ws: device scratch of at least 8 * B * tiles floats, tiles =
+ * ceil(C0/T0) * ceil(C1/T1) * ceil(C2/T2), read and written only when some gam bit is set (the per-workgroup minima and maxima; a
+ * second launch per eight samples reduces them and applies gamma in place on dst).  Nothing synchronises with the host.
+ * CWF_E_BADARG, before any launch: B or a crop extent <= 0, a null or misaligned pointer (4 B), a stride smaller than one sample, a
+ * mask outside 0..15, a non-finite tap or amplitude or a negative amplitude, a gamma that is not finite or not > 0 where its bit is
+ * set, overlapping src and dst as above, gamma on with ws null or ws_floats too small; CWF_E_TOOLARGE: 2^31 voxels or more. */
+int cwf_augment_intensity(const struct cwf_intensity_sample* h_samples, int B, int C0, int C1, int C2, const float* src,
+                          int64_t src_bstride, float* dst, int64_t dst_bstride, float* ws, int64_t ws_floats, void* stream);
 /* In place on one subject image fp32 [4][V]: over the voxels whose ((x0 + x1) + x2) + x3 > 0 (float32), each channel becomes
  * float32((x - mean_c) / std_c) with the float64 mean and population std of that channel over those voxels (two passes); other voxels,
  * and channels with std 0, are untouched.  ws: CWF_NORM_WS_DOUBLES doubles of device scratch. */

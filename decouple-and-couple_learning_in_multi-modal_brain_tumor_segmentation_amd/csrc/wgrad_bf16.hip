@@ -55,6 +55,31 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned short* p0, const unsign
   const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
   return __builtin_bit_cast(bf16x8, v);
 }
+// the same on LDS byte addresses (the persistent kernels keep per-lane bases in registers and everything else in the ds_read
+// immediate): addr = first block row, addr + second = the block row four voxels on
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ bf16x8 tr_frag_at(unsigned addr, unsigned second) {
+  const s16x4 u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)addr);
+  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(addr + second));
+  const s16x8 w = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
+  return __builtin_bit_cast(bf16x8, w);
+}
+// ones operand for the bias row: bf16 1.0 = 0x3F80
+__device__ __forceinline__ bf16x8 ones_frag() {
+  const s16x8 ones_s = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
+  return __builtin_bit_cast(bf16x8, ones_s);
+}
+
+// tile index -> sample and output origin of a 4 x 4 x 16 tile (tiles_sp = tiles_d * tiles_h * tiles_w)
+struct TileOrigin { int n, od0, oh0, ow0; };
+__device__ __forceinline__ TileOrigin tile_origin(int tile, int tiles_sp, int tiles_h, int tiles_w) {
+  TileOrigin o;
+  o.n = tile / tiles_sp; int rem = tile - o.n * tiles_sp;
+  const int tile_w = rem % tiles_w; rem /= tiles_w;
+  const int tile_h = rem % tiles_h; const int tile_d = rem / tiles_h;
+  o.od0 = tile_d * 4; o.oh0 = tile_h * 4; o.ow0 = tile_w * 16;
+  return o;
+}
 
 // LDS row pitches (in voxels) that make the transposed fragment reads bank-conflict free.  One ds_read_b64_tr_b16 half-wave
 // meets two image rows (lane bit kq & 1) x four block rows (bq) x four 8-byte columns (bp); the two image rows must start
@@ -62,9 +87,9 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned short* p0, const unsign
 // unpadded for the three stride-2 layers).  dy image, 2*CGW bytes per voxel, 16 voxels per row: CGW = 16 -> pitch 20; CGW = 32:
 // the four block rows already span the bank period at a 64-B stride, so every odd row adds a 32-B skew instead (pitch stays 16:
 // the layer set with 32 output channels keeps two workgroups per CU, which a wider pitch loses); CGW = 64: left as is.
-__host__ __device__ inline int wg_x_pitch(int IW, int is) { if (is != 1) return IW; int p = IW; while ((p & 7) != 4) ++p; return p; }
-__host__ __device__ inline int wg_dy_pitch(int CGW) { return CGW == 16 ? 20 : 16; }
-__host__ __device__ inline int wg_dy_skew(int CGW) { return CGW == 32 ? 16 : 0; }            // bf16 elements added to odd rows
+__host__ __device__ constexpr int wg_x_pitch(int IW, int is) { if (is != 1) return IW; int p = IW; while ((p & 7) != 4) ++p; return p; }
+__host__ __device__ constexpr int wg_dy_pitch(int CGW) { return CGW == 16 ? 20 : 16; }
+__host__ __device__ constexpr int wg_dy_skew(int CGW) { return CGW == 32 ? 16 : 0; }            // bf16 elements added to odd rows
 
 template <int TPW, int NTW, bool TAPSPLIT, bool X3>
 __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgArgsB a) {
@@ -431,15 +456,39 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgArgsB a) {
 //     7 accumulators in registers across ALL tiles of the workgroup: no per-tile epilogue at all;
 //   * raw s_barrier (lgkmcnt only) hands the buffers over; one slab per workgroup at the end (reduced by cwf_wgrad_reduce).
 // ---------------------------------------------------------------------------------------------------
-#ifndef CWF_W16_DEPTH
-#define CWF_W16_DEPTH 7
-#endif
-#ifndef CWF_WS1_DEPTH
-#define CWF_WS1_DEPTH 5
-#endif
+constexpr int W16_DEPTH = 7, WS1_DEPTH = 5;             // LDS-read lookahead of the MFMA waves in tap steps (wgrad16_mfma, wgrad_s1_mfma)
+static_assert(WS1_DEPTH < 8 && W16_DEPTH < 8, "the dy fragment of K-step ks+2 reuses the registers of K-step ks");
+
+// x image of the persistent 3x3x3 stride-1 kernels: the 6 x 6 x 18 halo of a 4 x 4 x 16 tile x one 16-channel chunk, voxel-major
+// [row][voxel][16 ch] bf16 with rows PADDED to 20 voxels (640 B = 40 granules of 16 B): the two M-tile rows that the lanes of one
+// half-wave read in a transposed fragment then start 128 B apart modulo the 256-B bank period, so the ds_read_b64_tr_b16 are
+// conflict-free (unpadded: 2-way conflicts, SQ_LDS_BANK_CONFLICT ~ 2k cycles per tile).  The LDS-DMA kernels fill it in pieces of
+// 1 KiB (64 lanes x one granule), so there it takes whole pieces.
+struct WgXImage {
+  static constexpr int XW = 20;                                          // row pitch in voxels (18 + 2 pad)
+  static constexpr int XI = 36 * XW * 16;                                // bf16 elements
+  static constexpr int XP = (XI * 2 + 1023) / 1024;                      // DMA pieces: 1440 granules -> 23
+};
+static_assert(WgXImage::XW == wg_x_pitch(18, 1), "x pitch");
+
+// LDS layout of the wgrad16 pair, one definition for kernels and launchers.  A buffer is xh [xl] dh [dl]; the dy image is 4 x 4 rows of
+// 16 voxels x 16 channels, padded to 20 voxels like the x image.  DMA = false: two buffers written by converting loader waves
+// (wgrad16_kernel<X3>); DMA = true: a four-buffer ring filled by LDS-DMA (wgrad16d_kernel).  Offsets in bytes.
+template <bool X3_, bool DMA> struct W16Lds : WgXImage {
+  static constexpr bool X3 = X3_;
+  static constexpr int DW = 20;                                          // dy row pitch in voxels (16 + 4 pad)
+  static constexpr int DI = 16 * DW * 16;                                // bf16 elements of one dy image
+  static constexpr int DPC = DI * 2 / 1024;                              // its DMA pieces: 16 rows x 40 granules -> 10
+  static constexpr unsigned XLO = DMA ? XP * 1024u : XI * 2u;            // x lo image past the hi image = bytes an x image takes
+  static constexpr unsigned DY = XLO * (X3 ? 2 : 1);                     // dy hi image
+  static constexpr unsigned DLO = DI * 2u;                               // dy lo image past the hi image
+  static constexpr unsigned BUFB = DY + DLO * (X3 ? 2 : 1);              // buffer pitch (DMA: 33,792 B)
+  static constexpr int NBUF = DMA ? 4 : 2;
+  static constexpr size_t BYTES = (size_t)NBUF * BUFB;                   // dynamic LDS of a launch
+  static_assert(DW == wg_dy_pitch(16) && wg_dy_skew(16) == 0 && DI * 2 % 1024 == 0 && BUFB % 16 == 0 && !(X3 && DMA), "wgrad16 layout");
+};
+
 #define W16_NVOX 648
-#define W16_XW 20                                       // LDS row pitch of the x image in voxels (18 + 2 pad), see below
-#define W16_DW 20                                       // LDS row pitch of the dy image in voxels (16 + 4 pad)
 #define W16_LW 6                                        // loader waves (MFMA waves: 4) -> 640-thread workgroups
 #define W16_VPP (W16_LW * 16)                           // voxels staged per pass (4 threads per voxel)
 #define W16_XS ((W16_NVOX + W16_VPP - 1) / W16_VPP)     // 7 x staging slots per loader thread
@@ -457,16 +506,101 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned&
   lo = pk_bf16(a - ha, b - hb);
 }
 
+// MFMA waves (0-3) of the wgrad16 pair.  L: the pair's LDS layout (operand form, image offsets, buffer pitch and count);
+// out: the workgroup's slab.
+template <class L>
+__device__ __forceinline__ void wgrad16_mfma(unsigned lds_base, int wave, int lane, int niter, float4* out) {
+  constexpr bool X3 = L::X3;
+  constexpr int XW = L::XW, DW = L::DW;
+  const int kq = lane >> 4;
+  const int bq = (lane & 15) >> 2, bp = lane & 3;
+  f32x4 acc[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const bf16x8 ones = ones_frag();
+  // K = 32 voxels per MFMA = M-tile rows (2ks, 2ks+1) x 16 voxels.  Lane group kq reads row 2ks + (kq & 1), voxels
+  // 8 (kq >> 1) + [0, 8): the two rows met inside one half-wave are 640 B apart (see the padding note at WgXImage).
+  // Addresses are integers (LDS byte addresses): per-tap bases in registers, everything else in the ds_read immediate, so
+  // the fully unrolled loop has no address arithmetic (same vector-issue argument as conv16_kernel).
+  const unsigned lane_x = lds_base + (((kq & 1) * XW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;
+  unsigned xa[7];                                      // x hi image: lane part + tap offset (+ buffer)
+  unsigned da = lds_base + L::DY + (((kq & 1) * DW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;   // dy hi image
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const int t = wave + 4 * i;
+    xa[i] = lane_x + (t < 27 ? (((t / 9) * 6 + (t / 3) % 3) * XW + t % 3) * 32 : 0);
+  }
+  // Two straight-line copies of the whole tile loop (wave 3's last slot is the bias row).  A tile is 8 K-steps x 7 taps =
+  // 56 "tap steps" of 3 MFMAs (48 cycles); the 4 transposed reads of tap step f+2 are issued before the MFMAs of step f
+  // (explicit register double-buffering, pinned with sched_barrier: left alone, the compiler issues each read right
+  // before its MFMA and every MFMA waits out the LDS latency).
+  auto tiles = [&](auto BIAS_) {
+    constexpr bool BIAS = decltype(BIAS_)::value;
+    // LDS-read lookahead in tap steps.  Split operands: a step is 3 MFMAs = 48 cycles, two steps cover the transposed-read latency.
+    // Single-bf16 operands (what the bench runs): ONE MFMA = 16 cycles per step -- at two steps every MFMA waited out most of an
+    // LDS round trip (5.6k cycles per tile against 0.9k of MFMAs); seven steps ahead (the most the two-slot dy-fragment ring allows), in registers the lo fragments do not need.
+    constexpr int DEPTH = X3 ? 2 : W16_DEPTH;
+    for (int it = 0; it < niter; ++it) {
+      asm volatile("s_barrier" ::: "memory");          // buffer it & (NBUF - 1) is complete
+      bf16x8 ah[DEPTH + 1], al[DEPTH + 1], bh[2], bl[2];
+      auto issue = [&](int f) {                        // f = ks * 7 + i, compile-time after unrolling
+        const int ks = f / 7, i = f % 7;
+        if (i == 0) {
+          const unsigned od_ = (2 * ks * DW) * 32;
+          bh[ks & 1] = tr_frag_at(da + od_, 4 * 32);
+          if (X3) bl[ks & 1] = tr_frag_at(da + od_ + L::DLO, 4 * 32);
+        }
+        if (!(BIAS && i == 6)) {
+          const unsigned ox = (((ks >> 1) * 6 + ((2 * ks) & 3)) * XW) * 32;
+          ah[f % (DEPTH + 1)] = tr_frag_at(xa[i] + ox, 4 * 32);
+          if (X3) al[f % (DEPTH + 1)] = tr_frag_at(xa[i] + ox + L::XLO, 4 * 32);
+        }
+      };
+#pragma unroll
+      for (int f = 0; f < DEPTH; ++f) issue(f);
+#pragma unroll
+      for (int f = 0; f < 56; ++f) {
+        if (f + DEPTH < 56) issue(f + DEPTH);
+        __builtin_amdgcn_sched_barrier(0);
+        const int ks = f / 7, i = f % 7;
+        const bf16x8 bhf = bh[ks & 1];
+        if (BIAS && i == 6) {                          // tap slot 27 = bias row (ones . dy)
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bhf, acc[i], 0, 0, 0);
+          if (X3) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bl[ks & 1], acc[i], 0, 0, 0);
+        } else {
+          const bf16x8 ahf = ah[f % (DEPTH + 1)];
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahf, bhf, acc[i], 0, 0, 0);
+          if (X3) {
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahf, bl[ks & 1], acc[i], 0, 0, 0);
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[f % (DEPTH + 1)], bhf, acc[i], 0, 0, 0);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      {                                                // the next buffer of the ring is read next
+        constexpr int LAST = L::NBUF - 1;
+        const unsigned dlt = ((it & LAST) == LAST) ? (unsigned)(-(int)(LAST * L::BUFB)) : L::BUFB;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) xa[i] += dlt;
+        da += dlt;
+      }
+    }
+  };
+  if (wave == 3) tiles(std::true_type{}); else tiles(std::false_type{});
+  // one slab per workgroup: [tap slot 0..27][lane][4]   (chunk 0, group 0, CG = 1)
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const int t = wave + 4 * i;
+    if (t > 27) continue;
+    out[(int64_t)t * 64 + lane] = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+  }
+}
+
 template <bool X3>
 __global__ __launch_bounds__(256 + 64 * W16_LW) void wgrad16_kernel(const WgArgsB a, int total_tiles) {
+  using L = W16Lds<X3, false>;
   extern __shared__ float4 lds4[];
   const ConvGeom& g = a.g;
-  // LDS images are voxel-major [row][voxel][16 ch] bf16 with rows PADDED to 20 voxels (640 B): the two M-tile rows that the
-  // lanes of one half-wave read in a transposed fragment then start 128 B apart modulo the 256-B bank period, so the
-  // ds_read_b64_tr_b16 are conflict-free (unpadded: 2-way conflicts, SQ_LDS_BANK_CONFLICT ~ 2k cycles per tile).
-  constexpr int XI = 36 * W16_XW * 16;                 // bf16 elements of one x image  (6 x 6 rows)
-  constexpr int DI = 16 * W16_DW * 16;                 // bf16 elements of one dy image (4 x 4 rows)
-  constexpr int BUF = (XI + DI) * (X3 ? 2 : 1);        // per buffer: xh [xl] dh [dl]
   unsigned short* lds = reinterpret_cast<unsigned short*>(lds4);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the role branch below is provably wave-uniform
@@ -477,98 +611,8 @@ __global__ __launch_bounds__(256 + 64 * W16_LW) void wgrad16_kernel(const WgArgs
   const int niter = first < total_tiles ? (total_tiles - first + G - 1) / G : 0;   // empty workgroups still write a zero slab
 
   if (wave < 4) {
-    // =============================================================== MFMA waves
-    const int kq = lane >> 4;
-    const int bq = (lane & 15) >> 2, bp = lane & 3;
-    f32x4 acc[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 ones_s = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_s);
-    // K = 32 voxels per MFMA = M-tile rows (2ks, 2ks+1) x 16 voxels.  Lane group kq reads row 2ks + (kq & 1), voxels
-    // 8 (kq >> 1) + [0, 8): the two rows met inside one half-wave are 640 B apart (see the padding note above).
-    // Addresses are integers (LDS byte addresses): per-tap bases in registers, everything else in the ds_read immediate, so
-    // the fully unrolled loop has no address arithmetic (same vector-issue argument as conv16_kernel).
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds4;
-    const unsigned lane_x = lds_base + (((kq & 1) * W16_XW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;
-    unsigned xa[7];                                      // x hi image: lane part + tap offset (+ buffer parity)
-    unsigned da = lds_base + XI * 2 * (X3 ? 2 : 1) + (((kq & 1) * W16_DW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;   // dy hi image
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int t = wave + 4 * i;
-      xa[i] = lane_x + (t < 27 ? (((t / 9) * 6 + (t / 3) % 3) * W16_XW + t % 3) * 32 : 0);
-    }
-    auto trf = [&](unsigned addr) {                      // two transposed reads (block rows +0, +4) -> one 8-element K fragment
-      const s16x4 u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)addr);
-      const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(addr + 4 * 32));
-      const s16x8 w = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-      return __builtin_bit_cast(bf16x8, w);
-    };
-    // Two straight-line copies of the whole tile loop (wave 3's last slot is the bias row).  A tile is 8 K-steps x 7 taps =
-    // 56 "tap steps" of 3 MFMAs (48 cycles); the 4 transposed reads of tap step f+2 are issued before the MFMAs of step f
-    // (explicit register double-buffering, pinned with sched_barrier: left alone, the compiler issues each read right
-    // before its MFMA and every MFMA waits out the LDS latency).
-    auto tiles = [&](auto BIAS_) {
-      constexpr bool BIAS = decltype(BIAS_)::value;
-      // LDS-read lookahead in tap steps.  Split operands: a step is 3 MFMAs = 48 cycles, two steps cover the transposed-read latency.
-      // Single-bf16 operands (what the bench runs): ONE MFMA = 16 cycles per step -- at two steps every MFMA waited out most of an
-      // LDS round trip (5.6k cycles per tile against 0.9k of MFMAs); seven steps ahead (the most the two-slot dy-fragment ring allows), in registers the lo fragments do not need.
-      constexpr int DEPTH = X3 ? 2 : CWF_W16_DEPTH;
-      for (int it = 0; it < niter; ++it) {
-        asm volatile("s_barrier" ::: "memory");          // buffer it&1 is complete
-        bf16x8 ah[DEPTH + 1], al[DEPTH + 1], bh[2], bl[2];
-        auto issue = [&](int f) {                        // f = ks * 7 + i, compile-time after unrolling
-          const int ks = f / 7, i = f % 7;
-          if (i == 0) {
-            const unsigned od_ = (2 * ks * W16_DW) * 32;
-            bh[ks & 1] = trf(da + od_);
-            if (X3) bl[ks & 1] = trf(da + od_ + DI * 2);
-          }
-          if (!(BIAS && i == 6)) {
-            const unsigned ox = (((ks >> 1) * 6 + ((2 * ks) & 3)) * W16_XW) * 32;
-            ah[f % (DEPTH + 1)] = trf(xa[i] + ox);
-            if (X3) al[f % (DEPTH + 1)] = trf(xa[i] + ox + XI * 2);
-          }
-        };
-#pragma unroll
-        for (int f = 0; f < DEPTH; ++f) issue(f);
-#pragma unroll
-        for (int f = 0; f < 56; ++f) {
-          if (f + DEPTH < 56) issue(f + DEPTH);
-          __builtin_amdgcn_sched_barrier(0);
-          const int ks = f / 7, i = f % 7;
-          const bf16x8 bhf = bh[ks & 1];
-          if (BIAS && i == 6) {                          // tap slot 27 = bias row (ones . dy)
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bhf, acc[i], 0, 0, 0);
-            if (X3) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bl[ks & 1], acc[i], 0, 0, 0);
-          } else {
-            const bf16x8 ahf = ah[f % (DEPTH + 1)];
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahf, bhf, acc[i], 0, 0, 0);
-            if (X3) {
-              acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahf, bl[ks & 1], acc[i], 0, 0, 0);
-              acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[f % (DEPTH + 1)], bhf, acc[i], 0, 0, 0);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        {                                                // the other buffer is read next
-          const unsigned dlt = (it & 1) ? (unsigned)(-(BUF * 2)) : (unsigned)(BUF * 2);
-#pragma unroll
-          for (int i = 0; i < 7; ++i) xa[i] += dlt;
-          da += dlt;
-        }
-      }
-    };
-    if (wave == 3) tiles(std::true_type{}); else tiles(std::false_type{});
-    // one slab per workgroup: [tap slot 0..27][lane][4]   (chunk 0, group 0, CG = 1)
-    float4* out = reinterpret_cast<float4*>(a.partial + (int64_t)blockIdx.x * a.slab_floats);
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int t = wave + 4 * i;
-      if (t > 27) continue;
-      out[(int64_t)t * 64 + lane] = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
-    }
+    wgrad16_mfma<L>(lds_base, wave, lane, niter, reinterpret_cast<float4*>(a.partial + (int64_t)blockIdx.x * a.slab_floats));
   } else {
     // =============================================================== loader waves
     const int lt = tid - 256;
@@ -594,19 +638,17 @@ __global__ __launch_bounds__(256 + 64 * W16_LW) void wgrad16_kernel(const WgArgs
     const bool dlast_ok = (lt >> 2) + W16_VPP * (W16_DS - 1) < 256;
     int xo[W16_XS], dofs[W16_DS];                        // LDS element offsets of this thread's staging slots (padded rows)
 #pragma unroll
-    for (int i = 0; i < W16_XS; ++i) { const int v = (lt >> 2) + W16_VPP * i; xo[i] = ((v / 18) * W16_XW + v % 18) * 16 + q * 4; }
+    for (int i = 0; i < W16_XS; ++i) { const int v = (lt >> 2) + W16_VPP * i; xo[i] = ((v / 18) * L::XW + v % 18) * 16 + q * 4; }
 #pragma unroll
-    for (int i = 0; i < W16_DS; ++i) { const int v = (lt >> 2) + W16_VPP * i; dofs[i] = ((v >> 4) * W16_DW + (v & 15)) * 16 + q * 4; }
+    for (int i = 0; i < W16_DS; ++i) { const int v = (lt >> 2) + W16_VPP * i; dofs[i] = ((v >> 4) * L::DW + (v & 15)) * 16 + q * 4; }
     float4 px[1][W16_XS], pd[1][W16_DS];
     unsigned inbx[1] = {0u}, inbd[1] = {0u};
     __builtin_amdgcn_s_setprio(1);
     struct Org { const float* xb; const float* db; bool interior; int id0, ih0, iw0, od0, oh0, ow0, n; };
     auto origin = [&](int tile) {
       Org o;
-      o.n = tile / tiles_sp; int rem = tile - o.n * tiles_sp;
-      const int tile_w = rem % g.tiles_w; rem /= g.tiles_w;
-      const int tile_h = rem % g.tiles_h; const int tile_d = rem / g.tiles_h;
-      o.od0 = tile_d * 4; o.oh0 = tile_h * 4; o.ow0 = tile_w * 16;
+      const TileOrigin t = tile_origin(tile, tiles_sp, g.tiles_h, g.tiles_w);
+      o.n = t.n; o.od0 = t.od0; o.oh0 = t.oh0; o.ow0 = t.ow0;
       o.id0 = o.od0 - 1; o.ih0 = o.oh0 - 1; o.iw0 = o.ow0 - 1;
       o.xb = a.x + ((((int64_t)o.n * g.Di + o.id0) * g.Hi + o.ih0) * g.Wi + o.iw0) * g.x_ldc;
       o.db = a.dy + ((((int64_t)o.n * g.Do + o.od0) * g.Ho + o.oh0) * g.Wo + o.ow0) * a.dy_ldc;
@@ -660,10 +702,10 @@ __global__ __launch_bounds__(256 + 64 * W16_LW) void wgrad16_kernel(const WgArgs
       }
       float4 dsc = make_float4(1.f, 1.f, 1.f, 1.f);
       if (a.dy_scale) dsc = *reinterpret_cast<const float4*>(a.dy_scale + (int64_t)(tc / tiles_sp) * g.Cout + c);
-      unsigned short* xh = lds + buf * BUF;
-      unsigned short* xl = xh + XI;
-      unsigned short* dh = lds + buf * BUF + XI * (X3 ? 2 : 1);
-      unsigned short* dl = dh + DI;
+      unsigned short* xh = lds + buf * (L::BUFB / 2);
+      unsigned short* xl = xh + L::XLO / 2;
+      unsigned short* dh = xh + L::DY / 2;
+      unsigned short* dl = dh + L::DLO / 2;
       const unsigned mx = inbx[SET], md = inbd[SET];
       const unsigned fullx = last_ok ? ((1u << W16_XS) - 1u) : ((1u << (W16_XS - 1)) - 1u);
       const unsigned fulld = dlast_ok ? ((1u << W16_DS) - 1u) : ((1u << (W16_DS - 1)) - 1u);
@@ -743,164 +785,133 @@ __global__ __launch_bounds__(256 + 64 * W16_LW) void wgrad16_kernel(const WgArgs
 // LDS image = wgrad16's (voxel-major rows padded to 20 voxels = 640 B = 40 granules of 16 B: conflict-free transposed reads); a
 // piece is 64 consecutive granules, per-lane source address; pad granules read the zero page.  MFMA waves: wgrad16's.
 // ---------------------------------------------------------------------------------------------------
-#define W16D_XP 23                                      // DMA pieces of the x image (36 rows x 40 granules = 1440 -> 23 pieces)
-#define W16D_DP 10                                      // DMA pieces of the dy image (16 rows x 40 granules = 640)
-#define W16D_XIB (W16D_XP * 1024)
-#define W16D_BUFB ((W16D_XP + W16D_DP) * 1024)          // 33,792 B per buffer
-#define W16D_NBUF 4
 #define W16D_LW 6                                       // loader waves
+// arguments of wgrad16d_kernel, and what wgrad_s1d_kernel's (Ws1dArgs) share with them
 struct W16dArgs {
   const uint4* xa; const uint4* dy; const uint4* zero; float* partial;
   int N, D, H, W, tiles_d, tiles_h, tiles_w, total_tiles;
   int64_t slab_floats;
 };
 
+// The loader waves of the image kernels: nothing but LDS-DMA.  A piece is 64 consecutive 16-byte granules of LDS filled by one
+// global_load_lds_dwordx4 with a per-lane source address; pad granules and voxels outside the volume read the zero page.  Pieces
+// 0 .. XP-1 are the x image (WgXImage: 36 rows x 40 granules), pieces XP .. XP+DPC-1 the dy image; loader wave lw issues pieces
+// lw, lw + LW, ...: NI of them, a compile-time count that the vmcnt immediates need.  Tile `it` goes to buffer it & 3.
+// What a kernel brings is the policy P:
+//   P::L, P::LW, P::DPC     LDS layout, loader waves, pieces of the dy image
+//   p.a                     the kernel's arguments (W16dArgs)
+//   p.gx, p.gd, p.xg0       16-byte granules per voxel of xa16 / dy16; first granule of the workgroup's 16-channel chunk
+//   p.tile(it)              the workgroup's tile walk
+//   p.dy_piece(m, lane, ..) granule `lane` of dy piece m -> M-tile row (c0, c1), voxel w, granule g of that voxel, valid (no pad)
+//   P::dy_dst(m)            LDS byte offset of dy piece m in its buffer
+typedef __attribute__((address_space(3))) void* lds_vp;
+typedef __attribute__((address_space(1))) const void* glb_vp;
+template <int NI, class P>
+__device__ __forceinline__ void wgrad_dma_run(const P& p, unsigned lds_base, int lw, int lane, int niter) {
+  using L = typename P::L;
+  static_assert(L::NBUF == 4, "three tiles in flight, one being read");
+  constexpr int GPR = 2 * L::XW;                         // granules per x-image row
+  const auto& a = p.a;
+  const int tiles_sp = a.tiles_d * a.tiles_h * a.tiles_w;
+  int off[NI]; unsigned crd[NI];                         // granule offset from the tile's operand origin; (c0, c1, w, valid)
+#pragma unroll
+  for (int k = 0; k < NI; ++k) {
+    const int s = lw + P::LW * k;                        // (wave-uniform)
+    int c0, c1, w, g, gv; bool valid;
+    if (s < L::XP) {
+      const int gi = 64 * s + lane;
+      const int row = gi / GPR, gr = gi % GPR;
+      c0 = row / 6; c1 = row % 6; w = gr >> 1; g = p.xg0 + (gr & 1); gv = p.gx;
+      valid = row < 36 && gr < 36;
+    } else {
+      p.dy_piece(s - L::XP, lane, c0, c1, w, g, valid); gv = p.gd;
+    }
+    off[k] = ((c0 * a.H + c1) * a.W + w) * gv + g;
+    crd[k] = (unsigned)c0 | ((unsigned)c1 << 3) | ((unsigned)w << 6) | (valid ? 1u << 11 : 0u);
+  }
+  auto issue = [&](int it) __attribute__((always_inline)) {
+    const TileOrigin o = tile_origin(p.tile(it), tiles_sp, a.tiles_h, a.tiles_w);
+    const int64_t vd = (((int64_t)o.n * a.D + o.od0) * a.H + o.oh0) * a.W + o.ow0;     // voxel index of the dy tile origin
+    const int64_t vx = vd - ((int64_t)a.H + 1) * a.W - 1;                              // ... of the x halo origin (-1, -1, -1)
+    const unsigned lbuf = lds_base + (unsigned)(it & 3) * L::BUFB;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+      const int s = lw + P::LW * k;
+      const bool isd = s >= L::XP;
+      const int c0 = (int)(crd[k] & 7u), c1 = (int)((crd[k] >> 3) & 7u), w = (int)((crd[k] >> 6) & 31u);
+      const int gd = (isd ? o.od0 : o.od0 - 1) + c0, gh = (isd ? o.oh0 : o.oh0 - 1) + c1, gw = (isd ? o.ow0 : o.ow0 - 1) + w;
+      const bool ok = (crd[k] >> 11) != 0u && (unsigned)gd < (unsigned)a.D && (unsigned)gh < (unsigned)a.H && (unsigned)gw < (unsigned)a.W;
+      const uint4* src = (isd ? a.dy + vd * p.gd : a.xa + vx * p.gx) + off[k];
+      src = ok ? src : a.zero;
+      const unsigned dst = isd ? P::dy_dst(s - L::XP) : (unsigned)s * 1024u;
+      __builtin_amdgcn_global_load_lds((glb_vp)src, (lds_vp)(uintptr_t)(lbuf + dst), 16, 0, 0);
+    }
+  };
+  if (niter > 0) issue(0);
+  if (niter > 1) issue(1);
+  if (niter > 2) issue(2);
+  for (int it = 0; it < niter; ++it) {
+    // tile `it` has landed once all but the pieces of the (at most two) younger tiles in flight are done
+    if (it + 2 < niter) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NI) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_barrier" ::: "memory");
+    if (it + 3 < niter) issue(it + 3);                   // into the buffer the MFMA waves finished before this barrier
+  }
+}
+template <class P>
+__device__ __forceinline__ void wgrad_dma_loader(const P& p, unsigned lds_base, int lw, int lane, int niter) {
+  constexpr int NP = P::L::XP + P::DPC;
+  if (lw < NP % P::LW) wgrad_dma_run<NP / P::LW + 1>(p, lds_base, lw, lane, niter);
+  else wgrad_dma_run<NP / P::LW>(p, lds_base, lw, lane, niter);
+}
+
+struct W16dDma {
+  using L = W16Lds<false, true>;
+  static constexpr int LW = W16D_LW, DPC = L::DPC;
+  static constexpr int gx = 2, gd = 2, xg0 = 0;          // 16 channels: two granules per voxel, one chunk
+  const W16dArgs& a; int first, G;
+  __device__ int tile(int it) const { return first + it * G; }
+  __device__ void dy_piece(int m, int lane, int& c0, int& c1, int& w, int& g, bool& valid) const {   // rows of 40 granules, like x
+    const int gi = 64 * m + lane, row = gi / 40, gr = gi % 40;
+    c0 = row >> 2; c1 = row & 3; w = gr >> 1; g = gr & 1; valid = gr < 32;
+  }
+  static __device__ constexpr unsigned dy_dst(int m) { return L::DY + (unsigned)m * 1024u; }
+};
+
 __global__ __launch_bounds__(256 + 64 * W16D_LW) void wgrad16d_kernel(const W16dArgs a) {
   extern __shared__ float4 lds4[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tiles_sp = a.tiles_d * a.tiles_h * a.tiles_w;
   const int G = (int)gridDim.x, per = G >> 3;
   const int first = (blockIdx.x & 7) * per + (blockIdx.x >> 3);      // tile(it) = first + it * G   (XCD-aware, see wgrad16_kernel)
   const int niter = first < a.total_tiles ? (a.total_tiles - first + G - 1) / G : 0;
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds4;
-
-  if (wave < 4) {
-    // =============================================================== MFMA waves (wgrad16_kernel<false>, four buffers)
-    const int kq = lane >> 4;
-    const int bq = (lane & 15) >> 2, bp = lane & 3;
-    f32x4 acc[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 ones_s = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_s);
-    const unsigned lane_x = lds_base + (((kq & 1) * W16_XW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;
-    unsigned xa[7];
-    unsigned da = lds_base + W16D_XIB + (((kq & 1) * W16_DW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int t = wave + 4 * i;
-      xa[i] = lane_x + (t < 27 ? (((t / 9) * 6 + (t / 3) % 3) * W16_XW + t % 3) * 32 : 0);
-    }
-    auto trf = [&](unsigned addr) {
-      const s16x4 u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)addr);
-      const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(addr + 4 * 32));
-      const s16x8 w = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-      return __builtin_bit_cast(bf16x8, w);
-    };
-    auto tiles = [&](auto BIAS_) {
-      constexpr bool BIAS = decltype(BIAS_)::value;
-      constexpr int DEPTH = CWF_W16_DEPTH;
-      for (int it = 0; it < niter; ++it) {
-        asm volatile("s_barrier" ::: "memory");          // buffer it & 3 has landed
-        bf16x8 ah[DEPTH + 1], bh[2];
-        auto issue = [&](int f) {
-          const int ks = f / 7, i = f % 7;
-          if (i == 0) bh[ks & 1] = trf(da + (2 * ks * W16_DW) * 32);
-          if (!(BIAS && i == 6)) ah[f % (DEPTH + 1)] = trf(xa[i] + (((ks >> 1) * 6 + ((2 * ks) & 3)) * W16_XW) * 32);
-        };
-#pragma unroll
-        for (int f = 0; f < DEPTH; ++f) issue(f);
-#pragma unroll
-        for (int f = 0; f < 56; ++f) {
-          if (f + DEPTH < 56) issue(f + DEPTH);
-          __builtin_amdgcn_sched_barrier(0);
-          const int ks = f / 7, i = f % 7;
-          const bf16x8 bhf = bh[ks & 1];
-          if (BIAS && i == 6) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bhf, acc[i], 0, 0, 0);
-          else acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[f % (DEPTH + 1)], bhf, acc[i], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        {
-          const unsigned dlt = ((it & 3) == 3) ? (unsigned)(-(3 * W16D_BUFB)) : (unsigned)W16D_BUFB;
-#pragma unroll
-          for (int i = 0; i < 7; ++i) xa[i] += dlt;
-          da += dlt;
-        }
-      }
-    };
-    if (wave == 3) tiles(std::true_type{}); else tiles(std::false_type{});
-    float4* out = reinterpret_cast<float4*>(a.partial + (int64_t)blockIdx.x * a.slab_floats);
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int t = wave + 4 * i;
-      if (t > 27) continue;
-      out[(int64_t)t * 64 + lane] = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
-    }
-  } else {
-    // =============================================================== loader waves: DMA only
-    const int lw = wave - 4;                               // pieces lw, lw + 6, ... of the 33
-    typedef __attribute__((address_space(3))) void* lds_vp;
-    typedef __attribute__((address_space(1))) const void* glb_vp;
-    auto run = [&](auto NI_) __attribute__((always_inline)) {
-      constexpr int NI = decltype(NI_)::value;
-      int off[NI]; unsigned crd[NI];                       // granule offset from the tile's operand origin; (c0, c1, w, valid)
-#pragma unroll
-      for (int k = 0; k < NI; ++k) {
-        const int s = lw + W16D_LW * k;
-        const bool isd = s >= W16D_XP;
-        const int gi = 64 * (isd ? s - W16D_XP : s) + lane;
-        const int row = gi / 40, gr = gi % 40, w = gr >> 1, half = gr & 1;
-        const int c0 = isd ? (row >> 2) : row / 6, c1 = isd ? (row & 3) : row % 6;
-        const bool valid = isd ? gr < 32 : (row < 36 && gr < 36);
-        off[k] = ((c0 * a.H + c1) * a.W + w) * 2 + half;
-        crd[k] = (unsigned)c0 | ((unsigned)c1 << 3) | ((unsigned)w << 6) | (valid ? 1u << 11 : 0u);
-      }
-      auto issue = [&](int it) __attribute__((always_inline)) {
-        const int tile = first + it * G;
-        const int n = tile / tiles_sp; int rem = tile - n * tiles_sp;
-        const int tile_w = rem % a.tiles_w; rem /= a.tiles_w;
-        const int tile_h = rem % a.tiles_h; const int tile_d = rem / a.tiles_h;
-        const int od0 = tile_d * 4, oh0 = tile_h * 4, ow0 = tile_w * 16;
-        const int64_t vd = (((int64_t)n * a.D + od0) * a.H + oh0) * a.W + ow0;       // voxel index of the dy tile origin
-        const int64_t vx = vd - ((int64_t)a.H + 1) * a.W - 1;                        // ... of the x halo origin (-1, -1, -1)
-        const unsigned lbuf = lds_base + (unsigned)(it & 3) * W16D_BUFB;
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-          const int s = lw + W16D_LW * k;                 // (wave-uniform)
-          const bool isd = s >= W16D_XP;
-          const int c0 = (int)(crd[k] & 7u), c1 = (int)((crd[k] >> 3) & 7u), w = (int)((crd[k] >> 6) & 31u);
-          const int gd = (isd ? od0 : od0 - 1) + c0, gh = (isd ? oh0 : oh0 - 1) + c1, gw = (isd ? ow0 : ow0 - 1) + w;
-          const bool ok = (crd[k] >> 11) != 0u && (unsigned)gd < (unsigned)a.D && (unsigned)gh < (unsigned)a.H && (unsigned)gw < (unsigned)a.W;
-          const uint4* src = (isd ? a.dy + vd * 2 : a.xa + vx * 2) + off[k];
-          src = ok ? src : a.zero;
-          __builtin_amdgcn_global_load_lds((glb_vp)src, (lds_vp)(uintptr_t)(lbuf + (unsigned)s * 1024u), 16, 0, 0);
-        }
-      };
-      if (niter > 0) issue(0);
-      if (niter > 1) issue(1);
-      if (niter > 2) issue(2);
-      for (int it = 0; it < niter; ++it) {
-        // tile `it` has landed once all but the pieces of the (at most two) younger tiles in flight are done
-        if (it + 2 < niter) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NI) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_barrier" ::: "memory");
-        if (it + 3 < niter) issue(it + 3);               // into the buffer the MFMA waves finished before this barrier
-      }
-    };
-    if (lw < (W16D_XP + W16D_DP) % W16D_LW) run(std::integral_constant<int, (W16D_XP + W16D_DP) / W16D_LW + 1>{});
-    else run(std::integral_constant<int, (W16D_XP + W16D_DP) / W16D_LW>{});
-  }
+  if (wave < 4)
+    wgrad16_mfma<W16dDma::L>(lds_base, wave, lane, niter, reinterpret_cast<float4*>(a.partial + (int64_t)blockIdx.x * a.slab_floats));
+  else
+    wgrad_dma_loader(W16dDma{a, first, G}, lds_base, wave - 4, lane, niter);
 }
 
-static int wgrad16_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
-  const void* xa16 = d.xa16; const void* dy16 = d.dy16; const void* zero16 = d.zero16; float* partial = d.partial;
-  const int N = d.N, D = d.Di, H = d.Hi, W = d.Wi;
-  if (!xa16 || !dy16 || !zero16 || !partial || N <= 0 || D <= 0 || H <= 0 || W <= 0) return CWF_E_BADARG;
-  if (((uintptr_t)xa16 & 15) || ((uintptr_t)dy16 & 15) || ((uintptr_t)zero16 & 15) || ((uintptr_t)partial & 15)) return CWF_E_ALIGN;
-  if ((int64_t)N * D * H * W >= (1ll << 30)) return CWF_E_TOOLARGE;
+// what both image launchers ask of their arguments; fills the fields the two kernels share
+static int wgrad_image_args(const cwf_wgrad_args& d, W16dArgs& a) {
+  if (!d.xa16 || !d.dy16 || !d.zero16 || !d.partial || d.N <= 0 || d.Di <= 0 || d.Hi <= 0 || d.Wi <= 0) return CWF_E_BADARG;
+  if (((uintptr_t)d.xa16 & 15) || ((uintptr_t)d.dy16 & 15) || ((uintptr_t)d.zero16 & 15) || ((uintptr_t)d.partial & 15)) return CWF_E_ALIGN;
+  a.xa = (const uint4*)d.xa16; a.dy = (const uint4*)d.dy16; a.zero = (const uint4*)d.zero16; a.partial = d.partial;
+  a.N = d.N; a.D = d.Di; a.H = d.Hi; a.W = d.Wi;
+  a.tiles_d = cdiv(a.D, 4); a.tiles_h = cdiv(a.H, 4); a.tiles_w = cdiv(a.W, 16);
+  a.total_tiles = a.N * a.tiles_d * a.tiles_h * a.tiles_w;
+  return 0;
+}
+
+static int wgrad16d_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
   W16dArgs a;
-  a.xa = (const uint4*)xa16; a.dy = (const uint4*)dy16; a.zero = (const uint4*)zero16; a.partial = partial;
-  a.N = N; a.D = D; a.H = H; a.W = W;
-  a.tiles_d = cdiv(D, 4); a.tiles_h = cdiv(H, 4); a.tiles_w = cdiv(W, 16);
-  a.total_tiles = N * a.tiles_d * a.tiles_h * a.tiles_w;
+  if (const int rc = wgrad_image_args(d, a)) return rc;
+  if ((int64_t)a.N * a.D * a.H * a.W >= (1ll << 30)) return CWF_E_TOOLARGE;
   a.slab_floats = 28 * 256;                               // = cwf_wgrad_slab_floats(CWF_CONV3_S1, 16, 16)
   int grid = SIDE_WGS; while (grid > 8 && grid > a.total_tiles) grid -= 8;      // multiple of 8 (XCD-aware tile map)
-  if (grid > cwf_wgrad_nsplit(CWF_CONV3_S1, N, D, H, W, 16, 16)) return CWF_E_BADARG;    // (the caller's slab buffer is sized by it)
-  const size_t lds = (size_t)W16D_NBUF * W16D_BUFB;
+  if (grid > cwf_wgrad_nsplit(CWF_CONV3_S1, a.N, a.D, a.H, a.W, 16, 16)) return CWF_E_BADARG;    // (the caller's slab buffer is sized by it)
   CWF_MAX_LDS_ONCE((&wgrad16d_kernel));
-  hipLaunchKernelGGL(wgrad16d_kernel, dim3(grid), dim3(256 + 64 * W16D_LW), lds, st, a);
+  hipLaunchKernelGGL(wgrad16d_kernel, dim3(grid), dim3(256 + 64 * W16D_LW), W16dDma::L::BYTES, st, a);
   CWF_LAUNCH_CHECK();
   if (nsplit_used) *nsplit_used = grid;
   return 0;
@@ -927,15 +938,91 @@ static int wgrad16_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t
 // both chunks of a tile against one dy fetch, a sliding halo.
 // ---------------------------------------------------------------------------------------------------
 #define WS1_LW 8                                        // loader waves (MFMA waves: 4) -> 768-thread workgroups
+// LDS layout of the wgrad_s1 pair, one definition for kernels and launchers.  A buffer is x image | dy image.  The dy image is 16
+// M-tile rows of 16 voxels x CGW channels in the generic kernel's form (wg_dy_pitch / wg_dy_skew): row m starts at element
+// m * DP * CGW + ((m + 1) >> 1) * DSK.  DMA = false: two buffers written by converting loader waves (wgrad_s1_kernel<NTW>);
+// DMA = true: a four-buffer ring filled by LDS-DMA (wgrad_s1d_kernel), where one row of 32 channels is one piece.  Offsets in bytes.
+template <int NTW_, bool DMA> struct Ws1Lds : WgXImage {
+  static constexpr int NTW = NTW_, CGW = NTW * 16;
+  static constexpr int DP = wg_dy_pitch(CGW), DSK = wg_dy_skew(CGW);
+  static constexpr int DSLOTS = DMA ? 8 : 16 / 2 + 1;                    // skews allotted: row 15 carries 8, the generic form allots MT / 2 + 1
+  static constexpr unsigned DIB = (16 * DP * CGW + DSLOTS * DSK) * 2u;   // bytes of the dy image
+  static constexpr unsigned DY = DMA ? XP * 1024u : XI * 2u;             // dy image = bytes the x image takes
+  static constexpr unsigned BUFB = DY + DIB;                             // buffer pitch (DMA: 40,192 B)
+  static constexpr int NBUF = DMA ? 4 : 2;
+  static constexpr size_t BYTES = (size_t)NBUF * BUFB;                   // dynamic LDS of a launch
+  static_assert((NTW == 1 || NTW == 2) && BUFB % 16 == 0 && (!DMA || DP * CGW * 2 == 1024), "wgrad_s1 layout");
+};
+
+// MFMA waves (0-3) of the wgrad_s1 pair.  L: the pair's LDS layout (NTW, dy pitch and skew, image offset, buffer pitch and count);
+// out: the (chunk, group) block of the workgroup's slab, [tap slot 0..27][tile j][lane][4] (layout of wgrad_bf16_kernel).
+template <class L>
+__device__ __forceinline__ void wgrad_s1_mfma(unsigned lds_base, int wave, int lane, int niter, float4* out) {
+  constexpr int NTW = L::NTW, CGW = L::CGW, XW = L::XW, DP = L::DP, DSK = L::DSK;
+  const int kq = lane >> 4, bq = (lane & 15) >> 2, bp = lane & 3;
+  f32x4 acc[7][NTW];
+#pragma unroll
+  for (int i = 0; i < 7; ++i)
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const bf16x8 ones = ones_frag();
+  const bool bias_wave = wave == 3;
+  const unsigned lane_x = lds_base + (((kq & 1) * XW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;
+  unsigned xa0[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const int t = wave + 4 * i;
+    xa0[i] = lane_x + (t < 27 ? (((t / 9) * 6 + (t / 3) % 3) * XW + t % 3) * 32 : 0);
+  }
+  const unsigned da0 = lds_base + L::DY + (((kq & 1) * DP + (kq >> 1) * 8 + bq) * CGW + (kq & 1) * DSK + bp * 4) * 2;
+  for (int it = 0; it < niter; ++it) {
+    asm volatile("s_barrier" ::: "memory");              // buffer it & (NBUF - 1) is complete
+    const unsigned bo = (unsigned)(it & (L::NBUF - 1)) * L::BUFB;
+    unsigned xa[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) xa[i] = xa0[i] + bo;
+    const unsigned da = da0 + bo;
+    constexpr int DEPTH = WS1_DEPTH;                   // tap steps of LDS-read lookahead (a step is NTW MFMAs = 16-32 cycles)
+    bf16x8 ah[DEPTH + 1], bh[2][NTW];
+    auto issue = [&](int f) __attribute__((always_inline)) {   // f = ks * 7 + i, compile-time after unrolling
+      const int ks = f / 7, i = f % 7;
+      if (i == 0) {
+        const unsigned od_ = (2 * ks * DP * CGW + ks * DSK) * 2;
+#pragma unroll
+        for (int j = 0; j < NTW; ++j) bh[ks & 1][j] = tr_frag_at(da + od_ + j * 32, 4 * CGW * 2);
+      }
+      const unsigned ox = (((ks >> 1) * 6 + ((2 * ks) & 3)) * XW) * 32;
+      ah[f % (DEPTH + 1)] = tr_frag_at(xa[i] + ox, 4 * 32);
+    };
+#pragma unroll
+    for (int f = 0; f < DEPTH; ++f) issue(f);
+#pragma unroll
+    for (int f = 0; f < 56; ++f) {
+      if (f + DEPTH < 56) issue(f + DEPTH);
+      __builtin_amdgcn_sched_barrier(0);
+      const int ks = f / 7, i = f % 7;
+      bf16x8 ahf = ah[f % (DEPTH + 1)];
+      if (i == 6) ahf = bias_wave ? ones : ahf;            // wave 3: tap slot 27 = bias row (ones . dy); wave-uniform select
+#pragma unroll
+      for (int j = 0; j < NTW; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahf, bh[ks & 1][j], acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const int t = wave + 4 * i;
+    if (t > 27) continue;
+#pragma unroll
+    for (int j = 0; j < NTW; ++j)
+      out[((int64_t)t * NTW + j) * 64 + lane] = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+  }
+}
+
 template <int NTW>
 __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArgsB a) {
-  constexpr int CG = NTW, CGW = CG * 16;
-  constexpr int XW = 20, DP = CGW == 16 ? 20 : 16, DSK = CGW == 32 ? 16 : 0;
-  constexpr int XIMG = 36 * XW * 16;                                   // bf16 elements of the x image
-  constexpr int DIMG = 16 * DP * CGW + (16 / 2 + 1) * DSK;             // bf16 elements of the dy image
-  constexpr unsigned BUFB = (unsigned)(XIMG + DIMG) * 2u;              // bytes of one buffer (x | dy)
-  static_assert(BUFB % 16 == 0, "buffer pitch");
-  static_assert(CWF_WS1_DEPTH < 8 && CWF_W16_DEPTH < 8, "the dy fragment of K-step ks+2 reuses the registers of K-step ks");
+  using L = Ws1Lds<NTW, false>;
+  constexpr int CGW = L::CGW, XW = L::XW, DP = L::DP, DSK = L::DSK;
   extern __shared__ float4 lds4[];
   const ConvGeom& g = a.g;
   unsigned short* lds = reinterpret_cast<unsigned short*>(lds4);
@@ -953,78 +1040,9 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArg
   const int niter = max(t_end - t_begin, 0);
 
   if (wave < 4) {
-    // =============================================================== MFMA waves
-    const int kq = lane >> 4, bq = (lane & 15) >> 2, bp = lane & 3;
-    f32x4 acc[7][NTW];
-#pragma unroll
-    for (int i = 0; i < 7; ++i)
-#pragma unroll
-      for (int j = 0; j < NTW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 ones_s = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_s);
-    const bool bias_wave = wave == 3;
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds4;
-    const unsigned lane_x = lds_base + (((kq & 1) * XW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;
-    unsigned xa0[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int t = wave + 4 * i;
-      xa0[i] = lane_x + (t < 27 ? (((t / 9) * 6 + (t / 3) % 3) * XW + t % 3) * 32 : 0);
-    }
-    const unsigned da0 = lds_base + XIMG * 2 + (((kq & 1) * DP + (kq >> 1) * 8 + bq) * CGW + (kq & 1) * DSK + bp * 4) * 2;
-    auto trf = [&](unsigned addr, unsigned second) __attribute__((always_inline)) {   // two transposed reads -> one K fragment
-      const s16x4 u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)addr);
-      const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(addr + second));
-      const s16x8 w = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-      return __builtin_bit_cast(bf16x8, w);
-    };
-    for (int it = 0; it < niter; ++it) {
-      asm volatile("s_barrier" ::: "memory");              // buffer it & 1 is complete
-      const unsigned bo = (it & 1) ? BUFB : 0u;
-      unsigned xa[7];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) xa[i] = xa0[i] + bo;
-      const unsigned da = da0 + bo;
-      constexpr int DEPTH = CWF_WS1_DEPTH;               // tap steps of LDS-read lookahead (a step is NTW MFMAs = 16-32 cycles)
-      bf16x8 ah[DEPTH + 1], bh[2][NTW];
-      auto issue = [&](int f) __attribute__((always_inline)) {   // f = ks * 7 + i, compile-time after unrolling
-        const int ks = f / 7, i = f % 7;
-        if (i == 0) {
-          const unsigned od_ = (2 * ks * DP * CGW + ks * DSK) * 2;
-#pragma unroll
-          for (int j = 0; j < NTW; ++j) bh[ks & 1][j] = trf(da + od_ + j * 32, 4 * CGW * 2);
-        }
-        const unsigned ox = (((ks >> 1) * 6 + ((2 * ks) & 3)) * XW) * 32;
-        ah[f % (DEPTH + 1)] = trf(xa[i] + ox, 4 * 32);
-      };
-#pragma unroll
-      for (int f = 0; f < DEPTH; ++f) issue(f);
-#pragma unroll
-      for (int f = 0; f < 56; ++f) {
-        if (f + DEPTH < 56) issue(f + DEPTH);
-        __builtin_amdgcn_sched_barrier(0);
-        const int ks = f / 7, i = f % 7;
-        bf16x8 ahf = ah[f % (DEPTH + 1)];
-        if (i == 6) ahf = bias_wave ? ones : ahf;            // wave 3: tap slot 27 = bias row (ones . dy); wave-uniform select
-#pragma unroll
-        for (int j = 0; j < NTW; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahf, bh[ks & 1][j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // ---- slab (layout of wgrad_bf16_kernel: block = (chunk, group, tap, tile))
-    float4* out = reinterpret_cast<float4*>(apart_ + (int64_t)split * a.slab_floats);
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int t = wave + 4 * i;
-      if (t > 27) continue;
-#pragma unroll
-      for (int j = 0; j < NTW; ++j) {
-        const int64_t blk = (((int64_t)chunk * a.ngroups + grp) * 28 + t) * CG + j;
-        out[blk * 64 + lane] = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-      }
-    }
+    float4* slab = reinterpret_cast<float4*>(apart_ + (int64_t)split * a.slab_floats);
+    wgrad_s1_mfma<L>(lds_base, wave, lane, niter, slab + ((int64_t)chunk * a.ngroups + grp) * (28 * NTW * 64));
   } else {
     // =============================================================== loader waves
     const int lt = tid - 256;
@@ -1062,10 +1080,8 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArg
     sc[0] = sc[1] = make_float4(1.f, 1.f, 1.f, 1.f); sh[0] = sh[1] = make_float4(0.f, 0.f, 0.f, 0.f);
     auto issue = [&](int tile, auto S) __attribute__((always_inline)) {
       constexpr int SET = decltype(S)::value;
-      const int n = tile / tiles_sp; int rem = tile % tiles_sp;
-      const int tile_w = rem % g.tiles_w; rem /= g.tiles_w;
-      const int tile_h = rem % g.tiles_h; const int tile_d = rem / g.tiles_h;
-      const int od0 = tile_d * 4, oh0 = tile_h * 4, ow0 = tile_w * 16;
+      const TileOrigin o = tile_origin(tile, tiles_sp, g.tiles_h, g.tiles_w);
+      const int n = o.n, od0 = o.od0, oh0 = o.oh0, ow0 = o.ow0;
       const int id0 = od0 - 1, ih0 = oh0 - 1, iw0 = ow0 - 1;
       const float* xb = ax_ + ((((int64_t)n * g.Di + id0) * g.Hi + ih0) * g.Wi + iw0) * g.x_ldc;
       const float* db = ady_ + ((((int64_t)n * g.Do + od0) * g.Ho + oh0) * g.Wo + ow0) * a.dy_ldc;
@@ -1093,8 +1109,8 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArg
     };
     auto commit = [&](int buf, auto S) __attribute__((always_inline)) {
       constexpr int SET = decltype(S)::value;
-      unsigned short* xh = lds + (buf ? BUFB / 2 : 0);
-      unsigned short* dh = xh + XIMG;
+      unsigned short* xh = lds + (buf ? L::BUFB / 2 : 0);
+      unsigned short* dh = xh + L::DY / 2;
 #pragma unroll
       for (int i = 0; i < XS; ++i) {
         if (i == XS - 1 && !last_x) continue;
@@ -1152,177 +1168,45 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArg
 // and (chunk, group) blocking: wgrad_s1_kernel<2>.  (wgrad_s1 moves 3.3-3.5x its algorithmic bytes from L2 as fp32; this form
 // moves the same halo-amplified voxels at half the bytes, without conversion work and with three tiles of latency cover.)
 // ---------------------------------------------------------------------------------------------------
-#define WS1D_XP 23
-#define WS1D_DP 16
-#define WS1D_XIB (WS1D_XP * 1024)
-#define WS1D_DIB (16 * 1024 + 8 * 32)                   // 16 rows + the skew of the odd rows
-#define WS1D_BUFB (WS1D_XIB + WS1D_DIB)                 // 40,192 B per buffer
-#define WS1D_NBUF 4
-struct Ws1dArgs {
-  const uint4* xa; const uint4* dy; const uint4* zero; float* partial;
-  int N, D, H, W, Cin, Cout, tiles_d, tiles_h, tiles_w, total_tiles, tiles_per_split, ngroups;
-  int64_t slab_floats;
+struct Ws1dArgs : W16dArgs { int Cin, Cout, tiles_per_split, ngroups; };
+
+struct Ws1dDma {
+  using L = Ws1Lds<2, true>;
+  static constexpr int LW = WS1_LW, DPC = 16;
+  const Ws1dArgs& a; int gx, gd, xg0, dg0, t_begin;     // dg0: first granule of the workgroup's 32-channel group
+  __device__ int tile(int it) const { return t_begin + it; }
+  __device__ void dy_piece(int m, int lane, int& c0, int& c1, int& w, int& g, bool& valid) const {   // M-tile row m: 16 voxels x 4 granules
+    c0 = m >> 2; c1 = m & 3; w = lane >> 2; g = dg0 + (lane & 3); valid = true;
+  }
+  static __device__ constexpr unsigned dy_dst(int m) { return L::DY + (unsigned)(m * 1024 + ((m + 1) >> 1) * 32); }   // (skewed rows)
 };
 
 __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1d_kernel(const Ws1dArgs a) {
-  constexpr int NTW = 2, CG = 2, CGW = 32, XW = 20, DP = 16, DSK = 16;
+  using L = Ws1dDma::L;
   extern __shared__ float4 lds4[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int split = blockIdx.x;
   const int chunk = blockIdx.y / a.ngroups, grp = blockIdx.y % a.ngroups;
-  const int tiles_sp = a.tiles_d * a.tiles_h * a.tiles_w;
   const int t_begin = split * a.tiles_per_split;
   const int t_end = min(a.total_tiles, t_begin + a.tiles_per_split);
   const int niter = max(t_end - t_begin, 0);
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds4;
-
   if (wave < 4) {
-    // =============================================================== MFMA waves (wgrad_s1_kernel<2>, four buffers)
-    const int kq = lane >> 4, bq = (lane & 15) >> 2, bp = lane & 3;
-    f32x4 acc[7][NTW];
-#pragma unroll
-    for (int i = 0; i < 7; ++i)
-#pragma unroll
-      for (int j = 0; j < NTW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 ones_s = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_s);
-    const bool bias_wave = wave == 3;
-    const unsigned lane_x = lds_base + (((kq & 1) * XW + (kq >> 1) * 8 + bq) * 16 + bp * 4) * 2;
-    unsigned xa0[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int t = wave + 4 * i;
-      xa0[i] = lane_x + (t < 27 ? (((t / 9) * 6 + (t / 3) % 3) * XW + t % 3) * 32 : 0);
-    }
-    const unsigned da0 = lds_base + WS1D_XIB + (((kq & 1) * DP + (kq >> 1) * 8 + bq) * CGW + (kq & 1) * DSK + bp * 4) * 2;
-    auto trf = [&](unsigned addr, unsigned second) __attribute__((always_inline)) {
-      const s16x4 u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)addr);
-      const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(addr + second));
-      const s16x8 w = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-      return __builtin_bit_cast(bf16x8, w);
-    };
-    for (int it = 0; it < niter; ++it) {
-      asm volatile("s_barrier" ::: "memory");              // buffer it & 3 has landed
-      const unsigned bo = (unsigned)(it & 3) * WS1D_BUFB;
-      unsigned xa[7];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) xa[i] = xa0[i] + bo;
-      const unsigned da = da0 + bo;
-      constexpr int DEPTH = CWF_WS1_DEPTH;
-      bf16x8 ah[DEPTH + 1], bh[2][NTW];
-      auto issue = [&](int f) __attribute__((always_inline)) {
-        const int ks = f / 7, i = f % 7;
-        if (i == 0) {
-          const unsigned od_ = (2 * ks * DP * CGW + ks * DSK) * 2;
-#pragma unroll
-          for (int j = 0; j < NTW; ++j) bh[ks & 1][j] = trf(da + od_ + j * 32, 4 * CGW * 2);
-        }
-        const unsigned ox = (((ks >> 1) * 6 + ((2 * ks) & 3)) * XW) * 32;
-        ah[f % (DEPTH + 1)] = trf(xa[i] + ox, 4 * 32);
-      };
-#pragma unroll
-      for (int f = 0; f < DEPTH; ++f) issue(f);
-#pragma unroll
-      for (int f = 0; f < 56; ++f) {
-        if (f + DEPTH < 56) issue(f + DEPTH);
-        __builtin_amdgcn_sched_barrier(0);
-        const int ks = f / 7, i = f % 7;
-        bf16x8 ahf = ah[f % (DEPTH + 1)];
-        if (i == 6) ahf = bias_wave ? ones : ahf;
-#pragma unroll
-        for (int j = 0; j < NTW; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahf, bh[ks & 1][j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    float4* out = reinterpret_cast<float4*>(a.partial + (int64_t)split * a.slab_floats);
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int t = wave + 4 * i;
-      if (t > 27) continue;
-#pragma unroll
-      for (int j = 0; j < NTW; ++j) {
-        const int64_t blk = (((int64_t)chunk * a.ngroups + grp) * 28 + t) * CG + j;
-        out[blk * 64 + lane] = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-      }
-    }
+    float4* slab = reinterpret_cast<float4*>(a.partial + (int64_t)split * a.slab_floats);
+    wgrad_s1_mfma<L>(lds_base, wave, lane, niter, slab + ((int64_t)chunk * a.ngroups + grp) * (28 * L::NTW * 64));
   } else {
-    // =============================================================== loader waves: DMA only
-    const int lw = wave - 4;                               // pieces lw, lw + 8, ... of the 39
-    typedef __attribute__((address_space(3))) void* lds_vp;
-    typedef __attribute__((address_space(1))) const void* glb_vp;
-    const int gx = a.Cin >> 3, gd = a.Cout >> 3;           // 16-byte granules per voxel
-    auto run = [&](auto NI_) __attribute__((always_inline)) {
-      constexpr int NI = decltype(NI_)::value;
-      int off[NI]; unsigned crd[NI];
-#pragma unroll
-      for (int k = 0; k < NI; ++k) {
-        const int s = lw + WS1_LW * k;
-        if (s < WS1D_XP) {
-          const int gi = 64 * s + lane;
-          const int row = gi / 40, gr = gi % 40, w = gr >> 1, half = gr & 1;
-          const int c0 = row / 6, c1 = row % 6;
-          off[k] = ((c0 * a.H + c1) * a.W + w) * gx + chunk * 2 + half;
-          crd[k] = (unsigned)c0 | ((unsigned)c1 << 3) | ((unsigned)w << 6) | ((row < 36 && gr < 36) ? 1u << 11 : 0u);
-        } else {
-          const int m = s - WS1D_XP, w = lane >> 2, q = lane & 3;
-          off[k] = (((m >> 2) * a.H + (m & 3)) * a.W + w) * gd + grp * 4 + q;
-          crd[k] = (unsigned)(m >> 2) | ((unsigned)(m & 3) << 3) | ((unsigned)w << 6) | (1u << 11);
-        }
-      }
-      auto issue = [&](int it) __attribute__((always_inline)) {
-        const int tile = t_begin + it;
-        const int n = tile / tiles_sp; int rem = tile - n * tiles_sp;
-        const int tile_w = rem % a.tiles_w; rem /= a.tiles_w;
-        const int tile_h = rem % a.tiles_h; const int tile_d = rem / a.tiles_h;
-        const int od0 = tile_d * 4, oh0 = tile_h * 4, ow0 = tile_w * 16;
-        const int64_t vd = (((int64_t)n * a.D + od0) * a.H + oh0) * a.W + ow0;
-        const int64_t vx = vd - ((int64_t)a.H + 1) * a.W - 1;
-        const unsigned lbuf = lds_base + (unsigned)(it & 3) * WS1D_BUFB;
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-          const int s = lw + WS1_LW * k;                   // (wave-uniform)
-          const bool isd = s >= WS1D_XP;
-          const int c0 = (int)(crd[k] & 7u), c1 = (int)((crd[k] >> 3) & 7u), w = (int)((crd[k] >> 6) & 31u);
-          const int gdd = (isd ? od0 : od0 - 1) + c0, gh = (isd ? oh0 : oh0 - 1) + c1, gw = (isd ? ow0 : ow0 - 1) + w;
-          const bool ok = (crd[k] >> 11) != 0u && (unsigned)gdd < (unsigned)a.D && (unsigned)gh < (unsigned)a.H && (unsigned)gw < (unsigned)a.W;
-          const uint4* src = (isd ? a.dy + vd * gd : a.xa + vx * gx) + off[k];
-          src = ok ? src : a.zero;
-          const int m = s - WS1D_XP;
-          const unsigned dst = isd ? (unsigned)(WS1D_XIB + m * 1024 + ((m + 1) >> 1) * 32) : (unsigned)s * 1024u;
-          __builtin_amdgcn_global_load_lds((glb_vp)src, (lds_vp)(uintptr_t)(lbuf + dst), 16, 0, 0);
-        }
-      };
-      if (niter > 0) issue(0);
-      if (niter > 1) issue(1);
-      if (niter > 2) issue(2);
-      for (int it = 0; it < niter; ++it) {
-        if (it + 2 < niter) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NI) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_barrier" ::: "memory");
-        if (it + 3 < niter) issue(it + 3);
-      }
-    };
-    constexpr int NP = WS1D_XP + WS1D_DP;
-    if (lw < NP % WS1_LW) run(std::integral_constant<int, NP / WS1_LW + 1>{});
-    else run(std::integral_constant<int, NP / WS1_LW>{});
+    wgrad_dma_loader(Ws1dDma{a, a.Cin >> 3, a.Cout >> 3, chunk * 2, grp * 4, t_begin}, lds_base, wave - 4, lane, niter);
   }
 }
 
 static int wgrad_s1d_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
-  const void* xa16 = d.xa16; const void* dy16 = d.dy16; const void* zero16 = d.zero16; float* partial = d.partial;
-  const int N = d.N, D = d.Di, H = d.Hi, W = d.Wi, Cin = d.Cin, Cout = d.Cout;
-  if (!xa16 || !dy16 || !zero16 || !partial || N <= 0 || D <= 0 || H <= 0 || W <= 0) return CWF_E_BADARG;
-  if (((uintptr_t)xa16 & 15) || ((uintptr_t)dy16 & 15) || ((uintptr_t)zero16 & 15) || ((uintptr_t)partial & 15)) return CWF_E_ALIGN;
-  if (Cin < 16 || (Cin & 15) || Cout < 32 || (Cout & 31)) return CWF_E_BADARG;
-  if ((int64_t)N * D * H * W * (Cin > Cout ? Cin : Cout) >= (1ll << 33)) return CWF_E_TOOLARGE;
+  const int Cin = d.Cin, Cout = d.Cout;
   Ws1dArgs a;
-  a.xa = (const uint4*)xa16; a.dy = (const uint4*)dy16; a.zero = (const uint4*)zero16; a.partial = partial;
-  a.N = N; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.tiles_d = cdiv(D, 4); a.tiles_h = cdiv(H, 4); a.tiles_w = cdiv(W, 16);
-  a.total_tiles = N * a.tiles_d * a.tiles_h * a.tiles_w;
+  if (const int rc = wgrad_image_args(d, a)) return rc;
+  if (Cin < 16 || (Cin & 15) || Cout < 32 || (Cout & 31)) return CWF_E_BADARG;
+  if ((int64_t)a.N * a.D * a.H * a.W * (Cin > Cout ? Cin : Cout) >= (1ll << 33)) return CWF_E_TOOLARGE;
+  a.Cin = Cin; a.Cout = Cout;
   const int nchunks = Cin / 16;
   a.ngroups = Cout / 32;
   const int nblk = nchunks * a.ngroups;
@@ -1331,10 +1215,9 @@ static int wgrad_s1d_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream
   int want = SIDE_WGS / nblk; if (want < 1) want = 1; if (want > a.total_tiles) want = a.total_tiles;
   a.tiles_per_split = cdiv(a.total_tiles, want);
   const int splits = cdiv(a.total_tiles, a.tiles_per_split);
-  if (splits > cwf_wgrad_nsplit(CWF_CONV3_S1, N, D, H, W, Cin, Cout)) return CWF_E_BADARG;     // (the caller's slab buffer is sized by it)
-  const size_t lds = (size_t)WS1D_NBUF * WS1D_BUFB;
+  if (splits > cwf_wgrad_nsplit(CWF_CONV3_S1, a.N, a.D, a.H, a.W, Cin, Cout)) return CWF_E_BADARG;     // (the caller's slab buffer is sized by it)
   CWF_MAX_LDS_ONCE((&wgrad_s1d_kernel));
-  hipLaunchKernelGGL(wgrad_s1d_kernel, dim3(splits, nblk), dim3(256 + 64 * WS1_LW), lds, st, a);
+  hipLaunchKernelGGL(wgrad_s1d_kernel, dim3(splits, nblk), dim3(256 + 64 * WS1_LW), Ws1dDma::L::BYTES, st, a);
   CWF_LAUNCH_CHECK();
   if (nsplit_used) *nsplit_used = splits;
   return 0;
@@ -1551,7 +1434,7 @@ static int wgrad_bf16_impl(const cwf_wgrad_args& d, int* nsplit_used, hipStream_
     // full-resolution 16-channel layers: persistent producer/consumer kernel, one slab per workgroup (<= 256 <= generic nsplit)
     // (the stem layer -- 4 input channels -- is the LAST kernel of backward: nothing runs beside it, it takes every CU)
     int grid = Cin <= 4 ? 256 : SIDE_WGS; while (grid > 8 && grid > total) grid -= 8;      // multiple of 8 (XCD-aware tile map)
-    const size_t lds16 = (size_t)2 * (36 * W16_XW * 16 + 16 * W16_DW * 16) * sizeof(unsigned short) * (x3 ? 2 : 1);
+    const size_t lds16 = x3 ? W16Lds<true, false>::BYTES : W16Lds<false, false>::BYTES;
     if (x3) {
       CWF_MAX_LDS_ONCE((&wgrad16_kernel<true>));
       hipLaunchKernelGGL((wgrad16_kernel<true>), dim3(grid), dim3(256 + 64 * W16_LW), lds16, st, a, total);
@@ -1588,7 +1471,7 @@ static int wgrad_bf16_impl(const cwf_wgrad_args& d, int* nsplit_used, hipStream_
     if (splits1 <= wg_splits) {                          // (the workspace was sized for wg_splits slabs)
       a.tiles_per_split = tps1;
       if (nsplit_used) *nsplit_used = splits1;
-      const size_t lds1 = (size_t)2 * (36 * 20 * 16 + 16 * (CG == 1 ? 20 : 16) * CG * 16 + (16 / 2 + 1) * (CG == 2 ? 16 : 0)) * sizeof(unsigned short);
+      const size_t lds1 = CG == 1 ? Ws1Lds<1, false>::BYTES : Ws1Lds<2, false>::BYTES;
       dim3 grid1(splits1, nchunks * ngroups, groups ? groups : 1);
       CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<1>));
       CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<2>));
@@ -1622,7 +1505,7 @@ extern "C" int cwf_wgrad(const struct cwf_wgrad_args* args, int* nsplit_used, vo
   hipStream_t st = cwf_stream(stream);
   if (d.xa16 || d.dy16) {                                  // bf16 operand images (x, dy and x's prologue are not read)
     if (!d.xa16 || !d.dy16 || d.precision != CWF_BF16 || d.op != CWF_CONV3_S1 || d.groups || d.dy_scale) return CWF_E_BADARG;
-    if (d.Cin == 16 && d.Cout == 16 && (int64_t)d.Do * d.Ho * d.Wo >= 32768) return wgrad16_launch(d, nsplit_used, st);
+    if (d.Cin == 16 && d.Cout == 16 && (int64_t)d.Do * d.Ho * d.Wo >= 32768) return wgrad16d_launch(d, nsplit_used, st);
     return wgrad_s1d_launch(d, nsplit_used, st);
   }
   if (d.groups) {

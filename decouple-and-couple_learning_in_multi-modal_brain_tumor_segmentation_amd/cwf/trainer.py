@@ -202,13 +202,24 @@ class Trainer:
 
     def _capture(self, x, target, edge):
         import ctypes
+        import gc
         self._static = (x.clone(), target.clone(), edge.clone())
         want_plan = self.graph_mode == "plan"
         g = torch.cuda.CUDAGraph(keep_graph=True) if want_plan else torch.cuda.CUDAGraph()
-        # thread-local capture mode: with a process group alive, RCCL's watchdog thread polls events while this thread captures; in the
-        # default (global) mode any such call from another thread invalidates the capture
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._static_out = self._fwd_bwd(*self._static)
+        # No cyclic garbage collection inside the capture.  A Trainer and its model form a cycle (model.phase_callback), so an earlier
+        # Trainer's plan (streams, events) and kept hipGraph are destroyed by the collector, whenever it runs; when it ran inside this
+        # capture, from the autograd thread, the process aborted there.  (torch.cuda.graph itself no longer collects on entry.)
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            # thread-local capture mode: with a process group alive, RCCL's watchdog thread polls events while this thread captures; in
+            # the default (global) mode any such call from another thread invalidates the capture
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._static_out = self._fwd_bwd(*self._static)
+        finally:
+            if gc_was_on:
+                gc.enable()
         self._graph = g
         if want_plan:
             K = kernels_backend()

@@ -216,10 +216,13 @@ def test_conv16s_reads_a_bf16_input_image(hip, size, n):
             close(outs[1][1], outs[0][1].cpu(), rtol=1e-6, what="nb sums")          # (fp32 partial sums folded by f64 atomics)
 
 
-@pytest.mark.parametrize("cin,cout,size,n", [(32, 32, (16, 16, 32), 2), (64, 64, (8, 12, 16), 1), (128, 256, (6, 6, 10), 2), (96, 96, (8, 8, 16), 1)])
+@pytest.mark.parametrize("cin,cout,size,n", [(32, 32, (16, 16, 32), 2), (64, 64, (8, 12, 16), 1), (128, 256, (6, 6, 10), 2), (96, 96, (8, 8, 16), 1),
+                                                (64, 64, (19, 22, 40), 1)])
 def test_dma_weight_gradient_32_channel_groups(hip, cin, cout, size, n):
     """cwf_wgrad on bf16 images (wgrad_s1d_kernel: bf16 images by LDS-DMA, 16-channel chunks x 32-channel groups) against the fp32-tensor
-    kernel (same single-bf16 operands: summation order only) and the oracle; ragged tiles included."""
+    kernel (same single-bf16 operands: summation order only) and the oracle; ragged tiles included.  The last case (90 tiles, ragged in
+    all three axes, 8 (chunk, group) blocks) gives every workgroup of either kernel five tiles: the image kernel's four-buffer ring
+    wraps and the fp32-tensor kernel's two buffers and register sets turn several times."""
     from cwf import functional as CF, kernels
     d, h, w_ = size
     x = rnd(n, d, h, w_, cin, seed=41); g = rnd(n, d, h, w_, cout, seed=42)

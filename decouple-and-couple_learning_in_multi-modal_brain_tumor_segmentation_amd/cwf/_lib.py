@@ -118,6 +118,7 @@ SIGNATURES = {
     "cwf_prepare_batch_affine": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_prepare_batch_elastic": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_augment_intensity": [P, I, I, I, I, P, L, P, L, P, L, P],
+    "cwf_augment_acquisition": [P, I, I, I, I, P, L, P, L, P, L, P],
     "cwf_window_gather": [P, P, P, I, I, P],
     "cwf_window_blend": [P, P, P, P, I, I, I, P],
     "cwf_window_finalize": [P, P, P, P, P],
@@ -214,6 +215,23 @@ def intensity_ws_floats(nb, crop):
     for c, t in zip(crop, INTENSITY_TILE):
         tiles *= (int(c) + t - 1) // t
     return 8 * int(nb) * tiles
+
+
+class AcquireSample(C.Structure):
+    """struct cwf_acquire_sample (include/cwf_hip.h)"""
+    _fields_ = [("bias", P * 4), ("G0", I), ("G1", I), ("G2", I), ("bias_mask", I), ("contrast_mask", I), ("lowres_mask", I),
+                ("factor", F * 4), ("lattice", (I * 3) * 4)]
+
+
+ACQUIRE_TILE = (32, 8, 32)   # CWF_ACQUIRE_T0, _T1, _T2: the voxels of one (sum, min, max) partial
+
+
+def acquire_ws_doubles(nb, crop):
+    """doubles of device scratch cwf_augment_acquisition needs for nb samples of `crop` voxels when some contrast bit is set"""
+    tiles = 1
+    for c, t in zip(crop, ACQUIRE_TILE):
+        tiles *= (int(c) + t - 1) // t
+    return 12 * int(nb) * tiles
 
 
 WINDOW_MAX_STARTS = 128   # CWF_WINDOW_MAX_STARTS

@@ -1524,7 +1524,12 @@ class HipBackend:
         (x, target, edge) to write into; each needs contiguous inner dimensions, its sample stride may be larger than one sample.
         .blur / .noise / .noise_key / .gamma (utils.data.AugParams): when some channel of some sample has one on, the intensity stage
         (cwf_augment_intensity) follows on x: in place without a blur; with one the prepare kernel writes x into a workspace from
-        torch's allocator and the stage writes the batch's x.  With all of them off nothing but the prepare entry is called."""
+        torch's allocator and the stage writes the batch's x.  With all of them off nothing but the prepare entry is called.
+        .bias / .bias_mask / .contrast / .lowres: when some channel of some sample has one on, the acquisition stage
+        (cwf_augment_acquisition) runs between the two: in place on what the prepare kernel wrote without a lowres bit; with one
+        it gathers into the next buffer of the chain (the batch's x, or a second workspace when a blur follows).  The control
+        multipliers travel as the elastic grids do.  At most two batch-sized workspaces, from torch's allocator, which hands the
+        same blocks out again call after call."""
         crop = tuple(int(c) for c in crop)
         if len(crop) != 3:
             raise ValueError("prepare_batch: crop needs three extents, got %r" % (crop,))
@@ -1589,17 +1594,69 @@ class HipBackend:
                 if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or tuple(t.stride()[1:]) != inner:
                     raise ValueError("prepare_batch: out %s must be a %s %s tensor on %s with contiguous samples" % (name, dt, shape, dev))
         stage = self._intensity_samples(params)
-        x_prep = x
-        if stage is not None and any(s.blur for s in stage):      # a blur reads its neighbours: not in place
-            x_prep = torch.empty((nb, 4) + tuple(x.shape[2:]), dtype=_f32, device=dev)
+        acq, bias_dev = self._acquire_samples(params, crop, dev)
+        blur = stage is not None and any(s.blur for s in stage)   # a blur reads its neighbours: not in place
+        lowres = acq is not None and any(s.lowres_mask for s in acq)    # nor does the gather of the low-resolution step
+
+        def scratch():
+            return torch.empty((nb, 4) + tuple(x.shape[2:]), dtype=_f32, device=dev)
+
+        x_acq = scratch() if blur else x                          # what the intensity stage reads
+        x_prep = scratch() if lowres else x_acq                   # what the prepare kernel writes
         self._call(entry, ctypes.addressof(samples), nb, crop[0], crop[1], crop[2], x_prep.data_ptr(), x_prep.stride(0),
                    target.data_ptr(), target.stride(0), edge.data_ptr(), edge.stride(0), self._stream())
+        if acq is not None:
+            nws = _lib.acquire_ws_doubles(nb, crop) if any(s.contrast_mask for s in acq) else 0
+            ws = torch.empty(nws, dtype=torch.float64, device=dev) if nws else None
+            self._call("cwf_augment_acquisition", ctypes.addressof(acq), nb, crop[0], crop[1], crop[2], x_prep.data_ptr(),
+                       x_prep.stride(0), x_acq.data_ptr(), x_acq.stride(0), _p(ws), nws, self._stream())
+        x_prep = x_acq
         if stage is not None:
             nws = _lib.intensity_ws_floats(nb, crop) if any(s.gam for s in stage) else 0
             ws = torch.empty(nws, dtype=_f32, device=dev) if nws else None
             self._call("cwf_augment_intensity", ctypes.addressof(stage), nb, crop[0], crop[1], crop[2], x_prep.data_ptr(),
                        x_prep.stride(0), x.data_ptr(), x.stride(0), _p(ws), nws, self._stream())
         return x, target, edge
+
+    @staticmethod
+    def _acquire_samples(params, crop, dev):
+        """(cwf_acquire_sample [len(params)], the device tensor that holds their control multipliers or None) of the samples' bias /
+        contrast / lowres, or (None, None) when every channel of every one is off.  The grids of the channels that are on are packed
+        into one pinned host buffer and copied by one non-blocking copy on the current stream."""
+        from utils import data
+        acq = (_lib.AcquireSample * len(params))()
+        on, grids = False, []
+        for s, p in zip(acq, params):
+            mask, bias = getattr(p, "bias_mask", None), getattr(p, "bias", None)
+            contrast, lowres = getattr(p, "contrast", None), getattr(p, "lowres", None)
+            if bias is not None and mask is not None and any(mask):
+                if bias.dtype != np.float32 or bias.ndim != 4 or bias.shape[0] != 4:
+                    raise ValueError("prepare_batch: bias must be a float32 [4, G0, G1, G2] array, got %s %r" % (bias.dtype, bias.shape))
+                s.G0, s.G1, s.G2 = (int(v) for v in bias.shape[1:])
+            for c in range(4):
+                if bias is not None and mask is not None and mask[c]:
+                    grids.append((s, c, bias[c]))
+                    s.bias_mask |= 1 << c
+                if contrast is not None and contrast[c] > 0.0:
+                    s.factor[c] = float(contrast[c])
+                    s.contrast_mask |= 1 << c
+                if lowres is not None and lowres[c] > 0.0:
+                    s.lattice[c][:] = data.lowres_lattice(crop, lowres[c])
+                    s.lowres_mask |= 1 << c
+            on = on or bool(s.bias_mask or s.contrast_mask or s.lowres_mask)
+        if not on:
+            return None, None
+        bias_dev = None
+        if grids:
+            host = torch.empty(sum(int(g.size) for _, _, g in grids), dtype=_f32, pin_memory=True)
+            view, at = host.numpy(), 0
+            bias_dev = torch.empty(host.numel(), dtype=_f32, device=dev)
+            for s, c, g in grids:
+                view[at:at + g.size] = g.reshape(-1)
+                s.bias[c] = bias_dev.data_ptr() + 4 * at
+                at += int(g.size)
+            bias_dev.copy_(host, non_blocking=True)
+        return acq, bias_dev
 
     @staticmethod
     def _intensity_samples(params):

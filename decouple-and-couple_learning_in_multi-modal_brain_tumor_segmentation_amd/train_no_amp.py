@@ -106,6 +106,16 @@ def build_parser():
                    help="(--device_data) n > 0: additive noise on each channel with probability 1/2, sigma ~ U(0, n)")
     p.add_argument("--aug_gamma", default=0.0, type=float,
                    help="(--device_data) g in (0, 1): gamma map of each channel's range with probability 1/2, exponent ~ U(1-g, 1+g)")
+    p.add_argument("--aug_bias", default=0.0, type=float,
+                   help="(--device_data) b in (0, 1]: smooth multiplicative bias field on each channel with probability 1/2, a cubic "
+                        "B-spline of control multipliers exp(U(-b, b))")
+    p.add_argument("--aug_bias_grid", default=4, type=int, help="(--aug_bias) control points per axis, 4..8")
+    p.add_argument("--aug_contrast", default=0.0, type=float,
+                   help="(--device_data) k in (0, 1): contrast about each channel's mean with probability 1/2, factor ~ U(1-k, 1+k), "
+                        "clamped to the channel's range")
+    p.add_argument("--aug_lowres", default=0.0, type=float,
+                   help="(--device_data) z in [0.5, 1): low-resolution simulation of each channel with probability 1/2, sampled on a "
+                        "lattice zoomed by U(z, 1) (nearest) and interpolated back (trilinear)")
     p.add_argument("--normalize", default=False, type=_bool,
                    help="(--device_data) z-score each subject's channels over its brain mask (four-channel sum > 0) at load")
     p.add_argument("--accum_steps", default=1, type=int,
@@ -146,6 +156,21 @@ def check_intensity_aug(args):
         raise SystemExit("--aug_gamma takes a half-width in [0, 1) of the exponent's range about 1")
 
 
+def check_acquisition_aug(args):
+    """the values of --aug_bias / --aug_bias_grid / --aug_contrast / --aug_lowres (SystemExit with the rule, like the other checks)"""
+    if args.device_data == "off" and (args.aug_bias != 0.0 or args.aug_contrast != 0.0 or args.aug_lowres != 0.0):
+        raise SystemExit("--aug_bias / --aug_contrast / --aug_lowres run on the prepared crop on the device: they need --device_data "
+                         "cache or staged")
+    if not 0.0 <= args.aug_bias <= 1.0:
+        raise SystemExit("--aug_bias takes a half-width in [0, 1] of the log multiplier's range about 0")
+    if args.aug_bias > 0.0 and not 4 <= args.aug_bias_grid <= 8:
+        raise SystemExit("--aug_bias_grid takes 4..8 control points per axis")
+    if not 0.0 <= args.aug_contrast < 1.0:
+        raise SystemExit("--aug_contrast takes a half-width in [0, 1) of the factor's range about 1")
+    if args.aug_lowres != 0.0 and not 0.5 <= args.aug_lowres < 1.0:
+        raise SystemExit("--aug_lowres takes 0 (off) or a smallest zoom in [0.5, 1)")
+
+
 def should_save(epoch, end_epoch, save_freq):
     """train_no_amp.py:243-246 (epochs are 0-based in the loop, 1-based in the test)."""
     e = epoch + 1
@@ -183,7 +208,8 @@ def make_device_dataset(args, device):
     return data.DeviceBraTS(source, device, crop, args.seed, flip=args.aug_flip, intensity=args.aug_intensity,
                             normalize=args.normalize, cache=(args.device_data == "cache"), list_file=lst, rotate=args.aug_rotate,
                             scale=args.aug_scale, elastic=args.aug_elastic, elastic_grid=args.aug_elastic_grid,
-                            blur=args.aug_blur, noise=args.aug_noise, gamma=args.aug_gamma)
+                            blur=args.aug_blur, noise=args.aug_noise, gamma=args.aug_gamma, bias=args.aug_bias,
+                            bias_grid=args.aug_bias_grid, contrast=args.aug_contrast, lowres=args.aug_lowres)
 
 
 def main(argv=None):
@@ -199,6 +225,7 @@ def main(argv=None):
     if args.aug_elastic < 0.0 or not 4 <= args.aug_elastic_grid <= 8:
         raise SystemExit("--aug_elastic takes voxels >= 0 and --aug_elastic_grid 4 to 8 control points per axis")
     check_intensity_aug(args)
+    check_acquisition_aug(args)
     check_step_controls(args)
     from cwf import kernels
     from cwf.parallel import shard_indices

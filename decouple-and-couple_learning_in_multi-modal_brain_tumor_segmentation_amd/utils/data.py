@@ -13,8 +13,9 @@ Edge codes are derived from the label with utils.synthetic.edge_codes (boundary 
 ``DeviceBraTS`` / ``prepare_batch`` produce the same tuple on the GPU (csrc/prep.hip: crop, optional flips and intensity scale / shift,
 label remap and edge codes in one launch per eight samples; with a matrix in the parameters the crop is rotated and zoomed, trilinear for
 the image and nearest for the label; with a control grid it is deformed elastically on top of that; with blur, noise or gamma in the
-parameters csrc/intensity.hip then runs the intensity stage on the prepared crop), bit-equal to the CPU statement in this module,
-except gamma-mapped channels, which are bounded (below: _intensity_stage_cpu)."""
+parameters csrc/intensity.hip then runs the intensity stage on the prepared crop; with a bias field, contrast or a low-resolution
+zoom csrc/acquire.hip runs the acquisition stage before it), bit-equal to the CPU statement in this module, except gamma-mapped and
+contrast-mapped channels, which are bounded (below: _intensity_stage_cpu, _acquisition_stage_cpu)."""
 import glob
 import math
 import os
@@ -118,11 +119,16 @@ class AugParams:
     no deformation.  Non-finite control values are allowed: the voxels they reach read nothing).  The intensity stage on the prepared
     crop (_intensity_stage_cpu), per channel: blur, the Gaussian's sigma in voxels (float32 [4], 0 = off; None = all off); noise, the
     sigma of the additive noise (float32 [4], 0 = off) with noise_key, an int in [0, 2^63), the key of its counter-based stream;
-    gamma, the exponent (float32 [4], 0 = off)."""
-    __slots__ = ("origin", "flip", "scale", "shift", "matrix", "blur", "noise", "noise_key", "gamma", "disp")
+    gamma, the exponent (float32 [4], 0 = off).  The acquisition stage, which runs before it (_acquisition_stage_cpu), per channel:
+    bias, the control multipliers of the bias field, float32 [4, G0, G1, G2] with 4 <= G_d <= 8 and finite values > 0 (a read-only
+    array; None = off), with bias_mask, four bools, the channels it applies to; contrast, the factor (float32 [4], 0 = off); lowres,
+    the zoom of the coarse lattice in [0.5, 1) (float32 [4], 0 = off)."""
+    __slots__ = ("origin", "flip", "scale", "shift", "matrix", "blur", "noise", "noise_key", "gamma", "bias_mask", "contrast", "lowres",
+                 "disp", "bias")
+    _ARRAYS = ("disp", "bias")            # compared bit for bit
 
     def __init__(self, origin, flip=(False, False, False), scale=None, shift=None, matrix=None, disp=None, *, blur=None, noise=None,
-                 noise_key=None, gamma=None):
+                 noise_key=None, gamma=None, bias=None, bias_mask=None, contrast=None, lowres=None):
         self.origin = tuple(int(o) for o in origin)
         self.flip = tuple(bool(f) for f in flip)
         if (scale is None) != (shift is None):
@@ -150,14 +156,41 @@ class AugParams:
         if noise_key is not None and not 0 <= int(noise_key) < 2 ** 63:
             raise ValueError("AugParams: noise_key must lie in [0, 2^63), got %r" % (noise_key,))
         self.noise_key = 0 if noise_key is None else int(noise_key)
+        if bias is not None:
+            bias = np.array(bias, dtype=np.float32, order="C")
+            if bias.ndim != 4 or bias.shape[0] != 4 or not all(ELASTIC_GRID_MIN <= g <= ELASTIC_GRID_MAX for g in bias.shape[1:]):
+                raise ValueError("AugParams: bias takes a [4, G0, G1, G2] grid with %d <= G_d <= %d, got shape %r"
+                                 % (ELASTIC_GRID_MIN, ELASTIC_GRID_MAX, tuple(bias.shape)))
+            if not bool(np.all(np.isfinite(bias) & (bias > 0))):
+                raise ValueError("AugParams: bias takes finite control multipliers > 0")
+            if bias_mask is None:
+                raise ValueError("AugParams: bias comes with bias_mask, the four channels it applies to")
+            bias.setflags(write=False)
+        self.bias = bias
+        mask = (False,) * 4 if bias_mask is None else tuple(bool(v) for v in bias_mask)
+        if len(mask) != 4 or (bias is None and any(mask)):
+            raise ValueError("AugParams: bias_mask takes 4 bools, and needs a bias where one is set, got %r" % (bias_mask,))
+        self.bias_mask = mask
+        for name, val, lo, hi in (("contrast", contrast, 0.0, np.inf), ("lowres", lowres, 0.5, 1.0)):
+            if val is not None:
+                val = tuple(float(v) for v in np.asarray(val, dtype=np.float32).reshape(-1))
+                if len(val) != 4 or not all(v == 0.0 or (np.isfinite(v) and lo <= v < hi and v > 0.0) for v in val):
+                    raise ValueError("AugParams: %s takes 4 values, each 0 (off) or %s, got %r"
+                                     % (name, "finite and > 0" if name == "contrast" else "in [0.5, 1)", val))
+            setattr(self, name, val)
 
     def at_origin(self, origin):
         return AugParams(origin, self.flip, self.scale, self.shift, self.matrix, self.disp, blur=self.blur, noise=self.noise,
-                         noise_key=self.noise_key, gamma=self.gamma)
+                         noise_key=self.noise_key, gamma=self.gamma, bias=self.bias, bias_mask=self.bias_mask if self.bias is not None
+                         else None, contrast=self.contrast, lowres=self.lowres)
 
     def intensity_stage(self):
         """True when blur, noise or gamma is on for some channel"""
         return any(v is not None and any(c > 0.0 for c in v) for v in (self.blur, self.noise, self.gamma))
+
+    def acquisition_stage(self):
+        """True when the bias field, contrast or the low-resolution simulation is on for some channel"""
+        return any(self.bias_mask) or any(v is not None and any(c > 0.0 for c in v) for v in (self.contrast, self.lowres))
 
     def source_box(self, crop):
         """Integer bounds ((lo_0, hi_0), ...) relative to the origin, hi exclusive, that contain every source index the crop reads
@@ -181,11 +214,18 @@ class AugParams:
         return tuple(box)
 
     def __eq__(self, other):
-        if not isinstance(other, AugParams) or not all(getattr(self, k) == getattr(other, k) for k in self.__slots__[:-1]):
+        if not isinstance(other, AugParams):
             return False
-        if self.disp is None or other.disp is None:
-            return self.disp is other.disp
-        return self.disp.shape == other.disp.shape and self.disp.tobytes() == other.disp.tobytes()      # bit for bit (NaN included)
+        if not all(getattr(self, k) == getattr(other, k) for k in self.__slots__ if k not in self._ARRAYS):
+            return False
+        for k in self._ARRAYS:
+            a, b = getattr(self, k), getattr(other, k)
+            if a is None or b is None:
+                if a is not b:
+                    return False
+            elif a.shape != b.shape or a.tobytes() != b.tobytes():                                   # bit for bit (NaN included)
+                return False
+        return True
 
     def __repr__(self):
         head = "AugParams(origin=%r, flip=%r, scale=%r, shift=%r" % (self.origin, self.flip, self.scale, self.shift)
@@ -195,6 +235,11 @@ class AugParams:
         head += "" if self.gamma is None else ", gamma=%r" % (self.gamma,)
         if self.disp is not None:
             head += ", disp=float32%r max |.| %r" % (list(self.disp.shape), float(np.max(np.abs(self.disp))))
+        if self.bias is not None:
+            head += ", bias=float32%r in [%r, %r], bias_mask=%r" % (list(self.bias.shape), float(self.bias.min()),
+                                                                    float(self.bias.max()), self.bias_mask)
+        head += "" if self.contrast is None else ", contrast=%r" % (self.contrast,)
+        head += "" if self.lowres is None else ", lowres=%r" % (self.lowres,)
         return head + ")"
 
 
@@ -209,7 +254,7 @@ def rotation_zoom_matrix(angles_deg, zoom=1.0):
 
 
 def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7,
-                blur=0.0, noise=0.0, gamma=0.0):
+                blur=0.0, noise=0.0, gamma=0.0, bias=0.0, bias_grid=4, contrast=0.0, lowres=0.0):
     """Parameters of sample `index` in `epoch`: a pure function of the arguments, drawn from default_rng([seed, epoch, index]).  The
     origin is drawn first, by random_crop_origin's calls, so with augmentation off it is the origin NpzBraTS / SyntheticBraTS pick.
     flip: three uniforms, each < 0.5 flipping that axis; intensity f > 0: scale ~ U(1-f, 1+f)[4], then shift ~ U(-f, f)[4] (float32).
@@ -219,7 +264,10 @@ def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotat
     no earlier field depends on them, the intensity stage, each transform switching a channel on where its u < 0.5 and making all its
     draws whatever the outcome: blur s (0, or 0.5 <= s <= 1.5): u = random(4), sigma ~ U(0.5, s)[4]; noise n > 0: u = random(4),
     sigma ~ U(0, n)[4], noise_key = integers(0, 2^63); gamma g (0 < g < 1): u = random(4), exponent ~ U(1-g, 1+g)[4].  A channel that
-    is off has the value 0; a transform that is off is None."""
+    is off has the value 0; a transform that is off is None.  Last, in the same manner, the acquisition stage: bias b (0 < b <= 1):
+    u = random(4), a ~ U(-b, b)[4, g, g, g] with g = bias_grid, the control multipliers float32(exp(a)) (float64 exp: the field is
+    positive without an exponential on the device), bias_mask = u < 0.5; contrast k (0 < k < 1): u = random(4), factor ~ U(1-k, 1+k)[4];
+    lowres z (0.5 <= z < 1): u = random(4), zoom ~ U(z, 1)[4] (a zoom that float32 rounds to 1 becomes the float32 below 1)."""
     rng = np.random.default_rng([int(seed), int(epoch), int(index)])
     origin = random_crop_origin(tuple(full), tuple(crop), rng)
     r, z = float(rotate), float(scale)
@@ -255,7 +303,28 @@ def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotat
     if g > 0.0:
         u, ex = rng.random(4), rng.uniform(1.0 - g, 1.0 + g, 4)
         gm = np.where(u < 0.5, ex, 0.0).astype(np.float32)
-    return AugParams(origin, fl, scale, shift, matrix, disp, blur=bl, noise=ns, noise_key=key, gamma=gm)
+    b, bg, k, zmin = float(bias), int(bias_grid), float(contrast), float(lowres)
+    if not 0.0 <= b <= 1.0:
+        raise ValueError("draw_params: bias takes a half-width of the log multiplier in [0, 1], got %r" % (bias,))
+    if b > 0.0 and not ELASTIC_GRID_MIN <= bg <= ELASTIC_GRID_MAX:
+        raise ValueError("draw_params: bias_grid takes %d..%d control points per axis, got %r" % (ELASTIC_GRID_MIN, ELASTIC_GRID_MAX, bias_grid))
+    if not 0.0 <= k < 1.0:
+        raise ValueError("draw_params: contrast takes a half-width in [0, 1), got %r" % (contrast,))
+    if zmin != 0.0 and not 0.5 <= zmin < 1.0:
+        raise ValueError("draw_params: lowres takes 0 or a smallest zoom in [0.5, 1), got %r" % (lowres,))
+    bf = bm = ct = lr = None
+    if b > 0.0:
+        u, a = rng.random(4), rng.uniform(-b, b, (4, bg, bg, bg))
+        bf, bm = np.exp(a).astype(np.float32), tuple(bool(v) for v in u < 0.5)
+    if k > 0.0:
+        u, fc = rng.random(4), rng.uniform(1.0 - k, 1.0 + k, 4)
+        ct = np.where(u < 0.5, fc, 0.0).astype(np.float32)
+    if zmin > 0.0:
+        u, zm = rng.random(4), rng.uniform(zmin, 1.0, 4)
+        zm = np.minimum(zm.astype(np.float32), np.nextafter(np.float32(1.0), np.float32(0.0)))
+        lr = np.where(u < 0.5, zm, np.float32(0.0)).astype(np.float32)
+    return AugParams(origin, fl, scale, shift, matrix, disp, blur=bl, noise=ns, noise_key=key, gamma=gm, bias=bf, bias_mask=bm,
+                     contrast=ct, lowres=lr)
 
 
 _Q_MAX = np.float32(2.0 ** 30)      # |q| at and beyond it (and NaN): the voxel lies outside every volume
@@ -467,6 +536,83 @@ def _intensity_stage_cpu(x, p):
     return x
 
 
+def bias_field(grid, crop):
+    """m [*crop] float32 of the statement in _acquisition_stage_cpu for one channel's control multipliers grid [G0, G1, G2]: the
+    spline of _elastic_disp at the unflipped crop index, the nested sums taken axis by axis as there"""
+    w, idx = zip(*(_spline_axis(crop[d], False, grid.shape[d]) for d in range(3)))
+
+    def sum4(term):
+        return ((term(0) + term(1)) + term(2)) + term(3)
+
+    a = sum4(lambda j: w[2][:, j] * grid[:, :, idx[2][:, j]])                                    # [G0, G1, C2]
+    b = sum4(lambda j: w[1][:, j, None] * a[:, idx[1][:, j], :])                                 # [G0, C1, C2]
+    return sum4(lambda j: w[0][:, j, None, None] * b[idx[0][:, j], :, :]).astype(np.float32)     # [C0, C1, C2]
+
+
+def lowres_lattice(crop, zoom):
+    """(n_0, n_1, n_2): n_d = min(C_d, max(1, floor(float64(C_d) * zoom + 0.5))) for the float32 zoom"""
+    z = float(np.float32(zoom))
+    return tuple(min(int(c), max(1, int(math.floor(float(c) * z + 0.5)))) for c in crop)
+
+
+def _lowres_axis(C, n):
+    """(lo int64 [C], hi int64 [C], t float32 [C]): the crop indices of the two taps and the fraction, along one axis of C voxels
+    interpolated back from n lattice points"""
+    f32 = np.float32
+    r = f32(n) / f32(C)
+    u = (np.arange(C, dtype=np.int64).astype(f32) + f32(0.5)) * r - f32(0.5)
+    u = np.minimum(np.maximum(u, f32(0.0)), f32(n - 1)).astype(f32)
+    k = np.maximum(np.minimum(np.floor(u).astype(np.int64), n - 2), 0)
+    t = (u - k.astype(f32)).astype(f32)
+    k1 = np.minimum(k + 1, n - 1)
+    return ((2 * k + 1) * C) // (2 * n), ((2 * k1 + 1) * C) // (2 * n), t
+
+
+def _acquisition_stage_cpu(x, p):
+    """The acquisition stage on the prepared crop x [4, C0, C1, C2] (numpy float32, changed in place), before _intensity_stage_cpu;
+    every operation a float32 round-to-nearest one in the association written.  With V = C0*C1*C2 and p = (p0, p1, p2) the crop
+    voxel, per channel c, in this order (all three are this project's definitions):
+      bias field (bias_mask[c]): x = x * m(p), m(p) = sum_j0 w0[j0] * (sum_j1 w1[j1] * (sum_j2 w2[j2] * bias[c][i0+j0][i1+j1][i2+j2]))
+          with the weights, clamped control indices and ((a + b) + c) + d sums of _resample_cpu's D_c at the unflipped crop index
+          (bias_field).  The weights are non-negative and sum to 1 within rounding, so m lies between the smallest and the largest
+          control multiplier up to a few ulps: smooth and positive.
+      contrast (contrast[c] = f > 0): S = the float64 sum of the channel, mean = float32(S / V); mn, mx the NaN-ignoring minimum and
+          maximum; when mean is finite: x = min(max(((x - mean) * f) + mean, mn), mx)
+      low resolution (lowres[c] = z in [0.5, 1)): the lattice n = lowres_lattice(crop, z); lattice point k along axis d samples crop
+          index s_d(k) = ((2k + 1) * C_d) // (2 * n_d); back to the crop, r_d = float32(n_d) / float32(C_d),
+          u = (float32(p_d) + 0.5) * r_d - 0.5 clamped to [0, n_d - 1], k = min(floor(u), n_d - 2) (0 when n_d == 1), t = u - k, taps
+          s_d(k) and s_d(min(k + 1, n_d - 1)); lerp(a, b, t) = a + t*(b - a) along axis 2, then 1, then 0, over the channel as the
+          contrast step left it.  With n_d == C_d the taps are p_d and p_d + 1 and t = 0, except at p_d = C_d - 1 > 0, where they are
+          p_d - 1 and p_d and t = 1: the step returns a + 0*(b - a) = a (finite values; -0.0 may become 0.0), and a + (b - a) on those
+          last planes, which is b up to one rounding of b - a.
+    A step that is off leaves the channel's bits alone.  The device differs from this only in S: its float64 sum is taken in another
+    (fixed) order than numpy's, so a contrast-mapped channel is bit-equal where the sum is exact and bounded otherwise
+    (tests/test_acquisition_prepare_gpu.py)."""
+    crop = tuple(int(n) for n in x.shape[1:])
+    V = int(x[0].size)
+    f32 = np.float32
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for c in range(4):
+            if p.bias_mask[c]:
+                x[c] = x[c] * bias_field(p.bias[c], crop)
+            if p.contrast is not None and p.contrast[c] > 0.0:
+                mean = f32(x[c].astype(np.float64).sum() / V)
+                mn, mx = np.fmin.reduce(x[c], axis=None), np.fmax.reduce(x[c], axis=None)
+                if np.isfinite(mean):
+                    x[c] = np.minimum(np.maximum(((x[c] - mean) * f32(p.contrast[c])) + mean, mn), mx)
+            if p.lowres is not None and p.lowres[c] > 0.0:
+                (l0, h0, t0), (l1, h1, t1), (l2, h2, t2) = (_lowres_axis(C, n) for C, n in zip(crop, lowres_lattice(crop, p.lowres[c])))
+                a = x[c]
+
+                def lerp(lo, hi, t):
+                    return lo + t * (hi - lo)
+
+                a = lerp(a[:, :, l2], a[:, :, h2], t2[None, None, :]).astype(f32)
+                a = lerp(a[:, l1, :], a[:, h1, :], t1[None, :, None]).astype(f32)
+                x[c] = lerp(a[l0], a[h0], t0[:, None, None]).astype(f32)
+    return x
+
+
 def _prepare_one_cpu(img, lab, p, crop):
     if p.matrix is not None or p.disp is not None:
         x, t = _resample_cpu(img, lab, p, crop)
@@ -480,6 +626,8 @@ def _prepare_one_cpu(img, lab, p, crop):
     if p.scale is not None:
         x = x * torch.tensor(p.scale, dtype=torch.float32).reshape(4, 1, 1, 1)
         x = x + torch.tensor(p.shift, dtype=torch.float32).reshape(4, 1, 1, 1)
+    if p.acquisition_stage():
+        x = torch.from_numpy(_acquisition_stage_cpu(np.array(x.numpy(), dtype=np.float32, order="C"), p))
     if p.intensity_stage():
         x = torch.from_numpy(_intensity_stage_cpu(np.array(x.numpy(), dtype=np.float32, order="C"), p))
     t[t == 4] = 3
@@ -490,8 +638,9 @@ def prepare_batch(images, labels, params, crop, out=None):
     """(x [B,4,*crop] float32, target [B,*crop] int64, edge [B,*crop] int64) from source volumes images[b] float32 [4,S0,S1,S2] and
     labels[b] uint8 [S0,S1,S2] (values 0..4): crop_pad at params[b].origin (with params[b].matrix or .disp: the resampled crop of
     _resample_cpu, any origin) -> torch.flip of the flipped crop axes -> x * scale then + shift in float32 -> label 4 -> 3 ->
-    utils.synthetic.edge_codes; with params[b].blur / .noise / .gamma the intensity stage
-    (_intensity_stage_cpu) then acts on x.  On GPU tensors this is one HIP launch per eight samples, plus the stage's when it is on
+    utils.synthetic.edge_codes; with params[b].bias / .contrast / .lowres the acquisition stage (_acquisition_stage_cpu) then acts
+    on x (bit-equal on the GPU except contrast-mapped channels, whose mean comes from another summation order); with
+    params[b].blur / .noise / .gamma the intensity stage (_intensity_stage_cpu) acts on x after it.  On GPU tensors this is one HIP launch per eight samples, plus the stage's when it is on
     (HipBackend.prepare_batch, bit-equal to the CPU statement except gamma-mapped channels); on CPU tensors it is the CPU statement itself.  out: (x, target, edge)
     to write into (sample stride free, samples contiguous)."""
     crop = tuple(int(c) for c in crop)
@@ -575,7 +724,7 @@ class NpzCropSource(Dataset):
     item is instead the part of the volume the resampled crop reads (staged_box: shapes differ from item to item); flip and
     intensity are taken only because they move the matrix's place in draw_params' stream.  DeviceBraTS's blur / noise / gamma are not
     taken: draw_params draws them after the matrix and the grid, so they move nothing this class reads, and they act on the prepared
-    crop only, so the item is the same with and without them."""
+    crop only, so the item is the same with and without them; the same holds for its bias / contrast / lowres, drawn last of all."""
 
     def __init__(self, subjects, crop, seed=1000, normalize=False, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0,
                  elastic_grid=7):
@@ -648,6 +797,9 @@ class DeviceBraTS:
     launch; elastic (voxels) > 0 deforms it by a cubic B-spline of elastic_grid^3 control displacements ~ U(-elastic, elastic).
     blur (largest sigma, 0.5..1.5) / noise (largest sigma) / gamma (half-width of the exponent's range about 1) > 0 switch the
     intensity stage on per channel (draw_params), which runs on the prepared crop in launches of its own.
+    bias (half-width of the log multiplier, with bias_grid^3 control points) / contrast (half-width of the factor's range about 1) /
+    lowres (smallest zoom of the coarse lattice, 0.5 <= z < 1) > 0 switch the acquisition stage on per channel, which runs between
+    the two: bias field, contrast, low-resolution simulation (_acquisition_stage_cpu).
       cache=True   every subject is loaded once onto the device (fp32 image, uint8 label, optionally z-scored by normalize_nonzero)
       cache=False  "staged": NpzCropSource crops in DataLoader workers (batches()), the crops are uploaded from pinned memory and
                    prepared at origin 0 -- 36 MB per 128^3 sample over the host link instead of a whole subject.  With rotate /
@@ -655,13 +807,17 @@ class DeviceBraTS:
                    the batch is bit-equal to cache=True."""
 
     def __init__(self, source, device, crop=(128, 128, 128), seed=1000, flip=False, intensity=0.0, normalize=False, cache=True,
-                 list_file=None, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7, blur=0.0, noise=0.0, gamma=0.0):
+                 list_file=None, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7, blur=0.0, noise=0.0, gamma=0.0, bias=0.0,
+                 bias_grid=4, contrast=0.0, lowres=0.0):
         self.device = torch.device(device)
         self.crop, self.seed, self.epoch = tuple(int(c) for c in crop), int(seed), 0
         self.flip, self.intensity, self.normalize, self.cache = bool(flip), float(intensity), bool(normalize), bool(cache)
         self.rotate, self.scale = float(rotate), float(scale)
         self.elastic, self.elastic_grid = float(elastic), int(elastic_grid)
         self.blur, self.noise, self.gamma = float(blur), float(noise), float(gamma)
+        self.bias, self.bias_grid, self.contrast, self.lowres = float(bias), int(bias_grid), float(contrast), float(lowres)
+        if self.bias > 0.0 and not ELASTIC_GRID_MIN <= self.bias_grid <= ELASTIC_GRID_MAX:
+            raise ValueError("DeviceBraTS: bias_grid takes %d..%d control points per axis" % (ELASTIC_GRID_MIN, ELASTIC_GRID_MAX))
         if self.elastic > 0.0 and not ELASTIC_GRID_MIN <= self.elastic_grid <= ELASTIC_GRID_MAX:
             raise ValueError("DeviceBraTS: elastic_grid takes %d..%d control points per axis" % (ELASTIC_GRID_MIN, ELASTIC_GRID_MAX))
         self.affine = self.rotate > 0.0 or self.scale > 0.0 or self.elastic > 0.0      # the crop is resampled
@@ -721,7 +877,8 @@ class DeviceBraTS:
 
     def params(self, i):
         return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity, self.rotate, self.scale,
-                           self.elastic, self.elastic_grid, self.blur, self.noise, self.gamma)
+                           self.elastic, self.elastic_grid, self.blur, self.noise, self.gamma, self.bias, self.bias_grid, self.contrast,
+                           self.lowres)
 
     def _missing(self, n):
         return torch.zeros((n, 4), dtype=torch.bool, device=self.device)

@@ -668,6 +668,53 @@ struct cwf_intensity_sample {
  * set, overlapping src and dst as above, gamma on with ws null or ws_floats too small; CWF_E_TOOLARGE: 2^31 voxels or more. */
 int cwf_augment_intensity(const struct cwf_intensity_sample* h_samples, int B, int C0, int C1, int C2, const float* src,
                           int64_t src_bstride, float* dst, int64_t dst_bstride, float* ws, int64_t ws_floats, void* stream);
+/* The acquisition stage of one prepared sample x [4][C0][C1][C2] (utils/data.py: bias field, contrast, low-resolution simulation).
+ * bias_mask / contrast_mask / lowres_mask are 4-bit channel masks (bit c = channel c).  bias[c] is DEVICE memory, the control
+ * multipliers of channel c, fp32 [G0][G1][G2] (4-byte aligned, 4 <= G_d <= 8, one grid shape for the sample's channels), read when
+ * the kernel runs; factor[c] is the contrast factor; lattice[c][d] the extent n_d of channel c's coarse lattice along axis d.  Values
+ * of a channel whose bit is off are not used. */
+struct cwf_acquire_sample {
+  const float* bias[4];
+  int G0, G1, G2;
+  int bias_mask, contrast_mask, lowres_mask;
+  float factor[4];
+  int lattice[4][3];
+};
+#define CWF_ACQUIRE_T0 32   /* voxels per workgroup along axis 0, 1, 2: one (float64 sum, min, max) partial per such tile */
+#define CWF_ACQUIRE_T1 8
+#define CWF_ACQUIRE_T2 32
+/* dst[b][c] = the stage applied to src[b][c], for each of the B samples (h_samples is HOST memory, passed by value, eight samples
+ * per launch: the call can be captured).  It runs after a prepare entry and before cwf_augment_intensity.  With V = C0*C1*C2, p =
+ * (p0, p1, p2) the crop voxel and every operation a float32 round-to-nearest one in the association written (no fused
+ * multiply-add), per channel c, in this order:
+ *   bias (bit c of bias_mask):  x = x * m(p),  m(p) = sum_j0 w[0][j0] * (sum_j1 w[1][j1] * (sum_j2 w[2][j2] * bias[c][..][..][..]))
+ *           with the weights w, the clamped control indices and the ((a + b) + c) + d sums of cwf_prepare_batch_elastic's D_c, taken
+ *           at the crop index p itself (no flip: the stage acts on the finished crop)
+ *   contrast (bit c of contrast_mask):  S = the float64 sum of the channel after the bias step, mean = float(S / V); mn, mx the
+ *           NaN-ignoring minimum and maximum; mean not finite: nothing; otherwise
+ *           x = fminf(fmaxf(((x - mean) * factor[c]) + mean, mn), mx).  S is formed from one float64 partial per tile of
+ *           T0 x T1 x T2 voxels, each summed and then all reduced in a fixed order: the same input gives the same bits on every
+ *           run, but S is not tied to any other summation order, so the result is bit-defined only where the float64 sum is exact.
+ *   lowres (bit c of lowres_mask), n_d = lattice[c][d]:  lattice point k along axis d samples crop index s_d(k) = ((2k + 1) * C_d) /
+ *           (2 * n_d) (integer division); r_d = float(n_d) / float(C_d) (correctly rounded), u = (float(p_d) + 0.5) * r_d - 0.5
+ *           clamped to [0, float(n_d - 1)], k = min(floor(u), n_d - 2) (0 when n_d == 1), t = u - float(k), taps s_d(k) and
+ *           s_d(min(k + 1, n_d - 1)); lerp(a, b, t) = a + t*(b - a) along axis 2, then 1, then 0, over the eight taps of the channel
+ *           as the contrast step left it.  No coarse volume is formed.  (n_d == C_d gives t = 0 and tap p_d itself everywhere but
+ *           at p_d = C_d - 1 > 0, where t = 1 and the result is a + (b - a).)
+ * A channel with a bit off keeps its bits through that step.
+ * Buffers: src and dst have their own sample strides (elements).  Without a lowres bit anywhere they may be the same buffer with
+ * the same stride (in place) or disjoint, and src is only read.  With a lowres bit set anywhere they must be disjoint, and src is
+ * also WRITTEN: a channel whose lowres bit is set gets its bias and contrast steps in place in src, from where the gather reads
+ * its taps; the other channels of src are left alone.  Any other overlap is refused.  ws: device scratch of at least 12 * B * tiles
+ * doubles (8-byte aligned), tiles = ceil(C0/T0) * ceil(C1/T1) * ceil(C2/T2), read and written only when some contrast bit is set.
+ * Launches per eight samples: the partials (only with a contrast bit), the pointwise store (bias, contrast, copies), the gather
+ * (only with a lowres bit).  Nothing is copied host to device and nothing synchronises with the host.
+ * CWF_E_BADARG, before any launch: B or a crop extent <= 0, a null or misaligned pointer (src / dst 4 B, ws 8 B, a grid whose bit
+ * is set 4 B), a stride smaller than one sample, a mask outside 0..15, some G_d outside 4..8 in a sample with a bias bit, a factor
+ * that is not finite or not > 0 where its bit is set, a lattice entry outside [1, C_d] where its bit is set, overlapping src and dst
+ * as above, contrast on with ws null or ws_doubles too small; CWF_E_TOOLARGE: 2^31 voxels or more. */
+int cwf_augment_acquisition(const struct cwf_acquire_sample* h_samples, int B, int C0, int C1, int C2, float* src,
+                            int64_t src_bstride, float* dst, int64_t dst_bstride, double* ws, int64_t ws_doubles, void* stream);
 /* In place on one subject image fp32 [4][V]: over the voxels whose ((x0 + x1) + x2) + x3 > 0 (float32), each channel becomes
  * float32((x - mean_c) / std_c) with the float64 mean and population std of that channel over those voxels (two passes); other voxels,
  * and channels with std 0, are untouched.  ws: CWF_NORM_WS_DOUBLES doubles of device scratch. */

@@ -319,6 +319,7 @@ class _ConvFn(torch.autograd.Function):
                     link.sums = K.new_stats(x.shape[0], spec.cin, x.device)
                     dx = K.conv(pk.dgrad_op(spec.op), dy, spec.packed(True), None, spec.cin, out=dxa, w_ref=w, fwd_op=spec.op, residual=dcarry,
                                 stats=link.sums, nb=(link.g, link.scale, link.shift, link.slope), **kw16)
+                    link.dy = dx                         # the sums are those of THIS tensor (see _NormActAddFn.backward)
                 else:
                     dx = K.conv(pk.dgrad_op(spec.op), dy, spec.packed(True), None, spec.cin, out=dxa, w_ref=w, fwd_op=spec.op, residual=dcarry, **kw16)
         elif dcarry is not None:
@@ -563,11 +564,11 @@ class NaaLink:
     """Connects a block tail y = act(IN(g)) + x (norm_act_add) with the ONE conv that consumes y: that conv's data gradient
     produces dL/dy, and its epilogue can accumulate the two InstanceNorm-backward sums of the tail (sum dy act', sum dy act' ghat)
     while the values are in registers -- the tail's backward then skips its reduction pass over (dy, g)."""
-    __slots__ = ("g", "scale", "shift", "slope", "sums", "claimed", "shared")
+    __slots__ = ("g", "scale", "shift", "slope", "sums", "dy", "claimed", "shared")
 
     def __init__(self, g, scale, shift, slope):
         self.g, self.scale, self.shift, self.slope = g, scale, shift, slope
-        self.sums, self.claimed, self.shared = None, False, False
+        self.sums, self.dy, self.claimed, self.shared = None, None, False, False
 
 
 class _NormActAddFn(torch.autograd.Function):
@@ -590,8 +591,13 @@ class _NormActAddFn(torch.autograd.Function):
         x, scale, shift = ctx.saved_tensors
         link = ctx.link
         K = backend()
-        if link is not None and link.sums is not None and not link.shared:
-            sums, link.sums = link.sums, None        # from the consuming conv's data-gradient epilogue (this backward pass)
+        sums = made_for = None
+        if link is not None:
+            sums, made_for, link.sums, link.dy = link.sums, link.dy, None, None
+        # the sums from the consuming conv's data-gradient epilogue (this backward pass) are the tail's only if that conv's dx is the
+        # tail's WHOLE dL/dy: a consumer conv() never saw (the loss, any torch op) makes autograd hand over the sum of both gradients, a
+        # new tensor (never the conv's dx accumulated in place: the link holds a reference to it) -- the tail then reduces for itself
+        if sums is not None and not link.shared and made_for is not None and (dy is made_for or dy.data_ptr() == made_for.data_ptr()):
             if ctx.up16 and "dx" in getattr(K, "APPLY_EMITS", ()):
                 only16 = ctx.up16 == "only" and ctx.single and active_sink() is not None
                 dx, dx16, _ = K.in_bwd_apply16(dy, x, scale, shift, ctx.slope, sums, want_dx16=True, need_f32=not only16)

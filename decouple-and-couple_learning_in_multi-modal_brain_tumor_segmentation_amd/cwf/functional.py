@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import packing as pk
-from .kernels import backend, precision
+from .kernels import REGION_MASKS, backend, precision
 
 
 def active_sink():
@@ -906,3 +906,45 @@ def dice_ce_loss(prob_ncdhw, label, posmask=0):
     if label.dtype != torch.int64:
         label = label.long()
     return _DiceCeFn.apply(to_channels_last_view(prob_ncdhw), label, int(posmask))
+
+
+class _BoundaryLossFn(torch.autograd.Function):
+    """mean over (sample, region, voxel) of phi_r * p_r, times a device-resident weight (csrc/boundary.hip)."""
+
+    @staticmethod
+    def forward(ctx, prob_cl, phi, posmasks, weight):
+        loss, coef = backend().boundary_loss(prob_cl, phi, posmasks, weight)
+        ctx.posmasks = posmasks
+        ctx.save_for_backward(prob_cl, phi, coef)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        prob_cl, phi, coef = ctx.saved_tensors
+        gs = g.reshape(1).to(torch.float32).contiguous()
+        return backend().boundary_loss_bwd(prob_cl, phi, ctx.posmasks, coef, gs), None, None, None
+
+
+def boundary_weight_tensor(weight, device):
+    """float or one-element tensor -> the one-float32 device tensor the boundary kernels read (a tensor already of that kind is
+    returned as it is, so a caller can change the weight in place between steps of a captured plan)"""
+    if isinstance(weight, torch.Tensor):
+        if weight.numel() != 1:
+            raise ValueError("boundary weight must have one element, got shape %s" % (tuple(weight.shape),))
+        if weight.dtype == torch.float32 and weight.device == torch.device(device) and weight.dim() == 1:
+            return weight
+        return weight.detach().reshape(1).to(device=device, dtype=torch.float32)
+    return torch.full((1,), float(weight), dtype=torch.float32, device=device)
+
+
+def boundary_loss(prob_ncdhw, label, posmasks=REGION_MASKS, weight=1.0, phi=None):
+    """Boundary loss of Kervadec et al.: weight * mean over (sample, region, voxel) of phi_r * p_r, p_r the summed probability of the
+    region's classes and phi_r the signed distance to the region's boundary in `label` (int64 [N,D,H,W]).  phi: precomputed maps
+    [N,R,D,H,W] (backend().signed_distance), else computed here.  weight: float or one-element device tensor."""
+    posmasks = tuple(int(m) for m in posmasks)
+    if phi is None:
+        label = label.contiguous()
+        if label.dtype != torch.int64:
+            label = label.long()
+        phi = backend().signed_distance(label, posmasks)
+    return _BoundaryLossFn.apply(to_channels_last_view(prob_ncdhw), phi.contiguous(), posmasks, boundary_weight_tensor(weight, prob_ncdhw.device))

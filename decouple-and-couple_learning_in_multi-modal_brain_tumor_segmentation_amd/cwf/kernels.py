@@ -18,6 +18,8 @@ from . import _lib
 from . import packing as pk
 
 _f32 = torch.float32
+# the evaluation's regions as class bitmasks (bit c = class c belongs): WT = {1, 2, 3}, TC = {1, 3}, ET = {3}
+REGION_MASKS = (0b1110, 0b1010, 0b1000)
 
 
 def cl(t: torch.Tensor):
@@ -1130,6 +1132,59 @@ class HipBackend:
         dprob = torch.empty_like(prob)
         self._call("cwf_dice_ce_bwd", prob.data_ptr(), label.data_ptr(), posmask, coef.data_ptr(), gscale.data_ptr(), dprob.data_ptr(),
                    n, d * h * w, c, self._stream())
+        return dprob
+
+    # ------------------------------------------------------------------ L2 (boundary loss)
+    @staticmethod
+    def _posmasks(name, posmasks):
+        masks = tuple(int(m) for m in posmasks)
+        if any(m < 0 or m > 0xFFFFFFFF for m in masks):
+            raise ValueError("%s: a region is a 32-bit class bitmask, got %r" % (name, posmasks))
+        return masks, (ctypes.c_uint32 * max(len(masks), 1))(*masks)
+
+    def signed_distance(self, label, posmasks=REGION_MASKS):
+        """label int64 [N, D0, D1, D2] -> phi float32 [N, R, D0, D1, D2]: the exact Euclidean signed distance map of every region
+        (class bitmask) of `posmasks`, sqrt(q) outside and 1 - sqrt(q) inside, rounded once from float64; zeros where a region is empty
+        or fills the volume (cwf_signed_distance).  No host synchronisation: the workspace comes from torch's allocator."""
+        if label.dim() != 4 or label.dtype != torch.int64 or not label.is_cuda:
+            raise ValueError("signed_distance: label must be an int64 [N, D0, D1, D2] tensor on the GPU")
+        masks, cm = self._posmasks("signed_distance", posmasks)
+        label = label.contiguous()
+        n, d0, d1, d2 = (int(s) for s in label.shape)
+        nbytes = self.lib.cwf_signed_distance_workspace(n, len(masks), d0, d1, d2)
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_signed_distance_workspace failed with status %d (N=%d R=%d %dx%dx%d)" % (nbytes, n, len(masks), d0, d1, d2))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=label.device)
+        phi = torch.empty((n, len(masks), d0, d1, d2), dtype=_f32, device=label.device)
+        self._call("cwf_signed_distance", label.data_ptr(), ctypes.addressof(cm), phi.data_ptr(), n, len(masks), d0, d1, d2, ws.data_ptr(),
+                   self._stream())
+        return phi
+
+    def boundary_loss(self, prob, phi, posmasks, weight):
+        """prob [N,D0,D1,D2,C] dense channels-last, phi [N,R,D0,D1,D2], weight a one-float device tensor -> (loss [1], coef [1])"""
+        masks, cm = self._posmasks("boundary_loss", posmasks)
+        n, c = int(prob.shape[0]), int(prob.shape[-1])
+        v = int(prob[0, ..., 0].numel())
+        if tuple(phi.shape) != (n, len(masks)) + tuple(prob.shape[1:4]) or phi.dtype != _f32 or prob.dtype != _f32:
+            raise ValueError("boundary_loss: phi must be float32 [N, R, D0, D1, D2] for prob [N, D0, D1, D2, C], got %s and %s"
+                             % (tuple(phi.shape), tuple(prob.shape)))
+        if weight.numel() != 1 or weight.dtype != _f32 or weight.device != prob.device:
+            raise ValueError("boundary_loss: weight must be a one-element float32 tensor on the device of prob")
+        assert prob.is_contiguous() and phi.is_contiguous()
+        s = self._zeros_f64((1,), prob.device)
+        self._call("cwf_boundary_sums", prob.data_ptr(), phi.data_ptr(), ctypes.addressof(cm), s.data_ptr(), n, len(masks), v, c, self._stream())
+        loss = torch.empty(1, dtype=_f32, device=prob.device)
+        coef = torch.empty(1, dtype=_f32, device=prob.device)
+        self._call("cwf_boundary_finalize", s.data_ptr(), weight.data_ptr(), loss.data_ptr(), coef.data_ptr(), n, len(masks), v, self._stream())
+        return loss, coef
+
+    def boundary_loss_bwd(self, prob, phi, posmasks, coef, gscale):
+        """-> dprob like prob: (gscale * coef) * (sum of phi over the regions holding the class)"""
+        masks, cm = self._posmasks("boundary_loss_bwd", posmasks)
+        n, c = int(prob.shape[0]), int(prob.shape[-1])
+        dprob = torch.empty_like(prob)
+        self._call("cwf_boundary_bwd", phi.data_ptr(), ctypes.addressof(cm), coef.data_ptr(), gscale.data_ptr(), dprob.data_ptr(), n, len(masks),
+                   int(prob[0, ..., 0].numel()), c, self._stream())
         return dprob
 
     def head_loss(self, logits, label, posmasks, scale):

@@ -33,9 +33,13 @@ Step controls (all off by default; then the step issues exactly the launches des
     (SURVEY.md F2).  Accumulate and fold launches are never captured: the captured step is the same for every micro-step.
   * max_grad_norm: the averaged gradient is clipped by its global norm inside the Adam launch (cwf.optim); no host sync.
   * ema_decay: the Adam launch also maintains an EMA copy of the weights (ema_state_dict() for validation / checkpoints).
+  * boundary_weight = w: a sixth loss term, w * boundary loss of the main output (tools.boundary_loss: signed distance maps of the
+    target's WT / TC / ET computed on the device every step), in front of the same backward.  w lives in a one-float device tensor
+    that the kernels read, so set_boundary_weight() between steps needs no recapture.  None: the step makes no new call.
 Checkpoints use the reference layout {'epoch', 'state_dict' with 'module.' prefix, 'optim_dict'} (:248-253)."""
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -44,13 +48,34 @@ import torch.distributed as dist
 from .optim import FusedAdam, poly_lr
 
 
-def total_loss(outputs, target, edge):
+def total_loss(outputs, target, edge, boundary=None):
+    """The reference's five terms; with `boundary` (the one-float device tensor holding the boundary weight) a sixth part,
+    tools.boundary_loss(outputs[0], target) at that weight, is appended and added to the total."""
     from models import criterions
     from utils import tools
     parts = [criterions.softmax_dice(outputs[0], target), tools.get_separate_loss(outputs[1], target),
              tools.get_edge_separate_loss(outputs[2], edge), tools.get_separate_loss(outputs[3], target),
              tools.get_edge_separate_loss(outputs[4], edge)]
-    return parts[0] + parts[1] + parts[2] + parts[3] + parts[4], parts
+    total = parts[0] + parts[1] + parts[2] + parts[3] + parts[4]
+    if boundary is not None:
+        parts.append(tools.boundary_loss(outputs[0], target, weight=boundary))
+        total = total + parts[5]
+    return total, parts
+
+
+def check_boundary_weight(w):
+    """None (term off) or a finite float >= 0"""
+    if w is None:
+        return None
+    w = float(w)
+    if not math.isfinite(w) or w < 0.0:
+        raise ValueError("boundary_weight must be None or a finite number >= 0, got %r" % (w,))
+    return w
+
+
+def boundary_schedule(weight, epoch, warmup):
+    """--boundary_weight A / --boundary_warmup E: A * min(1, epoch / E), E = 0 meaning constant"""
+    return float(weight) if warmup <= 0 else float(weight) * min(1.0, float(epoch) / float(warmup))
 
 
 def kernels_backend():
@@ -60,7 +85,10 @@ def kernels_backend():
 
 class Trainer:
     def __init__(self, model, lr=2e-4, weight_decay=1e-5, amsgrad=True, end_epoch=1000, use_graph=False,
-                 graph_warmup=2, overlap_comm=True, wgrad_async=True, accum_steps=1, max_grad_norm=None, ema_decay=None):
+                 graph_warmup=2, overlap_comm=True, wgrad_async=True, accum_steps=1, max_grad_norm=None, ema_decay=None,
+                 boundary_weight=None):
+        self.boundary_weight = check_boundary_weight(boundary_weight)
+        self._boundary = None                           # the weight as a one-float device tensor, made at the first step that needs it
         self.model = model
         self.init_lr, self.end_epoch = lr, end_epoch
         if int(accum_steps) != accum_steps or accum_steps < 1:
@@ -160,7 +188,7 @@ class Trainer:
         K = kernels_backend()
         K.wgrad_async = self.wgrad_async       # (from the forward pass on: it prepares weight-gradient operands on the side stream)
         outputs = self.model(x, None)
-        loss, parts = total_loss(outputs, target, edge)
+        loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device))
         self.opt.zero_grad(set_to_none=True)
         if hasattr(K, "flush_every_default"):
             # graph modes: one reduce per phase, in warm-up too
@@ -186,6 +214,25 @@ class Trainer:
                 torch.cuda.current_stream().wait_stream(self._comm_stream)      # (a capture must end with its forked streams joined)
         return loss.detach(), [p.detach() for p in parts]
 
+    def _boundary_tensor(self, device):
+        if self.boundary_weight is None:
+            return None
+        if self._boundary is None:
+            if _capturing():
+                raise RuntimeError("the boundary weight tensor must exist before the step is captured")
+            self._boundary = torch.full((1,), self.boundary_weight, dtype=torch.float32, device=device)
+        return self._boundary
+
+    def set_boundary_weight(self, w):
+        """New weight of the boundary term from the next step on, in every step mode: the kernels read it from device memory, so a
+        captured step needs no recapture.  Only for a Trainer built with a boundary_weight (the captured step has the term or not)."""
+        w = check_boundary_weight(w)
+        if self.boundary_weight is None or w is None:
+            raise ValueError("the boundary term is switched on or off at construction (boundary_weight=...), not between steps")
+        self.boundary_weight = w
+        if self._boundary is not None:
+            self._boundary.fill_(w)
+
     def _finish_comm(self):
         if not self.comm:
             return
@@ -204,6 +251,7 @@ class Trainer:
         import ctypes
         import gc
         self._static = (x.clone(), target.clone(), edge.clone())
+        self._boundary_tensor(x.device)                 # (allocated and filled outside the capture)
         want_plan = self.graph_mode == "plan"
         g = torch.cuda.CUDAGraph(keep_graph=True) if want_plan else torch.cuda.CUDAGraph()
         # No cyclic garbage collection inside the capture.  A Trainer and its model form a cycle (model.phase_callback), so an earlier
@@ -276,7 +324,7 @@ class Trainer:
     def step(self, x, target, edge, epoch=0):
         """One optimisation step on a rank-local batch -- with accum_steps = N > 1 one MICRO-step: every N-th call updates the weights
         (learning rate of that call's epoch), the calls before it only accumulate.  Returns this batch's (loss, [five parts]) as
-        device tensors (no host sync)."""
+        device tensors (no host sync); six parts with a boundary_weight."""
         self._last_micro = self._micro + 1 >= self.accum_steps
         if self._last_micro:
             self.opt.param_groups[0]["lr"] = float(poly_lr(self.init_lr, epoch, self.end_epoch))   # plain float: checkpoints stay weights_only-loadable

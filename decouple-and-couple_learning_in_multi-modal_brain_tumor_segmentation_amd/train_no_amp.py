@@ -130,7 +130,33 @@ def build_parser():
                    help="0.5 <= d < 1: keep ema = d * ema + (1 - d) * weights, updated at every weight update (with --accum_steps N "
                         "once per window; iterations of a partial window dropped at the end of training never reach it); checkpoints "
                         "carry it as 'ema_state_dict' and --resume restores it when present.  Default: off")
+    p.add_argument("--boundary_weight", default=None, type=float,
+                   help="A >= 0: add A x the boundary loss of the main output (Kervadec et al. 2019: mean of signed distance to the "
+                        "ground-truth WT / TC / ET boundary x predicted probability of the region; distance maps computed on the device "
+                        "every step) to the five terms; the log line gains boundary_loss.  Default: off")
+    p.add_argument("--boundary_warmup", default=0, type=int,
+                   help="E >= 0: ramp the boundary weight linearly, A x min(1, epoch / E), set once per epoch; 0: constant A")
     return p
+
+
+def boundary_weight_at(args, epoch):
+    """the boundary weight of `epoch`: None with the term off, else A x min(1, epoch / E) (E = 0: A)"""
+    if args.boundary_weight is None:
+        return None
+    from cwf.trainer import boundary_schedule
+    return boundary_schedule(args.boundary_weight, epoch, args.boundary_warmup)
+
+
+def check_boundary(args):
+    """the values of --boundary_weight / --boundary_warmup (SystemExit with the rule, like the other checks)"""
+    if args.boundary_weight is not None and not 0.0 <= args.boundary_weight < float("inf"):
+        raise SystemExit("--boundary_weight takes a finite weight >= 0 (leave the flag out for no boundary term)")
+    if args.boundary_warmup < 0:
+        raise SystemExit("--boundary_warmup takes a number of epochs >= 0")
+    if args.boundary_warmup > 0 and args.boundary_weight is None:
+        raise SystemExit("--boundary_warmup ramps --boundary_weight: give that too")
+    if args.boundary_weight is not None and args.no_cuda:
+        raise SystemExit("--boundary_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
 
 
 def check_step_controls(args):
@@ -227,6 +253,7 @@ def main(argv=None):
     check_intensity_aug(args)
     check_acquisition_aug(args)
     check_step_controls(args)
+    check_boundary(args)
     from cwf import kernels
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint
@@ -269,8 +296,9 @@ def main(argv=None):
         log.info("re-training!!!")
     trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, amsgrad=args.amsgrad, end_epoch=args.end_epoch,
                       use_graph={"eager": False, "plan": "plan", "hipgraph": "hipgraph"}[args.step_mode] if use_cuda else False,
-                      accum_steps=args.accum_steps, max_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay)
-    clip, use_ema = args.clip_grad_norm is not None, args.ema_decay is not None
+                      accum_steps=args.accum_steps, max_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay,
+                      boundary_weight=boundary_weight_at(args, args.start_epoch))
+    clip, use_ema, use_boundary = args.clip_grad_norm is not None, args.ema_decay is not None, args.boundary_weight is not None
     if use_ema and os.path.isfile(args.resume) and args.load:
         ck = torch.load(args.resume, map_location="cpu", weights_only=True)
         if "ema_state_dict" in ck:
@@ -290,6 +318,8 @@ def main(argv=None):
     for epoch in range(args.start_epoch, args.end_epoch):
         if hasattr(ds, "set_epoch"):
             ds.set_epoch(epoch)
+        if use_boundary:
+            trainer.set_boundary_weight(boundary_weight_at(args, epoch))
         mine = shard_indices(len(ds), rank, world, epoch=epoch, shuffle=True, seed=args.seed)      # DistributedSampler semantics
         drop_last = args.step_mode != "eager" and use_cuda
         if device_data:
@@ -311,7 +341,7 @@ def main(argv=None):
                     ev.synchronize() if ev is not None else None
                     v = host.tolist()
                     log.info("Epoch: %d_Iter:%d  loss: %.5f || end_loss: %.5f || s_loss:%.4f || edge_loss:%.4f || mid_s_loss:%.4f || mid_edge_loss:%.4f ||"
-                             + (" grad_norm: %.4f" if clip else ""), tag[0], tag[1], *v)
+                             + (" boundary_loss: %.5f ||" if use_boundary else "") + (" grad_norm: %.4f" if clip else ""), tag[0], tag[1], *v)
                 # (grad_norm: of the last update -- inside an accumulation window that is the previous window's)
                 snap = torch.stack([loss] + list(parts) + ([trainer.opt.grad_norm] if clip else [])).float()
                 if use_cuda:

@@ -23,6 +23,13 @@ def dice_ce(output, target, num_cls=4, posmask=0):
     return CF.dice_ce_loss(output, target, posmask)
 
 
+def boundary_loss(output, target, posmasks=CF.REGION_MASKS, weight=1.0, phi=None):
+    """Boundary loss (Kervadec et al., MIDL 2019) of the probabilities output [B,C,D,H,W] against the label map target [B,D,H,W]:
+    weight * mean of (signed distance to the region's ground-truth boundary) * (probability of the region) over the regions
+    `posmasks` (class bitmasks; default WT, TC, ET).  Not in the reference; off unless asked for."""
+    return CF.boundary_loss(output, target, posmasks=posmasks, weight=weight, phi=phi)
+
+
 def _separate(output, target, masks):
     maps = [output[r] for r in ("01", "02", "04")]
     if all(isinstance(m, CF.LazyProb) for m in maps) and len({(m.scale, tuple(m.logit.shape)) for m in maps}) == 1:

@@ -399,6 +399,32 @@ int cwf_dice_ce_bwd(const float* prob, const int64_t* label, uint32_t posmask, c
                     float* dprob, int N, int64_t V, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * L2  boundary loss (Kervadec et al., MIDL 2019): dense exact signed distance maps of label maps + fused loss (csrc/boundary.hip)
+ *   label int64 [B][D0][D1][D2]; region r = class bitmask posmasks[r] (host memory, R values, copied into the launches): a voxel is in
+ *   G_r iff 0 <= label < 32 and (posmasks[r] >> label) & 1.  1 <= R <= 8, 1 <= D_d <= 512.
+ *   phi float [B][R][D0][D1][D2]: with q the exact integer squared Euclidean distance (unit spacing) to the nearest voxel of the other
+ *   side of G_r inside the volume, float32(sqrt((double)q)) outside G_r and float32(1.0 - sqrt((double)q)) inside; +0 throughout a
+ *   (sample, region) whose G_r is empty or fills the volume.  Exact: bit-equal to the float64 statement.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of device workspace cwf_signed_distance needs (6 bytes per voxel, sample and region, 256-B aligned), or a negative CWF_E_*:
+ * CWF_E_BADARG for B <= 0, R outside 1..8 or an extent outside 1..512; CWF_E_TOOLARGE for more than 2^31 - 1 workgroups. */
+int64_t cwf_signed_distance_workspace(int B, int R, int D0, int D1, int D2);
+/* Three launches, no host synchronisation, nothing read back, no kernel waits on another workgroup: capturable.  ws is fully rewritten
+ * (nothing needs zeroing).  CWF_E_BADARG as above and for a null pointer, before any launch; CWF_E_ALIGN: ws off 256 bytes. */
+int cwf_signed_distance(const int64_t* label, const uint32_t* posmasks, float* phi, int B, int R, int D0, int D1, int D2, void* ws,
+                        void* stream);
+/* prob float [N][V][C] channels-last, 1 <= C <= 32; p_r = float32 sum of prob[..][c] over the classes c < C of region r, increasing c.
+ * sum[0] (double, zeroed by the caller) += sum over n, r, v of (double)phi_r * (double)p_r. */
+int cwf_boundary_sums(const float* prob, const float* phi, const uint32_t* posmasks, double* sum, int N, int R, int64_t V, int C,
+                      void* stream);
+/* weight: one float in DEVICE memory.  loss[0] = float32((double)w / (N R V) * sum[0]);  coef[0] = k = float32((double)w / (N R V)). */
+int cwf_boundary_finalize(const double* sum, const float* weight, float* loss, float* coef, int N, int R, int64_t V, void* stream);
+/* dprob[n][v][c] = (gscale[0] * coef[0]) * s_c, s_c = float32 sum of phi_r over the regions r holding class c, increasing r, every
+ * product rounded on its own; +0 for a class in no region.  dprob is fully written. */
+int cwf_boundary_bwd(const float* phi, const uint32_t* posmasks, const float* coef, const float* gscale, float* dprob, int N, int R,
+                     int64_t V, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N1  sliding-window inference glue   predict_overlap.py:31-58 (tailor_and_concat), :134-141 + utils/tools.py:44-47,64-109
  *     and utils/hausdorff.py (Hausdorff distance / HD95)
  * ---------------------------------------------------------------------------------------------- */

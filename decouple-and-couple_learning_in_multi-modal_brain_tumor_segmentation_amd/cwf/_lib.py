@@ -110,6 +110,9 @@ SIGNATURES = {
     "cwf_boundary_sums": [P, P, P, P, I, I, L, I, P],
     "cwf_boundary_finalize": [P, P, P, P, I, I, L, P],
     "cwf_boundary_bwd": [P, P, P, P, P, I, I, L, I, P],
+    "cwf_topk_ce_workspace": [I, L],
+    "cwf_topk_ce": [P, P, U, L, P, P, P, I, L, I, P, P],
+    "cwf_topk_ce_bwd": [P, P, U, P, P, P, I, L, I, P],
     "cwf_components_workspace": [I, I, I, I, I],
     "cwf_components": [P, I, I, I, I, I, I, P, P, P, P, P, L, P],
     "cwf_postprocess_labels": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
@@ -250,7 +253,8 @@ class WindowGrid(C.Structure):
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
 GRADNORM_WS_DOUBLES = 1024     # CWF_GRADNORM_WS_DOUBLES
 RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
-                 "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace"}
+                 "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace",
+                 "cwf_topk_ce_workspace"}
 
 _lib = None
 

@@ -925,16 +925,21 @@ class _BoundaryLossFn(torch.autograd.Function):
         return backend().boundary_loss_bwd(prob_cl, phi, ctx.posmasks, coef, gs), None, None, None
 
 
-def boundary_weight_tensor(weight, device):
-    """float or one-element tensor -> the one-float32 device tensor the boundary kernels read (a tensor already of that kind is
-    returned as it is, so a caller can change the weight in place between steps of a captured plan)"""
+def loss_weight_tensor(weight, device, what):
+    """float or one-element tensor -> the one-float32 device tensor a loss kernel reads its weight from (a tensor already of that kind
+    is returned as it is, so a caller can change the weight in place between steps of a captured plan)"""
     if isinstance(weight, torch.Tensor):
         if weight.numel() != 1:
-            raise ValueError("boundary weight must have one element, got shape %s" % (tuple(weight.shape),))
+            raise ValueError("%s weight must have one element, got shape %s" % (what, tuple(weight.shape)))
         if weight.dtype == torch.float32 and weight.device == torch.device(device) and weight.dim() == 1:
             return weight
         return weight.detach().reshape(1).to(device=device, dtype=torch.float32)
     return torch.full((1,), float(weight), dtype=torch.float32, device=device)
+
+
+def boundary_weight_tensor(weight, device):
+    """the boundary weight as the one-float32 device tensor the boundary kernels read (loss_weight_tensor)"""
+    return loss_weight_tensor(weight, device, "boundary")
 
 
 def boundary_loss(prob_ncdhw, label, posmasks=REGION_MASKS, weight=1.0, phi=None):
@@ -948,3 +953,38 @@ def boundary_loss(prob_ncdhw, label, posmasks=REGION_MASKS, weight=1.0, phi=None
             label = label.long()
         phi = backend().signed_distance(label, posmasks)
     return _BoundaryLossFn.apply(to_channels_last_view(prob_ncdhw), phi.contiguous(), posmasks, boundary_weight_tensor(weight, prob_ncdhw.device))
+
+
+class _TopkCeFn(torch.autograd.Function):
+    """weight x mean of -log p_t over the k hardest voxels of the batch, exact selection on the device (csrc/topk.hip)."""
+
+    @staticmethod
+    def forward(ctx, prob_cl, label, posmask, k, weight):
+        loss, coef = backend().topk_ce(prob_cl, label, posmask, k, weight)
+        ctx.posmask = posmask
+        ctx.save_for_backward(prob_cl, label, coef)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        prob_cl, label, coef = ctx.saved_tensors
+        gs = g.reshape(1).to(torch.float32).contiguous()
+        return backend().topk_ce_bwd(prob_cl, label, ctx.posmask, coef, gs), None, None, None, None
+
+
+def topk_count(M, percent):
+    """k of `percent` % of M voxels, nnU-Net's rounding (int(M * percent / 100)), kept inside 1..M"""
+    return max(1, min(int(M), int(M * percent / 100)))
+
+
+def topk_ce_loss(prob_ncdhw, label, percent=10.0, weight=1.0, posmask=0):
+    """Top-k cross-entropy (nnU-Net's TopKLoss): weight x mean of -log max(p_t, 1e-7) over the hardest `percent` % of the voxels of the
+    whole batch.  prob [N,C,D,H,W] (C = 4: class = label; C = 2: class = (posmask >> label) & 1), label int64 [N,D,H,W]; weight: float
+    or one-element device tensor.  Ties at the threshold share the remaining weight equally."""
+    if not 0.0 < float(percent) <= 100.0:
+        raise ValueError("topk percent must lie in (0, 100], got %r" % (percent,))
+    label = label.contiguous()
+    if label.dtype != torch.int64:
+        label = label.long()
+    k = topk_count(label.numel(), float(percent))
+    return _TopkCeFn.apply(to_channels_last_view(prob_ncdhw), label, int(posmask), k, loss_weight_tensor(weight, prob_ncdhw.device, "topk"))

@@ -1187,6 +1187,50 @@ class HipBackend:
                    int(prob[0, ..., 0].numel()), c, self._stream())
         return dprob
 
+    # ------------------------------------------------------------------ L3 (top-k cross-entropy)
+    @staticmethod
+    def _topk_args(name, prob, label, posmask):
+        if prob.dim() != 5 or prob.dtype != _f32 or not prob.is_cuda or int(prob.shape[-1]) not in (2, 4):
+            raise ValueError("%s: prob must be a float32 [N, D0, D1, D2, C] tensor on the GPU with C = 2 or 4, got %s %s"
+                             % (name, tuple(prob.shape), prob.dtype))
+        if tuple(label.shape) != tuple(prob.shape[:4]) or label.dtype != torch.int64 or label.device != prob.device:
+            raise ValueError("%s: label must be int64 %s on the device of prob, got %s %s"
+                             % (name, tuple(prob.shape[:4]), tuple(label.shape), label.dtype))
+        posmask = int(posmask)
+        if posmask < 0 or posmask > 0xFFFFFFFF:
+            raise ValueError("%s: posmask is a 32-bit class bitmask, got %r" % (name, posmask))
+        assert prob.is_contiguous() and label.is_contiguous()
+        return int(prob.shape[0]), int(prob[0, ..., 0].numel()), int(prob.shape[-1]), posmask
+
+    def topk_ce(self, prob, label, posmask, k, weight):
+        """prob [N,D0,D1,D2,C] dense channels-last (C = 4 or 2), label int64 [N,D0,D1,D2], k voxels of the whole batch, weight a
+        one-float device tensor -> (loss [1], coef [4]): weight x mean of -log p_t over the k hardest voxels by an exact radix select
+        on the device (cwf_topk_ce).  No host synchronisation: the workspace comes from torch's allocator."""
+        n, v, c, posmask = self._topk_args("topk_ce", prob, label, posmask)
+        k = int(k)
+        if k < 1 or k > n * v:
+            raise ValueError("topk_ce: k must lie in 1..N V = %d, got %d" % (n * v, k))
+        if weight.numel() != 1 or weight.dtype != _f32 or weight.device != prob.device:
+            raise ValueError("topk_ce: weight must be a one-element float32 tensor on the device of prob")
+        nbytes = self.lib.cwf_topk_ce_workspace(n, v)
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_topk_ce_workspace failed with status %d (N=%d V=%d)" % (nbytes, n, v))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=prob.device)
+        loss = torch.empty(1, dtype=_f32, device=prob.device)
+        coef = torch.empty(4, dtype=_f32, device=prob.device)
+        self._call("cwf_topk_ce", prob.data_ptr(), label.data_ptr(), posmask, k, weight.data_ptr(), loss.data_ptr(), coef.data_ptr(), n, v, c,
+                   ws.data_ptr(), self._stream())
+        return loss, coef
+
+    def topk_ce_bwd(self, prob, label, posmask, coef, gscale):
+        """-> dprob like prob: (gscale * coef[0]) * (-1 / max(pc, 1e-7)) at the target class of the voxels below tau, that times coef[1]
+        on the ties at tau, +0 elsewhere"""
+        n, v, c, posmask = self._topk_args("topk_ce_bwd", prob, label, posmask)
+        dprob = torch.empty_like(prob)
+        self._call("cwf_topk_ce_bwd", prob.data_ptr(), label.data_ptr(), posmask, coef.data_ptr(), gscale.data_ptr(), dprob.data_ptr(), n, v, c,
+                   self._stream())
+        return dprob
+
     def head_loss(self, logits, label, posmasks, scale):
         """Fused head -> loss forward: logits = up to 3 low-res [N,d,h,w,ldc] tensors (2 channels used), label int64 [N,D,H,W].
         -> (total [1], loss [nm], coef [nm,N,2,4])"""

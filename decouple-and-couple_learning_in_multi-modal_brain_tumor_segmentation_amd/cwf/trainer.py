@@ -36,6 +36,10 @@ Step controls (all off by default; then the step issues exactly the launches des
   * boundary_weight = w: a sixth loss term, w * boundary loss of the main output (tools.boundary_loss: signed distance maps of the
     target's WT / TC / ET computed on the device every step), in front of the same backward.  w lives in a one-float device tensor
     that the kernels read, so set_boundary_weight() between steps needs no recapture.  None: the step makes no new call.
+  * topk_weight = w, topk_percent = K: a further loss term after the boundary part, w * top-k cross-entropy of the main output
+    (tools.topk_ce: mean of -log p_target over the hardest K % of the batch's voxels, selected exactly on the device), in front of
+    the same backward.  w lives in a one-float device tensor (set_topk_weight() needs no recapture); K is fixed at construction, k
+    being a launch argument.  None: the step makes no new call and calls total_loss as before.
 Checkpoints use the reference layout {'epoch', 'state_dict' with 'module.' prefix, 'optim_dict'} (:248-253)."""
 from __future__ import annotations
 
@@ -48,9 +52,10 @@ import torch.distributed as dist
 from .optim import FusedAdam, poly_lr
 
 
-def total_loss(outputs, target, edge, boundary=None):
+def total_loss(outputs, target, edge, boundary=None, topk=None):
     """The reference's five terms; with `boundary` (the one-float device tensor holding the boundary weight) a sixth part,
-    tools.boundary_loss(outputs[0], target) at that weight, is appended and added to the total."""
+    tools.boundary_loss(outputs[0], target) at that weight, is appended and added to the total; with `topk` = (the one-float device
+    tensor holding the top-k weight, percent) the part tools.topk_ce(outputs[0], target) is appended after it."""
     from models import criterions
     from utils import tools
     parts = [criterions.softmax_dice(outputs[0], target), tools.get_separate_loss(outputs[1], target),
@@ -60,6 +65,9 @@ def total_loss(outputs, target, edge, boundary=None):
     if boundary is not None:
         parts.append(tools.boundary_loss(outputs[0], target, weight=boundary))
         total = total + parts[5]
+    if topk is not None:
+        parts.append(tools.topk_ce(outputs[0], target, percent=topk[1], weight=topk[0]))
+        total = total + parts[-1]
     return total, parts
 
 
@@ -71,6 +79,19 @@ def check_boundary_weight(w):
     if not math.isfinite(w) or w < 0.0:
         raise ValueError("boundary_weight must be None or a finite number >= 0, got %r" % (w,))
     return w
+
+
+def check_topk(weight, percent):
+    """(weight, percent): weight None (term off) or a finite float >= 0; percent a float in (0, 100]"""
+    percent = float(percent)
+    if not 0.0 < percent <= 100.0:                      # (NaN fails both comparisons)
+        raise ValueError("topk_percent must lie in (0, 100], got %r" % (percent,))
+    if weight is None:
+        return None, percent
+    weight = float(weight)
+    if not math.isfinite(weight) or weight < 0.0:
+        raise ValueError("topk_weight must be None or a finite number >= 0, got %r" % (weight,))
+    return weight, percent
 
 
 def boundary_schedule(weight, epoch, warmup):
@@ -86,9 +107,11 @@ def kernels_backend():
 class Trainer:
     def __init__(self, model, lr=2e-4, weight_decay=1e-5, amsgrad=True, end_epoch=1000, use_graph=False,
                  graph_warmup=2, overlap_comm=True, wgrad_async=True, accum_steps=1, max_grad_norm=None, ema_decay=None,
-                 boundary_weight=None):
+                 boundary_weight=None, topk_weight=None, topk_percent=10.0):
         self.boundary_weight = check_boundary_weight(boundary_weight)
         self._boundary = None                           # the weight as a one-float device tensor, made at the first step that needs it
+        self.topk_weight, self.topk_percent = check_topk(topk_weight, topk_percent)
+        self._topk = None                               # likewise
         self.model = model
         self.init_lr, self.end_epoch = lr, end_epoch
         if int(accum_steps) != accum_steps or accum_steps < 1:
@@ -188,7 +211,10 @@ class Trainer:
         K = kernels_backend()
         K.wgrad_async = self.wgrad_async       # (from the forward pass on: it prepares weight-gradient operands on the side stream)
         outputs = self.model(x, None)
-        loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device))
+        if self.topk_weight is None:
+            loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device))
+        else:
+            loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device), topk=(self._topk_tensor(x.device), self.topk_percent))
         self.opt.zero_grad(set_to_none=True)
         if hasattr(K, "flush_every_default"):
             # graph modes: one reduce per phase, in warm-up too
@@ -233,6 +259,25 @@ class Trainer:
         if self._boundary is not None:
             self._boundary.fill_(w)
 
+    def _topk_tensor(self, device):
+        if self.topk_weight is None:
+            return None
+        if self._topk is None:
+            if _capturing():
+                raise RuntimeError("the top-k weight tensor must exist before the step is captured")
+            self._topk = torch.full((1,), self.topk_weight, dtype=torch.float32, device=device)
+        return self._topk
+
+    def set_topk_weight(self, w):
+        """New weight of the top-k term from the next step on, in every step mode (no recapture: the kernels read it from device
+        memory).  Only for a Trainer built with a topk_weight; the percentage stays as constructed."""
+        if w is None or self.topk_weight is None:
+            raise ValueError("the top-k term is switched on or off at construction (topk_weight=...), not between steps")
+        w, _ = check_topk(w, self.topk_percent)
+        self.topk_weight = w
+        if self._topk is not None:
+            self._topk.fill_(w)
+
     def _finish_comm(self):
         if not self.comm:
             return
@@ -252,6 +297,7 @@ class Trainer:
         import gc
         self._static = (x.clone(), target.clone(), edge.clone())
         self._boundary_tensor(x.device)                 # (allocated and filled outside the capture)
+        self._topk_tensor(x.device)
         want_plan = self.graph_mode == "plan"
         g = torch.cuda.CUDAGraph(keep_graph=True) if want_plan else torch.cuda.CUDAGraph()
         # No cyclic garbage collection inside the capture.  A Trainer and its model form a cycle (model.phase_callback), so an earlier
@@ -324,7 +370,7 @@ class Trainer:
     def step(self, x, target, edge, epoch=0):
         """One optimisation step on a rank-local batch -- with accum_steps = N > 1 one MICRO-step: every N-th call updates the weights
         (learning rate of that call's epoch), the calls before it only accumulate.  Returns this batch's (loss, [five parts]) as
-        device tensors (no host sync); six parts with a boundary_weight."""
+        device tensors (no host sync); a boundary_weight and a topk_weight each append a part, in that order."""
         self._last_micro = self._micro + 1 >= self.accum_steps
         if self._last_micro:
             self.opt.param_groups[0]["lr"] = float(poly_lr(self.init_lr, epoch, self.end_epoch))   # plain float: checkpoints stay weights_only-loadable

@@ -17,6 +17,16 @@ def boundary_loss(output, target, **kw):
     return tools.boundary_loss(output, target, **kw)
 
 
+def topk_ce(output, target, **kw):
+    """tools.topk_ce: the mean cross-entropy over the hardest k % of the batch's voxels (nnU-Net's TopKLoss)."""
+    return tools.topk_ce(output, target, **kw)
+
+
+def softmax_dice_topk(output, target):
+    """softmax_dice + topk_ce at k = 10 %, weight 1 (nnU-Net's DC_and_topk_loss shape): selectable as --criterion softmax_dice_topk."""
+    return softmax_dice(output, target) + tools.topk_ce(output, target)
+
+
 def _not_built(name):
     def f(*a, **k):
         raise NotImplementedError("criterions.%s is an unused alternative in the reference and is not built; "

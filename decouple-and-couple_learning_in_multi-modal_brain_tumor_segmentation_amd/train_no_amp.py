@@ -136,7 +136,23 @@ def build_parser():
                         "every step) to the five terms; the log line gains boundary_loss.  Default: off")
     p.add_argument("--boundary_warmup", default=0, type=int,
                    help="E >= 0: ramp the boundary weight linearly, A x min(1, epoch / E), set once per epoch; 0: constant A")
+    p.add_argument("--topk_weight", default=None, type=float,
+                   help="W >= 0: add W x the top-k cross-entropy of the main output (nnU-Net's TopKLoss: mean of -log p_target over the "
+                        "hardest --topk_percent %% of the batch's voxels, selected exactly on the device) after the other terms; the log "
+                        "line gains topk_loss.  Default: off")
+    p.add_argument("--topk_percent", default=10.0, type=float,
+                   help="K in (0, 100]: the share of the batch's voxels the top-k term averages over (fixed for the run).  Default: 10")
     return p
+
+
+def check_topk(args):
+    """the values of --topk_weight / --topk_percent (SystemExit with the rule, like the other checks)"""
+    if args.topk_weight is not None and not 0.0 <= args.topk_weight < float("inf"):
+        raise SystemExit("--topk_weight takes a finite weight >= 0 (leave the flag out for no top-k term)")
+    if not 0.0 < args.topk_percent <= 100.0:
+        raise SystemExit("--topk_percent takes a percentage in (0, 100]")
+    if args.topk_weight is not None and args.no_cuda:
+        raise SystemExit("--topk_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
 
 
 def boundary_weight_at(args, epoch):
@@ -254,6 +270,7 @@ def main(argv=None):
     check_acquisition_aug(args)
     check_step_controls(args)
     check_boundary(args)
+    check_topk(args)
     from cwf import kernels
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint
@@ -297,8 +314,10 @@ def main(argv=None):
     trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, amsgrad=args.amsgrad, end_epoch=args.end_epoch,
                       use_graph={"eager": False, "plan": "plan", "hipgraph": "hipgraph"}[args.step_mode] if use_cuda else False,
                       accum_steps=args.accum_steps, max_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay,
-                      boundary_weight=boundary_weight_at(args, args.start_epoch))
+                      boundary_weight=boundary_weight_at(args, args.start_epoch), topk_weight=args.topk_weight,
+                      topk_percent=args.topk_percent)
     clip, use_ema, use_boundary = args.clip_grad_norm is not None, args.ema_decay is not None, args.boundary_weight is not None
+    use_topk = args.topk_weight is not None
     if use_ema and os.path.isfile(args.resume) and args.load:
         ck = torch.load(args.resume, map_location="cpu", weights_only=True)
         if "ema_state_dict" in ck:
@@ -341,7 +360,8 @@ def main(argv=None):
                     ev.synchronize() if ev is not None else None
                     v = host.tolist()
                     log.info("Epoch: %d_Iter:%d  loss: %.5f || end_loss: %.5f || s_loss:%.4f || edge_loss:%.4f || mid_s_loss:%.4f || mid_edge_loss:%.4f ||"
-                             + (" boundary_loss: %.5f ||" if use_boundary else "") + (" grad_norm: %.4f" if clip else ""), tag[0], tag[1], *v)
+                             + (" boundary_loss: %.5f ||" if use_boundary else "") + (" topk_loss: %.5f ||" if use_topk else "")
+                             + (" grad_norm: %.4f" if clip else ""), tag[0], tag[1], *v)
                 # (grad_norm: of the last update -- inside an accumulation window that is the previous window's)
                 snap = torch.stack([loss] + list(parts) + ([trainer.opt.grad_norm] if clip else [])).float()
                 if use_cuda:

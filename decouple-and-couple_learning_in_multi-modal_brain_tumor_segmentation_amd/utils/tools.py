@@ -30,6 +30,13 @@ def boundary_loss(output, target, posmasks=CF.REGION_MASKS, weight=1.0, phi=None
     return CF.boundary_loss(output, target, posmasks=posmasks, weight=weight, phi=phi)
 
 
+def topk_ce(output, target, percent=10.0, weight=1.0, posmask=0):
+    """Top-k cross-entropy (nnU-Net's TopKLoss, k = 10 %) of the probabilities output [B,C,D,H,W] (C = 4, or 2 with a posmask) against
+    the label map target [B,D,H,W]: weight * mean of -log max(p_target, 1e-7) over the hardest `percent` % of the voxels of the whole
+    batch, selected exactly on the device.  Not in the reference; off unless asked for."""
+    return CF.topk_ce_loss(output, target, percent=percent, weight=weight, posmask=posmask)
+
+
 def _separate(output, target, masks):
     maps = [output[r] for r in ("01", "02", "04")]
     if all(isinstance(m, CF.LazyProb) for m in maps) and len({(m.scale, tuple(m.logit.shape)) for m in maps}) == 1:

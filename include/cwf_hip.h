@@ -425,6 +425,30 @@ int cwf_boundary_bwd(const float* phi, const uint32_t* posmasks, const float* co
                      int64_t V, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * L3  top-k (hard-voxel) cross-entropy with an exact on-device selection (csrc/topk.hip; this project's statement)
+ *   prob float [N][V][C] channels-last, C = 4 or 2; label int64 [N][V]; target class t = label (C = 4, labels 0..3) or
+ *   (posmask >> (label & 31)) & 1 (C = 2), as in cwf_dice_ce_*.  M = N V; the selection runs over the whole batch.
+ *   pc = (p_t > 0) ? fminf(p_t, 1.0f) : 0.0f (NaN, negatives, -0 -> +0);  key = bits(pc) as uint32 (key order = value order);
+ *   l = -logf(fmaxf(pc, 1e-7f));  tau = the k-th smallest key;  a = #{key < tau}, n = #{key = tau}, s = k - a.
+ *   loss[0] = float32((double)w / k * (sum_{key < tau} (double)l + (double)s * (double)l(tau))), w = weight[0] in DEVICE memory.
+ *   coef[0] = float32((double)w / k), coef[1] = float32((double)s / (double)n), coef[2] = bits of tau, coef[3] = +0.
+ *   tau, s, n are exact and the loss repeats bit for bit from run to run (integer histograms, partials added in a fixed order).
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of device workspace cwf_topk_ce needs (4 bytes per voxel + 49,408, 256-B aligned), or a negative CWF_E_*: CWF_E_BADARG for
+ * N <= 0 or V <= 0, CWF_E_TOOLARGE for more than 2^40 voxels. */
+int64_t cwf_topk_ce_workspace(int N, int64_t V);
+/* Nine launches, no host synchronisation, nothing read back, no kernel waits on another workgroup, no memcpy: capturable.  ws may
+ * hold anything (what needs zeroing is zeroed by a kernel).  CWF_E_BADARG before any launch: a null pointer, C not 2 or 4, N <= 0,
+ * V <= 0, k < 1 or k > N V; CWF_E_ALIGN: ws off 256 bytes. */
+int cwf_topk_ce(const float* prob, const int64_t* label, uint32_t posmask, int64_t k, const float* weight, float* loss, float* coef,
+                int N, int64_t V, int C, void* ws, void* stream);
+/* One streaming launch.  g0 = gscale[0] * coef[0], r = -1.0f / fmaxf(pc, 1e-7f), every product rounded on its own:
+ * dprob[v][t] = g0 * r for key < tau, (g0 * coef[1]) * r for key = tau (ties share the remaining weight equally), +0 for key > tau
+ * and for every other class; dprob is fully written.  The gradient passes through the 1e-7 floor as -1 / 1e-7. */
+int cwf_topk_ce_bwd(const float* prob, const int64_t* label, uint32_t posmask, const float* coef, const float* gscale, float* dprob,
+                    int N, int64_t V, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N1  sliding-window inference glue   predict_overlap.py:31-58 (tailor_and_concat), :134-141 + utils/tools.py:44-47,64-109
  *     and utils/hausdorff.py (Hausdorff distance / HD95)
  * ---------------------------------------------------------------------------------------------- */

@@ -159,7 +159,7 @@ extern "C" int cwf_plan_create(void* graph_, void** out) {
         } else if (ty == hipGraphNodeTypeMemcpy) {
             // hipMemcpyAsync under capture makes a 1-D copy node, for which the runtime has no parameter getter (the 3-D getter
             // returns garbage on it): refuse copy nodes altogether rather than guess.  The step this library captures has none
-            // (its copies are kernels); a graph that does is replayed by the caller with hipGraphLaunch.
+            // (its copies are kernels); for a graph that does, the caller drops the capture and goes on with eager steps.
             snprintf(g_detail, sizeof g_detail, "memcpy node at position %zu (copy nodes are not supported: no 1-D parameter getter)", i);
             destroy(P);
             return CWF_E_TOOLARGE;

@@ -8,6 +8,7 @@ gradient (recomputed) and undone analytically in the data gradient (full Instanc
 from __future__ import annotations
 
 import contextlib
+import functools
 import math
 from typing import Optional
 
@@ -161,10 +162,65 @@ class WeightPacker:
 # ======================================================================================================
 # conv family
 # ======================================================================================================
+# Side channels.  Neighbouring layers tell each other things through plain Python attributes of the tensor that joins them.  An attribute
+# is LOST when autograd re-materialises the tensor (it sums the gradients of two consumers into a new tensor; retain_grad and hooks
+# do the same), so every reader takes a missing attribute as "no".
+#   on activations, set in the forward pass:
+#     _cwf_link         NaaLink of a block tail.  Written by norm_act_add() on its output; read by conv() on its input.
+#     _cwf_carry        CarryLink of a carried alias.  Written by conv(carry=True) on the alias; read by conv() on its `residual`.
+#     _cwf_catbuf       the concatenation buffer a skip tensor already lives in.  Written by the models (Unet's encoder) on the skip
+#                       tensor and copied by conv() onto its carried alias; read by the models' decoder.
+#     _cwf16x           bf16 image of the tensor.  Written by conv() / norm_act_add() (emit16) on their output; read by _ConvFn.forward
+#                       of the consumer: the x operand of its weight gradient.
+#     _cwf_want16       True or "only": the layer that produced this tensor reads bf16 images of its incoming gradient ("only": and
+#                       nothing else).  Written by conv() on its output; read by the consumer's forward (_ConvFn, _NormActAddFn), whose
+#                       backward then writes the image.
+#     _cwf_wgrad_first  the consumer's weight gradient is one of the last of backward and is issued before its data gradient.
+#                       Written by the models (the stem, on its output); read by _ConvFn.forward.
+#   on gradients, set in the backward pass:
+#     _cwf16            bf16 image of the gradient.  Written by _apply16 on the dx it returns; read by _ConvFn.backward of the layer
+#                       that receives it as dy.
+#     _cwf_f32_missing  the fp32 tensor is an unwritten carrier, only _cwf16 holds the gradient.  Written by _apply16; read by
+#                       _ConvFn.backward and _dy_f32.
+def _sink_views(sink, spec, w, b, needs_w):
+    """Is a gradient sink active and does it own this layer's weight and bias?  Its views (of w, of b or None for a layer without
+    bias), or None: the gradients then return through autograd (no sink, a weight applied twice, a frozen weight, a foreign tensor)."""
+    if sink is None or spec.uses > 1 or not needs_w:
+        return None
+    sw = sink.view(w)
+    sb = sink.view(b) if (sw is not None and b is not None) else None
+    if sw is None or (b is not None and sb is None):
+        return None
+    return sw, sb
+
+
+def _wgrad_images(op, cin, cout, nvox, emit=False):
+    """Will the weight gradient of such a layer (nvox output voxels) take bf16 operand images?  HipBackend.bf16_operands_ok's answer,
+    and 0 where no backward pass follows.  emit: asked by the producer of the layer's un-normalised input before it writes bf16 of its
+    own output -- only where apply passes write that operand for the normalised layers too ("xa" in APPLY_EMITS)."""
+    K = backend()
+    if not torch.is_grad_enabled() or (emit and "xa" not in K.APPLY_EMITS):
+        return 0
+    return K.bf16_operands_ok(op, cin, cout, nvox)
+
+
+def _apply16(K, dy, x, scale, shift, slope, sums, dx_add, want_dx16, want_xa16, only16):
+    """The InstanceNorm-backward apply pass with bf16 side outputs, (dx, xa16): the pass has x, its statistics and dx in registers, so it
+    also writes this layer's weight-gradient operand bf16(act(IN(x))) (want_xa16) and the bf16 image of dx for the layer that produced x
+    (want_dx16; left on dx as _cwf16) -- and ONLY that image where that layer reads nothing else (only16: dx is an unwritten carrier)."""
+    dx, dx16, xa16 = K.in_bwd_apply16(dy, x, scale, shift, slope, sums, dx_add=dx_add, want_dx16=want_dx16, want_xa16=want_xa16,
+                                      need_f32=not only16)
+    if dx16 is not None:
+        dx._cwf16 = dx16
+        if only16:
+            dx._cwf_f32_missing = True
+    return dx, xa16
+
+
 class _ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, spec, in_scale, in_shift, slope, residual, out_scale, want_stats, carry, x_link, out=None, res_link=None,
-                carry_link=None, y16=None):
+                carry_link=None, y16=None, use16=0):
         K = backend()
         ctx.set_materialize_grads(False)     # (autograd would zero-FILL a gradient for each of the (scale, shift) outputs: 2 launches per conv)
         ctx.x_link = x_link
@@ -185,11 +241,10 @@ class _ConvFn(torch.autograd.Function):
         ctx.spec, ctx.slope = spec, slope
         ctx.bias_ref = b
         ctx.has_res = residual is not None
-        # bf16 operand images for this layer's weight gradient (full-resolution 16-channel layers, HipBackend.bf16_operands_ok)
-        ok16 = getattr(K, "bf16_operands_ok", None)
-        ctx.use16 = bool(ok16 is not None and ok16(spec.op, spec.cin, spec.cout, y.shape[1] * y.shape[2] * y.shape[3]))
+        # bf16 operand images for this layer's weight gradient (conv(): _wgrad_images)
+        ctx.use16 = bool(use16)
         ctx.x16 = getattr(x, "_cwf16x", None) if (ctx.use16 and in_scale is None) else None     # bf16(x) from x's producer (a block tail)
-        if ctx.use16 and ctx.x16 is None and ctx.needs_input_grad[1] and getattr(K, "wgrad_async", False) and \
+        if ctx.use16 and ctx.x16 is None and ctx.needs_input_grad[1] and K.wgrad_async and \
                 getattr(x, "_cwf_wgrad_first", False):   # (wgrad_async: a Trainer step)
             # the weight-gradient operand bf16(act(IN(x))) depends on forward data only: made NOW, on the weight-gradient side stream,
             # which idles during the forward pass -- the backward pass then neither converts it nor waits for this layer's own
@@ -216,28 +271,18 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _a, _b, dcarry):
+        # five steps: 1 collect the carried gradient, 2 scale dy (and sort out its bf16 image), 3 the early weight gradient, 4 the data
+        # gradient, 5 the weight gradient -- the backend calls in this order
         K = backend()
-        if ctx.carry_link is not None and ctx.carry_link.grads:
-            # gradients the consumers of the carried alias handed over directly (CarryLink) join whatever autograd delivered
-            for gq in ctx.carry_link.grads:
-                dcarry = gq if dcarry is None else K.add(dcarry, gq)
-            ctx.carry_link.grads = []
+        dcarry = _collect_carry(K, ctx.carry_link, dcarry)
         if dy is None:                       # y itself unused downstream: only the carried alias has a gradient
-            return (dcarry,) + (None,) * 15
+            return (dcarry,) + (None,) * 16
         x, w, in_scale, in_shift, out_scale = ctx.saved_tensors
-        spec = ctx.spec
-        dys = None
-        if out_scale is not None:
-            sink0 = active_sink()
-            fold = (sink0 is not None and not ctx.needs_input_grad[0] and not ctx.has_res and spec.uses <= 1 and ctx.needs_input_grad[1] and
-                    sink0.view(w) is not None and (ctx.bias_ref is None or sink0.view(ctx.bias_ref) is not None) and
-                    getattr(K, "dy_scale_ok", lambda *a: False)(spec.op, spec.cin, spec.cout, dy.shape[1] * dy.shape[2] * dy.shape[3])
-                    and dy.shape[-1] == spec.cout and dy.is_contiguous())
-            if fold:
-                dys = out_scale                       # the weight gradient (the only reader of dy here) scales dy while staging it
-                dy = _dy_f32(K, dy)
-            else:
-                dy = K.channel_scale(_dy_f32(K, dy), out_scale)
+        spec, need_dx, need_dw = ctx.spec, ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        sink = active_sink()
+        views = _sink_views(sink, spec, w, ctx.bias_ref, need_dw)
+        # (the fold: only where the weight gradient is the one reader of dy)
+        dy, dys = _scale_dy(K, spec, dy, out_scale, may_fold=views is not None and not need_dx and not ctx.has_res)
         dres = dy if ctx.has_res else None
         dy_private = not ctx.has_res
         if ctx.has_res and ctx.res_link is not None:
@@ -246,100 +291,117 @@ class _ConvFn(torch.autograd.Function):
             ctx.res_link.grads.append(dy)
             dres = None
             dy_private = True
-        dw = db = dx = None
-        sink = active_sink()
-        sw = sink.view(w) if (sink is not None and spec.uses <= 1 and ctx.needs_input_grad[1]) else None
-        sb = sink.view(ctx.bias_ref) if (sw is not None and ctx.bias_ref is not None) else None
-        to_sink = sw is not None and (ctx.bias_ref is None or sb is not None)
-        use16 = ctx.use16 and to_sink and out_scale is None
-        # (no producer wrote a bf16 image of a gradient that comes out of a stride-2 data gradient: the weight gradient converts it on
-        # the side stream -- one conversion here on the main stream, for both gradients, measured 0.3 % slower)
-        dy16 = getattr(dy, "_cwf16", None) if out_scale is None else None
-        dg16 = dy16 if (dy16 is not None and dy.shape[-1] == spec.cout and getattr(K, "bf16_dgrad_ok", lambda *a: False)(
-            spec.op, spec.cin, spec.cout, dy.shape)) else None     # the data gradient reads the bf16 image
-        if getattr(dy, "_cwf_f32_missing", False) and not (use16 and dy16 is not None and (dg16 is not None or not ctx.needs_input_grad[0])
-                                                           and not ctx.has_res):
-            dy = _dy_f32(K, dy)                         # some consumer below reads the fp32 tensor
-        if not use16:
-            dy16 = None
+        use16 = ctx.use16 and views is not None and out_scale is None
+        dy, dy16, dg16 = _dy_images(K, ctx, dy, use16, scaled=out_scale is not None)
         xa16 = ctx.x16 if use16 else None
-
-        def issue_sink_wgrad(xa16_):
-            # gradient-sink path (Trainer): slabs now, ONE batched reduce per backward phase writes dW / db into the flat buffer
-            dyv = dy[..., :spec.cout] if dy.shape[-1] != spec.cout else dy
-            kw = dict(x16=xa16_, dy16=dy16) if (use16 and (xa16_ is not None or dy16 is not None)) else {}
-            if dys is not None:
-                kw["dy_scale"] = dys
-            K.wgrad_to(spec, spec.op, x, in_scale, in_shift, ctx.slope, dyv, spec.cout, spec.inv_map, sw, sb if spec.has_bias_map else None,
-                       allow_async=dy_private, **kw)
-            sink.mark(w)
-            if sb is not None:
-                if not spec.has_bias_map:   # ConvTranspose: the bias gradient spans the 8 parity classes
-                    if hasattr(K, "channel_sum_to"):
-                        K.channel_sum_to(dy, sb, allow_async=dy_private)      # (a full pass over dy: on the weight-gradient side stream)
-                    else:
-                        K.stats_channel_sum(K.in_stats(dy), sb)
-                sink.mark(ctx.bias_ref)
-
-        early = to_sink and use16 and ctx.wgrad_first
+        norm = (in_scale, in_shift, ctx.slope)
+        early = use16 and ctx.wgrad_first
         if early:
-            issue_sink_wgrad(xa16)
-        if ctx.needs_input_grad[0]:
-            dxa = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-            fused = in_scale is not None and getattr(K, "supports_fused_norm_bwd", lambda: False)()
-            kw16 = dict(x16=dg16) if dg16 is not None else {}
-            if fused:
-                # the InstanceNorm-backward sums come out of the data gradient's epilogue: one pass over (g, x) less
-                sums = K.new_stats(x.shape[0], spec.cin, x.device)
-                K.conv(pk.dgrad_op(spec.op), dy, spec.packed(True), None, spec.cin, out=dxa, w_ref=w, fwd_op=spec.op,
-                       stats=sums, nb=(x, in_scale, in_shift, ctx.slope), **kw16)
-                emits = getattr(K, "APPLY_EMITS", ())
-                want_xa, want_dx = use16 and "xa" in emits and not early, ctx.up16 and "dx" in emits
-                if want_xa or want_dx:
-                    # the apply pass has x, its statistics and dx in registers: it also writes this layer's weight-gradient operand
-                    # bf16(act(IN(x))) and the bf16 image of dx for the layer that produced x -- and ONLY that image where the layer
-                    # that produced x reads nothing else (ctx.up16 == "only", a single-consumer graph)
-                    only16 = want_dx and ctx.up16 == "only" and ctx.single and to_sink
-                    dx, dx16, xa16 = K.in_bwd_apply16(dxa, x, in_scale, in_shift, ctx.slope, sums, dx_add=dcarry,
-                                                      want_dx16=want_dx, want_xa16=want_xa, need_f32=not only16)
-                    if dx16 is not None:
-                        dx._cwf16 = dx16
-                        if only16:
-                            dx._cwf_f32_missing = True
-                else:
-                    dx = K.in_bwd_apply(dxa, x, in_scale, in_shift, ctx.slope, sums, dx_add=dcarry)
-            elif in_scale is not None:
-                K.conv(pk.dgrad_op(spec.op), dy, spec.packed(True), None, spec.cin, out=dxa, w_ref=w, fwd_op=spec.op)
-                dx = K.in_bwd(dxa, x, in_scale, in_shift, ctx.slope, dx_add=dcarry)
-            else:
-                link = ctx.x_link
-                if link is not None and not link.shared and getattr(K, "supports_fused_norm_bwd", lambda: False)():
-                    # x is the output of a block tail act(IN(g)) + r whose only consumer is this conv: dx (carry included) is the
-                    # tail's dL/dy, so the epilogue also accumulates the tail's InstanceNorm-backward sums
-                    link.sums = K.new_stats(x.shape[0], spec.cin, x.device)
-                    dx = K.conv(pk.dgrad_op(spec.op), dy, spec.packed(True), None, spec.cin, out=dxa, w_ref=w, fwd_op=spec.op, residual=dcarry,
-                                stats=link.sums, nb=(link.g, link.scale, link.shift, link.slope), **kw16)
-                    link.dy = dx                         # the sums are those of THIS tensor (see _NormActAddFn.backward)
-                else:
-                    dx = K.conv(pk.dgrad_op(spec.op), dy, spec.packed(True), None, spec.cin, out=dxa, w_ref=w, fwd_op=spec.op, residual=dcarry, **kw16)
-        elif dcarry is not None:
-            dx = dcarry
-        if to_sink:
+            _wgrad_to_sink(K, sink, views, spec, x, norm, dy, w, ctx.bias_ref, xa16, dy16, dys, dy_private)
+        dx = dcarry
+        if need_dx:
+            dx, made16 = _data_grad(K, ctx, x, w, norm, dy, dg16, dcarry, want_xa=use16 and "xa" in K.APPLY_EMITS and not early,
+                                    to_sink=views is not None)
+            xa16 = made16 if made16 is not None else xa16
+        dw = db = None
+        if views is not None:
             if not early:
-                issue_sink_wgrad(xa16)
-        elif ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dyv = dy[..., :spec.cout] if dy.shape[-1] != spec.cout else dy
-            # side-stream weight gradients only where nothing on the main stream can touch their operands or results early:
-            #  * a weight applied twice in the forward, or a .grad that already exists, makes AccumulateGrad add IN PLACE;
-            #  * with a residual, dy itself is handed on as the residual's gradient and the engine may accumulate into it
-            #    in place while the side stream still reads it (record_stream guards reuse, not modification)
-            once = spec.uses <= 1 and w.grad is None and dy_private
-            dwf, db = K.wgrad(spec.op, x, in_scale, in_shift, ctx.slope, dyv, spec.cout, spec.inv_map, spec.has_bias_map, w.numel(), w_ref_shape=w.shape,
-                              allow_async=once)
-            dw = dwf.view(w.shape)
-            if db is None:      # ConvTranspose: bias gradient spans the 8 parity classes
-                db = K.stats_channel_sum(K.in_stats(dy), torch.empty(spec.cout, dtype=torch.float32, device=dy.device))
-        return dx, dw, db, None, None, None, None, dres, None, None, None, None, None, None, None, None
+                _wgrad_to_sink(K, sink, views, spec, x, norm, dy, w, ctx.bias_ref, xa16, dy16, dys, dy_private)
+        elif need_dw or ctx.needs_input_grad[2]:
+            dw, db = _wgrad_autograd(K, spec, x, norm, dy, w, dy_private)
+        return (dx, dw, db, None, None, None, None, dres) + (None,) * 9
+
+
+def _collect_carry(K, carry_link, dcarry):
+    """step 1: gradients the consumers of the carried alias handed over directly (CarryLink) join whatever autograd delivered"""
+    if carry_link is not None and carry_link.grads:
+        for gq in carry_link.grads:
+            dcarry = gq if dcarry is None else K.add(dcarry, gq)
+        carry_link.grads = []
+    return dcarry
+
+
+def _scale_dy(K, spec, dy, out_scale, may_fold):
+    """step 2: (dy * out_scale, None) by a pass of its own, or (dy, out_scale) where the weight gradient scales dy while staging it"""
+    if out_scale is None:
+        return dy, None
+    if may_fold and K.dy_scale_ok(spec.op, spec.cin, spec.cout, dy.shape[1] * dy.shape[2] * dy.shape[3]) and \
+            dy.shape[-1] == spec.cout and dy.is_contiguous():
+        return _dy_f32(K, dy), out_scale
+    return K.channel_scale(_dy_f32(K, dy), out_scale), None
+
+
+def _dy_images(K, ctx, dy, use16, scaled):
+    """(dy, dy16, dg16): the bf16 image its producer left on dy, for the weight gradient (dy16) and for the data gradient (dg16, where
+    the kernel reads one); dy itself made from the image if it is an unwritten carrier and some consumer below reads the fp32 tensor"""
+    spec = ctx.spec
+    # (no producer wrote a bf16 image of a gradient that comes out of a stride-2 data gradient: the weight gradient converts it on
+    # the side stream -- one conversion here on the main stream, for both gradients, measured 0.3 % slower)
+    dy16 = getattr(dy, "_cwf16", None) if not scaled else None
+    dg16 = dy16 if (dy16 is not None and dy.shape[-1] == spec.cout and K.bf16_dgrad_ok(spec.op, spec.cin, spec.cout, dy.shape)) else None
+    if getattr(dy, "_cwf_f32_missing", False) and not (use16 and dy16 is not None and (dg16 is not None or not ctx.needs_input_grad[0])
+                                                       and not ctx.has_res):
+        dy = _dy_f32(K, dy)
+    return dy, (dy16 if use16 else None), dg16
+
+
+def _wgrad_to_sink(K, sink, views, spec, x, norm, dy, w, b, x16, dy16, dys, private):
+    """steps 3 and 5, gradient-sink route (Trainer): slabs now, ONE batched reduce per backward phase writes dW / db into the flat buffer.
+    norm: (scale, shift, slope) of x; x16 / dy16: bf16 operand images; dys: dy_scale; private: nothing but the glue references dy."""
+    sw, sb = views
+    dyv = dy[..., :spec.cout] if dy.shape[-1] != spec.cout else dy
+    kw = dict(x16=x16, dy16=dy16) if (x16 is not None or dy16 is not None) else {}
+    if dys is not None:
+        kw["dy_scale"] = dys
+    K.wgrad_to(spec, spec.op, x, *norm, dyv, spec.cout, spec.inv_map, sw, sb if spec.has_bias_map else None, allow_async=private, **kw)
+    sink.mark(w)
+    if sb is not None:
+        if not spec.has_bias_map:   # ConvTranspose: the bias gradient spans the 8 parity classes
+            K.channel_sum_to(dy, sb, allow_async=private)      # (a full pass over dy: on the weight-gradient side stream)
+        sink.mark(b)
+
+
+def _wgrad_autograd(K, spec, x, norm, dy, w, private):
+    """step 5, the route through autograd: (dW, db).  Side-stream weight gradients only where nothing on the main stream can touch
+    their operands or results early:
+     * a weight applied twice in the forward, or a .grad that already exists, makes AccumulateGrad add IN PLACE;
+     * with a residual, dy itself is handed on as the residual's gradient and the engine may accumulate into it in place while the
+       side stream still reads it (record_stream guards reuse, not modification): not `private`"""
+    dyv = dy[..., :spec.cout] if dy.shape[-1] != spec.cout else dy
+    dwf, db = K.wgrad(spec.op, x, *norm, dyv, spec.cout, spec.inv_map, spec.has_bias_map, w.numel(), w_ref_shape=w.shape,
+                      allow_async=spec.uses <= 1 and w.grad is None and private)
+    if db is None:      # ConvTranspose: bias gradient spans the 8 parity classes
+        db = K.stats_channel_sum(K.in_stats(dy), torch.empty(spec.cout, dtype=torch.float32, device=dy.device))
+    return dwf.view(w.shape), db
+
+
+def _data_grad(K, ctx, x, w, norm, dy, dg16, dcarry, want_xa, to_sink):
+    """step 4: (dx, xa16) -- the data gradient, carried gradient included, and the weight-gradient operand image where the apply pass
+    wrote one (want_xa).  dg16: the bf16 image of dy the data-gradient kernel reads in its place."""
+    spec = ctx.spec
+    dxa = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    kw16 = dict(x16=dg16) if dg16 is not None else {}
+    dgrad = functools.partial(K.conv, pk.dgrad_op(spec.op), dy, spec.packed(True), None, spec.cin, out=dxa, w_ref=w, fwd_op=spec.op)
+    if norm[0] is not None and K.supports_fused_norm_bwd():
+        # the InstanceNorm-backward sums come out of the data gradient's epilogue: one pass over (g, x) less
+        sums = K.new_stats(x.shape[0], spec.cin, x.device)
+        dgrad(stats=sums, nb=(x,) + norm, **kw16)
+        want_dx = ctx.up16 and "dx" in K.APPLY_EMITS
+        if want_xa or want_dx:
+            # ("only": a single-consumer graph, and the producing layer's weight gradient goes to the sink like this one's)
+            return _apply16(K, dxa, x, *norm, sums, dcarry, want_dx, want_xa, only16=want_dx and ctx.up16 == "only" and ctx.single and to_sink)
+        return K.in_bwd_apply(dxa, x, *norm, sums, dx_add=dcarry), None
+    if norm[0] is not None:
+        dgrad()
+        return K.in_bwd(dxa, x, *norm, dx_add=dcarry), None
+    link = ctx.x_link
+    if link is not None and not link.shared and K.supports_fused_norm_bwd():
+        # x is the output of a block tail act(IN(g)) + r whose only consumer is this conv: dx (carry included) is the
+        # tail's dL/dy, so the epilogue also accumulates the tail's InstanceNorm-backward sums
+        link.sums = K.new_stats(x.shape[0], spec.cin, x.device)
+        link.dy = dgrad(residual=dcarry, stats=link.sums, nb=(link.g, link.scale, link.shift, link.slope), **kw16)
+        return link.dy, None                     # the sums are those of THIS tensor (see _NormActAddFn.backward)
+    return dgrad(residual=dcarry, **kw16), None
 
 
 class _FusedConvFn(torch.autograd.Function):
@@ -368,8 +430,9 @@ class _FusedConvFn(torch.autograd.Function):
         w0, w1, w2, b0, b1, b2 = ctx.params
         dy = dy.contiguous()
         sink = active_sink()
-        views = [sink.view(t) for t in ctx.params] if (sink is not None and spec.uses <= 1) else None
-        adjacent = views is not None and all(v is not None for v in views) and \
+        pairs = [_sink_views(sink, spec, w_, b_, True) for w_, b_ in ((w0, b0), (w1, b1), (w2, b2))]
+        views = [p[0] for p in pairs] + [p[1] for p in pairs] if all(p is not None for p in pairs) else None
+        adjacent = views is not None and \
             views[1].data_ptr() == views[0].data_ptr() + 4 * w0.numel() and views[2].data_ptr() == views[1].data_ptr() + 4 * w1.numel() and \
             views[4].data_ptr() == views[3].data_ptr() + 4 * b0.numel() and views[5].data_ptr() == views[4].data_ptr() + 4 * b1.numel()
         grads = (None,) * 6
@@ -451,28 +514,27 @@ def conv(x, w, b, spec, in_norm=None, slope=1.0, residual=None, out_scale=None, 
     carry_link = CarryLink() if (carry and torch.is_grad_enabled()) else None
     # emit16: the output is the un-normalised input of a layer whose weight gradient reads bf16 operand images (a 1x1x1 conv in front of a
     # block's first conv): the same launch writes bf16(y)
+    dhw = pk.out_dims(spec.op, x.shape[1], x.shape[2], x.shape[3])
+    nvox = dhw[0] * dhw[1] * dhw[2]
     y16 = None
-    ok16_ = getattr(backend(), "bf16_operands_ok", None)
-    if emit16 and ok16_ is not None and torch.is_grad_enabled() and "xa" in getattr(backend(), "APPLY_EMITS", ()) and out is None and out_scale is None:
-        n_, d_, h_, w_ = x.shape[0], *pk.out_dims(spec.op, x.shape[1], x.shape[2], x.shape[3])
-        if ok16_(pk.CONV3_S1, spec.cout, spec.cout, d_ * h_ * w_) and (spec.cout_alloc or spec.cout) == spec.cout:
-            y16 = torch.empty((n_, d_, h_, w_, spec.cout), dtype=torch.bfloat16, device=x.device)
-    y, s1, s2, xc = _ConvFn.apply(x, w, b, spec, sc, sh, float(slope), residual, out_scale, want_stats, carry, link, out, res_link, carry_link, y16)
+    if emit16 and out is None and out_scale is None and (spec.cout_alloc or spec.cout) == spec.cout and \
+            _wgrad_images(pk.CONV3_S1, spec.cout, spec.cout, nvox, emit=True):
+        y16 = torch.empty((x.shape[0],) + dhw + (spec.cout,), dtype=torch.bfloat16, device=x.device)
+    use16 = _wgrad_images(spec.op, spec.cin, spec.cout, nvox)
+    y, s1, s2, xc = _ConvFn.apply(x, w, b, spec, sc, sh, float(slope), residual, out_scale, want_stats, carry, link, out, res_link, carry_link, y16,
+                                  use16)
     if y16 is not None:
         y._cwf16x = y16
     if carry_link is not None and xc is not None:
         xc._cwf_carry = carry_link
     if xc is not None and getattr(x, "_cwf_catbuf", None) is not None:
         xc._cwf_catbuf = x._cwf_catbuf                   # the carried alias of a skip tensor still names its concatenation buffer
-    ok16 = getattr(backend(), "bf16_operands_ok", None)
-    if ok16 is not None and out_scale is None and torch.is_grad_enabled() and \
-            ok16(spec.op, spec.cin, spec.cout, y.shape[1] * y.shape[2] * y.shape[3]):
+    if use16 and out_scale is None:
         # whoever computes dL/dy (an InstanceNorm-backward apply pass) adds its bf16 image: this layer's kernels take it -- both of
         # them ("only") if its data gradient reads bf16 images too
-        okd = getattr(backend(), "bf16_dgrad_ok", None)
         # (with a residual the fp32 gradient is needed as well: it is the residual's gradient)
-        y._cwf_want16 = "only" if (_SINGLE_CONSUMER and residual is None and okd is not None and
-                                   y.shape[-1] == spec.cout and okd(spec.op, spec.cin, spec.cout, y.shape)) else True
+        y._cwf_want16 = "only" if (_SINGLE_CONSUMER and residual is None and y.shape[-1] == spec.cout and
+                                   backend().bf16_dgrad_ok(spec.op, spec.cin, spec.cout, y.shape)) else True
     st = (s1, s2) if want_stats else None
     return (y, st, xc) if carry else (y, st)
 
@@ -512,38 +574,22 @@ class _GroupedConvFn(torch.autograd.Function):
         ca = s0.cout_alloc or cout
         dy_all = dy_all.contiguous()
         sink = active_sink()
-        grads = []
-        views = None
-        if sink is not None and all(spec.uses <= 1 and spec.has_bias_map for spec in specs) and all(ctx.needs_input_grad[2:]):
-            views = [(sink.view(wb[2 * q]), sink.view(wb[2 * q + 1])) for q in range(G)]
-            if any(v[0] is None or v[1] is None for v in views):
-                views = None
-        if views is not None:
+        grads = [None, None] * G
+        xs = [x_all[..., q * cin:(q + 1) * cin] for q in range(G)]
+        dys = [dy_all[..., q * ca:q * ca + cout] for q in range(G)]
+        views = [_sink_views(sink, spec, wb[2 * q], wb[2 * q + 1], ctx.needs_input_grad[2 + 2 * q]) for q, spec in enumerate(specs)]
+        if all(v is not None for v in views) and all(spec.has_bias_map for spec in specs) and all(ctx.needs_input_grad[2:]):
             # gradient-sink path: the G layers' slabs in ONE launch (their reductions are rows of the phase's batched reduce)
-            K.wgrad_to_grouped(list(specs), s0.op, [x_all[..., q * cin:(q + 1) * cin] for q in range(G)],
-                               [dy_all[..., q * ca:q * ca + cout] for q in range(G)], cout, [spec.inv_map for spec in specs],
+            K.wgrad_to_grouped(list(specs), s0.op, xs, dys, cout, [spec.inv_map for spec in specs],
                                [v[0] for v in views], [v[1] for v in views], allow_async=True)
-            for q in range(G):
-                sink.mark(wb[2 * q]); sink.mark(wb[2 * q + 1])
-            grads = [None, None] * G
-        for q, spec in enumerate(specs if views is None else ()):
-            w, b = wb[2 * q], wb[2 * q + 1]
-            xs = x_all[..., q * cin:(q + 1) * cin]
-            dys = dy_all[..., q * ca:q * ca + cout]
-            sw = sink.view(w) if (sink is not None and spec.uses <= 1 and ctx.needs_input_grad[2 + 2 * q]) else None
-            sb = sink.view(b) if (sw is not None and b is not None) else None
-            if sw is not None and (b is None or sb is not None):
-                K.wgrad_to(spec, spec.op, xs, None, None, 1.0, dys, cout, spec.inv_map, sw, sb if spec.has_bias_map else None, allow_async=True)
-                sink.mark(w)
-                if sb is not None:
-                    sink.mark(b)
-                grads += [None, None]
-            elif ctx.needs_input_grad[2 + 2 * q]:
-                dwf, db = K.wgrad(spec.op, xs, None, None, 1.0, dys, cout, spec.inv_map, spec.has_bias_map, w.numel(), w_ref_shape=w.shape,
-                                  allow_async=spec.uses <= 1 and w.grad is None)
-                grads += [dwf.view(w.shape), db]
-            else:
-                grads += [None, None]
+            for t in wb:
+                sink.mark(t)
+        else:
+            for q, spec in enumerate(specs):         # layer by layer, each by its own route
+                if views[q] is not None:
+                    _wgrad_to_sink(K, sink, views[q], spec, xs[q], (None, None, 1.0), dys[q], wb[2 * q], wb[2 * q + 1], None, None, None, True)
+                elif ctx.needs_input_grad[2 + 2 * q]:
+                    grads[2 * q:2 * q + 2] = _wgrad_autograd(K, spec, xs[q], (None, None, 1.0), dys[q], wb[2 * q], True)
         dx_all = None
         if ctx.needs_input_grad[0]:
             dx_all = torch.empty(x_all.shape, dtype=torch.float32, device=x_all.device)
@@ -598,12 +644,9 @@ class _NormActAddFn(torch.autograd.Function):
         # tail's WHOLE dL/dy: a consumer conv() never saw (the loss, any torch op) makes autograd hand over the sum of both gradients, a
         # new tensor (never the conv's dx accumulated in place: the link holds a reference to it) -- the tail then reduces for itself
         if sums is not None and not link.shared and made_for is not None and (dy is made_for or dy.data_ptr() == made_for.data_ptr()):
-            if ctx.up16 and "dx" in getattr(K, "APPLY_EMITS", ()):
-                only16 = ctx.up16 == "only" and ctx.single and active_sink() is not None
-                dx, dx16, _ = K.in_bwd_apply16(dy, x, scale, shift, ctx.slope, sums, want_dx16=True, need_f32=not only16)
-                dx._cwf16 = dx16
-                if only16:
-                    dx._cwf_f32_missing = True
+            if ctx.up16 and "dx" in K.APPLY_EMITS:
+                dx, _ = _apply16(K, dy, x, scale, shift, ctx.slope, sums, None, True, False,
+                                 only16=ctx.up16 == "only" and ctx.single and active_sink() is not None)
             else:
                 dx = K.in_bwd_apply(dy, x, scale, shift, ctx.slope, sums)
         else:
@@ -615,9 +658,7 @@ def norm_act_add(x, stats, slope, residual=None, emit16=False):
     """emit16: the consumer of y is a full-resolution 16-channel conv without prologue -- y also leaves as a bf16 image, the operand
     of that conv's weight gradient (HipBackend.bf16_operands_ok)."""
     link = NaaLink(x, stats[0], stats[1], float(slope)) if torch.is_grad_enabled() else None
-    ok16 = getattr(backend(), "bf16_operands_ok", None)
-    want16 = bool(emit16 and torch.is_grad_enabled() and ok16 is not None and "xa" in getattr(backend(), "APPLY_EMITS", ()) and
-                  ok16(pk.CONV3_S1, x.shape[-1], x.shape[-1], x.shape[1] * x.shape[2] * x.shape[3]))
+    want16 = bool(emit16 and _wgrad_images(pk.CONV3_S1, x.shape[-1], x.shape[-1], x.shape[1] * x.shape[2] * x.shape[3], emit=True))
     y, y16 = _NormActAddFn.apply(x, stats[0], stats[1], float(slope), residual, link, want16)
     if link is not None:
         y._cwf_link = link                           # picked up by the conv that takes y as its (un-normalised) input

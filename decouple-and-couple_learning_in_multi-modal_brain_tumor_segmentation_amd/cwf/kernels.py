@@ -7,8 +7,8 @@ passed zero-copy as (data_ptr, ldc = stride(3)).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
-
 import threading
 
 import numpy as np
@@ -133,6 +133,8 @@ class HipBackend:
         self._wg_pending = []                  # descriptor rows awaiting the batched reduce (wgrad_flush)
         self._wg_held = []                     # launches held back while wgrad_defer is set (wgrad_release)
         self._wg_keep = []                     # operands of released launches, referenced until join_wgrad_stream
+        self._wg_sync_needed = False           # a main-stream launch queued slabs: the side-stream reduce must wait for it (wgrad_flush)
+        self._zero16 = {}                      # device -> 64 zero bytes, the halo source of the LDS-DMA kernels (zero16)
         self.flush_every_default = 10
         self.flush_every = self.flush_every_default
         self.wgrad_defer = False
@@ -302,13 +304,10 @@ class HipBackend:
         return bool(self.lib.cwf_conv_x16_ok(op, n, d, h, w, cout, cin))
 
     def zero16(self, device):
-        z = getattr(self, "_zero16", None)
-        if z is None:
-            z = self._zero16 = {}
         device = torch.device(device)
-        t = z.get(device)
+        t = self._zero16.get(device)
         if t is None:
-            t = z[device] = torch.zeros(64, dtype=torch.uint8, device=device)
+            t = self._zero16[device] = torch.zeros(64, dtype=torch.uint8, device=device)
         return t
 
     def in_bwd_apply16(self, dy, x, scale, shift, slope, sums, dx_add=None, want_dx16=False, want_xa16=False, need_f32=True):
@@ -342,13 +341,8 @@ class HipBackend:
     def to_bf16_side(self, x, scale, shift, slope):
         if not self.wgrad_async:
             return self.to_bf16(x, scale, shift, slope)
-        side = self.wgrad_stream(x.device)
-        side.wait_stream(torch.cuda.current_stream(x.device))
-        with torch.cuda.stream(side):
+        with self._on_side_stream(x.device, x, scale, shift):
             y = self.to_bf16(x, scale, shift, slope)
-        for t in (x, scale, shift):
-            if t is not None:
-                t.record_stream(side)
         y.record_stream(torch.cuda.current_stream(x.device))      # (consumed on the side stream; freed by whoever drops the last reference)
         return y
 
@@ -392,18 +386,24 @@ class HipBackend:
             torch.cuda.current_stream(st.device).wait_stream(st)
         self._wg_keep.clear()                  # (blocks freed now are reused in main-stream order, which follows the side stream)
 
+    @contextlib.contextmanager
+    def _on_side_stream(self, device, *operands):
+        """The hand-off to the weight-gradient side stream: it waits for the current stream, the launches of the body go to it, and on
+        a normal exit every operand given (None: skipped) is recorded on it, so that its block is not reused before the side stream
+        has passed this point.  Also under hipGraph capture: the side stream joins the capture through wait_stream and becomes a
+        parallel branch of the graph; record_stream defers the operands' blocks until the capture ends (no reuse inside the graph)."""
+        side = self.wgrad_stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            yield
+        for t in operands:
+            if t is not None:
+                t.record_stream(side)
+
     def wgrad(self, op, x, in_scale, in_shift, slope, dy, cout, inv_map, has_bias_map, w_numel, w_ref_shape=None, prec=None, allow_async=False):
         if self.wgrad_async and allow_async:
-            # also under hipGraph capture: the side stream joins the capture through wait_stream and becomes a parallel branch of
-            # the graph; record_stream defers the operands' blocks until the capture ends (no reuse inside the graph)
-            side = self.wgrad_stream(x.device)
-            side.wait_stream(torch.cuda.current_stream(x.device))
-            with torch.cuda.stream(side):
-                out = self._wgrad_impl(op, x, in_scale, in_shift, slope, dy, cout, inv_map, has_bias_map, w_numel, w_ref_shape, prec)
-            for t in (x, dy, in_scale, in_shift):
-                if t is not None:
-                    t.record_stream(side)
-            return out
+            with self._on_side_stream(x.device, x, dy, in_scale, in_shift):
+                return self._wgrad_impl(op, x, in_scale, in_shift, slope, dy, cout, inv_map, has_bias_map, w_numel, w_ref_shape, prec)
         return self._wgrad_impl(op, x, in_scale, in_shift, slope, dy, cout, inv_map, has_bias_map, w_numel, w_ref_shape, prec)
 
     # Gradient-sink form (cwf.optim.GradSink, used by the Trainer): the layer's split-K slabs go to a buffer of its own and the
@@ -423,10 +423,7 @@ class HipBackend:
             return
         # ONE hand-over to the side stream for the whole batch (instead of an event + stream switch + four record_stream calls per
         # launch); the operands stay referenced until the side stream is joined (join_wgrad_stream) instead of being recorded on it
-        dev = held[0][2].device
-        side = self.wgrad_stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+        with self._on_side_stream(held[0][2].device):
             for args in held:
                 self._wgrad_to_impl(*args)
         self._wg_keep.extend(held)
@@ -435,11 +432,8 @@ class HipBackend:
         """out[c] = sum over (n, voxels) of dy[..., c] (the bias gradient of a layer whose slabs carry no bias row): a full pass over
         dy that only the optimizer waits for -- on the weight-gradient side stream when that is in use."""
         if self.wgrad_async and allow_async:
-            side = self.wgrad_stream(dy.device)
-            side.wait_stream(torch.cuda.current_stream(dy.device))
-            with torch.cuda.stream(side):
+            with self._on_side_stream(dy.device, dy):
                 self.stats_channel_sum(self.in_stats(dy), out)
-            dy.record_stream(side)
         else:
             self.stats_channel_sum(self.in_stats(dy), out)
             self._wg_sync_needed = self.wgrad_async
@@ -460,13 +454,8 @@ class HipBackend:
             self._wg_held.append((key, op, x, in_scale, in_shift, slope, dy, cout, inv_map, dw_dst, db_dst, prec, x16, dy16, dy_scale))
             return
         if self.wgrad_async and allow_async:
-            side = self.wgrad_stream(x.device)
-            side.wait_stream(torch.cuda.current_stream(x.device))
-            with torch.cuda.stream(side):
+            with self._on_side_stream(x.device, x, dy, in_scale, in_shift, x16, dy16, dy_scale):
                 self._wgrad_to_impl(key, op, x, in_scale, in_shift, slope, dy, cout, inv_map, dw_dst, db_dst, prec, x16, dy16, dy_scale)
-            for t in (x, dy, in_scale, in_shift, x16, dy16, dy_scale):
-                if t is not None:
-                    t.record_stream(side)
         else:
             self._wgrad_to_impl(key, op, x, in_scale, in_shift, slope, dy, cout, inv_map, dw_dst, db_dst, prec, x16, dy16, dy_scale)
             self._wg_sync_needed = self.wgrad_async          # a main-stream producer: the side-stream reduce must wait for it
@@ -496,15 +485,8 @@ class HipBackend:
         # eligible layers always take the bf16-image kernel; an image nobody handed over is made here, i.e. on the stream this launch
         # runs on (normally the side stream, which has slack: the main stream's kernels are the step's critical path)
         use16 = self.bf16_operands_ok(op, cin, cout, do * ho * wo) if prec is None else 0
-        nsplit = self.lib.cwf_wgrad_nsplit(op, n, do, ho, wo, cin, cout)
-        slab = self.lib.cwf_wgrad_slab_floats(op, cin, cout)
-        if nsplit <= 0 or slab <= 0 or slab != inv_map.numel():
-            raise _lib.CwfError("cwf_wgrad plan failed (%d, %d, %d)" % (nsplit, slab, inv_map.numel()))
-        pk_ = (key, x.device)                 # persistent, also across graph capture: the descriptor tables below stay valid
-        part = self._wg_part.get(pk_)
-        if part is None or part.numel() < nsplit * slab:
-            part = torch.empty(int(nsplit * slab), dtype=_f32, device=x.device)
-            self._wg_part[pk_] = part
+        nsplit, slab = self._wgrad_plan(op, dy.shape, cin, cout, (inv_map,))
+        part = self._wgrad_slabs(key, x.device, nsplit * slab)
         a = self._wgrad_args(op, x, x_ldc, in_scale, in_shift, slope, dy, dy_ldc, cout, part, prec)
         if use16:
             if x16 is None:
@@ -518,6 +500,24 @@ class HipBackend:
         used = ctypes.c_int(0)
         self._call("cwf_wgrad", ctypes.addressof(a), ctypes.addressof(used), self._stream())
         self._wg_pending.append((part.data_ptr(), inv_map.data_ptr(), dw_dst.data_ptr(), _p(db_dst), int(slab), int(used.value)))
+
+    def _wgrad_plan(self, op, dy_shape, cin, cout, inv_maps):
+        """(nsplit, slab): the library's split-K plan of a layer with output gradient [n, do, ho, wo, .] -- at most nsplit slabs of
+        `slab` floats -- checked against the layer's (the group's layers') inverse maps"""
+        n, do, ho, wo = dy_shape[:4]
+        nsplit = self.lib.cwf_wgrad_nsplit(op, n, do, ho, wo, cin, cout)
+        slab = self.lib.cwf_wgrad_slab_floats(op, cin, cout)
+        if nsplit <= 0 or slab <= 0 or any(slab != m.numel() for m in inv_maps):
+            raise _lib.CwfError("cwf_wgrad plan failed (%d, %d, %s)" % (nsplit, slab, [m.numel() for m in inv_maps]))
+        return nsplit, slab
+
+    def _wgrad_slabs(self, key, device, nfloats):
+        """the slab buffer of layer `key` on `device`: persistent, also across graph capture, so the descriptor tables of wgrad_flush
+        stay valid"""
+        part = self._wg_part.get((key, device))
+        if part is None or part.numel() < nfloats:
+            part = self._wg_part[(key, device)] = torch.empty(int(nfloats), dtype=_f32, device=device)
+        return part
 
     @staticmethod
     def _wgrad_args(op, x, x_ldc, in_scale, in_shift, slope, dy, dy_ldc, cout, part, prec):
@@ -537,13 +537,8 @@ class HipBackend:
                 self.wgrad_to(keys[q], op, xs[q], None, None, 1.0, dys[q], cout, inv_maps[q], dw_dsts[q], db_dsts[q], prec=prec, allow_async=allow_async)
             return
         if self.wgrad_async and allow_async:
-            dev = xs[0].device
-            side = self.wgrad_stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
+            with self._on_side_stream(xs[0].device, *xs, *dys):
                 self._wgrad_to_grouped_impl(keys, op, xs, dys, cout, inv_maps, dw_dsts, db_dsts, mode)
-            for t in list(xs) + list(dys):
-                t.record_stream(side)
         else:
             self._wgrad_to_grouped_impl(keys, op, xs, dys, cout, inv_maps, dw_dsts, db_dsts, mode)
             self._wg_sync_needed = self.wgrad_async
@@ -554,19 +549,11 @@ class HipBackend:
         d0, dy_ldc = cl(dys[0])
         n, di, hi, wi, cin = x0.shape
         _, do, ho, wo, _ = d0.shape
-        nsplit = self.lib.cwf_wgrad_nsplit(op, n, do, ho, wo, cin, cout)
-        slab = self.lib.cwf_wgrad_slab_floats(op, cin, cout)
-        if nsplit <= 0 or slab <= 0 or any(slab != m.numel() for m in inv_maps):
-            raise _lib.CwfError("cwf_wgrad plan failed (%d, %d)" % (nsplit, slab))
+        nsplit, slab = self._wgrad_plan(op, d0.shape, cin, cout, inv_maps)
         parts = []
         for q in range(G):
             assert xs[q].stride() == xs[0].stride() and dys[q].stride() == dys[0].stride() and xs[q].shape == xs[0].shape
-            pk_ = (keys[q], x0.device)
-            part = self._wg_part.get(pk_)
-            if part is None or part.numel() < nsplit * slab:
-                part = torch.empty(int(nsplit * slab), dtype=_f32, device=x0.device)
-                self._wg_part[pk_] = part
-            parts.append(part)
+            parts.append(self._wgrad_slabs(keys[q], x0.device, nsplit * slab))
         a = _lib.WgradArgs(op=op, precision=_lib.PRECISION[mode], x_ldc=x_ldc, in_slope=1.0, dy_ldc=dy_ldc, groups=G,
                            N=n, Di=di, Hi=hi, Wi=wi, Cin=cin, Do=do, Ho=ho, Wo=wo, Cout=cout)
         for q in range(G):
@@ -601,7 +588,7 @@ class HipBackend:
             self._wg_tables[key] = table
         if self.wgrad_async:
             side = self.wgrad_stream(device)
-            if getattr(self, "_wg_sync_needed", False):
+            if self._wg_sync_needed:
                 side.wait_stream(torch.cuda.current_stream(device))
                 self._wg_sync_needed = False
             with torch.cuda.stream(side):
@@ -613,12 +600,7 @@ class HipBackend:
         """returns (dW flat [w_numel], db [cout] or None)"""
         x, x_ldc = cl(x)
         dy, dy_ldc = cl(dy)
-        n, di, hi, wi, cin = x.shape
-        _, do, ho, wo, _ = dy.shape
-        nsplit = self.lib.cwf_wgrad_nsplit(op, n, do, ho, wo, cin, cout)
-        slab = self.lib.cwf_wgrad_slab_floats(op, cin, cout)
-        if nsplit <= 0 or slab <= 0 or slab != inv_map.numel():
-            raise _lib.CwfError("cwf_wgrad plan failed (%d, %d, %d)" % (nsplit, slab, inv_map.numel()))
+        nsplit, slab = self._wgrad_plan(op, dy.shape, x.shape[4], cout, (inv_map,))
         part = self.workspace("wgrad", nsplit * slab, x.device)
         a = self._wgrad_args(op, x, x_ldc, in_scale, in_shift, slope, dy, dy_ldc, cout, part, prec)
         used = ctypes.c_int(0)

@@ -12,7 +12,8 @@ Execution modes:
     (csrc/plan.hip: one hipModuleLaunchKernel per node on the capture's stream chains, events for the cross-stream edges; ONE
     Python -> C call per step, or one per gradient phase when data-parallel).  Host cost ~2 ms per step instead of ~16.
   * hipgraph (use_graph="hipgraph"): the same capture replayed with hipGraphLaunch -- slower end to end than eager on this ROCm
-    build (~44 us of host time per node); kept as the fallback for graphs the plan cannot express.
+    build (~44 us of host time per node); only on request.  A capture the plan cannot express (a copy node) is
+    dropped and the Trainer goes on with eager steps.
 Gradients never exist as per-parameter tensors: backward kernels write them into ONE flat buffer laid out in backward-completion
 order (cwf.optim.GradSink; the conv weight gradients through one batched split-K reduce per phase), which the fused Adam launch reads.
 Multi-GPU gradient averaging (the only data-path collective) is overlapped with backward: the model fires a callback when backward
@@ -169,10 +170,9 @@ class Trainer:
         if not self._in_backward:
             return
         K = kernels_backend()
-        if getattr(K, "wgrad_defer", False):
+        if K.wgrad_defer:
             # the decoder's weight gradients, queued during phase 0, start now: beside the GPU-light heads / couplers backward
             K.wgrad_release()
-            K.wgrad_defer = False
         K.wgrad_flush()
         if self.overlap_comm:
             self._allreduce_chunk(k)
@@ -216,16 +216,14 @@ class Trainer:
         else:
             loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device), topk=(self._topk_tensor(x.device), self.topk_percent))
         self.opt.zero_grad(set_to_none=True)
-        if hasattr(K, "flush_every_default"):
-            # graph modes: one reduce per phase, in warm-up too
-            K.flush_every = (1 << 30) if self.use_graph else K.flush_every_default
-        if hasattr(K, "wgrad_release"):
-            K.wgrad_defer = self.wgrad_async and hasattr(self.model, "phase_callback")
+        # graph modes: one reduce per phase, in warm-up too
+        K.flush_every = (1 << 30) if self.use_graph else K.flush_every_default
+        K.wgrad_defer = self.wgrad_async and hasattr(self.model, "phase_callback")
         self._in_backward = True
         try:
             with sink:
                 loss.backward()
-                if getattr(K, "wgrad_defer", False):
+                if K.wgrad_defer:
                     K.wgrad_release()      # (no cut point fired: plain module)
                 K.wgrad_flush()            # the last phase (encoder)
         finally:

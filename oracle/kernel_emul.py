@@ -75,10 +75,42 @@ def _u01(seed, step, ctr):
 class EmulBackend:
     name = "emul"
 
+    # What the autograd glue (cwf/functional.py) and the Trainer ask a backend besides its kernels, under HipBackend's names: the
+    # emulation writes no bf16 images, fuses no InstanceNorm-backward sums and has no side stream.
+    APPLY_EMITS = ()
+    flush_every_default = 10
+
     def __init__(self):
         self._seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
         self._step = 0
         self._site = 0
+        self.wgrad_async = False
+        self.wgrad_defer = False
+        self.flush_every = self.flush_every_default
+
+    def bf16_operands_ok(self, op, cin, cout, nvox):
+        return 0
+
+    def bf16_dgrad_ok(self, op, cin, cout, shape):
+        return False
+
+    def dy_scale_ok(self, op, cin, cout, nvox):
+        return False
+
+    def supports_fused_norm_bwd(self, prec=None):
+        return False
+
+    def channel_sum_to(self, dy, out, allow_async=False):
+        return self.stats_channel_sum(self.in_stats(dy), out)
+
+    def to_bf16_side(self, x, scale, shift, slope):
+        return (x if scale is None else _prologue(x, scale, shift, slope)).to(torch.bfloat16)
+
+    def wgrad_release(self):
+        self.wgrad_defer = False
+
+    def join_wgrad_stream(self):
+        pass
 
     # ------------------------------------------------------------------ K12: counter-based dropout (bit-exact with cwf_keep)
     def set_rng(self, seed, step):

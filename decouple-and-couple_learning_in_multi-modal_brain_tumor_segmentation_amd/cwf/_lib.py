@@ -63,6 +63,8 @@ SIGNATURES = {
     "cwf_grad_add": [P, P, P, L, P],
     "cwf_grad_norm_clip": [P, L, F, F, P, P, P],
     "cwf_adam_amsgrad_ex": [P, I, L, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I, I, P, F, P, P, F, P],
+    "cwf_optim_step": [I, P, I, L, C.c_double, C.c_double, P, C.c_double, C.c_double, C.c_double, I, I, P, C.c_double, C.c_double, I, I,
+                       F, P, P, F, P],
     "cwf_wgrad_reduce_batched": [P, I, P],
     "cwf_dropout_mask": [P, L, F, F, C.c_uint64, C.c_uint64, P],
     "cwf_mul": [P, P, P, L, P],
@@ -252,6 +254,7 @@ class WindowGrid(C.Structure):
 
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
 GRADNORM_WS_DOUBLES = 1024     # CWF_GRADNORM_WS_DOUBLES
+RULE_ADAMW, RULE_SGD = 1, 2    # CWF_RULE_ADAMW, CWF_RULE_SGD
 RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
                  "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace",
                  "cwf_topk_ce_workspace"}

@@ -1811,6 +1811,24 @@ class HipBackend:
         self._call("cwf_adam_amsgrad_ex", table.data_ptr(), ntensors, max_n, lr, beta1, beta2, eps, wd, step, int(amsgrad),
                    _p(hyper_dev), float(grad_scale), _p(gscale_dev), _p(ema_table), float(ema_weight), self._stream())
 
+    # ------------------------------------------------------------------ K14 AdamW / SGD rules (csrc/optim_rules.hip)
+    def optim_step(self, rule, table, ntensors, max_n, lr, wd, wd_mul=None, beta1=0.9, beta2=0.999, eps=1e-8, step=0, amsgrad=False,
+                   hyper_dev=None, momentum=0.0, dampening=0.0, nesterov=False, first=False, grad_scale=1.0, gscale_dev=None,
+                   ema_table=None, ema_weight=0.0):
+        """One launch of rule "adamw" (torch.optim.AdamW) or "sgd" (torch.optim.SGD; the momentum buffer is the table's exp_avg
+        column, `first`: this is the buffers' first update) over a descriptor table.  wd_mul: float32 [ntensors] on the GPU, the
+        per-tensor multiplier of wd (None: all ones); gscale_dev / ema_table / ema_weight as in adam_ex."""
+        rules = {"adamw": _lib.RULE_ADAMW, "sgd": _lib.RULE_SGD}
+        if rule not in rules:
+            raise ValueError("optim_step: rule must be 'adamw' or 'sgd', got %r" % (rule,))
+        if wd_mul is not None and (wd_mul.dtype != _f32 or wd_mul.numel() != ntensors or not wd_mul.is_cuda or not wd_mul.is_contiguous()):
+            raise ValueError("optim_step: wd_mul must hold one float32 per tensor, on the GPU")
+        if ema_table is not None and (ema_table.dtype != torch.int64 or ema_table.numel() != ntensors or not ema_table.is_cuda):
+            raise ValueError("optim_step: ema_table must hold one int64 device address per tensor, on the GPU")
+        self._call("cwf_optim_step", rules[rule], table.data_ptr(), ntensors, max_n, float(lr), float(wd), _p(wd_mul), float(beta1),
+                   float(beta2), float(eps), int(step), int(amsgrad), _p(hyper_dev), float(momentum), float(dampening), int(nesterov),
+                   int(first), float(grad_scale), _p(gscale_dev), _p(ema_table), float(ema_weight), self._stream())
+
     def dropout_mask(self, shape, p, device, p2=0.0):
         """Pre-scaled keep mask(s) in one launch from the device generator state (capturable: the state advances by a kernel)."""
         m = torch.empty(shape, dtype=_f32, device=device)

@@ -41,6 +41,10 @@ Step controls (all off by default; then the step issues exactly the launches des
     (tools.topk_ce: mean of -log p_target over the hardest K % of the batch's voxels, selected exactly on the device), in front of
     the same backward.  w lives in a one-float device tensor (set_topk_weight() needs no recapture); K is fixed at construction, k
     being a launch argument.  None: the step makes no new call and calls total_loss as before.
+  * optimizer = "adamw" | "sgd" (with betas / momentum, nesterov / no_decay): the update is one launch of the AdamW or SGD rule
+    (cwf.optim.FusedAdamW / FusedSGD) in place of Adam's; sink, all-reduce, accumulation, clipping and EMA are the base class's and
+    work as above.  schedule = "cosine" | "constant" and warmup_steps = W shape the learning rate of an update:
+    schedule(init_lr, epoch, end_epoch) * min(1, (updates_done + 1) / W), updates_done counting weight updates.
 Checkpoints use the reference layout {'epoch', 'state_dict' with 'module.' prefix, 'optim_dict'} (:248-253)."""
 from __future__ import annotations
 
@@ -50,7 +54,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from .optim import FusedAdam, poly_lr
+from .optim import FusedAdam, FusedAdamW, FusedSGD, SCHEDULES, poly_lr, schedule_lr, warmup_factor
 
 
 def total_loss(outputs, target, edge, boundary=None, topk=None):
@@ -108,7 +112,8 @@ def kernels_backend():
 class Trainer:
     def __init__(self, model, lr=2e-4, weight_decay=1e-5, amsgrad=True, end_epoch=1000, use_graph=False,
                  graph_warmup=2, overlap_comm=True, wgrad_async=True, accum_steps=1, max_grad_norm=None, ema_decay=None,
-                 boundary_weight=None, topk_weight=None, topk_percent=10.0):
+                 boundary_weight=None, topk_weight=None, topk_percent=10.0, optimizer="adam", betas=(0.9, 0.999), momentum=0.0,
+                 nesterov=False, no_decay=None, schedule="poly", warmup_steps=0):
         self.boundary_weight = check_boundary_weight(boundary_weight)
         self._boundary = None                           # the weight as a one-float device tensor, made at the first step that needs it
         self.topk_weight, self.topk_percent = check_topk(topk_weight, topk_percent)
@@ -121,8 +126,25 @@ class Trainer:
         self._micro = 0                                 # micro-steps of the current window already accumulated
         self._last_micro = True                         # this call ends its window: fold, collectives, update
         phases = model.grad_phases() if hasattr(model, "grad_phases") else None
-        self.opt = FusedAdam(model.parameters(), lr=lr, weight_decay=weight_decay, amsgrad=amsgrad, phases=phases,
-                             max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+        if schedule not in SCHEDULES:
+            raise ValueError("schedule must be one of %s, got %r" % (", ".join(SCHEDULES), schedule))
+        if int(warmup_steps) != warmup_steps or warmup_steps < 0:
+            raise ValueError("warmup_steps must be an integer >= 0")
+        self.schedule, self.warmup_steps = schedule, int(warmup_steps)
+        controls = dict(phases=phases, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+        if optimizer == "adam":
+            if no_decay is not None:
+                raise ValueError("optimizer='adam' decays every parameter: no_decay needs optimizer='adamw' or 'sgd'")
+            self.opt = FusedAdam(model.parameters(), lr=lr, betas=betas, weight_decay=weight_decay, amsgrad=amsgrad, **controls)
+        elif optimizer == "adamw":
+            self.opt = FusedAdamW(model.named_parameters(), lr=lr, betas=betas, weight_decay=weight_decay, amsgrad=amsgrad,
+                                  no_decay=no_decay, **controls)
+        elif optimizer == "sgd":
+            self.opt = FusedSGD(model.named_parameters(), lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
+                                no_decay=no_decay, **controls)
+        else:
+            raise ValueError("optimizer must be 'adam', 'adamw' or 'sgd', got %r" % (optimizer,))
+        self.optimizer = optimizer
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # collectives on: more than one rank, or a one-rank group with CWF_FORCE_COMM=1 (exercises the RCCL path on a one-GPU box)
         self.comm = self.world > 1 or (dist.is_available() and dist.is_initialized() and os.environ.get("CWF_FORCE_COMM", "0") == "1")
@@ -371,7 +393,7 @@ class Trainer:
         device tensors (no host sync); a boundary_weight and a topk_weight each append a part, in that order."""
         self._last_micro = self._micro + 1 >= self.accum_steps
         if self._last_micro:
-            self.opt.param_groups[0]["lr"] = float(poly_lr(self.init_lr, epoch, self.end_epoch))   # plain float: checkpoints stay weights_only-loadable
+            self.opt.param_groups[0]["lr"] = self.learning_rate(epoch)    # plain float: checkpoints stay weights_only-loadable
         if self.use_graph and self._graph is None and self._eager_steps >= self._graph_warmup:
             torch.cuda.synchronize()
             self._capture(x, target, edge)
@@ -406,6 +428,19 @@ class Trainer:
         self.opt.advance_host()
         self.opt.launch()
         return loss, parts
+
+    @property
+    def updates_done(self):
+        """weight updates made so far (not micro-steps); an optimizer state loaded into self.opt restores it"""
+        return self.opt._steps
+
+    def learning_rate(self, epoch):
+        """The learning rate of the NEXT update if it falls into `epoch`: schedule(init_lr, epoch, end_epoch) times the linear warm-up
+        factor min(1, (updates_done + 1) / warmup_steps).  With the defaults this is float(poly_lr(...)), as it always was."""
+        lr = schedule_lr(self.schedule, self.init_lr, epoch, self.end_epoch)
+        if self.warmup_steps:
+            lr *= warmup_factor(self.updates_done, self.warmup_steps)
+        return float(lr)
 
     def _folds_per_chunk(self):
         """the phase slices are all-reduced one by one (each behind its own fold): the condition _finish_comm waits under"""

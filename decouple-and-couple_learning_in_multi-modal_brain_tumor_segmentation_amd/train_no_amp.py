@@ -142,7 +142,39 @@ def build_parser():
                         "line gains topk_loss.  Default: off")
     p.add_argument("--topk_percent", default=10.0, type=float,
                    help="K in (0, 100]: the share of the batch's voxels the top-k term averages over (fixed for the run).  Default: 10")
+    p.add_argument("--optimizer", default="adam", choices=("adam", "adamw", "sgd"),
+                   help="the update rule of the fused step: adam (the reference: L2 decay in the gradient, --amsgrad), adamw (decoupled "
+                        "decay, --beta1 / --beta2 / --amsgrad) or sgd (--momentum, --nesterov); --lr and --weight_decay apply to all")
+    p.add_argument("--momentum", default=0.0, type=float, help="(--optimizer sgd) momentum >= 0; nnU-Net trains with 0.99 and --nesterov true")
+    p.add_argument("--nesterov", default=False, type=_bool, help="(--optimizer sgd) Nesterov momentum; needs --momentum > 0")
+    p.add_argument("--beta1", default=0.9, type=float, help="(--optimizer adam / adamw) decay of the first moment, in [0, 1)")
+    p.add_argument("--beta2", default=0.999, type=float, help="(--optimizer adam / adamw) decay of the second moment, in [0, 1)")
+    p.add_argument("--no_decay", default=None, choices=("bias_norm",),
+                   help="(--optimizer adamw / sgd) bias_norm: no weight decay on parameters with at most one dimension (biases, norm "
+                        "gains, the couplers' tokens).  Default: every parameter is decayed")
+    p.add_argument("--lr_schedule", default="poly", choices=("poly", "cosine", "constant"),
+                   help="the learning rate of an epoch: poly (the reference: lr (1 - epoch / end_epoch)^0.9), cosine "
+                        "(lr / 2 (1 + cos(pi epoch / end_epoch))) or constant")
+    p.add_argument("--warmup_steps", default=0, type=int,
+                   help="W >= 0: multiply the scheduled rate by min(1, n / W) at the n-th weight update (with --accum_steps N once per "
+                        "window).  Default: 0, no warm-up")
     return p
+
+
+def check_optimizer(args):
+    """the values of --optimizer and the flags that go with it (SystemExit with the rule, like the other checks)"""
+    if not 0.0 <= args.momentum < float("inf"):
+        raise SystemExit("--momentum takes a finite momentum >= 0")
+    if args.nesterov and not (args.optimizer == "sgd" and args.momentum > 0.0):
+        raise SystemExit("--nesterov needs --optimizer sgd and --momentum > 0")
+    if args.momentum != 0.0 and args.optimizer != "sgd":
+        raise SystemExit("--momentum belongs to --optimizer sgd")
+    if not (0.0 <= args.beta1 < 1.0 and 0.0 <= args.beta2 < 1.0):
+        raise SystemExit("--beta1 / --beta2 take values in [0, 1)")
+    if args.no_decay is not None and args.optimizer == "adam":
+        raise SystemExit("--no_decay needs --optimizer adamw or sgd (adam folds the decay of every parameter into its gradient)")
+    if args.warmup_steps < 0:
+        raise SystemExit("--warmup_steps takes a number of weight updates >= 0")
 
 
 def check_topk(args):
@@ -271,6 +303,7 @@ def main(argv=None):
     check_step_controls(args)
     check_boundary(args)
     check_topk(args)
+    check_optimizer(args)
     from cwf import kernels
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint
@@ -315,7 +348,8 @@ def main(argv=None):
                       use_graph={"eager": False, "plan": "plan", "hipgraph": "hipgraph"}[args.step_mode] if use_cuda else False,
                       accum_steps=args.accum_steps, max_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay,
                       boundary_weight=boundary_weight_at(args, args.start_epoch), topk_weight=args.topk_weight,
-                      topk_percent=args.topk_percent)
+                      topk_percent=args.topk_percent, optimizer=args.optimizer, betas=(args.beta1, args.beta2), momentum=args.momentum,
+                      nesterov=args.nesterov, no_decay=args.no_decay, schedule=args.lr_schedule, warmup_steps=args.warmup_steps)
     clip, use_ema, use_boundary = args.clip_grad_norm is not None, args.ema_decay is not None, args.boundary_weight is not None
     use_topk = args.topk_weight is not None
     if use_ema and os.path.isfile(args.resume) and args.load:

@@ -814,6 +814,36 @@ int cwf_adam_amsgrad_ex(const struct cwf_adam_desc* table, int ntensors, int64_t
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K14 further update rules of the fused step (csrc/optim_rules.hip): one launch over a cwf_adam_desc table, as above
+ * ---------------------------------------------------------------------------------------------- */
+/* CWF_RULE_ADAMW -- torch.optim.AdamW (decoupled decay), per element, g = g_raw * scale:
+ *   p <- p * float(1 - lr * weight_decay * mul_t)                                (the factor is formed in double, once per workgroup)
+ *   m <- m + (1 - beta1) (g - m);  v <- beta2 v + (1 - beta2) g g;  amsgrad: vmax <- max(vmax, v) takes v's place below
+ *   p <- p - step_size * (m / (sqrt(v) / bc2_sqrt + eps)),  step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step), both
+ *   derived in double here; hyper_dev (nullable): device float[2] = {step_size, bc2_sqrt} that replaces them, as in cwf_adam_amsgrad
+ *   (the decay factor still uses the lr argument).  momentum, dampening, nesterov and first are ignored.
+ * CWF_RULE_SGD -- torch.optim.SGD, per element:
+ *   g <- g_raw * scale + float(weight_decay * mul_t) * p
+ *   momentum > 0:  buf <- g if `first` (the buffers' first update: dampening is not applied), else momentum * buf + (1 - dampening) g
+ *                  g <- g + momentum * buf with nesterov, else g <- buf
+ *   p <- p - lr * g
+ *   buf is the descriptor's m; v and vmax are never touched and may be null; with momentum = 0 neither is m.  beta1, beta2, eps,
+ *   step, amsgrad and hyper_dev are ignored.
+ * wd_mul (nullable): device array of ntensors floats, mul_t above -- 0 for a tensor that is not decayed, 1 otherwise; null: all ones.
+ * scale is grad_scale, or the device float gscale_dev[0] when gscale_dev is given (out2 of cwf_grad_norm_clip); ema_table and
+ * ema_weight as in cwf_adam_amsgrad_ex: ema += ema_weight * (p_new - ema) from the register that holds p_new.
+ * Gradients need 4-byte alignment only (slices of the flat buffer); every access is one float.
+ * CWF_E_BADARG, nothing launched: a null table; ntensors or max_n <= 0; a rule that is neither of the two; lr, weight_decay, momentum
+ * or dampening NaN or negative; an ema_table with ema_weight outside (0, 0.5]; AdamW: step <= 0 without hyper_dev, a beta outside
+ * [0, 1), eps NaN or negative; SGD: nesterov with momentum = 0 or dampening != 0 (torch's ValueError). */
+#define CWF_RULE_ADAMW 1
+#define CWF_RULE_SGD 2
+int cwf_optim_step(int rule, const struct cwf_adam_desc* table, int ntensors, int64_t max_n, double lr, double weight_decay,
+                   const float* wd_mul, double beta1, double beta2, double eps, int step, int amsgrad, const float* hyper_dev,
+                   double momentum, double dampening, int nesterov, int first,
+                   float grad_scale, const float* gscale_dev, float* const* ema_table, float ema_weight, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K12 / misc elementwise
  * ---------------------------------------------------------------------------------------------- */
 /* y[i] = a[i]*b[i]  (dropout masks) ; y = a + b ; y[n][v][c] = x[n][v][c]*s[n][c] (dropout3d) ; fill */

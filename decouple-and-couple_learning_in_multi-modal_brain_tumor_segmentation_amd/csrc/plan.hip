@@ -12,27 +12,34 @@
 // Marker nodes (cwf_plan_marker, captured on the communication stream behind the streams it waits for) cut the list into
 // segments: cwf_plan_run stops after a marker, the caller enqueues the data-parallel all-reduce of the finished gradient slice on
 // that stream, and continues -- the collective overlaps the rest of backward exactly as in eager mode.
+//
+// The order, the streams, the waits and the record flags are decided by plan_schedule.h, a host function without a HIP call
+// (cwf_plan_schedule exports it for tests on a machine without a GPU); this file maps the hipGraph to its inputs, owns the
+// streams and events, issues the list, and lets a test read a built plan back (cwf_plan_describe).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <queue>
+#include <string>
 #include <vector>
 #include "../../include/cwf_hip.h"
+#include "plan_schedule.h"
 
 namespace {
 
 __global__ void plan_marker_kernel(int id) { (void)id; }
 
-enum NodeKind { NK_KERNEL = 0, NK_MEMSET = 1, NK_EMPTY = 3, NK_MARKER = 4 };
-const int MAX_STREAMS = 2;      // the caller's stream and the weight-gradient stream
+using namespace cwf_plan;       // NodeKind, NodeClass, MAX_STREAMS, Schedule, schedule(): the pure part, plan_schedule.h
+static_assert(NK_KERNEL == CWF_PLAN_KERNEL && NK_MEMSET == CWF_PLAN_MEMSET && NK_EMPTY == CWF_PLAN_EMPTY && NK_MARKER == CWF_PLAN_MARKER, "");
+static_assert(NC_MAIN == CWF_PLAN_CLASS_MAIN && NC_SIDE == CWF_PLAN_CLASS_SIDE && NC_CONVERSION == CWF_PLAN_CLASS_CONVERSION, "");
 
 struct PlanNode {
     int kind = NK_EMPTY;
     int stream = 0;             // index into the run's stream set; -1 for markers (the caller's communication stream)
     int marker_id = -1;
+    int creation = -1;          // the node's index in the graph's node list (the order the host issued the work in)
+    std::string name;           // NK_KERNEL: what hipKernelNameRefByPtr gave (empty if it gave nothing)
     hipKernelNodeParams kp;     // NK_KERNEL (kernelParams / extra point into the graph node: the graph must outlive the plan)
     hipFunction_t fn = nullptr; // resolved once (hipGetFuncBySymbol); nullptr = launch through the host symbol
     hipMemsetParams ms;         // NK_MEMSET
@@ -43,6 +50,7 @@ struct PlanNode {
 
 struct Plan {
     std::vector<PlanNode> nodes;          // in issue order
+    std::vector<std::pair<int, int>> edges;   // the graph's edges in plan positions (cwf_plan_describe; the run does not read them)
     std::vector<hipStream_t> owned;       // stream 1, if any (stream 0 is the caller's)
     std::vector<hipEvent_t> join_ev;      // one per owned stream
     hipEvent_t start_ev = nullptr;
@@ -92,50 +100,61 @@ extern "C" int cwf_plan_create(void* graph_, void** out) {
         auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(h, -1));
         return (it != idx.end() && it->first == h) ? it->second : -1;
     };
-    std::vector<std::vector<int>> succ(n), pred(n);
+    std::vector<int> efrom(ne), eto(ne);
     for (size_t k = 0; k < ne; ++k) {
-        int a = find(ef[k]), b = find(et[k]);
-        if (a < 0 || b < 0) return CWF_E_BADARG;
-        succ[a].push_back(b);
-        pred[b].push_back(a);
+        efrom[k] = find(ef[k]);
+        eto[k] = find(et[k]);
+        if (efrom[k] < 0 || eto[k] < 0) return CWF_E_BADARG;
     }
-    // topological order, smallest creation index first
-    std::vector<int> indeg(n), order;
-    order.reserve(n);
-    std::priority_queue<int, std::vector<int>, std::greater<int>> ready;
+    // What the scheduler needs of every node, by creation index: its kind and its stream class.  The weight-gradient chain is
+    // recognised by its kernels (weight-gradient kernels, their operand conversions and slab reduces).  (A node type the plan cannot
+    // express is scheduled as an empty node and refused below, where its position is known.)
+    void* marker_fn = (void*)plan_marker_kernel;
+    std::vector<hipGraphNodeType> type(n);
+    std::vector<hipKernelNodeParams> kparams(n);
+    std::vector<const char*> kname(n, nullptr);
+    std::vector<int> kind(n, NK_EMPTY), cls(n, NC_MAIN);
     for (size_t i = 0; i < n; ++i) {
-        indeg[i] = (int)pred[i].size();
-        if (!indeg[i]) ready.push((int)i);
+        e = hipGraphNodeGetType(gn[i], &type[i]);
+        if (e != hipSuccess) return (int)e;
+        if (type[i] == hipGraphNodeTypeMemset) kind[i] = NK_MEMSET;
+        if (type[i] != hipGraphNodeTypeKernel) continue;
+        e = hipGraphKernelNodeGetParams(gn[i], &kparams[i]);
+        if (e != hipSuccess) return (int)e;
+        if (kparams[i].func == marker_fn && kparams[i].kernelParams) { kind[i] = NK_MARKER; continue; }
+        kind[i] = NK_KERNEL;
+        const char* nm = kname[i] = hipKernelNameRefByPtr(kparams[i].func, nullptr);
+        // (+ the bias-gradient sums of the transposed convs: in_reduce_kernel<0> + stats_channel_sum_kernel, cwf.kernels.channel_sum_to)
+        if (nm && (strstr(nm, "wgrad") || strstr(nm, "stats_channel_sum_kernel") ||
+                   strstr(nm, "in_reduce_kernelILi0") || strstr(nm, "in_reduce_kernel<0"))) cls[i] = NC_SIDE;
+        else if (nm && strstr(nm, "to_bf16_kernel")) cls[i] = NC_CONVERSION;      // decided by the scheduler: a conversion belongs where its readers are
     }
-    while (!ready.empty()) {
-        int u = ready.top();
-        ready.pop();
-        order.push_back(u);
-        for (int v : succ[u])
-            if (--indeg[v] == 0) ready.push(v);
-    }
-    if (order.size() != n) return CWF_E_BADARG;
-    std::vector<int> pos(n);
-    for (size_t i = 0; i < n; ++i) pos[order[i]] = (int)i;
+    (void)hipGetLastError();
+    Schedule S;
+    if (!schedule((int)n, kind.data(), cls.data(), (int)ne, efrom.data(), eto.data(), S)) return CWF_E_BADARG;
 
     Plan* P = new Plan();
     P->nodes.resize(n);
-    void* marker_fn = (void*)plan_marker_kernel;
+    P->edges = S.edges;
+    bool any_side = false;
     for (size_t i = 0; i < n; ++i) {
         PlanNode& N = P->nodes[i];
-        hipGraphNode_t h = gn[order[i]];
-        hipGraphNodeType ty;
-        e = hipGraphNodeGetType(h, &ty);
-        if (e != hipSuccess) { destroy(P); return (int)e; }
+        const int c = S.order[i];
+        N.creation = c;
+        N.stream = S.stream[i];
+        N.wait = S.wait[i];
+        N.record = S.record[i] != 0;
+        any_side = any_side || N.stream == 1;
+        const hipGraphNodeType ty = type[c];
         if (ty == hipGraphNodeTypeKernel) {
-            e = hipGraphKernelNodeGetParams(h, &N.kp);
-            if (e != hipSuccess) { destroy(P); return (int)e; }
-            if (N.kp.func == marker_fn && N.kp.kernelParams) {
+            N.kp = kparams[c];
+            if (kind[c] == NK_MARKER) {
                 N.kind = NK_MARKER;
                 N.marker_id = *(int*)N.kp.kernelParams[0];
                 P->n_markers++;
             } else {
                 N.kind = NK_KERNEL;
+                if (kname[c]) N.name = kname[c];
                 if (hipGetFuncBySymbol(&N.fn, N.kp.func) != hipSuccess) {
                     (void)hipGetLastError();
                     N.fn = nullptr;
@@ -148,7 +167,7 @@ extern "C" int cwf_plan_create(void* graph_, void** out) {
                 P->n_kernels++;
             }
         } else if (ty == hipGraphNodeTypeMemset) {
-            e = hipGraphMemsetNodeGetParams(h, &N.ms);
+            e = hipGraphMemsetNodeGetParams(gn[c], &N.ms);
             if (e != hipSuccess) { destroy(P); return (int)e; }
             if (N.ms.height > 1 || !(N.ms.elementSize == 1 || N.ms.elementSize == 2 || N.ms.elementSize == 4)) {
                 snprintf(g_detail, sizeof g_detail, "memset node %zu: elementSize %u width %zu height %zu pitch %zu", i, N.ms.elementSize, N.ms.width, N.ms.height, N.ms.pitch);
@@ -171,62 +190,7 @@ extern "C" int cwf_plan_create(void* graph_, void** out) {
             return CWF_E_TOOLARGE;       // not a step this library captured
         }
     }
-    // The weight-gradient chain is recognised by its kernels (weight-gradient kernels, their operand conversions and slab reduces):
-    // those nodes ALWAYS go to stream 1, the low-priority stream, wherever the capture had them -- a structural guess that put them
-    // on a high-priority stream, or the main chain on the low-priority one, cost 30-40 % of the step (any assignment is correct; the
-    // events below carry every cross-stream edge).
-    std::vector<char> side(n, 0);
-    bool any_side = false;
-    for (size_t i = 0; i < n; ++i) {
-        const PlanNode& N = P->nodes[i];
-        if (N.kind != NK_KERNEL) continue;
-        const char* nm = hipKernelNameRefByPtr(N.kp.func, nullptr);
-        // (+ the bias-gradient sums of the transposed convs: in_reduce_kernel<0> + stats_channel_sum_kernel, cwf.kernels.channel_sum_to)
-        if (nm && (strstr(nm, "wgrad") || strstr(nm, "stats_channel_sum_kernel") ||
-                   strstr(nm, "in_reduce_kernelILi0") || strstr(nm, "in_reduce_kernel<0"))) { side[order[i]] = 1; any_side = true; }
-        else if (nm && strstr(nm, "to_bf16_kernel")) side[order[i]] = 2;      // decided below: a conversion belongs where its readers are
-    }
-    (void)hipGetLastError();
-    for (int i = (int)n - 1; i >= 0; --i) {               // (reverse topological order: a conversion feeding a conversion is handled too)
-        const int u = order[i];
-        if (side[u] != 2) continue;
-        bool all_side = !succ[u].empty();
-        for (int v : succ[u]) all_side = all_side && side[v] == 1;
-        side[u] = all_side ? 1 : 0;
-        any_side = any_side || all_side;
-    }
-    // Everything that is not part of the weight-gradient chain stays on the caller's stream, in the order the host issued it (a valid
-    // topological order: ties above are broken by creation index).  Spreading independent branches over a third stream made every
-    // step 60 % SLOWER on this runtime (31 ms per step against 18).
-    int waited[MAX_STREAMS + 1][MAX_STREAMS];                 // [waiting stream (MAX_STREAMS = marker stream)][source] -> last position waited for
-    for (auto& row : waited) for (int& w : row) w = -1;
     const int n_streams = any_side ? 2 : 1;
-    for (size_t i = 0; i < n; ++i) {
-        const int v = order[i];
-        PlanNode& N = P->nodes[i];
-        N.stream = N.kind == NK_MARKER ? -1 : side[v] ? 1 : 0;
-        std::vector<int> w;
-        for (int p : pred[v]) {
-            const PlanNode& Q = P->nodes[pos[p]];
-            if (Q.kind == NK_MARKER) {                        // a marker orders nothing on the device beyond what IT waited for
-                for (int x : Q.wait)
-                    if (P->nodes[x].stream != N.stream) w.push_back(x);
-            } else if (Q.stream != N.stream) {
-                w.push_back(pos[p]);
-            }
-        }
-        int me = N.stream < 0 ? MAX_STREAMS : N.stream;
-        for (int c = 0; c < MAX_STREAMS; ++c) {               // waits are cumulative per source stream: the latest node is enough
-            int last = -1;
-            for (int x : w)
-                if (P->nodes[x].stream == c) last = std::max(last, x);
-            if (last > waited[me][c]) {
-                N.wait.push_back(last);
-                if (N.kind != NK_MARKER) waited[me][c] = last; // (the marker stream is the caller's: assume nothing across calls)
-                P->nodes[last].record = true;
-            }
-        }
-    }
     P->n_streams = n_streams;
     int least = 0, greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
@@ -255,6 +219,69 @@ extern "C" int cwf_plan_create(void* graph_, void** out) {
 }
 
 extern "C" const char* cwf_plan_last_error(void) { return g_detail; }
+
+extern "C" int cwf_plan_schedule(int n, const int* kind, const int* cls, int n_edges, const int* edge_from, const int* edge_to,
+                                 int* order, int* stream, int* wait_off, int* wait, int* record) {
+    if (!order || !stream || !wait_off || !wait || !record) return CWF_E_BADARG;
+    Schedule S;
+    if (!schedule(n, kind, cls, n_edges, edge_from, edge_to, S)) return CWF_E_BADARG;
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        order[i] = S.order[i];
+        stream[i] = S.stream[i];
+        record[i] = S.record[i];
+        wait_off[i] = k;
+        for (int x : S.wait[i]) wait[k++] = x;               // (at most one per source stream: k <= MAX_STREAMS * n)
+    }
+    wait_off[n] = k;
+    return 0;
+}
+
+extern "C" int cwf_plan_counts(void* plan, int* counts3) {
+    if (!plan || !counts3) return CWF_E_BADARG;
+    Plan* P = (Plan*)plan;
+    size_t waits = 0;
+    for (auto& N : P->nodes) waits += N.wait.size();
+    counts3[0] = (int)P->nodes.size(); counts3[1] = (int)waits; counts3[2] = (int)P->edges.size();
+    return 0;
+}
+
+extern "C" int cwf_plan_describe(void* plan, int* kind, int* stream, int* marker_id, int* record, int* creation, int* wait_off,
+                                 int* wait, int* edge_from, int* edge_to) {
+    if (!plan || (!wait_off) != (!wait) || (!edge_from) != (!edge_to)) return CWF_E_BADARG;
+    Plan* P = (Plan*)plan;
+    const int n = (int)P->nodes.size();
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        const PlanNode& N = P->nodes[i];
+        if (kind) kind[i] = N.kind;
+        if (stream) stream[i] = N.stream;
+        if (marker_id) marker_id[i] = N.marker_id;
+        if (record) record[i] = N.record ? 1 : 0;
+        if (creation) creation[i] = N.creation;
+        if (wait) {
+            wait_off[i] = k;
+            for (int x : N.wait) wait[k++] = x;
+        }
+    }
+    if (wait) wait_off[n] = k;
+    if (edge_from)
+        for (size_t j = 0; j < P->edges.size(); ++j) { edge_from[j] = P->edges[j].first; edge_to[j] = P->edges[j].second; }
+    return 0;
+}
+
+extern "C" int cwf_plan_kernel_name(void* plan, int position, char* buf, int cap) {
+    if (!plan || cap < 0 || (cap > 0 && !buf)) return CWF_E_BADARG;
+    Plan* P = (Plan*)plan;
+    if (position < 0 || position >= (int)P->nodes.size()) return CWF_E_BADARG;
+    const std::string& s = P->nodes[position].name;
+    if (cap > 0) {
+        const size_t m = std::min(s.size(), (size_t)cap - 1);
+        memcpy(buf, s.data(), m);
+        buf[m] = 0;
+    }
+    return (int)s.size();
+}
 
 extern "C" int cwf_plan_info(void* plan, int* info8) {
     if (!plan || !info8) return CWF_E_BADARG;

@@ -140,7 +140,38 @@ SIGNATURES = {
     "cwf_plan_run": [P, P, P, I, P, P],
     "cwf_plan_destroy": [P],
     "cwf_plan_marker": [I, P],
+    "cwf_plan_schedule": [I, P, P, I, P, P, P, P, P, P, P],
+    "cwf_plan_counts": [P, P],
+    "cwf_plan_describe": [P, P, P, P, P, P, P, P, P, P],
+    "cwf_plan_kernel_name": [P, I, P, I],
 }
+
+PLAN_KERNEL, PLAN_MEMSET, PLAN_EMPTY, PLAN_MARKER = 0, 1, 3, 4     # CWF_PLAN_*
+PLAN_CLASS_MAIN, PLAN_CLASS_SIDE, PLAN_CLASS_CONVERSION = 0, 1, 2  # CWF_PLAN_CLASS_*
+
+
+def plan_describe(lib, plan):
+    """What cwf_plan_counts / cwf_plan_describe / cwf_plan_kernel_name say about a built plan, as Python lists indexed by plan
+    position: kind, stream, marker_id, record, creation, waits (a list per position), name ('' for a node that is no kernel), and
+    edges (position pairs).  Nothing is launched."""
+    cnt = (I * 3)()
+    check(lib.cwf_plan_counts(plan, cnt), "cwf_plan_counts")
+    n, nw, ne = cnt[0], cnt[1], cnt[2]
+    kind, stream, marker, record, creation = ((I * n)() for _ in range(5))
+    off, wait = (I * (n + 1))(), (I * max(nw, 1))()
+    ef, et = (I * max(ne, 1))(), (I * max(ne, 1))()
+    check(lib.cwf_plan_describe(plan, kind, stream, marker, record, creation, off, wait, ef, et), "cwf_plan_describe")
+    names = []
+    for i in range(n):
+        ln = lib.cwf_plan_kernel_name(plan, i, None, 0)
+        if ln < 0:
+            raise CwfError("cwf_plan_kernel_name failed with status %d" % ln)
+        buf = C.create_string_buffer(ln + 1)
+        lib.cwf_plan_kernel_name(plan, i, buf, ln + 1)
+        names.append(buf.value.decode())
+    return {"kind": list(kind), "stream": list(stream), "marker_id": list(marker), "record": [int(r) for r in record],
+            "creation": list(creation), "waits": [list(wait[off[i]:off[i + 1]]) for i in range(n)], "name": names,
+            "edges": [(ef[j], et[j]) for j in range(ne)]}
 
 
 class GemmArgs(C.Structure):

@@ -887,6 +887,37 @@ int cwf_plan_destroy(void* plan);
 /* a no-op kernel carrying `id`: launched (under capture) on the communication stream to mark a cut point of the step */
 int cwf_plan_marker(int id, void* stream);
 
+/* The scheduling rules of cwf_plan_create on plain arrays; no HIP call, works without a GPU (cwf_plan_create calls the same code).
+ * Nodes are named by creation index (the order the host issued the work in).  kind[n]: CWF_PLAN_*; cls[n]: CWF_PLAN_CLASS_* of a
+ * kernel node, 0 for every other kind (cwf_plan_create derives it from the kernel's name: weight-gradient chain = SIDE, to_bf16
+ * conversions = CONVERSION); edge_from / edge_to[n_edges]: the graph's edges.  Out: order[n] = creation index per plan position
+ * (topological, smallest creation index first); stream[n] per position: 0 = the caller's stream, 1 = the side stream (SIDE nodes,
+ * and a CONVERSION all of whose successors are on it), -1 = a marker (the communication stream); record[n]: an event is recorded
+ * behind this position; wait_off[n + 1] / wait[2 n]: position i waits for the events of positions wait[wait_off[i] ..
+ * wait_off[i + 1]), each earlier, on another stream and recorded.  One wait per source stream at most, none where the node's own
+ * stream already waited for that position or a later one of the same source; a node behind a marker takes over the marker's waits.
+ * CWF_E_BADARG: n <= 0, a null array, a kind or class out of range, a class on a node that is no kernel, an edge that names no
+ * node, a cycle. */
+#define CWF_PLAN_KERNEL 0
+#define CWF_PLAN_MEMSET 1
+#define CWF_PLAN_EMPTY  3
+#define CWF_PLAN_MARKER 4
+#define CWF_PLAN_CLASS_MAIN       0
+#define CWF_PLAN_CLASS_SIDE       1
+#define CWF_PLAN_CLASS_CONVERSION 2
+int cwf_plan_schedule(int n, const int* kind, const int* cls, int n_edges, const int* edge_from, const int* edge_to,
+                      int* order, int* stream, int* wait_off, int* wait, int* record);
+/* Reading a built plan (nothing is launched).  counts3 = {positions, waits in all, edges of the graph}.  cwf_plan_describe fills,
+ * per plan position: kind (CWF_PLAN_*), stream (0, 1, -1 for a marker), marker_id (-1 for any other kind), record, creation (index
+ * in the graph's node list), wait_off[positions + 1] / wait[waits] as above; and the graph's edges as position pairs in
+ * edge_from / edge_to[edges].  Any array may be NULL (wait_off with wait, edge_from with edge_to: both or neither).
+ * cwf_plan_kernel_name copies the name hipKernelNameRefByPtr gave for the kernel at `position` into buf (at most cap - 1 characters
+ * and a NUL; buf may be NULL with cap 0) and returns its full length: 0 for a memset, empty or marker node. */
+int cwf_plan_counts(void* plan, int* counts3);
+int cwf_plan_describe(void* plan, int* kind, int* stream, int* marker_id, int* record, int* creation, int* wait_off, int* wait,
+                      int* edge_from, int* edge_to);
+int cwf_plan_kernel_name(void* plan, int position, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

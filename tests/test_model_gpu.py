@@ -377,6 +377,20 @@ def test_batch_two_at_bench_shape_128(hip):
         kernels.set_precision("fp32")
 
 
+def _described_plan(tr):
+    """cwf_plan_describe of the Trainer's plan, held to the happens-before checker and the stream rule (tests/plan_ref.py: every node
+    behind every ancestor it has in the captured graph; side-class kernels, and conversions only they read, on stream 1 and nothing
+    else there).  Host-side only: nothing is launched."""
+    import plan_ref
+    from cwf import _lib
+    from cwf.kernels import backend
+    desc = _lib.plan_describe(backend().lib, tr._plan)
+    pairs = plan_ref.check_described(desc)
+    print("plan: %d nodes, %d edges, %d waits, %d (ancestor, node) pairs ordered" % (len(desc["kind"]), len(desc["edges"]),
+                                                                                  sum(len(w) for w in desc["waits"]), pairs))
+    return desc
+
+
 def _replay(tr):
     if tr._plan is not None:
         tr._run_plan()
@@ -422,6 +436,10 @@ def test_graph_replay_matches_eager_step(hip, mode):
             # every node is a plain launch; the weight-gradient chain sits on a stream of its own
             assert pi["kernels"] > 300 and pi["streams"] >= 2 and pi["on_stream1"] >= 20 and pi["markers"] == 0, pi
             assert pi["on_stream0"] > 4 * (pi["on_stream1"] + pi["on_streams2plus"]), pi
+            # the plan as built honours every edge of the captured graph (tests/plan_ref.py: happens-before over the issue sequence), and
+            # stream 1 holds the weight-gradient chain and nothing else
+            desc = _described_plan(trg)
+            assert len(desc["kind"]) == pi["nodes"] and desc["stream"].count(1) == pi["on_stream1"] and sum(desc["record"]) == pi["events"]
         else:
             assert trg._plan is None
         for i in (0, 1, 0):
@@ -591,6 +609,10 @@ def test_rccl_phase_allreduce_path_one_rank(hip, monkeypatch):
         tr2, g2, w2 = run("plan", steps=4)
         _, g0c, w0c = run(False, steps=4)
         assert tr2._plan is not None and tr2.plan_info["markers"] == 3 and tr2.overlap_comm and tr2._works == [], tr2.plan_info
+        # ... and each marker makes the communication stream wait for every ancestor it has in the graph, on either stream
+        desc2 = _described_plan(tr2)
+        assert [k for k in desc2["marker_id"] if k >= 0] == [0, 1, 2] and desc2["stream"].count(-1) == 3
+        assert desc2["stream"].count(1) == tr2.plan_info["on_stream1"] >= 20
     finally:
         dist.destroy_process_group()
     assert float((g1 - g0).norm() / g0.norm()) < max(5e-5, 10 * noise)

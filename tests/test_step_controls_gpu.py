@@ -399,6 +399,14 @@ def test_trainer_window_under_communication_one_rank(hip, monkeypatch, use_graph
         assert tr.comm and tr.overlap_comm and tr._comm_stream is not None and len(tr.opt.sink.chunks) == 3
         if use_graph:
             assert tr._plan is not None and tr.plan_info["markers"] == 3, tr.plan_info
+            # the plan with its three markers honours every edge of the captured graph and keeps stream 1 to the weight-gradient chain
+            # (tests/plan_ref.py; read from the built plan, nothing is launched)
+            import plan_ref
+            from cwf import _lib
+            desc = _lib.plan_describe(hip.lib, tr._plan)
+            plan_ref.check_described(desc)
+            assert [k for k in desc["marker_id"] if k >= 0] == [0, 1, 2] and desc["stream"].count(-1) == 3
+            assert desc["stream"].count(1) == tr.plan_info["on_stream1"] >= 20
         _check_window(tr, R, R["w_half"])
     finally:
         dist.destroy_process_group()

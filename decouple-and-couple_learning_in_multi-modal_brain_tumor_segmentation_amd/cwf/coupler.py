@@ -66,17 +66,35 @@ def _by_param(flat, groups):
 
 def _grad_buffers(P):
     """Destination of parameter gradients (P: list of lists of parameters): slices of the Trainer's flat gradient buffer when
-    a sink is active (the Functions then return None for them: autograd never sees these gradients), fresh tensors otherwise."""
+    a sink is active (the Functions then return None for them: autograd never sees these gradients), fresh tensors otherwise.
+    -> (buffers, sunk, late): `late` goes to _add_late once the backward launches of the call are issued.
+
+    The kernels WRITE their destinations (only the second cross-attention of a call accumulates), and GradSink.finish skips what
+    is marked written.  So a parameter whose slice is already written in this backward pass (since sink.begin()) -- a weight set
+    applied more than once under the sink, by one Function type or across the coupler Functions -- gets a fresh tensor here,
+    which _add_late adds into the slice: the slice ends up holding the sum, as plain autograd would give.  A set applied once
+    (every set of ClsWiseFormer) takes the views and launches nothing extra."""
     from .optim import active_sink
     sink = active_sink()
     if sink is not None:
         views = [[sink.view(p) for p in ps] for ps in P]
         if all(v is not None for vs in views for v in vs):
-            for ps in P:
-                for p in ps:
-                    sink.mark(p)
-            return views, True
-    return [[torch.empty_like(p) for p in ps] for ps in P], False
+            late = []
+            for ps, vs in zip(P, views):
+                for i, p in enumerate(ps):
+                    if p.data_ptr() in sink.written:
+                        late.append((vs[i], torch.empty_like(p)))
+                        vs[i] = late[-1][1]
+                    else:
+                        sink.mark(p)
+            return views, True, late
+    return [[torch.empty_like(p) for p in ps] for ps in P], False, []
+
+
+def _add_late(late):
+    """second and later contributions to slices of the sink that were already written (see _grad_buffers)"""
+    if late:
+        torch._foreach_add_([v for v, _ in late], [t for _, t in late])
 
 
 def _site(K, cfg_p, n):
@@ -226,7 +244,7 @@ class RegionCouplerFn(torch.autograd.Function):
         te, ts = Ef.shape[1], Sf.shape[1]
         c = lambda g, n: None if g is None else g.contiguous().view(gb, n, e)
         dgated_e, dgated_s, dscat_s, dsem_tok = c(dgated_e, te), c(dgated_s, ts), c(dscat_s, ts), c(dsem_tok, 1)
-        Gw, sunk = _grad_buffers(P)
+        Gw, sunk, late = _grad_buffers(P)
         dR = torch.empty_like(R)
         K.scatter_bwd(dgated_e, None, Ef, inv_e, idx_e, R[:, 0, 1:], R[:, 0, 0:1], None, dR[:, 0, 1:], dR[:, 0, 0:1])
         K.scatter_bwd(dgated_s, dscat_s, Sf, inv_s, idx_s, R[:, 1, 1:], R[:, 1, 0:1], dsem_tok, dR[:, 1, 1:], dR[:, 1, 0:1])
@@ -238,8 +256,9 @@ class RegionCouplerFn(torch.autograd.Function):
         dE = K.token_grad(dgated_e, None, R[:, 0, 0:1], inv_e, inv_es, dX1[:, 0], dX2[:, 1], k, cfg.p_select, offs[0], offs[3])
         dS = K.token_grad(dgated_s, dscat_s, R[:, 1, 0:1], inv_s, inv_se, dX1[:, 1], dX2[:, 0], k, cfg.p_select, offs[1], offs[2])
         e_toks, s_toks = ctx.toks
-        (tk, tk_sunk) = _grad_buffers([e_toks, s_toks])
+        tk, tk_sunk, tk_late = _grad_buffers([e_toks, s_toks])
         K.head_grad(dX1[:, 0, 0], dX2[:, 1, 0], dX1[:, 1, 0], dX2[:, 0, 0], out1=tk[0], out2=tk[1])
+        _add_late(late + tk_late)
         b = gb // G
         dtoks = ((None,) * (2 * G)) if tk_sunk else (tuple(tk[0]) + tuple(tk[1]))
         dP = ((None,) * (NP * G)) if sunk else tuple(Gw[i][g] for g in range(G) for i in range(NP))
@@ -284,11 +303,12 @@ class FusionCouplerFn(torch.autograd.Function):
         P = _by_param(ctx.saved_tensors[4:], 1)
         b, t, e = R.shape
         dfused = dfused.contiguous()
-        Gw, sunk = _grad_buffers(P)
+        Gw, sunk, late = _grad_buffers(P)
         dR = torch.empty_like(R)
         K.scatter_bwd(dfused, None, feats, inv, idx, R[:, 1:], R[:, 0:1], None, dR[:, 1:], dR[:, 0:1])
         dy1 = _ffn_bwd(K, P, Gw, sv2, dR.view(b * t, e))
         dx, _ = _ca_bwd(K, P, Gw, cfg, sv1, dy1, first=True, dual=False)
+        _add_late(late)
         dX = dx.view(b, t, e)
         dfeats = K.token_grad(dfused, None, R[:, 0:1], inv, None, dX, None, k, cfg.p_select, off, 0)
         return (None, dfeats, dX[:, 0:1]) + (((None,) * NP) if sunk else tuple(Gw[i][0] for i in range(NP)))
@@ -322,10 +342,11 @@ class IntraCouplerBlockFn(torch.autograd.Function):
         cfg, (sv1, sv2, sv3) = ctx.cfg, ctx.sv
         b, t, e = ctx.shape
         P = _by_param(ctx.saved_tensors, 1)
-        Gw, sunk = _grad_buffers(P)
+        Gw, sunk, late = _grad_buffers(P)
         dy2 = _ffn_bwd(K, P, Gw, sv3, dr.contiguous().view(b * 2 * t, e))
         dy1, _ = _ca_bwd(K, P, Gw, cfg, sv2, dy2, first=True, dual=False)
         dx1, dx2 = _ca_bwd(K, P, Gw, cfg, sv1, dy1, first=False, dual=True)
+        _add_late(late)
         dX1, dX2 = dx1.view(b, 2, t, e), dx2.view(b, 2, t, e)
         dP = ((None,) * NP) if sunk else tuple(Gw[i][0] for i in range(NP))
         return (None, dX1[:, 0], dX2[:, 0], dX1[:, 1], dX2[:, 1]) + dP
@@ -352,9 +373,10 @@ class FusionBlockFn(torch.autograd.Function):
         cfg, (sv1, sv2) = ctx.cfg, ctx.sv
         b, t, e = ctx.shape
         P = _by_param(ctx.saved_tensors, 1)
-        Gw, sunk = _grad_buffers(P)
+        Gw, sunk, late = _grad_buffers(P)
         dy1 = _ffn_bwd(K, P, Gw, sv2, dr.contiguous().view(b * t, e))
         dx, _ = _ca_bwd(K, P, Gw, cfg, sv1, dy1, first=True, dual=False)
+        _add_late(late)
         return (None, dx.view(b, t, e)) + (((None,) * NP) if sunk else tuple(Gw[i][0] for i in range(NP)))
 
 

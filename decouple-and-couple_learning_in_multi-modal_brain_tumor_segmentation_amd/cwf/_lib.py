@@ -115,6 +115,9 @@ SIGNATURES = {
     "cwf_topk_ce_workspace": [I, L],
     "cwf_topk_ce": [P, P, U, L, P, P, P, I, L, I, P, P],
     "cwf_topk_ce_bwd": [P, P, U, P, P, P, I, L, I, P],
+    "cwf_focal_workspace": [I, L, I],
+    "cwf_focal_loss": [P, P, P, I, P, P, P, P, I, L, I, P, P],
+    "cwf_focal_loss_bwd": [P, P, P, I, P, P, P, P, I, L, I, P],
     "cwf_components_workspace": [I, I, I, I, I],
     "cwf_components": [P, I, I, I, I, I, I, P, P, P, P, P, L, P],
     "cwf_postprocess_labels": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
@@ -247,6 +250,11 @@ class IntensitySample(C.Structure):
     _fields_ = [("taps", (F * 7) * 4), ("amp", F * 4), ("key", U64), ("gamma", F * 4), ("blur", I), ("noise", I), ("gam", I)]
 
 
+class FocalParams(C.Structure):
+    """struct cwf_focal_params (include/cwf_hip.h)"""
+    _fields_ = [("fn", D), ("fp", D), ("exponent", D), ("smooth", D), ("gamma", D), ("ce_ratio", D), ("class_weight", D * 4)]
+
+
 INTENSITY_TILE = (10, 10, 32)   # CWF_INTENSITY_T0, _T1, _T2: the blur's output tile (3-voxel halo on every side)
 
 
@@ -288,7 +296,7 @@ GRADNORM_WS_DOUBLES = 1024     # CWF_GRADNORM_WS_DOUBLES
 RULE_ADAMW, RULE_SGD = 1, 2    # CWF_RULE_ADAMW, CWF_RULE_SGD
 RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
                  "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace",
-                 "cwf_topk_ce_workspace"}
+                 "cwf_topk_ce_workspace", "cwf_focal_workspace"}
 
 _lib = None
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import packing as pk
-from .kernels import REGION_MASKS, backend, precision
+from .kernels import REGION_MASKS, backend, check_focal_params, precision
 
 
 def active_sink():
@@ -1029,3 +1029,40 @@ def topk_ce_loss(prob_ncdhw, label, percent=10.0, weight=1.0, posmask=0):
         label = label.long()
     k = topk_count(label.numel(), float(percent))
     return _TopkCeFn.apply(to_channels_last_view(prob_ncdhw), label, int(posmask), k, loss_weight_tensor(weight, prob_ncdhw.device, "topk"))
+
+
+class _FocalLossFn(torch.autograd.Function):
+    """weight x (focal Tversky of the regions + ce_ratio x focal cross-entropy), sums over the whole batch (csrc/focal.hip)."""
+
+    @staticmethod
+    def forward(ctx, prob_cl, label, posmasks, params, weight):
+        loss, coef = backend().focal_loss(prob_cl, label, posmasks, params, weight)
+        ctx.posmasks, ctx.params = posmasks, params
+        ctx.save_for_backward(prob_cl, label, coef)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        prob_cl, label, coef = ctx.saved_tensors
+        gs = g.reshape(1).to(torch.float32).contiguous()
+        return backend().focal_loss_bwd(prob_cl, label, ctx.posmasks, ctx.params, coef, gs), None, None, None, None
+
+
+def focal_loss(prob_ncdhw, label, posmasks=REGION_MASKS, fn=0.7, fp=0.3, exponent=0.75, smooth=1e-5, gamma=2.0, ce_ratio=1.0,
+               class_weight=None, weight=1.0):
+    """Focal Tversky (Salehi et al. 2017; Abraham & Khan 2019) on the regions `posmasks` (class bitmasks; default WT, TC, ET) plus
+    ce_ratio x focal cross-entropy (Lin et al. 2017):
+        weight x ( mean_r max(1 - TI_r, 0)^exponent + ce_ratio x mean_voxels -k_y (1 - q)^gamma ln q ),   q = clamp(p_y, 1e-7, 1),
+        TI_r = (TP_r + smooth) / (TP_r + fn FN_r + fp FP_r + smooth), the sums taken over the whole batch.
+    prob [N,4,D,H,W], label int64 [N,D,H,W] in 0..3; weight: float or one-element device tensor.  posmasks=() is focal cross-entropy
+    alone, ce_ratio=0 focal Tversky alone.  A value outside its range is a ValueError before the backend is touched."""
+    posmasks = tuple(int(m) for m in posmasks)
+    params = check_focal_params(posmasks, fn=fn, fp=fp, exponent=exponent, smooth=smooth, gamma=gamma, ce_ratio=ce_ratio,
+                                class_weight=class_weight)
+    if prob_ncdhw.dim() != 5 or int(prob_ncdhw.shape[1]) != 4:
+        raise ValueError("focal loss takes probabilities [N, 4, D, H, W], got %s" % (tuple(prob_ncdhw.shape),))
+    wt = loss_weight_tensor(weight, prob_ncdhw.device, "focal")
+    label = label.contiguous()
+    if label.dtype != torch.int64:
+        label = label.long()
+    return _FocalLossFn.apply(to_channels_last_view(prob_ncdhw), label, posmasks, params, wt)

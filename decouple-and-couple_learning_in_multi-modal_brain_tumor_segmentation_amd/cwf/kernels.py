@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import threading
 
 import numpy as np
@@ -20,6 +21,37 @@ from . import packing as pk
 _f32 = torch.float32
 # the evaluation's regions as class bitmasks (bit c = class c belongs): WT = {1, 2, 3}, TC = {1, 3}, ET = {3}
 REGION_MASKS = (0b1110, 0b1010, 0b1000)
+# the focal Tversky / focal cross-entropy term's parameters (struct cwf_focal_params) at their defaults
+FOCAL_DEFAULTS = dict(fn=0.7, fp=0.3, exponent=0.75, smooth=1e-5, gamma=2.0, ce_ratio=1.0, class_weight=(1.0, 1.0, 1.0, 1.0))
+
+
+def check_focal_params(posmasks, fn=0.7, fp=0.3, exponent=0.75, smooth=1e-5, gamma=2.0, ce_ratio=1.0, class_weight=None):
+    """The accepted values of the focal term (the rules cwf_focal_loss enforces, here as ValueError before anything is called):
+    at most 8 regions, each a non-zero bitmask over classes 0..3; fn, fp finite >= 0 with fn + fp > 0; 0 < exponent <= 4; smooth > 0;
+    gamma = 0 or 1 <= gamma <= 5; ce_ratio finite >= 0; four class weights finite >= 0; not both parts off.  -> the parameters as a
+    dict of floats (class_weight a 4-tuple)."""
+    masks = tuple(int(m) for m in posmasks)
+    if len(masks) > 8:
+        raise ValueError("focal loss: at most 8 regions, got %d" % len(masks))
+    if any(m <= 0 or m > 15 for m in masks):
+        raise ValueError("focal loss: a region is a non-zero bitmask over classes 0..3, got %r" % (posmasks,))
+    fn, fp, exponent, smooth, gamma, ce_ratio = (float(v) for v in (fn, fp, exponent, smooth, gamma, ce_ratio))
+    if not (math.isfinite(fn) and math.isfinite(fp) and fn >= 0.0 and fp >= 0.0 and fn + fp > 0.0):
+        raise ValueError("focal loss: fn and fp must be finite and >= 0 with fn + fp > 0, got %r and %r" % (fn, fp))
+    if not 0.0 < exponent <= 4.0:
+        raise ValueError("focal loss: exponent must lie in (0, 4], got %r" % (exponent,))
+    if not (math.isfinite(smooth) and smooth > 0.0):
+        raise ValueError("focal loss: smooth must be finite and > 0, got %r" % (smooth,))
+    if not (gamma == 0.0 or 1.0 <= gamma <= 5.0):
+        raise ValueError("focal loss: gamma must be 0 or lie in [1, 5] (a gamma in (0, 1) gives 0 * inf at p = 1), got %r" % (gamma,))
+    if not (math.isfinite(ce_ratio) and ce_ratio >= 0.0):
+        raise ValueError("focal loss: ce_ratio must be finite and >= 0, got %r" % (ce_ratio,))
+    kw = (1.0, 1.0, 1.0, 1.0) if class_weight is None else tuple(float(k) for k in class_weight)
+    if len(kw) != 4 or not all(math.isfinite(k) and k >= 0.0 for k in kw):
+        raise ValueError("focal loss: class_weight must be four finite numbers >= 0, got %r" % (class_weight,))
+    if not masks and ce_ratio == 0.0:
+        raise ValueError("focal loss: both parts are off (no region and ce_ratio = 0)")
+    return dict(fn=fn, fp=fp, exponent=exponent, smooth=smooth, gamma=gamma, ce_ratio=ce_ratio, class_weight=kw)
 
 
 def cl(t: torch.Tensor):
@@ -1211,6 +1243,50 @@ class HipBackend:
         dprob = torch.empty_like(prob)
         self._call("cwf_topk_ce_bwd", prob.data_ptr(), label.data_ptr(), posmask, coef.data_ptr(), gscale.data_ptr(), dprob.data_ptr(), n, v, c,
                    self._stream())
+        return dprob
+
+    # ------------------------------------------------------------------ L4 (focal Tversky + focal cross-entropy)
+    @staticmethod
+    def _focal_args(name, prob, label, posmasks, params):
+        """-> (N, V, masks, the uint32 array, the cwf_focal_params struct); every check the C entry makes, made before any call"""
+        if prob.dim() != 5 or prob.dtype != _f32 or not prob.is_cuda or int(prob.shape[-1]) != 4:
+            raise ValueError("%s: prob must be a float32 [N, D0, D1, D2, 4] tensor on the GPU, got %s %s" % (name, tuple(prob.shape), prob.dtype))
+        if tuple(label.shape) != tuple(prob.shape[:4]) or label.dtype != torch.int64 or label.device != prob.device:
+            raise ValueError("%s: label must be int64 %s on the device of prob, got %s %s"
+                             % (name, tuple(prob.shape[:4]), tuple(label.shape), label.dtype))
+        masks, cm = HipBackend._posmasks(name, posmasks)
+        p = check_focal_params(masks, **params)
+        assert prob.is_contiguous() and label.is_contiguous()
+        cp = _lib.FocalParams(p["fn"], p["fp"], p["exponent"], p["smooth"], p["gamma"], p["ce_ratio"], (ctypes.c_double * 4)(*p["class_weight"]))
+        return int(prob.shape[0]), int(prob[0, ..., 0].numel()), masks, cm, cp
+
+    def focal_loss(self, prob, label, posmasks, params, weight):
+        """prob [N,D0,D1,D2,4] dense channels-last, label int64 [N,D0,D1,D2], posmasks R <= 8 class bitmasks over bits 0..3, params a
+        dict (fn, fp, exponent, smooth, gamma, ce_ratio, class_weight), weight a one-float device tensor -> (loss [1], coef [2 R + 1]):
+        weight x (focal Tversky of the regions + ce_ratio x focal cross-entropy), sums over the whole batch (cwf_focal_loss).  No host
+        synchronisation: the workspace comes from torch's allocator."""
+        n, v, masks, cm, cp = self._focal_args("focal_loss", prob, label, posmasks, params)
+        if weight.numel() != 1 or weight.dtype != _f32 or weight.device != prob.device:
+            raise ValueError("focal_loss: weight must be a one-element float32 tensor on the device of prob")
+        nbytes = self.lib.cwf_focal_workspace(n, v, len(masks))
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_focal_workspace failed with status %d (N=%d V=%d R=%d)" % (nbytes, n, v, len(masks)))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=prob.device)
+        loss = torch.empty(1, dtype=_f32, device=prob.device)
+        coef = torch.empty(2 * len(masks) + 1, dtype=_f32, device=prob.device)
+        self._call("cwf_focal_loss", prob.data_ptr(), label.data_ptr(), ctypes.addressof(cm), len(masks), ctypes.addressof(cp), weight.data_ptr(),
+                   loss.data_ptr(), coef.data_ptr(), n, v, 4, ws.data_ptr(), self._stream())
+        return loss, coef
+
+    def focal_loss_bwd(self, prob, label, posmasks, params, coef, gscale):
+        """-> dprob like prob: gscale x (the sum of t_r coef[2 r] + coef[2 r + 1] over the regions holding the class, plus coef[2 R] k_y
+        d/dq[-(1 - q)^gamma ln q] at the label's class where 1e-7 <= p_y <= 1); every element written (cwf_focal_loss_bwd)"""
+        n, v, masks, cm, cp = self._focal_args("focal_loss_bwd", prob, label, posmasks, params)
+        if coef.numel() != 2 * len(masks) + 1 or coef.dtype != _f32 or coef.device != prob.device or not coef.is_contiguous():
+            raise ValueError("focal_loss_bwd: coef must be the float32 [2 R + 1] tensor focal_loss returned")
+        dprob = torch.empty_like(prob)
+        self._call("cwf_focal_loss_bwd", prob.data_ptr(), label.data_ptr(), ctypes.addressof(cm), len(masks), ctypes.addressof(cp), coef.data_ptr(),
+                   gscale.data_ptr(), dprob.data_ptr(), n, v, 4, self._stream())
         return dprob
 
     def head_loss(self, logits, label, posmasks, scale):

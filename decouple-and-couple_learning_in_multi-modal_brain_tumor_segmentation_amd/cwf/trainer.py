@@ -41,6 +41,10 @@ Step controls (all off by default; then the step issues exactly the launches des
     (tools.topk_ce: mean of -log p_target over the hardest K % of the batch's voxels, selected exactly on the device), in front of
     the same backward.  w lives in a one-float device tensor (set_topk_weight() needs no recapture); K is fixed at construction, k
     being a launch argument.  None: the step makes no new call and calls total_loss as before.
+  * focal_weight = w, focal_params = {...}: a further loss term after the boundary and top-k parts, w * (focal Tversky on WT / TC / ET
+    + ce_ratio * focal cross-entropy) of the main output (tools.focal_loss; sums over the whole batch), in front of the same backward.
+    w lives in a one-float device tensor (set_focal_weight() needs no recapture); the parameters (posmasks, fn, fp, exponent, smooth,
+    gamma, ce_ratio, class_weight) are fixed at construction, being launch arguments.  None: no new call, total_loss called as before.
   * optimizer = "adamw" | "sgd" (with betas / momentum, nesterov / no_decay): the update is one launch of the AdamW or SGD rule
     (cwf.optim.FusedAdamW / FusedSGD) in place of Adam's; sink, all-reduce, accumulation, clipping and EMA are the base class's and
     work as above.  schedule = "cosine" | "constant" and warmup_steps = W shape the learning rate of an update:
@@ -57,10 +61,12 @@ import torch.distributed as dist
 from .optim import FusedAdam, FusedAdamW, FusedSGD, SCHEDULES, poly_lr, schedule_lr, warmup_factor
 
 
-def total_loss(outputs, target, edge, boundary=None, topk=None):
+def total_loss(outputs, target, edge, boundary=None, topk=None, focal=None):
     """The reference's five terms; with `boundary` (the one-float device tensor holding the boundary weight) a sixth part,
     tools.boundary_loss(outputs[0], target) at that weight, is appended and added to the total; with `topk` = (the one-float device
-    tensor holding the top-k weight, percent) the part tools.topk_ce(outputs[0], target) is appended after it."""
+    tensor holding the top-k weight, percent) the part tools.topk_ce(outputs[0], target) is appended after it; with `focal` = (the
+    one-float device tensor holding the focal weight, the parameters as keyword arguments of tools.focal_loss) the part
+    tools.focal_loss(outputs[0], target) is appended last."""
     from models import criterions
     from utils import tools
     parts = [criterions.softmax_dice(outputs[0], target), tools.get_separate_loss(outputs[1], target),
@@ -72,6 +78,9 @@ def total_loss(outputs, target, edge, boundary=None, topk=None):
         total = total + parts[5]
     if topk is not None:
         parts.append(tools.topk_ce(outputs[0], target, percent=topk[1], weight=topk[0]))
+        total = total + parts[-1]
+    if focal is not None:
+        parts.append(tools.focal_loss(outputs[0], target, weight=focal[0], **focal[1]))
         total = total + parts[-1]
     return total, parts
 
@@ -99,6 +108,25 @@ def check_topk(weight, percent):
     return weight, percent
 
 
+def check_focal(weight, params):
+    """(weight, params): weight None (term off) or a finite float >= 0; params None or a dict of tools.focal_loss's keyword arguments
+    (posmasks, fn, fp, exponent, smooth, gamma, ce_ratio, class_weight), checked by cwf.kernels.check_focal_params with the term off too.
+    -> (weight, the keyword arguments with every default filled in)"""
+    from .kernels import REGION_MASKS, check_focal_params
+    params = dict(params or {})
+    unknown = set(params) - {"posmasks", "fn", "fp", "exponent", "smooth", "gamma", "ce_ratio", "class_weight"}
+    if unknown:
+        raise ValueError("focal_params takes posmasks, fn, fp, exponent, smooth, gamma, ce_ratio and class_weight, got %s" % sorted(unknown))
+    posmasks = tuple(int(m) for m in params.pop("posmasks", REGION_MASKS))
+    checked = dict(check_focal_params(posmasks, **params), posmasks=posmasks)
+    if weight is None:
+        return None, checked
+    weight = float(weight)
+    if not math.isfinite(weight) or weight < 0.0:
+        raise ValueError("focal_weight must be None or a finite number >= 0, got %r" % (weight,))
+    return weight, checked
+
+
 def boundary_schedule(weight, epoch, warmup):
     """--boundary_weight A / --boundary_warmup E: A * min(1, epoch / E), E = 0 meaning constant"""
     return float(weight) if warmup <= 0 else float(weight) * min(1.0, float(epoch) / float(warmup))
@@ -113,11 +141,13 @@ class Trainer:
     def __init__(self, model, lr=2e-4, weight_decay=1e-5, amsgrad=True, end_epoch=1000, use_graph=False,
                  graph_warmup=2, overlap_comm=True, wgrad_async=True, accum_steps=1, max_grad_norm=None, ema_decay=None,
                  boundary_weight=None, topk_weight=None, topk_percent=10.0, optimizer="adam", betas=(0.9, 0.999), momentum=0.0,
-                 nesterov=False, no_decay=None, schedule="poly", warmup_steps=0):
+                 nesterov=False, no_decay=None, schedule="poly", warmup_steps=0, focal_weight=None, focal_params=None):
         self.boundary_weight = check_boundary_weight(boundary_weight)
         self._boundary = None                           # the weight as a one-float device tensor, made at the first step that needs it
         self.topk_weight, self.topk_percent = check_topk(topk_weight, topk_percent)
         self._topk = None                               # likewise
+        self.focal_weight, self.focal_params = check_focal(focal_weight, focal_params)
+        self._focal = None                              # likewise
         self.model = model
         self.init_lr, self.end_epoch = lr, end_epoch
         if int(accum_steps) != accum_steps or accum_steps < 1:
@@ -233,10 +263,12 @@ class Trainer:
         K = kernels_backend()
         K.wgrad_async = self.wgrad_async       # (from the forward pass on: it prepares weight-gradient operands on the side stream)
         outputs = self.model(x, None)
-        if self.topk_weight is None:
-            loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device))
-        else:
-            loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device), topk=(self._topk_tensor(x.device), self.topk_percent))
+        extra = {}                                      # (a term that is off is not named: total_loss is called as before it existed)
+        if self.topk_weight is not None:
+            extra["topk"] = (self._topk_tensor(x.device), self.topk_percent)
+        if self.focal_weight is not None:
+            extra["focal"] = (self._focal_tensor(x.device), self.focal_params)
+        loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device), **extra)
         self.opt.zero_grad(set_to_none=True)
         # graph modes: one reduce per phase, in warm-up too
         K.flush_every = (1 << 30) if self.use_graph else K.flush_every_default
@@ -298,6 +330,25 @@ class Trainer:
         if self._topk is not None:
             self._topk.fill_(w)
 
+    def _focal_tensor(self, device):
+        if self.focal_weight is None:
+            return None
+        if self._focal is None:
+            if _capturing():
+                raise RuntimeError("the focal weight tensor must exist before the step is captured")
+            self._focal = torch.full((1,), self.focal_weight, dtype=torch.float32, device=device)
+        return self._focal
+
+    def set_focal_weight(self, w):
+        """New weight of the focal term from the next step on, in every step mode (no recapture: the kernels read it from device
+        memory).  Only for a Trainer built with a focal_weight; the parameters stay as constructed."""
+        if w is None or self.focal_weight is None:
+            raise ValueError("the focal term is switched on or off at construction (focal_weight=...), not between steps")
+        w, _ = check_focal(w, self.focal_params)
+        self.focal_weight = w
+        if self._focal is not None:
+            self._focal.fill_(w)
+
     def _finish_comm(self):
         if not self.comm:
             return
@@ -318,6 +369,7 @@ class Trainer:
         self._static = (x.clone(), target.clone(), edge.clone())
         self._boundary_tensor(x.device)                 # (allocated and filled outside the capture)
         self._topk_tensor(x.device)
+        self._focal_tensor(x.device)
         want_plan = self.graph_mode == "plan"
         g = torch.cuda.CUDAGraph(keep_graph=True) if want_plan else torch.cuda.CUDAGraph()
         # No cyclic garbage collection inside the capture.  A Trainer and its model form a cycle (model.phase_callback), so an earlier
@@ -390,7 +442,7 @@ class Trainer:
     def step(self, x, target, edge, epoch=0):
         """One optimisation step on a rank-local batch -- with accum_steps = N > 1 one MICRO-step: every N-th call updates the weights
         (learning rate of that call's epoch), the calls before it only accumulate.  Returns this batch's (loss, [five parts]) as
-        device tensors (no host sync); a boundary_weight and a topk_weight each append a part, in that order."""
+        device tensors (no host sync); a boundary_weight, a topk_weight and a focal_weight each append a part, in that order."""
         self._last_micro = self._micro + 1 >= self.accum_steps
         if self._last_micro:
             self.opt.param_groups[0]["lr"] = self.learning_rate(epoch)    # plain float: checkpoints stay weights_only-loadable

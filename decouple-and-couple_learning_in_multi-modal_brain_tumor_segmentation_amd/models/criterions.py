@@ -27,6 +27,27 @@ def softmax_dice_topk(output, target):
     return softmax_dice(output, target) + tools.topk_ce(output, target)
 
 
+def focal_tversky(output, target, **kw):
+    """tools.focal_tversky: the focal Tversky loss of the regions WT / TC / ET, sums over the whole batch."""
+    return tools.focal_tversky(output, target, **kw)
+
+
+def focal_ce(output, target, **kw):
+    """tools.focal_ce: the focal cross-entropy, mean over the batch's voxels."""
+    return tools.focal_ce(output, target, **kw)
+
+
+def focal_loss(output, target, **kw):
+    """tools.focal_loss: focal Tversky + ce_ratio * focal cross-entropy, the term added when --focal_weight is set."""
+    return tools.focal_loss(output, target, **kw)
+
+
+def softmax_dice_focal(output, target):
+    """softmax_dice + focal_loss at its defaults (fn 0.7, fp 0.3, exponent 0.75, gamma 2, ce_ratio 1, weight 1): selectable as
+    --criterion softmax_dice_focal."""
+    return softmax_dice(output, target) + tools.focal_loss(output, target)
+
+
 def _not_built(name):
     def f(*a, **k):
         raise NotImplementedError("criterions.%s is an unused alternative in the reference and is not built; "

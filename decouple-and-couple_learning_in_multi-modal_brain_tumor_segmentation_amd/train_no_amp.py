@@ -142,6 +142,15 @@ def build_parser():
                         "line gains topk_loss.  Default: off")
     p.add_argument("--topk_percent", default=10.0, type=float,
                    help="K in (0, 100]: the share of the batch's voxels the top-k term averages over (fixed for the run).  Default: 10")
+    p.add_argument("--focal_weight", default=None, type=float,
+                   help="W >= 0: add W x (focal Tversky on WT / TC / ET + --focal_ce_ratio x focal cross-entropy) of the main output, sums "
+                        "over the whole batch, after the other terms; the log line gains focal_loss.  Default: off")
+    p.add_argument("--tversky_fn", default=0.7, type=float, help="(--focal_weight) weight of the false negatives in the Tversky index, >= 0")
+    p.add_argument("--tversky_fp", default=0.3, type=float, help="(--focal_weight) weight of the false positives in the Tversky index, >= 0")
+    p.add_argument("--tversky_exponent", default=0.75, type=float, help="(--focal_weight) (1 - Tversky index)^e, e in (0, 4]")
+    p.add_argument("--focal_gamma", default=2.0, type=float, help="(--focal_weight) (1 - p)^gamma of the focal cross-entropy: 0, or in [1, 5]")
+    p.add_argument("--focal_ce_ratio", default=1.0, type=float,
+                   help="(--focal_weight) weight of the focal cross-entropy beside the Tversky part, >= 0; 0: focal Tversky alone")
     p.add_argument("--optimizer", default="adam", choices=("adam", "adamw", "sgd"),
                    help="the update rule of the fused step: adam (the reference: L2 decay in the gradient, --amsgrad), adamw (decoupled "
                         "decay, --beta1 / --beta2 / --amsgrad) or sgd (--momentum, --nesterov); --lr and --weight_decay apply to all")
@@ -185,6 +194,22 @@ def check_topk(args):
         raise SystemExit("--topk_percent takes a percentage in (0, 100]")
     if args.topk_weight is not None and args.no_cuda:
         raise SystemExit("--topk_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
+
+
+def focal_params_of(args):
+    """the focal_params of Trainer from --tversky_* / --focal_gamma / --focal_ce_ratio"""
+    return dict(fn=args.tversky_fn, fp=args.tversky_fp, exponent=args.tversky_exponent, gamma=args.focal_gamma, ce_ratio=args.focal_ce_ratio)
+
+
+def check_focal(args):
+    """the values of --focal_weight and the flags that go with it (SystemExit with the rule, like the other checks)"""
+    from cwf.trainer import check_focal as check
+    try:
+        check(args.focal_weight, focal_params_of(args))
+    except ValueError as e:
+        raise SystemExit("--focal_weight / --tversky_fn / --tversky_fp / --tversky_exponent / --focal_gamma / --focal_ce_ratio: %s" % e)
+    if args.focal_weight is not None and args.no_cuda:
+        raise SystemExit("--focal_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
 
 
 def boundary_weight_at(args, epoch):
@@ -303,6 +328,7 @@ def main(argv=None):
     check_step_controls(args)
     check_boundary(args)
     check_topk(args)
+    check_focal(args)
     check_optimizer(args)
     from cwf import kernels
     from cwf.parallel import shard_indices
@@ -349,9 +375,10 @@ def main(argv=None):
                       accum_steps=args.accum_steps, max_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay,
                       boundary_weight=boundary_weight_at(args, args.start_epoch), topk_weight=args.topk_weight,
                       topk_percent=args.topk_percent, optimizer=args.optimizer, betas=(args.beta1, args.beta2), momentum=args.momentum,
-                      nesterov=args.nesterov, no_decay=args.no_decay, schedule=args.lr_schedule, warmup_steps=args.warmup_steps)
+                      nesterov=args.nesterov, no_decay=args.no_decay, schedule=args.lr_schedule, warmup_steps=args.warmup_steps,
+                      focal_weight=args.focal_weight, focal_params=focal_params_of(args))
     clip, use_ema, use_boundary = args.clip_grad_norm is not None, args.ema_decay is not None, args.boundary_weight is not None
-    use_topk = args.topk_weight is not None
+    use_topk, use_focal = args.topk_weight is not None, args.focal_weight is not None
     if use_ema and os.path.isfile(args.resume) and args.load:
         ck = torch.load(args.resume, map_location="cpu", weights_only=True)
         if "ema_state_dict" in ck:
@@ -394,7 +421,7 @@ def main(argv=None):
                     ev.synchronize() if ev is not None else None
                     v = host.tolist()
                     log.info("Epoch: %d_Iter:%d  loss: %.5f || end_loss: %.5f || s_loss:%.4f || edge_loss:%.4f || mid_s_loss:%.4f || mid_edge_loss:%.4f ||"
-                             + (" boundary_loss: %.5f ||" if use_boundary else "") + (" topk_loss: %.5f ||" if use_topk else "")
+                             + (" boundary_loss: %.5f ||" if use_boundary else "") + (" topk_loss: %.5f ||" if use_topk else "") + (" focal_loss: %.5f ||" if use_focal else "")
                              + (" grad_norm: %.4f" if clip else ""), tag[0], tag[1], *v)
                 # (grad_norm: of the last update -- inside an accumulation window that is the previous window's)
                 snap = torch.stack([loss] + list(parts) + ([trainer.opt.grad_norm] if clip else [])).float()

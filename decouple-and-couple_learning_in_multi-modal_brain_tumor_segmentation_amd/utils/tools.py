@@ -37,6 +37,26 @@ def topk_ce(output, target, percent=10.0, weight=1.0, posmask=0):
     return CF.topk_ce_loss(output, target, percent=percent, weight=weight, posmask=posmask)
 
 
+def focal_loss(output, target, posmasks=CF.REGION_MASKS, fn=0.7, fp=0.3, exponent=0.75, smooth=1e-5, gamma=2.0, ce_ratio=1.0,
+               class_weight=None, weight=1.0):
+    """Focal Tversky on the regions `posmasks` (class bitmasks; default WT, TC, ET) + ce_ratio * focal cross-entropy of the probabilities
+    output [B,4,D,H,W] against the label map target [B,D,H,W]: weight * (mean_r max(1 - TI_r, 0)^exponent + ce_ratio * mean of
+    -k_y (1 - q)^gamma ln q), TI_r = (TP + smooth) / (TP + fn FN + fp FP + smooth) over the whole batch.  Not in the reference; off unless
+    asked for."""
+    return CF.focal_loss(output, target, posmasks=posmasks, fn=fn, fp=fp, exponent=exponent, smooth=smooth, gamma=gamma, ce_ratio=ce_ratio,
+                         class_weight=class_weight, weight=weight)
+
+
+def focal_tversky(output, target, posmasks=CF.REGION_MASKS, fn=0.7, fp=0.3, exponent=0.75, smooth=1e-5, weight=1.0):
+    """focal_loss with ce_ratio = 0: the recall-weighted overlap loss alone (Salehi et al. 2017; Abraham & Khan 2019)."""
+    return CF.focal_loss(output, target, posmasks=posmasks, fn=fn, fp=fp, exponent=exponent, smooth=smooth, ce_ratio=0.0, weight=weight)
+
+
+def focal_ce(output, target, gamma=2.0, class_weight=None, weight=1.0):
+    """focal_loss with no regions: weight * mean of -k_y (1 - q)^gamma ln q, q = clamp(p_target, 1e-7, 1) (Lin et al. 2017)."""
+    return CF.focal_loss(output, target, posmasks=(), gamma=gamma, ce_ratio=1.0, class_weight=class_weight, weight=weight)
+
+
 def _separate(output, target, masks):
     maps = [output[r] for r in ("01", "02", "04")]
     if all(isinstance(m, CF.LazyProb) for m in maps) and len({(m.scale, tuple(m.logit.shape)) for m in maps}) == 1:

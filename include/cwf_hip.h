@@ -449,6 +449,49 @@ int cwf_topk_ce_bwd(const float* prob, const int64_t* label, uint32_t posmask, c
                     int N, int64_t V, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * L4  focal Tversky on class-bitmask regions + focal cross-entropy (csrc/focal.hip; this project's statement)
+ *   prob float [N][V][4] channels-last; label int64 [N][V], class y = label & 3.  M = N V; every sum runs over the whole batch.
+ *   regions r < R (0 <= R <= 8): class bitmasks posmasks[r] over bits 0..3, in HOST memory.  t_r = (m_r >> y) & 1;
+ *   p_r = 0.0f + the p_c of the classes of m_r in ascending class order (float32).
+ *   TP_r = sum t_r p_r, SP_r = sum p_r, ST_r = sum t_r (float64);  FN = ST - TP, FP = SP - TP, num = TP + smooth,
+ *   den = ((TP + fn FN) + fp FP) + smooth, x = 1 - num / den;  FT = (1 / R) sum_r (x > 0 ? x pow(x, exponent - 1) : 0).
+ *   q = fminf(fmaxf(p_y, 1e-7f), 1.0f);  SF = sum (double)k_y ((double)(1.0f - q)^gamma (double)(-logf(q))): the power by
+ *   multiplication for gamma = 0, 1, 2, 3 and by powf otherwise; gamma and k = class_weight are rounded to float32 once.
+ *   loss[0] = float32(w (FT + ce_ratio SF / M)), w = weight[0] in DEVICE memory.  R = 0: FT = 0 (focal cross-entropy alone);
+ *   ce_ratio = 0: Tversky alone, no logarithm or power is evaluated.
+ *   coef float [2 R + 1]: [2 r] = w K_r A_r and [2 r + 1] = w K_r B_r, the multipliers of t_r and of 1 in d loss / d p_r, with
+ *   K_r = -(exponent / R) x^(exponent - 1), A_r = (den - num ((1 - fn) - fp)) / den^2, B_r = -(num fp) / den^2, both +0 where
+ *   x <= 0;  [2 R] = w ce_ratio / M.
+ *   No floating-point atomics: per-workgroup partials, added in workgroup-index order; the result repeats bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+struct cwf_focal_params {
+  double fn, fp;          /* weights of the false negatives and the false positives: finite, >= 0, fn + fp > 0 */
+  double exponent;        /* 0 < exponent <= 4 */
+  double smooth;          /* finite, > 0 */
+  double gamma;           /* 0, or 1 <= gamma <= 5 (a gamma in (0, 1) gives 0 * inf at p = 1) */
+  double ce_ratio;        /* finite, >= 0; 0 needs R >= 1 and R = 0 needs ce_ratio > 0 */
+  double class_weight[4]; /* finite, >= 0 */
+};
+/* Bytes of device workspace cwf_focal_loss needs (1024 rows of 3 R + 1 doubles, 256-B aligned), or a negative CWF_E_*:
+ * CWF_E_BADARG for N <= 0, V <= 0 or R outside 0..8, CWF_E_TOOLARGE for more than 2^40 voxels. */
+int64_t cwf_focal_workspace(int N, int64_t V, int R);
+/* Two launches, no host synchronisation, no allocation, nothing read back, no kernel waits on another workgroup: capturable.  ws may
+ * hold anything.  Before any launch: CWF_E_BADARG for a null pointer (posmasks may be null when R = 0), C != 4, N <= 0, V <= 0,
+ * R outside 0..8, a zero mask or one with bits above 3, a parameter outside the ranges above; CWF_E_ALIGN for ws off 256 bytes,
+ * prob off 16, label off 8. */
+int cwf_focal_loss(const float* prob, const int64_t* label, const uint32_t* posmasks, int R, const struct cwf_focal_params* params,
+                   const float* weight, float* loss, float* coef, int N, int64_t V, int C, void* ws, void* stream);
+/* One streaming launch, one 16-byte store per voxel, dprob fully written; float32, every operation rounded on its own:
+ *   u_r = t_r ? coef[2 r] + coef[2 r + 1] : coef[2 r + 1];  d_c = 0.0f + the u_r of the regions holding class c, ascending r;
+ *   where c = y and 1e-7 <= p_y <= 1 (torch's clamp rule), with om = 1.0f - p_y and l = logf(p_y):
+ *     h = -1 / p_y | l - om / p_y | (2 om) l - (om om) / p_y | (3 (om om)) l - ((om om) om) / p_y
+ *         | (gamma powf(om, gamma - 1)) l - powf(om, gamma) / p_y          for gamma = 0 | 1 | 2 | 3 | otherwise
+ *     d_y += coef[2 R] (k_y h);
+ *   dprob[v][c] = gscale[0] d_c.  With ce_ratio = 0 prob is not read.  Errors as cwf_focal_loss (dprob off 16 bytes: CWF_E_ALIGN). */
+int cwf_focal_loss_bwd(const float* prob, const int64_t* label, const uint32_t* posmasks, int R, const struct cwf_focal_params* params,
+                       const float* coef, const float* gscale, float* dprob, int N, int64_t V, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N1  sliding-window inference glue   predict_overlap.py:31-58 (tailor_and_concat), :134-141 + utils/tools.py:44-47,64-109
  *     and utils/hausdorff.py (Hausdorff distance / HD95)
  * ---------------------------------------------------------------------------------------------- */

@@ -1,5 +1,5 @@
 // Declarations shared by the split-bf16 conv kernels (conv_bf16.hip: tap-table kernel, conv16 / conv16s, pointwise streams;
-// conv_ws.hip: weight-stationary kernel for the 32/64/128-channel 3x3x3 layers; conv_wsp.hip: its wave-specialised split-bf16 forward).
+// conv_ws.hip: weight-stationary kernel for the 32/64/128-channel 3x3x3 layers; conv_wsp.hip: its wave-specialised split-bf16 forward; conv_wsd.hip: the wave-specialised single-bf16 kernel of the small deep layers).
 #pragma once
 #include "common.h"
 
@@ -67,6 +67,9 @@ int cwf_ws_takes_x3();
 // conv_wsp.hip: the wave-specialised split-bf16 forward of the 32-256-channel 3x3x3 layers (same contract as cwf_try_conv_ws; cfg_mt /
 // cfg_wm: the tap-table configuration the launch would otherwise take, whose statistics partials it reproduces)
 int cwf_try_conv_wsp(int op, int x3, int cfg_mt, int cfg_wm, ConvArgsB& a, hipStream_t st, int* rc);
+// conv_wsd.hip: the wave-specialised weight-in-LDS single-bf16 kernel of the small 128 / 256-channel 3x3x3 layers (the data gradients at
+// 16^3); same contract as cwf_try_conv_wsp
+int cwf_try_conv_wsd(int op, int x3, int cfg_mt, int cfg_wm, ConvArgsB& a, hipStream_t st, int* rc);
 
 // Host launchers behind the routers cwf_conv (conv_bf16.hip) and cwf_wgrad (wgrad_bf16.hip), which have checked the route.
 int conv_fp32_launch(const cwf_conv_args& d, hipStream_t st);        // conv_mfma.hip: the fp32 tap-table kernel

@@ -1284,7 +1284,7 @@ static void c16_tap_order(ConvGeom& g) {
 }
 
 // The split-bf16 launches that share ConvArgsB, in order of preference: conv16s on a bf16 input image (x16), the pointwise streams,
-// the weight-stationary kernels (conv_wsp, conv_ws), conv16s, the tap-table kernel.
+// the weight-stationary kernels (conv_wsp, conv_wsd, conv_ws), conv16s, the tap-table kernel.
 static int conv_bf16_impl(const cwf_conv_args& d, hipStream_t st) {
   const int op = d.op, x3 = d.precision == CWF_BF16X3, N = d.N, Cin = d.Cin, Cout = d.Cout, y_ldc = d.y_ldc;
   // a bf16 input image stands in for x: conv16s / convws read it through LDS-DMA (16-byte granules, Cin / 8 per voxel)
@@ -1329,6 +1329,10 @@ static int conv_bf16_impl(const cwf_conv_args& d, hipStream_t st) {
   {
     int rcw = 0;                                           // 32 / 64 / 128-channel 3x3x3 layers: weight-stationary kernels
     if (cwf_try_conv_wsp(op, x3, c.MT, c.WM, a, st, &rcw)) return rcw;   // split-bf16 forward, wave-specialised (conv_wsp.hip)
+    // single-bf16 launches of the small deep layers (128 / 256 channels at 16^3: too few tiles for conv_ws.hip's persistent workgroups,
+    // and on the tap-table kernel every wave streams its own weights from L2): one tile x 16 or 32 output channels per workgroup,
+    // weights staged in LDS once (conv_wsd.hip).  In front of conv_ws.hip, which takes 128 -> 256 @16^3 otherwise.
+    if (cwf_try_conv_wsd(op, x3, c.MT, c.WM, a, st, &rcw)) return rcw;
     if (cwf_try_conv_ws(op, x3, a, st, &rcw)) return rcw;    // (conv_ws.hip)
   }
   if (op == CWF_CONV3_S1 && Cin <= 16 && Cout <= 16) c16_tap_order(a.g);

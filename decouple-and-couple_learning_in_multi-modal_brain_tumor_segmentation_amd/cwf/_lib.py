@@ -21,6 +21,8 @@ SIGNATURES = {
     "cwf_version": [],
     "cwf_conv": [P, P],
     "cwf_conv_x16_ok": [I, I, I, I, I, I, I],
+    "cwf_debug_wsd": [I],
+    "cwf_debug_wsd_launches": [],
     "cwf_wgrad": [P, P, P],
     "cwf_gather_split_bf16": [P, I, L, P],
     "cwf_wgrad_nsplit": [I, I, I, I, I, I, I],
@@ -294,7 +296,7 @@ class WindowGrid(C.Structure):
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
 GRADNORM_WS_DOUBLES = 1024     # CWF_GRADNORM_WS_DOUBLES
 RULE_ADAMW, RULE_SGD = 1, 2    # CWF_RULE_ADAMW, CWF_RULE_SGD
-RESTYPE_INT64 = {"cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
+RESTYPE_INT64 = {"cwf_debug_wsd_launches", "cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
                  "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace",
                  "cwf_topk_ce_workspace", "cwf_focal_workspace"}
 

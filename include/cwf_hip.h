@@ -97,6 +97,13 @@ int cwf_conv(const struct cwf_conv_args* args /* host */, void* stream);
 /* 1 if cwf_conv takes a single-bf16 3x3x3 stride-1 launch of these dimensions (Cin / Cout of the LAUNCH: for a data gradient the forward
  * layer's Cout / Cin) with its input as a bf16 image (x16); 0 otherwise.  Host code only; the same code the dispatch evaluates. */
 int cwf_conv_x16_ok(int op, int N, int D, int H, int W, int Cin, int Cout);
+/* Tests and tools: the route of the wave-specialised weight-in-LDS single-bf16 kernel (the data gradients of the 128 / 256-channel
+ * 3x3x3 stride-1 layers at 16^3).  cwf_debug_wsd: 1 = the product route (default), 0 = never (the tap-table kernel's result), 2 = every
+ * eligible launch whatever its size, 3 = as 2 with 32 output channels per workgroup wherever Cout allows; returns the previous value.
+ * cwf_debug_wsd_launches: launches of that kernel so far (host-side count).  Results do not depend on the route: y bit-identical, the
+ * statistics / norm-backward sums equal up to the order of their float64 summation. */
+int cwf_debug_wsd(int v);
+long long cwf_debug_wsd_launches(void);
 
 /* Weight gradient (+ bias gradient) of the same family (op in {CONV3_S1, CONV3_S2, CONV1, CONVT2}):
  *   dW[tap][ci][co] = sum_{n,vox} act(x*in_scale+in_shift)[n, vox*is+tap, ci] * dy[n, vox, co]

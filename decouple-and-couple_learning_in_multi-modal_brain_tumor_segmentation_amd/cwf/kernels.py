@@ -1846,6 +1846,31 @@ class HipBackend:
         self._call("cwf_normalize_nonzero", image.data_ptr(), image[0].numel(), ws.data_ptr(), self._stream())
         return image
 
+    def class_locations(self, label, posmasks, K, out=None):
+        """label: a contiguous uint8 tensor on a GPU (any shape; its C-order linear index is what the table holds) -> (counts int64
+        [R], table int32 [R, K]) on its device: per region (class bitmask over classes 0..3, label 4 read as 3) the voxel count and
+        the evenly ranked table of linear indices, -1 past min(count, K) (cwf_class_locations).  out: (counts, table) to write into,
+        e.g. one subject's rows of a [n, R] / [n, R, K] pair.  No host synchronisation."""
+        if label.dtype != torch.uint8 or not label.is_cuda or not label.is_contiguous() or label.numel() < 1:
+            raise ValueError("class_locations: label must be a non-empty contiguous uint8 tensor on a GPU")
+        masks, cm = self._posmasks("class_locations", posmasks)
+        R, K, V = len(masks), int(K), int(label.numel())
+        nbytes = self.lib.cwf_class_locations_workspace(V, R)
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_class_locations_workspace failed with status %d (V=%d R=%d)" % (nbytes, V, R))
+        if out is None:
+            if not 1 <= K <= 65536:
+                raise _lib.CwfError("cwf_class_locations: K must lie in 1..65536, got %d" % K)
+            out = (torch.empty(R, dtype=torch.int64, device=label.device), torch.empty((R, K), dtype=torch.int32, device=label.device))
+        counts, table = out
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (R,) or table.dtype != torch.int32 or tuple(table.shape) != (R, K) \
+                or not counts.is_contiguous() or not table.is_contiguous() or counts.device != label.device or table.device != label.device:
+            raise ValueError("class_locations: out must be contiguous (int64 [%d], int32 [%d, %d]) tensors on the label's device" % (R, R, K))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=label.device)
+        self._call("cwf_class_locations", label.data_ptr(), V, ctypes.addressof(cm), R, K, counts.data_ptr(), table.data_ptr(),
+                   ws.data_ptr(), self._stream())
+        return counts, table
+
     # ------------------------------------------------------------------ K11 / misc
     def adam(self, table, ntensors, max_n, lr, beta1, beta2, eps, wd, step, amsgrad, hyper_dev=None, grad_scale=1.0):
         self._call("cwf_adam_amsgrad_scaled", table.data_ptr(), ntensors, max_n, lr, beta1, beta2, eps, wd, step, int(amsgrad),

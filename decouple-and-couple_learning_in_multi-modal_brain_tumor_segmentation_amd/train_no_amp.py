@@ -116,6 +116,12 @@ def build_parser():
     p.add_argument("--aug_lowres", default=0.0, type=float,
                    help="(--device_data) z in [0.5, 1): low-resolution simulation of each channel with probability 1/2, sampled on a "
                         "lattice zoomed by U(z, 1) (nearest) and interpolated back (trilinear)")
+    p.add_argument("--oversample_foreground", default=0.0, type=float,
+                   help="(--device_data) P in [0, 1]: that share of the crops is centred on a voxel of a randomly chosen tumour class "
+                        "present in the subject, taken from per-subject location tables built on the device at start-up (nnU-Net's "
+                        "oversample_foreground_percent: 0.33); 0 = every origin uniform")
+    p.add_argument("--foreground_samples", default=4096, type=int,
+                   help="(--oversample_foreground) entries per class in a subject's location table, 1..65536")
     p.add_argument("--normalize", default=False, type=_bool,
                    help="(--device_data) z-score each subject's channels over its brain mask (four-channel sum > 0) at load")
     p.add_argument("--accum_steps", default=1, type=int,
@@ -270,6 +276,16 @@ def check_acquisition_aug(args):
         raise SystemExit("--aug_lowres takes 0 (off) or a smallest zoom in [0.5, 1)")
 
 
+def check_foreground(args):
+    """the values of --oversample_foreground / --foreground_samples (SystemExit with the rule, like the other checks)"""
+    if not 0.0 <= args.oversample_foreground <= 1.0:
+        raise SystemExit("--oversample_foreground takes a share of the crops in [0, 1]")
+    if args.device_data == "off" and args.oversample_foreground > 0.0:
+        raise SystemExit("--oversample_foreground draws from location tables built on the device: it needs --device_data cache or staged")
+    if not 1 <= args.foreground_samples <= 65536:
+        raise SystemExit("--foreground_samples takes 1..65536 table entries per class")
+
+
 def should_save(epoch, end_epoch, save_freq):
     """train_no_amp.py:243-246 (epochs are 0-based in the loop, 1-based in the test)."""
     e = epoch + 1
@@ -308,7 +324,8 @@ def make_device_dataset(args, device):
                             normalize=args.normalize, cache=(args.device_data == "cache"), list_file=lst, rotate=args.aug_rotate,
                             scale=args.aug_scale, elastic=args.aug_elastic, elastic_grid=args.aug_elastic_grid,
                             blur=args.aug_blur, noise=args.aug_noise, gamma=args.aug_gamma, bias=args.aug_bias,
-                            bias_grid=args.aug_bias_grid, contrast=args.aug_contrast, lowres=args.aug_lowres)
+                            bias_grid=args.aug_bias_grid, contrast=args.aug_contrast, lowres=args.aug_lowres,
+                            oversample=args.oversample_foreground, foreground_samples=args.foreground_samples)
 
 
 def main(argv=None):
@@ -325,6 +342,7 @@ def main(argv=None):
         raise SystemExit("--aug_elastic takes voxels >= 0 and --aug_elastic_grid 4 to 8 control points per axis")
     check_intensity_aug(args)
     check_acquisition_aug(args)
+    check_foreground(args)
     check_step_controls(args)
     check_boundary(args)
     check_topk(args)

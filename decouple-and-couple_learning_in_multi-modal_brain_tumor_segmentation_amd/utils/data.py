@@ -253,8 +253,70 @@ def rotation_zoom_matrix(angles_deg, zoom=1.0):
     return ((rz @ ry @ rx) / float(zoom)).astype(np.float32).reshape(9)
 
 
+FOREGROUND_CLASSES = (0b0010, 0b0100, 0b1000)    # the default regions of class_locations: classes 1, 2 and 3, each on its own
+LOCATIONS_MAX_REGIONS, LOCATIONS_MAX_SAMPLES = 8, 65536
+
+
+def _check_regions(posmasks, samples):
+    masks, K = tuple(int(m) for m in posmasks), int(samples)
+    if not 1 <= len(masks) <= LOCATIONS_MAX_REGIONS:
+        raise ValueError("class_locations: takes 1..%d regions, got %d" % (LOCATIONS_MAX_REGIONS, len(masks)))
+    if any(m < 0 or m > 0b1111 for m in masks):
+        raise ValueError("class_locations: a region is a bitmask over classes 0..3, got %r" % (tuple(posmasks),))
+    if not 1 <= K <= LOCATIONS_MAX_SAMPLES:
+        raise ValueError("class_locations: the table length must lie in 1..%d, got %r" % (LOCATIONS_MAX_SAMPLES, samples))
+    return masks, K
+
+
+def class_locations(label, posmasks=FOREGROUND_CLASSES, samples=4096):
+    """(counts int64 [R], table int32 [R, K]) of one subject's label uint8 [S0, S1, S2] (values 0..4 are classes, 4 read as 3; any
+    other value belongs to no region), K = samples, on the label's device.  Region r is the class bitmask posmasks[r] over classes
+    0..3 (1 <= R <= 8; regions may overlap).  counts[r] = n_r, its voxels; with m_r = min(n_r, K), table[r][j] for j < m_r is the
+    C-order linear index of the region voxel of rank floor(j * n_r / m_r), ranks counted in increasing linear index, and -1 for
+    j >= m_r: every voxel of the region when n_r <= K, an evenly ranked sample otherwise.  Exact integers throughout.
+    GPU tensors: HipBackend.class_locations (bit-equal); CPU tensors: numpy."""
+    masks, K = _check_regions(posmasks, samples)
+    if label.dtype != torch.uint8 or not 1 <= label.numel() <= 2 ** 31 - 1:
+        raise ValueError("class_locations: label must be a uint8 tensor of 1..2^31 - 1 voxels")
+    if label.is_cuda:
+        from cwf import kernels
+        return kernels.backend().class_locations(label.contiguous(), masks, K)
+    a = label.contiguous().numpy().reshape(-1)
+    counts, table = np.zeros(len(masks), dtype=np.int64), np.full((len(masks), K), -1, dtype=np.int32)
+    for r, mk in enumerate(masks):
+        member = np.zeros(256, dtype=bool)
+        member[:5] = [bool((mk >> c) & 1) for c in (0, 1, 2, 3, 3)]
+        where = np.flatnonzero(member[a])
+        n = int(where.size)
+        m = min(n, K)
+        counts[r] = n
+        if m:
+            table[r, :m] = where[(np.arange(m, dtype=np.int64) * n) // m]
+    return torch.from_numpy(counts), torch.from_numpy(table)
+
+
+def foreground_origin(seed, epoch, index, full, crop, counts, table, oversample):
+    """The foreground draw of sample `index` in `epoch`, from a stream of its own, default_rng([seed, epoch, index, 1]) (no field of
+    draw_params depends on it): u = random(); the crop is a foreground crop iff u < oversample and some region is non-empty.  Then
+    r = the integers(0, #non-empty)-th non-empty region in region order, j = integers(0, min(counts[r], K)), v = the voxel whose
+    linear index is table[r][j], and origin_d = clamp(v_d - crop_d // 2, 0, max(S_d - crop_d, 0)): inside random_crop_origin's range,
+    with v inside [origin, origin + crop) whichever way the clamp acts and when S_d < crop_d.  Returns (origin, r, v), or
+    (None, None, None) when the crop is not a foreground crop.  counts [R], table [R, K]: class_locations' result on the host."""
+    counts, table = np.asarray(counts), np.asarray(table)
+    rng = np.random.default_rng([int(seed), int(epoch), int(index), 1])
+    u = rng.random()
+    regions = [r for r in range(counts.shape[0]) if int(counts[r]) > 0]
+    if not (u < float(oversample) and regions):
+        return None, None, None
+    r = regions[int(rng.integers(0, len(regions)))]
+    j = int(rng.integers(0, min(int(counts[r]), table.shape[1])))
+    v = tuple(int(c) for c in np.unravel_index(int(table[r][j]), tuple(int(s) for s in full)))
+    origin = tuple(min(max(vd - c // 2, 0), max(s - c, 0)) for vd, c, s in zip(v, crop, full))
+    return origin, r, v
+
+
 def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7,
-                blur=0.0, noise=0.0, gamma=0.0, bias=0.0, bias_grid=4, contrast=0.0, lowres=0.0):
+                blur=0.0, noise=0.0, gamma=0.0, bias=0.0, bias_grid=4, contrast=0.0, lowres=0.0, oversample=0.0, foreground=None):
     """Parameters of sample `index` in `epoch`: a pure function of the arguments, drawn from default_rng([seed, epoch, index]).  The
     origin is drawn first, by random_crop_origin's calls, so with augmentation off it is the origin NpzBraTS / SyntheticBraTS pick.
     flip: three uniforms, each < 0.5 flipping that axis; intensity f > 0: scale ~ U(1-f, 1+f)[4], then shift ~ U(-f, f)[4] (float32).
@@ -267,9 +329,20 @@ def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotat
     is off has the value 0; a transform that is off is None.  Last, in the same manner, the acquisition stage: bias b (0 < b <= 1):
     u = random(4), a ~ U(-b, b)[4, g, g, g] with g = bias_grid, the control multipliers float32(exp(a)) (float64 exp: the field is
     positive without an exponential on the device), bias_mask = u < 0.5; contrast k (0 < k < 1): u = random(4), factor ~ U(1-k, 1+k)[4];
-    lowres z (0.5 <= z < 1): u = random(4), zoom ~ U(z, 1)[4] (a zoom that float32 rounds to 1 becomes the float32 below 1)."""
+    lowres z (0.5 <= z < 1): u = random(4), zoom ~ U(z, 1)[4] (a zoom that float32 rounds to 1 becomes the float32 below 1).
+    oversample p in [0, 1] with foreground = (counts, table), the subject's class_locations on the host: the uniform origin is drawn
+    as ever and then replaced by foreground_origin's when that returns one (a stream of its own: nothing else moves).  With p = 0
+    nothing new is called."""
+    p = float(oversample)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("draw_params: oversample takes a probability in [0, 1], got %r" % (oversample,))
+    if p > 0.0 and foreground is None:
+        raise ValueError("draw_params: oversample > 0 needs foreground = (counts, table), the subject's class_locations")
     rng = np.random.default_rng([int(seed), int(epoch), int(index)])
     origin = random_crop_origin(tuple(full), tuple(crop), rng)
+    if p > 0.0:
+        fg = foreground_origin(seed, epoch, index, full, crop, foreground[0], foreground[1], p)[0]
+        origin = origin if fg is None else fg
     r, z = float(rotate), float(scale)
     fl = tuple(bool(u < 0.5) for u in rng.random(3)) if flip else (False, False, False)
     scale = shift = None
@@ -701,17 +774,22 @@ def _npz_shapes(path):
     return out["image"], out["label"]
 
 
+def _label_array(lab, name):
+    """label -> uint8 [H,W,D] with values in {0,1,2,3,4} (a CPU tensor)"""
+    lab = np.asarray(lab.numpy() if isinstance(lab, torch.Tensor) else lab)
+    if lab.size and (lab.min() < 0 or lab.max() > 4 or np.any(lab != np.round(lab))):
+        bad = sorted(set(np.unique(lab).tolist()) - {0, 1, 2, 3, 4})
+        raise ValueError("%s: label values must lie in {0, 1, 2, 3, 4} (BraTS labels), found %s" % (name, bad[:8]))
+    return torch.from_numpy(np.ascontiguousarray(lab.astype(np.uint8)))
+
+
 def _subject_arrays(img, lab, name):
     """image -> float32 [4,H,W,D] (accepting [H,W,D,4]), label -> uint8 [H,W,D] with values in {0,1,2,3,4} (CPU tensors)."""
     img = torch.as_tensor(np.ascontiguousarray(img.numpy() if isinstance(img, torch.Tensor) else img, dtype=np.float32))
     if img.shape[-1] == 4 and img.shape[0] != 4:
         img = img.permute(3, 0, 1, 2)
     img = img.contiguous()
-    lab = np.asarray(lab.numpy() if isinstance(lab, torch.Tensor) else lab)
-    if lab.size and (lab.min() < 0 or lab.max() > 4 or np.any(lab != np.round(lab))):
-        bad = sorted(set(np.unique(lab).tolist()) - {0, 1, 2, 3, 4})
-        raise ValueError("%s: label values must lie in {0, 1, 2, 3, 4} (BraTS labels), found %s" % (name, bad[:8]))
-    lab = torch.from_numpy(np.ascontiguousarray(lab.astype(np.uint8)))
+    lab = _label_array(lab, name)
     if img.dim() != 4 or img.shape[0] != 4 or tuple(img.shape[1:]) != tuple(lab.shape):
         raise ValueError("%s: image %s and label %s do not form one [4,H,W,D] / [H,W,D] subject" % (name, tuple(img.shape), tuple(lab.shape)))
     return img, lab
@@ -724,10 +802,17 @@ class NpzCropSource(Dataset):
     item is instead the part of the volume the resampled crop reads (staged_box: shapes differ from item to item); flip and
     intensity are taken only because they move the matrix's place in draw_params' stream.  DeviceBraTS's blur / noise / gamma are not
     taken: draw_params draws them after the matrix and the grid, so they move nothing this class reads, and they act on the prepared
-    crop only, so the item is the same with and without them; the same holds for its bias / contrast / lowres, drawn last of all."""
+    crop only, so the item is the same with and without them; the same holds for its bias / contrast / lowres, drawn last of all.
+    oversample > 0 with foreground, the per-subject list of host (counts, table) pairs of class_locations: the origin is draw_params'
+    foreground-oversampled one, on the plain-crop path and the staged_box path alike."""
 
     def __init__(self, subjects, crop, seed=1000, normalize=False, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0,
-                 elastic_grid=7):
+                 elastic_grid=7, oversample=0.0, foreground=None):
+        self.oversample, self.foreground = float(oversample), foreground
+        if not 0.0 <= self.oversample <= 1.0:
+            raise ValueError("NpzCropSource: oversample takes a probability in [0, 1], got %r" % (oversample,))
+        if self.oversample > 0.0 and (foreground is None or len(foreground) != len(subjects)):
+            raise ValueError("NpzCropSource: oversample > 0 needs foreground, one (counts, table) pair per subject")
         self.subjects, self.crop, self.seed, self.normalize, self.epoch = list(subjects), tuple(crop), int(seed), bool(normalize), 0
         self.flip, self.intensity, self.rotate, self.scale = bool(flip), float(intensity), float(rotate), float(scale)
         self.elastic, self.elastic_grid = float(elastic), int(elastic_grid)
@@ -737,6 +822,21 @@ class NpzCropSource(Dataset):
 
     def __len__(self):
         return len(self.subjects)
+
+    def _foreground(self, i):
+        """draw_params' two keywords for subject i"""
+        if self.oversample > 0.0:
+            return {"oversample": self.oversample, "foreground": self.foreground[i]}
+        return {}
+
+    def load_label(self, i):
+        """subject i's label alone, uint8 (only the label array of an .npz is read)"""
+        s = self.subjects[i]
+        if isinstance(s, str):
+            with np.load(s, allow_pickle=False) as z:
+                return _label_array(z["label"], s)
+        lab = s[1]
+        return lab if isinstance(lab, torch.Tensor) and lab.dtype == torch.uint8 else _label_array(lab, "subject %d" % i)
 
     def load(self, i):
         s = self.subjects[i]
@@ -758,10 +858,10 @@ class NpzCropSource(Dataset):
         img, lab = self.load(i)
         if self.rotate > 0.0 or self.scale > 0.0 or self.elastic > 0.0:
             p = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop, self.flip, self.intensity, self.rotate, self.scale,
-                            self.elastic, self.elastic_grid)
+                            self.elastic, self.elastic_grid, **self._foreground(i))
             (a0, b0), (a1, b1), (a2, b2) = staged_box(p, tuple(lab.shape), self.crop)
             return img[:, a0:b0, a1:b1, a2:b2].contiguous(), lab[a0:b0, a1:b1, a2:b2].contiguous(), i
-        o = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop).origin
+        o = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop, **self._foreground(i)).origin
         return crop_pad(img, o, self.crop), crop_pad(lab, o, self.crop), i
 
 
@@ -804,11 +904,17 @@ class DeviceBraTS:
       cache=False  "staged": NpzCropSource crops in DataLoader workers (batches()), the crops are uploaded from pinned memory and
                    prepared at origin 0 -- 36 MB per 128^3 sample over the host link instead of a whole subject.  With rotate /
                    scale / elastic the workers cut staged_box, the part of the volume the resampled crop reads, and the origin moves with it:
-                   the batch is bit-equal to cache=True."""
+                   the batch is bit-equal to cache=True.
+    oversample p > 0 (nnU-Net's oversample_foreground_percent; 0.33 there) moves that share of the crops onto a voxel of a randomly
+    chosen non-empty region of foreground_regions (class bitmasks, default classes 1, 2, 3), taken from the subject's class_locations
+    table of foreground_samples entries per region (draw_params, foreground_origin).  The tables are built once at construction, on
+    `device`: with cache=True from the cached labels into one [n, R, K] / [n, R] tensor pair that is copied to the host once, after
+    the last subject; with cache=False from each subject's label alone (the only array read), which is dropped again.  With p = 0
+    no table is built and nothing new is called."""
 
     def __init__(self, source, device, crop=(128, 128, 128), seed=1000, flip=False, intensity=0.0, normalize=False, cache=True,
                  list_file=None, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7, blur=0.0, noise=0.0, gamma=0.0, bias=0.0,
-                 bias_grid=4, contrast=0.0, lowres=0.0):
+                 bias_grid=4, contrast=0.0, lowres=0.0, oversample=0.0, foreground_regions=FOREGROUND_CLASSES, foreground_samples=4096):
         self.device = torch.device(device)
         self.crop, self.seed, self.epoch = tuple(int(c) for c in crop), int(seed), 0
         self.flip, self.intensity, self.normalize, self.cache = bool(flip), float(intensity), bool(normalize), bool(cache)
@@ -827,8 +933,16 @@ class DeviceBraTS:
         self.source = NpzCropSource(subjects, self.crop, self.seed, self.normalize, self.flip, self.intensity, self.rotate, self.scale,
                                     self.elastic, self.elastic_grid)
         self.images = self.labels = None
+        self.oversample, self.foreground = float(oversample), None
+        if not 0.0 <= self.oversample <= 1.0:
+            raise ValueError("DeviceBraTS: oversample takes a probability in [0, 1], got %r" % (oversample,))
+        if self.oversample > 0.0:
+            self.foreground_regions, self.foreground_samples = _check_regions(foreground_regions, foreground_samples)
         if self.cache:
             self._load_all(subjects)
+        if self.oversample > 0.0:
+            self.foreground = self._locate_all()
+            self.source.oversample, self.source.foreground = self.oversample, self.foreground
 
     def _load_all(self, subjects):
         if self.device.type == "cuda":
@@ -848,6 +962,23 @@ class DeviceBraTS:
             img, lab = self.source.load(i) if self.device.type == "cpu" else self._load_raw(i)
             self.images.append(img)
             self.labels.append(lab)
+
+    def _locate_all(self):
+        """the per-subject list of host (counts int64 [R], table int32 [R, K]) pairs: one class_locations call per subject into its
+        rows of one tensor pair on the device, one copy to the host after the last"""
+        n, R, K = len(self.source), len(self.foreground_regions), self.foreground_samples
+        counts = torch.empty((n, R), dtype=torch.int64, device=self.device)
+        table = torch.empty((n, R, K), dtype=torch.int32, device=self.device)
+        for i in range(n):
+            lab = self.labels[i] if self.labels is not None else self.source.load_label(i).to(self.device)
+            if lab.is_cuda:
+                from cwf import kernels
+                kernels.backend().class_locations(lab.contiguous(), self.foreground_regions, K, out=(counts[i], table[i]))
+            else:
+                c, t = class_locations(lab, self.foreground_regions, K)
+                counts[i], table[i] = c, t
+        counts, table = counts.cpu().numpy(), table.cpu().numpy()
+        return [(counts[i], table[i]) for i in range(n)]
 
     def _load_raw(self, i):
         """subject i on the device; normalised there (the device kernel) when asked"""
@@ -878,7 +1009,7 @@ class DeviceBraTS:
     def params(self, i):
         return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity, self.rotate, self.scale,
                            self.elastic, self.elastic_grid, self.blur, self.noise, self.gamma, self.bias, self.bias_grid, self.contrast,
-                           self.lowres)
+                           self.lowres, **self.source._foreground(i))
 
     def _missing(self, n):
         return torch.zeros((n, 4), dtype=torch.bool, device=self.device)

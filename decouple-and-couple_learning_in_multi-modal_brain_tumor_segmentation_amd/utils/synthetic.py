@@ -108,8 +108,8 @@ def synthetic_sample(index: int, size: Sequence[int] = (128, 128, 128), seed: in
     return x, target, edge_codes(target)
 
 
-def synthetic_volume(index: int, size: Sequence[int] = (128, 128, 128), seed: int = 1000):
-    """(x, target) of synthetic_sample without the edge codes (utils.data.DeviceBraTS derives those per crop)."""
+def synthetic_label(index: int, size: Sequence[int] = (128, 128, 128), seed: int = 1000):
+    """target of synthetic_volume alone (no image is generated)"""
     d, h, w = size
     name = "sample%d_%d" % (seed, index)
     u = uniform01(name + "_c", 8)
@@ -121,6 +121,14 @@ def synthetic_volume(index: int, size: Sequence[int] = (128, 128, 128), seed: in
     target[rr < rad] = 2            # oedema shell
     target[rr < 0.62 * rad] = 1     # core
     target[rr < 0.35 * rad] = 3     # enhancing
+    return target
+
+
+def synthetic_volume(index: int, size: Sequence[int] = (128, 128, 128), seed: int = 1000):
+    """(x, target) of synthetic_sample without the edge codes (utils.data.DeviceBraTS derives those per crop)."""
+    d, h, w = size
+    name = "sample%d_%d" % (seed, index)
+    target = synthetic_label(index, size, seed)
     n = 4 * d * h * w
     x = torch.from_numpy(((uniform01(name + "_x", n) * 2.0 - 1.0) * math.sqrt(3.0)).astype(np.float32)).reshape(4, d, h, w)
     x = x + 0.5 * target.float()[None] * torch.tensor([1.0, -1.0, 0.5, 0.25]).reshape(4, 1, 1, 1)

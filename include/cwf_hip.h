@@ -822,6 +822,26 @@ int cwf_augment_acquisition(const struct cwf_acquire_sample* h_samples, int B, i
 int cwf_normalize_nonzero(float* image, int64_t V, double* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * N4  class location tables of one subject's label, for foreground-oversampled crops (csrc/locations.hip)
+ *   label uint8 [V] (any byte alignment), v the C-order linear index.  Values 0..4 are classes, 4 read as 3; any other value belongs to
+ *   no region.  Region r = class bitmask posmasks[r] over classes 0..3 (host memory, R values, copied into the launches), 1 <= R <= 8;
+ *   regions may overlap.
+ *   counts int64 [R]: counts[r] = n_r, the voxels of region r.
+ *   table int32 [R][K], 1 <= K <= 65536: with m_r = min(n_r, K), table[r][j] for j < m_r is the linear index of the region voxel of rank
+ *   floor(j n_r / m_r), ranks counted in increasing linear index (exact integers); table[r][j] = -1 for j >= m_r.  With n_r <= K the
+ *   row lists every voxel of the region, otherwise an evenly ranked sample.  The result depends on nothing but the label.
+ * ---------------------------------------------------------------------------------------------- */
+#define CWF_LOCATIONS_TILE 16384   /* consecutive voxels of one workgroup, counted from the 16-byte boundary at or below `label` */
+/* Bytes of device workspace cwf_class_locations needs (4 R bytes per tile, 256-B aligned), or CWF_E_BADARG for V < 1, V > 2^31 - 1 or
+ * R outside 1..8. */
+int64_t cwf_class_locations_workspace(int64_t V, int R);
+/* Three launches (count, scan, select); no atomics, no host synchronisation, nothing read back, no kernel waits on another workgroup:
+ * capturable.  ws may hold anything; counts and table are fully written.  Before any launch: CWF_E_BADARG for a null pointer, V < 1 or
+ * V > 2^31 - 1, R outside 1..8, K outside 1..65536, a posmask with bits above class 3; CWF_E_ALIGN for ws off 256 bytes. */
+int cwf_class_locations(const uint8_t* label, int64_t V, const uint32_t* posmasks, int R, int K, int64_t* counts, int32_t* table,
+                        void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K11 fused Adam (amsgrad, L2 weight decay in the gradient)  torch.optim.Adam as used at train_no_amp.py:136,239
  *   table: device array of cwf_adam_desc; one launch updates every parameter.
  * ---------------------------------------------------------------------------------------------- */

@@ -137,9 +137,13 @@ SIGNATURES = {
     "cwf_window_gather": [P, P, P, I, I, P],
     "cwf_window_blend": [P, P, P, P, I, I, I, P],
     "cwf_window_finalize": [P, P, P, P, P],
+    "cwf_window_gather_box": [P, P, P, P, I, I, P],
+    "cwf_window_finalize_box": [P, P, P, P, P, P],
     "cwf_normalize_nonzero": [P, L, P, P],
     "cwf_class_locations_workspace": [L, I],
     "cwf_class_locations": [P, L, P, I, I, P, P, P, P],
+    "cwf_nonzero_box_workspace": [I, I, I, I],
+    "cwf_nonzero_box": [P, L, I, I, I, I, P, P, P, P],
     "cwf_rng_advance": [P, P],
     "cwf_dropout_mask_rng": [P, L, F, F, P, U64, P],
     "cwf_plan_create": [P, P],
@@ -295,13 +299,19 @@ class WindowGrid(C.Structure):
     _fields_ = [("B", I), ("S", I * 3), ("r", I * 3), ("n", I * 3), ("start", (I * WINDOW_MAX_STARTS) * 3)]
 
 
+class WindowBox(C.Structure):
+    """struct cwf_window_box (include/cwf_hip.h)"""
+    _fields_ = [("full", I * 3), ("lo", I * 3)]
+
+
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
 GRADNORM_WS_DOUBLES = 1024     # CWF_GRADNORM_WS_DOUBLES
 RULE_ADAMW, RULE_SGD = 1, 2    # CWF_RULE_ADAMW, CWF_RULE_SGD
 RESTYPE_INT64 = {"cwf_debug_wsd_launches", "cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
                  "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace",
-                 "cwf_topk_ce_workspace", "cwf_focal_workspace", "cwf_class_locations_workspace"}
+                 "cwf_topk_ce_workspace", "cwf_focal_workspace", "cwf_class_locations_workspace", "cwf_nonzero_box_workspace"}
 LOCATIONS_TILE = 16384     # CWF_LOCATIONS_TILE: the voxels of one workgroup of cwf_class_locations (a 16-byte aligned label starts tile 0)
+NONZERO_BOX_TILE = 4096    # CWF_NONZERO_BOX_TILE: the voxels of one workgroup of cwf_nonzero_box (a 16-byte aligned sample starts tile 0)
 
 _lib = None
 

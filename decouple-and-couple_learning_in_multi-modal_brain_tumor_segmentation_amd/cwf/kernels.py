@@ -1668,6 +1668,37 @@ class HipBackend:
         self._call("cwf_window_finalize", acc.data_ptr(), weights.data_ptr(), y.data_ptr(), ctypes.byref(grid), self._stream())
         return y
 
+    @staticmethod
+    def window_box(full, lo):
+        """struct cwf_window_box: the grid's volume is the box [lo, lo + grid.S) of a volume of extent `full`.  Only packs it."""
+        bx = _lib.WindowBox()
+        for a in range(3):
+            bx.full[a], bx.lo[a] = int(full[a]), int(lo[a])
+        return bx
+
+    def window_gather_box(self, x, grid, box, w0, count):
+        """window_gather of the crop x[:, :, lo0:lo0+S0, lo1:lo1+S1, lo2:lo2+S2] (S = grid.S, lo = box.lo), bit for bit, reading the
+        whole x [B,4,*box.full] in place: voxels of a window outside the box are zero (cwf_window_gather_box)."""
+        x = x.contiguous()
+        assert x.dtype == _f32 and x.dim() == 5 and x.shape[1] == 4 and tuple(x.shape[2:]) == tuple(box.full) and x.shape[0] == grid.B
+        r = tuple(grid.r)
+        win = torch.empty((int(count) * grid.B,) + r + (4,), dtype=_f32, device=x.device)
+        self._call("cwf_window_gather_box", x.data_ptr(), win.data_ptr(), ctypes.byref(grid), ctypes.byref(box), int(w0), int(count),
+                   self._stream())
+        return win.permute(0, 4, 1, 2, 3)
+
+    def window_finalize_box(self, acc, weights, grid, box, out=None):
+        """acc [B,S0,S1,S2,4] in box coordinates -> prob [B,4,*box.full] NCDHW: window_finalize's values inside the box, the background
+        one-hot (1, 0, 0, 0) outside it, every element written once by one launch (cwf_window_finalize_box).  out: the tensor to fill."""
+        assert acc.is_contiguous() and tuple(acc.shape) == (grid.B,) + tuple(grid.S) + (4,)
+        assert weights.is_contiguous() and weights.dtype == _f32 and weights.numel() == sum(grid.r)
+        shape = (grid.B, 4) + tuple(box.full)
+        y = torch.empty(shape, dtype=_f32, device=acc.device) if out is None else out
+        assert y.is_contiguous() and y.dtype == _f32 and tuple(y.shape) == shape and y.device == acc.device
+        self._call("cwf_window_finalize_box", acc.data_ptr(), weights.data_ptr(), y.data_ptr(), ctypes.byref(grid), ctypes.byref(box),
+                   self._stream())
+        return y
+
     # ------------------------------------------------------------------ N3 training-batch preparation
     def prepare_batch(self, images, labels, params, crop, out=None):
         """Training batch (x [B,4,C0,C1,C2] fp32, target [B,C0,C1,C2] int64, edge [B,C0,C1,C2] int64) from per-sample source volumes
@@ -1870,6 +1901,31 @@ class HipBackend:
         self._call("cwf_class_locations", label.data_ptr(), V, ctypes.addressof(cm), R, K, counts.data_ptr(), table.data_ptr(),
                    ws.data_ptr(), self._stream())
         return counts, table
+
+    def nonzero_box(self, x, out=None):
+        """x fp32 [B,4,S0,S1,S2] on a GPU, each sample's four channels contiguous (a batch stride of its own is fine, any 4-byte
+        alignment) -> (box int32 [B,6] = lo0, lo1, lo2, hi0, hi1, hi2 with hi exclusive, count int64 [B]) on its device: the tightest
+        box of the voxels with a channel whose bits & 0x7fffffff != 0, and their number; lo = S, hi = 0, count = 0 for a sample
+        without one (cwf_nonzero_box).  out: (box, count) to write into, e.g. one subject's rows.  No host synchronisation."""
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == _f32 and x.dim() == 5 and x.shape[1] == 4 and x.numel() > 0):
+            raise ValueError("nonzero_box: x must be a non-empty float32 [B, 4, S0, S1, S2] tensor on a GPU")
+        if not x[0].is_contiguous() or (x.shape[0] > 1 and x.stride(0) < x[0].numel()):
+            x = x.contiguous()
+        B, (S0, S1, S2) = int(x.shape[0]), (int(s) for s in x.shape[2:])
+        nbytes = self.lib.cwf_nonzero_box_workspace(B, S0, S1, S2)
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_nonzero_box_workspace failed with status %d (B=%d S=%r)" % (nbytes, B, (S0, S1, S2)))
+        if out is None:
+            out = (torch.empty((B, 6), dtype=torch.int32, device=x.device), torch.empty(B, dtype=torch.int64, device=x.device))
+        box, count = out
+        if box.dtype != torch.int32 or tuple(box.shape) != (B, 6) or count.dtype != torch.int64 or tuple(count.shape) != (B,) \
+                or not box.is_contiguous() or not count.is_contiguous() or box.device != x.device or count.device != x.device:
+            raise ValueError("nonzero_box: out must be contiguous (int32 [%d, 6], int64 [%d]) tensors on x's device" % (B, B))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+        bstride = int(x.stride(0)) if B > 1 else 4 * S0 * S1 * S2
+        self._call("cwf_nonzero_box", x.data_ptr(), bstride, B, S0, S1, S2, box.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                   self._stream())
+        return box, count
 
     # ------------------------------------------------------------------ K11 / misc
     def adam(self, table, ntensors, max_n, lr, beta1, beta2, eps, wd, step, amsgrad, hyper_dev=None, grad_scale=1.0):

@@ -122,6 +122,9 @@ def build_parser():
                         "oversample_foreground_percent: 0.33); 0 = every origin uniform")
     p.add_argument("--foreground_samples", default=4096, type=int,
                    help="(--oversample_foreground) entries per class in a subject's location table, 1..65536")
+    p.add_argument("--crop_nonzero", default=False, type=_bool,
+                   help="(--device_data) draw every crop that is not a foreground crop inside the subject's nonzero box (the brain): the "
+                        "crop lies in the box, or the box in the crop (what nnU-Net gets from cropping subjects to nonzero)")
     p.add_argument("--normalize", default=False, type=_bool,
                    help="(--device_data) z-score each subject's channels over its brain mask (four-channel sum > 0) at load")
     p.add_argument("--accum_steps", default=1, type=int,
@@ -284,6 +287,8 @@ def check_foreground(args):
         raise SystemExit("--oversample_foreground draws from location tables built on the device: it needs --device_data cache or staged")
     if not 1 <= args.foreground_samples <= 65536:
         raise SystemExit("--foreground_samples takes 1..65536 table entries per class")
+    if args.device_data == "off" and args.crop_nonzero:
+        raise SystemExit("--crop_nonzero draws from the subjects' nonzero boxes, which DeviceBraTS takes: it needs --device_data cache or staged")
 
 
 def should_save(epoch, end_epoch, save_freq):
@@ -325,7 +330,8 @@ def make_device_dataset(args, device):
                             scale=args.aug_scale, elastic=args.aug_elastic, elastic_grid=args.aug_elastic_grid,
                             blur=args.aug_blur, noise=args.aug_noise, gamma=args.aug_gamma, bias=args.aug_bias,
                             bias_grid=args.aug_bias_grid, contrast=args.aug_contrast, lowres=args.aug_lowres,
-                            oversample=args.oversample_foreground, foreground_samples=args.foreground_samples)
+                            oversample=args.oversample_foreground, foreground_samples=args.foreground_samples,
+                            crop_nonzero=args.crop_nonzero)
 
 
 def main(argv=None):

@@ -35,6 +35,57 @@ def random_crop_origin(full, crop, rng):
     return tuple(int(rng.integers(0, max(f - c, 0) + 1)) for f, c in zip(full, crop))
 
 
+def nonzero_boxes_host(a):
+    """(box int32 [B, 6] = lo0, lo1, lo2, hi0, hi1, hi2 with hi exclusive, count int64 [B]) of a float32 array [B, 4, S0, S1, S2]:
+    per sample the tightest box of the voxels with some channel whose bits & 0x7fffffff != 0 (+-0 is background; denormals,
+    infinities and NaN are not) and their number; lo = S, hi = 0, count = 0 without one.  The numpy statement of cwf_nonzero_box."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    nz = ((a.view(np.uint32) & np.uint32(0x7fffffff)) != 0).any(axis=1)
+    box = np.empty((a.shape[0], 6), dtype=np.int32)
+    for b in range(a.shape[0]):
+        for d in range(3):
+            where = np.flatnonzero(nz[b].any(axis=tuple(k for k in range(3) if k != d)))
+            box[b, d], box[b, 3 + d] = (where[0], where[-1] + 1) if where.size else (a.shape[2 + d], 0)
+    return box, nz.reshape(a.shape[0], -1).sum(axis=1, dtype=np.int64)
+
+
+def nonzero_box(image):
+    """(lo, hi), two triples of Python ints with hi exclusive: the tightest box holding every nonzero voxel of one subject image
+    float32 [4, S0, S1, S2] (nonzero_boxes_host's rule: the bits are tested), or None when the image is zero everywhere.  GPU
+    tensors: HipBackend.nonzero_box and one copy of six integers to the host; CPU tensors: numpy.  The two are bit-equal."""
+    if not (torch.is_tensor(image) and image.dtype == torch.float32 and image.dim() == 4 and image.shape[0] == 4 and image.numel() > 0):
+        raise ValueError("nonzero_box: image must be a non-empty float32 [4, S0, S1, S2] tensor, got %s %s"
+                         % (getattr(image, "dtype", type(image)), tuple(getattr(image, "shape", ()))))
+    if image.is_cuda:
+        from cwf import kernels
+        box = kernels.backend().nonzero_box(image.contiguous()[None])[0].cpu().numpy()[0]
+    else:
+        box = nonzero_boxes_host(image.numpy()[None])[0][0]
+    return _box_tuple(box)
+
+
+def _box_tuple(box):
+    """six integers lo | hi -> (lo, hi), None for the empty box (hi = 0)"""
+    box = [int(v) for v in box]
+    return None if box[3] == 0 else (tuple(box[:3]), tuple(box[3:]))
+
+
+def box_crop_origin(full, crop, box, rng):
+    """Crop origin inside the nonzero box = (lo, hi) of a volume of extent `full`: one rng.integers call per axis, as
+    random_crop_origin makes.  Per axis, with a, b the box's lo and hi, c the crop and top = max(S - c, 0) (random_crop_origin's
+    largest origin): the origin is uniform on [max(lo', 0), min(hi', top)] with [lo', hi'] = [a, b - c] when b - a >= c (the crop
+    lies in the box) and [b - c, a] otherwise (the box lies in the crop).  The range is never empty, and every draw has
+    |crop n box| = min(c, b - a) along the axis."""
+    origin = []
+    for s, c, a, b in zip(full, crop, box[0], box[1]):
+        s, c, a, b = int(s), int(c), int(a), int(b)
+        if not 0 <= a < b <= s:
+            raise ValueError("box_crop_origin: the box (%r, %r) does not lie in a volume of extent %r" % (tuple(box[0]), tuple(box[1]), tuple(full)))
+        lo, hi = (a, b - c) if b - a >= c else (b - c, a)
+        origin.append(int(rng.integers(max(lo, 0), min(hi, max(s - c, 0)) + 1)))
+    return tuple(origin)
+
+
 def crop_pad(vol, origin, crop):
     """vol [..., H, W, D] -> [..., crop]; zero padding where the crop leaves the volume."""
     out = vol.new_zeros(vol.shape[:-3] + tuple(crop))
@@ -316,7 +367,7 @@ def foreground_origin(seed, epoch, index, full, crop, counts, table, oversample)
 
 
 def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7,
-                blur=0.0, noise=0.0, gamma=0.0, bias=0.0, bias_grid=4, contrast=0.0, lowres=0.0, oversample=0.0, foreground=None):
+                blur=0.0, noise=0.0, gamma=0.0, bias=0.0, bias_grid=4, contrast=0.0, lowres=0.0, oversample=0.0, foreground=None, box=None):
     """Parameters of sample `index` in `epoch`: a pure function of the arguments, drawn from default_rng([seed, epoch, index]).  The
     origin is drawn first, by random_crop_origin's calls, so with augmentation off it is the origin NpzBraTS / SyntheticBraTS pick.
     flip: three uniforms, each < 0.5 flipping that axis; intensity f > 0: scale ~ U(1-f, 1+f)[4], then shift ~ U(-f, f)[4] (float32).
@@ -332,14 +383,18 @@ def draw_params(seed, epoch, index, full, crop, flip=False, intensity=0.0, rotat
     lowres z (0.5 <= z < 1): u = random(4), zoom ~ U(z, 1)[4] (a zoom that float32 rounds to 1 becomes the float32 below 1).
     oversample p in [0, 1] with foreground = (counts, table), the subject's class_locations on the host: the uniform origin is drawn
     as ever and then replaced by foreground_origin's when that returns one (a stream of its own: nothing else moves).  With p = 0
-    nothing new is called."""
+    nothing new is called.
+    box = (lo, hi), the subject's nonzero_box: the origin's three draws, still the first of the stream, are box_crop_origin's instead
+    of random_crop_origin's, so the crop lies in the box or the box in the crop.  The ranges differ from the uniform ones, and a
+    bounded draw may take a different number of words from the generator, so every later field may differ from a box-less call's.
+    A foreground origin replaces this one as it replaces the uniform one.  With box = None nothing moves, bit for bit."""
     p = float(oversample)
     if not 0.0 <= p <= 1.0:
         raise ValueError("draw_params: oversample takes a probability in [0, 1], got %r" % (oversample,))
     if p > 0.0 and foreground is None:
         raise ValueError("draw_params: oversample > 0 needs foreground = (counts, table), the subject's class_locations")
     rng = np.random.default_rng([int(seed), int(epoch), int(index)])
-    origin = random_crop_origin(tuple(full), tuple(crop), rng)
+    origin = random_crop_origin(tuple(full), tuple(crop), rng) if box is None else box_crop_origin(tuple(full), tuple(crop), box, rng)
     if p > 0.0:
         fg = foreground_origin(seed, epoch, index, full, crop, foreground[0], foreground[1], p)[0]
         origin = origin if fg is None else fg
@@ -804,10 +859,16 @@ class NpzCropSource(Dataset):
     taken: draw_params draws them after the matrix and the grid, so they move nothing this class reads, and they act on the prepared
     crop only, so the item is the same with and without them; the same holds for its bias / contrast / lowres, drawn last of all.
     oversample > 0 with foreground, the per-subject list of host (counts, table) pairs of class_locations: the origin is draw_params'
-    foreground-oversampled one, on the plain-crop path and the staged_box path alike."""
+    foreground-oversampled one, on the plain-crop path and the staged_box path alike.
+    crop_nonzero: the origin is draw_params' box origin, inside the subject's nonzero box.  The box is taken from the raw image the
+    item has just loaded, before normalize_nonzero, by the numpy statement (nonzero_boxes_host) and memoised per subject in `boxes`
+    (index -> six integers lo | hi); the item then carries it as a fourth element, so that the process that prepares the batch
+    learns it from a DataLoader worker without loading the subject itself.  A subject that is zero everywhere is drawn as if the
+    option were off."""
 
     def __init__(self, subjects, crop, seed=1000, normalize=False, flip=False, intensity=0.0, rotate=0.0, scale=0.0, elastic=0.0,
-                 elastic_grid=7, oversample=0.0, foreground=None):
+                 elastic_grid=7, oversample=0.0, foreground=None, crop_nonzero=False):
+        self.crop_nonzero, self.boxes = bool(crop_nonzero), {}
         self.oversample, self.foreground = float(oversample), foreground
         if not 0.0 <= self.oversample <= 1.0:
             raise ValueError("NpzCropSource: oversample takes a probability in [0, 1], got %r" % (oversample,))
@@ -828,6 +889,18 @@ class NpzCropSource(Dataset):
         if self.oversample > 0.0:
             return {"oversample": self.oversample, "foreground": self.foreground[i]}
         return {}
+
+    def box(self, i):
+        """subject i's nonzero box as six integers lo | hi (hi = 0: empty); loads the subject when no one has yet"""
+        if i not in self.boxes:
+            self.load(i)
+        return self.boxes[i]
+
+    def _origin_keywords(self, i):
+        """draw_params' keywords that move the origin of subject i: _foreground's and, with crop_nonzero, the box"""
+        kw = self._foreground(i)
+        box = _box_tuple(self.box(i)) if self.crop_nonzero else None
+        return kw if box is None else dict(kw, box=box)
 
     def load_label(self, i):
         """subject i's label alone, uint8 (only the label array of an .npz is read)"""
@@ -850,6 +923,8 @@ class NpzCropSource(Dataset):
                 img, lab = _subject_arrays(img, lab, "subject %d" % i)
             elif self.normalize:
                 img = img.clone()
+        if self.crop_nonzero and i not in self.boxes:
+            self.boxes[i] = tuple(int(v) for v in nonzero_boxes_host(img.numpy()[None])[0][0])
         if self.normalize:
             normalize_nonzero(img)
         return img, lab
@@ -858,11 +933,13 @@ class NpzCropSource(Dataset):
         img, lab = self.load(i)
         if self.rotate > 0.0 or self.scale > 0.0 or self.elastic > 0.0:
             p = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop, self.flip, self.intensity, self.rotate, self.scale,
-                            self.elastic, self.elastic_grid, **self._foreground(i))
+                            self.elastic, self.elastic_grid, **self._origin_keywords(i))
             (a0, b0), (a1, b1), (a2, b2) = staged_box(p, tuple(lab.shape), self.crop)
-            return img[:, a0:b0, a1:b1, a2:b2].contiguous(), lab[a0:b0, a1:b1, a2:b2].contiguous(), i
-        o = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop, **self._foreground(i)).origin
-        return crop_pad(img, o, self.crop), crop_pad(lab, o, self.crop), i
+            item = img[:, a0:b0, a1:b1, a2:b2].contiguous(), lab[a0:b0, a1:b1, a2:b2].contiguous(), i
+        else:
+            o = draw_params(self.seed, self.epoch, i, tuple(lab.shape), self.crop, **self._origin_keywords(i)).origin
+            item = crop_pad(img, o, self.crop), crop_pad(lab, o, self.crop), i
+        return item + (self.boxes[i],) if self.crop_nonzero else item
 
 
 def staged_box(p, extents, crop):
@@ -876,10 +953,11 @@ def staged_box(p, extents, crop):
 
 
 def _collate_crops(items, stack=True):
-    imgs, labs, idx = zip(*items)
+    imgs, labs, idx, *boxes = zip(*items)
+    boxes = tuple(list(b) for b in boxes)   # crop_nonzero: the subjects' nonzero boxes as a fourth element
     if not stack:                       # source boxes of resampled crops: one shape per item
-        return list(imgs), list(labs), list(idx)
-    return torch.stack(imgs), torch.stack(labs), list(idx)
+        return (list(imgs), list(labs), list(idx)) + boxes
+    return (torch.stack(imgs), torch.stack(labs), list(idx)) + boxes
 
 
 def _collate_boxes(items):
@@ -910,12 +988,21 @@ class DeviceBraTS:
     table of foreground_samples entries per region (draw_params, foreground_origin).  The tables are built once at construction, on
     `device`: with cache=True from the cached labels into one [n, R, K] / [n, R] tensor pair that is copied to the host once, after
     the last subject; with cache=False from each subject's label alone (the only array read), which is dropped again.  With p = 0
-    no table is built and nothing new is called."""
+    no table is built and nothing new is called.
+    crop_nonzero (what nnU-Net gets from cropping every subject to its nonzero box in preprocessing; off by default, and then nothing
+    new is called) draws the origins that are not foreground origins inside the subject's nonzero box (draw_params(box=),
+    box_crop_origin): the crop lies in the box, or the box in the crop.  The box is that of the raw image, before normalize.  With
+    cache=True on a GPU it is one cwf_nonzero_box call per subject at construction into one [n, 6] tensor that is copied to the host
+    once, after the last subject; otherwise (staged mode, a CPU instance) NpzCropSource takes it with numpy from the image it has
+    just loaded, DataLoader workers included.  All of them give bit-equal batches; a subject that is zero everywhere is drawn as if
+    the option were off."""
 
     def __init__(self, source, device, crop=(128, 128, 128), seed=1000, flip=False, intensity=0.0, normalize=False, cache=True,
                  list_file=None, rotate=0.0, scale=0.0, elastic=0.0, elastic_grid=7, blur=0.0, noise=0.0, gamma=0.0, bias=0.0,
-                 bias_grid=4, contrast=0.0, lowres=0.0, oversample=0.0, foreground_regions=FOREGROUND_CLASSES, foreground_samples=4096):
+                 bias_grid=4, contrast=0.0, lowres=0.0, oversample=0.0, foreground_regions=FOREGROUND_CLASSES, foreground_samples=4096,
+                 crop_nonzero=False):
         self.device = torch.device(device)
+        self.crop_nonzero = bool(crop_nonzero)
         self.crop, self.seed, self.epoch = tuple(int(c) for c in crop), int(seed), 0
         self.flip, self.intensity, self.normalize, self.cache = bool(flip), float(intensity), bool(normalize), bool(cache)
         self.rotate, self.scale = float(rotate), float(scale)
@@ -931,7 +1018,7 @@ class DeviceBraTS:
         if not subjects:
             raise ValueError("DeviceBraTS: no subjects")
         self.source = NpzCropSource(subjects, self.crop, self.seed, self.normalize, self.flip, self.intensity, self.rotate, self.scale,
-                                    self.elastic, self.elastic_grid)
+                                    self.elastic, self.elastic_grid, crop_nonzero=self.crop_nonzero)
         self.images = self.labels = None
         self.oversample, self.foreground = float(oversample), None
         if not 0.0 <= self.oversample <= 1.0:
@@ -958,10 +1045,17 @@ class DeviceBraTS:
                 raise MemoryError("DeviceBraTS(cache=True) needs %.1f GB of device memory for %d subjects, %.1f GB are free: use "
                                   "cache=False (the 'staged' mode) instead" % (need / 1e9, len(subjects), free / 1e9))
         self.images, self.labels = [], []
+        boxes = None
+        if self.crop_nonzero and self.device.type != "cpu":     # one row per subject, written by cwf_nonzero_box on the raw image
+            boxes = torch.empty((len(subjects), 6), dtype=torch.int32, device=self.device)
+            counts = torch.empty(len(subjects), dtype=torch.int64, device=self.device)
         for i in range(len(subjects)):
-            img, lab = self.source.load(i) if self.device.type == "cpu" else self._load_raw(i)
+            img, lab = self.source.load(i) if self.device.type == "cpu" else \
+                self._load_raw(i, None if boxes is None else (boxes[i:i + 1], counts[i:i + 1]))
             self.images.append(img)
             self.labels.append(lab)
+        if boxes is not None:
+            self.source.boxes = {i: tuple(int(v) for v in row) for i, row in enumerate(boxes.cpu().numpy())}
 
     def _locate_all(self):
         """the per-subject list of host (counts int64 [R], table int32 [R, K]) pairs: one class_locations call per subject into its
@@ -980,15 +1074,19 @@ class DeviceBraTS:
         counts, table = counts.cpu().numpy(), table.cpu().numpy()
         return [(counts[i], table[i]) for i in range(n)]
 
-    def _load_raw(self, i):
-        """subject i on the device; normalised there (the device kernel) when asked"""
+    def _load_raw(self, i, box_out=None):
+        """subject i on the device; normalised there (the device kernel) when asked.  box_out: the (box [1, 6], count [1]) rows that
+        cwf_nonzero_box fills from the raw image"""
         src = self.source
-        norm, src.normalize = src.normalize, False
+        norm, src.normalize, nz, src.crop_nonzero = src.normalize, False, src.crop_nonzero, False
         try:
             img, lab = src.load(i)
         finally:
-            src.normalize = norm
+            src.normalize, src.crop_nonzero = norm, nz
         img, lab = img.to(self.device).contiguous(), lab.to(self.device).contiguous()
+        if box_out is not None:
+            from cwf import kernels
+            kernels.backend().nonzero_box(img[None], out=box_out)
         if self.normalize:
             normalize_nonzero(img)
         return img, lab
@@ -1009,7 +1107,7 @@ class DeviceBraTS:
     def params(self, i):
         return draw_params(self.seed, self.epoch, i, self.extents(i), self.crop, self.flip, self.intensity, self.rotate, self.scale,
                            self.elastic, self.elastic_grid, self.blur, self.noise, self.gamma, self.bias, self.bias_grid, self.contrast,
-                           self.lowres, **self.source._foreground(i))
+                           self.lowres, **self.source._origin_keywords(i))
 
     def _missing(self, n):
         return torch.zeros((n, 4), dtype=torch.bool, device=self.device)
@@ -1026,7 +1124,9 @@ class DeviceBraTS:
     def prepare_staged(self, crops, out=None):
         """(image crops [B,4,*crop] float32, label crops [B,*crop] uint8, indices) from NpzCropSource -> the prepared batch; with
         rotate / scale / elastic the crops are lists of source boxes and every sample is re-origined by its box's low corner"""
-        imgs, labs, idx = crops
+        imgs, labs, idx, *boxes = crops
+        if boxes:                           # crop_nonzero: what the loader (a worker, perhaps) found for these subjects
+            self.source.boxes.update((int(i), tuple(int(v) for v in b)) for i, b in zip(idx, boxes[0]))
         params = [self.params(i) for i in idx]
         if self.affine:
             if self.device.type == "cuda":

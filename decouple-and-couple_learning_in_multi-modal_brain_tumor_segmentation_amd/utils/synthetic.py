@@ -135,6 +135,24 @@ def synthetic_volume(index: int, size: Sequence[int] = (128, 128, 128), seed: in
     return x, target
 
 
+def ellipsoid_mask(size: Sequence[int], box: Sequence[Sequence[int]]) -> torch.Tensor:
+    """bool [*size]: the ellipsoid inscribed in box = (lo, hi), hi exclusive -- voxel i is inside iff the sum over the axes of
+    ((2 i - (lo + hi - 1)) / (hi - lo))^2 is <= 1 (float64), so the mask touches every face of the box at its centre and its
+    nonzero box is the box itself."""
+    lo, hi = box
+    axes = [((2.0 * torch.arange(s, dtype=torch.float64) - (a + b - 1)) / (b - a)) ** 2 for s, a, b in zip(size, lo, hi)]
+    return (axes[0][:, None, None] + axes[1][None, :, None] + axes[2][None, None, :]) <= 1.0
+
+
+def synthetic_masked_volume(index: int, size: Sequence[int] = (240, 240, 155), box=((50, 35, 8), (190, 205, 148)), seed: int = 1000):
+    """(x, target) of synthetic_volume with a background, as a skull-stripped BraTS subject has one: x and target are zero outside
+    ellipsoid_mask(size, box).  The default box, 140 x 170 x 140 in 240 x 240 x 155, is about the brain's; the noise of x is nonzero
+    at the face centres (a zero there has probability 2^-96), so the nonzero box of x is `box`."""
+    x, target = synthetic_volume(index, size, seed)
+    m = ellipsoid_mask(size, box)
+    return x * m[None].to(x.dtype), target * m.to(target.dtype)
+
+
 def synthetic_batch(indices: Sequence[int], size=(128, 128, 128), seed: int = 1000):
     xs, ts, es = zip(*(synthetic_sample(i, size, seed) for i in indices))
     return torch.stack(xs), torch.stack(ts), torch.stack(es)

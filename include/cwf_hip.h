@@ -669,6 +669,25 @@ int cwf_window_finalize(const float* acc, const float* weights, float* y, const 
 /* CWF_E_BADARG (all three): a null pointer, a misaligned windows / probs / acc (16 B) or x / weights / y (4 B), B, S, r or n out of
  * range, a window entirely outside the volume, count <= 0 or windows past the last; CWF_E_TOOLARGE: 2^31 voxels or more in the
  * volume or a window, count * B > 65535.                                                                                             */
+/* Windows on a sub-box of a volume, read and written in place (sliding_window_inference(crop_nonzero=True): the windows cover the
+ * nonzero box of the brain only).  The box covers voxels [lo[a], lo[a] + grid->S[a]) of a [B][4][full0][full1][full2] volume: the
+ * grid's S is the BOX's extent and its starts are box coordinates.                                                                  */
+struct cwf_window_box {
+  int full[3];                                /* the extent of the whole volume */
+  int lo[3];                                  /* the box's low corner in it; lo[a] >= 0, lo[a] + S[a] <= full[a] */
+};
+/* cwf_window_gather of the contiguous copy x[:, :, lo0:lo0+S0, lo1:lo1+S1, lo2:lo2+S2], bit for bit, without the copy: x is the whole
+ * volume; voxels of a window outside the BOX are zero, whatever the volume holds there.                                             */
+int cwf_window_gather_box(const float* x, float* windows, const struct cwf_window_grid* grid, const struct cwf_window_box* box, int w0,
+                          int count, void* stream);
+/* acc[b][S0][S1][S2][4] in box coordinates, as cwf_window_blend leaves it; y[b][4][full0][full1][full2] the whole volume: inside the
+ * box what cwf_window_finalize writes, bit for bit; outside it the background one-hot (1, 0, 0, 0).  One thread per voxel of the whole
+ * volume: every element of y is written exactly once, no fill pass and no paste copy.                                                */
+int cwf_window_finalize_box(const float* acc, const float* weights, float* y, const struct cwf_window_grid* grid,
+                            const struct cwf_window_box* box, void* stream);
+/* Both refuse what cwf_window_gather / cwf_window_finalize refuse, with the same codes, and CWF_E_BADARG: a null box, full < 1,
+ * lo < 0 or lo + S > full along an axis; CWF_E_TOOLARGE: 2^31 voxels or more in the whole volume.  cwf_window_gather and
+ * cwf_window_finalize are these two with the box the whole volume.                                                                   */
 
 /* ------------------------------------------------------------------------------------------------
  * N3  training-batch preparation (utils/data.py prepare_batch / DeviceBraTS: crop, flips, intensity, label remap, edge codes)
@@ -840,6 +859,25 @@ int64_t cwf_class_locations_workspace(int64_t V, int R);
  * V > 2^31 - 1, R outside 1..8, K outside 1..65536, a posmask with bits above class 3; CWF_E_ALIGN for ws off 256 bytes. */
 int cwf_class_locations(const uint8_t* label, int64_t V, const uint32_t* posmasks, int R, int K, int64_t* counts, int32_t* table,
                         void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * N9  the nonzero bounding box of four-channel volumes (csrc/nonzero_box.hip): where the skull-stripped brain lies in a BraTS volume
+ *   x fp32 [B][4][S0][S1][S2]: sample b at x + b * bstride floats (bstride >= 4 V, V = S0 S1 S2 <= 2^31 - 1), its four channels
+ *   contiguous; any 4-byte alignment.  A voxel is nonzero iff (bits & 0x7fffffff) != 0 in some channel: +-0 is background, denormals,
+ *   infinities and NaN are not (the bits are tested, not a float compare).
+ *   box int32 [B][6] = lo0, lo1, lo2, hi0, hi1, hi2 (hi exclusive): the tightest box holding every nonzero voxel of the sample.
+ *   count int64 [B]: its nonzero voxels.  A sample without one: lo = S, hi = 0, count = 0.  The result depends on nothing but x.
+ * ---------------------------------------------------------------------------------------------- */
+#define CWF_NONZERO_BOX_TILE 4096  /* consecutive voxels of one workgroup, counted from the 16-byte boundary at or below the sample */
+/* Bytes of device workspace cwf_nonzero_box needs (32 bytes per tile and sample, 256-B aligned), or the code cwf_nonzero_box returns
+ * for the same B and extents. */
+int64_t cwf_nonzero_box_workspace(int B, int S0, int S1, int S2);
+/* Two launches (per-tile partials stored plainly, a one-workgroup finalize per sample); no atomics, no host synchronisation, nothing
+ * read back: capturable.  ws may hold anything; box and count are fully written.  Before any launch: CWF_E_BADARG for a null pointer,
+ * B < 1, an extent < 1, bstride < 4 V; CWF_E_TOOLARGE for V > 2^31 - 1 or B > 65535; CWF_E_ALIGN for x or box off 4 bytes, count off
+ * 8, ws off 256. */
+int cwf_nonzero_box(const float* x, int64_t bstride, int B, int S0, int S1, int S2, int32_t* box, int64_t* count, void* ws,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K11 fused Adam (amsgrad, L2 weight decay in the gradient)  torch.optim.Adam as used at train_no_amp.py:136,239

@@ -120,6 +120,9 @@ SIGNATURES = {
     "cwf_focal_workspace": [I, L, I],
     "cwf_focal_loss": [P, P, P, I, P, P, P, P, I, L, I, P, P],
     "cwf_focal_loss_bwd": [P, P, P, I, P, P, P, P, I, L, I, P],
+    "cwf_lovasz_workspace": [I, L, I],
+    "cwf_lovasz": [P, P, P, I, I, P, P, P, P, I, L, P, P],
+    "cwf_lovasz_bwd": [P, P, I, P, P, P, I, L, P],
     "cwf_components_workspace": [I, I, I, I, I],
     "cwf_components": [P, I, I, I, I, I, I, P, P, P, P, P, L, P],
     "cwf_postprocess_labels": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
@@ -309,7 +312,7 @@ GRADNORM_WS_DOUBLES = 1024     # CWF_GRADNORM_WS_DOUBLES
 RULE_ADAMW, RULE_SGD = 1, 2    # CWF_RULE_ADAMW, CWF_RULE_SGD
 RESTYPE_INT64 = {"cwf_debug_wsd_launches", "cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
                  "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace",
-                 "cwf_topk_ce_workspace", "cwf_focal_workspace", "cwf_class_locations_workspace", "cwf_nonzero_box_workspace"}
+                 "cwf_topk_ce_workspace", "cwf_focal_workspace", "cwf_lovasz_workspace", "cwf_class_locations_workspace", "cwf_nonzero_box_workspace"}
 LOCATIONS_TILE = 16384     # CWF_LOCATIONS_TILE: the voxels of one workgroup of cwf_class_locations (a 16-byte aligned label starts tile 0)
 NONZERO_BOX_TILE = 4096    # CWF_NONZERO_BOX_TILE: the voxels of one workgroup of cwf_nonzero_box (a 16-byte aligned sample starts tile 0)
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import packing as pk
-from .kernels import REGION_MASKS, backend, check_focal_params, precision
+from .kernels import CLASS_MASKS, REGION_MASKS, backend, check_focal_params, check_lovasz_params, precision
 
 
 def active_sink():
@@ -1066,3 +1066,37 @@ def focal_loss(prob_ncdhw, label, posmasks=REGION_MASKS, fn=0.7, fp=0.3, exponen
     if label.dtype != torch.int64:
         label = label.long()
     return _FocalLossFn.apply(to_channels_last_view(prob_ncdhw), label, posmasks, params, wt)
+
+
+class _LovaszFn(torch.autograd.Function):
+    """weight x the mean over the counted regions of the Lovasz extension of the Jaccard loss, sorted over the whole batch
+    (csrc/lovasz.hip).  The forward leaves the signed per-voxel coefficients; the backward is one streaming launch over them."""
+
+    @staticmethod
+    def forward(ctx, prob_cl, label, posmasks, only_present, weight):
+        loss, coef, vcoef = backend().lovasz(prob_cl, label, posmasks, only_present, weight)
+        ctx.posmasks, ctx.shape = posmasks, tuple(prob_cl.shape)
+        ctx.save_for_backward(coef, vcoef)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        coef, vcoef = ctx.saved_tensors
+        gs = g.reshape(1).to(torch.float32).contiguous()
+        return backend().lovasz_bwd(vcoef, ctx.posmasks, coef, gs, ctx.shape), None, None, None, None
+
+
+def lovasz_softmax(prob_ncdhw, label, posmasks=CLASS_MASKS, only_present=True, weight=1.0):
+    """Lovasz-Softmax (Berman, Triggs, Blaschko 2018): weight x the mean over the counted regions of the Lovasz extension of the Jaccard
+    loss of the region's per-voxel errors, sorted over the whole batch (per_image=False).  posmasks: class bitmasks, default the four
+    classes (Lovasz-Softmax proper), REGION_MASKS for WT / TC / ET; only_present: count only the regions the label holds (Berman's
+    classes='present').  prob [N,4,D,H,W], label int64 [N,D,H,W] in 0..3; weight: float or one-element device tensor.  Voxels with equal
+    error share their group's Jaccard increment equally, so the gradient depends on neither voxel order nor launch geometry."""
+    posmasks, only_present = check_lovasz_params(posmasks, only_present)
+    if prob_ncdhw.dim() != 5 or int(prob_ncdhw.shape[1]) != 4:
+        raise ValueError("lovasz_softmax takes probabilities [N, 4, D, H, W], got %s" % (tuple(prob_ncdhw.shape),))
+    wt = loss_weight_tensor(weight, prob_ncdhw.device, "lovasz")
+    label = label.contiguous()
+    if label.dtype != torch.int64:
+        label = label.long()
+    return _LovaszFn.apply(to_channels_last_view(prob_ncdhw), label, posmasks, only_present, wt)

@@ -54,6 +54,26 @@ def check_focal_params(posmasks, fn=0.7, fp=0.3, exponent=0.75, smooth=1e-5, gam
     return dict(fn=fn, fp=fp, exponent=exponent, smooth=smooth, gamma=gamma, ce_ratio=ce_ratio, class_weight=kw)
 
 
+# the Lovasz-Softmax term's default regions: the four classes, one bitmask each (Lovasz-Softmax proper)
+CLASS_MASKS = (1, 2, 4, 8)
+
+
+def check_lovasz_params(posmasks, only_present=True):
+    """The accepted values of the Lovasz-Softmax term (the rules cwf_lovasz enforces, here as ValueError before anything is called):
+    1 to 8 regions, each a bitmask in 1..15 over classes 0..3; only_present a bool.  -> (the masks as a tuple of ints, only_present)"""
+    try:
+        masks = tuple(int(m) for m in posmasks)
+    except TypeError:
+        raise ValueError("lovasz: posmasks must be a sequence of class bitmasks, got %r" % (posmasks,))
+    if not 1 <= len(masks) <= 8:
+        raise ValueError("lovasz: 1 to 8 regions, got %d" % len(masks))
+    if any(m < 1 or m > 15 for m in masks) or any(float(m) != float(q) for m, q in zip(masks, posmasks)):
+        raise ValueError("lovasz: a region is a bitmask in 1..15 over classes 0..3, got %r" % (posmasks,))
+    if not isinstance(only_present, (bool, np.bool_)):
+        raise ValueError("lovasz: only_present must be True or False, got %r" % (only_present,))
+    return masks, bool(only_present)
+
+
 def cl(t: torch.Tensor):
     """(tensor, ldc) of a channels-last activation usable by the kernels; copies only if the strides are unusable."""
     assert t.dim() == 5 and t.dtype == _f32, (t.shape, t.dtype)
@@ -1287,6 +1307,55 @@ class HipBackend:
         dprob = torch.empty_like(prob)
         self._call("cwf_focal_loss_bwd", prob.data_ptr(), label.data_ptr(), ctypes.addressof(cm), len(masks), ctypes.addressof(cp), coef.data_ptr(),
                    gscale.data_ptr(), dprob.data_ptr(), n, v, 4, self._stream())
+        return dprob
+
+    # ------------------------------------------------------------------ L5 (Lovasz-Softmax)
+    def lovasz(self, prob, label, posmasks, only_present, weight):
+        """prob [N,D0,D1,D2,4] dense channels-last, label int64 [N,D0,D1,D2], posmasks 1..8 class bitmasks in 1..15, weight a one-float
+        device tensor -> (loss [1], coef [4], vcoef [R, N V]): weight x the mean over the counted regions of the Lovasz extension of the
+        Jaccard loss, by an exact sort of the errors of the whole batch on the device (cwf_lovasz).  No host synchronisation: the
+        workspace comes from torch's allocator."""
+        if prob.dim() != 5 or prob.dtype != _f32 or not prob.is_cuda or int(prob.shape[-1]) != 4:
+            raise ValueError("lovasz: prob must be a float32 [N, D0, D1, D2, 4] tensor on the GPU, got %s %s" % (tuple(prob.shape), prob.dtype))
+        if tuple(label.shape) != tuple(prob.shape[:4]) or label.dtype != torch.int64 or label.device != prob.device:
+            raise ValueError("lovasz: label must be int64 %s on the device of prob, got %s %s"
+                             % (tuple(prob.shape[:4]), tuple(label.shape), label.dtype))
+        masks, only_present = check_lovasz_params(posmasks, only_present)
+        if weight.numel() != 1 or weight.dtype != _f32 or weight.device != prob.device:
+            raise ValueError("lovasz: weight must be a one-element float32 tensor on the device of prob")
+        assert prob.is_contiguous() and label.is_contiguous()
+        n, v = int(prob.shape[0]), int(prob[0, ..., 0].numel())
+        if n * v > 0x7FFFFFFF:
+            raise ValueError("lovasz: at most 2^31 - 1 voxels in the batch, got %d" % (n * v))
+        cm = (ctypes.c_uint32 * len(masks))(*masks)
+        nbytes = self.lib.cwf_lovasz_workspace(n, v, len(masks))
+        if nbytes < 0:
+            raise _lib.CwfError("cwf_lovasz_workspace failed with status %d (N=%d V=%d R=%d)" % (nbytes, n, v, len(masks)))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=prob.device)
+        loss = torch.empty(1, dtype=_f32, device=prob.device)
+        coef = torch.empty(4, dtype=_f32, device=prob.device)
+        vcoef = torch.empty((len(masks), n * v), dtype=_f32, device=prob.device)
+        self._call("cwf_lovasz", prob.data_ptr(), label.data_ptr(), ctypes.addressof(cm), len(masks), int(only_present), weight.data_ptr(),
+                   loss.data_ptr(), coef.data_ptr(), vcoef.data_ptr(), n, v, ws.data_ptr(), self._stream())
+        return loss, coef, vcoef
+
+    def lovasz_bwd(self, vcoef, posmasks, coef, gscale, shape):
+        """-> dprob float32 `shape` = [N,D0,D1,D2,4]: (gscale x coef[0]) x vcoef[r] summed over the regions holding the class, ascending
+        r; every element written (cwf_lovasz_bwd)"""
+        masks, _ = check_lovasz_params(posmasks)
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 5 or shape[-1] != 4:
+            raise ValueError("lovasz_bwd: shape must be [N, D0, D1, D2, 4], got %r" % (shape,))
+        n, v = shape[0], shape[1] * shape[2] * shape[3]
+        if not vcoef.is_cuda or tuple(vcoef.shape) != (len(masks), n * v) or vcoef.dtype != _f32 or not vcoef.is_contiguous():
+            raise ValueError("lovasz_bwd: vcoef must be the float32 [R, N V] tensor lovasz returned")
+        if coef.numel() != 4 or coef.dtype != _f32 or coef.device != vcoef.device or gscale.numel() != 1 or gscale.dtype != _f32 \
+                or gscale.device != vcoef.device:
+            raise ValueError("lovasz_bwd: coef must be the float32 [4] tensor lovasz returned and gscale one float32, on the device of vcoef")
+        cm = (ctypes.c_uint32 * len(masks))(*masks)
+        dprob = torch.empty(shape, dtype=_f32, device=vcoef.device)
+        self._call("cwf_lovasz_bwd", vcoef.data_ptr(), ctypes.addressof(cm), len(masks), coef.data_ptr(), gscale.data_ptr(), dprob.data_ptr(),
+                   n, v, self._stream())
         return dprob
 
     def head_loss(self, logits, label, posmasks, scale):

@@ -45,6 +45,11 @@ Step controls (all off by default; then the step issues exactly the launches des
     + ce_ratio * focal cross-entropy) of the main output (tools.focal_loss; sums over the whole batch), in front of the same backward.
     w lives in a one-float device tensor (set_focal_weight() needs no recapture); the parameters (posmasks, fn, fp, exponent, smooth,
     gamma, ce_ratio, class_weight) are fixed at construction, being launch arguments.  None: no new call, total_loss called as before.
+  * lovasz_weight = w, lovasz_regions = "classes" | "regions" | a tuple of class bitmasks, lovasz_only_present: a further loss term after
+    the boundary, top-k and focal parts, w * Lovasz-Softmax of the main output (tools.lovasz_softmax: the errors of the whole batch
+    sorted exactly on the device; "classes" is the four classes, "regions" WT / TC / ET), in front of the same backward.  w lives in a
+    one-float device tensor (set_lovasz_weight() needs no recapture); the regions are fixed at construction, being launch arguments.
+    None: no new call, total_loss called as before.
   * optimizer = "adamw" | "sgd" (with betas / momentum, nesterov / no_decay): the update is one launch of the AdamW or SGD rule
     (cwf.optim.FusedAdamW / FusedSGD) in place of Adam's; sink, all-reduce, accumulation, clipping and EMA are the base class's and
     work as above.  schedule = "cosine" | "constant" and warmup_steps = W shape the learning rate of an update:
@@ -61,12 +66,13 @@ import torch.distributed as dist
 from .optim import FusedAdam, FusedAdamW, FusedSGD, SCHEDULES, poly_lr, schedule_lr, warmup_factor
 
 
-def total_loss(outputs, target, edge, boundary=None, topk=None, focal=None):
+def total_loss(outputs, target, edge, boundary=None, topk=None, focal=None, lovasz=None):
     """The reference's five terms; with `boundary` (the one-float device tensor holding the boundary weight) a sixth part,
     tools.boundary_loss(outputs[0], target) at that weight, is appended and added to the total; with `topk` = (the one-float device
     tensor holding the top-k weight, percent) the part tools.topk_ce(outputs[0], target) is appended after it; with `focal` = (the
     one-float device tensor holding the focal weight, the parameters as keyword arguments of tools.focal_loss) the part
-    tools.focal_loss(outputs[0], target) is appended last."""
+    tools.focal_loss(outputs[0], target) is appended after those; with `lovasz` = (the one-float device tensor holding the Lovasz weight,
+    the region masks, only_present) the part tools.lovasz_softmax(outputs[0], target) is appended last."""
     from models import criterions
     from utils import tools
     parts = [criterions.softmax_dice(outputs[0], target), tools.get_separate_loss(outputs[1], target),
@@ -81,6 +87,9 @@ def total_loss(outputs, target, edge, boundary=None, topk=None, focal=None):
         total = total + parts[-1]
     if focal is not None:
         parts.append(tools.focal_loss(outputs[0], target, weight=focal[0], **focal[1]))
+        total = total + parts[-1]
+    if lovasz is not None:
+        parts.append(tools.lovasz_softmax(outputs[0], target, posmasks=lovasz[1], only_present=lovasz[2], weight=lovasz[0]))
         total = total + parts[-1]
     return total, parts
 
@@ -127,6 +136,24 @@ def check_focal(weight, params):
     return weight, checked
 
 
+def check_lovasz(weight, regions="classes", only_present=True):
+    """(weight, regions, only_present): weight None (term off) or a finite float >= 0; regions "classes" (the four classes), "regions"
+    (WT / TC / ET) or 1 to 8 class bitmasks in 1..15, checked by cwf.kernels.check_lovasz_params with the term off too.
+    -> (weight, the masks as a tuple, only_present)"""
+    from .kernels import CLASS_MASKS, REGION_MASKS, check_lovasz_params
+    if isinstance(regions, str):
+        if regions not in ("classes", "regions"):
+            raise ValueError("lovasz_regions must be 'classes', 'regions' or a tuple of class bitmasks, got %r" % (regions,))
+        regions = CLASS_MASKS if regions == "classes" else REGION_MASKS
+    masks, only_present = check_lovasz_params(regions, only_present)
+    if weight is None:
+        return None, masks, only_present
+    weight = float(weight)
+    if not math.isfinite(weight) or weight < 0.0:
+        raise ValueError("lovasz_weight must be None or a finite number >= 0, got %r" % (weight,))
+    return weight, masks, only_present
+
+
 def boundary_schedule(weight, epoch, warmup):
     """--boundary_weight A / --boundary_warmup E: A * min(1, epoch / E), E = 0 meaning constant"""
     return float(weight) if warmup <= 0 else float(weight) * min(1.0, float(epoch) / float(warmup))
@@ -141,13 +168,16 @@ class Trainer:
     def __init__(self, model, lr=2e-4, weight_decay=1e-5, amsgrad=True, end_epoch=1000, use_graph=False,
                  graph_warmup=2, overlap_comm=True, wgrad_async=True, accum_steps=1, max_grad_norm=None, ema_decay=None,
                  boundary_weight=None, topk_weight=None, topk_percent=10.0, optimizer="adam", betas=(0.9, 0.999), momentum=0.0,
-                 nesterov=False, no_decay=None, schedule="poly", warmup_steps=0, focal_weight=None, focal_params=None):
+                 nesterov=False, no_decay=None, schedule="poly", warmup_steps=0, focal_weight=None, focal_params=None,
+                 lovasz_weight=None, lovasz_regions="classes", lovasz_only_present=True):
         self.boundary_weight = check_boundary_weight(boundary_weight)
         self._boundary = None                           # the weight as a one-float device tensor, made at the first step that needs it
         self.topk_weight, self.topk_percent = check_topk(topk_weight, topk_percent)
         self._topk = None                               # likewise
         self.focal_weight, self.focal_params = check_focal(focal_weight, focal_params)
         self._focal = None                              # likewise
+        self.lovasz_weight, self.lovasz_regions, self.lovasz_only_present = check_lovasz(lovasz_weight, lovasz_regions, lovasz_only_present)
+        self._lovasz = None                             # likewise
         self.model = model
         self.init_lr, self.end_epoch = lr, end_epoch
         if int(accum_steps) != accum_steps or accum_steps < 1:
@@ -268,6 +298,8 @@ class Trainer:
             extra["topk"] = (self._topk_tensor(x.device), self.topk_percent)
         if self.focal_weight is not None:
             extra["focal"] = (self._focal_tensor(x.device), self.focal_params)
+        if self.lovasz_weight is not None:
+            extra["lovasz"] = (self._lovasz_tensor(x.device), self.lovasz_regions, self.lovasz_only_present)
         loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device), **extra)
         self.opt.zero_grad(set_to_none=True)
         # graph modes: one reduce per phase, in warm-up too
@@ -349,6 +381,25 @@ class Trainer:
         if self._focal is not None:
             self._focal.fill_(w)
 
+    def _lovasz_tensor(self, device):
+        if self.lovasz_weight is None:
+            return None
+        if self._lovasz is None:
+            if _capturing():
+                raise RuntimeError("the Lovasz weight tensor must exist before the step is captured")
+            self._lovasz = torch.full((1,), self.lovasz_weight, dtype=torch.float32, device=device)
+        return self._lovasz
+
+    def set_lovasz_weight(self, w):
+        """New weight of the Lovasz-Softmax term from the next step on, in every step mode (no recapture: the kernels read it from
+        device memory).  Only for a Trainer built with a lovasz_weight; the regions stay as constructed."""
+        if w is None or self.lovasz_weight is None:
+            raise ValueError("the Lovasz term is switched on or off at construction (lovasz_weight=...), not between steps")
+        w, _, _ = check_lovasz(w, self.lovasz_regions, self.lovasz_only_present)
+        self.lovasz_weight = w
+        if self._lovasz is not None:
+            self._lovasz.fill_(w)
+
     def _finish_comm(self):
         if not self.comm:
             return
@@ -370,6 +421,7 @@ class Trainer:
         self._boundary_tensor(x.device)                 # (allocated and filled outside the capture)
         self._topk_tensor(x.device)
         self._focal_tensor(x.device)
+        self._lovasz_tensor(x.device)
         want_plan = self.graph_mode == "plan"
         g = torch.cuda.CUDAGraph(keep_graph=True) if want_plan else torch.cuda.CUDAGraph()
         # No cyclic garbage collection inside the capture.  A Trainer and its model form a cycle (model.phase_callback), so an earlier
@@ -442,7 +494,8 @@ class Trainer:
     def step(self, x, target, edge, epoch=0):
         """One optimisation step on a rank-local batch -- with accum_steps = N > 1 one MICRO-step: every N-th call updates the weights
         (learning rate of that call's epoch), the calls before it only accumulate.  Returns this batch's (loss, [five parts]) as
-        device tensors (no host sync); a boundary_weight, a topk_weight and a focal_weight each append a part, in that order."""
+        device tensors (no host sync); a boundary_weight, a topk_weight, a focal_weight and a lovasz_weight each append a part, in that
+        order."""
         self._last_micro = self._micro + 1 >= self.accum_steps
         if self._last_micro:
             self.opt.param_groups[0]["lr"] = self.learning_rate(epoch)    # plain float: checkpoints stay weights_only-loadable

@@ -48,6 +48,17 @@ def softmax_dice_focal(output, target):
     return softmax_dice(output, target) + tools.focal_loss(output, target)
 
 
+def lovasz_softmax(output, target, **kw):
+    """tools.lovasz_softmax: the Lovasz extension of the Jaccard loss, mean over the classes present, sorted over the whole batch."""
+    return tools.lovasz_softmax(output, target, **kw)
+
+
+def softmax_dice_lovasz(output, target):
+    """softmax_dice + lovasz_softmax at its defaults (the four classes, only those present, weight 1): selectable as
+    --criterion softmax_dice_lovasz."""
+    return softmax_dice(output, target) + tools.lovasz_softmax(output, target)
+
+
 def _not_built(name):
     def f(*a, **k):
         raise NotImplementedError("criterions.%s is an unused alternative in the reference and is not built; "

@@ -160,6 +160,12 @@ def build_parser():
     p.add_argument("--focal_gamma", default=2.0, type=float, help="(--focal_weight) (1 - p)^gamma of the focal cross-entropy: 0, or in [1, 5]")
     p.add_argument("--focal_ce_ratio", default=1.0, type=float,
                    help="(--focal_weight) weight of the focal cross-entropy beside the Tversky part, >= 0; 0: focal Tversky alone")
+    p.add_argument("--lovasz_weight", default=None, type=float,
+                   help="W >= 0: add W x the Lovasz-Softmax loss of the main output (Berman et al. 2018: the Jaccard loss's convex surrogate, "
+                        "the errors of the whole batch sorted exactly on the device) after the other terms; the log line gains lovasz_loss.  "
+                        "Default: off")
+    p.add_argument("--lovasz_regions", default="classes", choices=("classes", "regions"),
+                   help="(--lovasz_weight) classes: the four classes, those the batch holds counted (Lovasz-Softmax proper); regions: WT / TC / ET")
     p.add_argument("--optimizer", default="adam", choices=("adam", "adamw", "sgd"),
                    help="the update rule of the fused step: adam (the reference: L2 decay in the gradient, --amsgrad), adamw (decoupled "
                         "decay, --beta1 / --beta2 / --amsgrad) or sgd (--momentum, --nesterov); --lr and --weight_decay apply to all")
@@ -219,6 +225,17 @@ def check_focal(args):
         raise SystemExit("--focal_weight / --tversky_fn / --tversky_fp / --tversky_exponent / --focal_gamma / --focal_ce_ratio: %s" % e)
     if args.focal_weight is not None and args.no_cuda:
         raise SystemExit("--focal_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
+
+
+def check_lovasz(args):
+    """the values of --lovasz_weight / --lovasz_regions (SystemExit with the rule, like the other checks)"""
+    from cwf.trainer import check_lovasz as check
+    try:
+        check(args.lovasz_weight, args.lovasz_regions)
+    except ValueError as e:
+        raise SystemExit("--lovasz_weight / --lovasz_regions: %s" % e)
+    if args.lovasz_weight is not None and args.no_cuda:
+        raise SystemExit("--lovasz_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
 
 
 def boundary_weight_at(args, epoch):
@@ -353,6 +370,7 @@ def main(argv=None):
     check_boundary(args)
     check_topk(args)
     check_focal(args)
+    check_lovasz(args)
     check_optimizer(args)
     from cwf import kernels
     from cwf.parallel import shard_indices
@@ -400,9 +418,10 @@ def main(argv=None):
                       boundary_weight=boundary_weight_at(args, args.start_epoch), topk_weight=args.topk_weight,
                       topk_percent=args.topk_percent, optimizer=args.optimizer, betas=(args.beta1, args.beta2), momentum=args.momentum,
                       nesterov=args.nesterov, no_decay=args.no_decay, schedule=args.lr_schedule, warmup_steps=args.warmup_steps,
-                      focal_weight=args.focal_weight, focal_params=focal_params_of(args))
+                      focal_weight=args.focal_weight, focal_params=focal_params_of(args), lovasz_weight=args.lovasz_weight,
+                      lovasz_regions=args.lovasz_regions)
     clip, use_ema, use_boundary = args.clip_grad_norm is not None, args.ema_decay is not None, args.boundary_weight is not None
-    use_topk, use_focal = args.topk_weight is not None, args.focal_weight is not None
+    use_topk, use_focal, use_lovasz = args.topk_weight is not None, args.focal_weight is not None, args.lovasz_weight is not None
     if use_ema and os.path.isfile(args.resume) and args.load:
         ck = torch.load(args.resume, map_location="cpu", weights_only=True)
         if "ema_state_dict" in ck:
@@ -446,6 +465,7 @@ def main(argv=None):
                     v = host.tolist()
                     log.info("Epoch: %d_Iter:%d  loss: %.5f || end_loss: %.5f || s_loss:%.4f || edge_loss:%.4f || mid_s_loss:%.4f || mid_edge_loss:%.4f ||"
                              + (" boundary_loss: %.5f ||" if use_boundary else "") + (" topk_loss: %.5f ||" if use_topk else "") + (" focal_loss: %.5f ||" if use_focal else "")
+                             + (" lovasz_loss: %.5f ||" if use_lovasz else "")
                              + (" grad_norm: %.4f" if clip else ""), tag[0], tag[1], *v)
                 # (grad_norm: of the last update -- inside an accumulation window that is the previous window's)
                 snap = torch.stack([loss] + list(parts) + ([trainer.opt.grad_norm] if clip else [])).float()

@@ -57,6 +57,14 @@ def focal_ce(output, target, gamma=2.0, class_weight=None, weight=1.0):
     return CF.focal_loss(output, target, posmasks=(), gamma=gamma, ce_ratio=1.0, class_weight=class_weight, weight=weight)
 
 
+def lovasz_softmax(output, target, posmasks=CF.CLASS_MASKS, only_present=True, weight=1.0):
+    """Lovasz-Softmax (Berman et al. 2018) of the probabilities output [B,4,D,H,W] against the label map target [B,D,H,W]: weight * the
+    mean over the counted regions `posmasks` (class bitmasks; default the four classes, CF.REGION_MASKS for WT / TC / ET) of the Lovasz
+    extension of the Jaccard loss, the errors of the whole batch sorted exactly on the device; only_present counts only the regions the
+    target holds.  Not in the reference; off unless asked for."""
+    return CF.lovasz_softmax(output, target, posmasks=posmasks, only_present=only_present, weight=weight)
+
+
 def _separate(output, target, masks):
     maps = [output[r] for r in ("01", "02", "04")]
     if all(isinstance(m, CF.LazyProb) for m in maps) and len({(m.scale, tuple(m.logit.shape)) for m in maps}) == 1:

@@ -499,6 +499,36 @@ int cwf_focal_loss_bwd(const float* prob, const int64_t* label, const uint32_t* 
                        const float* coef, const float* gscale, float* dprob, int N, int64_t V, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * L5  Lovasz-Softmax on class-bitmask regions, by an exact device-wide sort (csrc/lovasz.hip; this project's statement)
+ *   prob float [N][V][4] channels-last; label int64 [N][V], class y = label & 3.  M = N V; the sort runs over the whole batch.
+ *   regions r < R (1 <= R <= 8): class bitmasks posmasks[r] in 1..15, in HOST memory.  Per region and voxel:
+ *   fg = (m_r >> y) & 1;  q = the p_c of the classes of m_r added in ascending class order (float32; one class: q = p_c);
+ *   qc = (q > 0) ? fminf(q, 1.0f) : 0.0f;  e = fg ? 1.0f - qc : qc;  sgn = (e > 0) ? (fg ? -1 : +1) : 0.
+ *   G = #{fg}.  Group j = the m_j voxels (f_j of them foreground) sharing the j-th largest distinct e; n_j, F_j the running sums.
+ *   J(n, F) = n ? 1.0 - (double)(G - F) / (double)(G + n - F) : 0.0;  dJ_j = J(n_j, F_j) - J(n_{j-1}, F_{j-1});  L_r = sum_j (double)e_j dJ_j.
+ *   A region is counted if G_r > 0, or always with only_present = 0; P = the number counted.
+ *   loss[0] = float32((double)w / max(P, 1) * sum_counted L_r), w = weight[0] in DEVICE memory (+0 for P = 0).
+ *   coef float [4]: [0] = float32((double)w / P) (+0 for P = 0), [1] = (float)P, [2] = [3] = +0.
+ *   vcoef float [R][M]: float32(dJ_j / (double)m_j) * (float)sgn -- ties share their group's increment equally, so neither voxel order
+ *   nor launch geometry enters; 0 in a region that is not counted.
+ *   No floating-point atomics, no workgroup waits on another; loss, coef and vcoef repeat bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of device workspace cwf_lovasz needs (two key arrays of 4 bytes per voxel and region, the per-tile digit counts, 73,728
+ * bytes of totals and partials, a search tree of about 4 / 15 bytes per voxel and region; 256-B aligned), or a negative CWF_E_*: CWF_E_BADARG for N <= 0, V <= 0 or R outside 1..8,
+ * CWF_E_TOOLARGE for more than 2^31 - 1 voxels (positions in the sorted arrays are 32-bit). */
+int64_t cwf_lovasz_workspace(int N, int64_t V, int R);
+/* Fifteen launches, no host synchronisation, no allocation, nothing read back: capturable.  ws may hold anything.  Before any
+ * launch: CWF_E_BADARG for a null pointer, N <= 0, V <= 0, R outside 1..8, a mask outside 1..15; CWF_E_TOOLARGE as above;
+ * CWF_E_ALIGN for ws off 256 bytes, prob off 16, label off 8. */
+int cwf_lovasz(const float* prob, const int64_t* label, const uint32_t* posmasks, int R, int only_present, const float* weight,
+               float* loss, float* coef, float* vcoef, int N, int64_t V, void* ws, void* stream);
+/* One streaming launch, one 16-byte store per voxel, dprob [N][V][4] fully written; float32, every operation rounded on its own:
+ * g0 = gscale[0] * coef[0];  dprob[v][c] = 0.0f + the (g0 * vcoef[r][v]) of the regions holding class c, ascending r.
+ * Errors as cwf_lovasz (dprob off 16 bytes: CWF_E_ALIGN). */
+int cwf_lovasz_bwd(const float* vcoef, const uint32_t* posmasks, int R, const float* coef, const float* gscale, float* dprob,
+                   int N, int64_t V, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N1  sliding-window inference glue   predict_overlap.py:31-58 (tailor_and_concat), :134-141 + utils/tools.py:44-47,64-109
  *     and utils/hausdorff.py (Hausdorff distance / HD95)
  * ---------------------------------------------------------------------------------------------- */

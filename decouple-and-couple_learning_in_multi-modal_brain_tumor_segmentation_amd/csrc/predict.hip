@@ -31,9 +31,11 @@ extern "C" int cwf_stitch_windows(const float* windows, float* y, int B, void* s
   return 0;
 }
 
-// seg[v] = argmax_c prob[b][c][v] (first maximum, as torch.argmax) ; counts[k][0..2] += (|o & t|, |o|, |t|) for the three BraTS regions
-// k = WT (label > 0), TC (label 1 or 3), ET (label 3) of tools.softmax_output_dice and, with NC = 18, for the three classes
-// k = 3 + (c - 1), c = 1, 2, 3 of tools.softmax_mIOU_score (|o | t| = |o| + |t| - |o & t|).  target may be NULL (no counts).
+// seg[v] = argmax_c prob[b][c][v] (first maximum, as torch.argmax: a NaN is the maximum and the first NaN wins, -0 == +0) ;
+// counts[k][0..2] += (|o & t|, |o|, |t|) for the three BraTS regions k = WT (label > 0), TC (label 1 or 3), ET (label 3) of
+// tools.softmax_output_dice and, with NC = 18, for the three classes k = 3 + (c - 1), c = 1, 2, 3 of tools.softmax_mIOU_score
+// (|o | t| = |o| + |t| - |o & t|), the rules applied to the whole int64 label as cwf_label_metrics applies them.  target may be NULL
+// (no counts).
 template <int NC>
 __global__ __launch_bounds__(256) void argmax_dice_kernel(const float* __restrict__ prob, int64_t sb, int64_t sc, int64_t sv, const int64_t* __restrict__ target,
                                                          int64_t* __restrict__ seg, unsigned long long* __restrict__ counts, int64_t V, int64_t total) {
@@ -47,10 +49,10 @@ __global__ __launch_bounds__(256) void argmax_dice_kernel(const float* __restric
     const float* p = prob + b * sb + v * sv;
     int best = 0; float bv = p[0];
 #pragma unroll
-    for (int c = 1; c < 4; ++c) { const float q = p[c * sc]; if (q > bv) { bv = q; best = c; } }
+    for (int c = 1; c < 4; ++c) { const float q = p[c * sc]; if (q > bv || (q != q && bv == bv)) { bv = q; best = c; } }
     seg[idx] = best;
     if (target) {
-      const int t = (int)target[idx];
+      const int64_t t = target[idx];                            // the full value: 2^32 + 3 is whole tumour, not ET
       const bool o[6] = {best > 0, best == 1 || best == 3, best == 3, best == 1, best == 2, best == 3};
       const bool g[6] = {t > 0, t == 1 || t == 3, t == 3, t == 1, t == 2, t == 3};
 #pragma unroll

@@ -1404,25 +1404,41 @@ class HipBackend:
     def stitch_windows(self, out8, nb):
         """out8: the model's output for the 8 windows stacked along the batch, logical [8*nb,4,128,128,128] over channels-last memory
         -> stitched [nb,4,240,240,155] (predict_overlap.py:49-58, incl. the depth-axis offset quirk)"""
+        if not (torch.is_tensor(out8) and out8.is_cuda and out8.dtype == _f32 and int(nb) >= 1
+                and tuple(out8.shape) == (8 * int(nb), 4, 128, 128, 128)):
+            raise ValueError("stitch_windows: out8 must be a CUDA float32 [8 * nb, 4, 128, 128, 128] tensor with nb >= 1, got %s %s and nb = %r"
+                             % (getattr(out8, "dtype", type(out8)), tuple(getattr(out8, "shape", ())), nb))
+        nb = int(nb)
         w = out8.permute(0, 2, 3, 4, 1)
         if not w.is_contiguous():
             w = w.contiguous()
-        assert tuple(w.shape) == (8 * nb, 128, 128, 128, 4)
         y = torch.empty((nb, 4, 240, 240, 155), dtype=_f32, device=out8.device)
         self._call("cwf_stitch_windows", w.data_ptr(), y.data_ptr(), nb, self._stream())
         return y
 
     def argmax_dice(self, prob, target=None, miou=False):
-        """prob [B,4,...] (any strides with one voxel stride) -> (seg int64 [B,...], [WT, TC, ET] Dice tensor or None); with miou=True
-        (target required) a third result: the [class 1, 2, 3] IoU tensor of tools.softmax_mIOU_score (utils/tools.py:50-61)"""
+        """prob: CUDA float32 [B,4,...] with at least one spatial axis, of any strides (contiguous and channels-last memory are read in
+        place, anything else is copied) -> (seg int64 [B,...], [WT, TC, ET] Dice tensor or None); target: None or an int64 tensor
+        [B,...] on prob's device; with miou=True (target required) a third result: the [class 1, 2, 3] IoU tensor of
+        tools.softmax_mIOU_score (utils/tools.py:50-61).  The argmax is torch.argmax's: the first maximum, a NaN being the maximum."""
+        if not (torch.is_tensor(prob) and prob.is_cuda and prob.dtype == _f32 and prob.dim() >= 3 and prob.shape[1] == 4 and prob.numel() > 0):
+            raise ValueError("argmax_dice: prob must be a non-empty CUDA float32 [B, 4, ...] tensor with at least one spatial axis, got %s %s"
+                             % (getattr(prob, "dtype", type(prob)), tuple(getattr(prob, "shape", ()))))
         b = prob.shape[0]
         sp = tuple(prob.shape[2:])
+        if target is not None and not (torch.is_tensor(target) and target.dtype == torch.int64 and target.device == prob.device
+                                       and tuple(target.shape) == (b,) + sp):
+            raise ValueError("argmax_dice: target must be an int64 %r tensor on the device of prob, got %s %s on %s"
+                             % ((b,) + sp, getattr(target, "dtype", type(target)), tuple(getattr(target, "shape", ())),
+                                getattr(target, "device", None)))
+        if miou and target is None:
+            raise ValueError("argmax_dice: miou=True needs a target")
         v = 1
         for d in sp:
             v *= d
         if prob.is_contiguous():
             sb, sc, sv = 4 * v, v, 1
-        elif prob.permute(0, 2, 3, 4, 1).is_contiguous():
+        elif prob.movedim(1, -1).is_contiguous():              # channels-last memory of any rank (5-D: permute(0, 2, 3, 4, 1))
             sb, sc, sv = 4 * v, 1, 4
         else:
             prob = prob.contiguous(); sb, sc, sv = 4 * v, v, 1
@@ -1430,10 +1446,8 @@ class HipBackend:
         counts = None
         if target is not None:
             target = target.contiguous()
-            assert target.dtype == torch.int64 and tuple(target.shape) == (b,) + sp
             counts = torch.zeros((6 if miou else 3, 3), dtype=torch.int64, device=prob.device)
         if miou:
-            assert target is not None, "mIoU needs a target"
             self._call("cwf_argmax_metrics", prob.data_ptr(), sb, sc, sv, target.data_ptr(), seg.data_ptr(), counts.data_ptr(), b, v, self._stream())
         else:
             self._call("cwf_argmax_dice", prob.data_ptr(), sb, sc, sv, _p(target), seg.data_ptr(), _p(counts), b, v, self._stream())
@@ -1448,8 +1462,10 @@ class HipBackend:
 
     def region_bits(self, labels):
         """int64 label map (any shape) -> uint8 region bits of tools.softmax_output_dice: bit 0 WT, bit 1 TC, bit 2 ET (cwf_region_bits)"""
+        if not (torch.is_tensor(labels) and labels.dtype == torch.int64 and labels.is_cuda):
+            raise ValueError("region_bits: labels must be a CUDA int64 tensor, got %s on %s"
+                             % (getattr(labels, "dtype", type(labels)), getattr(labels, "device", None)))
         labels = labels.contiguous()
-        assert labels.dtype == torch.int64 and labels.is_cuda
         bits = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
         if labels.numel():
             self._call("cwf_region_bits", labels.data_ptr(), bits.data_ptr(), labels.numel(), self._stream())
@@ -1608,8 +1624,14 @@ class HipBackend:
     def label_metrics(self, seg, target):
         """(dice [3], iou [3]) float64 device tensors of two int64 label maps of one shape: WT / TC / ET Dice of tools.softmax_output_dice
         and class 1 / 2 / 3 IoU of tools.softmax_mIOU_score, by the formulas of argmax_dice (cwf_label_metrics)."""
+        for name, t in (("seg", seg), ("target", target)):
+            if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.is_cuda):
+                raise ValueError("label_metrics: %s must be a CUDA int64 tensor, got %s on %s"
+                                 % (name, getattr(t, "dtype", type(t)), getattr(t, "device", None)))
+        if tuple(seg.shape) != tuple(target.shape) or seg.device != target.device or seg.numel() == 0:
+            raise ValueError("label_metrics: seg and target must have one non-empty shape and one device, got %r on %s and %r on %s"
+                             % (tuple(seg.shape), seg.device, tuple(target.shape), target.device))
         seg, target = seg.contiguous(), target.contiguous()
-        assert seg.dtype == torch.int64 and target.dtype == torch.int64 and seg.is_cuda and tuple(seg.shape) == tuple(target.shape)
         counts = torch.zeros((6, 3), dtype=torch.int64, device=seg.device)
         self._call("cwf_label_metrics", seg.data_ptr(), target.data_ptr(), counts.data_ptr(), seg.numel(), self._stream())
         c = counts.double()

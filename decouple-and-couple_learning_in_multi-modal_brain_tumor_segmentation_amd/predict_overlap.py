@@ -308,7 +308,7 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
 def _validate(prob, target, with_miou, cut=155):
     if prob.is_cuda and prob.dtype == torch.float32 and prob.dim() == 5 and prob.shape[1] == 4:
         from cwf.kernels import backend                     # argmax + WT/TC/ET counts in one launch (cwf_argmax_dice)
-        tgt = None if target is None else target[..., :cut].long()
+        tgt = None if target is None else target[..., :cut].long().to(prob.device)
         if with_miou and tgt is not None:
             seg, d, iou = backend().argmax_dice(prob, tgt, miou=True)          # argmax + Dice + IoU counts, still one launch
             return seg, prob, [d[0], d[1], d[2]], [iou[0], iou[1], iou[2]]

@@ -536,8 +536,11 @@ int cwf_lovasz_bwd(const float* vcoef, const uint32_t* posmasks, int R, const fl
  * own output memory), w in the reference's window order; hard overwrite by the later window incl. the reference's last-axis offset
  * quirk (voxels 123..149 of the second depth window land at 128..154).  Replaces x.clone() + eight slice assignments.              */
 int cwf_stitch_windows(const float* windows, float* y, int B, void* stream);
-/* seg[b][v] = argmax over the 4 classes of prob[b*sb + c*sc + v*sv] (first maximum); with a target (int64 labels 0..3) also the
- * counts[k][3] += (|o & t|, |o|, |t|) of tools.softmax_output_dice's three regions k = WT, TC, ET (uint64, zeroed by the caller)   */
+/* seg[b][v] = argmax over the 4 classes of prob[b*sb + c*sc + v*sv] (first maximum in torch.argmax's order: a NaN is the maximum
+ * and the first NaN wins, -0 == +0); with a target (int64 labels of any value, the rules applied to the whole 64 bits: WT is > 0, TC is
+ * == 1 or == 3, ET is == 3, so a label outside 0..3 is whole tumour if positive and nothing else) also the
+ * counts[k][3] += (|o & t|, |o|, |t|) of tools.softmax_output_dice's three regions k = WT, TC, ET (uint64, zeroed by the caller).
+ * target may be NULL, and counts with it.  CWF_E_BADARG before any launch: a null prob or seg, B <= 0, V <= 0, a target without counts. */
 int cwf_argmax_dice(const float* prob, int64_t sb, int64_t sc, int64_t sv, const int64_t* target, int64_t* seg, uint64_t* counts,
                     int B, int64_t V, void* stream);
 /* the same plus the per-class counts of tools.softmax_mIOU_score (utils/tools.py:50-61, reported by predict_simple.py): counts[6][3] =

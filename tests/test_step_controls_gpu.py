@@ -383,9 +383,12 @@ def test_trainer_clips_the_window_without_a_host_sync(hip):
 
 @pytest.mark.parametrize("use_graph", [False, "plan"])
 def test_trainer_window_under_communication_one_rank(hip, monkeypatch, use_graph):
-    """The same window in a one-rank RCCL group with CWF_FORCE_COMM=1: each phase slice is folded on the communication stream behind
-    its waits and before its all-reduce (eager: from the backward cut points; plan: at the three captured markers); micro-step 1
-    enqueues no collective.  Same gradient and weight bounds; no work object is left behind by any call."""
+    """The same window in a one-rank RCCL group with CWF_FORCE_COMM=1: the per-slice folds and the real RCCL all-reduces of the
+    communication path run (eager: from the backward cut points; plan: at the three captured markers) and leave the gradient and the
+    weights of the window without communication, within the same bounds; no work object is left behind by any call.  A one-rank
+    all-reduce is the identity, so this cannot tell a fold in front of its collective from one behind it, nor a slice reduced once
+    from one reduced twice or never: that order, the tiling and what each collective reads are checked at world size 2 with a
+    simulated peer in tests/test_two_rank_step_gpu.py."""
     import torch.distributed as dist
     from cwf import kernels
     R = _window_reference()                                            # (before the group exists: its Trainers are single-process)

@@ -1416,11 +1416,13 @@ class HipBackend:
         self._call("cwf_stitch_windows", w.data_ptr(), y.data_ptr(), nb, self._stream())
         return y
 
-    def argmax_dice(self, prob, target=None, miou=False):
+    def argmax_dice(self, prob, target=None, miou=False, counts=False):
         """prob: CUDA float32 [B,4,...] with at least one spatial axis, of any strides (contiguous and channels-last memory are read in
         place, anything else is copied) -> (seg int64 [B,...], [WT, TC, ET] Dice tensor or None); target: None or an int64 tensor
         [B,...] on prob's device; with miou=True (target required) a third result: the [class 1, 2, 3] IoU tensor of
-        tools.softmax_mIOU_score (utils/tools.py:50-61).  The argmax is torch.argmax's: the first maximum, a NaN being the maximum."""
+        tools.softmax_mIOU_score (utils/tools.py:50-61).  The argmax is torch.argmax's: the first maximum, a NaN being the maximum.
+        counts=True (target required) appends the int64 device tensor the ratios were formed from: rows of (|o & t|, |o|, |t|) for WT, TC,
+        ET and, with miou, class 1, 2, 3 -- [3, 3] or [6, 3]."""
         if not (torch.is_tensor(prob) and prob.is_cuda and prob.dtype == _f32 and prob.dim() >= 3 and prob.shape[1] == 4 and prob.numel() > 0):
             raise ValueError("argmax_dice: prob must be a non-empty CUDA float32 [B, 4, ...] tensor with at least one spatial axis, got %s %s"
                              % (getattr(prob, "dtype", type(prob)), tuple(getattr(prob, "shape", ()))))
@@ -1433,6 +1435,9 @@ class HipBackend:
                                 getattr(target, "device", None)))
         if miou and target is None:
             raise ValueError("argmax_dice: miou=True needs a target")
+        if counts and target is None:
+            raise ValueError("argmax_dice: counts=True needs a target")
+        want_counts = bool(counts)
         v = 1
         for d in sp:
             v *= d
@@ -1457,8 +1462,8 @@ class HipBackend:
             dice = (2 * c[:3, 0] + 1e-8) / (c[:3, 1] + c[:3, 2] + 1e-8)       # tools.dice_score (utils/tools.py:44-47)
             if miou:
                 iou = (c[3:, 0] + 1e-8) / (c[3:, 1] + c[3:, 2] - c[3:, 0] + 1e-8)   # tools.mIOU (utils/tools.py:50-53): |o & t| / |o | t|
-                return seg, dice, iou
-        return seg, dice
+                return (seg, dice, iou, counts) if want_counts else (seg, dice, iou)
+        return (seg, dice, counts) if want_counts else (seg, dice)
 
     def region_bits(self, labels):
         """int64 label map (any shape) -> uint8 region bits of tools.softmax_output_dice: bit 0 WT, bit 1 TC, bit 2 ET (cwf_region_bits)"""
@@ -1621,9 +1626,10 @@ class HipBackend:
                    int(et_min_voxels), int(et_replace), stats.data_ptr(), ws.data_ptr(), self._stream())
         return out, stats
 
-    def label_metrics(self, seg, target):
+    def label_metrics(self, seg, target, counts=False):
         """(dice [3], iou [3]) float64 device tensors of two int64 label maps of one shape: WT / TC / ET Dice of tools.softmax_output_dice
-        and class 1 / 2 / 3 IoU of tools.softmax_mIOU_score, by the formulas of argmax_dice (cwf_label_metrics)."""
+        and class 1 / 2 / 3 IoU of tools.softmax_mIOU_score, by the formulas of argmax_dice (cwf_label_metrics).  counts=True appends the
+        int64 [6, 3] device tensor they were formed from: (|o & t|, |o|, |t|) of WT, TC, ET, class 1, 2, 3."""
         for name, t in (("seg", seg), ("target", target)):
             if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.is_cuda):
                 raise ValueError("label_metrics: %s must be a CUDA int64 tensor, got %s on %s"
@@ -1632,10 +1638,11 @@ class HipBackend:
             raise ValueError("label_metrics: seg and target must have one non-empty shape and one device, got %r on %s and %r on %s"
                              % (tuple(seg.shape), seg.device, tuple(target.shape), target.device))
         seg, target = seg.contiguous(), target.contiguous()
-        counts = torch.zeros((6, 3), dtype=torch.int64, device=seg.device)
-        self._call("cwf_label_metrics", seg.data_ptr(), target.data_ptr(), counts.data_ptr(), seg.numel(), self._stream())
-        c = counts.double()
-        return (2 * c[:3, 0] + 1e-8) / (c[:3, 1] + c[:3, 2] + 1e-8), (c[3:, 0] + 1e-8) / (c[3:, 1] + c[3:, 2] - c[3:, 0] + 1e-8)
+        table = torch.zeros((6, 3), dtype=torch.int64, device=seg.device)
+        self._call("cwf_label_metrics", seg.data_ptr(), target.data_ptr(), table.data_ptr(), seg.numel(), self._stream())
+        c = table.double()
+        dice, iou = (2 * c[:3, 0] + 1e-8) / (c[:3, 1] + c[:3, 2] + 1e-8), (c[3:, 0] + 1e-8) / (c[3:, 1] + c[3:, 2] - c[3:, 0] + 1e-8)
+        return (dice, iou, table) if counts else (dice, iou)
 
     # ------------------------------------------------------------------ N7 lesion-wise Dice and HD95
     @staticmethod

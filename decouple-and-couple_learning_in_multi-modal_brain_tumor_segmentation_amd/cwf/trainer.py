@@ -578,6 +578,49 @@ class Trainer:
                         raise KeyError("EMA state lacks parameter %r" % name)
                     ema[id(p)].copy_(sd[name])
 
+    def validate(self, validator, use_ema=False):
+        """validator.run(self.model) (cwf.validation.Validator) between two steps, leaving the training run as it found it.  Every
+        model forward calls begin_step, which advances the device dropout counter, in eval mode too, and validate_softmax leaves the
+        model in eval mode; so saved before and put back after: `training` of every sub-module, the stem dropout value, and the two
+        int64 words of the device generator (device copies, no synchronisation) -- the dropout masks after a validation are those of
+        a run that never validated.  The captured step, its static inputs, the optimizer state and the flat gradient are not touched.
+        use_ema: the EMA lives in the optimizer and the captured step holds parameter pointers, so the raw parameters are copied
+        aside, the EMA is copied INTO the parameter storage (the forward repacks weights from it on every call) and the raw values are
+        copied back after the run: parameters and EMA are bit-equal to before.  With more than one rank every rank calls this; it ends
+        with the Validator's all_reduce.  Returns the ValidationResult."""
+        if self._micro != 0:
+            raise ValueError("validate() inside an accumulation window (%d of %d micro-steps done): the window's gradient sum would "
+                             "be left waiting; validate after the step that ends the window" % (self._micro, self.accum_steps))
+        if use_ema and self.opt.ema_decay is None:
+            raise RuntimeError("this Trainer keeps no EMA (ema_decay=None)")
+        model = self.model
+        modes = [(m, m.training) for m in model.modules()]
+        stem = model.Unet_list.InitConv if hasattr(model, "Unet_list") else None
+        dropout = None if stem is None else stem.dropout
+        rng = kernels_backend().rng(next(model.parameters()).device) if self.cuda else None
+        rng_saved = None if rng is None else rng.clone()
+        raw = None
+        if use_ema:
+            self.opt._ensure()
+            params = [p.data for p in self.opt._plist]
+            raw = [p.clone(memory_format=torch.preserve_format) for p in params]
+            torch._foreach_copy_(params, self.opt.ema)
+        try:
+            return validator.run(model)
+        finally:
+            if raw is not None:
+                torch._foreach_copy_(params, raw)
+            self._restore_rng(rng, rng_saved)
+            if stem is not None:
+                stem.dropout = dropout
+            for m, training in modes:
+                m.training = training
+
+    @staticmethod
+    def _restore_rng(rng, saved):
+        if rng is not None:
+            rng.copy_(saved)
+
 
 def _capturing():
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()

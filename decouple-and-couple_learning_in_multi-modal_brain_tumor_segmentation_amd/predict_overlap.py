@@ -259,7 +259,7 @@ def windows(starts):
 
 @torch.no_grad()
 def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_miou=False, with_hd95=False, window=None,
-                     postprocess=None, lesionwise=None, with_nsd=None):
+                     postprocess=None, lesionwise=None, with_nsd=None, with_counts=False, predict=None):
     """One subject: stitched probabilities -> label map (argmax; class 3 stands for BraTS label 4) -> [WT, TC, ET] Dice.
     ``deterministic`` zeroes the stem dropout that the reference leaves on in eval mode.  ``with_miou`` adds the per-class
     IoU list of tools.softmax_mIOU_score (what predict_simple.py reports next to Dice) as a fourth result.  ``with_hd95`` appends the
@@ -276,12 +276,22 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
     ``lesionwise``: None -- the result tuple is as above; True or a dict of `lesionwise_metrics` keyword arguments -- the dict that
     lesionwise_metrics(seg, target) returns for the final ``seg`` is appended as the last element (None without a target).
     ``with_nsd``: None -- nothing more; a tuple of tolerances -- the dict that surface_regions(seg, target, tolerances) returns for the
-    final ``seg`` (the post-processed map when ``postprocess`` is given) is appended after everything above (None without a target)."""
-    model.eval()
-    saved = model.Unet_list.InitConv.dropout
-    if deterministic:
-        model.Unet_list.InitConv.dropout = 0.0
-    if window is None:
+    final ``seg`` (the post-processed map when ``postprocess`` is given) is appended after everything above (None without a target).
+    ``with_counts``: True -- the int64 [6, 3] tensor of (|o & t|, |o|, |t|) for WT, TC, ET, class 1, 2, 3 of the final ``seg`` against the
+    target, the counts the Dice and IoU values are ratios of, is appended last of all (None without a target); on the device it is the
+    count tensor of the launch that produced them (argmax_dice / label_metrics counts=True), nothing is counted twice.
+    ``predict``: None -- the model predicts through the stitcher or the windows, as above; a callable x [B,4,...] -> probabilities
+    [B,4,...] of x's own extent -- it stands in for all of that (``model`` and ``window`` are not used and ``model`` may be None, the
+    target is compared at the volume's own shape), on CUDA or CPU tensors; everything after the probabilities is unchanged."""
+    given = predict
+    if given is None:
+        model.eval()
+        saved = model.Unet_list.InitConv.dropout
+        if deterministic:
+            model.Unet_list.InitConv.dropout = 0.0
+    if given is not None:
+        predict, cut = (lambda xb, mm: given(xb)), None
+    elif window is None:
         predict, cut = (lambda xb, mm: tailor_and_concat(xb, mm, model)), 155
     else:
         predict, cut = (lambda xb, mm: sliding_window_inference(xb, mm, model, **window)), None
@@ -291,10 +301,12 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
         else:
             prob = predict(x, None)
     finally:
-        model.Unet_list.InitConv.dropout = saved
-    res = _validate(prob, target, with_miou, cut)
+        if given is None:
+            model.Unet_list.InitConv.dropout = saved
+    counts = [] if with_counts and target is not None else None          # _validate / _revalidate append the tensor they counted
+    res = _validate(prob, target, with_miou, cut, counts)
     if postprocess is not None:
-        res = _revalidate(_apply_postprocess(res[0], postprocess), prob, target, with_miou, cut)
+        res = _revalidate(_apply_postprocess(res[0], postprocess), prob, target, with_miou, cut, counts)
     if with_hd95:
         res = res + ((None if target is None else hd95_regions(res[0], target[..., :cut].long())),)
     if lesionwise is not None and lesionwise is not False:
@@ -302,13 +314,30 @@ def validate_softmax(x, target, model, deterministic=True, use_TTA=False, with_m
         res = res + ((None if target is None else lesionwise_metrics(res[0], target[..., :cut].long().to(res[0].device), **kw)),)
     if with_nsd is not None:
         res = res + ((None if target is None else surface_regions(res[0], target[..., :cut].long().to(res[0].device), tuple(with_nsd))),)
+    if with_counts:
+        res = res + ((counts[-1] if counts else None),)
     return res
 
 
-def _validate(prob, target, with_miou, cut=155):
+def label_counts(seg, target):
+    """int64 [6, 3] tensor on seg's device of (|o & t|, |o|, |t|) for WT, TC, ET (the regions of tools.softmax_output_dice) and class 1, 2, 3
+    (tools.softmax_mIOU_score) of two integer label maps of one shape, by torch reductions: what cwf_argmax_metrics and
+    cwf_label_metrics count, for tensors that do not pass through them (CPU tensors)."""
+    pairs = [(seg > 0, target > 0), ((seg == 1) | (seg == 3), (target == 1) | (target == 3)), (seg == 3, target == 3)]
+    pairs += [(seg == c, target == c) for c in (1, 2, 3)]
+    return torch.stack([torch.stack([(o & t).sum(), o.sum(), t.sum()]) for o, t in pairs]).to(torch.int64)
+
+
+def _validate(prob, target, with_miou, cut=155, counts=None):
+    """counts: None, or a list that receives the int64 [6, 3] count tensor of the label map against the target"""
     if prob.is_cuda and prob.dtype == torch.float32 and prob.dim() == 5 and prob.shape[1] == 4:
         from cwf.kernels import backend                     # argmax + WT/TC/ET counts in one launch (cwf_argmax_dice)
         tgt = None if target is None else target[..., :cut].long().to(prob.device)
+        if counts is not None and tgt is not None:          # the launch of with_miou, its count tensor kept
+            seg, d, iou, table = backend().argmax_dice(prob, tgt, miou=True, counts=True)
+            counts.append(table)
+            res = (seg, prob, [d[0], d[1], d[2]])
+            return res + ([iou[0], iou[1], iou[2]],) if with_miou else res
         if with_miou and tgt is not None:
             seg, d, iou = backend().argmax_dice(prob, tgt, miou=True)          # argmax + Dice + IoU counts, still one launch
             return seg, prob, [d[0], d[1], d[2]], [iou[0], iou[1], iou[2]]
@@ -317,6 +346,8 @@ def _validate(prob, target, with_miou, cut=155):
         return res + (None,) if with_miou else res
     seg = prob.argmax(1)
     dice = tools.softmax_output_dice(seg, target[..., :cut]) if target is not None else None
+    if counts is not None and target is not None:
+        counts.append(label_counts(seg, target[..., :cut].to(seg.device)))
     if with_miou:
         return seg, prob, dice, (tools.softmax_mIOU_score(seg, target[..., :cut]) if target is not None else None)
     return seg, prob, dice
@@ -326,17 +357,23 @@ def _apply_postprocess(seg, policy):          # validate_softmax's keyword hides
     return postprocess(seg, **policy)
 
 
-def _revalidate(seg, prob, target, with_miou, cut):
-    """The result tuple of _validate for a label map that is already there (the post-processed one)."""
+def _revalidate(seg, prob, target, with_miou, cut, counts=None):
+    """The result tuple of _validate for a label map that is already there (the post-processed one); counts as there."""
     dice = miou = None
     if target is not None:
         tgt = target[..., :cut].long()
         if seg.is_cuda:
             from cwf.kernels import backend
-            d, iou = backend().label_metrics(seg, tgt.to(seg.device))
+            if counts is not None:
+                d, iou, table = backend().label_metrics(seg, tgt.to(seg.device), counts=True)
+                counts.append(table)
+            else:
+                d, iou = backend().label_metrics(seg, tgt.to(seg.device))
             dice, miou = [d[0], d[1], d[2]], [iou[0], iou[1], iou[2]]
         else:
             dice, miou = tools.softmax_output_dice(seg, tgt), tools.softmax_mIOU_score(seg, tgt)
+            if counts is not None:
+                counts.append(label_counts(seg, tgt))
     return (seg, prob, dice, miou) if with_miou else (seg, prob, dice)
 
 

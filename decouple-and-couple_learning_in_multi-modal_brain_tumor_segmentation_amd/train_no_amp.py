@@ -182,7 +182,92 @@ def build_parser():
     p.add_argument("--warmup_steps", default=0, type=int,
                    help="W >= 0: multiply the scheduled rate by min(1, n / W) at the n-th weight update (with --accum_steps N once per "
                         "window).  Default: 0, no warm-up")
+    # validation during training (cwf.validation): everything below is off while --valid_freq is 0, and may only be given with it on
+    p.add_argument("--valid_freq", default=0, type=int,
+                   help="N > 0: validate whole subjects by sliding windows of the training crop after every N-th epoch and after the "
+                        "last, log the mean and global Dice, append a record to log/<experiment><date>_valid.json and keep the best "
+                        "checkpoint as model_best.pth; the subjects are --root/--valid_dir listed by --valid_file, or --valid_synthetic.  "
+                        "Default: 0, off")
+    p.add_argument("--valid_synthetic", default=None, type=int,
+                   help="(--valid_freq) validate on M generated whole subjects of (input_H, input_W, output_D) voxels, with the indices "
+                        "after the --synthetic training subjects'")
+    p.add_argument("--valid_overlap", default=None, type=float, help="(--valid_freq) overlap of the windows, in [0, 1).  Default: 0.5")
+    p.add_argument("--valid_crop_nonzero", default=None, type=_bool,
+                   help="(--valid_freq) lay the windows over each subject's nonzero box only (0.435x the time on a BraTS case)")
+    p.add_argument("--valid_tta", default=None, type=_bool, help="(--valid_freq) 8-flip test-time augmentation (8x the time)")
+    p.add_argument("--valid_ema", default=None, type=_bool, help="(--valid_freq) validate the EMA weights; needs --ema_decay")
+    p.add_argument("--valid_postprocess", default=None, choices=("none", "reference"),
+                   help="(--valid_freq) reference: the 500-voxel enhancing-tumour rule before the counts are taken.  Default: none")
+    p.add_argument("--valid_hd95", default=None, type=_bool, help="(--valid_freq) also the WT / TC / ET HD95 of every case")
+    p.add_argument("--valid_cache", default=None, type=_bool,
+                   help="(--valid_freq) hold the validation subjects in device memory (default: true); false: load each when its turn comes")
     return p
+
+
+VALID_FLAGS = ("valid_synthetic", "valid_overlap", "valid_crop_nonzero", "valid_tta", "valid_ema", "valid_postprocess", "valid_hd95",
+               "valid_cache")
+
+
+def validation_subjects(args):
+    """the subjects --valid_freq validates: generated ones, or the .npz paths under --root/--valid_dir listed by --valid_file"""
+    if args.valid_synthetic:
+        from utils import synthetic as syn
+        full = (args.input_H, args.input_W, args.output_D)
+        vols = [syn.synthetic_volume(args.synthetic + j, full, args.seed) for j in range(args.valid_synthetic)]
+        return [(x, t.to(torch.uint8)) for x, t in vols]
+    from utils.data import _npz_paths
+    root = os.path.join(args.root, args.valid_dir)
+    lst = os.path.join(root, args.valid_file)
+    return _npz_paths(root, lst if os.path.isfile(lst) else None)
+
+
+def check_validation(args):
+    """the values of --valid_freq and the --valid_* flags (SystemExit with the rule, like the other checks); returns the subjects, or
+    None with validation off"""
+    if args.valid_freq < 0:
+        raise SystemExit("--valid_freq takes a number of epochs >= 0 (0: no validation)")
+    if args.valid_freq == 0:
+        given = ["--" + f for f in VALID_FLAGS if getattr(args, f) is not None]
+        if given:
+            raise SystemExit("%s belong%s to --valid_freq: give that too" % (" / ".join(given), "s" if len(given) == 1 else ""))
+        return None
+    if args.valid_ema and args.ema_decay is None:
+        raise SystemExit("--valid_ema validates the EMA weights: it needs --ema_decay")
+    if args.valid_synthetic is not None and args.valid_synthetic < 0:
+        raise SystemExit("--valid_synthetic takes a number of subjects >= 0")
+    if args.valid_overlap is not None and not 0.0 <= args.valid_overlap < 1.0:
+        raise SystemExit("--valid_overlap takes an overlap in [0, 1)")
+    try:
+        subjects = validation_subjects(args)
+    except FileNotFoundError as e:
+        raise SystemExit("--valid_freq found no validation subjects (%s): give --root / --valid_dir / --valid_file, or --valid_synthetic M" % e)
+    if not subjects:
+        raise SystemExit("--valid_freq found no validation subjects: --valid_synthetic takes M > 0")
+    from predict_overlap import check_roi
+    try:
+        check_roi((args.crop_H, args.crop_W, args.crop_D))
+    except ValueError as e:
+        raise SystemExit("--valid_freq validates by windows of the training crop: %s" % e)
+    if args.no_cuda or not torch.cuda.is_available():
+        raise SystemExit("--valid_freq runs on the device kernels only: it needs a GPU and cannot be combined with --no_cuda true")
+    return subjects
+
+
+def make_validator(args, subjects, device, rank, world):
+    """cwf.validation.Validator from the --valid_* flags: windows of the training crop, --normalize as in training"""
+    from cwf.validation import Validator
+    from predict_overlap import REFERENCE_POSTPROCESS
+    window = {"roi_size": (args.crop_H, args.crop_W, args.crop_D), "overlap": 0.5 if args.valid_overlap is None else args.valid_overlap}
+    if args.valid_crop_nonzero:
+        window["crop_nonzero"] = True
+    return Validator(subjects, device, window=window, use_tta=bool(args.valid_tta),
+                     postprocess=REFERENCE_POSTPROCESS if args.valid_postprocess == "reference" else None, normalize=args.normalize,
+                     cache=True if args.valid_cache is None else args.valid_cache, with_hd95=bool(args.valid_hd95), rank=rank, world=world)
+
+
+def should_validate(epoch, end_epoch, valid_freq, last=False):
+    """after every valid_freq-th epoch (epochs are 0-based in the loop) and after the last one of the run"""
+    return valid_freq > 0 and ((epoch + 1) % valid_freq == 0 or epoch + 1 >= end_epoch or last)
 
 
 def check_optimizer(args):
@@ -308,6 +393,28 @@ def check_foreground(args):
         raise SystemExit("--crop_nonzero draws from the subjects' nonzero boxes, which DeviceBraTS takes: it needs --device_data cache or staged")
 
 
+def report_validation(args, log, result, epoch, records, best, save, ckpt_dir):
+    """The printing rank's part after a validation: the log line, the record appended to log/<experiment><date>_valid.json (a list,
+    rewritten whole), and model_best.pth when the score is strictly better than every earlier one (cwf.validation.better_score).
+    Returns the new (best score, its epoch)."""
+    from cwf.validation import better_score, write_json
+    mean, glob = result.dice_stats["mean"], result.global_dice
+    line = "Validation: epoch %d  cases %d || dice WT %.5f TC %.5f ET %.5f || global WT %.5f TC %.5f ET %.5f || score %.5f" % (
+        epoch, len(result), mean[0], mean[1], mean[2], glob[0], glob[1], glob[2], result.score)
+    if result.mean_hd95 is not None:
+        line += " || hd95 WT %.3f TC %.3f ET %.3f" % tuple(result.mean_hd95)
+    is_best = better_score(result.score, best[0])
+    if is_best:
+        best = (result.score, epoch)
+        save(os.path.join(ckpt_dir, "model_best.pth"))
+    log.info(line + (" || best" if is_best else ""))
+    records.append(dict(result.to_json(), epoch=epoch, is_best=is_best, best_epoch=best[1], best_score=best[0]))
+    log_dir = os.path.join(args.project_root, "log")
+    os.makedirs(log_dir, exist_ok=True)
+    write_json(os.path.join(log_dir, args.experiment + args.date + "_valid.json"), records)
+    return best
+
+
 def should_save(epoch, end_epoch, save_freq):
     """train_no_amp.py:243-246 (epochs are 0-based in the loop, 1-based in the test)."""
     e = epoch + 1
@@ -372,6 +479,7 @@ def main(argv=None):
     check_focal(args)
     check_lovasz(args)
     check_optimizer(args)
+    valid_subjects = check_validation(args)
     from cwf import kernels
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint
@@ -436,6 +544,9 @@ def main(argv=None):
         os.makedirs(ckpt_dir, exist_ok=True)
     device_data = args.device_data != "off"
     ds = make_device_dataset(args, device) if device_data else make_dataset(args)
+    validator, valid_records, best = None, [], (None, None)          # best = (score, epoch)
+    if valid_subjects is not None:
+        validator = make_validator(args, valid_subjects, device, rank, world)
     t_start, iters, pending = time.time(), 0, None
     done = False
     for epoch in range(args.start_epoch, args.end_epoch):
@@ -481,6 +592,15 @@ def main(argv=None):
                 break
         if is_printer and should_save(epoch, args.end_epoch, args.save_freq):
             save_checkpoint(os.path.join(ckpt_dir, "model_epoch_%d.pth" % epoch), model, trainer.opt, epoch, ema=ema_sd())
+        if validator is not None and should_validate(epoch, args.end_epoch, args.valid_freq, last=done):
+            if trainer._micro != 0:             # (every rank is at the same micro-step)
+                if is_printer:
+                    log.info("Validation: epoch %d ends inside an accumulation window, skipped", epoch)
+            else:
+                result = trainer.validate(validator, use_ema=bool(args.valid_ema))
+                if is_printer:
+                    best = report_validation(args, log, result, epoch, valid_records, best,
+                                             lambda path: save_checkpoint(path, model, trainer.opt, epoch, ema=ema_sd()), ckpt_dir)
         if done:
             break
     if is_printer:

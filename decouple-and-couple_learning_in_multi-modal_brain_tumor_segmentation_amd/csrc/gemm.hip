@@ -1,12 +1,61 @@
 // K6/K7 -- token-path math: strided batched GEMM on v_mfma_f32_16x16x4_f32 (all Linear layers, QK^T, attn.V
 // and their gradients), LayerNorm fwd/bwd, row softmax fwd/bwd, GELU backward, column sums.
 // Reference: SelfAttention.py:74-102 (DualSelfAttention), ResidualNorm.py:4-47, ClsWiseTransformer.py:41-55,
-// FusionClsWiseTransformer.py:43-54.  Sequence length is 129 / 258 tokens x 512: launch-latency bound, so the
-// kernels are kept simple (64x64 or 32x32 workgroup tiles, K steps of 32, one pass).
+// FusionClsWiseTransformer.py:43-54.  Sequence length is 129 / 258 tokens x 512: 0.8-2.4 GFLOP per GEMM, 64x64 or 32x32 workgroup
+// tiles, one pass.  What bounds them is the latency of their operand loads, not launches: the looped kernels (gemm_mfma_kernel,
+// gemm_mfma_v_kernel) pay one exposed memory round trip per K step; the production contraction lengths run on gemm_mfma_p_kernel,
+// whose whole K walk is straight-line code with several panels of loads in flight (1.1-1.9x faster alone, same bits).
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 
 typedef struct cwf_gemm_args GemmArgs;
+
+// The epilogue and the rowsum tail of every GEMM kernel below (scalar, 16-byte-load, K-panel): each wave writes its TM/32 x TN/32
+// MFMA tiles in the order alpha*AB + bias -> C2 -> act -> dropout -> + residual -> (accumulate) -> C; the waves of the first
+// column tile write the row sums (every column of accr holds the row sum; column 0 writes it).
+template <int TM, int TN>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, const f32x4 (&acc)[TM / 32][TN / 32], const f32x4 (&accr)[TM / 32], int zb, int zh,
+                                              int m0, int n0, int wr, int wc, int r, int kq, bool do_rs, float* rowsum) {
+  constexpr int IM = TM / 32, JN = TN / 32;
+  const int64_t c_zoff = zb * a.sc_zb + zh * a.sc_zh;
+  float* C = a.C_tab[0] ? a.C_tab[blockIdx.z] : a.C + c_zoff;
+  float* C2 = a.C2 ? a.C2 + c_zoff : nullptr;
+  const float* bias = a.bias_tab[0] ? a.bias_tab[blockIdx.z] : a.bias;
+  const float* R = a.residual ? a.residual + zb * a.sr_zb + zh * a.sr_zh : nullptr;
+  const bool c_drop = a.c_drop_p > 0.f;
+#pragma unroll
+  for (int i = 0; i < IM; ++i)
+#pragma unroll
+    for (int j = 0; j < JN; ++j) {
+      const int gn = n0 + wc * (TN / 2) + j * 16 + r;
+      if (gn >= a.N) continue;
+      const float bv = bias ? bias[gn] : 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int gm = m0 + wr * (TM / 2) + i * 16 + kq * 4 + e;
+        if (gm >= a.M) continue;
+        const int64_t off = gm * a.sc_m + gn;
+        float v = acc[i][j][e] * a.alpha + bv;
+        if (C2) C2[off] = v;
+        if (a.act == 1) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+        if (c_drop) v *= cwf_keep(a.rng, a.c_drop_off, (uint64_t)(c_zoff + off), a.c_drop_n, a.c_drop_p, a.c_drop_p2);
+        if (R) v += R[gm * a.sr_m + gn];
+        float* p = C + off;
+        if (a.accumulate) v += *p;
+        *p = v;
+      }
+    }
+  if (do_rs && r == 0) {
+#pragma unroll
+    for (int i = 0; i < IM; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int gm = m0 + wr * (TM / 2) + i * 16 + kq * 4 + e;
+        if (gm < a.M) rowsum[gm] = (a.rowsum_acc ? rowsum[gm] : 0.f) + accr[i][e];
+      }
+  }
+}
 
 
 // TM x TN output tile per workgroup (64 x 64: each of the 4 waves owns 2 x 2 MFMA tiles; 32 x 32: one tile per wave), K in
@@ -110,43 +159,7 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(const GemmArgs a) {
       }
     }
   }
-  const int64_t c_zoff = zb * a.sc_zb + zh * a.sc_zh;
-  float* C = a.C_tab[0] ? a.C_tab[blockIdx.z] : a.C + c_zoff;
-  float* C2 = a.C2 ? a.C2 + c_zoff : nullptr;
-  const float* bias = a.bias_tab[0] ? a.bias_tab[blockIdx.z] : a.bias;
-  const float* R = a.residual ? a.residual + zb * a.sr_zb + zh * a.sr_zh : nullptr;
-  const bool c_drop = a.c_drop_p > 0.f;
-#pragma unroll
-  for (int i = 0; i < IM; ++i)
-#pragma unroll
-    for (int j = 0; j < JN; ++j) {
-      const int gn = n0 + wc * (TN / 2) + j * 16 + r;
-      if (gn >= a.N) continue;
-      const float bv = bias ? bias[gn] : 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int gm = m0 + wr * (TM / 2) + i * 16 + kq * 4 + e;
-        if (gm >= a.M) continue;
-        const int64_t off = gm * a.sc_m + gn;
-        float v = acc[i][j][e] * a.alpha + bv;
-        if (C2) C2[off] = v;
-        if (a.act == 1) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-        if (c_drop) v *= cwf_keep(a.rng, a.c_drop_off, (uint64_t)(c_zoff + off), a.c_drop_n, a.c_drop_p, a.c_drop_p2);
-        if (R) v += R[gm * a.sr_m + gn];
-        float* p = C + off;
-        if (a.accumulate) v += *p;
-        *p = v;
-      }
-    }
-  if (do_rs && r == 0) {                        // every column of accr holds the row sum; column 0 writes it
-#pragma unroll
-    for (int i = 0; i < IM; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int gm = m0 + wr * (TM / 2) + i * 16 + kq * 4 + e;
-        if (gm < a.M) rowsum[gm] = (a.rowsum_acc ? rowsum[gm] : 0.f) + accr[i][e];
-      }
-  }
+  gemm_epilogue<TM, TN>(a, acc, accr, zb, zh, m0, n0, wr, wc, r, kq, do_rs, rowsum);
 }
 
 // The same kernel with 16-byte global loads and K steps of 64.  The scalar form above fetches ONE float per lane and load
@@ -255,44 +268,170 @@ __global__ __launch_bounds__(256) void gemm_mfma_v_kernel(const GemmArgs a) {
       }
     }
   }
-  // ---- epilogue: identical to the scalar kernel
-  const int64_t c_zoff = zb * a.sc_zb + zh * a.sc_zh;
-  float* C = a.C_tab[0] ? a.C_tab[blockIdx.z] : a.C + c_zoff;
-  float* C2 = a.C2 ? a.C2 + c_zoff : nullptr;
-  const float* bias = a.bias_tab[0] ? a.bias_tab[blockIdx.z] : a.bias;
-  const float* R = a.residual ? a.residual + zb * a.sr_zb + zh * a.sr_zh : nullptr;
-  const bool c_drop = a.c_drop_p > 0.f;
+  gemm_epilogue<TM, TN>(a, acc, accr, zb, zh, m0, n0, wr, wc, r, kq, do_rs, rowsum);
+}
+
+// The K-panel form of the 16-byte-load kernel.  The loop above holds ONE K step of global loads in flight: every step waits for
+// loads issued one short MFMA phase earlier, so a 512-deep contraction pays 8 (16 at 64 x 64) exposed memory round trips, and a
+// second register set in the loop buys nothing (across the back-edge the compiler's s_waitcnt vmcnt waits for the younger set
+// too).  Here the contraction length KC is a template parameter: K is covered by NP = ceil(KC / PK) panels as straight-line code
+// (no back-edge, so every wait is counted exactly), D panels of loads are in flight, and the loads of panel p + D are issued
+// right after the barrier that publishes panel p.
+// Requests never wait on arithmetic: a load's address is clamped into its operand (row min(gm, M - 1), a k inside the last full
+// vector) and never conditional; the A-operand dropout and the zeroing of rows / columns / k outside M, N, K happen when the panel
+// is stored into LDS, by select (a NaN next to the operand must not reach the result).  (The A2 / B2 switch is uniform per
+// workgroup: it picks the base pointer before the first request.)
+// A k-fast B operand (!BN) is transposed on its way into LDS: a lane's four dword stores go to four k rows, and with rows of TN + 16
+// words the 16 lanes of one n hit ONE bank of ds_write_b32's 32 (16-way conflict, 8 such stores per thread and panel: more LDS
+// cycles than the panel's MFMAs).  Row k therefore holds column n at n ^ ((k >> 2) & 15): the 16 lanes spread over 16 banks, and
+// the MFMA phase's read of row kk * 4 + kq XORs its 16 columns with the same wave-uniform kk -- a permutation inside the 16-column
+// block, still conflict-free.
+// Same work split, LDS tile shapes (PK for GK) and MFMA sequence per accumulator as gemm_mfma_v_kernel -- k ascending, four at a
+// time, from zero; k beyond K adds exact zeros, and the MFMAs of a tail panel that would only add zeros are not issued -- so every
+// result is bit-identical to that kernel's.
+template <int TM, int TN, int PK, int KC, int D, bool AK, bool BN>
+__global__ __launch_bounds__(256) void gemm_mfma_p_kernel(const GemmArgs a) {
+  constexpr int NP = (KC + PK - 1) / PK;
+  constexpr int K4 = (KC + 3) / 4 * 4;                         // the MFMAs' k extent
+  constexpr int LDA_S = PK + 1, LDB_S = TN + 16;
+  constexpr int IM = TM / 32, JN = TN / 32;
+  constexpr int SA = TM * PK / 1024, SB = TN * PK / 1024;      // float4 slots per thread and panel
+  static_assert(D >= 2 && PK % 4 == 0 && SA >= 1 && SB >= 1, "panel geometry");
+  static_assert(KC % 4 == 0 || (!AK && BN), "an operand with 16-byte loads along k needs K % 4 == 0");
+  __shared__ float As[TM * LDA_S];
+  __shared__ __attribute__((aligned(16))) float Bs[PK * LDB_S];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int r = lane & 15, kq = lane >> 4;
+  const int zb = blockIdx.z / a.ZH, zh = blockIdx.z % a.ZH;
+  const int m0 = blockIdx.y * TM, n0 = blockIdx.x * TN;
+  const int64_t a_zoff = zb * a.sa_zb + zh * a.sa_zh;
+  const float* A = ((a.A2 && n0 >= a.split_n) ? a.A2 : a.A) + a_zoff;
+  const bool tabB = a.B_tab[0] != nullptr;
+  const float* B = tabB ? a.B_tab[blockIdx.z] : a.B + zb * a.sb_zb + zh * a.sb_zh;
+  if (a.B2 && m0 >= a.split_m) B = a.B2 + zb * a.sb_zb + zh * a.sb_zh;
+  const bool a_drop = a.a_drop_p > 0.f;
+  float* rowsum = a.rowsum_tab[0] ? a.rowsum_tab[blockIdx.z] : a.rowsum;
+  const bool do_rs = rowsum != nullptr && blockIdx.x == 0 && wc == 0;
+
+  f32x4 acc[IM][JN], accr[IM];
 #pragma unroll
-  for (int i = 0; i < IM; ++i)
+  for (int i = 0; i < IM; ++i) {
+    accr[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int j = 0; j < JN; ++j) {
-      const int gn = n0 + wc * (TN / 2) + j * 16 + r;
-      if (gn >= a.N) continue;
-      const float bv = bias ? bias[gn] : 0.f;
+    for (int j = 0; j < JN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  // slot i of this thread, as in gemm_mfma_v_kernel; aoff / boff: the slot's element offset in panel 0 with its row (A) / column (B)
+  // clamped into the operand, a_ok / b_ok: that row / column exists
+  int am[SA], ak[SA], bk[SB], bn[SB];
+  int64_t aoff[SA], boff[SB];
+  bool a_ok[SA], b_ok[SB];
+  const int64_t a_sk = AK ? 1 : a.sa_k, a_sm = AK ? a.sa_m : 1, b_sn = BN ? 1 : a.sb_n, b_sk = BN ? a.sb_k : 1;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int gm = m0 + wr * (TM / 2) + i * 16 + kq * 4 + e;
-        if (gm >= a.M) continue;
-        const int64_t off = gm * a.sc_m + gn;
-        float v = acc[i][j][e] * a.alpha + bv;
-        if (C2) C2[off] = v;
-        if (a.act == 1) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-        if (c_drop) v *= cwf_keep(a.rng, a.c_drop_off, (uint64_t)(c_zoff + off), a.c_drop_n, a.c_drop_p, a.c_drop_p2);
-        if (R) v += R[gm * a.sr_m + gn];
-        float* p = C + off;
-        if (a.accumulate) v += *p;
-        *p = v;
+  for (int i = 0; i < SA; ++i) {
+    if (AK) { ak[i] = (tid % (PK / 4)) * 4; am[i] = tid / (PK / 4) + (1024 / PK) * i; }
+    else { am[i] = (tid % (TM / 4)) * 4; ak[i] = tid / (TM / 4) + (1024 / TM) * i; }
+    const int gm = m0 + am[i];
+    a_ok[i] = gm < a.M;
+    aoff[i] = min(gm, a.M - (AK ? 1 : 4)) * a_sm;
+  }
+#pragma unroll
+  for (int i = 0; i < SB; ++i) {
+    if (BN) { bn[i] = (tid % (TN / 4)) * 4; bk[i] = tid / (TN / 4) + (1024 / TN) * i; }
+    else { bk[i] = (tid % (PK / 4)) * 4; bn[i] = tid / (PK / 4) + (1024 / PK) * i; }
+    const int gn = n0 + bn[i];
+    b_ok[i] = gn < a.N;
+    boff[i] = min(gn, a.N - (BN ? 4 : 1)) * b_sn;
+  }
+  // the smallest k of slot i inside its panel: a slot wholly at or beyond the MFMAs' k extent is neither loaded nor stored
+  auto a_kmin = [](int i) { return AK ? 0 : (1024 / TM) * i; };
+  auto b_kmin = [](int i) { return BN ? (1024 / TN) * i : 0; };
+  f32x4 ra[D][SA], rb[D][SB];
+  auto fetch = [&](int p, f32x4 (&qa)[SA], f32x4 (&qb)[SB]) {
+    const int k0 = p * PK;
+    const bool tail = k0 + PK > KC;
+#pragma unroll
+    for (int i = 0; i < SA; ++i) {
+      if (k0 + a_kmin(i) >= K4) continue;
+      int gk = k0 + ak[i];
+      if (tail) gk = min(gk, KC - (AK ? 4 : 1));
+      qa[i] = *reinterpret_cast<const f32x4*>(A + aoff[i] + gk * a_sk);
+    }
+#pragma unroll
+    for (int i = 0; i < SB; ++i) {
+      if (k0 + b_kmin(i) >= K4) continue;
+      int gk = k0 + bk[i];
+      if (tail) gk = min(gk, KC - (BN ? 1 : 4));
+      qb[i] = *reinterpret_cast<const f32x4*>(B + boff[i] + gk * b_sk);
+    }
+  };
+  auto publish = [&](int p, const f32x4 (&qa)[SA], const f32x4 (&qb)[SB]) {
+    const int k0 = p * PK;
+    const bool tail = k0 + PK > KC;
+#pragma unroll
+    for (int i = 0; i < SA; ++i) {
+      if (k0 + a_kmin(i) >= K4) continue;
+      const int gk = k0 + ak[i];
+      const bool ok = a_ok[i] && (!tail || gk < KC);
+      f32x4 v = qa[i];
+      if (a_drop) {
+        const int64_t off = aoff[i] + (tail ? min(gk, KC - (AK ? 4 : 1)) : gk) * a_sk;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] *= cwf_keep(a.rng, a.a_drop_off, (uint64_t)(a_zoff + off + c), a.a_drop_n, a.a_drop_p, a.a_drop_p2);   // (unit stride along the vector)
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float w = ok ? v[c] : 0.f;
+        if (AK) As[am[i] * LDA_S + ak[i] + c] = w;
+        else As[(am[i] + c) * LDA_S + ak[i]] = w;
       }
     }
-  if (do_rs && r == 0) {
 #pragma unroll
-    for (int i = 0; i < IM; ++i)
+    for (int i = 0; i < SB; ++i) {
+      if (k0 + b_kmin(i) >= K4) continue;
+      const bool ok = b_ok[i] && (!tail || k0 + bk[i] < KC);
+      f32x4 v = qb[i];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int gm = m0 + wr * (TM / 2) + i * 16 + kq * 4 + e;
-        if (gm < a.M) rowsum[gm] = (a.rowsum_acc ? rowsum[gm] : 0.f) + accr[i][e];
+      for (int c = 0; c < 4; ++c) v[c] = ok ? v[c] : 0.f;
+      if (BN) *reinterpret_cast<f32x4*>(&Bs[bk[i] * LDB_S + bn[i]]) = v;
+      else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) Bs[(bk[i] + c) * LDB_S + (bn[i] ^ ((bk[i] >> 2) & 15))] = v[c];
       }
+    }
+  };
+#pragma unroll
+  for (int p = 0; p < D && p < NP; ++p) fetch(p, ra[p], rb[p]);
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    if (p) __syncthreads();
+    publish(p, ra[p % D], rb[p % D]);
+    __syncthreads();
+    if (p + D < NP) fetch(p + D, ra[p % D], rb[p % D]);     // D - 1 younger panels stay in flight behind it
+    constexpr int KK_ALL = PK / 4;
+    const int kk_n = (p + 1) * PK > K4 ? (K4 - p * PK) / 4 : KK_ALL;
+    auto mfmas = [&](auto rs) {                              // one branch per panel, not per MFMA: the phase is one basic block
+#pragma unroll
+      for (int kk = 0; kk < KK_ALL; ++kk) {
+        if (kk >= kk_n) continue;
+        float av[IM], bv[JN];
+#pragma unroll
+        for (int i = 0; i < IM; ++i) av[i] = As[(wr * (TM / 2) + i * 16 + r) * LDA_S + kk * 4 + kq];
+#pragma unroll
+        for (int j = 0; j < JN; ++j) bv[j] = Bs[(kk * 4 + kq) * LDB_S + wc * (TN / 2) + j * 16 + (BN ? r : r ^ (kk & 15))];
+#pragma unroll
+        for (int i = 0; i < IM; ++i)
+#pragma unroll
+          for (int j = 0; j < JN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+        if (decltype(rs)::value) {
+#pragma unroll
+          for (int i = 0; i < IM; ++i) accr[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], 1.0f, accr[i], 0, 0, 0);
+        }
+      }
+    };
+    if (do_rs) mfmas(std::true_type()); else mfmas(std::false_type());
   }
+  gemm_epilogue<TM, TN>(a, acc, accr, zb, zh, m0, n0, wr, wc, r, kq, do_rs, rowsum);
 }
 
 // every pointer / stride the vector kernel dereferences with 16-byte loads
@@ -337,6 +476,37 @@ static int gemm_check(const GemmArgs& a) {
   return 0;
 }
 
+// The K-panel instantiations: (layout AK / BN, K, tile) of every cwf_gemm_ex launch of the training step (tools/gemm_census.py), and
+// at the 32 x 32 tile the schedule's edge extents of one panel, exactly D panels and D + 1 panels for the tests.  `product`: the
+// shape class takes the panel kernel by default (cwf_debug_gemm_panel(1)): isolated, at least 10 % faster than gemm_mfma_v_kernel in
+// two repetitions AND the training step faster with it (profiles/gemm_panel_ab.txt); the others are reached with (2) only.
+constexpr int GP_PK = 64, GP_D32 = 4, GP_PK64 = 32, GP_D64 = 4;          // panel width and panels in flight at the 32 x 32 / 64 x 64 tile
+typedef void (*GemmKernel)(const GemmArgs);
+struct GemmPanelEntry { bool ak, bn; int K, tm; bool product; GemmKernel kernel; };
+#define CWF_GP(AKv, BNv, Kv, TMv, PROD) {AKv, BNv, Kv, TMv, PROD, gemm_mfma_p_kernel<TMv, TMv, (TMv == 64 ? GP_PK64 : GP_PK), Kv, (TMv == 64 ? GP_D64 : GP_D32), AKv, BNv>}
+static const GemmPanelEntry g_gemm_panel_tab[] = {
+  CWF_GP(true, false, 512, 64, true),   CWF_GP(true, false, 512, 32, true),                   // forward: qkv / out-projection, FFN, fusion block
+  CWF_GP(true, true, 512, 32, true),    CWF_GP(true, true, 1024, 32, true),                   // data gradients (dq / dkv views)
+  CWF_GP(false, true, 516, 64, true),   CWF_GP(false, true, 516, 32, true),   CWF_GP(false, true, 258, 32, true),    // weight gradients
+  CWF_GP(true, false, GP_PK, 32, false), CWF_GP(true, false, GP_D32 * GP_PK, 32, false), CWF_GP(true, false, (GP_D32 + 1) * GP_PK, 32, false),
+  CWF_GP(true, true, GP_PK, 32, false),  CWF_GP(true, true, GP_D32 * GP_PK, 32, false),  CWF_GP(true, true, (GP_D32 + 1) * GP_PK, 32, false),
+  CWF_GP(false, true, GP_PK, 32, false), CWF_GP(false, true, GP_D32 * GP_PK, 32, false), CWF_GP(false, true, (GP_D32 + 1) * GP_PK, 32, false),
+};
+#undef CWF_GP
+
+// cwf_debug_gemm_panel: 1 = the product route, 0 = never (tests: gemm_mfma_v_kernel's result), 2 = every launch with an instantiation.
+static int g_gemm_panel = 1;
+static long long g_gemm_panel_launches = 0;
+extern "C" int cwf_debug_gemm_panel(int v) { const int old = g_gemm_panel; g_gemm_panel = v; return old; }
+extern "C" long long cwf_debug_gemm_panel_launches() { return g_gemm_panel_launches; }
+
+static const GemmPanelEntry* gemm_panel_route(const GemmArgs& a, const GemmVariant& v) {
+  if (!v.vec || g_gemm_panel == 0) return nullptr;
+  for (const GemmPanelEntry& e : g_gemm_panel_tab)
+    if (e.ak == v.ak && e.bn == v.bn && e.K == a.K && e.tm == v.tm) return (e.product || g_gemm_panel == 2) ? &e : nullptr;
+  return nullptr;
+}
+
 extern "C" int cwf_gemm_ex(const struct cwf_gemm_args* args, void* stream) {
   if (!args) return CWF_E_BADARG;
   const GemmArgs& a = *args;
@@ -344,6 +514,13 @@ extern "C" int cwf_gemm_ex(const struct cwf_gemm_args* args, void* stream) {
   if (rc) return rc;
   const GemmVariant v = gemm_variant(a);
   const bool big = v.tm == 64;
+  if (const GemmPanelEntry* e = gemm_panel_route(a, v)) {
+    dim3 grid(cdiv(a.N, e->tm), cdiv(a.M, e->tm), a.ZB * a.ZH);
+    hipLaunchKernelGGL(e->kernel, grid, dim3(256), 0, cwf_stream(stream), a);
+    CWF_LAUNCH_CHECK();
+    ++g_gemm_panel_launches;
+    return 0;
+  }
   if (v.vec) {
     dim3 grid(cdiv(a.N, big ? 64 : 32), cdiv(a.M, big ? 64 : 32), a.ZB * a.ZH);
 #define CWF_GV(AKv, BNv) do { if (big) hipLaunchKernelGGL((gemm_mfma_v_kernel<64, 64, 32, AKv, BNv>), grid, dim3(256), 0, cwf_stream(stream), a); \

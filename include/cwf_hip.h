@@ -226,6 +226,13 @@ struct cwf_gemm_args {
   const float* B_tab[4]; const float* bias_tab[4]; float* C_tab[4]; float* rowsum_tab[4];
 };
 int cwf_gemm_ex(const struct cwf_gemm_args* args /* host */, void* stream);
+/* Tests and tools: the route of the K-panel GEMM kernels (the whole contraction as straight-line code over compile-time panels, several
+ * panels of 16-byte loads in flight; instantiated for the contraction lengths the training step launches).  cwf_debug_gemm_panel: 1 = the
+ * product route (the shape classes measured faster there), 0 = never (the 16-byte-load kernel's result), 2 = every launch that has an
+ * instantiation; returns the previous value.  cwf_debug_gemm_panel_launches: launches that took the route so far (host-side count).
+ * Results do not depend on the route: every output is bit-identical. */
+int cwf_debug_gemm_panel(int v);
+long long cwf_debug_gemm_panel_launches(void);
 
 /* The attention core of one coupler block in one launch each way (SelfAttention.py:94-98; K6):
  *   qkv [Z*T][ld] holds q | k | v side by side (columns [0,E) [E,2E) [2E,3E), head-major), T <= 144, E = heads*64

@@ -10,7 +10,7 @@ from __future__ import annotations
 import contextlib
 import functools
 import math
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -949,21 +949,58 @@ def dice_ce_loss(prob_ncdhw, label, posmask=0):
     return _DiceCeFn.apply(to_channels_last_view(prob_ncdhw), label, int(posmask))
 
 
-class _BoundaryLossFn(torch.autograd.Function):
-    """mean over (sample, region, voxel) of phi_r * p_r, times a device-resident weight (csrc/boundary.hip)."""
+def _label_i64(label):
+    """the label map as the contiguous int64 tensor the loss kernels read"""
+    label = label.contiguous()
+    return label if label.dtype == torch.int64 else label.long()
+
+
+def _grad_scale(g):
+    """the incoming gradient of a scalar loss as the one-float32 tensor the backward kernels read"""
+    return g.reshape(1).to(torch.float32).contiguous()
+
+
+class _TermCalls(NamedTuple):
+    """What _WeightedTermFn needs of a supplementary term: its pair of backend calls and the static (non-tensor) arguments of both."""
+    forward: Callable            # (K, prob_cl, aux, weight, *static) -> (loss [1], the tensors to save for backward)
+    backward: Callable           # (K, the saved tensors, gscale, *static) -> dprob
+    static: tuple = ()
+
+
+def _saving(out, *inputs):
+    """(loss, *tensors) of a backend forward -> (loss, the tensors backward needs: `inputs`, then what the forward left)"""
+    return out[0], inputs + tuple(out[1:])
+
+
+# boundary (csrc/boundary.hip): aux is phi; static = (posmasks,)
+_BOUNDARY = (lambda K, p, phi, w, masks: _saving(K.boundary_loss(p, phi, masks, w), p, phi),
+             lambda K, t, gs, masks: K.boundary_loss_bwd(t[0], t[1], masks, t[2], gs))
+# top-k cross-entropy (csrc/topk.hip): static = (posmask, k)
+_TOPK = (lambda K, p, label, w, posmask, k: _saving(K.topk_ce(p, label, posmask, k, w), p, label),
+         lambda K, t, gs, posmask, k: K.topk_ce_bwd(t[0], t[1], posmask, t[2], gs))
+# focal Tversky + focal cross-entropy (csrc/focal.hip): static = (posmasks, params)
+_FOCAL = (lambda K, p, label, w, masks, params: _saving(K.focal_loss(p, label, masks, params, w), p, label),
+          lambda K, t, gs, masks, params: K.focal_loss_bwd(t[0], t[1], masks, params, t[2], gs))
+# Lovasz-Softmax (csrc/lovasz.hip): the forward leaves (coef, the signed per-voxel coefficients), all that the one streaming launch of
+# the backward reads; static = (posmasks, only_present, the shape of prob_cl)
+_LOVASZ = (lambda K, p, label, w, masks, only_present, shape: _saving(K.lovasz(p, label, masks, only_present, w)),
+           lambda K, t, gs, masks, only_present, shape: K.lovasz_bwd(t[1], masks, t[0], gs, shape))
+
+
+class _WeightedTermFn(torch.autograd.Function):
+    """A supplementary loss term of the main output at a device-resident weight: term.forward through the backend, and term.backward
+    on what it saved."""
 
     @staticmethod
-    def forward(ctx, prob_cl, phi, posmasks, weight):
-        loss, coef = backend().boundary_loss(prob_cl, phi, posmasks, weight)
-        ctx.posmasks = posmasks
-        ctx.save_for_backward(prob_cl, phi, coef)
+    def forward(ctx, prob_cl, aux, weight, term):
+        loss, saved = term.forward(backend(), prob_cl, aux, weight, *term.static)
+        ctx.term = term
+        ctx.save_for_backward(*saved)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        prob_cl, phi, coef = ctx.saved_tensors
-        gs = g.reshape(1).to(torch.float32).contiguous()
-        return backend().boundary_loss_bwd(prob_cl, phi, ctx.posmasks, coef, gs), None, None, None
+        return ctx.term.backward(backend(), ctx.saved_tensors, _grad_scale(g), *ctx.term.static), None, None, None
 
 
 def loss_weight_tensor(weight, device, what):
@@ -989,28 +1026,9 @@ def boundary_loss(prob_ncdhw, label, posmasks=REGION_MASKS, weight=1.0, phi=None
     [N,R,D,H,W] (backend().signed_distance), else computed here.  weight: float or one-element device tensor."""
     posmasks = tuple(int(m) for m in posmasks)
     if phi is None:
-        label = label.contiguous()
-        if label.dtype != torch.int64:
-            label = label.long()
-        phi = backend().signed_distance(label, posmasks)
-    return _BoundaryLossFn.apply(to_channels_last_view(prob_ncdhw), phi.contiguous(), posmasks, boundary_weight_tensor(weight, prob_ncdhw.device))
-
-
-class _TopkCeFn(torch.autograd.Function):
-    """weight x mean of -log p_t over the k hardest voxels of the batch, exact selection on the device (csrc/topk.hip)."""
-
-    @staticmethod
-    def forward(ctx, prob_cl, label, posmask, k, weight):
-        loss, coef = backend().topk_ce(prob_cl, label, posmask, k, weight)
-        ctx.posmask = posmask
-        ctx.save_for_backward(prob_cl, label, coef)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        prob_cl, label, coef = ctx.saved_tensors
-        gs = g.reshape(1).to(torch.float32).contiguous()
-        return backend().topk_ce_bwd(prob_cl, label, ctx.posmask, coef, gs), None, None, None, None
+        phi = backend().signed_distance(_label_i64(label), posmasks)
+    wt = loss_weight_tensor(weight, prob_ncdhw.device, "boundary")
+    return _WeightedTermFn.apply(to_channels_last_view(prob_ncdhw), phi.contiguous(), wt, _TermCalls(*_BOUNDARY, (posmasks,)))
 
 
 def topk_count(M, percent):
@@ -1024,28 +1042,10 @@ def topk_ce_loss(prob_ncdhw, label, percent=10.0, weight=1.0, posmask=0):
     or one-element device tensor.  Ties at the threshold share the remaining weight equally."""
     if not 0.0 < float(percent) <= 100.0:
         raise ValueError("topk percent must lie in (0, 100], got %r" % (percent,))
-    label = label.contiguous()
-    if label.dtype != torch.int64:
-        label = label.long()
-    k = topk_count(label.numel(), float(percent))
-    return _TopkCeFn.apply(to_channels_last_view(prob_ncdhw), label, int(posmask), k, loss_weight_tensor(weight, prob_ncdhw.device, "topk"))
-
-
-class _FocalLossFn(torch.autograd.Function):
-    """weight x (focal Tversky of the regions + ce_ratio x focal cross-entropy), sums over the whole batch (csrc/focal.hip)."""
-
-    @staticmethod
-    def forward(ctx, prob_cl, label, posmasks, params, weight):
-        loss, coef = backend().focal_loss(prob_cl, label, posmasks, params, weight)
-        ctx.posmasks, ctx.params = posmasks, params
-        ctx.save_for_backward(prob_cl, label, coef)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        prob_cl, label, coef = ctx.saved_tensors
-        gs = g.reshape(1).to(torch.float32).contiguous()
-        return backend().focal_loss_bwd(prob_cl, label, ctx.posmasks, ctx.params, coef, gs), None, None, None, None
+    label = _label_i64(label)
+    wt = loss_weight_tensor(weight, prob_ncdhw.device, "topk")
+    static = (int(posmask), topk_count(label.numel(), float(percent)))
+    return _WeightedTermFn.apply(to_channels_last_view(prob_ncdhw), label, wt, _TermCalls(*_TOPK, static))
 
 
 def focal_loss(prob_ncdhw, label, posmasks=REGION_MASKS, fn=0.7, fp=0.3, exponent=0.75, smooth=1e-5, gamma=2.0, ce_ratio=1.0,
@@ -1062,28 +1062,7 @@ def focal_loss(prob_ncdhw, label, posmasks=REGION_MASKS, fn=0.7, fp=0.3, exponen
     if prob_ncdhw.dim() != 5 or int(prob_ncdhw.shape[1]) != 4:
         raise ValueError("focal loss takes probabilities [N, 4, D, H, W], got %s" % (tuple(prob_ncdhw.shape),))
     wt = loss_weight_tensor(weight, prob_ncdhw.device, "focal")
-    label = label.contiguous()
-    if label.dtype != torch.int64:
-        label = label.long()
-    return _FocalLossFn.apply(to_channels_last_view(prob_ncdhw), label, posmasks, params, wt)
-
-
-class _LovaszFn(torch.autograd.Function):
-    """weight x the mean over the counted regions of the Lovasz extension of the Jaccard loss, sorted over the whole batch
-    (csrc/lovasz.hip).  The forward leaves the signed per-voxel coefficients; the backward is one streaming launch over them."""
-
-    @staticmethod
-    def forward(ctx, prob_cl, label, posmasks, only_present, weight):
-        loss, coef, vcoef = backend().lovasz(prob_cl, label, posmasks, only_present, weight)
-        ctx.posmasks, ctx.shape = posmasks, tuple(prob_cl.shape)
-        ctx.save_for_backward(coef, vcoef)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        coef, vcoef = ctx.saved_tensors
-        gs = g.reshape(1).to(torch.float32).contiguous()
-        return backend().lovasz_bwd(vcoef, ctx.posmasks, coef, gs, ctx.shape), None, None, None, None
+    return _WeightedTermFn.apply(to_channels_last_view(prob_ncdhw), _label_i64(label), wt, _TermCalls(*_FOCAL, (posmasks, params)))
 
 
 def lovasz_softmax(prob_ncdhw, label, posmasks=CLASS_MASKS, only_present=True, weight=1.0):
@@ -1096,7 +1075,5 @@ def lovasz_softmax(prob_ncdhw, label, posmasks=CLASS_MASKS, only_present=True, w
     if prob_ncdhw.dim() != 5 or int(prob_ncdhw.shape[1]) != 4:
         raise ValueError("lovasz_softmax takes probabilities [N, 4, D, H, W], got %s" % (tuple(prob_ncdhw.shape),))
     wt = loss_weight_tensor(weight, prob_ncdhw.device, "lovasz")
-    label = label.contiguous()
-    if label.dtype != torch.int64:
-        label = label.long()
-    return _LovaszFn.apply(to_channels_last_view(prob_ncdhw), label, posmasks, only_present, wt)
+    prob_cl = to_channels_last_view(prob_ncdhw)
+    return _WeightedTermFn.apply(prob_cl, _label_i64(label), wt, _TermCalls(*_LOVASZ, (posmasks, only_present, tuple(prob_cl.shape))))

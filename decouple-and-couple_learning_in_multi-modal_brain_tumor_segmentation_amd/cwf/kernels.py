@@ -1168,7 +1168,7 @@ class HipBackend:
                    n, d * h * w, c, self._stream())
         return dprob
 
-    # ------------------------------------------------------------------ L2 (boundary loss)
+    # ------------------------------------------------------------------ L2-L5: the checks the supplementary loss terms share
     @staticmethod
     def _posmasks(name, posmasks):
         masks = tuple(int(m) for m in posmasks)
@@ -1176,19 +1176,43 @@ class HipBackend:
             raise ValueError("%s: a region is a 32-bit class bitmask, got %r" % (name, posmasks))
         return masks, (ctypes.c_uint32 * max(len(masks), 1))(*masks)
 
+    @staticmethod
+    def _prob_label(name, prob, label, channels):
+        """prob float32 [N, D0, D1, D2, C] on the GPU with C one of `channels`, label int64 of its leading shape on the same device, both
+        contiguous -> (N, V, C)"""
+        if prob.dim() != 5 or prob.dtype != _f32 or not prob.is_cuda or int(prob.shape[-1]) not in channels:
+            raise ValueError("%s: prob must be a float32 [N, D0, D1, D2, C] tensor on the GPU with C = %s, got %s %s"
+                             % (name, " or ".join(str(c) for c in channels), tuple(prob.shape), prob.dtype))
+        if tuple(label.shape) != tuple(prob.shape[:4]) or label.dtype != torch.int64 or label.device != prob.device:
+            raise ValueError("%s: label must be int64 %s on the device of prob, got %s %s"
+                             % (name, tuple(prob.shape[:4]), tuple(label.shape), label.dtype))
+        assert prob.is_contiguous() and label.is_contiguous()
+        return int(prob.shape[0]), int(prob[0, ..., 0].numel()), int(prob.shape[-1])
+
+    @staticmethod
+    def _one_float(name, what, t, device):
+        if t.numel() != 1 or t.dtype != _f32 or t.device != device:
+            raise ValueError("%s: %s must be a one-element float32 tensor on the device of prob" % (name, what))
+
+    def _workspace(self, fn_name, device, *dims):
+        """the uint8 workspace of the size the library's `fn_name`(*dims) asks for.  No host synchronisation: it comes from torch's
+        allocator."""
+        nbytes = getattr(self.lib, fn_name)(*dims)
+        if nbytes < 0:
+            raise _lib.CwfError("%s%r failed with status %d" % (fn_name, dims, nbytes))
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+    # ------------------------------------------------------------------ L2 (boundary loss)
     def signed_distance(self, label, posmasks=REGION_MASKS):
         """label int64 [N, D0, D1, D2] -> phi float32 [N, R, D0, D1, D2]: the exact Euclidean signed distance map of every region
         (class bitmask) of `posmasks`, sqrt(q) outside and 1 - sqrt(q) inside, rounded once from float64; zeros where a region is empty
-        or fills the volume (cwf_signed_distance).  No host synchronisation: the workspace comes from torch's allocator."""
+        or fills the volume (cwf_signed_distance)."""
         if label.dim() != 4 or label.dtype != torch.int64 or not label.is_cuda:
             raise ValueError("signed_distance: label must be an int64 [N, D0, D1, D2] tensor on the GPU")
         masks, cm = self._posmasks("signed_distance", posmasks)
         label = label.contiguous()
         n, d0, d1, d2 = (int(s) for s in label.shape)
-        nbytes = self.lib.cwf_signed_distance_workspace(n, len(masks), d0, d1, d2)
-        if nbytes < 0:
-            raise _lib.CwfError("cwf_signed_distance_workspace failed with status %d (N=%d R=%d %dx%dx%d)" % (nbytes, n, len(masks), d0, d1, d2))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=label.device)
+        ws = self._workspace("cwf_signed_distance_workspace", label.device, n, len(masks), d0, d1, d2)
         phi = torch.empty((n, len(masks), d0, d1, d2), dtype=_f32, device=label.device)
         self._call("cwf_signed_distance", label.data_ptr(), ctypes.addressof(cm), phi.data_ptr(), n, len(masks), d0, d1, d2, ws.data_ptr(),
                    self._stream())
@@ -1202,8 +1226,7 @@ class HipBackend:
         if tuple(phi.shape) != (n, len(masks)) + tuple(prob.shape[1:4]) or phi.dtype != _f32 or prob.dtype != _f32:
             raise ValueError("boundary_loss: phi must be float32 [N, R, D0, D1, D2] for prob [N, D0, D1, D2, C], got %s and %s"
                              % (tuple(phi.shape), tuple(prob.shape)))
-        if weight.numel() != 1 or weight.dtype != _f32 or weight.device != prob.device:
-            raise ValueError("boundary_loss: weight must be a one-element float32 tensor on the device of prob")
+        self._one_float("boundary_loss", "weight", weight, prob.device)
         assert prob.is_contiguous() and phi.is_contiguous()
         s = self._zeros_f64((1,), prob.device)
         self._call("cwf_boundary_sums", prob.data_ptr(), phi.data_ptr(), ctypes.addressof(cm), s.data_ptr(), n, len(masks), v, c, self._stream())
@@ -1224,32 +1247,22 @@ class HipBackend:
     # ------------------------------------------------------------------ L3 (top-k cross-entropy)
     @staticmethod
     def _topk_args(name, prob, label, posmask):
-        if prob.dim() != 5 or prob.dtype != _f32 or not prob.is_cuda or int(prob.shape[-1]) not in (2, 4):
-            raise ValueError("%s: prob must be a float32 [N, D0, D1, D2, C] tensor on the GPU with C = 2 or 4, got %s %s"
-                             % (name, tuple(prob.shape), prob.dtype))
-        if tuple(label.shape) != tuple(prob.shape[:4]) or label.dtype != torch.int64 or label.device != prob.device:
-            raise ValueError("%s: label must be int64 %s on the device of prob, got %s %s"
-                             % (name, tuple(prob.shape[:4]), tuple(label.shape), label.dtype))
+        n, v, c = HipBackend._prob_label(name, prob, label, (2, 4))
         posmask = int(posmask)
         if posmask < 0 or posmask > 0xFFFFFFFF:
             raise ValueError("%s: posmask is a 32-bit class bitmask, got %r" % (name, posmask))
-        assert prob.is_contiguous() and label.is_contiguous()
-        return int(prob.shape[0]), int(prob[0, ..., 0].numel()), int(prob.shape[-1]), posmask
+        return n, v, c, posmask
 
     def topk_ce(self, prob, label, posmask, k, weight):
         """prob [N,D0,D1,D2,C] dense channels-last (C = 4 or 2), label int64 [N,D0,D1,D2], k voxels of the whole batch, weight a
         one-float device tensor -> (loss [1], coef [4]): weight x mean of -log p_t over the k hardest voxels by an exact radix select
-        on the device (cwf_topk_ce).  No host synchronisation: the workspace comes from torch's allocator."""
+        on the device (cwf_topk_ce)."""
         n, v, c, posmask = self._topk_args("topk_ce", prob, label, posmask)
         k = int(k)
         if k < 1 or k > n * v:
             raise ValueError("topk_ce: k must lie in 1..N V = %d, got %d" % (n * v, k))
-        if weight.numel() != 1 or weight.dtype != _f32 or weight.device != prob.device:
-            raise ValueError("topk_ce: weight must be a one-element float32 tensor on the device of prob")
-        nbytes = self.lib.cwf_topk_ce_workspace(n, v)
-        if nbytes < 0:
-            raise _lib.CwfError("cwf_topk_ce_workspace failed with status %d (N=%d V=%d)" % (nbytes, n, v))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=prob.device)
+        self._one_float("topk_ce", "weight", weight, prob.device)
+        ws = self._workspace("cwf_topk_ce_workspace", prob.device, n, v)
         loss = torch.empty(1, dtype=_f32, device=prob.device)
         coef = torch.empty(4, dtype=_f32, device=prob.device)
         self._call("cwf_topk_ce", prob.data_ptr(), label.data_ptr(), posmask, k, weight.data_ptr(), loss.data_ptr(), coef.data_ptr(), n, v, c,
@@ -1269,29 +1282,19 @@ class HipBackend:
     @staticmethod
     def _focal_args(name, prob, label, posmasks, params):
         """-> (N, V, masks, the uint32 array, the cwf_focal_params struct); every check the C entry makes, made before any call"""
-        if prob.dim() != 5 or prob.dtype != _f32 or not prob.is_cuda or int(prob.shape[-1]) != 4:
-            raise ValueError("%s: prob must be a float32 [N, D0, D1, D2, 4] tensor on the GPU, got %s %s" % (name, tuple(prob.shape), prob.dtype))
-        if tuple(label.shape) != tuple(prob.shape[:4]) or label.dtype != torch.int64 or label.device != prob.device:
-            raise ValueError("%s: label must be int64 %s on the device of prob, got %s %s"
-                             % (name, tuple(prob.shape[:4]), tuple(label.shape), label.dtype))
+        n, v, _ = HipBackend._prob_label(name, prob, label, (4,))
         masks, cm = HipBackend._posmasks(name, posmasks)
         p = check_focal_params(masks, **params)
-        assert prob.is_contiguous() and label.is_contiguous()
         cp = _lib.FocalParams(p["fn"], p["fp"], p["exponent"], p["smooth"], p["gamma"], p["ce_ratio"], (ctypes.c_double * 4)(*p["class_weight"]))
-        return int(prob.shape[0]), int(prob[0, ..., 0].numel()), masks, cm, cp
+        return n, v, masks, cm, cp
 
     def focal_loss(self, prob, label, posmasks, params, weight):
         """prob [N,D0,D1,D2,4] dense channels-last, label int64 [N,D0,D1,D2], posmasks R <= 8 class bitmasks over bits 0..3, params a
         dict (fn, fp, exponent, smooth, gamma, ce_ratio, class_weight), weight a one-float device tensor -> (loss [1], coef [2 R + 1]):
-        weight x (focal Tversky of the regions + ce_ratio x focal cross-entropy), sums over the whole batch (cwf_focal_loss).  No host
-        synchronisation: the workspace comes from torch's allocator."""
+        weight x (focal Tversky of the regions + ce_ratio x focal cross-entropy), sums over the whole batch (cwf_focal_loss)."""
         n, v, masks, cm, cp = self._focal_args("focal_loss", prob, label, posmasks, params)
-        if weight.numel() != 1 or weight.dtype != _f32 or weight.device != prob.device:
-            raise ValueError("focal_loss: weight must be a one-element float32 tensor on the device of prob")
-        nbytes = self.lib.cwf_focal_workspace(n, v, len(masks))
-        if nbytes < 0:
-            raise _lib.CwfError("cwf_focal_workspace failed with status %d (N=%d V=%d R=%d)" % (nbytes, n, v, len(masks)))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=prob.device)
+        self._one_float("focal_loss", "weight", weight, prob.device)
+        ws = self._workspace("cwf_focal_workspace", prob.device, n, v, len(masks))
         loss = torch.empty(1, dtype=_f32, device=prob.device)
         coef = torch.empty(2 * len(masks) + 1, dtype=_f32, device=prob.device)
         self._call("cwf_focal_loss", prob.data_ptr(), label.data_ptr(), ctypes.addressof(cm), len(masks), ctypes.addressof(cp), weight.data_ptr(),
@@ -1313,25 +1316,14 @@ class HipBackend:
     def lovasz(self, prob, label, posmasks, only_present, weight):
         """prob [N,D0,D1,D2,4] dense channels-last, label int64 [N,D0,D1,D2], posmasks 1..8 class bitmasks in 1..15, weight a one-float
         device tensor -> (loss [1], coef [4], vcoef [R, N V]): weight x the mean over the counted regions of the Lovasz extension of the
-        Jaccard loss, by an exact sort of the errors of the whole batch on the device (cwf_lovasz).  No host synchronisation: the
-        workspace comes from torch's allocator."""
-        if prob.dim() != 5 or prob.dtype != _f32 or not prob.is_cuda or int(prob.shape[-1]) != 4:
-            raise ValueError("lovasz: prob must be a float32 [N, D0, D1, D2, 4] tensor on the GPU, got %s %s" % (tuple(prob.shape), prob.dtype))
-        if tuple(label.shape) != tuple(prob.shape[:4]) or label.dtype != torch.int64 or label.device != prob.device:
-            raise ValueError("lovasz: label must be int64 %s on the device of prob, got %s %s"
-                             % (tuple(prob.shape[:4]), tuple(label.shape), label.dtype))
+        Jaccard loss, by an exact sort of the errors of the whole batch on the device (cwf_lovasz)."""
+        n, v, _ = self._prob_label("lovasz", prob, label, (4,))
         masks, only_present = check_lovasz_params(posmasks, only_present)
-        if weight.numel() != 1 or weight.dtype != _f32 or weight.device != prob.device:
-            raise ValueError("lovasz: weight must be a one-element float32 tensor on the device of prob")
-        assert prob.is_contiguous() and label.is_contiguous()
-        n, v = int(prob.shape[0]), int(prob[0, ..., 0].numel())
+        self._one_float("lovasz", "weight", weight, prob.device)
         if n * v > 0x7FFFFFFF:
             raise ValueError("lovasz: at most 2^31 - 1 voxels in the batch, got %d" % (n * v))
         cm = (ctypes.c_uint32 * len(masks))(*masks)
-        nbytes = self.lib.cwf_lovasz_workspace(n, v, len(masks))
-        if nbytes < 0:
-            raise _lib.CwfError("cwf_lovasz_workspace failed with status %d (N=%d V=%d R=%d)" % (nbytes, n, v, len(masks)))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=prob.device)
+        ws = self._workspace("cwf_lovasz_workspace", prob.device, n, v, len(masks))
         loss = torch.empty(1, dtype=_f32, device=prob.device)
         coef = torch.empty(4, dtype=_f32, device=prob.device)
         vcoef = torch.empty((len(masks), n * v), dtype=_f32, device=prob.device)

@@ -34,22 +34,16 @@ Step controls (all off by default; then the step issues exactly the launches des
     (SURVEY.md F2).  Accumulate and fold launches are never captured: the captured step is the same for every micro-step.
   * max_grad_norm: the averaged gradient is clipped by its global norm inside the Adam launch (cwf.optim); no host sync.
   * ema_decay: the Adam launch also maintains an EMA copy of the weights (ema_state_dict() for validation / checkpoints).
-  * boundary_weight = w: a sixth loss term, w * boundary loss of the main output (tools.boundary_loss: signed distance maps of the
-    target's WT / TC / ET computed on the device every step), in front of the same backward.  w lives in a one-float device tensor
-    that the kernels read, so set_boundary_weight() between steps needs no recapture.  None: the step makes no new call.
-  * topk_weight = w, topk_percent = K: a further loss term after the boundary part, w * top-k cross-entropy of the main output
-    (tools.topk_ce: mean of -log p_target over the hardest K % of the batch's voxels, selected exactly on the device), in front of
-    the same backward.  w lives in a one-float device tensor (set_topk_weight() needs no recapture); K is fixed at construction, k
-    being a launch argument.  None: the step makes no new call and calls total_loss as before.
-  * focal_weight = w, focal_params = {...}: a further loss term after the boundary and top-k parts, w * (focal Tversky on WT / TC / ET
-    + ce_ratio * focal cross-entropy) of the main output (tools.focal_loss; sums over the whole batch), in front of the same backward.
-    w lives in a one-float device tensor (set_focal_weight() needs no recapture); the parameters (posmasks, fn, fp, exponent, smooth,
-    gamma, ce_ratio, class_weight) are fixed at construction, being launch arguments.  None: no new call, total_loss called as before.
-  * lovasz_weight = w, lovasz_regions = "classes" | "regions" | a tuple of class bitmasks, lovasz_only_present: a further loss term after
-    the boundary, top-k and focal parts, w * Lovasz-Softmax of the main output (tools.lovasz_softmax: the errors of the whole batch
-    sorted exactly on the device; "classes" is the four classes, "regions" WT / TC / ET), in front of the same backward.  w lives in a
-    one-float device tensor (set_lovasz_weight() needs no recapture); the regions are fixed at construction, being launch arguments.
-    None: no new call, total_loss called as before.
+  * <name>_weight = w for a supplementary loss term of cwf.loss_terms.TERMS: w * the term of the main output (outputs[0]) becomes a
+    further part, appended after the reference's five in the table's order and added to the total in front of the same backward.  w
+    lives in a one-float device tensor that the kernels read, made at the first step that needs it (before a capture), so
+    set_<name>_weight() between steps needs no recapture; the term's other options are launch arguments, fixed at construction.
+    None: the step makes no new call and total_loss is called without that keyword, as before the term existed.
+      boundary: tools.boundary_loss, signed distance maps of the target's WT / TC / ET computed on the device every step.
+      topk (topk_percent = K): tools.topk_ce, mean of -log p_target over the hardest K % of the batch's voxels, selected exactly.
+      focal (focal_params = {...}): tools.focal_loss, focal Tversky on WT / TC / ET + ce_ratio * focal cross-entropy, batch sums.
+      lovasz (lovasz_regions = "classes" | "regions" | class bitmasks, lovasz_only_present): tools.lovasz_softmax, exact sort.
+    A new term is one entry of that table, its pair of backend methods (cwf.kernels, cwf.functional) and its utils.tools wrapper.
   * optimizer = "adamw" | "sgd" (with betas / momentum, nesterov / no_decay): the update is one launch of the AdamW or SGD rule
     (cwf.optim.FusedAdamW / FusedSGD) in place of Adam's; sink, all-reduce, accumulation, clipping and EMA are the base class's and
     work as above.  schedule = "cosine" | "constant" and warmup_steps = W shape the learning rate of an update:
@@ -57,101 +51,43 @@ Step controls (all off by default; then the step issues exactly the launches des
 Checkpoints use the reference layout {'epoch', 'state_dict' with 'module.' prefix, 'optim_dict'} (:248-253)."""
 from __future__ import annotations
 
-import math
+import functools
 import os
 
 import torch
 import torch.distributed as dist
 
+from . import loss_terms
 from .optim import FusedAdam, FusedAdamW, FusedSGD, SCHEDULES, poly_lr, schedule_lr, warmup_factor
 
 
 def total_loss(outputs, target, edge, boundary=None, topk=None, focal=None, lovasz=None):
-    """The reference's five terms; with `boundary` (the one-float device tensor holding the boundary weight) a sixth part,
-    tools.boundary_loss(outputs[0], target) at that weight, is appended and added to the total; with `topk` = (the one-float device
-    tensor holding the top-k weight, percent) the part tools.topk_ce(outputs[0], target) is appended after it; with `focal` = (the
-    one-float device tensor holding the focal weight, the parameters as keyword arguments of tools.focal_loss) the part
-    tools.focal_loss(outputs[0], target) is appended after those; with `lovasz` = (the one-float device tensor holding the Lovasz weight,
-    the region masks, only_present) the part tools.lovasz_softmax(outputs[0], target) is appended last."""
+    """The reference's five terms, then one part per supplementary term that is given (cwf.loss_terms.TERMS, whose order the
+    keywords follow): tools.<tool>(outputs[0], target, ...) at the weight in the term's one-float device tensor, appended and added
+    to the total.  `boundary` is that tensor; a term with options receives (the tensor, *its options): topk = (tensor, percent),
+    focal = (tensor, the keyword arguments of tools.focal_loss), lovasz = (tensor, the region masks, only_present)."""
     from models import criterions
     from utils import tools
     parts = [criterions.softmax_dice(outputs[0], target), tools.get_separate_loss(outputs[1], target),
              tools.get_edge_separate_loss(outputs[2], edge), tools.get_separate_loss(outputs[3], target),
              tools.get_edge_separate_loss(outputs[4], edge)]
     total = parts[0] + parts[1] + parts[2] + parts[3] + parts[4]
-    if boundary is not None:
-        parts.append(tools.boundary_loss(outputs[0], target, weight=boundary))
-        total = total + parts[5]
-    if topk is not None:
-        parts.append(tools.topk_ce(outputs[0], target, percent=topk[1], weight=topk[0]))
-        total = total + parts[-1]
-    if focal is not None:
-        parts.append(tools.focal_loss(outputs[0], target, weight=focal[0], **focal[1]))
-        total = total + parts[-1]
-    if lovasz is not None:
-        parts.append(tools.lovasz_softmax(outputs[0], target, posmasks=lovasz[1], only_present=lovasz[2], weight=lovasz[0]))
-        total = total + parts[-1]
+    for term, value in zip(loss_terms.TERMS, (boundary, topk, focal, lovasz)):
+        if value is not None:
+            parts.append(getattr(tools, term.tool)(outputs[0], target, **loss_terms.unpack(term, value)))
+            total = total + parts[-1]
     return total, parts
 
 
 def check_boundary_weight(w):
     """None (term off) or a finite float >= 0"""
-    if w is None:
-        return None
-    w = float(w)
-    if not math.isfinite(w) or w < 0.0:
-        raise ValueError("boundary_weight must be None or a finite number >= 0, got %r" % (w,))
-    return w
+    return loss_terms.check_weight("boundary", w)
 
 
-def check_topk(weight, percent):
-    """(weight, percent): weight None (term off) or a finite float >= 0; percent a float in (0, 100]"""
-    percent = float(percent)
-    if not 0.0 < percent <= 100.0:                      # (NaN fails both comparisons)
-        raise ValueError("topk_percent must lie in (0, 100], got %r" % (percent,))
-    if weight is None:
-        return None, percent
-    weight = float(weight)
-    if not math.isfinite(weight) or weight < 0.0:
-        raise ValueError("topk_weight must be None or a finite number >= 0, got %r" % (weight,))
-    return weight, percent
-
-
-def check_focal(weight, params):
-    """(weight, params): weight None (term off) or a finite float >= 0; params None or a dict of tools.focal_loss's keyword arguments
-    (posmasks, fn, fp, exponent, smooth, gamma, ce_ratio, class_weight), checked by cwf.kernels.check_focal_params with the term off too.
-    -> (weight, the keyword arguments with every default filled in)"""
-    from .kernels import REGION_MASKS, check_focal_params
-    params = dict(params or {})
-    unknown = set(params) - {"posmasks", "fn", "fp", "exponent", "smooth", "gamma", "ce_ratio", "class_weight"}
-    if unknown:
-        raise ValueError("focal_params takes posmasks, fn, fp, exponent, smooth, gamma, ce_ratio and class_weight, got %s" % sorted(unknown))
-    posmasks = tuple(int(m) for m in params.pop("posmasks", REGION_MASKS))
-    checked = dict(check_focal_params(posmasks, **params), posmasks=posmasks)
-    if weight is None:
-        return None, checked
-    weight = float(weight)
-    if not math.isfinite(weight) or weight < 0.0:
-        raise ValueError("focal_weight must be None or a finite number >= 0, got %r" % (weight,))
-    return weight, checked
-
-
-def check_lovasz(weight, regions="classes", only_present=True):
-    """(weight, regions, only_present): weight None (term off) or a finite float >= 0; regions "classes" (the four classes), "regions"
-    (WT / TC / ET) or 1 to 8 class bitmasks in 1..15, checked by cwf.kernels.check_lovasz_params with the term off too.
-    -> (weight, the masks as a tuple, only_present)"""
-    from .kernels import CLASS_MASKS, REGION_MASKS, check_lovasz_params
-    if isinstance(regions, str):
-        if regions not in ("classes", "regions"):
-            raise ValueError("lovasz_regions must be 'classes', 'regions' or a tuple of class bitmasks, got %r" % (regions,))
-        regions = CLASS_MASKS if regions == "classes" else REGION_MASKS
-    masks, only_present = check_lovasz_params(regions, only_present)
-    if weight is None:
-        return None, masks, only_present
-    weight = float(weight)
-    if not math.isfinite(weight) or weight < 0.0:
-        raise ValueError("lovasz_weight must be None or a finite number >= 0, got %r" % (weight,))
-    return weight, masks, only_present
+# (weight, *options as given) -> (weight, *options as the Trainer stores them), ValueError for a bad value: cwf.loss_terms.check
+check_topk = functools.partial(loss_terms.check, "topk")            # (weight, percent)
+check_focal = functools.partial(loss_terms.check, "focal")          # (weight, params) -> (weight, every keyword of tools.focal_loss)
+check_lovasz = functools.partial(loss_terms.check, "lovasz")        # (weight, regions="classes", only_present=True) -> (weight, masks, ..)
 
 
 def boundary_schedule(weight, epoch, warmup):
@@ -170,14 +106,14 @@ class Trainer:
                  boundary_weight=None, topk_weight=None, topk_percent=10.0, optimizer="adam", betas=(0.9, 0.999), momentum=0.0,
                  nesterov=False, no_decay=None, schedule="poly", warmup_steps=0, focal_weight=None, focal_params=None,
                  lovasz_weight=None, lovasz_regions="classes", lovasz_only_present=True):
-        self.boundary_weight = check_boundary_weight(boundary_weight)
-        self._boundary = None                           # the weight as a one-float device tensor, made at the first step that needs it
-        self.topk_weight, self.topk_percent = check_topk(topk_weight, topk_percent)
-        self._topk = None                               # likewise
-        self.focal_weight, self.focal_params = check_focal(focal_weight, focal_params)
-        self._focal = None                              # likewise
-        self.lovasz_weight, self.lovasz_regions, self.lovasz_only_present = check_lovasz(lovasz_weight, lovasz_regions, lovasz_only_present)
-        self._lovasz = None                             # likewise
+        given = locals()                                # (the keyword arguments by name; nothing else is bound yet)
+        for term in loss_terms.TERMS:
+            # a term's state, under the names its keywords have: <name>_weight (None: off), its options as cwf.loss_terms stores
+            # them, and _<name>, the weight as a one-float device tensor, made at the first step that needs it
+            keys = (term.name + "_weight",) + term.options
+            for key, value in zip(keys, loss_terms.check(term.name, *(given[k] for k in keys))):
+                setattr(self, key, value)
+            setattr(self, "_" + term.name, None)
         self.model = model
         self.init_lr, self.end_epoch = lr, end_epoch
         if int(accum_steps) != accum_steps or accum_steps < 1:
@@ -294,13 +230,12 @@ class Trainer:
         K.wgrad_async = self.wgrad_async       # (from the forward pass on: it prepares weight-gradient operands on the side stream)
         outputs = self.model(x, None)
         extra = {}                                      # (a term that is off is not named: total_loss is called as before it existed)
-        if self.topk_weight is not None:
-            extra["topk"] = (self._topk_tensor(x.device), self.topk_percent)
-        if self.focal_weight is not None:
-            extra["focal"] = (self._focal_tensor(x.device), self.focal_params)
-        if self.lovasz_weight is not None:
-            extra["lovasz"] = (self._lovasz_tensor(x.device), self.lovasz_regions, self.lovasz_only_present)
-        loss, parts = total_loss(outputs, target, edge, self._boundary_tensor(x.device), **extra)
+        for term in loss_terms.TERMS:
+            wt = self._weight_tensor(term, x.device)
+            if wt is not None:
+                extra[term.name] = loss_terms.pack(term, wt, [getattr(self, k) for k in term.options])
+        # (the first term's value travels fourth, positionally, None when off: wrappers written before the keywords take it so)
+        loss, parts = total_loss(outputs, target, edge, extra.pop(loss_terms.TERMS[0].name, None), **extra)
         self.opt.zero_grad(set_to_none=True)
         # graph modes: one reduce per phase, in warm-up too
         K.flush_every = (1 << 30) if self.use_graph else K.flush_every_default
@@ -324,81 +259,38 @@ class Trainer:
                 torch.cuda.current_stream().wait_stream(self._comm_stream)      # (a capture must end with its forked streams joined)
         return loss.detach(), [p.detach() for p in parts]
 
-    def _boundary_tensor(self, device):
-        if self.boundary_weight is None:
-            return None
-        if self._boundary is None:
+    def _weight_tensor(self, term, device):
+        """the one-float device tensor the term's kernels read its weight from, made on first use; None with the term off"""
+        weight, key = getattr(self, term.name + "_weight"), "_" + term.name
+        if weight is not None and getattr(self, key) is None:
             if _capturing():
-                raise RuntimeError("the boundary weight tensor must exist before the step is captured")
-            self._boundary = torch.full((1,), self.boundary_weight, dtype=torch.float32, device=device)
-        return self._boundary
+                raise RuntimeError("the %s weight tensor must exist before the step is captured" % term.name)
+            setattr(self, key, torch.full((1,), weight, dtype=torch.float32, device=device))
+        return getattr(self, key)
+
+    def set_loss_weight(self, name, w):
+        """New weight of the term `name` (cwf.loss_terms) from the next step on, in every step mode: the kernels read it from device
+        memory, so a captured step needs no recapture.  Only for a Trainer built with a <name>_weight (the captured step has the term
+        or not); the term's other options stay as constructed."""
+        term = loss_terms.BY_NAME[name]
+        w = loss_terms.check_weight(name, w)
+        if w is None or getattr(self, name + "_weight") is None:
+            raise ValueError("the %s term is switched on or off at construction (%s_weight=...), not between steps" % (term.title, name))
+        setattr(self, name + "_weight", w)              # (remembered for a tensor that does not exist yet)
+        if getattr(self, "_" + name) is not None:
+            getattr(self, "_" + name).fill_(w)
 
     def set_boundary_weight(self, w):
-        """New weight of the boundary term from the next step on, in every step mode: the kernels read it from device memory, so a
-        captured step needs no recapture.  Only for a Trainer built with a boundary_weight (the captured step has the term or not)."""
-        w = check_boundary_weight(w)
-        if self.boundary_weight is None or w is None:
-            raise ValueError("the boundary term is switched on or off at construction (boundary_weight=...), not between steps")
-        self.boundary_weight = w
-        if self._boundary is not None:
-            self._boundary.fill_(w)
-
-    def _topk_tensor(self, device):
-        if self.topk_weight is None:
-            return None
-        if self._topk is None:
-            if _capturing():
-                raise RuntimeError("the top-k weight tensor must exist before the step is captured")
-            self._topk = torch.full((1,), self.topk_weight, dtype=torch.float32, device=device)
-        return self._topk
+        self.set_loss_weight("boundary", w)
 
     def set_topk_weight(self, w):
-        """New weight of the top-k term from the next step on, in every step mode (no recapture: the kernels read it from device
-        memory).  Only for a Trainer built with a topk_weight; the percentage stays as constructed."""
-        if w is None or self.topk_weight is None:
-            raise ValueError("the top-k term is switched on or off at construction (topk_weight=...), not between steps")
-        w, _ = check_topk(w, self.topk_percent)
-        self.topk_weight = w
-        if self._topk is not None:
-            self._topk.fill_(w)
-
-    def _focal_tensor(self, device):
-        if self.focal_weight is None:
-            return None
-        if self._focal is None:
-            if _capturing():
-                raise RuntimeError("the focal weight tensor must exist before the step is captured")
-            self._focal = torch.full((1,), self.focal_weight, dtype=torch.float32, device=device)
-        return self._focal
+        self.set_loss_weight("topk", w)
 
     def set_focal_weight(self, w):
-        """New weight of the focal term from the next step on, in every step mode (no recapture: the kernels read it from device
-        memory).  Only for a Trainer built with a focal_weight; the parameters stay as constructed."""
-        if w is None or self.focal_weight is None:
-            raise ValueError("the focal term is switched on or off at construction (focal_weight=...), not between steps")
-        w, _ = check_focal(w, self.focal_params)
-        self.focal_weight = w
-        if self._focal is not None:
-            self._focal.fill_(w)
-
-    def _lovasz_tensor(self, device):
-        if self.lovasz_weight is None:
-            return None
-        if self._lovasz is None:
-            if _capturing():
-                raise RuntimeError("the Lovasz weight tensor must exist before the step is captured")
-            self._lovasz = torch.full((1,), self.lovasz_weight, dtype=torch.float32, device=device)
-        return self._lovasz
+        self.set_loss_weight("focal", w)
 
     def set_lovasz_weight(self, w):
-        """New weight of the Lovasz-Softmax term from the next step on, in every step mode (no recapture: the kernels read it from
-        device memory).  Only for a Trainer built with a lovasz_weight; the regions stay as constructed."""
-        if w is None or self.lovasz_weight is None:
-            raise ValueError("the Lovasz term is switched on or off at construction (lovasz_weight=...), not between steps")
-        w, _, _ = check_lovasz(w, self.lovasz_regions, self.lovasz_only_present)
-        self.lovasz_weight = w
-        if self._lovasz is not None:
-            self._lovasz.fill_(w)
+        self.set_loss_weight("lovasz", w)
 
     def _finish_comm(self):
         if not self.comm:
@@ -418,10 +310,8 @@ class Trainer:
         import ctypes
         import gc
         self._static = (x.clone(), target.clone(), edge.clone())
-        self._boundary_tensor(x.device)                 # (allocated and filled outside the capture)
-        self._topk_tensor(x.device)
-        self._focal_tensor(x.device)
-        self._lovasz_tensor(x.device)
+        for term in loss_terms.TERMS:
+            self._weight_tensor(term, x.device)         # (allocated and filled outside the capture)
         want_plan = self.graph_mode == "plan"
         g = torch.cuda.CUDAGraph(keep_graph=True) if want_plan else torch.cuda.CUDAGraph()
         # No cyclic garbage collection inside the capture.  A Trainer and its model form a cycle (model.phase_callback), so an earlier

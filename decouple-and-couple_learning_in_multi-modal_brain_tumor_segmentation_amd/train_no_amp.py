@@ -11,6 +11,7 @@ What differs, deliberately: no per-iteration `.cpu()` / `.item()` / barrier + fi
 the gradient exchange is the Trainer's flat all-reduce; data comes from utils.data (the reference's `data/` package is absent).
 """
 import argparse
+import functools
 import logging
 import os
 
@@ -286,41 +287,9 @@ def check_optimizer(args):
         raise SystemExit("--warmup_steps takes a number of weight updates >= 0")
 
 
-def check_topk(args):
-    """the values of --topk_weight / --topk_percent (SystemExit with the rule, like the other checks)"""
-    if args.topk_weight is not None and not 0.0 <= args.topk_weight < float("inf"):
-        raise SystemExit("--topk_weight takes a finite weight >= 0 (leave the flag out for no top-k term)")
-    if not 0.0 < args.topk_percent <= 100.0:
-        raise SystemExit("--topk_percent takes a percentage in (0, 100]")
-    if args.topk_weight is not None and args.no_cuda:
-        raise SystemExit("--topk_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
-
-
 def focal_params_of(args):
     """the focal_params of Trainer from --tversky_* / --focal_gamma / --focal_ce_ratio"""
     return dict(fn=args.tversky_fn, fp=args.tversky_fp, exponent=args.tversky_exponent, gamma=args.focal_gamma, ce_ratio=args.focal_ce_ratio)
-
-
-def check_focal(args):
-    """the values of --focal_weight and the flags that go with it (SystemExit with the rule, like the other checks)"""
-    from cwf.trainer import check_focal as check
-    try:
-        check(args.focal_weight, focal_params_of(args))
-    except ValueError as e:
-        raise SystemExit("--focal_weight / --tversky_fn / --tversky_fp / --tversky_exponent / --focal_gamma / --focal_ce_ratio: %s" % e)
-    if args.focal_weight is not None and args.no_cuda:
-        raise SystemExit("--focal_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
-
-
-def check_lovasz(args):
-    """the values of --lovasz_weight / --lovasz_regions (SystemExit with the rule, like the other checks)"""
-    from cwf.trainer import check_lovasz as check
-    try:
-        check(args.lovasz_weight, args.lovasz_regions)
-    except ValueError as e:
-        raise SystemExit("--lovasz_weight / --lovasz_regions: %s" % e)
-    if args.lovasz_weight is not None and args.no_cuda:
-        raise SystemExit("--lovasz_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
 
 
 def boundary_weight_at(args, epoch):
@@ -331,16 +300,56 @@ def boundary_weight_at(args, epoch):
     return boundary_schedule(args.boundary_weight, epoch, args.boundary_warmup)
 
 
-def check_boundary(args):
-    """the values of --boundary_weight / --boundary_warmup (SystemExit with the rule, like the other checks)"""
-    if args.boundary_weight is not None and not 0.0 <= args.boundary_weight < float("inf"):
-        raise SystemExit("--boundary_weight takes a finite weight >= 0 (leave the flag out for no boundary term)")
+def _boundary_flags(args):
     if args.boundary_warmup < 0:
         raise SystemExit("--boundary_warmup takes a number of epochs >= 0")
     if args.boundary_warmup > 0 and args.boundary_weight is None:
         raise SystemExit("--boundary_warmup ramps --boundary_weight: give that too")
-    if args.boundary_weight is not None and args.no_cuda:
-        raise SystemExit("--boundary_weight runs on the device kernels only: it cannot be combined with --no_cuda true")
+
+
+def _topk_flags(args):
+    if not 0.0 < args.topk_percent <= 100.0:
+        raise SystemExit("--topk_percent takes a percentage in (0, 100]")
+
+
+def _trainer_check(flags, check, *values):
+    """a term whose flags are the Trainer's options: cwf.trainer.<check> on them, its ValueError as the SystemExit"""
+    import cwf.trainer
+    try:
+        getattr(cwf.trainer, check)(*values)
+    except ValueError as e:
+        raise SystemExit("%s: %s" % (flags, e))
+
+
+# per term of cwf.loss_terms.TERMS: the rules of the flags that go with --<name>_weight
+TERM_FLAGS = {
+    "boundary": _boundary_flags,
+    "topk": _topk_flags,
+    "focal": lambda args: _trainer_check("--focal_weight / --tversky_fn / --tversky_fp / --tversky_exponent / --focal_gamma / --focal_ce_ratio",
+                                         "check_focal", args.focal_weight, focal_params_of(args)),
+    "lovasz": lambda args: _trainer_check("--lovasz_weight / --lovasz_regions", "check_lovasz", args.lovasz_weight, args.lovasz_regions),
+}
+
+
+def check_loss_terms(args, only=None):
+    """the values of --<name>_weight and the flags that go with it, for every supplementary loss term or the one named (SystemExit with
+    the rule, like the other checks)"""
+    from cwf.loss_terms import TERMS
+    for term in TERMS:
+        if only not in (None, term.name):
+            continue
+        flag, weight = "--%s_weight" % term.name, getattr(args, term.name + "_weight")
+        if weight is not None and not 0.0 <= weight < float("inf"):
+            raise SystemExit("%s takes a finite weight >= 0 (leave the flag out for no %s term)" % (flag, term.title))
+        TERM_FLAGS[term.name](args)
+        if weight is not None and args.no_cuda:
+            raise SystemExit("%s runs on the device kernels only: it cannot be combined with --no_cuda true" % flag)
+
+
+check_boundary = functools.partial(check_loss_terms, only="boundary")
+check_topk = functools.partial(check_loss_terms, only="topk")
+check_focal = functools.partial(check_loss_terms, only="focal")
+check_lovasz = functools.partial(check_loss_terms, only="lovasz")
 
 
 def check_step_controls(args):
@@ -474,13 +483,11 @@ def main(argv=None):
     check_acquisition_aug(args)
     check_foreground(args)
     check_step_controls(args)
-    check_boundary(args)
-    check_topk(args)
-    check_focal(args)
-    check_lovasz(args)
+    check_loss_terms(args)
     check_optimizer(args)
     valid_subjects = check_validation(args)
     from cwf import kernels
+    from cwf.loss_terms import TERMS
     from cwf.parallel import shard_indices
     from cwf.trainer import Trainer, load_checkpoint, save_checkpoint
     from models.clswiseformer.cls_wise_former import get_cls_wise_former
@@ -528,8 +535,10 @@ def main(argv=None):
                       nesterov=args.nesterov, no_decay=args.no_decay, schedule=args.lr_schedule, warmup_steps=args.warmup_steps,
                       focal_weight=args.focal_weight, focal_params=focal_params_of(args), lovasz_weight=args.lovasz_weight,
                       lovasz_regions=args.lovasz_regions)
-    clip, use_ema, use_boundary = args.clip_grad_norm is not None, args.ema_decay is not None, args.boundary_weight is not None
-    use_topk, use_focal, use_lovasz = args.topk_weight is not None, args.focal_weight is not None, args.lovasz_weight is not None
+    clip, use_ema = args.clip_grad_norm is not None, args.ema_decay is not None
+    log_format = "Epoch: %d_Iter:%d  loss: %.5f || end_loss: %.5f || s_loss:%.4f || edge_loss:%.4f || mid_s_loss:%.4f || mid_edge_loss:%.4f ||" \
+        + "".join(" %s_loss: %%.5f ||" % t.name for t in TERMS if getattr(args, t.name + "_weight") is not None) \
+        + (" grad_norm: %.4f" if clip else "")
     if use_ema and os.path.isfile(args.resume) and args.load:
         ck = torch.load(args.resume, map_location="cpu", weights_only=True)
         if "ema_state_dict" in ck:
@@ -552,7 +561,7 @@ def main(argv=None):
     for epoch in range(args.start_epoch, args.end_epoch):
         if hasattr(ds, "set_epoch"):
             ds.set_epoch(epoch)
-        if use_boundary:
+        if args.boundary_weight is not None:            # (--boundary_warmup: the weight of this epoch)
             trainer.set_boundary_weight(boundary_weight_at(args, epoch))
         mine = shard_indices(len(ds), rank, world, epoch=epoch, shuffle=True, seed=args.seed)      # DistributedSampler semantics
         drop_last = args.step_mode != "eager" and use_cuda
@@ -574,10 +583,7 @@ def main(argv=None):
                     ev, host, tag = pending
                     ev.synchronize() if ev is not None else None
                     v = host.tolist()
-                    log.info("Epoch: %d_Iter:%d  loss: %.5f || end_loss: %.5f || s_loss:%.4f || edge_loss:%.4f || mid_s_loss:%.4f || mid_edge_loss:%.4f ||"
-                             + (" boundary_loss: %.5f ||" if use_boundary else "") + (" topk_loss: %.5f ||" if use_topk else "") + (" focal_loss: %.5f ||" if use_focal else "")
-                             + (" lovasz_loss: %.5f ||" if use_lovasz else "")
-                             + (" grad_norm: %.4f" if clip else ""), tag[0], tag[1], *v)
+                    log.info(log_format, tag[0], tag[1], *v)
                 # (grad_norm: of the last update -- inside an accumulation window that is the previous window's)
                 snap = torch.stack([loss] + list(parts) + ([trainer.opt.grad_norm] if clip else [])).float()
                 if use_cuda:

@@ -340,3 +340,34 @@ def test_trainer_with_focal_and_lovasz_on_the_regions_has_seven_parts_in_order(h
         assert abs(float(loss) - total) <= 1e-6 * abs(total)
     finally:
         kernels.set_precision("fp32")
+
+
+def test_trainer_with_all_four_supplementary_terms_has_nine_parts_in_order(hip, monkeypatch):
+    """64^3, B = 1, top-k token indices teacher-forced, dropout off, learning rate 0, one eager forward and backward with the boundary,
+    top-k, focal and Lovasz terms on together: each of the four appended parts is bit-equal to its utils.tools call on the step's own
+    main output with the same options (the forwards are deterministic; the boundary sum's float64 atomics differ by their order only
+    in bits that the one rounding to float32 drops), the four are different numbers, and the total is the sum of the nine."""
+    from cwf import kernels
+    from cwf.trainer import Trainer
+    from utils import tools
+    forced, batch = _batch()
+    seen = _record_main_output(monkeypatch)
+    kernels.set_precision("bf16x3")
+    try:
+        tr = Trainer(_no_dropout_model(forced), lr=0.0, weight_decay=0.0, boundary_weight=0.01, topk_weight=0.5, topk_percent=5.0,
+                     focal_weight=0.25, focal_params=dict(gamma=3.0), lovasz_weight=0.5, lovasz_regions="regions")
+        loss, parts = tr._fwd_bwd(*batch)
+        torch.cuda.synchronize()
+        assert len(parts) == 9 and list(seen["kw"]) == ["topk", "focal", "lovasz"]
+        out, target = seen["out"], batch[1]
+        again = [float(tools.boundary_loss(out, target, weight=0.01)), float(tools.topk_ce(out, target, percent=5.0, weight=0.5)),
+                 float(tools.focal_loss(out, target, gamma=3.0, weight=0.25)),
+                 float(tools.lovasz_softmax(out, target, posmasks=ref.REGION_MASKS, weight=0.5))]
+        got = [float(p) for p in parts[5:]]
+        print("parts 6-9 %s, tools %s" % (["%.9g" % g for g in got], ["%.9g" % a for a in again]))
+        assert got == again
+        assert len(set(got)) == 4                                                # four different numbers
+        total = sum(float(p) for p in parts)
+        assert abs(float(loss) - total) <= 1e-6 * abs(total)
+    finally:
+        kernels.set_precision("fp32")

@@ -892,31 +892,6 @@ __global__ __launch_bounds__(256 + 64 * W16D_LW) void wgrad16d_kernel(const W16d
     wgrad_dma_loader(W16dDma{a, first, G}, lds_base, wave - 4, lane, niter);
 }
 
-// what both image launchers ask of their arguments; fills the fields the two kernels share
-static int wgrad_image_args(const cwf_wgrad_args& d, W16dArgs& a) {
-  if (!d.xa16 || !d.dy16 || !d.zero16 || !d.partial || d.N <= 0 || d.Di <= 0 || d.Hi <= 0 || d.Wi <= 0) return CWF_E_BADARG;
-  if (((uintptr_t)d.xa16 & 15) || ((uintptr_t)d.dy16 & 15) || ((uintptr_t)d.zero16 & 15) || ((uintptr_t)d.partial & 15)) return CWF_E_ALIGN;
-  a.xa = (const uint4*)d.xa16; a.dy = (const uint4*)d.dy16; a.zero = (const uint4*)d.zero16; a.partial = d.partial;
-  a.N = d.N; a.D = d.Di; a.H = d.Hi; a.W = d.Wi;
-  a.tiles_d = cdiv(a.D, 4); a.tiles_h = cdiv(a.H, 4); a.tiles_w = cdiv(a.W, 16);
-  a.total_tiles = a.N * a.tiles_d * a.tiles_h * a.tiles_w;
-  return 0;
-}
-
-static int wgrad16d_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
-  W16dArgs a;
-  if (const int rc = wgrad_image_args(d, a)) return rc;
-  if ((int64_t)a.N * a.D * a.H * a.W >= (1ll << 30)) return CWF_E_TOOLARGE;
-  a.slab_floats = 28 * 256;                               // = cwf_wgrad_slab_floats(CWF_CONV3_S1, 16, 16)
-  int grid = SIDE_WGS; while (grid > 8 && grid > a.total_tiles) grid -= 8;      // multiple of 8 (XCD-aware tile map)
-  if (grid > cwf_wgrad_nsplit(CWF_CONV3_S1, a.N, a.D, a.H, a.W, 16, 16)) return CWF_E_BADARG;    // (the caller's slab buffer is sized by it)
-  CWF_MAX_LDS_ONCE((&wgrad16d_kernel));
-  hipLaunchKernelGGL(wgrad16d_kernel, dim3(grid), dim3(256 + 64 * W16D_LW), W16dDma::L::BYTES, st, a);
-  CWF_LAUNCH_CHECK();
-  if (nsplit_used) *nsplit_used = grid;
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------
 // wgrad_s1: the 3x3x3 stride-1 layers the generic kernel above used to take (32 / 64 / 128 channels; 38 launches per step, the
 // largest single item of the step's kernel time), single-bf16 operands, restructured like wgrad16_kernel.  The generic kernel
@@ -1200,29 +1175,6 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1d_kernel(const Ws1d
   }
 }
 
-static int wgrad_s1d_launch(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
-  const int Cin = d.Cin, Cout = d.Cout;
-  Ws1dArgs a;
-  if (const int rc = wgrad_image_args(d, a)) return rc;
-  if (Cin < 16 || (Cin & 15) || Cout < 32 || (Cout & 31)) return CWF_E_BADARG;
-  if ((int64_t)a.N * a.D * a.H * a.W * (Cin > Cout ? Cin : Cout) >= (1ll << 33)) return CWF_E_TOOLARGE;
-  a.Cin = Cin; a.Cout = Cout;
-  const int nchunks = Cin / 16;
-  a.ngroups = Cout / 32;
-  const int nblk = nchunks * a.ngroups;
-  a.slab_floats = (int64_t)nblk * 28 * 2 * 256;
-  if (a.slab_floats != cwf_wgrad_slab_floats(CWF_CONV3_S1, Cin, Cout)) return CWF_E_BADARG;
-  int want = SIDE_WGS / nblk; if (want < 1) want = 1; if (want > a.total_tiles) want = a.total_tiles;
-  a.tiles_per_split = cdiv(a.total_tiles, want);
-  const int splits = cdiv(a.total_tiles, a.tiles_per_split);
-  if (splits > cwf_wgrad_nsplit(CWF_CONV3_S1, a.N, a.D, a.H, a.W, Cin, Cout)) return CWF_E_BADARG;     // (the caller's slab buffer is sized by it)
-  CWF_MAX_LDS_ONCE((&wgrad_s1d_kernel));
-  hipLaunchKernelGGL(wgrad_s1d_kernel, dim3(splits, nblk), dim3(256 + 64 * WS1_LW), Ws1dDma::L::BYTES, st, a);
-  CWF_LAUNCH_CHECK();
-  if (nsplit_used) *nsplit_used = splits;
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------
 // pw_wgrad: weight gradients of the pointwise family (1x1x1 convs; ConvTranspose k = 2, s = 2), the counterpart of pw_conv_kernel
 // (conv_bf16.hip).  dW[ci][co] = sum_vox xa[vox][ci] * dy[vox][co] is a skinny product over a pure stream -- x and dy are each read
@@ -1366,38 +1318,117 @@ __global__ __launch_bounds__((64 * PwgCfg<NCH, NTL, NCLS>::WAVES)) void pw_wgrad
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// host side: ONE plan per descriptor.  wgrad_bf16_plan makes every decision of a bf16-form weight-gradient launch -- argument
+// checks, kernel instance, grid, tile walk, slabs written -- and fills the kernels' argument structs; wgrad_bf16_launch only
+// launches what the plan says, and cwf_debug_wgrad_bf16_plan reports the same plan without launching (include/cwf_hip.h).
+// The split-K plan agrees with wgrad_mfma.hip's: the caller sized the slab buffer through cwf_wgrad_nsplit / cwf_wgrad_slab_floats.
+// ---------------------------------------------------------------------------------------------------
+struct WgBf16Plan {
+  int id;                                                 // enum cwf_wgrad_bf16_instance
+  int gx, gy, gz, threads;
+  size_t lds;
+  int walk, walk_step, waves;                             // CWF_WGB_WALK_*; tiles_per_split / grid / groups per wave; waves sharing a pw walk
+  int items, items_lo, items_hi;                          // tiles (pw: 4-voxel groups per sample) in all; fewest / most per workgroup
+  int64_t slab;
+  int nsplit_used;
+  int exact;                                              // 1: exact fp32 products (pw_wgrad_kernel), 0: bf16 operands
+  WgArgsB a; PwWgWork wk; int CG;                         // arguments of the fp32-tensor kernels
+  Ws1dArgs ad;                                            // ... of the bf16-image kernels (wgrad16d_kernel takes its W16dArgs part)
+};
+
+// contiguous ranges of `tps` tiles over `total`: grid x, fewest / most tiles of a workgroup
+static void wg_plan_ranges(WgBf16Plan& p, int splits, int tps, int total) {
+  p.walk = CWF_WGB_WALK_RANGES; p.walk_step = tps; p.waves = 0; p.items = total;
+  p.items_hi = tps < total ? tps : total; p.items_lo = total - (splits - 1) * tps;
+}
+// the XCD-aware strided walk of the 16 -> 16 kernels over `grid` workgroups
+static void wg_plan_strided(WgBf16Plan& p, int grid, int total) {
+  p.walk = CWF_WGB_WALK_STRIDED; p.walk_step = grid; p.waves = 0; p.items = total;
+  p.items_lo = total / grid; p.items_hi = cdiv(total, grid);
+}
+
+// what both image kernels ask of their arguments; fills the fields the two kernels share
+static int wgrad_image_args(const cwf_wgrad_args& d, W16dArgs& a) {
+  if (!d.xa16 || !d.dy16 || !d.zero16 || !d.partial || d.N <= 0 || d.Di <= 0 || d.Hi <= 0 || d.Wi <= 0) return CWF_E_BADARG;
+  if (((uintptr_t)d.xa16 & 15) || ((uintptr_t)d.dy16 & 15) || ((uintptr_t)d.zero16 & 15) || ((uintptr_t)d.partial & 15)) return CWF_E_ALIGN;
+  a.xa = (const uint4*)d.xa16; a.dy = (const uint4*)d.dy16; a.zero = (const uint4*)d.zero16; a.partial = d.partial;
+  a.N = d.N; a.D = d.Di; a.H = d.Hi; a.W = d.Wi;
+  a.tiles_d = cdiv(a.D, 4); a.tiles_h = cdiv(a.H, 4); a.tiles_w = cdiv(a.W, 16);
+  a.total_tiles = a.N * a.tiles_d * a.tiles_h * a.tiles_w;
+  return 0;
+}
+
+static int wgrad16d_plan(const cwf_wgrad_args& d, WgBf16Plan& p) {
+  W16dArgs& a = p.ad;
+  if (const int rc = wgrad_image_args(d, a)) return rc;
+  if ((int64_t)a.N * a.D * a.H * a.W >= (1ll << 30)) return CWF_E_TOOLARGE;
+  a.slab_floats = 28 * 256;                               // = cwf_wgrad_slab_floats(CWF_CONV3_S1, 16, 16)
+  int grid = SIDE_WGS; while (grid > 8 && grid > a.total_tiles) grid -= 8;      // multiple of 8 (XCD-aware tile map)
+  if (grid > cwf_wgrad_nsplit(CWF_CONV3_S1, a.N, a.D, a.H, a.W, 16, 16)) return CWF_E_BADARG;    // (the caller's slab buffer is sized by it)
+  p.id = CWF_WGB_WGRAD16D; p.gx = grid; p.gy = 1; p.gz = 1; p.threads = 256 + 64 * W16D_LW; p.lds = W16dDma::L::BYTES;
+  wg_plan_strided(p, grid, a.total_tiles);
+  p.slab = a.slab_floats; p.nsplit_used = grid; p.exact = 0;
+  return 0;
+}
+
+static int wgrad_s1d_plan(const cwf_wgrad_args& d, WgBf16Plan& p) {
+  const int Cin = d.Cin, Cout = d.Cout;
+  Ws1dArgs& a = p.ad;
+  if (const int rc = wgrad_image_args(d, a)) return rc;
+  if (Cin < 16 || (Cin & 15) || Cout < 32 || (Cout & 31)) return CWF_E_BADARG;
+  if ((int64_t)a.N * a.D * a.H * a.W * (Cin > Cout ? Cin : Cout) >= (1ll << 33)) return CWF_E_TOOLARGE;
+  a.Cin = Cin; a.Cout = Cout;
+  const int nchunks = Cin / 16;
+  a.ngroups = Cout / 32;
+  const int nblk = nchunks * a.ngroups;
+  a.slab_floats = (int64_t)nblk * 28 * 2 * 256;
+  if (a.slab_floats != cwf_wgrad_slab_floats(CWF_CONV3_S1, Cin, Cout)) return CWF_E_BADARG;
+  int want = SIDE_WGS / nblk; if (want < 1) want = 1; if (want > a.total_tiles) want = a.total_tiles;
+  a.tiles_per_split = cdiv(a.total_tiles, want);
+  const int splits = cdiv(a.total_tiles, a.tiles_per_split);
+  if (splits > cwf_wgrad_nsplit(CWF_CONV3_S1, a.N, a.D, a.H, a.W, Cin, Cout)) return CWF_E_BADARG;     // (the caller's slab buffer is sized by it)
+  p.id = CWF_WGB_S1D; p.gx = splits; p.gy = nblk; p.gz = 1; p.threads = 256 + 64 * WS1_LW; p.lds = Ws1dDma::L::BYTES;
+  wg_plan_ranges(p, splits, a.tiles_per_split, a.total_tiles);
+  p.slab = a.slab_floats; p.nsplit_used = splits; p.exact = 0;
+  return 0;
+}
+
+// pointwise stream kernel <NCH, NTL, NCLS>: false when the workspace (max_slabs slabs) cannot hold one slab per sample
 template <int NCH, int NTL, int NCLS>
-static int launch_pw_wgrad(const WgArgsB& a, int CG, int max_slabs, int* nsplit_used, hipStream_t st) {
-  const ConvGeom& g = a.g;
-  PwWgWork wk;
+static bool pw_wgrad_plan(WgBf16Plan& p, int id, int max_slabs) {
+  const ConvGeom& g = p.a.g;
+  PwWgWork& wk = p.wk;
   wk.Vin = g.Di * g.Hi * g.Wi;
   wk.gps = wk.Vin >> 2;
   int wps = SIDE_WGS / g.N; if (wps < 1) wps = 1;        // ~one 8/16-wave workgroup per CU in all, each inside one sample
   if (wps * g.N > max_slabs) wps = max_slabs / g.N;
-  if (wps < 1) return -1;
+  if (wps < 1) return false;
   constexpr int PWG_WAVES = PwgCfg<NCH, NTL, NCLS>::WAVES;
   const int maxw = cdiv(wk.gps, PWG_WAVES * 8);
   if (wps > maxw) wps = maxw;
   wk.gpw = cdiv(wk.gps, wps * PWG_WAVES);
   wk.wps = cdiv(wk.gps, wk.gpw * PWG_WAVES);
-  hipLaunchKernelGGL((pw_wgrad_kernel<NCH, NTL, NCLS>), dim3((unsigned)(wk.wps * g.N)), dim3(64 * PWG_WAVES), 0, st, a, wk, CG);
-  CWF_LAUNCH_CHECK();
-  if (nsplit_used) *nsplit_used = wk.wps * g.N;
-  return 0;
+  p.id = id; p.gx = wk.wps * g.N; p.gy = 1; p.gz = 1; p.threads = 64 * PWG_WAVES; p.lds = 0;
+  p.walk = CWF_WGB_WALK_PW; p.walk_step = wk.gpw; p.waves = PWG_WAVES; p.items = wk.gps;
+  p.items_hi = wk.gps < wk.gpw * PWG_WAVES ? wk.gps : wk.gpw * PWG_WAVES;
+  p.items_lo = wk.gps - (wk.wps - 1) * wk.gpw * PWG_WAVES;
+  p.nsplit_used = wk.wps * g.N; p.exact = 1;
+  return true;
 }
 
-// The generic split-bf16 slab kernels (tiled, persistent 16-channel, pointwise stream, producer / consumer).  The plan makes the same
-// decisions as wgrad_mfma.hip's: the caller sized the slab buffer through cwf_wgrad_nsplit / cwf_wgrad_slab_floats.
-static int wgrad_bf16_impl(const cwf_wgrad_args& d, int* nsplit_used, hipStream_t st) {
+// The fp32-tensor kernels (tiled, persistent 16-channel, pointwise stream, producer / consumer), grouped launches included.
+static int wgrad_tensor_plan(const cwf_wgrad_args& d, WgBf16Plan& p) {
   const int op = d.op, x3 = d.precision == CWF_BF16X3, groups = d.groups, N = d.N, Cin = d.Cin, Cout = d.Cout;
   const int Di = d.Di, Hi = d.Hi, Wi = d.Wi, Do = d.Do, Ho = d.Ho, Wo = d.Wo, x_ldc = d.x_ldc, dy_ldc = d.dy_ldc;
   // a grouped launch passes group 0's views through the plain fields
   const float* x = groups ? d.x_g[0] : d.x; const float* dy = groups ? d.dy_g[0] : d.dy; float* partial = groups ? d.partial_g[0] : d.partial;
   const float* in_scale = d.in_scale; const float* dy_scale = d.dy_scale;
   if (!x || !dy || !partial || N <= 0) return CWF_E_BADARG;
-  // dy_scale is implemented by wgrad16_kernel alone
-  if (dy_scale && !(!groups && op == CWF_CONV3_S1 && Cin <= 16 && Cout == 16 && (dy_ldc & 3) == 0 && (((uintptr_t)dy) & 15) == 0 && (int64_t)Do * Ho * Wo >= 32768))
-    return CWF_E_BADARG;
+  // full-resolution 16-channel layers: persistent producer/consumer kernel (wgrad16_kernel), the only one that implements dy_scale
+  const bool full16 = !groups && op == CWF_CONV3_S1 && Cin <= 16 && Cout == 16 && (dy_ldc & 3) == 0 && (((uintptr_t)dy) & 15) == 0 &&
+                      (int64_t)Do * Ho * Wo >= 32768;
+  if (dy_scale && !full16) return CWF_E_BADARG;
   if ((Cin & 3) || (x_ldc & 3) || ((uintptr_t)x & 15) || ((uintptr_t)partial & 15)) return CWF_E_ALIGN;
   if (in_scale && !d.in_shift) return CWF_E_BADARG;
   if (!(op == CWF_CONV3_S1 || op == CWF_CONV3_S2 || op == CWF_CONV1 || op == CWF_CONVT2)) return CWF_E_BADARG;
@@ -1405,7 +1436,7 @@ static int wgrad_bf16_impl(const cwf_wgrad_args& d, int* nsplit_used, hipStream_
   const int MTOT = (op == CWF_CONV3_S2) ? 4 : 16;
   const int nt_all = cdiv(Cout, 16);
   const int CG = tapsplit ? (nt_all == 1 ? 1 : 2) : (nt_all == 1 ? 1 : (nt_all == 2 ? 2 : 4));
-  WgArgsB a;
+  WgArgsB& a = p.a;
   int rc = cwf_build_geom(a.g, op, N, Di, Hi, Wi, Cin, x_ldc, Do, Ho, Wo, Cout, dy_ldc, MTOT);
   if (rc) return rc;
   const int nchunks = a.g.nchunks, ncls = a.g.ncls, ngroups = cdiv(a.g.ntiles, CG);
@@ -1428,22 +1459,15 @@ static int wgrad_bf16_impl(const cwf_wgrad_args& d, int* nsplit_used, hipStream_
     a.partial_g[q] = (groups && q < groups) ? d.partial_g[q] : nullptr;
     if (groups && q < groups && (((uintptr_t)d.dy_g[q]) & 15)) dy_al = false;
   }
-  const int gz = groups ? groups : ncls;                 // grid z: group (grouped launches are single-class) or parity class
-  if (nsplit_used) *nsplit_used = tapsplit ? wg_splits : wg_splits * 4;
-  if (!groups && op == CWF_CONV3_S1 && Cin <= 16 && Cout == 16 && (dy_ldc & 3) == 0 && (((uintptr_t)dy) & 15) == 0 && (int64_t)Do * Ho * Wo >= 32768) {
-    // full-resolution 16-channel layers: persistent producer/consumer kernel, one slab per workgroup (<= 256 <= generic nsplit)
+  p.CG = CG; p.slab = a.slab_floats; p.exact = 0;
+  if (full16) {
+    // one slab per workgroup (<= 256 <= generic nsplit)
     // (the stem layer -- 4 input channels -- is the LAST kernel of backward: nothing runs beside it, it takes every CU)
     int grid = Cin <= 4 ? 256 : SIDE_WGS; while (grid > 8 && grid > total) grid -= 8;      // multiple of 8 (XCD-aware tile map)
-    const size_t lds16 = x3 ? W16Lds<true, false>::BYTES : W16Lds<false, false>::BYTES;
-    if (x3) {
-      CWF_MAX_LDS_ONCE((&wgrad16_kernel<true>));
-      hipLaunchKernelGGL((wgrad16_kernel<true>), dim3(grid), dim3(256 + 64 * W16_LW), lds16, st, a, total);
-    } else {
-      CWF_MAX_LDS_ONCE((&wgrad16_kernel<false>));
-      hipLaunchKernelGGL((wgrad16_kernel<false>), dim3(grid), dim3(256 + 64 * W16_LW), lds16, st, a, total);
-    }
-    CWF_LAUNCH_CHECK();
-    if (nsplit_used) *nsplit_used = grid;
+    p.id = x3 ? CWF_WGB_WGRAD16_X3 : CWF_WGB_WGRAD16; p.gx = grid; p.gy = 1; p.gz = 1; p.threads = 256 + 64 * W16_LW;
+    p.lds = x3 ? W16Lds<true, false>::BYTES : W16Lds<false, false>::BYTES;
+    wg_plan_strided(p, grid, total);
+    p.nsplit_used = grid;
     return 0;
   }
   if (!groups && (op == CWF_CONV1 || op == CWF_CONVT2) && ((int64_t)Di * Hi * Wi & 3) == 0 && (op == CWF_CONV1 || (Wi & 3) == 0) &&
@@ -1451,17 +1475,17 @@ static int wgrad_bf16_impl(const cwf_wgrad_args& d, int* nsplit_used, hipStream_
     // pointwise layers: stream kernel (fp32 MFMA straight from global memory, every operand read once), both precision modes
     const int nch = nchunks, ntl = a.g.ntiles;
     const int max_slabs = wg_splits * 4;                  // what the workspace was sized for
-    int r = -2;
+    bool ok = false;
     if (op == CWF_CONV1) {
-      if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 1>(a, CG, max_slabs, nsplit_used, st);
-      else if (nch == 2 && ntl == 1) r = launch_pw_wgrad<2, 1, 1>(a, CG, max_slabs, nsplit_used, st);
-      else if (nch == 4 && ntl == 2) r = launch_pw_wgrad<4, 2, 1>(a, CG, max_slabs, nsplit_used, st);
-      else if (nch == 8 && ntl == 4) r = launch_pw_wgrad<8, 4, 1>(a, CG, max_slabs, nsplit_used, st);
+      if (nch == 1 && ntl == 1) ok = pw_wgrad_plan<1, 1, 1>(p, CWF_WGB_PW_1_1_1, max_slabs);
+      else if (nch == 2 && ntl == 1) ok = pw_wgrad_plan<2, 1, 1>(p, CWF_WGB_PW_2_1_1, max_slabs);
+      else if (nch == 4 && ntl == 2) ok = pw_wgrad_plan<4, 2, 1>(p, CWF_WGB_PW_4_2_1, max_slabs);
+      else if (nch == 8 && ntl == 4) ok = pw_wgrad_plan<8, 4, 1>(p, CWF_WGB_PW_8_4_1, max_slabs);
     } else {
-      if (nch == 1 && ntl == 1) r = launch_pw_wgrad<1, 1, 8>(a, CG, max_slabs, nsplit_used, st);
-      else if (nch == 2 && ntl == 2) r = launch_pw_wgrad<2, 2, 8>(a, CG, max_slabs, nsplit_used, st);
+      if (nch == 1 && ntl == 1) ok = pw_wgrad_plan<1, 1, 8>(p, CWF_WGB_PW_1_1_8, max_slabs);
+      else if (nch == 2 && ntl == 2) ok = pw_wgrad_plan<2, 2, 8>(p, CWF_WGB_PW_2_2_8, max_slabs);
     }
-    if (r >= 0) return r;
+    if (ok) return 0;
   }
   if (!x3 && op == CWF_CONV3_S1 && CG <= 2 && a.g.TD == 4 && a.g.TH == 4 && a.g.ID == 6 && a.g.IH == 6 && a.g.IW == 18 && (Cout & 3) == 0 &&
       (dy_ldc & 3) == 0 && dy_al) {
@@ -1470,50 +1494,114 @@ static int wgrad_bf16_impl(const cwf_wgrad_args& d, int* nsplit_used, hipStream_
     const int tps1 = cdiv(total, want1), splits1 = cdiv(total, tps1);
     if (splits1 <= wg_splits) {                          // (the workspace was sized for wg_splits slabs)
       a.tiles_per_split = tps1;
-      if (nsplit_used) *nsplit_used = splits1;
-      const size_t lds1 = CG == 1 ? Ws1Lds<1, false>::BYTES : Ws1Lds<2, false>::BYTES;
-      dim3 grid1(splits1, nchunks * ngroups, groups ? groups : 1);
-      CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<1>));
-      CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<2>));
-      if (CG == 1) hipLaunchKernelGGL((wgrad_s1_kernel<1>), grid1, dim3(256 + 64 * WS1_LW), lds1, st, a);
-      else hipLaunchKernelGGL((wgrad_s1_kernel<2>), grid1, dim3(256 + 64 * WS1_LW), lds1, st, a);
-      CWF_LAUNCH_CHECK();
+      p.id = CG == 1 ? CWF_WGB_S1_1 : CWF_WGB_S1_2; p.gx = splits1; p.gy = nchunks * ngroups; p.gz = groups ? groups : 1;
+      p.threads = 256 + 64 * WS1_LW; p.lds = CG == 1 ? Ws1Lds<1, false>::BYTES : Ws1Lds<2, false>::BYTES;
+      wg_plan_ranges(p, splits1, tps1, total);
+      p.nsplit_used = splits1;
       return 0;
     }
   }
   const size_t ximg = (size_t)a.g.ID * a.g.IH * wg_x_pitch(a.g.IW, a.g.is) * 16;
   const size_t dimg = (size_t)a.g.TD * a.g.TH * wg_dy_pitch(CG * 16) * CG * 16 + (size_t)(a.g.TD * a.g.TH / 2 + 1) * wg_dy_skew(CG * 16);
-  const size_t lds = (ximg + dimg) * sizeof(unsigned short) * (x3 ? 2 : 1);
-  if (lds > 160 * 1024) return CWF_E_TOOLARGE;
-  dim3 grid(wg_splits, nchunks * ngroups, gz);
-#define CWF_WG(tpw, ntw, ts, xx) do { CWF_MAX_LDS_ONCE((&wgrad_bf16_kernel<tpw, ntw, ts, xx>)); \
-    hipLaunchKernelGGL((wgrad_bf16_kernel<tpw, ntw, ts, xx>), grid, dim3(256), lds, st, a); } while (0)
-#define CWF_WGX(tpw, ntw, ts) do { if (x3) CWF_WG(tpw, ntw, ts, true); else CWF_WG(tpw, ntw, ts, false); } while (0)
-  if (tapsplit) { if (CG == 1) CWF_WGX(7, 1, true); else CWF_WGX(7, 2, true); }
-  else { if (CG == 1) CWF_WGX(2, 1, false); else if (CG == 2) CWF_WGX(2, 2, false); else CWF_WGX(2, 4, false); }
-#undef CWF_WGX
-#undef CWF_WG
-  CWF_LAUNCH_CHECK();
+  p.lds = (ximg + dimg) * sizeof(unsigned short) * (x3 ? 2 : 1);
+  if (p.lds > 160 * 1024) return CWF_E_TOOLARGE;
+  if (tapsplit) p.id = (CG == 1 ? CWF_WGB_TILED_7_1 : CWF_WGB_TILED_7_2) + x3;
+  else p.id = (CG == 1 ? CWF_WGB_TILED_2_1 : (CG == 2 ? CWF_WGB_TILED_2_2 : CWF_WGB_TILED_2_4)) + x3;
+  p.gx = wg_splits; p.gy = nchunks * ngroups; p.gz = groups ? groups : ncls;     // grid z: group (grouped launches are single-class) or parity class
+  p.threads = 256;
+  wg_plan_ranges(p, wg_splits, tps, total);
+  p.nsplit_used = tapsplit ? wg_splits : wg_splits * 4;  // (the 1-tap kernel: every wave writes its own slab)
   return 0;
 }
 
-// The one place that chooses a weight-gradient slab kernel (include/cwf_hip.h, struct cwf_wgrad_args).
-extern "C" int cwf_wgrad(const struct cwf_wgrad_args* args, int* nsplit_used, void* stream) {
-  if (!args) return CWF_E_BADARG;
-  const cwf_wgrad_args& d = *args;
+// The one place that chooses a bf16-form weight-gradient slab kernel (include/cwf_hip.h, struct cwf_wgrad_args).
+static int wgrad_bf16_plan(const cwf_wgrad_args& d, WgBf16Plan& p) {
   if (d.precision != CWF_FP32 && d.precision != CWF_BF16X3 && d.precision != CWF_BF16) return CWF_E_BADARG;
-  hipStream_t st = cwf_stream(stream);
   if (d.xa16 || d.dy16) {                                  // bf16 operand images (x, dy and x's prologue are not read)
     if (!d.xa16 || !d.dy16 || d.precision != CWF_BF16 || d.op != CWF_CONV3_S1 || d.groups || d.dy_scale) return CWF_E_BADARG;
-    if (d.Cin == 16 && d.Cout == 16 && (int64_t)d.Do * d.Ho * d.Wo >= 32768) return wgrad16d_launch(d, nsplit_used, st);
-    return wgrad_s1d_launch(d, nsplit_used, st);
+    if (d.Cin == 16 && d.Cout == 16 && (int64_t)d.Do * d.Ho * d.Wo >= 32768) return wgrad16d_plan(d, p);
+    return wgrad_s1d_plan(d, p);
   }
   if (d.groups) {
     if (d.groups < 2 || d.groups > 3 || d.op != CWF_CONV3_S1 || d.precision == CWF_FP32 || d.in_scale || d.dy_scale) return CWF_E_BADARG;
     for (int q = 0; q < d.groups; ++q)
       if (!d.x_g[q] || !d.dy_g[q] || !d.partial_g[q] || ((uintptr_t)d.x_g[q] & 15) || ((uintptr_t)d.partial_g[q] & 15)) return CWF_E_ALIGN;
-    return wgrad_bf16_impl(d, nsplit_used, st);
+    return wgrad_tensor_plan(d, p);
   }
-  if (d.precision == CWF_FP32) return d.dy_scale ? CWF_E_BADARG : wgrad_fp32_launch(d, nsplit_used, st);
-  return wgrad_bf16_impl(d, nsplit_used, st);
+  if (d.precision == CWF_FP32) return CWF_E_BADARG;       // (cwf_wgrad: wgrad_fp32_launch, wgrad_mfma.hip)
+  return wgrad_tensor_plan(d, p);
+}
+
+static int wgrad_bf16_launch(const WgBf16Plan& p, int* nsplit_used, hipStream_t st) {
+  const dim3 grid(p.gx, p.gy, p.gz), block(p.threads);
+#define CWF_WGK(id_, ...) case id_: CWF_MAX_LDS_ONCE((&__VA_ARGS__)); hipLaunchKernelGGL((__VA_ARGS__), grid, block, p.lds, st, p.a); break
+#define CWF_WGP(id_, ...) case id_: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, p.a, p.wk, p.CG); break
+  switch (p.id) {
+    case CWF_WGB_WGRAD16: CWF_MAX_LDS_ONCE((&wgrad16_kernel<false>)); hipLaunchKernelGGL((wgrad16_kernel<false>), grid, block, p.lds, st, p.a, p.a.total_tiles); break;
+    case CWF_WGB_WGRAD16_X3: CWF_MAX_LDS_ONCE((&wgrad16_kernel<true>)); hipLaunchKernelGGL((wgrad16_kernel<true>), grid, block, p.lds, st, p.a, p.a.total_tiles); break;
+    CWF_WGP(CWF_WGB_PW_1_1_1, pw_wgrad_kernel<1, 1, 1>);
+    CWF_WGP(CWF_WGB_PW_2_1_1, pw_wgrad_kernel<2, 1, 1>);
+    CWF_WGP(CWF_WGB_PW_4_2_1, pw_wgrad_kernel<4, 2, 1>);
+    CWF_WGP(CWF_WGB_PW_8_4_1, pw_wgrad_kernel<8, 4, 1>);
+    CWF_WGP(CWF_WGB_PW_1_1_8, pw_wgrad_kernel<1, 1, 8>);
+    CWF_WGP(CWF_WGB_PW_2_2_8, pw_wgrad_kernel<2, 2, 8>);
+    case CWF_WGB_S1_1: case CWF_WGB_S1_2:
+      CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<1>));
+      CWF_MAX_LDS_ONCE((&wgrad_s1_kernel<2>));
+      if (p.id == CWF_WGB_S1_1) hipLaunchKernelGGL((wgrad_s1_kernel<1>), grid, block, p.lds, st, p.a);
+      else hipLaunchKernelGGL((wgrad_s1_kernel<2>), grid, block, p.lds, st, p.a);
+      break;
+    CWF_WGK(CWF_WGB_TILED_7_1, wgrad_bf16_kernel<7, 1, true, false>);
+    CWF_WGK(CWF_WGB_TILED_7_1_X3, wgrad_bf16_kernel<7, 1, true, true>);
+    CWF_WGK(CWF_WGB_TILED_7_2, wgrad_bf16_kernel<7, 2, true, false>);
+    CWF_WGK(CWF_WGB_TILED_7_2_X3, wgrad_bf16_kernel<7, 2, true, true>);
+    CWF_WGK(CWF_WGB_TILED_2_1, wgrad_bf16_kernel<2, 1, false, false>);
+    CWF_WGK(CWF_WGB_TILED_2_1_X3, wgrad_bf16_kernel<2, 1, false, true>);
+    CWF_WGK(CWF_WGB_TILED_2_2, wgrad_bf16_kernel<2, 2, false, false>);
+    CWF_WGK(CWF_WGB_TILED_2_2_X3, wgrad_bf16_kernel<2, 2, false, true>);
+    CWF_WGK(CWF_WGB_TILED_2_4, wgrad_bf16_kernel<2, 4, false, false>);
+    CWF_WGK(CWF_WGB_TILED_2_4_X3, wgrad_bf16_kernel<2, 4, false, true>);
+    case CWF_WGB_WGRAD16D:
+      CWF_MAX_LDS_ONCE((&wgrad16d_kernel));
+      hipLaunchKernelGGL(wgrad16d_kernel, grid, block, p.lds, st, static_cast<const W16dArgs&>(p.ad));
+      break;
+    case CWF_WGB_S1D: CWF_MAX_LDS_ONCE((&wgrad_s1d_kernel)); hipLaunchKernelGGL(wgrad_s1d_kernel, grid, block, p.lds, st, p.ad); break;
+    default: return CWF_E_BADARG;
+  }
+#undef CWF_WGP
+#undef CWF_WGK
+  CWF_LAUNCH_CHECK();
+  if (nsplit_used) *nsplit_used = p.nsplit_used;
+  return 0;
+}
+
+extern "C" int cwf_wgrad(const struct cwf_wgrad_args* args, int* nsplit_used, void* stream) {
+  if (!args) return CWF_E_BADARG;
+  const cwf_wgrad_args& d = *args;
+  if (d.precision != CWF_FP32 && d.precision != CWF_BF16X3 && d.precision != CWF_BF16) return CWF_E_BADARG;
+  hipStream_t st = cwf_stream(stream);
+  if (d.precision == CWF_FP32 && !d.xa16 && !d.dy16 && !d.groups) return d.dy_scale ? CWF_E_BADARG : wgrad_fp32_launch(d, nsplit_used, st);
+  WgBf16Plan p;
+  if (const int rc = wgrad_bf16_plan(d, p)) return rc;
+  return wgrad_bf16_launch(p, nsplit_used, st);
+}
+
+extern "C" int cwf_debug_wgrad_bf16_plan(const struct cwf_wgrad_args* args, int64_t* out) {
+  if (!args || !out) return CWF_E_BADARG;
+  WgBf16Plan p;
+  if (const int rc = wgrad_bf16_plan(*args, p)) return rc;
+  const bool pw = p.walk == CWF_WGB_WALK_PW;
+  const int64_t v[CWF_WGB_PLAN_FIELDS] = {p.id, p.gx, p.gy, p.gz, p.threads, p.walk, p.walk_step, pw ? p.wk.wps : 0, p.waves, p.items,
+                                          p.slab, p.nsplit_used, p.exact, p.items_lo, p.items_hi};
+  for (int i = 0; i < CWF_WGB_PLAN_FIELDS; ++i) out[i] = v[i];
+  return 0;
+}
+
+extern "C" const char* cwf_debug_wgrad_bf16_name(int instance) {
+  static const char* const names[CWF_WGB_COUNT] = {
+    "wgrad16", "wgrad16_x3", "pw_wgrad<1,1,1>", "pw_wgrad<2,1,1>", "pw_wgrad<4,2,1>", "pw_wgrad<8,4,1>", "pw_wgrad<1,1,8>", "pw_wgrad<2,2,8>",
+    "wgrad_s1<1>", "wgrad_s1<2>", "wgrad_bf16<7,1,ts>", "wgrad_bf16<7,1,ts,x3>", "wgrad_bf16<7,2,ts>", "wgrad_bf16<7,2,ts,x3>",
+    "wgrad_bf16<2,1>", "wgrad_bf16<2,1,x3>", "wgrad_bf16<2,2>", "wgrad_bf16<2,2,x3>", "wgrad_bf16<2,4>", "wgrad_bf16<2,4,x3>",
+    "wgrad16d", "wgrad_s1d"};
+  return (instance >= 0 && instance < CWF_WGB_COUNT) ? names[instance] : nullptr;
 }

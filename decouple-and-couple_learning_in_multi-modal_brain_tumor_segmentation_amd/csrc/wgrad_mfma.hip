@@ -131,25 +131,29 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(const WgArgs a) {
   }
 }
 
-// Sum the slabs in SLAB order (every load is a coalesced 16-B read; the nsplit loads of a thread are independent and
-// pipeline) and scatter the 4 sums through the inverse map: inv >= 0 -> dW index, inv <= -2 -> bias index (-2 - inv),
-// -1 -> padding.  Fixed summation order: bitwise reproducible.
+// Sum the slabs (every load is a coalesced 16-B read; the loads of a thread are independent and pipeline) and scatter the 4 sums
+// through the inverse map: inv >= 0 -> dW index, inv <= -2 -> bias index (-2 - inv), -1 -> padding.  Fixed summation order, the
+// one of wgrad_reduce_batched_kernel below -- four partial sums over the slabs k = l, l + 4, l + 8, ... (l = 0..3, each in rising
+// k), combined as (s0 + s1) + (s2 + s3) -- so a layer's gradient is the same bits whichever reduce entry point sums its slabs.
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, int nsplit, int64_t slab,
                                                           const int32_t* __restrict__ inv, float* __restrict__ dW, float* __restrict__ db) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // float4 index inside the slab
   if (q * 4 >= slab) return;
   const float4* p = reinterpret_cast<const float4*>(partial) + q;
   const int64_t stride4 = slab >> 2;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 l0 = make_float4(0.f, 0.f, 0.f, 0.f), l1 = l0, l2 = l0, l3 = l0;
   int k = 0;
   for (; k + 4 <= nsplit; k += 4) {
     const float4 a0 = p[(int64_t)k * stride4], a1 = p[(int64_t)(k + 1) * stride4], a2 = p[(int64_t)(k + 2) * stride4], a3 = p[(int64_t)(k + 3) * stride4];
-    s.x += a0.x; s.y += a0.y; s.z += a0.z; s.w += a0.w;
-    s.x += a1.x; s.y += a1.y; s.z += a1.z; s.w += a1.w;
-    s.x += a2.x; s.y += a2.y; s.z += a2.z; s.w += a2.w;
-    s.x += a3.x; s.y += a3.y; s.z += a3.z; s.w += a3.w;
+    l0.x += a0.x; l0.y += a0.y; l0.z += a0.z; l0.w += a0.w;
+    l1.x += a1.x; l1.y += a1.y; l1.z += a1.z; l1.w += a1.w;
+    l2.x += a2.x; l2.y += a2.y; l2.z += a2.z; l2.w += a2.w;
+    l3.x += a3.x; l3.y += a3.y; l3.z += a3.z; l3.w += a3.w;
   }
-  for (; k < nsplit; ++k) { const float4 a0 = p[(int64_t)k * stride4]; s.x += a0.x; s.y += a0.y; s.z += a0.z; s.w += a0.w; }
+  if (k < nsplit) { const float4 a0 = p[(int64_t)k * stride4]; l0.x += a0.x; l0.y += a0.y; l0.z += a0.z; l0.w += a0.w; }
+  if (k + 1 < nsplit) { const float4 a1 = p[(int64_t)(k + 1) * stride4]; l1.x += a1.x; l1.y += a1.y; l1.z += a1.z; l1.w += a1.w; }
+  if (k + 2 < nsplit) { const float4 a2 = p[(int64_t)(k + 2) * stride4]; l2.x += a2.x; l2.y += a2.y; l2.z += a2.z; l2.w += a2.w; }
+  const float4 s = make_float4((l0.x + l1.x) + (l2.x + l3.x), (l0.y + l1.y) + (l2.y + l3.y), (l0.z + l1.z) + (l2.z + l3.z), (l0.w + l1.w) + (l2.w + l3.w));
   const int4 m = reinterpret_cast<const int4*>(inv)[q];
   const int mm[4] = {m.x, m.y, m.z, m.w};
   const float ss[4] = {s.x, s.y, s.z, s.w};

@@ -24,6 +24,8 @@ SIGNATURES = {
     "cwf_debug_wsd": [I],
     "cwf_debug_wsd_launches": [],
     "cwf_wgrad": [P, P, P],
+    "cwf_debug_wgrad_bf16_plan": [P, P],
+    "cwf_debug_wgrad_bf16_name": [I],              # returns const char* (restype set in load())
     "cwf_gather_split_bf16": [P, I, L, P],
     "cwf_wgrad_nsplit": [I, I, I, I, I, I, I],
     "cwf_wgrad_partial_floats": [I, I, I, I, I, I, I],
@@ -342,6 +344,7 @@ def load():
     lib.cwf_arch.argtypes = []
     lib.cwf_plan_last_error.restype = C.c_char_p
     lib.cwf_plan_last_error.argtypes = []
+    lib.cwf_debug_wgrad_bf16_name.restype = C.c_char_p
     _lib = lib
     return lib
 

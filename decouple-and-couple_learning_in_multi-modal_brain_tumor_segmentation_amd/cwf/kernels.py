@@ -599,6 +599,10 @@ class HipBackend:
         G = len(keys)
         x0, x_ldc = cl(xs[0])
         d0, dy_ldc = cl(dys[0])
+        if any(cl(t)[0].data_ptr() != t.data_ptr() for t in list(xs) + list(dys)):
+            # the launch takes every group's own pointer with ONE row pitch: a view that cl() has to copy cannot be sent
+            raise _lib.CwfError("wgrad_to_grouped needs group views the kernels can read in place (channels-last, 16-byte aligned "
+                                "starts, a row pitch that is a multiple of 4)")
         n, di, hi, wi, cin = x0.shape
         _, do, ho, wo, _ = d0.shape
         nsplit, slab = self._wgrad_plan(op, d0.shape, cin, cout, inv_maps)

@@ -108,7 +108,9 @@ long long cwf_debug_wsd_launches(void);
 /* Weight gradient (+ bias gradient) of the same family (op in {CONV3_S1, CONV3_S2, CONV1, CONVT2}):
  *   dW[tap][ci][co] = sum_{n,vox} act(x*in_scale+in_shift)[n, vox*is+tap, ci] * dy[n, vox, co]
  * in two launches: cwf_wgrad writes partial slabs (MFMA accumulator layout) into `partial` (cwf_wgrad_partial_floats() floats)
- * and reports how many in *nsplit_used (<= cwf_wgrad_nsplit()); cwf_wgrad_reduce sums the slabs in slab order and scatters
+ * and reports how many in *nsplit_used (<= cwf_wgrad_nsplit()); cwf_wgrad_reduce sums the slabs in a fixed order (four
+ * partial sums over the slabs k = l, l + 4, ... for l = 0..3, combined as (s0 + s1) + (s2 + s3): the order of
+ * cwf_wgrad_reduce_batched, so both give the same bits) and scatters
  * through a host-built INVERSE map (int32 [slab_floats]: >= 0 index into dW ([Cout][Cin][k][k][k] as nn.Conv3d.weight), <= -2
  * bias index -2-v into db ([Cout], may be NULL), -1 padding).  The slab layout depends on (op, Cin, Cout) only.
  * Descriptor (zero-initialise; x / dy with their row pitches; precision as for cwf_conv):
@@ -135,6 +137,37 @@ struct cwf_wgrad_args {
   int N, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout;
 };
 int cwf_wgrad(const struct cwf_wgrad_args* args /* host */, int* nsplit_used /* host out, nullable */, void* stream);
+/* Tests and tools: the plan cwf_wgrad makes for a descriptor in a bf16 form (CWF_BF16, CWF_BF16X3; images and grouped launches
+ * included) -- the same host code the launch runs, so what it answers is what the launch does.  Read-only: launches nothing and
+ * dereferences no pointer of the descriptor (only their values and alignment count).  Returns what cwf_wgrad would return before
+ * its launch (0 or a negative CWF_E_*; CWF_E_BADARG also for a plain CWF_FP32 descriptor, whose plan is cwf_debug_wgrad_fp32_plan's)
+ * and on 0 fills out[CWF_WGB_PLAN_FIELDS]:
+ *   [0] kernel instance (enum below)      [1..3] grid x, y, z                  [4] threads per workgroup
+ *   [5] tile walk (CWF_WGB_WALK_*)        [6] tiles_per_split (WALK_RANGES), grid x (WALK_STRIDED), 4-voxel groups per wave (WALK_PW)
+ *   [7] workgroups per sample (WALK_PW, else 0)                                [8] waves that share the walk (WALK_PW, else 0)
+ *   [9] work items in all: spatial tiles of the launch; WALK_PW: 4-voxel groups per sample
+ *   [10] slab floats                      [11] nsplit_used: slabs written       [12] operand form: 0 bf16 products, 1 exact fp32 products
+ *   [13] fewest, [14] most work items of one workgroup (WALK_PW: of one workgroup's waves together)
+ * Tile walks: WALK_RANGES    workgroup x = s takes tiles [s * tiles_per_split, min(tiles, (s + 1) * tiles_per_split));
+ *             WALK_STRIDED   workgroup b of G takes tiles first, first + G, ... below tiles, first = (b & 7) * (G / 8) + (b >> 3);
+ *             WALK_PW        workgroup b = n * wps + w works in sample n; its wave v takes the 4-voxel groups
+ *                            [(w * waves + v) * gpw, min(groups, (w * waves + v + 1) * gpw)) of that sample (possibly none).
+ * cwf_debug_wgrad_bf16_name: a short name of an instance id (NULL outside [0, CWF_WGB_COUNT)). */
+enum cwf_wgrad_bf16_instance {
+  CWF_WGB_WGRAD16 = 0, CWF_WGB_WGRAD16_X3,                               /* wgrad16_kernel<X3> */
+  CWF_WGB_PW_1_1_1, CWF_WGB_PW_2_1_1, CWF_WGB_PW_4_2_1, CWF_WGB_PW_8_4_1, /* pw_wgrad_kernel<NCH, NTL, 1>: 1x1x1 */
+  CWF_WGB_PW_1_1_8, CWF_WGB_PW_2_2_8,                                     /* pw_wgrad_kernel<NCH, NTL, 8>: ConvTranspose */
+  CWF_WGB_S1_1, CWF_WGB_S1_2,                                             /* wgrad_s1_kernel<NTW> */
+  CWF_WGB_TILED_7_1, CWF_WGB_TILED_7_1_X3, CWF_WGB_TILED_7_2, CWF_WGB_TILED_7_2_X3,        /* wgrad_bf16_kernel<7, NTW, true, X3> */
+  CWF_WGB_TILED_2_1, CWF_WGB_TILED_2_1_X3, CWF_WGB_TILED_2_2, CWF_WGB_TILED_2_2_X3,        /* wgrad_bf16_kernel<2, NTW, false, X3> */
+  CWF_WGB_TILED_2_4, CWF_WGB_TILED_2_4_X3,
+  CWF_WGB_WGRAD16D, CWF_WGB_S1D,                                          /* wgrad16d_kernel, wgrad_s1d_kernel (bf16 images) */
+  CWF_WGB_COUNT
+};
+enum { CWF_WGB_WALK_RANGES = 0, CWF_WGB_WALK_STRIDED = 1, CWF_WGB_WALK_PW = 2 };
+#define CWF_WGB_PLAN_FIELDS 15
+int cwf_debug_wgrad_bf16_plan(const struct cwf_wgrad_args* args /* host */, int64_t* out /* host, CWF_WGB_PLAN_FIELDS */);
+const char* cwf_debug_wgrad_bf16_name(int instance);
 int cwf_wgrad_reduce(const float* partial, int nsplit, int64_t slab_floats,
                      const int32_t* inv_map, float* dW, float* db, void* stream);
 /* every layer of a backward phase in one launch: table = DEVICE array of descriptors (same slab / inverse-map conventions as

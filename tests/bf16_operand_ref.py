@@ -68,8 +68,8 @@ REL_SUMS = 1e-6                 # statistics / norm-backward sums, relative to t
 #       launch's input channel count (the forward's Cout for a data gradient).  256 channels x 27 taps: chain 6916, gamma 2^-14.6.
 #   weight gradient (wgrad_mfma_kernel): one accumulator per (tap, ci, co) and slab over the voxels of `tiles per split` spatial
 #       tiles of TD x TH x 16 voxels (the 27-tap kernel: every voxel of a tile through one wave; the 1-tap kernel: a quarter of the
-#       M-tiles per wave, each wave its own slab -- shorter), then the reduce of the nsplit slabs: in slab order
-#       (wgrad_reduce_kernel) or four lanes of stride 4 combined as (l0 + l1) + (l2 + l3) (wgrad_reduce_batched_kernel), at most
+#       M-tiles per wave, each wave its own slab -- shorter), then the reduce of the nsplit slabs: four lanes of
+#       stride 4 combined as (l0 + l1) + (l2 + l3) (wgrad_reduce_kernel and wgrad_reduce_batched_kernel alike), at most
 #       nsplit + 1 roundings; plus the product's own: wgrad_chain_fp32.
 #   statistics: per-thread fp32 sums of at most 16 stored values, shuffles, f64 across waves: REL_SUMS, as for the bf16 kernels.
 #       (This describes the sums fused into the conv epilogues only.  in_reduce_kernel of csrc/norm.hip adds up to 256 values per
@@ -266,9 +266,11 @@ def conv_ref(op, x, w, mode, bias=None, in_scale=None, in_shift=None, slope=1.0,
 
 def wgrad_operand_mode(op, cin, cout, size, mode):
     """the operand form of the weight-gradient kernel cwf_wgrad runs for op (cin -> cout) on a forward input of extent
-    size (D, H, W) -- wgrad_bf16_impl, csrc/wgrad_bf16.hip: pw_wgrad_kernel (exact fp32 products in both bf16 modes) for 1x1x1 layers
-    with D*H*W % 4 == 0 and (16-channel chunks, 16-channel tiles) in {(1, 1), (2, 1), (4, 2), (8, 4)}, and for ConvTranspose layers
-    with D*H*W % 4 == 0, W % 4 == 0 and (chunks, tiles) in {(1, 1), (2, 2)}; the bf16 tiled / persistent kernels otherwise"""
+    size (D, H, W) -- a copy of the pointwise conditions of wgrad_tensor_plan, csrc/wgrad_bf16.hip, for the CPU reference tests;
+    tests/test_wgrad_bf16_plan_cpu.py holds it to the library's own answer: pw_wgrad_kernel (exact fp32 products in both bf16
+    modes) for 1x1x1 layers with D*H*W % 4 == 0 and (16-channel chunks, 16-channel tiles) in {(1, 1), (2, 1), (4, 2), (8, 4)}, and
+    for ConvTranspose layers with D*H*W % 4 == 0, W % 4 == 0 and (chunks, tiles) in {(1, 1), (2, 2)}; the bf16 tiled / persistent
+    kernels otherwise"""
     d, h, w = size
     shape = (-(-cin // 16), -(-cout // 16))
     if op == CONV1 and (d * h * w) % 4 == 0 and shape in ((1, 1), (2, 1), (4, 2), (8, 4)):

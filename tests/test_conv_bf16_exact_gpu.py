@@ -13,7 +13,8 @@ import pytest
 import torch
 
 import bf16_operand_ref as R
-from cwf import packing as pk
+import wgrad_bf16_cases as WG
+from cwf import _lib, packing as pk
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -381,7 +382,9 @@ def test_weight_gradient_is_operand_exact(hip, path, mode, probe):
             s = s.abs() + 0.25 * (s == 0)
         if imp:
             s = _bf(s)                                             # dy * s then has <= 16 significant bits: hi + lo is exact
-    ex = R.wgrad_operand_mode(op, cin, cout, size, mode)           # (pw_wgrad_kernel: exact fp32 products in both modes)
+    # the operand form of the kernel that runs, from the library's own plan (pw_wgrad_kernel: exact fp32 products in both modes)
+    ex = WG.operand_form(_lib, hip.lib, op, cin, cout, size, n, mode, {"tiled": "contig", "images": "images", "dys": "dys"}[route])
+    assert ex == R.wgrad_operand_mode(op, cin, cout, size, mode)
     dw_ref, db_ref, aw, ab = R.wgrad_ref(op, x, dy, ex, sc, sh, slope, dy_scale=s)
     dv = lambda t: None if t is None else t.to(DEV)
     wn = math.prod(_wshape(op, cin, cout))

@@ -59,10 +59,16 @@ def exact(got, ref, prec, what, gamma=R.GAMMA_CONV, chain=None):
     R.check(got, ref, gamma, what)
 
 
-def exact_wgrad(gw, gb, op, x, dy, prec, in_scale, in_shift, slope, size, what, hip=None):
+def exact_wgrad(gw, gb, op, x, dy, prec, in_scale, in_shift, slope, size, what, hip=None, form="contig"):
     """the weight / bias gradient of hip.wgrad / wgrad_to against the operand-exact reference (operand form of the kernel that ran; in
-    fp32 wgrad_mfma_kernel, held to gamma_fp32 of the chain of its plan)"""
-    dw, db, aw, ab = R.wgrad_ref(op, x, dy, R.wgrad_operand_mode(op, x.shape[-1], dy.shape[-1], size, prec), in_scale, in_shift, slope)
+    fp32 wgrad_mfma_kernel, held to gamma_fp32 of the chain of its plan).  form: how the launch got its operands ("contig": fp32
+    tensors, "images": bf16 images), see tests/wgrad_bf16_cases.py"""
+    mode = R.wgrad_operand_mode(op, x.shape[-1], dy.shape[-1], size, prec)
+    if hip is not None and prec != "fp32":               # the library's own plan for the launch says which kernel ran
+        import wgrad_bf16_cases as WG
+        from cwf import _lib
+        mode = WG.operand_form(_lib, hip.lib, op, x.shape[-1], dy.shape[-1], size, x.shape[0], prec, form)
+    dw, db, aw, ab = R.wgrad_ref(op, x, dy, mode, in_scale, in_shift, slope)
     gamma = R.GAMMA_WGRAD
     if prec == "fp32":
         import ctypes
@@ -249,7 +255,8 @@ def test_dma_weight_gradient_32_channel_groups(hip, cin, cout, size, n):
     close(dw_b, gw_ref, rtol=PREC_TOL["bf16"], what="dma wgrad vs oracle")
     close(db_b, gb_ref, rtol=PREC_TOL["bf16"], what="dma bgrad vs oracle")
     for dw, db, what in ((dw_a, db_a, "fp32-tensor"), (dw_b, db_b, "dma")):
-        exact_wgrad(dw, db, pk.CONV3_S1, x, g, "bf16", sc, sh, 0.01, size, what)
+        exact_wgrad(dw, db, pk.CONV3_S1, x, g, "bf16", sc, sh, 0.01, size, what, hip=hip,
+                    form="images" if what == "dma" else "contig")
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
@@ -394,7 +401,8 @@ def test_bf16_operand_images_and_dma_weight_gradient(hip, size, n):
     close(dw_b, gw_ref, rtol=PREC_TOL["bf16"], what="dma wgrad vs oracle")
     close(db_b, gb_ref, rtol=PREC_TOL["bf16"], what="dma bgrad vs oracle")
     for dw, db, what in ((dw_a, db_a, "fp32-tensor"), (dw_b, db_b, "dma")):
-        exact_wgrad(dw, db, pk.CONV3_S1, x, g, "bf16", sc, sh, 0.01, size, what)
+        exact_wgrad(dw, db, pk.CONV3_S1, x, g, "bf16", sc, sh, 0.01, size, what, hip=hip,
+                    form="images" if what == "dma" else "contig")
 
 
 def _dy_scale(n, seed):

@@ -398,26 +398,32 @@ struct ScatBwdArgs {
   const float* rows; int64_t rows_ld, rows_bs; const float* gate; int64_t gate_bs; const float* dgate_extra; int64_t extra_bs;
   float* drows; int64_t drows_ld, drows_bs; float* dgate; int64_t dgate_bs; int T, k, E;
 };
+// drows[b][j] = dgated[b][index[j]] * gate[b] (+ dscat[b][index[j]]) by `nt` threads: the product is rounded, then the sum (the form
+// scatter_bwd_kernel has always been compiled to; contraction is off so that every kernel using this agrees bit for bit)
+__device__ __forceinline__ void scat_bwd_drows(const ScatBwdArgs& a, int b, int j, int tid, int nt) {
+#pragma clang fp contract(off)
+  const int E = a.E, T = a.T;
+  const int t = min(max(a.index[(int64_t)b * a.k + j], 0), T - 1);
+  const int64_t o = ((int64_t)b * T + t) * E;
+  for (int e = tid * 4; e < E; e += nt * 4) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.dgated) {
+      const float4 d = *reinterpret_cast<const float4*>(a.dgated + o + e);
+      const float4 g = *reinterpret_cast<const float4*>(a.gate + b * a.gate_bs + e);
+      v = make_float4(d.x * g.x, d.y * g.y, d.z * g.z, d.w * g.w);
+    }
+    if (a.dscat) { const float4 s = *reinterpret_cast<const float4*>(a.dscat + o + e); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
+    *reinterpret_cast<float4*>(a.drows + b * a.drows_bs + (int64_t)j * a.drows_ld + e) = v;
+  }
+}
+
 // grid (k + E/64, B), 1024 threads.  Blocks [0, k): drows[b][j] = dgated[b][index[j]] * gate[b] (+ dscat[b][index[j]]).
 // Blocks [k, k + E/64): dgate[b][c] = sum_t dgated[b][t][c] * scat[b][t][c] (+ dgate_extra[b][c]); scat is re-derived from
 // (feats, inv, rows); 64 columns x 16 row lanes, four rows in flight, fixed order -- written, no atomics, no zero fill.
 __global__ __launch_bounds__(1024) void scatter_bwd_kernel(const ScatBwdArgs a) {
   const int b = blockIdx.y, E = a.E, T = a.T;
   if ((int)blockIdx.x < a.k) {
-    if (threadIdx.x >= 128) return;
-    const int j = blockIdx.x;
-    const int t = min(max(a.index[(int64_t)b * a.k + j], 0), T - 1);
-    const int64_t o = ((int64_t)b * T + t) * E;
-    for (int e = threadIdx.x * 4; e < E; e += 512) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (a.dgated) {
-        const float4 d = *reinterpret_cast<const float4*>(a.dgated + o + e);
-        const float4 g = *reinterpret_cast<const float4*>(a.gate + b * a.gate_bs + e);
-        v = make_float4(d.x * g.x, d.y * g.y, d.z * g.z, d.w * g.w);
-      }
-      if (a.dscat) { const float4 s = *reinterpret_cast<const float4*>(a.dscat + o + e); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
-      *reinterpret_cast<float4*>(a.drows + b * a.drows_bs + (int64_t)j * a.drows_ld + e) = v;
-    }
+    if (threadIdx.x < 128) scat_bwd_drows(a, b, blockIdx.x, threadIdx.x, 128);
     return;
   }
   __shared__ float red[16][64];
@@ -438,7 +444,10 @@ __global__ __launch_bounds__(1024) void scatter_bwd_kernel(const ScatBwdArgs a) 
         }
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) acc += d[u] * s[u];
+      for (int u = 0; u < 4; ++u) {
+#pragma clang fp contract(off)
+        acc = acc + d[u] * s[u];
+      }
     }
   }
   red[w][lane] = acc;
@@ -449,6 +458,56 @@ __global__ __launch_bounds__(1024) void scatter_bwd_kernel(const ScatBwdArgs a) 
     for (int i = 0; i < 16; ++i) tsum += red[i][lane];
     if (a.dgate_extra) tsum += a.dgate_extra[b * a.extra_bs + c];
     a.dgate[b * a.dgate_bs + c] = tsum;
+  }
+}
+
+// scatter_bwd_kernel with COLS columns per workgroup (grid (k + E/COLS, B), 16 * COLS/VEC threads) and the loads of 16 rows per thread
+// issued ahead of the adds.  dgate[b][c] is summed exactly as there: row lane w = 0..15 adds dgated*scat (product rounded, then the
+// sum) over its rows t = w, w + 16, ... in ascending order inside one thread, the 16 partials are added in order from zero, then
+// dgate_extra.  (Rows past T add +0 to a sum that is never -0: no effect on the bits.)  A thread owns VEC adjacent columns.
+template <int COLS, int VEC>
+__global__ __launch_bounds__(16 * COLS / VEC) void scatter_bwd_wide_kernel(const ScatBwdArgs a) {
+  constexpr int NT = 16 * COLS / VEC, CT = COLS / VEC, R = 16;
+  typedef float fv __attribute__((ext_vector_type(VEC)));
+  const int b = blockIdx.y, E = a.E, T = a.T;
+  if ((int)blockIdx.x < a.k) { scat_bwd_drows(a, b, blockIdx.x, threadIdx.x, NT); return; }
+  __shared__ float red[16][COLS];
+  const int w = threadIdx.x / CT, ct = threadIdx.x % CT;
+  const int c0 = (blockIdx.x - a.k) * COLS;
+  const int c = c0 + ct * VEC;
+  fv acc = 0.f;
+  if (a.dgated) {
+    const int64_t row0 = (int64_t)b * T;
+    for (int t0 = w; t0 < T; t0 += 16 * R) {
+      int j[R]; fv d[R], s[R];
+#pragma unroll
+      for (int u = 0; u < R; ++u) { const int t = t0 + 16 * u; j[u] = t < T ? a.inv[row0 + t] : -1; }
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        const int t = t0 + 16 * u;
+        d[u] = 0.f; s[u] = 0.f;
+        if (t < T) {
+          d[u] = *reinterpret_cast<const fv*>(a.dgated + (row0 + t) * E + c);
+          s[u] = *reinterpret_cast<const fv*>(j[u] >= 0 ? a.rows + b * a.rows_bs + (int64_t)j[u] * a.rows_ld + c : a.feats + (row0 + t) * E + c);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+#pragma clang fp contract(off)
+        acc = acc + d[u] * s[u];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) red[w][ct * VEC + i] = acc[i];
+  __syncthreads();
+  if ((int)threadIdx.x < COLS) {
+    const int col = threadIdx.x;
+    float tsum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tsum += red[i][col];
+    if (a.dgate_extra) tsum += a.dgate_extra[b * a.extra_bs + c0 + col];
+    a.dgate[b * a.dgate_bs + c0 + col] = tsum;
   }
 }
 
@@ -576,6 +635,15 @@ extern "C" int cwf_scatter_inv(const float* feats, const int32_t* inv, const flo
   return 0;
 }
 
+// cwf_debug_scatter_bwd: 1 = the product route (SCB_WIDE_COLS columns per workgroup), 0 = scatter_bwd_kernel, 8 / 16 / 32 = that width.
+constexpr int SCB_WIDE_COLS = 16;
+static int g_scatter_bwd = 1;
+extern "C" int cwf_debug_scatter_bwd(int v) {
+  const int old = g_scatter_bwd;
+  if (v == 0 || v == 1 || v == 8 || v == 16 || v == 32) g_scatter_bwd = v;
+  return old;
+}
+
 extern "C" int cwf_scatter_bwd(const float* dgated, const float* dscat, const float* feats, const int32_t* inv, const int32_t* index,
                                const float* rows, int64_t rows_ld, int64_t rows_bs, const float* gate, int64_t gate_bs,
                                const float* dgate_extra, int64_t extra_bs, float* drows, int64_t drows_ld, int64_t drows_bs,
@@ -585,7 +653,13 @@ extern "C" int cwf_scatter_bwd(const float* dgated, const float* dscat, const fl
   if ((rows_ld | rows_bs | gate_bs | drows_ld | drows_bs) & 3) return CWF_E_BADARG;
   ScatBwdArgs a{dgated, dscat, feats, inv, index, rows, rows_ld, rows_bs, gate, gate_bs, dgate_extra, extra_bs, drows, drows_ld, drows_bs,
                 dgate, dgate_bs, T, k, E};
-  hipLaunchKernelGGL(scatter_bwd_kernel, dim3(k + E / 64, B), dim3(1024), 0, cwf_stream(stream), a);
+  // the narrow-block kernel reads VEC columns per access: every operand 16-byte aligned, or the 64-column kernel takes the launch
+  const bool aligned = !(((uintptr_t)dgated | (uintptr_t)feats | (uintptr_t)rows) & 15);
+  const int cols = !aligned ? 0 : g_scatter_bwd == 1 ? SCB_WIDE_COLS : g_scatter_bwd;
+  if (cols == 8) hipLaunchKernelGGL((scatter_bwd_wide_kernel<8, 2>), dim3(k + E / 8, B), dim3(64), 0, cwf_stream(stream), a);
+  else if (cols == 16) hipLaunchKernelGGL((scatter_bwd_wide_kernel<16, 4>), dim3(k + E / 16, B), dim3(64), 0, cwf_stream(stream), a);
+  else if (cols == 32) hipLaunchKernelGGL((scatter_bwd_wide_kernel<32, 4>), dim3(k + E / 32, B), dim3(128), 0, cwf_stream(stream), a);
+  else hipLaunchKernelGGL(scatter_bwd_kernel, dim3(k + E / 64, B), dim3(1024), 0, cwf_stream(stream), a);
   CWF_LAUNCH_CHECK();
   return 0;
 }

@@ -83,6 +83,11 @@ SIGNATURES = {
     "cwf_debug_gemm_panel_launches": [],
     "cwf_attn_fwd": [P, L, P, L, I, I, I, I, F, P, U64, F, P],
     "cwf_attn_bwd": [P, L, P, L, P, I, I, I, I, F, P, U64, F, P],
+    "cwf_attn_bwd_ws": [P, L, P, L, P, I, I, I, I, F, P, U64, F, P, L, P],
+    "cwf_attn_bwd_ws_bytes": [I, I, I],
+    "cwf_debug_attn_split": [I],
+    "cwf_debug_attn_split_waves": [I],
+    "cwf_debug_attn_split_launches": [],
     "cwf_ln_pair_fwd": [P, P, I, P, P, P, P, P, P, P, I, I, F, P],
     "cwf_ln_pair_bwd": [P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, P],
     "cwf_gelu_bwd_drop": [P, P, P, L, P, U64, F, P],
@@ -92,6 +97,7 @@ SIGNATURES = {
     "cwf_gather_multi": [P, I, I, I, I, F, P, F, P],
     "cwf_scatter_inv": [P, P, P, L, L, P, L, P, P, I, I, I, P],
     "cwf_scatter_bwd": [P, P, P, P, P, P, L, L, P, L, P, L, P, L, L, P, L, I, I, I, I, P],
+    "cwf_debug_scatter_bwd": [I],
     "cwf_token_grad": [P, P, P, L, P, P, P, L, P, L, P, U64, U64, F, P, I, I, I, I, P],
     "cwf_head_grad": [P, P, P, P, L, P, P, I, I, P],
     "cwf_dice_ce_finalize_multi": [P, P, P, P, I, I, L, I, P],
@@ -314,7 +320,7 @@ class WindowBox(C.Structure):
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
 GRADNORM_WS_DOUBLES = 1024     # CWF_GRADNORM_WS_DOUBLES
 RULE_ADAMW, RULE_SGD = 1, 2    # CWF_RULE_ADAMW, CWF_RULE_SGD
-RESTYPE_INT64 = {"cwf_debug_wsd_launches", "cwf_debug_gemm_panel_launches", "cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
+RESTYPE_INT64 = {"cwf_debug_wsd_launches", "cwf_debug_gemm_panel_launches", "cwf_debug_attn_split_launches", "cwf_attn_bwd_ws_bytes", "cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
                  "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace",
                  "cwf_topk_ce_workspace", "cwf_focal_workspace", "cwf_lovasz_workspace", "cwf_class_locations_workspace", "cwf_nonzero_box_workspace"}
 LOCATIONS_TILE = 16384     # CWF_LOCATIONS_TILE: the voxels of one workgroup of cwf_class_locations (a 16-byte aligned label starts tile 0)

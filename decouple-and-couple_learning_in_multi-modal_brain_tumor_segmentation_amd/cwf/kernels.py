@@ -995,8 +995,11 @@ class HipBackend:
         assert d_o.is_contiguous()
         dqkv = torch.empty_like(qkv)
         off, p = (drop[0], drop[1]) if drop else (0, 0.0)
-        self._call("cwf_attn_bwd", qkv.data_ptr(), qkv.stride(0), d_o.data_ptr(), e, dqkv.data_ptr(), z, t, e, heads,
-                   float((e // heads) ** -0.5), self.rng(qkv.device).data_ptr(), off, float(p), self._stream())
+        # the probabilities between the two launches: a persistent buffer, so the launch plan and a captured graph see one pointer
+        nbytes = int(self.lib.cwf_attn_bwd_ws_bytes(z, t, heads))
+        ws = self.workspace("attn_bwd", nbytes // 4, qkv.device)
+        self._call("cwf_attn_bwd_ws", qkv.data_ptr(), qkv.stride(0), d_o.data_ptr(), e, dqkv.data_ptr(), z, t, e, heads,
+                   float((e // heads) ** -0.5), self.rng(qkv.device).data_ptr(), off, float(p), ws.data_ptr(), ws.numel() * 4, self._stream())
         return dqkv
 
     def gelu_bwd_drop(self, z, dh, drop=None):

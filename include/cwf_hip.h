@@ -276,6 +276,19 @@ int cwf_attn_fwd(const float* qkv, int64_t ld, float* o, int64_t ldo, int Z, int
                  const uint64_t* rng, uint64_t drop_off, float drop_p, void* stream);
 int cwf_attn_bwd(const float* qkv, int64_t ld, const float* d_o, int64_t ldo, float* dqkv, int Z, int T, int E, int heads,
                  float scale, const uint64_t* rng, uint64_t drop_off, float drop_p, void* stream);
+/* The same backward pass in two launches that fill the device: A, one workgroup per (query tile, sequence, head), runs scores, row
+ * step and dQ and leaves the dropped probabilities and dS*scale in `ws`; B, one workgroup per (key tile, sequence, head), forms
+ * dK / dV from them.  No sum and no order across workgroups: dqkv is bit-identical to cwf_attn_bwd's.  ws: caller-owned device
+ * memory, 16-byte aligned, at least cwf_attn_bwd_ws_bytes(Z, T, heads) = 2 * Z*heads * ceil(T/32)*32 * 144 * 4 bytes; a null,
+ * misaligned or too small workspace is CWF_E_BADARG and nothing is written.  cwf_debug_attn_split: 1 = two launches (default), 0 = the
+ * one-launch kernel; cwf_debug_attn_split_waves: 4, 8 or 16 waves per workgroup of launch A (results do not depend on it); both
+ * return the previous value.  cwf_debug_attn_split_launches: calls that took the two-launch route so far (host-side count). */
+int64_t cwf_attn_bwd_ws_bytes(int Z, int T, int heads);
+int cwf_attn_bwd_ws(const float* qkv, int64_t ld, const float* d_o, int64_t ldo, float* dqkv, int Z, int T, int E, int heads,
+                    float scale, const uint64_t* rng, uint64_t drop_off, float drop_p, void* ws, int64_t ws_bytes, void* stream);
+int cwf_debug_attn_split(int v);
+int cwf_debug_attn_split_waves(int v);
+long long cwf_debug_attn_split_launches(void);
 
 /* Paired LayerNorm of a coupler block (PreNormDrop: norm(x), norm2(x2); ResidualNorm.py:23-32):
  *   ya = LN(x; g1,b1) ; yb[r] = LN(x2[perm(r)]; g2,b2) ; stats [2][rows][2] = (mean, rstd) ; x2 may be NULL (PreNorm of the FFN)
@@ -377,6 +390,10 @@ int cwf_scatter_bwd(const float* dgated, const float* dscat, const float* feats,
                     const float* rows, int64_t rows_ld, int64_t rows_bs, const float* gate, int64_t gate_bs,
                     const float* dgate_extra, int64_t extra_bs, float* drows, int64_t drows_ld, int64_t drows_bs,
                     float* dgate, int64_t dgate_bs, int B, int T, int k, int E, void* stream);
+/* cwf_debug_scatter_bwd: 1 = the product route (default), 0 = scatter_bwd_kernel (64 columns per workgroup), 8 / 16 / 32 = the narrow-block
+ * kernel at that many columns per workgroup; returns the previous value.  Every route sums dgate in the same chains: bit-identical.
+ * (The narrow-block kernel reads 8 / 16 bytes per access: a launch whose dgated, feats or rows is not 16-byte aligned takes route 0.) */
+int cwf_debug_scatter_bwd(int v);
 /* gradient of a token matrix from its three uses in one pass (written): scatter pass-through of the non-selected rows
  * (dgated*gate + dscat) + adjoint of the primary gather (inv_p, dseq_p) + adjoint of the supplementary gather (inv_q, dseq_q) */
 int cwf_token_grad(const float* dgated, const float* dscat, const float* gate, int64_t gate_bs,

@@ -446,6 +446,190 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgArgsB a) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// wgrad_s2: the single-bf16 3x3x3 STRIDE-2 launches of wgrad_bf16_kernel<7, NTW, true, false> (instances TILED_7_1 / TILED_7_2)
+// with every global load of a tile in flight at once.  Same grid, tile ranges, LDS images, fragment reads, MFMA order per
+// accumulator and slabs as that kernel -- its slabs are bit-equal -- but the geometry is compile-time (2 x 2 x 16 output voxels,
+// 5 x 5 x 33 halo, two K-steps; the launcher checks the ConvGeom against it), so
+//   * a thread's staging slots are fixed: 825 voxels x 4 channel quads over 256 threads = 13 float4 of x (LDS byte tid * 8 +
+//     2048 * slot: the image is unpadded) and NTW float4 of dy; all are loaded, without branches, before the first is converted
+//     (a padding slot loads the tensor's first quad and is zeroed at the conversion) -- the loop form paid one memory latency
+//     per slot, 15 a tile.  The next tile's loads follow the MFMAs with no barrier between, so they overlap them;
+//   * the K loop is straight-line with immediate LDS offsets, the bias row folded in by operand selection (cf. geo_s1);
+//   * one LDS buffer and two barriers a tile.  A second buffer (tile t+1's loads issued before tile t's MFMA phase, converted
+//     after it, one barrier a tile) measured no faster, alone or in the step (profiles/wgrad_s2_ab.txt), and is not kept.
+// dy must be 16-byte aligned with a row pitch that is a multiple of 4 and >= Cout (no scalar dy path; such launches stay on
+// wgrad_bf16_kernel).
+// ---------------------------------------------------------------------------------------------------
+template <int NTW> struct WgS2Lds {
+  static constexpr int CGW = NTW * 16;
+  static constexpr int NVOX = 5 * 5 * 33, XS = (NVOX * 4 + 255) / 256;     // halo voxels; x staging slots per thread (13)
+  static constexpr int DP = wg_dy_pitch(CGW), DSK = wg_dy_skew(CGW);
+  static constexpr unsigned XB = NVOX * 16 * 2;                              // x image (bytes), unpadded rows
+  static constexpr unsigned DYB = (4 * DP * CGW + 3 * DSK) * 2;              // dy image: 4 rows of 16 voxels, wgrad_bf16_kernel's layout
+  static constexpr unsigned BYTES = (XB + DYB + 15) & ~15u;                 // dynamic LDS of a launch
+  static constexpr unsigned KSX = 2 * 5 * 33 * 32, KSD = (2 * DP * CGW + DSK) * 2;   // K-step 1 past K-step 0 in the two images
+  static_assert(XS == 13 && XB % 16 == 0 && XS * 2048 >= XB, "stride-2 staging slots");
+};
+
+template <int NTW>
+__global__ __launch_bounds__(256, 2) void wgrad_s2_kernel(const WgArgsB a) {
+  typedef WgS2Lds<NTW> L;
+  constexpr int CG = NTW, CGW = L::CGW, XS = L::XS, DP = L::DP, DSK = L::DSK;
+  extern __shared__ float4 lds4[];
+  char* const ldsc = reinterpret_cast<char*>(lds4);
+  const ConvGeom& g = a.g;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kq = lane >> 4, bq = (lane & 15) >> 2, bp = lane & 3;
+  const int split = blockIdx.x;
+  const int chunk = blockIdx.y / a.ngroups, grp = blockIdx.y % a.ngroups;
+  const int Dc = g.cls_dims[0][0], Hc = g.cls_dims[0][1], Wc = g.cls_dims[0][2];
+  const int co0 = grp * CGW;
+  const int of0 = g.cls_ooff[0][0], of1 = g.cls_ooff[0][1], of2 = g.cls_ooff[0][2];
+
+  // per-lane fragment bases (LDS byte addresses): wave w owns taps w, w + 4, ...; slot 27 (wave 3) is the bias row
+  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds4;
+  const int tw0 = (kq >> 1) * 8 + bq;
+  unsigned xa[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const int t = wave + 4 * i;
+    xa[i] = lds_base + ((((kq & 1) * 2 * 33 + tw0 * 2) * 16 + bp * 4) * 2) + (t < 27 ? (((t / 9) * 5 + (t / 3) % 3) * 33 + t % 3) * 32 : 0);
+  }
+  const unsigned da = lds_base + L::XB + ((((kq & 1) * DP + tw0) * CGW + (kq & 1) * DSK + bp * 4) * 2);
+  const bool bias_wave = wave == 3;
+  const bf16x8 ones = ones_frag();
+
+  f32x4 acc[7][NTW];
+#pragma unroll
+  for (int i = 0; i < 7; ++i)
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int tiles_sp = g.tiles_d * g.tiles_h * g.tiles_w;
+  const int t_begin = split * a.tiles_per_split;
+  const int t_end = min(a.total_tiles, t_begin + a.tiles_per_split);
+
+  // staging slots of this thread (tile-invariant)
+  const int q = tid & 3;
+  const int c = chunk * 16 + q * 4;
+  const bool cval = c < g.Cin;
+  const bool has_norm = a.in_scale != nullptr;
+  const bool pro = has_norm || a.in_slope != 1.f;
+  const float slope = a.in_slope;
+
+  float4 vx[XS], vd[NTW], sc, sh;
+  unsigned okx = 0, okd = 0;
+
+  // every global load of one tile: prologue coefficients, 13 x quads, NTW dy quads; okx / okd: the slots the tiled kernel loads
+  // (it writes zero elsewhere)
+  auto issue = [&](int tile) {
+    const int n = tile / tiles_sp; int rem = tile - n * tiles_sp;
+    const int tile_w = rem % g.tiles_w; rem /= g.tiles_w;
+    const int tile_h = rem % g.tiles_h; const int tile_d = rem / g.tiles_h;
+    const int od0 = tile_d * 2, oh0 = tile_h * 2, ow0 = tile_w * 16;
+    sc = make_float4(1.f, 1.f, 1.f, 1.f); sh = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (has_norm) {                                        // (a quad past Cin reads quad 0; its slots are zeroed at the conversion)
+      sc = *reinterpret_cast<const float4*>(a.in_scale + (int64_t)n * g.Cin + (cval ? c : 0));
+      sh = *reinterpret_cast<const float4*>(a.in_shift + (int64_t)n * g.Cin + (cval ? c : 0));
+    }
+    const int id0 = od0 * 2 + g.lo[0], ih0 = oh0 * 2 + g.lo[1], iw0 = ow0 * 2 + g.lo[2];
+    const float* xb = a.x + ((((int64_t)n * g.Di + id0) * g.Hi + ih0) * g.Wi + iw0) * g.x_ldc;    // (uniform; never dereferenced itself)
+    okx = 0;
+#pragma unroll
+    for (int i = 0; i < XS; ++i) {
+      const int v = (tid >> 2) + 64 * i;
+      const int r = v / 33, iw = v - r * 33, idd = r / 5, ih = r - idd * 5;
+      const int gd = id0 + idd, gh = ih0 + ih, gw = iw0 + iw;
+      const bool ok = cval & (v < L::NVOX) & ((unsigned)gd < (unsigned)g.Di) & ((unsigned)gh < (unsigned)g.Hi) & ((unsigned)gw < (unsigned)g.Wi);
+      const int off = ((idd * g.Hi + ih) * g.Wi + iw) * g.x_ldc + c;
+      vx[i] = *reinterpret_cast<const float4*>(ok ? xb + off : a.x);      // (no branch: a padding slot reads the tensor's first quad)
+      okx |= ok ? (1u << i) : 0u;
+    }
+    okd = 0;
+#pragma unroll
+    for (int k = 0; k < NTW; ++k) {
+      const int e = tid + 256 * k;
+      const int vox = e / (CGW / 4), cq = e % (CGW / 4);
+      const int tw = vox & 15, mt = vox >> 4;
+      const int od = od0 + (mt >> 1), oh = oh0 + (mt & 1), ow = ow0 + tw;
+      const int co = co0 + cq * 4;
+      const bool ok = (od < Dc) & (oh < Hc) & (ow < Wc) & (co < g.Cout);
+      const int64_t gv = (((int64_t)n * g.Do + (od * g.os + of0)) * g.Ho + (oh * g.os + of1)) * g.Wo + (ow * g.os + of2);
+      vd[k] = *reinterpret_cast<const float4*>(ok ? a.dy + gv * a.dy_ldc + co : a.dy);
+      okd |= ok ? (1u << k) : 0u;
+    }
+  };
+  // prologue, rounding and LDS stores of the tile held in vx / vd
+  auto convert = [&]() {
+#pragma unroll
+    for (int i = 0; i < XS; ++i) {
+      if ((tid >> 2) + 64 * i >= L::NVOX) continue;
+      float4 val = vx[i];
+      if (pro) {
+        val.x = cwf_act(val.x * sc.x + sh.x, slope); val.y = cwf_act(val.y * sc.y + sh.y, slope);
+        val.z = cwf_act(val.z * sc.z + sh.z, slope); val.w = cwf_act(val.w * sc.w + sh.w, slope);
+      }
+      const bool was = (okx >> i) & 1u;                    // zero padding applies after the activation
+      val.x = was ? val.x : 0.f; val.y = was ? val.y : 0.f; val.z = was ? val.z : 0.f; val.w = was ? val.w : 0.f;
+      uint2 h; h.x = pack_bf16w(val.x, val.y); h.y = pack_bf16w(val.z, val.w);
+      *reinterpret_cast<uint2*>(ldsc + tid * 8 + 2048 * i) = h;
+    }
+#pragma unroll
+    for (int k = 0; k < NTW; ++k) {
+      const int e = tid + 256 * k;
+      const int vox = e / (CGW / 4), cq = e % (CGW / 4);
+      const int tw = vox & 15, mt = vox >> 4;
+      const int co = co0 + cq * 4;
+      const bool was = (okd >> k) & 1u;
+      float4 val = vd[k];
+      val.x = was ? val.x : 0.f;
+      val.y = was && co + 1 < g.Cout ? val.y : 0.f; val.z = was && co + 2 < g.Cout ? val.z : 0.f; val.w = was && co + 3 < g.Cout ? val.w : 0.f;
+      uint2 h; h.x = pack_bf16w(val.x, val.y); h.y = pack_bf16w(val.z, val.w);
+      *reinterpret_cast<uint2*>(ldsc + L::XB + ((mt * DP + tw) * CGW + ((mt + 1) >> 1) * DSK + cq * 4) * 2) = h;
+    }
+  };
+  // the tile's two K-steps: all transposed reads, then 14 x NTW MFMAs (K-step order per accumulator as in the tiled kernel)
+  auto mfma = [&]() {
+    bf16x8 ah[2][7], bh[2][NTW];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+      for (int j = 0; j < NTW; ++j) bh[ks][j] = tr_frag_at(da + ks * L::KSD + j * 32, 4 * CGW * 2);
+#pragma unroll
+      for (int i = 0; i < 7; ++i) ah[ks][i] = tr_frag_at(xa[i] + ks * L::KSX, 4 * 2 * 32);
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int i = 0; i < 7; ++i) {
+        const bf16x8 ahf = (i == 6 && bias_wave) ? ones : ah[ks][i];      // wave-uniform select
+#pragma unroll
+        for (int j = 0; j < NTW; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahf, bh[ks][j], acc[i][j], 0, 0, 0);
+      }
+  };
+
+  for (int tile = t_begin; tile < t_end; ++tile) {
+    issue(tile);
+    __syncthreads();                                       // the previous tile's fragment reads are done
+    convert();
+    __syncthreads();
+    mfma();
+  }
+
+  float4* out = reinterpret_cast<float4*>(a.partial + (int64_t)split * a.slab_floats);
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const int t = wave + 4 * i;
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) {
+      const int64_t blk = (int64_t)a.cls_slab_base[0] + (((int64_t)chunk * a.ngroups + grp) * 28 + t) * CG + j;
+      out[blk * 64 + lane] = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // wgrad16: weight gradient of the full-resolution 3x3x3 convolutions with <= 16 input and 16 output channels
 // (the conv16 layers).  Same producer / consumer structure as conv16_kernel (conv_bf16.hip), for the same measured reasons:
 //   * 8-wave persistent workgroups, one per CU, each owning a CONTIGUOUS range of 4x4x16 tiles;
@@ -1532,8 +1716,40 @@ static int wgrad_bf16_plan(const cwf_wgrad_args& d, WgBf16Plan& p) {
   return wgrad_tensor_plan(d, p);
 }
 
+// Route of the single-bf16 stride-2 launches behind TILED_7_1 / TILED_7_2 (include/cwf_hip.h): 1 = wgrad_s2_kernel, 0 = the tiled kernel.
+static int g_wgrad_s2 = 1;
+static long long g_wgrad_s2_launches = 0;
+extern "C" int cwf_debug_wgrad_s2(int v) { const int old = g_wgrad_s2; g_wgrad_s2 = v; return old; }
+extern "C" long long cwf_debug_wgrad_s2_launches() { return g_wgrad_s2_launches; }
+
+// wgrad_s2_kernel takes a tiled plan when the geometry is the one it has compiled in and dy needs no scalar path
+static bool wgrad_s2_takes(const WgBf16Plan& p) {
+  if (p.id != CWF_WGB_TILED_7_1 && p.id != CWF_WGB_TILED_7_2) return false;
+  const WgArgsB& a = p.a; const ConvGeom& g = a.g;
+  if (a.groups || p.threads != 256 || g.ncls != 1 || g.is != 2 || g.os != 1 || g.TD != 2 || g.TH != 2 || g.ID != 5 || g.IH != 5 || g.IW != 33 ||
+      g.cls_ntaps[0] != 27 || g.tiles_d != cdiv(g.cls_dims[0][0], 2) || g.tiles_h != cdiv(g.cls_dims[0][1], 2) || g.tiles_w != cdiv(g.cls_dims[0][2], 16))
+    return false;
+  for (int t = 0; t < 27; ++t) if (g.tapofs[t] != ((t / 9) * 5 + (t / 3) % 3) * 33 + t % 3) return false;
+  if ((a.dy_ldc & 3) || ((uintptr_t)a.dy & 15) || g.Cout > a.dy_ldc || g.y_ldc != a.dy_ldc) return false;
+  return (int64_t)6 * g.Hi * g.Wi * g.x_ldc < (1ll << 31);   // (a thread's slot offsets inside a halo are 32-bit)
+}
+
+template <int NTW>
+static void wgrad_s2_launch(const WgBf16Plan& p, dim3 grid, hipStream_t st) {
+  CWF_MAX_LDS_ONCE((&wgrad_s2_kernel<NTW>));
+  hipLaunchKernelGGL((wgrad_s2_kernel<NTW>), grid, dim3(256), WgS2Lds<NTW>::BYTES, st, p.a);
+}
+
 static int wgrad_bf16_launch(const WgBf16Plan& p, int* nsplit_used, hipStream_t st) {
   const dim3 grid(p.gx, p.gy, p.gz), block(p.threads);
+  if (g_wgrad_s2 && wgrad_s2_takes(p)) {
+    if (p.id == CWF_WGB_TILED_7_1) wgrad_s2_launch<1>(p, grid, st);
+    else wgrad_s2_launch<2>(p, grid, st);
+    ++g_wgrad_s2_launches;
+    CWF_LAUNCH_CHECK();
+    if (nsplit_used) *nsplit_used = p.nsplit_used;
+    return 0;
+  }
 #define CWF_WGK(id_, ...) case id_: CWF_MAX_LDS_ONCE((&__VA_ARGS__)); hipLaunchKernelGGL((__VA_ARGS__), grid, block, p.lds, st, p.a); break
 #define CWF_WGP(id_, ...) case id_: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, p.a, p.wk, p.CG); break
   switch (p.id) {

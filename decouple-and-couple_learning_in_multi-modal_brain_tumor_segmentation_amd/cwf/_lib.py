@@ -26,6 +26,8 @@ SIGNATURES = {
     "cwf_wgrad": [P, P, P],
     "cwf_debug_wgrad_bf16_plan": [P, P],
     "cwf_debug_wgrad_bf16_name": [I],              # returns const char* (restype set in load())
+    "cwf_debug_wgrad_s2": [I],
+    "cwf_debug_wgrad_s2_launches": [],
     "cwf_gather_split_bf16": [P, I, L, P],
     "cwf_wgrad_nsplit": [I, I, I, I, I, I, I],
     "cwf_wgrad_partial_floats": [I, I, I, I, I, I, I],
@@ -320,7 +322,7 @@ class WindowBox(C.Structure):
 NORM_WS_DOUBLES = 2568     # CWF_NORM_WS_DOUBLES
 GRADNORM_WS_DOUBLES = 1024     # CWF_GRADNORM_WS_DOUBLES
 RULE_ADAMW, RULE_SGD = 1, 2    # CWF_RULE_ADAMW, CWF_RULE_SGD
-RESTYPE_INT64 = {"cwf_debug_wsd_launches", "cwf_debug_gemm_panel_launches", "cwf_debug_attn_split_launches", "cwf_attn_bwd_ws_bytes", "cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
+RESTYPE_INT64 = {"cwf_debug_wsd_launches", "cwf_debug_wgrad_s2_launches", "cwf_debug_gemm_panel_launches", "cwf_debug_attn_split_launches", "cwf_attn_bwd_ws_bytes", "cwf_wgrad_partial_floats", "cwf_wgrad_slab_floats", "cwf_hausdorff_workspace", "cwf_components_workspace",
                  "cwf_lesionwise_workspace", "cwf_surface_metrics_workspace", "cwf_lesionwise_ex_workspace", "cwf_signed_distance_workspace",
                  "cwf_topk_ce_workspace", "cwf_focal_workspace", "cwf_lovasz_workspace", "cwf_class_locations_workspace", "cwf_nonzero_box_workspace"}
 LOCATIONS_TILE = 16384     # CWF_LOCATIONS_TILE: the voxels of one workgroup of cwf_class_locations (a 16-byte aligned label starts tile 0)

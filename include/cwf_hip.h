@@ -168,6 +168,13 @@ enum { CWF_WGB_WALK_RANGES = 0, CWF_WGB_WALK_STRIDED = 1, CWF_WGB_WALK_PW = 2 };
 #define CWF_WGB_PLAN_FIELDS 15
 int cwf_debug_wgrad_bf16_plan(const struct cwf_wgrad_args* args /* host */, int64_t* out /* host, CWF_WGB_PLAN_FIELDS */);
 const char* cwf_debug_wgrad_bf16_name(int instance);
+/* Tests and tools: the route of the single-bf16 3x3x3 stride-2 launches behind CWF_WGB_TILED_7_1 / CWF_WGB_TILED_7_2 (fp32 operands, dy
+ * 16-byte aligned with a row pitch that is a multiple of 4).  cwf_debug_wgrad_s2: 1 = wgrad_s2_kernel, which keeps all of a tile's
+ * loads in flight (default), 0 = never (the tiled kernel wgrad_bf16_kernel); returns the previous value.
+ * cwf_debug_wgrad_s2_launches: launches of that kernel so far (host-side count).  The plan that cwf_debug_wgrad_bf16_plan reports and
+ * the slabs do not depend on the route: the slabs are bit-identical. */
+int cwf_debug_wgrad_s2(int v);
+long long cwf_debug_wgrad_s2_launches(void);
 int cwf_wgrad_reduce(const float* partial, int nsplit, int64_t slab_floats,
                      const int32_t* inv_map, float* dW, float* db, void* stream);
 /* every layer of a backward phase in one launch: table = DEVICE array of descriptors (same slab / inverse-map conventions as

@@ -36,6 +36,7 @@ def _load(name, path):
 
 syn = _load("cwf_synthetic", os.path.join(PKG, "utils", "synthetic.py"))
 rm = _load("oracle_reference_model", os.path.join(REPO, "oracle", "reference_model.py"))
+gs = _load("grad_sketch", os.path.join(REPO, "tests", "grad_sketch.py"))
 
 
 def import_reference(n_index=8192):
@@ -178,6 +179,78 @@ def whole_model(get_model, criterions, tools, size, tag, with_grad=True):
     return dev
 
 
+def gradient_sketches(get_model, criterions, tools, size, tag, samples=(0,)):
+    """tests/golden/grads_<tag>.npz: a count-sketch (tests/grad_sketch.py, 256 float64 numbers per tensor, tensors of at most 256
+    elements whole) of EVERY parameter gradient of the imported reference run in float64, on the weights and inputs whole_model()
+    uses; the reference's own fp32 distance from it in the same metric (the noise floor the tests scale their bound by); the five loss
+    parts and the total in fp32 and float64; and the top-k index sets of the float64 forward, for teacher forcing (a near-tie flip
+    changes gradients wholesale and is not what the sketch measures).  ``samples`` = the synthetic subjects of the batch: [0, 1] pins
+    batch 2, where softmax_dice and the separate losses sum over the batch before they divide.  The reference's forward raises at
+    B = 2 (its class tokens are concatenated as [1, 1, E]), and the only consistent meaning of a batch is independent samples:
+    so the reference model runs once per sample, and the reference's loss functions -- which do take a batch -- run on the
+    concatenated outputs.  The restatement runs the batch in one forward and has to agree.
+
+    128^3 is left out on purpose: the float64 reference backward at that size does not fit the build container's 62 GB with margin, and
+    the wiring these fixtures pin (which gradient lands in which tensor, slice and order) is the same at 64^3; what differs at 128^3 is
+    tile geometry, which the kernel suites own."""
+    torch.manual_seed(0)
+    state = syn.det_state_dict(rm.param_shapes())
+    m, full = ref_model(get_model, state, size)
+    x, target, edge = syn.synthetic_batch(list(samples), size)
+
+    def run_ref(model, xin):
+        for q in model.parameters():
+            q.requires_grad_(True)
+            q.grad = None
+        per = [model(xin[b:b + 1], None) for b in range(xin.shape[0])]
+        o = [torch.cat([q[0] for q in per])] + [{r: torch.cat([q[j][r] for q in per]) for r in rm.REGIONS} for j in (1, 2, 3, 4)]
+        pr = [criterions.softmax_dice(o[0], target), tools.get_separate_loss(o[1], target),
+              tools.get_edge_separate_loss(o[2], edge), tools.get_separate_loss(o[3], target),
+              tools.get_edge_separate_loss(o[4], edge)]
+        tot = sum(pr)
+        tot.backward()
+        return [float(v.detach()) for v in pr], float(tot.detach()), {n: q.grad.detach().clone() for n, q in model.named_parameters()}
+
+    parts32, loss32, g32 = run_ref(m, x)
+    parts64, loss64, g64 = run_ref(m.double(), x.double())
+    names = list(g64.keys())
+    fx = gs.pack_reference(names, g64, g32)
+    fx.update(size=np.array(size), samples=np.array(samples), n_not_live=np.int64(int((fx["l2_f64"] <= gs.LIVE_L2).sum())),
+              loss_parts=np.array(parts32), loss=np.float64(loss32), loss_parts_f64=np.array(parts64), loss_f64=np.float64(loss64))
+
+    # ---- the same computation as the existing fixture (B = 1 tags)
+    if len(samples) == 1:
+        old = np.load(os.path.join(GOLD, "model_%s.npz" % tag))
+        assert list(old["grad_names"]) == names
+        live = old["grad_l2_f64"] > gs.LIVE_L2
+        rel = np.abs(fx["l2_f64"][live] - old["grad_l2_f64"][live]) / old["grad_l2_f64"][live]
+        assert rel.max() < 1e-9 and (fx["l2_f64"][~live] <= gs.LIVE_L2).all(), rel.max()
+        print("[grads_%s] l2_f64 vs model_%s.npz grad_l2_f64: max rel %.1e" % (tag, tag, rel.max()))
+
+    # ---- the restatement in float64 on the same inputs: every live tensor within 1e-8 in the sketch metric; its top-k sets are the fixture's
+    p64 = {k: v.double().clone().requires_grad_(not k.endswith(".pe")) for k, v in full.items()}
+    o64, aux = rm.forward(p64, x.double(), return_aux=True)
+    l64, _ = rm.total_loss(o64, target, edge, ce_float32=True)      # (the reference's CE term is fp32 arithmetic even in this run)
+    l64.backward()
+    refs = gs.reference_sketches(fx)
+    dr = {n: gs.distance(gs.sketch_np(p64[n].grad.numpy(), i), r) for n, (i, r) in refs.items() if fx["l2_f64"][i] > gs.LIVE_L2}
+    worst = max(dr, key=dr.get)
+    print("[grads_%s] restatement float64 vs reference float64, sketch distance: worst %.1e (%s); loss %.1e" % (
+        tag, dr[worst], worst, abs(float(l64.detach()) - loss64)))
+    assert dr[worst] < 1e-8 and abs(float(l64.detach()) - loss64) < 1e-8 * abs(loss64), (worst, dr[worst])
+    for k, v in aux.items():
+        if v.dtype == torch.int64:
+            fx["topk_" + k] = v.numpy().astype(np.int32)
+    with torch.no_grad():                              # (the fp32 forward's selections, for the record: a near tie would show here)
+        _, aux32 = rm.forward(full, x, return_aux=True)
+    flips = {k: int((np.sort(fx["topk_" + k], -1) != np.sort(v.numpy(), -1)).sum()) for k, v in aux32.items() if v.dtype == torch.int64}
+    lv = fx["l2_f64"] > gs.LIVE_L2
+    print("[grads_%s] %d tensors, %d not live; reference fp32 noise in the sketch metric: median %.1e max %.1e; fp32 vs float64 top-k "
+          "entries differing: %d" % (tag, len(names), int(fx["n_not_live"]), float(np.median(fx["noise_sketch"][lv])),
+                                     float(fx["noise_sketch"][lv].max()), sum(flips.values())))
+    np.savez_compressed(os.path.join(GOLD, "grads_%s.npz" % tag), **fx)
+
+
 def loss_fixtures(criterions, tools):
     """tools.dice_loss / softmax_weighted_loss / get_separate_loss / get_edge_separate_loss
     on 2 x 16^3 random probabilities (values and gradients w.r.t. the probabilities)."""
@@ -242,7 +315,7 @@ def adam_fixture():
 
 
 def main():
-    """python oracle/make_golden.py [--only TAG ...]   TAG in {losses, adam, 64, 128, noncubic, config4}"""
+    """python oracle/make_golden.py [--only TAG ...]   TAG in {losses, adam, 64, 128, noncubic, config4, grads_64, grads_noncubic, grads_64_b2}"""
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(8)
     only = set(sys.argv[sys.argv.index("--only") + 1:]) if "--only" in sys.argv else None
@@ -262,6 +335,13 @@ def main():
         whole_model(get_model, criterions, tools, (64, 96, 80), "noncubic")
     if want("config4"):
         whole_model(get_model, criterions, tools, (160, 192, 160), "config4", with_grad=False)
+    # every parameter gradient, by count-sketch (after the model_* fixtures: the B = 1 tags assert against them)
+    if want("grads_64"):
+        gradient_sketches(get_model, criterions, tools, (64, 64, 64), "64")
+    if want("grads_noncubic"):
+        gradient_sketches(get_model, criterions, tools, (64, 96, 80), "noncubic")
+    if want("grads_64_b2"):
+        gradient_sketches(get_model, criterions, tools, (64, 64, 64), "64_b2", samples=(0, 1))
     print("golden fixtures written to", GOLD)
 
 

@@ -327,55 +327,61 @@ def dice_loss(prob, onehot, num_cls, eps=1e-7):
     return 1.0 - dice / num_cls
 
 
-def softmax_weighted_loss(prob, onehot, num_cls):
+def softmax_weighted_loss(prob, onehot, num_cls, ce_float32=False):
     """tools.softmax_weighted_loss (tools.py:21-34): per-sample class-frequency weight
-    1 - sum(t_c)/sum(t); -w t log(clamp(p, 0.005, 1)); mean over B*D*H*W."""
+    1 - sum(t_c)/sum(t); -w t log(clamp(p, 0.005, 1)); mean over B*D*H*W.
+
+    ce_float32: the reference casts the log to float32 (tools.py:30-32), which does nothing in its fp32 runs; in a float64 run it makes
+    this term fp32 arithmetic (the value and, through the cast's backward, -w t / N rounded to fp32: 6e-8 relative wherever N is no power
+    of two).  Off by default -- the kernel references want the operation itself in float64 -- and on where the restatement has to
+    reproduce the reference's float64 run (oracle/make_golden.py: gradient_sketches)."""
     t = onehot.float()
     tot = torch.sum(t, (1, 2, 3, 4))
     loss = 0.0
     for i in range(num_cls):
         w = 1.0 - torch.sum(t[:, i], (1, 2, 3)) / tot
-        loss = loss - w.reshape(-1, 1, 1, 1) * t[:, i] * torch.log(torch.clamp(prob[:, i], min=0.005, max=1))
+        lg = torch.log(torch.clamp(prob[:, i], min=0.005, max=1))
+        loss = loss - w.reshape(-1, 1, 1, 1) * t[:, i] * (lg.float() if ce_float32 else lg)
     return torch.mean(loss)
 
 
-def _dice_ce(prob, labels, num_cls):
+def _dice_ce(prob, labels, num_cls, ce_float32=False):
     oh = F.one_hot(labels, num_cls).permute(0, 4, 1, 2, 3).contiguous()
-    return dice_loss(prob, oh, num_cls) + softmax_weighted_loss(prob, oh, num_cls)
+    return dice_loss(prob, oh, num_cls) + softmax_weighted_loss(prob, oh, num_cls, ce_float32)
 
 
-def softmax_dice(prob, target):
+def softmax_dice(prob, target, ce_float32=False):
     """criterions.softmax_dice (criterions.py:49-62)."""
-    return _dice_ce(prob, target, 4)
+    return _dice_ce(prob, target, 4, ce_float32)
 
 
-def get_separate_loss(out, target):
+def get_separate_loss(out, target, ce_float32=False):
     """tools.get_separate_loss (tools.py:112-162): binary problems {target==k}, k=1,2,3."""
     total = 0.0
     for key, k in zip(REGIONS, (1, 2, 3)):
-        total = total + _dice_ce(out[key], (target == k).long(), 2)
+        total = total + _dice_ce(out[key], (target == k).long(), 2, ce_float32)
     return total
 
 
 EDGE_SETS = {"01": (1, 5, 6, 7), "02": (2, 5, 6, 8), "04": (4, 5, 7, 8)}
 
 
-def get_edge_separate_loss(out, edge):
+def get_edge_separate_loss(out, edge, ce_float32=False):
     """tools.get_edge_separate_loss (tools.py:165-231): edge code sets E1/E2/E4."""
     total = 0.0
     for key in REGIONS:
         m = torch.zeros_like(edge, dtype=torch.bool)
         for c in EDGE_SETS[key]:
             m |= edge == c
-        total = total + _dice_ce(out[key], m.long(), 2)
+        total = total + _dice_ce(out[key], m.long(), 2, ce_float32)
     return total
 
 
-def total_loss(outputs, target, edge):
+def total_loss(outputs, target, edge, ce_float32=False):
     """train_no_amp.py:205-211 (all weights 1.0).  Returns (total, [five parts])."""
-    parts = [softmax_dice(outputs[0], target), get_separate_loss(outputs[1], target),
-             get_edge_separate_loss(outputs[2], edge), get_separate_loss(outputs[3], target),
-             get_edge_separate_loss(outputs[4], edge)]
+    parts = [softmax_dice(outputs[0], target, ce_float32), get_separate_loss(outputs[1], target, ce_float32),
+             get_edge_separate_loss(outputs[2], edge, ce_float32), get_separate_loss(outputs[3], target, ce_float32),
+             get_edge_separate_loss(outputs[4], edge, ce_float32)]
     return sum(parts), parts
 
 

@@ -28,6 +28,21 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __device__ __forceinline__ float cwf_act(float v, float slope) { return v > 0.f ? v : v * slope; }
 __device__ __forceinline__ float cwf_act_grad(float v, float slope) { return v > 0.f ? 1.f : slope; }
 
+// The bf16 operands of every kernel family (tests/bf16_operand_ref.py restates them): round to nearest even.
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pack_bf16(float a, float b) {          // one v_cvt_pk_bf16_f32
+  const f32x2_t f = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
+}
+__device__ __forceinline__ float bf16_round(float a) { return (float)(__bf16)a; }
+// split two floats into packed bf16 hi and lo (lo = bf16(v - hi)):  cvt_pk, shl/and, 2 sub, cvt_pk
+__device__ __forceinline__ void split_bf16(float a, float b, unsigned& hi, unsigned& lo) {
+  hi = pack_bf16(a, b);
+  const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
+  lo = pack_bf16(a - ha, b - hb);
+}
+
 // 64-lane butterfly sum
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -31,21 +31,70 @@ struct ConvArgsB {
   unsigned short* y16;
 };
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {          // one v_cvt_pk_bf16_f32
-  const f32x2_t f = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ float bf16_round(float a) { return (float)(__bf16)a; }
-// split two floats into packed bf16 hi and lo (lo = bf16(v - hi)):  cvt_pk, shl/and, 2 sub, cvt_pk
-__device__ __forceinline__ void split_bf16(float a, float b, unsigned& hi, unsigned& lo) {
-  hi = pack_bf16(a, b);
-  const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
-  lo = pack_bf16(a - ha, b - hb);
-}
 // branch-free (Leaky)ReLU / identity for slope in [0,1]: max(v, slope*v)
 __device__ __forceinline__ float act01(float v, float slope) { return fmaxf(v, v * slope); }
+
+// ---- The 4x4x16 output tile of conv_ws / conv_wsp / conv_wsd and its halo, staged as an LDS image [voxel][16 channels] of bf16 by 256
+// loader threads: thread tg holds channel quad tg & 3 of the voxels (tg >> 2) + HALO_DV i, i < HALO_SLOTS.
+constexpr int HALO_D = 6, HALO_H = 6, HALO_W = 18;
+constexpr int HALO_NVOX = HALO_D * HALO_H * HALO_W;                  // 648 halo voxels
+constexpr int HALO_DV = 256 / 4;                                     // voxels between two staging slots of a thread
+constexpr int HALO_SLOTS = (HALO_NVOX + HALO_DV - 1) / HALO_DV;      // 11 (the last one only for tg >> 2 < 8)
+// byte offset in the image of the voxel that tap t = (kd * 3 + kh) * 3 + kw reads for output voxel 0
+__host__ __device__ constexpr int halo_tap_bytes(int t) { return (((t / 9) * HALO_H + (t / 3) % 3) * HALO_W + t % 3) * 32; }
+
+// One step of a loader thread's halo slot walk over the tile whose halo starts at voxel (id0, ih0, iw0) of its sample.  (iw, row) is
+// the slot's voxel as (v % HALO_W, v / HALO_W), row = idd * HALO_H + ih, from ((tg >> 2) % HALO_W, (tg >> 2) / HALO_W) for slot 0; the step
+// moves it on to the next slot.  Returns whether the voxel lies in the volume; boff: the byte offset of its channel quad q in the sample's
+// fp32 tensor (ldc4 = 4 x_ldc bytes per voxel), clamped to voxel 0 outside the volume so that the caller's load can be unconditional.
+__device__ __forceinline__ bool halo_slot_next(const ConvGeom& g, int id0, int ih0, int iw0, unsigned ldc4, int q, int& iw, int& row, unsigned& boff) {
+  const int idd = (row * 43) >> 8, ih = row - idd * HALO_H;                   // row / 6 for row < 48
+  const int gd = id0 + idd, gh = ih0 + ih, gw = iw0 + iw;
+  const bool ok = (row < HALO_D * HALO_H) & ((unsigned)gd < (unsigned)g.Di) & ((unsigned)gh < (unsigned)g.Hi) & ((unsigned)gw < (unsigned)g.Wi);
+  iw += HALO_DV % HALO_W; row += HALO_DV / HALO_W;                            // HALO_DV voxels on: 3 rows + 10
+  if (iw >= HALO_W) { iw -= HALO_W; ++row; }
+  const unsigned lin = (unsigned)((gd * g.Hi + gh) * g.Wi + gw) * ldc4 + (unsigned)q * 16u;
+  boff = ok ? lin : (unsigned)q * 16u;
+  return ok;
+}
+
+// sample and tile coordinates of tile index `tile` (tiles_per_n = g.tiles_d * g.tiles_h * g.tiles_w)
+__device__ __forceinline__ void tile_pos(const ConvGeom& g, int tiles_per_n, int tile, int& n, int& td, int& th, int& tw) {
+  n = tile / tiles_per_n;
+  int bx = tile - n * tiles_per_n;
+  tw = bx % g.tiles_w; bx /= g.tiles_w;
+  th = bx % g.tiles_h; td = bx / g.tiles_h;
+}
+
+// Row epilogue of conv_bf16 (interior fast path) / conv_ws / conv_wsp / conv_wsd: the byte offset of a lane's element -- voxel vi of the
+// row, channel c0 -- in a tensor of ldc floats per voxel, as an opaque copy (keeps the zero-extension at the access: saddr form).
+__device__ __forceinline__ unsigned epi_lane_off(int vi, int ldc, int c0) {
+  unsigned o = (unsigned)(vi * ldc + c0) * 4u;
+  asm volatile("" : "+v"(o));
+  return o;
+}
+// What one stored output element v adds to the sums of the row epilogue of conv_bf16 (interior fast path) / conv_ws / conv_wsp / conv_wsd:
+// the InstanceNorm sums of v (stat_sums), or the norm-backward sums of gn = v act'(h), h = x * nsc + nsh (nb_sums; ConvArgsB::nb_x).
+__device__ __forceinline__ void stat_sums(float v, float& s1, float& s2) { s1 += v; s2 = fmaf(v, v, s2); }
+__device__ __forceinline__ void nb_sums(float v, float x, float nsc, float nsh, float nb_slope, float& s1, float& s2) {
+  const float h = fmaf(x, nsc, nsh);
+  const float gn = v * (h > 0.f ? 1.f : nb_slope);
+  s1 += gn; s2 = fmaf(gn, h, s2);
+}
+
+// The statistics fold of conv_wsp / conv_wsd: a wave's fp32 partials (per lane, over the voxels the tap-table kernel would have summed)
+// go through that kernel's two shuffles into the float64 sums, and start again from zero.
+template <int NT>
+__device__ __forceinline__ void fold_stats(float (&s1)[NT], float (&s2)[NT], double (&d1)[NT], double (&d2)[NT]) {
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    float u1 = s1[j], u2 = s2[j];
+    u1 += __shfl_xor(u1, 16, 64); u1 += __shfl_xor(u1, 32, 64);
+    u2 += __shfl_xor(u2, 16, 64); u2 += __shfl_xor(u2, 32, 64);
+    d1[j] += (double)u1; d2[j] += (double)u2;
+    s1[j] = 0.f; s2[j] = 0.f;
+  }
+}
 
 
 // The extent choose_cfg tiles (per output-parity class) and the class count of a launch: the output extent, or for the eight-class

@@ -251,15 +251,16 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgsB a) {
         bvj[j] = 0.f;
       }
     }
+    // (this row loop has copies in conv_ws.hip, conv_wsp.hip and conv_wsd.hip that must stay equal to it: v = acc + bias, + residual, store, sums)
     auto epi = [&](auto HR, auto HT, auto HN) {
       constexpr bool HAS_RES = decltype(HR)::value, HAS_STATS = decltype(HT)::value, HAS_NB = decltype(HN)::value;
       unsigned yo[4], ro[4], xo[4];
       float nsc[NT], nsh[NT];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {                      // opaque copies: keep the zero-extension in this block (saddr form)
-        yo[i] = (unsigned)((kq * 4 + i) * os * g.y_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(yo[i]));
-        if (HAS_RES) { ro[i] = (unsigned)((kq * 4 + i) * os * a.r_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(ro[i])); }
-        if (HAS_NB) { xo[i] = (unsigned)((kq * 4 + i) * os * a.nb_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(xo[i])); }
+        yo[i] = epi_lane_off((kq * 4 + i) * os, g.y_ldc, nt0 * 16 + r);
+        if (HAS_RES) ro[i] = epi_lane_off((kq * 4 + i) * os, a.r_ldc, nt0 * 16 + r);
+        if (HAS_NB) xo[i] = epi_lane_off((kq * 4 + i) * os, a.nb_ldc, nt0 * 16 + r);
       }
       if (HAS_NB) {
 #pragma unroll
@@ -296,11 +297,11 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgsB a) {
             float v = acc[m][j][i] + bvj[j];
             if (HAS_RES) v += rv[j][i];
             *reinterpret_cast<float*>(yb + yo[i] + j * 64) = v;
-            if (HAS_NB) {
+            if (HAS_NB) {                                // (nb_sums of conv_args.h written out, and to stay equal to it: through the helper this kernel's code changes)
               const float h = fmaf(xv[j][i], nsc[j], nsh[j]);
               const float gn = v * (h > 0.f ? 1.f : a.nb_slope);
               s1[j] += gn; s2[j] = fmaf(gn, h, s2[j]);
-            } else if (HAS_STATS) { s1[j] += v; s2[j] = fmaf(v, v, s2[j]); }
+            } else if (HAS_STATS) stat_sums(v, s1[j], s2[j]);
           }
       }
     };

@@ -14,24 +14,12 @@
 #include <cstdlib>
 
 typedef __bf16 bf16x8_d __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2_d __attribute__((ext_vector_type(2)));
-typedef float f2_d __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4_d __attribute__((ext_vector_type(4)));
 
 struct S2Args {
   const float* x; int x_ldc; const float* w; const float* bias; float* y; int y_ldc; double* stats;
   int N, Di, Hi, Wi, Do, Ho, Wo, tiles_d, tiles_h, tiles_w, total_tiles, tiles_per_wg;
 };
-
-__device__ __forceinline__ unsigned s2_pk(float a, float b) {
-  const f2_d f = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf2_d));
-}
-__device__ __forceinline__ void s2_split(float a, float b, unsigned& hi, unsigned& lo) {
-  hi = s2_pk(a, b);
-  const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
-  lo = s2_pk(a - ha, b - hb);
-}
 
 #define S2_ROW 34                                        // voxel slots per halo row: 17 even + 17 odd
 #define S2_NVOX (5 * 5 * 33)                             // 825 halo voxels
@@ -76,8 +64,8 @@ __global__ __launch_bounds__(512) void conv_s2c16_kernel(const S2Args a) {
         unsigned h[4], l[4];
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-          if (X3) s2_split(wv[2 * p], wv[2 * p + 1], h[p], l[p]);
-          else { h[p] = s2_pk(wv[2 * p], wv[2 * p + 1]); l[p] = 0u; }
+          if (X3) split_bf16(wv[2 * p], wv[2 * p + 1], h[p], l[p]);
+          else { h[p] = pack_bf16(wv[2 * p], wv[2 * p + 1]); l[p] = 0u; }
         }
         bh[s][j] = make_uint4(h[0], h[1], h[2], h[3]);
         if (X3 && wave == 0) wlo[(s * 2 + j) * 64 + lane] = make_uint4(l[0], l[1], l[2], l[3]);
@@ -185,8 +173,8 @@ __global__ __launch_bounds__(512) void conv_s2c16_kernel(const S2Args a) {
         if (i == S2_SLOTS - 1 && !last_slot) continue;
         const float4 val = pf[i];
         uint2 h, l;
-        if (X3) { s2_split(val.x, val.y, h.x, l.x); s2_split(val.z, val.w, h.y, l.y); }
-        else { h.x = s2_pk(val.x, val.y); h.y = s2_pk(val.z, val.w); l = make_uint2(0u, 0u); }
+        if (X3) { split_bf16(val.x, val.y, h.x, l.x); split_bf16(val.z, val.w, h.y, l.y); }
+        else { h.x = pack_bf16(val.x, val.y); h.y = pack_bf16(val.z, val.w); l = make_uint2(0u, 0u); }
         *reinterpret_cast<uint2*>(xh + lofs[i]) = h;
         if (X3) *reinterpret_cast<uint2*>(xl + lofs[i]) = l;
       }

@@ -15,28 +15,16 @@
 #include <cstdlib>
 
 typedef __bf16 bf16x8_s __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2_s __attribute__((ext_vector_type(2)));
-typedef float f2_s __attribute__((ext_vector_type(2)));
 
 struct StemArgs {
   const float* x; int x_ldc; const float* w; const float* bias; float* y; int y_ldc; const float* out_scale; double* stats;
   int N, D, H, W, tiles_d, tiles_h, tiles_w, total_tiles, tiles_per_wg;
 };
 
-__device__ __forceinline__ unsigned stem_pk(float a, float b) {
-  const f2_s f = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf2_s));
-}
-__device__ __forceinline__ void stem_split(float a, float b, unsigned& hi, unsigned& lo) {
-  hi = stem_pk(a, b);
-  const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
-  lo = stem_pk(a - ha, b - hb);
-}
-
 template <bool X3>
 __global__ __launch_bounds__(256) void stem_conv_kernel(const StemArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned short xh[648 * 4];
-  __shared__ __attribute__((aligned(16))) unsigned short xl[648 * 4];
+  __shared__ __attribute__((aligned(16))) unsigned short xh[HALO_NVOX * 4];
+  __shared__ __attribute__((aligned(16))) unsigned short xl[HALO_NVOX * 4];
   __shared__ float red[4][32];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -62,8 +50,8 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemArgs a) {
     unsigned h[4], l[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      if (X3) stem_split(wv[2 * p], wv[2 * p + 1], h[p], l[p]);
-      else { h[p] = stem_pk(wv[2 * p], wv[2 * p + 1]); l[p] = 0u; }
+      if (X3) split_bf16(wv[2 * p], wv[2 * p + 1], h[p], l[p]);
+      else { h[p] = pack_bf16(wv[2 * p], wv[2 * p + 1]); l[p] = 0u; }
     }
     bh[s] = make_uint4(h[0], h[1], h[2], h[3]); bl[s] = make_uint4(l[0], l[1], l[2], l[3]);
   }
@@ -93,7 +81,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemArgs a) {
     hv[i] = idd | (ih << 4) | (iw << 8);
     hoff[i] = ((idd * a.H + ih) * a.W + iw) * a.x_ldc;
   }
-  const bool last_slot = tid + 512 < 648;
+  const bool last_slot = tid + 512 < HALO_NVOX;
   float4 pf[3];
   auto fetch = [&](int tile) {                            // all loads of a tile issued together; consumed one tile later
     const int n = tile / tiles_sp; int rem = tile - n * tiles_sp;
@@ -125,8 +113,8 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemArgs a) {
       const int v = tid + 256 * i;
       const float4 val = pf[i];
       uint2 h, l;
-      if (X3) { stem_split(val.x, val.y, h.x, l.x); stem_split(val.z, val.w, h.y, l.y); }
-      else { h.x = stem_pk(val.x, val.y); h.y = stem_pk(val.z, val.w); l = make_uint2(0u, 0u); }
+      if (X3) { split_bf16(val.x, val.y, h.x, l.x); split_bf16(val.z, val.w, h.y, l.y); }
+      else { h.x = pack_bf16(val.x, val.y); h.y = pack_bf16(val.z, val.w); l = make_uint2(0u, 0u); }
       *reinterpret_cast<uint2*>(xh + v * 4) = h;
       if (X3) *reinterpret_cast<uint2*>(xl + v * 4) = l;
     }

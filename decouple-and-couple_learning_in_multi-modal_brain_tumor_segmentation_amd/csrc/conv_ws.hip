@@ -22,17 +22,10 @@
 #include <cstdlib>
 #include <type_traits>
 
-#define WS_ID 6
-#define WS_IH 6
-#define WS_IW 18
-#define WS_NVOX (WS_ID * WS_IH * WS_IW)      // 648 halo voxels of a 4x4x16 tile
-#define WS_SLOTS 11                          // staging slots per thread of a group: 648 voxels x 4 channel quads / 256 threads
 #define WS_NT 2                              // output-channel tiles (of 16) per workgroup
 #define WS_A16_PIECES 21                     // IN16: the halo image as LDS-DMA pieces of 64 granules (1296 granules + a zero tail)
 
 struct WsWork { int ngroups, slots, tiles, xcd_perm; };
-
-__host__ __device__ constexpr int ws_tap_bytes(int t) { return (((t / 9) * WS_IH + (t / 3) % 3) * WS_IW + t % 3) * 32; }
 
 // IN16 = true (single-bf16 data-gradient launches whose input gradient exists as a bf16 image [N][D][H][W][Cin], a.x16): nothing is
 // converted and nothing is staged in registers.  The halo of a (tile, chunk) item -- 648 voxels x 32 B = 1296 granules of 16 B, in
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
   char* lds = reinterpret_cast<char*>(lds4);
   constexpr int B_IMG = 14 * NT * 1024;                    // one chunk of one image (hi or lo)
   constexpr int B_ALL = B_IMG * (X3 ? 2 : 1);
-  constexpr int A_IMG = IN16 ? WS_A16_PIECES * 1024 : WS_NVOX * 32;
+  constexpr int A_IMG = IN16 ? WS_A16_PIECES * 1024 : HALO_NVOX * 32;
   constexpr int A_GRP = A_IMG * ((X3 || IN16) ? 2 : 1);  // hi + lo images, or (IN16) the images of two consecutive items
   constexpr int B_RES = B_ALL * (IN16 ? 2 : 1);            // weights in LDS (IN16: two chunks)
   constexpr int NB = (B_ALL + 4095) / 4096;                // uint4 per thread of GROUP 0 for one chunk's weights
@@ -120,8 +113,8 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
 
   // ---- staging slots of this thread: halo voxel v = (tg >> 2) + 64 i, channel quad q = tg & 3
   const int q = tg & 3;
-  const int vox0 = tg >> 2;                                // slot i holds voxel vox0 + 64 i (valid below WS_NVOX: slot 10 only for vox0 < 8)
-  const int iw_0 = vox0 % WS_IW, row_0 = vox0 / WS_IW;        // (row = idd * WS_IH + ih; 64 voxels = 3 rows + 10)
+  const int vox0 = tg >> 2;                                // slot i holds voxel vox0 + 64 i (valid below HALO_NVOX: slot 10 only for vox0 < 8)
+  const int iw_0 = vox0 % HALO_W, row_0 = vox0 / HALO_W;        // (row = idd * HALO_H + ih; 64 voxels = 3 rows + 10)
   const bool plain = a.in_scale == nullptr && a.in_slope == 1.f;
 
   // The prefetch loads are written in inline asm: hipcc waits for every load IT tracks before it reuses a register it believes
@@ -129,14 +122,12 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
   // are invisible to its counters.  Their completion is counted by hand: ONE s_waitcnt vmcnt(0) in front of the convert (pf_wait,
   // naming every destination register).  hipcc's own counted waits stay sufficient beside them: vector-memory operations return
   // in order, so "all but my k youngest" can only wait for MORE than it assumes.
-  f32x4 pf[WS_SLOTS];
+  f32x4 pf[HALO_SLOTS];
   f32x4 pf_sc, pf_sh;                                      // the item's prologue parameters (in_scale / in_shift of its sample and chunk)
   unsigned pf_inb = 0u;
   auto issue_loads = [&](int tile, int chunk) {
-    const int n = tile / tiles_per_n;
-    int bx = tile - n * tiles_per_n;
-    const int tw = bx % g.tiles_w; bx /= g.tiles_w;
-    const int th = bx % g.tiles_h, td = bx / g.tiles_h;
+    int n, td, th, tw;
+    tile_pos(g, tiles_per_n, tile, n, td, th, tw);
     const int id0 = td * 4 - 1, ih0 = th * 4 - 1, iw0 = tw * 16 - 1;
     const float* xb = a.x + (int64_t)n * g.Di * g.Hi * g.Wi * g.x_ldc + chunk * 16;      // wave-uniform (SGPR pair)
     const unsigned ldc4 = (unsigned)g.x_ldc * 4u;
@@ -144,14 +135,9 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
     int iw = iw_0, row = row_0;
     asm volatile("" : "+v"(iw), "+v"(row));                // (opaque: per-slot coordinates are recomputed here, not kept in 30+ hoisted registers)
 #pragma unroll
-    for (int i = 0; i < WS_SLOTS; ++i) {
-      const int idd = (row * 43) >> 8, ih = row - idd * WS_IH;                 // row / 6 for row < 48
-      const int gd = id0 + idd, gh = ih0 + ih, gw = iw0 + iw;
-      const bool ok = (row < WS_ID * WS_IH) & ((unsigned)gd < (unsigned)g.Di) & ((unsigned)gh < (unsigned)g.Hi) & ((unsigned)gw < (unsigned)g.Wi);
-      iw += 10; row += 3;
-      if (iw >= WS_IW) { iw -= WS_IW; ++row; }
-      const unsigned lin = (unsigned)((gd * g.Hi + gh) * g.Wi + gw) * ldc4 + (unsigned)q * 16u;
-      const unsigned boff = ok ? lin : (unsigned)q * 16u;          // (clamped: the load itself is unconditional)
+    for (int i = 0; i < HALO_SLOTS; ++i) {
+      unsigned boff;
+      const bool ok = halo_slot_next(g, id0, ih0, iw0, ldc4, q, iw, row, boff);
       pf[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(xb) + boff);
       pf_inb |= ok ? (1u << i) : 0u;
     }
@@ -167,8 +153,8 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
     int vbase = (tg >> 2) * 32 + q * 8;                    // byte offset of slot 0 in the image; slot i adds an immediate
     asm volatile("" : "+v"(vbase));
 #pragma unroll
-    for (int i = 0; i < WS_SLOTS; ++i) {
-      if (i == WS_SLOTS - 1 && vox0 + 64 * i >= WS_NVOX) continue;
+    for (int i = 0; i < HALO_SLOTS; ++i) {
+      if (i == HALO_SLOTS - 1 && vox0 + HALO_DV * i >= HALO_NVOX) continue;
       float v0 = pf[i][0], v1 = pf[i][1], v2 = pf[i][2], v3 = pf[i][3];
       if (!plain) {
         v0 = act01(fmaf(v0, sc[0], sh[0]), slope); v1 = act01(fmaf(v1, sc[1], sh[1]), slope);
@@ -179,13 +165,13 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
       else { h.x = pack_bf16(v0, v1); h.y = pack_bf16(v2, v3); l = make_uint2(0u, 0u); }
       const bool was = (pf_inb >> i) & 1u;                // zero padding applies AFTER the activation
       h.x = was ? h.x : 0u; h.y = was ? h.y : 0u; l.x = was ? l.x : 0u; l.y = was ? l.y : 0u;
-      *reinterpret_cast<uint2*>(Ah + vbase + i * (64 * 32)) = h;
-      if (X3) *reinterpret_cast<uint2*>(Al + vbase + i * (64 * 32)) = l;
+      *reinterpret_cast<uint2*>(Ah + vbase + i * (HALO_DV * 32)) = h;
+      if (X3) *reinterpret_cast<uint2*>(Al + vbase + i * (HALO_DV * 32)) = l;
     }
   };
 
   // ---- MFMA operands: lane base addresses (bytes); everything else is an immediate
-  const int a_lane = ((wl * WS_IH) * WS_IW + r) * 32 + (kq & 1) * 16;
+  const int a_lane = ((wl * HALO_H) * HALO_W + r) * 32 + (kq & 1) * 16;
   const int b_lane = lane * 16;
 
   f32x4 acc[T][4][NT];
@@ -219,10 +205,8 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
 
   auto epilogue = [&](int tile, auto KK) {
     constexpr int k = decltype(KK)::value;
-    const int n = tile / tiles_per_n;
-    int bx = tile - n * tiles_per_n;
-    const int tw = bx % g.tiles_w; bx /= g.tiles_w;
-    const int th = bx % g.tiles_h, td = bx / g.tiles_h;
+    int n, td, th, tw;
+    tile_pos(g, tiles_per_n, tile, n, td, th, tw);
     if (a.stats && n != stats_n) {
       if (stats_n >= 0) flush_stats_wave();
       stats_n = n;
@@ -230,15 +214,16 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
     float bvj[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) bvj[j] = a.bias ? a.bias[(nt0 + j) * 16 + r] : 0.f;
+    // (this row loop is a copy of conv_bf16.hip's fast-path epilogue, as are conv_wsp.hip's and conv_wsd.hip's, and must stay equal to it)
     auto epi = [&](auto HR, auto HT, auto HN) {
       constexpr bool HAS_RES = decltype(HR)::value, HAS_STATS = decltype(HT)::value, HAS_NB = decltype(HN)::value;
       unsigned yo[4], ro[4], xo[4];
       float nsc[NT], nsh[NT];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {                        // opaque copies: keep the zero-extension in this block (saddr form)
-        yo[i] = (unsigned)((kq * 4 + i) * g.y_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(yo[i]));
-        if (HAS_RES) { ro[i] = (unsigned)((kq * 4 + i) * a.r_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(ro[i])); }
-        if (HAS_NB) { xo[i] = (unsigned)((kq * 4 + i) * a.nb_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(xo[i])); }
+        yo[i] = epi_lane_off(kq * 4 + i, g.y_ldc, nt0 * 16 + r);
+        if (HAS_RES) ro[i] = epi_lane_off(kq * 4 + i, a.r_ldc, nt0 * 16 + r);
+        if (HAS_NB) xo[i] = epi_lane_off(kq * 4 + i, a.nb_ldc, nt0 * 16 + r);
       }
       if (HAS_NB) {
 #pragma unroll
@@ -274,11 +259,8 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
             float v = acc[k][m][j][i] + bvj[j];
             if (HAS_RES) v += rv[j][i];
             *reinterpret_cast<float*>(yb + yo[i] + j * 64) = v;
-            if (HAS_NB) {
-              const float h = fmaf(xv[j][i], nsc[j], nsh[j]);
-              const float gn = v * (h > 0.f ? 1.f : a.nb_slope);
-              s1[j] += gn; s2[j] = fmaf(gn, h, s2[j]);
-            } else if (HAS_STATS) { s1[j] += v; s2[j] = fmaf(v, v, s2[j]); }
+            if (HAS_NB) nb_sums(v, xv[j][i], nsc[j], nsh[j], a.nb_slope, s1[j], s2[j]);
+            else if (HAS_STATS) stat_sums(v, s1[j], s2[j]);
             acc[k][m][j][i] = 0.f;
           }
       }
@@ -307,19 +289,19 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
     uint4 fa[2][4], fb[2][NT], fl[4], fbl[NT];
     auto rd_hi = [&](auto S, auto P) {
       constexpr int s = decltype(S)::value, p = decltype(P)::value;
-      constexpr int c0 = ws_tap_bytes(2 * s), c1 = ws_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);   // padded tap: zero weights, valid address
+      constexpr int c0 = halo_tap_bytes(2 * s), c1 = halo_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);   // padded tap: zero weights, valid address
       const int to = second ? c1 : c0;
 #pragma unroll
-      for (int m = 0; m < 4; ++m) fa[p][m] = *reinterpret_cast<const uint4*>(ah0 + to + m * (WS_IW * 32));
+      for (int m = 0; m < 4; ++m) fa[p][m] = *reinterpret_cast<const uint4*>(ah0 + to + m * (HALO_W * 32));
 #pragma unroll
       for (int j = 0; j < NT; ++j) fb[p][j] = *reinterpret_cast<const uint4*>(bh + (s * NT + j) * 1024);
     };
     auto rd_lo = [&](auto S) {
       constexpr int s = decltype(S)::value;
-      constexpr int c0 = ws_tap_bytes(2 * s), c1 = ws_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);
+      constexpr int c0 = halo_tap_bytes(2 * s), c1 = halo_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);
       const int to = second ? c1 : c0;
 #pragma unroll
-      for (int m = 0; m < 4; ++m) fl[m] = *reinterpret_cast<const uint4*>(al0 + to + m * (WS_IW * 32));
+      for (int m = 0; m < 4; ++m) fl[m] = *reinterpret_cast<const uint4*>(al0 + to + m * (HALO_W * 32));
 #pragma unroll
       for (int j = 0; j < NT; ++j) fbl[j] = *reinterpret_cast<const uint4*>(bl + (s * NT + j) * 1024);
     };
@@ -405,15 +387,13 @@ __global__ __launch_bounds__(IN16 ? 768 : 512) void convws_kernel(const ConvArgs
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         const int gi = (lp0 + 2 * i) * 64 + lane, v = gi >> 1, half = gi & 1;
-        const int idd = v / (WS_IH * WS_IW), rem = v % (WS_IH * WS_IW), ih = rem / WS_IW, iw = rem % WS_IW;
+        const int idd = v / (HALO_H * HALO_W), rem = v % (HALO_H * HALO_W), ih = rem / HALO_W, iw = rem % HALO_W;
         aoff[i] = (unsigned)((idd * g.Hi + ih) * g.Wi + iw) * cin2 + (unsigned)half * 16u;     // (bytes; the host keeps the image below 4 GiB)
-        acrd[i] = (unsigned)idd | ((unsigned)ih << 3) | ((unsigned)iw << 6) | (v < WS_NVOX ? 1u << 11 : 0u);
+        acrd[i] = (unsigned)idd | ((unsigned)ih << 3) | ((unsigned)iw << 6) | (v < HALO_NVOX ? 1u << 11 : 0u);
       }
       auto issue_a = [&](int tile, int chunk, int buf) {
-        const int n = tile / tiles_per_n;
-        int bx = tile - n * tiles_per_n;
-        const int tw = bx % g.tiles_w; bx /= g.tiles_w;
-        const int th = bx % g.tiles_h, td = bx / g.tiles_h;
+        int n, td, th, tw;
+        tile_pos(g, tiles_per_n, tile, n, td, th, tw);
         const int id0 = td * 4 - 1, ih0 = th * 4 - 1, iw0 = tw * 16 - 1;
         // (wave-uniform; it may point in front of the image: only in-volume lanes add their offset to it)
         const char* xb = reinterpret_cast<const char*>(a.x16) + ((((int64_t)n * g.Di + id0) * g.Hi + ih0) * g.Wi + iw0) * (int64_t)cin2 + chunk * 32;
@@ -528,7 +508,7 @@ namespace {
 template <bool X3, bool IN16 = false>
 int launch_ws(const ConvArgsB& a, const WsWork& wk, int grid, hipStream_t st) {
   const size_t lds = (IN16 ? (size_t)2 * 14 * WS_NT * 1024 + (size_t)4 * WS_A16_PIECES * 1024      // two weight chunks, two A images per group
-                           : (size_t)14 * WS_NT * 1024 * (X3 ? 2 : 1) + (size_t)2 * WS_NVOX * 32 * (X3 ? 2 : 1)) +
+                           : (size_t)14 * WS_NT * 1024 * (X3 ? 2 : 1) + (size_t)2 * HALO_NVOX * 32 * (X3 ? 2 : 1)) +
                      8 * WS_NT * 16 * 2 * sizeof(float) + 64;
   if (lds > 160 * 1024) return CWF_E_TOOLARGE;
   CWF_MAX_LDS_ONCE((&convws_kernel<X3, IN16>));

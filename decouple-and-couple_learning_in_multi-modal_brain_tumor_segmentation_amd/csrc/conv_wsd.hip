@@ -25,19 +25,12 @@
 #include <cstdlib>
 #include <type_traits>
 
-#define WSD_ID 6
-#define WSD_IH 6
-#define WSD_IW 18
-#define WSD_NVOX (WSD_ID * WSD_IH * WSD_IW)   // 648 halo voxels of a 4x4x16 tile
-
 // stat_rows: output rows (of 16 voxels) per fp32 partial of the sums -- 1 or 4, as in the tap-table launch this one replaces
 struct WsdWork { int ngroups, stat_rows; };
 
-__host__ __device__ constexpr int wsd_tap_bytes(int t) { return (((t / 9) * WSD_IH + (t / 3) % 3) * WSD_IW + t % 3) * 32; }
-
 template <int NT>
 __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const WsdWork wk) {
-  constexpr int A_IMG = WSD_NVOX * 32;                     // the halo image of one chunk (bf16)
+  constexpr int A_IMG = HALO_NVOX * 32;                    // the halo image of one chunk (bf16)
   constexpr int B_IMG = 14 * NT * 1024;                    // the hi weights of one chunk: [tap pair][N-tile][lane] 16 B
   constexpr int BUF = A_IMG + B_IMG;
   extern __shared__ float4 lds4[];
@@ -55,17 +48,15 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
   const int cgrp = b % wk.ngroups, tile = b / wk.ngroups;
   const int nt0 = cgrp * NT;
   const int tiles_per_n = g.tiles_d * g.tiles_h * g.tiles_w;
-  const int n = tile / tiles_per_n;
-  int bx = tile - n * tiles_per_n;
-  const int tw = bx % g.tiles_w; bx /= g.tiles_w;
-  const int th = bx % g.tiles_h, td = bx / g.tiles_h;
+  int n, td, th, tw;
+  tile_pos(g, tiles_per_n, tile, n, td, th, tw);
 
   if (wave < 4) {
     // =============================================================== MFMA waves
     const int wl = wave;
     const int r = lane & 15, kq = lane >> 4;
     const bool second = (kq >> 1) != 0;
-    const int a_lane = ((wl * WSD_IH) * WSD_IW + r) * 32 + (kq & 1) * 16;
+    const int a_lane = ((wl * HALO_H) * HALO_W + r) * 32 + (kq & 1) * 16;
     const int b_lane = A_IMG + lane * 16;
 
     f32x4 acc[4][NT];
@@ -82,10 +73,10 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
       uint4 fa[3][4], fb[3][NT];
       auto rd = [&](auto S) {
         constexpr int s = decltype(S)::value, p = s % 3;
-        constexpr int c0 = wsd_tap_bytes(2 * s), c1 = wsd_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);   // padded tap: zero weights
+        constexpr int c0 = halo_tap_bytes(2 * s), c1 = halo_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);   // padded tap: zero weights
         const int to = second ? c1 : c0;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) fa[p][m] = *reinterpret_cast<const uint4*>(ab + to + m * (WSD_IW * 32));
+        for (int m = 0; m < 4; ++m) fa[p][m] = *reinterpret_cast<const uint4*>(ab + to + m * (HALO_W * 32));
 #pragma unroll
         for (int j = 0; j < NT; ++j) fb[p][j] = *reinterpret_cast<const uint4*>(bb + (s * NT + j) * 1024);
       };
@@ -120,28 +111,19 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
     double d1[NT], d2[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) { s1[j] = 0.f; s2[j] = 0.f; d1[j] = 0.0; d2[j] = 0.0; }
-    auto fold_stats = [&]() {
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        float u1 = s1[j], u2 = s2[j];
-        u1 += __shfl_xor(u1, 16, 64); u1 += __shfl_xor(u1, 32, 64);
-        u2 += __shfl_xor(u2, 16, 64); u2 += __shfl_xor(u2, 32, 64);
-        d1[j] += (double)u1; d2[j] += (double)u2;
-        s1[j] = 0.f; s2[j] = 0.f;
-      }
-    };
     float bvj[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) bvj[j] = a.bias ? a.bias[(nt0 + j) * 16 + r] : 0.f;
+    // (this row loop is a copy of conv_bf16.hip's fast-path epilogue, as are conv_ws.hip's and conv_wsp.hip's, and must stay equal to it)
     auto epi = [&](auto HR, auto HT, auto HN) {
       constexpr bool HAS_RES = decltype(HR)::value, HAS_STATS = decltype(HT)::value, HAS_NB = decltype(HN)::value;
       unsigned yo[4], ro[4], xo[4];
       float nsc[NT], nsh[NT];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {                        // opaque copies: keep the zero-extension in this block (saddr form)
-        yo[i] = (unsigned)((kq * 4 + i) * g.y_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(yo[i]));
-        if (HAS_RES) { ro[i] = (unsigned)((kq * 4 + i) * a.r_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(ro[i])); }
-        if (HAS_NB) { xo[i] = (unsigned)((kq * 4 + i) * a.nb_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(xo[i])); }
+        yo[i] = epi_lane_off(kq * 4 + i, g.y_ldc, nt0 * 16 + r);
+        if (HAS_RES) ro[i] = epi_lane_off(kq * 4 + i, a.r_ldc, nt0 * 16 + r);
+        if (HAS_NB) xo[i] = epi_lane_off(kq * 4 + i, a.nb_ldc, nt0 * 16 + r);
       }
       if (HAS_NB) {
 #pragma unroll
@@ -181,13 +163,10 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
             float v = acc[m][j][i] + bvj[j];
             if (HAS_RES) v += rv[m][j][i];
             *reinterpret_cast<float*>(yb + yo[i] + j * 64) = v;
-            if (HAS_NB) {
-              const float h = fmaf(xv[m][j][i], nsc[j], nsh[j]);
-              const float gn = v * (h > 0.f ? 1.f : a.nb_slope);
-              s1[j] += gn; s2[j] = fmaf(gn, h, s2[j]);
-            } else if (HAS_STATS) { s1[j] += v; s2[j] = fmaf(v, v, s2[j]); }
+            if (HAS_NB) nb_sums(v, xv[m][j][i], nsc[j], nsh[j], a.nb_slope, s1[j], s2[j]);
+            else if (HAS_STATS) stat_sums(v, s1[j], s2[j]);
           }
-        if (HAS_STATS && (wk.stat_rows == 1 || m == 3)) fold_stats();
+        if (HAS_STATS && (wk.stat_rows == 1 || m == 3)) fold_stats(s1, s2, d1, d2);
       }
     };
     using T_ = std::true_type; using F_ = std::false_type;
@@ -215,8 +194,7 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
     }
   } else {
     // =============================================================== loader waves
-    constexpr int TG = 256, DV = TG / 4;                   // loader threads; voxels between two staging slots of a thread
-    constexpr int SLOTS = (WSD_NVOX + DV - 1) / DV;        // halo slots per thread: 648 voxels x 4 channel quads / 256 threads = 11
+    constexpr int TG = 256, DV = HALO_DV, SLOTS = HALO_SLOTS;      // loader threads and their halo staging slots (conv_args.h)
     constexpr int NBW = (B_IMG / 16 + TG - 1) / TG;        // weight granules per thread: 4 (the last half used) or 7
     const int tg = tid - 256;
     // ---- weights of one chunk, hi granules only: global -> registers (with the halo) -> LDS
@@ -225,7 +203,7 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
     // ---- halo staging: slot i of this thread holds voxel (tg >> 2) + DV i, channel quad q = tg & 3
     const int q = tg & 3;
     const int vox0 = tg >> 2;
-    const int iw_0 = vox0 % WSD_IW, row_0 = vox0 / WSD_IW;
+    const int iw_0 = vox0 % HALO_W, row_0 = vox0 / HALO_W;
     const int id0 = td * 4 - 1, ih0 = th * 4 - 1, iw0 = tw * 16 - 1;
     // A workgroup owns ONE tile: which voxel each staging slot reads, whether it lies in the volume, and which weight granules this
     // thread fetches are the same for every chunk, so they are worked out once; a chunk's loads are scalar base + these offsets.
@@ -236,11 +214,12 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
       int iw = iw_0, row = row_0;
 #pragma unroll
       for (int i = 0; i < SLOTS; ++i) {
-        const int idd = (row * 43) >> 8, ih = row - idd * WSD_IH;            // row / 6 for row < 48
+        // (halo_slot_next of conv_args.h written out, and to stay equal to it: through the helper hipcc orders this block differently)
+        const int idd = (row * 43) >> 8, ih = row - idd * HALO_H;            // row / 6 for row < 48
         const int gd = id0 + idd, gh = ih0 + ih, gw = iw0 + iw;
-        const bool ok = (row < WSD_ID * WSD_IH) & ((unsigned)gd < (unsigned)g.Di) & ((unsigned)gh < (unsigned)g.Hi) & ((unsigned)gw < (unsigned)g.Wi);
-        iw += DV % WSD_IW; row += DV / WSD_IW;             // DV voxels on
-        if (iw >= WSD_IW) { iw -= WSD_IW; ++row; }
+        const bool ok = (row < HALO_D * HALO_H) & ((unsigned)gd < (unsigned)g.Di) & ((unsigned)gh < (unsigned)g.Hi) & ((unsigned)gw < (unsigned)g.Wi);
+        iw += DV % HALO_W; row += DV / HALO_W;             // DV voxels on
+        if (iw >= HALO_W) { iw -= HALO_W; ++row; }
         const unsigned lin = (unsigned)((gd * g.Hi + gh) * g.Wi + gw) * ldc4 + (unsigned)q * 16u;
         xoff[i] = ok ? lin : (unsigned)q * 16u;            // (clamped: the load itself is unconditional)
         pf_inb |= ok ? (1u << i) : 0u;
@@ -271,7 +250,7 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
       char* ah = lds + vbase;
 #pragma unroll
       for (int i = 0; i < SLOTS; ++i) {
-        if (DV * (i + 1) > WSD_NVOX && vox0 + DV * i >= WSD_NVOX) continue;
+        if (DV * (i + 1) > HALO_NVOX && vox0 + DV * i >= HALO_NVOX) continue;
         const bool was = (inb >> i) & 1u;
         uint2 h;
         h.x = was ? pack_bf16(pf[i][0], pf[i][1]) : 0u;
@@ -305,7 +284,7 @@ __global__ __launch_bounds__(512) void convwsd_kernel(const ConvArgsB a, const W
 namespace {
 template <int NT>
 int launch_wsd(const ConvArgsB& a, const WsdWork& wk, int grid, hipStream_t st) {
-  const size_t lds = (size_t)2 * (WSD_NVOX * 32 + 14 * NT * 1024) + 4 * NT * 16 * 2 * sizeof(double);
+  const size_t lds = (size_t)2 * (HALO_NVOX * 32 + 14 * NT * 1024) + 4 * NT * 16 * 2 * sizeof(double);
   CWF_MAX_LDS_ONCE((&convwsd_kernel<NT>));
   hipLaunchKernelGGL((convwsd_kernel<NT>), dim3(grid), dim3(512), lds, st, a, wk);
   CWF_LAUNCH_CHECK();

@@ -31,24 +31,17 @@
 #include <cstdlib>
 #include <type_traits>
 
-#define WSP_ID 6
-#define WSP_IH 6
-#define WSP_IW 18
-#define WSP_NVOX (WSP_ID * WSP_IH * WSP_IW)   // 648 halo voxels of a 4x4x16 tile
-#define WSP_SLOTS 11                          // staging slots per loader thread: 648 voxels x 4 channel quads / 256 threads
 #define WSP_NT 2                              // output-channel tiles (of 16) per workgroup
 #define WSP_NBW 14                            // uint4 of one weight chunk (hi + lo) per loader thread: 57,344 B / 16 / 256
 
 // stat_rows: output rows (of 16 voxels) per fp32 partial of the statistics -- 1 or 4, as in the tap-table launch this one replaces
 struct WspWork { int ngroups, slots, tiles, xcd_perm, stat_rows; };
 
-__host__ __device__ constexpr int wsp_tap_bytes(int t) { return (((t / 9) * WSP_IH + (t / 3) % 3) * WSP_IW + t % 3) * 32; }
-
 template <int T>
 __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const WspWork wk) {
   constexpr int NT = WSP_NT;
   constexpr int B_IMG = 14 * NT * 1024;                    // one chunk of one weight image (hi or lo)
-  constexpr int A_IMG = WSP_NVOX * 32;                     // one halo image (hi or lo)
+  constexpr int A_IMG = HALO_NVOX * 32;                    // one halo image (hi or lo)
   constexpr int A_BUF = 2 * A_IMG;                         // one halo buffer (hi + lo)
   extern __shared__ float4 lds4[];
   char* lds = reinterpret_cast<char*>(lds4);
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
     const int wl = wave;
     const int r = lane & 15, kq = lane >> 4;
     const bool second = (kq >> 1) != 0;
-    const int a_lane = ((wl * WSP_IH) * WSP_IW + r) * 32 + (kq & 1) * 16;
+    const int a_lane = ((wl * HALO_H) * HALO_W + r) * 32 + (kq & 1) * 16;
     const int b_lane = lane * 16;
 
     f32x4 acc[T][4][NT];
@@ -101,16 +94,7 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
 #pragma unroll
     for (int j = 0; j < NT; ++j) { s1[j] = 0.f; s2[j] = 0.f; d1[j] = 0.0; d2[j] = 0.0; }
     int stats_n = -1;
-    auto fold_stats = [&]() {
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        float u1 = s1[j], u2 = s2[j];
-        u1 += __shfl_xor(u1, 16, 64); u1 += __shfl_xor(u1, 32, 64);
-        u2 += __shfl_xor(u2, 16, 64); u2 += __shfl_xor(u2, 32, 64);
-        d1[j] += (double)u1; d2[j] += (double)u2;
-        s1[j] = 0.f; s2[j] = 0.f;
-      }
-    };
+    auto fold = [&]() { fold_stats(s1, s2, d1, d2); };     // (a closure of its own: called directly from epi, hipcc allocates registers differently)
     auto flush_stats = [&]() {
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
@@ -126,10 +110,8 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
     // epilogue of round tile k (the tap-table kernel's interior fast path): v = acc + bias (+ residual), statistics of v
     auto epilogue = [&](int tile, auto KK) {
       constexpr int k = decltype(KK)::value;
-      const int n = tile / tiles_per_n;
-      int bx = tile - n * tiles_per_n;
-      const int tw = bx % g.tiles_w; bx /= g.tiles_w;
-      const int th = bx % g.tiles_h, td = bx / g.tiles_h;
+      int n, td, th, tw;
+      tile_pos(g, tiles_per_n, tile, n, td, th, tw);
       if (a.stats && n != stats_n) {
         if (stats_n >= 0) flush_stats();
         stats_n = n;
@@ -137,13 +119,14 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
       float bvj[NT];
 #pragma unroll
       for (int j = 0; j < NT; ++j) bvj[j] = a.bias ? a.bias[(nt0 + j) * 16 + r] : 0.f;
+      // (this row loop is a copy of conv_bf16.hip's fast-path epilogue, as are conv_ws.hip's and conv_wsd.hip's, and must stay equal to it)
       auto epi = [&](auto HR, auto HT) {
         constexpr bool HAS_RES = decltype(HR)::value, HAS_STATS = decltype(HT)::value;
         unsigned yo[4], ro[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {                      // opaque copies: keep the zero-extension in this block (saddr form)
-          yo[i] = (unsigned)((kq * 4 + i) * g.y_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(yo[i]));
-          if (HAS_RES) { ro[i] = (unsigned)((kq * 4 + i) * a.r_ldc + nt0 * 16 + r) * 4u; asm volatile("" : "+v"(ro[i])); }
+          yo[i] = epi_lane_off(kq * 4 + i, g.y_ldc, nt0 * 16 + r);
+          if (HAS_RES) ro[i] = epi_lane_off(kq * 4 + i, a.r_ldc, nt0 * 16 + r);
         }
         const int od = td * 4 + wl;
         float rv[4][NT][4];
@@ -169,10 +152,10 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
               float v = acc[k][m][j][i] + bvj[j];
               if (HAS_RES) v += rv[m][j][i];
               *reinterpret_cast<float*>(yb + yo[i] + j * 64) = v;
-              if (HAS_STATS) { s1[j] += v; s2[j] = fmaf(v, v, s2[j]); }
+              if (HAS_STATS) stat_sums(v, s1[j], s2[j]);
               acc[k][m][j][i] = 0.f;
             }
-          if (HAS_STATS && (wk.stat_rows == 1 || m == 3)) fold_stats();
+          if (HAS_STATS && (wk.stat_rows == 1 || m == 3)) fold();
         }
       };
       using T_ = std::true_type; using F_ = std::false_type;
@@ -192,19 +175,19 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
       uint4 fa[2][4], fb[2][NT], fl[4], fbl[NT];
       auto rd_hi = [&](auto S, auto P) {
         constexpr int s = decltype(S)::value, p = decltype(P)::value;
-        constexpr int c0 = wsp_tap_bytes(2 * s), c1 = wsp_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);   // padded tap: zero weights
+        constexpr int c0 = halo_tap_bytes(2 * s), c1 = halo_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);   // padded tap: zero weights
         const int to = second ? c1 : c0;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) fa[p][m] = *reinterpret_cast<const uint4*>(ah0 + to + m * (WSP_IW * 32));
+        for (int m = 0; m < 4; ++m) fa[p][m] = *reinterpret_cast<const uint4*>(ah0 + to + m * (HALO_W * 32));
 #pragma unroll
         for (int j = 0; j < NT; ++j) fb[p][j] = *reinterpret_cast<const uint4*>(bh + (s * NT + j) * 1024);
       };
       auto rd_lo = [&](auto S) {
         constexpr int s = decltype(S)::value;
-        constexpr int c0 = wsp_tap_bytes(2 * s), c1 = wsp_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);
+        constexpr int c0 = halo_tap_bytes(2 * s), c1 = halo_tap_bytes(2 * s + 1 < 27 ? 2 * s + 1 : 2 * s);
         const int to = second ? c1 : c0;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) fl[m] = *reinterpret_cast<const uint4*>(al0 + to + m * (WSP_IW * 32));
+        for (int m = 0; m < 4; ++m) fl[m] = *reinterpret_cast<const uint4*>(al0 + to + m * (HALO_W * 32));
 #pragma unroll
         for (int j = 0; j < NT; ++j) fbl[j] = *reinterpret_cast<const uint4*>(bl + (s * NT + j) * 1024);
       };
@@ -302,18 +285,16 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
     // ---- halo staging: slot i of this thread holds voxel (tg >> 2) + 64 i, channel quad q = tg & 3
     const int q = tg & 3;
     const int vox0 = tg >> 2;
-    const int iw_0 = vox0 % WSP_IW, row_0 = vox0 / WSP_IW;
+    const int iw_0 = vox0 % HALO_W, row_0 = vox0 / HALO_W;
     const bool plain = a.in_scale == nullptr && a.in_slope == 1.f;
-    f32x4 pf[WSP_SLOTS];
+    f32x4 pf[HALO_SLOTS];
     f32x4 pf_sc, pf_sh;
     unsigned pf_inb = 0u;
     auto issue = [&](int it) {
       const Item itm = item_of(it);
       const int tile = itm.tile, chunk = itm.chunk;
-      const int n = tile / tiles_per_n;
-      int bx = tile - n * tiles_per_n;
-      const int tw = bx % g.tiles_w; bx /= g.tiles_w;
-      const int th = bx % g.tiles_h, td = bx / g.tiles_h;
+      int n, td, th, tw;
+      tile_pos(g, tiles_per_n, tile, n, td, th, tw);
       const int id0 = td * 4 - 1, ih0 = th * 4 - 1, iw0 = tw * 16 - 1;
       const char* xb = reinterpret_cast<const char*>(a.x + (int64_t)n * g.Di * g.Hi * g.Wi * g.x_ldc + chunk * 16);
       const unsigned ldc4 = (unsigned)g.x_ldc * 4u;
@@ -321,14 +302,9 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
       int iw = iw_0, row = row_0;
       asm volatile("" : "+v"(iw), "+v"(row));              // (opaque: per-slot coordinates are recomputed per item, not kept in hoisted registers)
 #pragma unroll
-      for (int i = 0; i < WSP_SLOTS; ++i) {
-        const int idd = (row * 43) >> 8, ih = row - idd * WSP_IH;            // row / 6 for row < 48
-        const int gd = id0 + idd, gh = ih0 + ih, gw = iw0 + iw;
-        const bool ok = (row < WSP_ID * WSP_IH) & ((unsigned)gd < (unsigned)g.Di) & ((unsigned)gh < (unsigned)g.Hi) & ((unsigned)gw < (unsigned)g.Wi);
-        iw += 10; row += 3;                                // 64 voxels = 3 rows + 10
-        if (iw >= WSP_IW) { iw -= WSP_IW; ++row; }
-        const unsigned lin = (unsigned)((gd * g.Hi + gh) * g.Wi + gw) * ldc4 + (unsigned)q * 16u;
-        const unsigned boff = ok ? lin : (unsigned)q * 16u;                 // (clamped: the load itself is unconditional)
+      for (int i = 0; i < HALO_SLOTS; ++i) {
+        unsigned boff;
+        const bool ok = halo_slot_next(g, id0, ih0, iw0, ldc4, q, iw, row, boff);
         pf[i] = *reinterpret_cast<const f32x4*>(xb + boff);
         inb |= ok ? (1u << i) : 0u;
       }
@@ -349,8 +325,8 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
       asm volatile("" : "+v"(vbase));
       char* ah = A0 + buf * A_BUF + vbase;
 #pragma unroll
-      for (int i = 0; i < WSP_SLOTS; ++i) {
-        if (i == WSP_SLOTS - 1 && vox0 + 64 * i >= WSP_NVOX) continue;
+      for (int i = 0; i < HALO_SLOTS; ++i) {
+        if (i == HALO_SLOTS - 1 && vox0 + HALO_DV * i >= HALO_NVOX) continue;
         float v0 = pf[i][0], v1 = pf[i][1], v2 = pf[i][2], v3 = pf[i][3];
         if (!plain) {
           v0 = act01(fmaf(v0, sc[0], sh[0]), slope); v1 = act01(fmaf(v1, sc[1], sh[1]), slope);
@@ -360,8 +336,8 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
         split_bf16(v0, v1, h.x, l.x); split_bf16(v2, v3, h.y, l.y);
         const bool was = (inb >> i) & 1u;                  // zero padding applies AFTER the activation
         h.x = was ? h.x : 0u; h.y = was ? h.y : 0u; l.x = was ? l.x : 0u; l.y = was ? l.y : 0u;
-        *reinterpret_cast<uint2*>(ah + i * (64 * 32)) = h;
-        *reinterpret_cast<uint2*>(ah + A_IMG + i * (64 * 32)) = l;
+        *reinterpret_cast<uint2*>(ah + i * (HALO_DV * 32)) = h;
+        *reinterpret_cast<uint2*>(ah + A_IMG + i * (HALO_DV * 32)) = l;
       }
     };
 
@@ -396,7 +372,7 @@ __global__ __launch_bounds__(512) void convwsp_kernel(const ConvArgsB a, const W
 namespace {
 template <int T>
 int launch_wsp(const ConvArgsB& a, const WspWork& wk, int grid, hipStream_t st) {
-  const size_t lds = (size_t)2 * 14 * WSP_NT * 1024 + (size_t)2 * 2 * WSP_NVOX * 32;
+  const size_t lds = (size_t)2 * 14 * WSP_NT * 1024 + (size_t)2 * 2 * HALO_NVOX * 32;
   CWF_MAX_LDS_ONCE((&convwsp_kernel<T>));
   hipLaunchKernelGGL((convwsp_kernel<T>), dim3(grid), dim3(512), lds, st, a, wk);
   CWF_LAUNCH_CHECK();

@@ -4,13 +4,6 @@
 // 697-711,737-752 and their autograd.
 #include "common.h"
 
-__device__ __forceinline__ unsigned norm_pk_bf16(float a, float b) {          // one v_cvt_pk_bf16_f32 (round to nearest even)
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const f2 f = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf2));
-}
-
 __global__ void in_finalize_kernel(const double* __restrict__ stats, float* __restrict__ scale, float* __restrict__ shift,
                                    int NC, double invV, float eps) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,7 +85,7 @@ __global__ void norm_act_add_kernel(const float* __restrict__ x, int x_ldc, cons
     o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
   }
   *reinterpret_cast<float4*>(y + gv * y_ldc + cq * 4) = o;
-  if (y16) *reinterpret_cast<uint2*>(y16 + gv * C + cq * 4) = make_uint2(norm_pk_bf16(o.x, o.y), norm_pk_bf16(o.z, o.w));
+  if (y16) *reinterpret_cast<uint2*>(y16 + gv * C + cq * 4) = make_uint2(pack_bf16(o.x, o.y), pack_bf16(o.z, o.w));
 }
 
 // dx = scale*(g - S1/V - xhat*S2/V) (+ dx_add), g = dy*act'(xhat).
@@ -134,8 +127,8 @@ __global__ void in_bwd_apply_kernel(const float* __restrict__ dy, int dy_ldc, co
     o[0] += av.x; o[1] += av.y; o[2] += av.z; o[3] += av.w;
   }
   if (F32) *reinterpret_cast<float4*>(dx + gv * dx_ldc + cq * 4) = make_float4(o[0], o[1], o[2], o[3]);
-  if (DX16) *reinterpret_cast<uint2*>(dx16 + gv * C + cq * 4) = make_uint2(norm_pk_bf16(o[0], o[1]), norm_pk_bf16(o[2], o[3]));
-  if (XA16) *reinterpret_cast<uint2*>(xa16 + gv * C + cq * 4) = make_uint2(norm_pk_bf16(xa[0], xa[1]), norm_pk_bf16(xa[2], xa[3]));
+  if (DX16) *reinterpret_cast<uint2*>(dx16 + gv * C + cq * 4) = make_uint2(pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]));
+  if (XA16) *reinterpret_cast<uint2*>(xa16 + gv * C + cq * 4) = make_uint2(pack_bf16(xa[0], xa[1]), pack_bf16(xa[2], xa[3]));
 }
 
 // y16 = bf16(act(x*scale+shift)) (scale == NULL: bf16(x)): the bf16 operand image of a tensor for the bf16-operand kernels where no
@@ -155,7 +148,7 @@ __global__ void to_bf16_kernel(const float* __restrict__ x, int x_ldc, const flo
     v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y); v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
     v.x = fmaxf(v.x, v.x * slope); v.y = fmaxf(v.y, v.y * slope); v.z = fmaxf(v.z, v.z * slope); v.w = fmaxf(v.w, v.w * slope);
   }
-  *reinterpret_cast<uint2*>(y16 + gv * C + cq * 4) = make_uint2(norm_pk_bf16(v.x, v.y), norm_pk_bf16(v.z, v.w));
+  *reinterpret_cast<uint2*>(y16 + gv * C + cq * 4) = make_uint2(pack_bf16(v.x, v.y), pack_bf16(v.z, v.w));
 }
 
 static int check_cl(const void* p, int ldc, int C) {

@@ -41,11 +41,12 @@ struct WgArgsB {
   const float* dy_scale;
 };
 
+// Deliberately the scalar-cast form (two casts and an OR), not pack_bf16 (common.h): the values are the same, but hipcc emits a
+// different instruction sequence for it, and swapping the two changes the generated code of every weight-gradient kernel below.
 __device__ __forceinline__ unsigned pack_bf16w(float a, float b) {
   const __bf16 x = (__bf16)a, y = (__bf16)b;
   return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
 }
-__device__ __forceinline__ float bf16_roundw(float a) { return (float)(__bf16)a; }
 
 // two transposed reads -> one 8-element K fragment.  p0 / p1: this lane's block-row addresses (bf16 element pointers)
 __device__ __forceinline__ bf16x8 tr_frag(const unsigned short* p0, const unsigned short* p1) {
@@ -241,8 +242,8 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgArgsB a) {
         *reinterpret_cast<uint2*>(xh + vo) = h;
         if (X3) {
           uint2 l;
-          l.x = pack_bf16w(v0 - bf16_roundw(v0), v1 - bf16_roundw(v1));
-          l.y = pack_bf16w(v2 - bf16_roundw(v2), v3 - bf16_roundw(v3));
+          l.x = pack_bf16w(v0 - bf16_round(v0), v1 - bf16_round(v1));
+          l.y = pack_bf16w(v2 - bf16_round(v2), v3 - bf16_round(v3));
           *reinterpret_cast<uint2*>(xl + vo) = l;
         }
       }
@@ -257,8 +258,8 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgArgsB a) {
         *reinterpret_cast<uint2*>(dh + dofs) = h;
         if (X3) {
           uint2 l;
-          l.x = pack_bf16w(val.x - bf16_roundw(val.x), val.y - bf16_roundw(val.y));
-          l.y = pack_bf16w(val.z - bf16_roundw(val.z), val.w - bf16_roundw(val.w));
+          l.x = pack_bf16w(val.x - bf16_round(val.x), val.y - bf16_round(val.y));
+          l.y = pack_bf16w(val.z - bf16_round(val.z), val.w - bf16_round(val.w));
           *reinterpret_cast<uint2*>(dl + dofs) = l;
         }
       }
@@ -293,8 +294,8 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgArgsB a) {
         *reinterpret_cast<uint2*>(xh + vo) = h;
         if (X3) {
           uint2 l;
-          l.x = pack_bf16w(val.x - bf16_roundw(val.x), val.y - bf16_roundw(val.y));
-          l.y = pack_bf16w(val.z - bf16_roundw(val.z), val.w - bf16_roundw(val.w));
+          l.x = pack_bf16w(val.x - bf16_round(val.x), val.y - bf16_round(val.y));
+          l.y = pack_bf16w(val.z - bf16_round(val.z), val.w - bf16_round(val.w));
           *reinterpret_cast<uint2*>(xl + vo) = l;
         }
       }
@@ -326,8 +327,8 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgArgsB a) {
       *reinterpret_cast<uint2*>(dh + dofs) = h;
       if (X3) {
         uint2 l;
-        l.x = pack_bf16w(val.x - bf16_roundw(val.x), val.y - bf16_roundw(val.y));
-        l.y = pack_bf16w(val.z - bf16_roundw(val.z), val.w - bf16_roundw(val.w));
+        l.x = pack_bf16w(val.x - bf16_round(val.x), val.y - bf16_round(val.y));
+        l.y = pack_bf16w(val.z - bf16_round(val.z), val.w - bf16_round(val.w));
         *reinterpret_cast<uint2*>(dl + dofs) = l;
       }
     }
@@ -672,23 +673,11 @@ template <bool X3_, bool DMA> struct W16Lds : WgXImage {
   static_assert(DW == wg_dy_pitch(16) && wg_dy_skew(16) == 0 && DI * 2 % 1024 == 0 && BUFB % 16 == 0 && !(X3 && DMA), "wgrad16 layout");
 };
 
-#define W16_NVOX 648
+#define W16_NVOX HALO_NVOX                              // the x tile of a 4x4x16 dy tile is that tile's halo (conv_args.h)
 #define W16_LW 6                                        // loader waves (MFMA waves: 4) -> 640-thread workgroups
 #define W16_VPP (W16_LW * 16)                           // voxels staged per pass (4 threads per voxel)
 #define W16_XS ((W16_NVOX + W16_VPP - 1) / W16_VPP)     // 7 x staging slots per loader thread
 #define W16_DS ((256 + W16_VPP - 1) / W16_VPP)          // 3 dy staging slots per loader thread
-
-typedef __bf16 bf16x2_w __attribute__((ext_vector_type(2)));
-typedef float f32x2_w __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  const f32x2_w f = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_w));
-}
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
-  hi = pk_bf16(a, b);
-  const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
-  lo = pk_bf16(a - ha, b - hb);
-}
 
 // MFMA waves (0-3) of the wgrad16 pair.  L: the pair's LDS layout (operand form, image offsets, buffer pitch and count);
 // out: the workgroup's slab.
@@ -906,7 +895,7 @@ __global__ __launch_bounds__(256 + 64 * W16_LW) void wgrad16_kernel(const WgArgs
             v2 = fmaxf(fmaf(v2, sc.z, sh.z), fmaf(v2, sc.z, sh.z) * sl); v3 = fmaxf(fmaf(v3, sc.w, sh.w), fmaf(v3, sc.w, sh.w) * sl);
           }
           uint2 h, l;
-          if (X3) { split2(v0, v1, h.x, l.x); split2(v2, v3, h.y, l.y); } else { h.x = pk_bf16(v0, v1); h.y = pk_bf16(v2, v3); }
+          if (X3) { split_bf16(v0, v1, h.x, l.x); split_bf16(v2, v3, h.y, l.y); } else { h.x = pack_bf16(v0, v1); h.y = pack_bf16(v2, v3); }
           if (!ALLIN) {                                  // zero padding applies after the activation
             const bool was = (mx >> i) & 1u;
             h.x = was ? h.x : 0u; h.y = was ? h.y : 0u;
@@ -921,7 +910,7 @@ __global__ __launch_bounds__(256 + 64 * W16_LW) void wgrad16_kernel(const WgArgs
           float4 val = pd[SET][i];
           val.x *= dsc.x; val.y *= dsc.y; val.z *= dsc.z; val.w *= dsc.w;
           uint2 h, l;
-          if (X3) { split2(val.x, val.y, h.x, l.x); split2(val.z, val.w, h.y, l.y); } else { h.x = pk_bf16(val.x, val.y); h.y = pk_bf16(val.z, val.w); }
+          if (X3) { split_bf16(val.x, val.y, h.x, l.x); split_bf16(val.z, val.w, h.y, l.y); } else { h.x = pack_bf16(val.x, val.y); h.y = pack_bf16(val.z, val.w); }
           if (!ALLIN) {
             const bool was = (md >> i) & 1u;
             h.x = was ? h.x : 0u; h.y = was ? h.y : 0u;
@@ -1207,7 +1196,7 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArg
     const int lt = tid - 256;
     constexpr int LT = 64 * WS1_LW;                         // loader threads
     constexpr int VPP = LT / 4;                             // x voxels staged per pass (4 threads per voxel)
-    constexpr int XS = (648 + VPP - 1) / VPP;               // 6 x staging slots per loader thread
+    constexpr int XS = (W16_NVOX + VPP - 1) / VPP;              // 6 x staging slots per loader thread
     constexpr int DSL = CGW / 4;                            // channel quads per dy voxel
     constexpr int DS = 256 * DSL / LT;                      // 2 (16 output channels) or 4 (32) dy staging slots per loader thread
     constexpr int DROWS = LT / DSL / 16;                    // M-tile rows covered by one dy slot over all loader threads
@@ -1230,7 +1219,7 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArg
     // M-tile rows -- per-thread base + wave-uniform increments
     const int vox0 = lt / DSL, cq0 = lt % DSL, m0 = vox0 >> 4, tw = vox0 & 15;
     const int reld0 = (((m0 >> 2) * g.Ho + (m0 & 3)) * g.Wo + tw) * a.dy_ldc + co0 + cq0 * 4;
-    const bool last_x = (lt >> 2) + VPP * (XS - 1) < 648;   // the last slot holds a real voxel for this thread
+    const bool last_x = (lt >> 2) + VPP * (XS - 1) < W16_NVOX; // the last slot holds a real voxel for this thread
     const bool co_ok = co0 + cq0 * 4 < g.Cout;
     // TWO register sets of loads in flight (a tile period is shorter than one memory round trip under load); eight loader waves
     // keep a set at XS + DS = 8..10 float4 per thread
@@ -1278,7 +1267,7 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArg
           val.x = cwf_act(val.x * sc[SET].x + sh[SET].x, a.in_slope); val.y = cwf_act(val.y * sc[SET].y + sh[SET].y, a.in_slope);
           val.z = cwf_act(val.z * sc[SET].z + sh[SET].z, a.in_slope); val.w = cwf_act(val.w * sc[SET].w + sh[SET].w, a.in_slope);
         }
-        uint2 h; h.x = pk_bf16(val.x, val.y); h.y = pk_bf16(val.z, val.w);
+        uint2 h; h.x = pack_bf16(val.x, val.y); h.y = pack_bf16(val.z, val.w);
         const bool was = (okx[SET] >> i) & 1u;              // zero padding applies after the activation
         h.x = was ? h.x : 0u; h.y = was ? h.y : 0u;
         *reinterpret_cast<uint2*>(xh + (xo[i] & 0xffffu)) = h;
@@ -1287,7 +1276,7 @@ __global__ __launch_bounds__(256 + 64 * WS1_LW) void wgrad_s1_kernel(const WgArg
       for (int k = 0; k < DS; ++k) {
         const int m = m0 + k * DROWS;
         const float4 val = vd[SET][k];
-        uint2 h; h.x = pk_bf16(val.x, val.y); h.y = pk_bf16(val.z, val.w);
+        uint2 h; h.x = pack_bf16(val.x, val.y); h.y = pack_bf16(val.z, val.w);
         const bool was = (okd[SET] >> k) & 1u;
         h.x = was ? h.x : 0u; h.y = was ? h.y : 0u;
         *reinterpret_cast<uint2*>(dh + (m * DP + tw) * CGW + ((m + 1) >> 1) * DSK + cq0 * 4) = h;

@@ -14,7 +14,7 @@ Operand forms ("mode"):
 What each kernel path rounds, read from its source (csrc/):
   conv_bf16_kernel (tap table), conv16s_kernel, pw_conv_kernel, convws_kernel, the grouped launch:
       input operand  = act01(fmaf(x, scale, shift), slope) = max(h, h * slope) in fp32, rounded by v_cvt_pk_bf16_f32 (RNE),
-                       split as split_bf16 (conv_args.h); no prologue when scale is NULL and slope == 1 (data gradients);
+                       split as split_bf16 (common.h); no prologue when scale is NULL and slope == 1 (data gradients);
                        zero padding is applied AFTER the activation (stage_tile_bf16).
       weights        = hi / lo of the fp32 parameter (gather_split_bf16_kernel, the same split rule).
       epilogue       = (acc + bias + residual) * out_scale (the fast epilogue never has residual and out_scale together);
@@ -100,7 +100,7 @@ def hi(v):
 
 
 def lo(v):
-    """bf16_rne(v - hi(v)) (split_bf16, conv_args.h); v - hi(v) is exact in fp32"""
+    """bf16_rne(v - hi(v)) (split_bf16, common.h); v - hi(v) is exact in fp32"""
     v = v.float()
     return (v - v.to(torch.bfloat16).float()).to(torch.bfloat16).double()
 

@@ -1,21 +1,21 @@
 """Float64 reference and per-element bounds for the InstanceNorm kernel family (a helper module for the tests, not a test file).
 
 Kernels (csrc/norm.hip; csrc/optim.hip for the channel sum) and the rule each function here restates:
-  in_reduce_kernel<0> / <1> (norm.hip:27-72), launched by launch_reduce (norm.hip:175-186):
-      vpb = max(256, ceil(N V / 2048)) capped at V voxels per workgroup (norm.hip:180), nvs = 256 / (C / 4) voxel sub-lanes per
-      workgroup (norm.hip:33); a thread adds its L = ceil(vpb / nvs) voxels into fp32 registers (norm.hip:46-59), the nvs sub-lanes
-      are folded in f64 (norm.hip:65-69) and the workgroups meet in f64 atomics (norm.hip:70).  `launch_L` restates that rule:
-      whoever changes norm.hip:180 or :33 changes launch_L too.
+  in_reduce_kernel<0> / <1> (norm.hip:20-65), launched by launch_reduce (norm.hip:168-179):
+      vpb = max(256, ceil(N V / 2048)) capped at V voxels per workgroup (norm.hip:173), nvs = 256 / (C / 4) voxel sub-lanes per
+      workgroup (norm.hip:26); a thread adds its L = ceil(vpb / nvs) voxels into fp32 registers (norm.hip:39-52), the nvs sub-lanes
+      are folded in f64 (norm.hip:58-62) and the workgroups meet in f64 atomics (norm.hip:63).  `launch_L` restates that rule:
+      whoever changes norm.hip:173 or :26 changes launch_L too.
       <0>: S1 = sum x, S2 = sum x^2.   <1>: h = x*scale + shift (plain multiply-add, the compiler may contract it),
       g = dy * act'(h), act'(h) = h > 0 ? 1 : slope (common.h:29), S1 = sum g, S2 = sum g*h.
-  in_finalize_kernel (norm.hip:14-24): mean = S1/V, var = max(S2/V - mean^2, 0), rstd = 1/sqrt(var + (double)eps) with eps an fp32
+  in_finalize_kernel (norm.hip:7-17): mean = S1/V, var = max(S2/V - mean^2, 0), rstd = 1/sqrt(var + (double)eps) with eps an fp32
       argument, scale = fp32(rstd), shift = fp32(-mean*rstd); all in f64 before the two casts.
-  norm_act_add_kernel (norm.hip:75-96): y = act(x*scale + shift) + residual, act(h) = h > 0 ? h : h*slope (common.h:28);
-      y16 = bf16_rne(y) (norm_pk_bf16, norm.hip:7-12).
-  in_bwd_apply_kernel<F32, DX16, XA16> (norm.hip:103-139): h = fmaf(x, scale, shift), g = dy*act'(h), invV = 1.0f/(float)V,
+  norm_act_add_kernel (norm.hip:68-89): y = act(x*scale + shift) + residual, act(h) = h > 0 ? h : h*slope (common.h:28);
+      y16 = bf16_rne(y) (pack_bf16, common.h:34-37).
+  in_bwd_apply_kernel<F32, DX16, XA16> (norm.hip:96-132): h = fmaf(x, scale, shift), g = dy*act'(h), invV = 1.0f/(float)V,
       m1 = fp32(S1 * (double)invV), m2 = fp32(S2 * (double)invV), dx = scale*(g - m1 - h*m2) (+ dx_add), dx16 = bf16_rne(dx),
       xa16 = bf16_rne(fmaxf(h, h*slope)).
-  to_bf16_kernel (norm.hip:143-159): bf16_rne(fmaxf(h, h*slope)), h = fmaf(x, scale, shift).
+  to_bf16_kernel (norm.hip:136-152): bf16_rne(fmaxf(h, h*slope)), h = fmaf(x, scale, shift).
   stats_channel_sum_kernel (optim.hip:156-162): out[c] = fp32(sum_n S1[n, c]) in f64.
 slope reaches every kernel as an fp32 argument: the reference uses fp32(slope), not the Python double.
 
@@ -84,7 +84,7 @@ def bc(s):
 
 # ------------------------------------------------------------------ the reduce
 def launch_L(N, V, C):
-    """(L, vpb, nvs) of launch_reduce + in_reduce_kernel for the public arguments (norm.hip:180 and :33, see the module docstring)"""
+    """(L, vpb, nvs) of launch_reduce + in_reduce_kernel for the public arguments (norm.hip:173 and :26, see the module docstring)"""
     vpb = max(256, -(-(V * N) // 2048))
     vpb = min(vpb, V)
     nvs = 256 // (C // 4)
